@@ -7,8 +7,11 @@ A "step" = one pass of the hot path over one resident synthetic batch:
   frozen backbone forward (bf16 MFMA) -> last-layer key map -> bilinear 37->68 -> DBA student + EMA teacher ->
   Gram orthogonality loss -> APM (2 discriminator calls) -> both BCE losses -> closed-form backward ->
   [all-reduce] -> AdamW + EMA.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel class, timed live
-with HIP events on the launch stream over the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and prints the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) of that timed region.  `--full` adds everything else
+to the line: `roofline` (dominant kernel class, timed live with HIP events on the launch stream in a serial pass), the sustained run, the
+discriminator phase, the backbone-backward mode, `cpu_baseline` (the CPU oracle on a bounded sample, with the full-size parity table) and
+the other backbone configurations.  `--dump-outputs DIR` writes what the last timed step computed (DIR/<name>.npy).
 """
 import argparse
 import ctypes as C
@@ -27,6 +30,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 MFMA_BF16_PEAK_TFLOPS = 2500.0      # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md chip table
+DUMP_SAMPLE = 1 << 20               # --dump-outputs: elements kept of a larger output (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
 MFMA_F32_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
 
@@ -55,7 +60,7 @@ def parse():
                          "split3: the split-operand pass (SplitViTEngine: two / three bf16 terms per f32 operand, f32 residual stream) -- split2 is the fastest configuration "
                          "that meets the bar on trained-like weights, split3 is f32-equivalent (what the feature-cache pass runs); all reported beside the headline")
     ap.add_argument("--sustain-s", type=float, default=40.0,
-                    help="after the timed region, keep running the same step for this many seconds in 10-s windows (images/s and held shader clock per window); 0 = skip. "
+                    help="--full: after the timed region, keep running the same step for this many seconds in 10-s windows (images/s and held shader clock per window); 0 = skip. "
                          "The reference's hot loop is 126 steps x 25 epochs (engine/runner/loop_UCOD_DPL.py:94-146), the timed region 0.2-0.4 s")
     ap.add_argument("--pmc-traffic", action="store_true",
                     help="measure roofline.traffic in THIS run: two child `rocprofv3 --pmc` passes (FETCH_SIZE, WRITE_SIZE) of the serial step before the timed run "
@@ -65,7 +70,18 @@ def parse():
                     "(fallback centre box on every image); use with --arch dinov2_vitl14 --batch 16")
     ap.add_argument("--lora-resid", default="auto", choices=["auto", "f32", "f16"], help="residual stream of the backbone-backward engine (auto: fp16 with bf16 operands)")
     ap.add_argument("--lora-steps", type=int, default=6, help="steps of the separate backbone-backward (LoRA) measurement; 0 = skip")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the serial pass with per-kernel HIP events (kernels, roofline), the sustained run, the discriminator phase, "
+                         "the backbone-backward (LoRA) mode, the CPU baseline with the full-size parity table and the other backbone configurations in their own "
+                         "processes (Look-Twice leg: the exclusive per-kernel pass, the first backbone pass alone and its CPU baseline).  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its LAST step as DIR/<name>.npy (float32; an output of more than "
+                         f"{DUMP_SAMPLE} elements as a fixed, seeded sample of them): the same arguments give the same inputs in every run")
+    a = ap.parse_args()
+    if a.pmc_traffic and not a.full:
+        ap.error("--pmc-traffic feeds the roofline of a --full run: add --full")
+    return a
 
 
 def make_cfg(fs=68, dim=768):
@@ -137,7 +153,7 @@ def pmc_traffic_pass(a):
         return None
     tmp = tempfile.mkdtemp(prefix="ucod_pmc_", dir="/tmp")
     args = ["--half", a.half, "--resid", a.resid, "--ln-fold", a.ln_fold, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--lora-steps", "-1", "--no-pipeline",
-            "--streams", "1", "--sustain-s", "0", "--batch", str(a.batch), "--arch", a.arch, "--image", str(a.image), "--attn-variant", str(a.attn_variant)]
+            "--streams", "1", "--sustain-s", "0", "--batch", str(a.batch), "--arch", a.arch, "--image", str(a.image), "--attn-variant", str(a.attn_variant), "--full"]
     env = dict(os.environ, TMPDIR="/tmp", UCOD_BENCH_CHILD="1")
     for counter, sub in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
         cmd = ["timeout", "900", "rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", os.path.join(tmp, sub), "--", sys.executable, os.path.abspath(__file__)] + args
@@ -160,7 +176,7 @@ def main():
         a.resid = "auto"                                          # the engine's own choice (round 6: fp16 stream + fold for fp16 operands where the fold exists)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(a)
-    measured_traffic = pmc_traffic_pass(a) if (a.pmc_traffic and a.gpus == 1 and not os.environ.get("UCOD_BENCH_CHILD")) else None   # (before this process touches the GPU)
+    measured_traffic = pmc_traffic_pass(a) if (a.full and a.pmc_traffic and a.gpus == 1 and not os.environ.get("UCOD_BENCH_CHILD")) else None   # (before this process touches the GPU)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -209,9 +225,11 @@ def main():
     gh = a.image // P
     kpad = bb.engine.Kpad
     key = torch.empty(B, D, gh, gh, dtype=torch.float32, device=dev)
+    last = {}                                                 # the key map the latest step's decoder step consumed (--dump-outputs)
 
     def serial_step():
         bb.engine.forward(images, out=key)
+        last["key"] = key
         return loop._process_batch((pl, key))
 
     # Default schedule: the frozen backbone pass of step k+1 runs on side HIP streams (two image-parallel halves) while the
@@ -223,6 +241,7 @@ def main():
     def pipelined_step():
         k = pipe.next_features()
         pipe.submit(images)
+        last["key"] = k
         return loop._process_batch((pl, k))
 
     def barrier():
@@ -249,6 +268,19 @@ def main():
     dt = time.perf_counter() - t0
     final_loss = float(loss.item())
     bb.engine.check_overflow(wait=True)                       # a saturated fp16 residual stream is an error of the run, never a green line
+    if world > 1:
+        tdt = torch.tensor([dt], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
+        dt = tdt.item()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, train_step_outputs(loop, last["key"]))
+    if not a.full:
+        if rank == 0:
+            _flush_c_stdio()
+            print(json.dumps(plain_line(a, dict(world=world, B=B, image=a.image, resid16=resid16, ln_fold=ln_fold, dt=dt, final_loss=final_loss,
+                                                host_enqueue=host_enqueue, host_threads=host_threads, pinned_cores=pinned_cores, ranks_seen=ranks_seen,
+                                                collectives=collectives_label(world, parallel)))), flush=True)
+        return
 
     # Roofline pass: the SAME step in serial order on one stream, so that every launch has the chip to itself and the
     # HIP-event duration of a kernel class is its exclusive duration (with overlapping streams it is not).
@@ -283,10 +315,6 @@ def main():
         for i in range(ncls):
             tot[i] += t_[i]
             cnt[i] += c_[i]
-    if world > 1:
-        tdt = torch.tensor([dt], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
-        dt = tdt.item()
     # Sustained run: the same step, back to back, for --sustain-s seconds in ~10-s windows; with several ranks they agree every 16 steps on the
     # slowest rank's clock, so that all leave a window after the same number of steps (the all-reduces stay matched); the host keeps at most 16 steps in flight.
     sustained = None
@@ -387,7 +415,7 @@ def main():
                 continue
             cmd = [sys.executable, os.path.abspath(__file__), "--half", half, "--steps", str(a.steps), "--warmup", str(a.warmup),
                    "--batch", str(B), "--arch", a.arch, "--image", str(a.image), "--streams", str(a.streams), "--attn-variant", str(a.attn_variant),
-                   "--lora-steps", "-1", "--no-cpu-baseline", "--ln-fold", a.ln_fold, "--sustain-s", "0"] + (["--resid", resid] if resid else []) + \
+                   "--lora-steps", "-1", "--no-cpu-baseline", "--ln-fold", a.ln_fold, "--sustain-s", "0", "--full"] + (["--resid", resid] if resid else []) + \
                   (["--no-pipeline"] if a.no_pipeline else []) + (["--full-last-layer"] if a.full_last_layer and resid else [])
             if half in ("split2", "split3"):                     # 3x / 6x the matrix work: a quarter of the steps keeps the whole run inside minutes
                 cmd[cmd.index("--steps") + 1], cmd[cmd.index("--warmup") + 1] = str(max(3, a.steps // 4)), str(max(1, a.warmup // 4))
@@ -411,11 +439,47 @@ def main():
     meas = dict(world=world, B=B, D=D, heads=heads, L=L, P=P, kpad=kpad, image=a.image, resid16=resid16, ln_fold=ln_fold, dt=dt, dt_serial=dt_serial, dt_serial_plain=dt_serial_plain,
                 classes=classes, final_loss=final_loss, dis_phase=dis_phase, lora_mode=lora_mode, host_enqueue=host_enqueue, host_threads=host_threads,
                 pinned_cores=pinned_cores, ranks_seen=ranks_seen, cpu=cpu, others=others, traffic=traffic, traffic_source=traffic_source, sustained=sustained,
-                collectives=("RCCL world-size-1 process group FORCED (UCOD_FORCE_DIST=1): broadcast at construction and every all-reduce of the step are issued on the "
-                             "group's stream" if (world == 1 and parallel.collectives_on()) else ("one asynchronous RCCL all-reduce of the flat gradient arena per step" if world > 1
-                                                                                                     else "none (world size 1: short-circuit)")))
+                collectives=collectives_label(world, parallel))
     _flush_c_stdio()
     print(json.dumps(build_line(a, meas)), flush=True)
+
+
+def collectives_label(world, parallel):
+    if world == 1 and parallel.collectives_on():
+        return "RCCL world-size-1 process group FORCED (UCOD_FORCE_DIST=1): broadcast at construction and every all-reduce of the step are issued on the group's stream"
+    return "one asynchronous RCCL all-reduce of the flat gradient arena per step" if world > 1 else "none (world size 1: short-circuit)"
+
+
+def train_step_outputs(loop, key):
+    """What a caller of the timed training step holds after its last step: the loss it returned, the step's other results (TrainLoop.last: mask logits of
+    student and teacher, APM weights and merged pseudo label, discriminator probabilities and loss, orthogonality term), the key map the step consumed
+    and the decoder / EMA-teacher parameters the optimiser left behind."""
+    out = {name: t for name, t in loop.last.items()}
+    out["key"] = key
+    out["decoder_params"] = loop.runner.arena.p
+    out["decoder_ema_params"] = loop.runner.arena.ema
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 stays float64).  An output of more than DUMP_SAMPLE elements is written as
+    <name>_sample.npy: its flattened elements at DUMP_SAMPLE sorted positions drawn by a generator of fixed seed (the same positions in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = torch.as_tensor(t).detach()
+        t = t.cpu().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx], name + "_sample"
+        arr = t.numpy()
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def _flush_c_stdio():
@@ -492,6 +556,38 @@ def sustain(a, lib, dev, world, B, sec_per_step, barrier):
 
 
 _STEP = {}
+
+
+METRIC = "training images/sec at 3x518x518, DINOv2-B (frozen backbone fwd + DBA/APM/discriminator train step)"
+
+
+def _dtype(a):
+    return {"split2": "bf16x2", "split3": "bf16x3"}.get(a.half, a.half)
+
+
+def _config(a, m):
+    """The line's `config` block (both forms of the line)."""
+    world, B, resid16, split = m["world"], m["B"], m["resid16"], a.half in ("split2", "split3")
+    arith = {"bf16": "bf16 MFMA", "f16": "fp16 MFMA", "split2": "two-term split bf16 MFMA (16 significand bits per operand), f32 residual stream",
+             "split3": "three-term split bf16 MFMA (f32-equivalent), f32 residual stream"}[a.half]
+    return {"workload": f"{which_config(a.arch, m['image'], B, a.attn_variant)}: {a.arch} @{m['image']}x{m['image']}, batch {B}/GPU, full APM+DBA+discriminator step, "
+                        f"decoder path f32 (1x1 conv as a three-way bf16 split on the matrix pipe: f32-equivalent), backbone {arith}", "global_batch": B * world, "parallelism": f"dp{world}",
+            "backbone_last_layer": "full (as reference)" if a.full_last_layer else "key-minimal (identical key output; 279.6 of 303.1 GFLOP/img)",
+            "random_init_weights": True, "residual_stream": "fp16" if resid16 else "f32", "ln_fold": m["ln_fold"],
+            "schedule": "serial, one stream" if a.no_pipeline else
+                        f"backbone pass of step k+1 on {1 if split else a.streams} side stream(s) overlapped with the decoder step of step k"}
+
+
+def plain_line(a, m):
+    """The line of a run without --full: the headline of the timed region alone.  `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step`
+    are what build_line reports for the same timed region (value = the timed region: a plain run has no sustained run)."""
+    world, B, dt = m["world"], m["B"], m["dt"]
+    ips = world * B * a.steps / dt
+    return {"metric": METRIC, "value": round(ips, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": _dtype(a), "data": "synthetic",
+            "value_is": "the timed region", "value_timed_region": round(ips, 2), "full": False, "final_loss": round(m["final_loss"], 6),
+            "host_enqueue_ms_per_step": round(m["host_enqueue"] / a.steps * 1e3, 3), "host_threads": m["host_threads"], "host_cores_pinned": m["pinned_cores"],
+            "ranks_seen": m["ranks_seen"], "collectives": m.get("collectives"), "config": _config(a, m)}
 
 
 def build_line(a, m):
@@ -628,13 +724,11 @@ def build_line(a, m):
     value, value_is = round(ips, 2), "the timed region"
     if sustained and sustained["value_sustained"] < 0.97 * ips:      # a burst figure the chip does not hold is not the headline
         value, value_is = sustained["value_sustained"], "the LAST ~10-s window of the sustained run (below 0.97 of the timed region's figure, reported as value_timed_region)"
-    arith = {"bf16": "bf16 MFMA", "f16": "fp16 MFMA", "split2": "two-term split bf16 MFMA (16 significand bits per operand), f32 residual stream",
-             "split3": "three-term split bf16 MFMA (f32-equivalent), f32 residual stream"}[a.half]
     out = {
-        "metric": "training images/sec at 3x518x518, DINOv2-B (frozen backbone fwd + DBA/APM/discriminator train step)",
+        "metric": METRIC,
         "value": value, "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": {"split2": "bf16x2", "split3": "bf16x3"}.get(a.half, a.half), "data": "synthetic",
+        "dtype": _dtype(a), "data": "synthetic", "full": True,
         "value_is": value_is, "value_timed_region": round(ips, 2), "value_sustained": (sustained or {}).get("value_sustained"), "sustained": sustained,
         "logit_max_abs": logit_max_abs, "bar": BAR, "bar_met": (None if logit_max_abs is None else bool(logit_max_abs <= BAR)),
         "logit_max_abs_trained_like_weights": own_tl.get("logit_max_abs"),
@@ -651,12 +745,7 @@ def build_line(a, m):
         "configurations": configurations, "bar_meeting_config": bar_meeting, "bar_meeting_config_on_trained_like_weights": bar_meeting_tl, "f16_vs_bf16_per_kernel": f16_vs_bf16,
         "host_enqueue_ms_per_step": round(m["host_enqueue"] / a.steps * 1e3, 3), "host_threads": m["host_threads"], "host_cores_pinned": m["pinned_cores"],
         "ranks_seen": m["ranks_seen"], "collectives": m.get("collectives"),
-        "config": {"workload": f"{which_config(a.arch, m['image'], B, a.attn_variant)}: {a.arch} @{m['image']}x{m['image']}, batch {B}/GPU, full APM+DBA+discriminator step, "
-                               f"decoder path f32 (1x1 conv as a three-way bf16 split on the matrix pipe: f32-equivalent), backbone {arith}", "global_batch": B * world, "parallelism": f"dp{world}",
-                   "backbone_last_layer": "full (as reference)" if a.full_last_layer else "key-minimal (identical key output; 279.6 of 303.1 GFLOP/img)",
-                   "random_init_weights": True, "residual_stream": "fp16" if resid16 else "f32", "ln_fold": ln_fold,
-                   "schedule": "serial, one stream" if a.no_pipeline else
-                               f"backbone pass of step k+1 on {1 if split else a.streams} side stream(s) overlapped with the decoder step of step k"},
+        "config": _config(a, m),
         "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels, "final_loss": round(m["final_loss"], 6),
         "backbone_backward_mode": m["lora_mode"], "discriminator_phase": m["dis_phase"],
     }
@@ -706,7 +795,7 @@ def look_twice_leg(a, dev, lib, world, rank, host_threads, pinned_cores):
         _, key = bb(images)
         preds_up, boxes = loop.validate_batch(key, paths)
         stats.step(labels, ops.bilinear_resize(preds_up.reshape(B, 1, S, S).contiguous(), S, S).reshape(B, S, S) > 0.5)
-        return preds_up, boxes
+        return preds_up, boxes, key
 
     def barrier():
         if world > 1:
@@ -714,20 +803,38 @@ def look_twice_leg(a, dev, lib, world, rank, host_threads, pinned_cores):
         torch.cuda.synchronize()
 
     for _ in range(max(1, a.warmup)):
-        preds_up, boxes = step()
+        preds_up, boxes, _ = step()
     if not all(b == [list(LT.DEFAULT_BOX)] for b in boxes):
         raise SystemExit("bench.py --look-twice: not every image took the fallback box")
     stats.reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        preds_up, boxes, key = step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         tdt = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
         dt = tdt.item()
+    if a.dump_outputs and rank == 0:                          # the final masks, their boxes, the first-stage key maps of the last step
+        dump_outputs(a.dump_outputs, {"preds_up": preds_up, "key": key,
+                                      "boxes": torch.tensor([float(v) for b in boxes for bx in b for v in bx], dtype=torch.float64).reshape(-1, 4),
+                                      "boxes_per_image": torch.tensor([float(len(b)) for b in boxes])})
+    head = {"metric": "validation images/sec at 3x518x518 with the Look-Twice second pass (two backbone passes per image + decode + box logic + paste + COD measures)",
+            "value": round(world * B * a.steps / dt, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.half, "data": "synthetic",
+            "full": a.full,
+            "config": {"workload": f"BASELINE configs[3] (validation side, SURVEY 8d C4): {a.arch} @{S}x{S}, batch {B}/GPU, Look-Twice second pass with the fallback centre box "
+                                   f"{LT.DEFAULT_BOX} (2x zoom) on every image", "global_batch": B * world, "parallelism": f"dp{world}", "random_init_weights": True,
+                       "residual_stream": "fp16" if bb.engine.resid16 else "f32", "ln_fold": bool(bb.engine.ln_fold),
+                       "batched": "all crops of all images in one crop launch pair, one backbone pass, one decoder pass, one paste call (loop_look_twice.py::look_twice_batch)",
+                       "schedule": f"serial steps; each backbone pass as {a.streams} image-parallel sub-batches on independent HIP streams"}}
+    if not a.full:
+        if rank == 0:
+            _flush_c_stdio()
+            print(json.dumps(dict(head, host_threads=host_threads, host_cores_pinned=pinned_cores)), flush=True)
+        return
     # exclusive per-class durations: the same step with each backbone pass on ONE stream (no two launches overlap)
     libs = [lib] + ([bb.engine.lib] if bb.engine.lib is not lib else [])
     bb.engine.streams = 1
@@ -820,14 +927,7 @@ def look_twice_leg(a, dev, lib, world, rank, host_threads, pinned_cores):
     roofline = {"kernel": dom, "bound": "mfma", "achieved": kernels[dom]["tflops"], "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": round(kernels[dom]["tflops"] / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None, "avg_launch_us": kernels[dom]["avg_us"],
                 "measured_in": "the same step with every backbone pass on ONE stream and HIP events around every launch (exclusive launch durations)"}
-    out = {"metric": "validation images/sec at 3x518x518 with the Look-Twice second pass (two backbone passes per image + decode + box logic + paste + COD measures)",
-           "value": round(world * B * a.steps / dt, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-           "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.half, "data": "synthetic",
-           "config": {"workload": f"BASELINE configs[3] (validation side, SURVEY 8d C4): {a.arch} @{S}x{S}, batch {B}/GPU, Look-Twice second pass with the fallback centre box "
-                                  f"{LT.DEFAULT_BOX} (2x zoom) on every image", "global_batch": B * world, "parallelism": f"dp{world}", "random_init_weights": True,
-                      "residual_stream": "fp16" if bb.engine.resid16 else "f32", "ln_fold": bool(bb.engine.ln_fold),
-                      "batched": "all crops of all images in one crop launch pair, one backbone pass, one decoder pass, one paste call (loop_look_twice.py::look_twice_batch)",
-                      "schedule": f"serial steps; each backbone pass as {a.streams} image-parallel sub-batches on independent HIP streams"},
+    out = {**head,
            "first_backbone_pass_ms": round(dt_first / a.steps * 1e3, 3),
            "second_pass_and_tail_ms": round((dt - dt_first) / a.steps * 1e3, 3),
            "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels,

@@ -138,3 +138,47 @@ def test_the_committed_line_of_the_round_keeps_the_contract():
             continue
         check_line(d, n_gpus=d["n_gpus"])
         assert abs(d.get("value_timed_region", d["value"]) - d["config"]["global_batch"] / d["ms_per_step"] * 1e3) / d["value"] < 2e-3
+
+
+def test_the_plain_line_reports_the_headline_as_the_full_line_does():
+    """A run without --full prints the headline of the timed region alone; its metric, value, unit, higher_is_better, dtype, ms_per_step (and config) are the
+    full line's for the same timed region."""
+    for kw in (dict(), dict(half="bf16"), dict(half="split2", steps=5)):
+        a, m = args(**kw), canned()
+        full, plain = bench.build_line(a, m), json.loads(json.dumps(bench.plain_line(a, m)))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "scaling", "vs_baseline", "data", "config",
+                  "final_loss", "value_is"):
+            assert plain[k] == full[k], k
+        assert plain["full"] is False and full["full"] is True and "roofline" not in plain and "cpu_baseline" not in plain
+        assert abs(plain["ms_per_step"] - 9.364e-3 * 20 / a.steps * 1e3) < 1e-3
+
+
+def test_options_of_the_plain_and_the_full_run(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out", "--pmc-traffic"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out" and a.pmc_traffic is True
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--pmc-traffic"])
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_a_large_one(tmp_path):
+    import numpy as np
+    import torch
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float32).reshape(3, -1)
+    arrays = {"loss": torch.tensor(0.5), "mask": torch.rand(4, 9) > 0.5, "params": torch.randn(100, dtype=torch.float64), "key": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["key_sample.npy", "loss.npy", "mask.npy", "params.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "mask.npy").shape == (4, 9) and np.load(tmp_path / "a" / "params.npy").dtype == np.float64
+    s = np.load(tmp_path / "a" / "key_sample.npy")
+    assert s.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(s) >= 0) and s.max() > 2 * bench.DUMP_SAMPLE    # sorted positions drawn over the whole array
+    assert np.array_equal(s, big.reshape(-1).numpy()[s.astype(np.int64)])

@@ -300,7 +300,7 @@ def test_bench_launches_two_ranks_itself(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--lora-steps", "1",
-                        "--no-cpu-baseline", "--image", "224", "--arch", "dino_vits8", "--sustain-s", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--image", "224", "--arch", "dino_vits8", "--sustain-s", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -309,6 +309,62 @@ def test_bench_launches_two_ranks_itself(tmp_path):
     assert d["backbone_backward_mode"]["value"] > 0 and d["discriminator_phase"]["value"] > 0
     assert sorted(r[0] for r in d["ranks_seen"]) == [0, 1] and d["host_cores_pinned"] >= 1
     assert d["sustained"]["windows"][0]["steps"] % 16 == 0 and d["sustained"]["value_sustained"] > 0 and d["sustained"]["held_clock_mhz"] > 100     # the sustained leg with two ranks
+
+
+def test_bench_plain_run_with_two_ranks(tmp_path):
+    """`python bench.py --gpus 2` without --full: both ranks time the same steps, agree on the slowest rank's time and leave; rank 0 alone dumps its
+    last step and prints ONE headline line for the global batch (here both ranks share the one GPU over gloo)."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, UCOD_SINGLE_DEVICE="1", UCOD_DIST_BACKEND="gloo")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--image", "224",
+                        "--arch", "dino_vits8", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 2 and d["config"]["global_batch"] == 4 and d["config"]["parallelism"] == "dp2" and d["steps"] == 3
+    assert abs(d["value"] - 4 / d["ms_per_step"] * 1e3) / d["value"] < 2e-3 and sorted(r_[0] for r_ in d["ranks_seen"]) == [0, 1]
+    assert "roofline" not in d and "sustained" not in d and "backbone_backward_mode" not in d
+    names = set(os.listdir(out))
+    assert {"loss.npy", "fg.npy", "decoder_params.npy", "key.npy"} <= names        # rank 0's arrays of its last step
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, the outputs of the last step under --dump-outputs, one JSON line with the
+    headline alone.  Two runs with the same arguments get the same inputs: their dumps hold the same arrays, and the backbone's key map (a function of the
+    inputs and the weights alone; the decoder step sums its gradients with float atomics) agrees between them."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2", "--image", "224",
+                            "--arch", "dino_vits8", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines += [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    for d in lines:
+        assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["unit"] == "images/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 2 / d["ms_per_step"] * 1e3) / d["value"] < 2e-3 and d["dtype"] == "f16"
+        assert "roofline" not in d and "sustained" not in d and "cpu_baseline" not in d and "configurations" not in d
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "fg.npy", "teacher.npy", "merged.npy", "decoder_params.npy", "decoder_ema_params.npy"} <= set(names)
+    assert "key.npy" in names or "key_sample.npy" in names
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and np.all(np.isfinite(x)), n
+        total += x.nbytes
+        if n.startswith("key"):
+            assert np.allclose(x, y, rtol=1e-5, atol=1e-6), n
+    assert total <= 64 << 20 and abs(float(np.load(tmp_path / "a" / "loss.npy").reshape(-1)[0]) - lines[0]["final_loss"]) < 1e-5
 
 
 def test_eight_ranks_on_one_gpu_first_contact(tmp_path):
@@ -323,7 +379,7 @@ def test_eight_ranks_on_one_gpu_first_contact(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2", "--lora-steps", "1",
-                        "--no-cpu-baseline", "--image", "224", "--arch", "dino_vits8", "--sustain-s", "2"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--no-cpu-baseline", "--image", "224", "--arch", "dino_vits8", "--sustain-s", "2", "--full"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

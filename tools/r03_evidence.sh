@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r03_lora -- python3 $R/tools/lora_bench.py 32 2 1 > $O/prof_r03_lora_bench.txt 2> $O/prof_r03_lora.err
 find $O/prof_r03_lora -name '*kernel_trace.csv' -delete
 # bf16 vs fp16 operands: duration and clock per kernel class
-PM="--steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1 --resid f16"
+PM="--full --steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1 --resid f16"
 for h in bf16 f16; do
   rocprofv3 --pmc SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/clock_r03_$h -- python3 $R/bench.py --half $h $PM > /dev/null 2> $O/clock_r03_$h.err
 done

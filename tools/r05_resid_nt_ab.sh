@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 for i in 1 2 3; do
   for v in 0 1; do
-    UCOD_RESID16_NT=$v timeout 300 python bench.py --no-cpu-baseline --lora-steps 0 --steps 40 2>/dev/null | python -c "
+    UCOD_RESID16_NT=$v timeout 300 python bench.py --full --no-cpu-baseline --lora-steps 0 --steps 40 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

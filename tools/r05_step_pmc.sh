@@ -8,14 +8,14 @@ for half in f16 bf16; do
   i=0
   for set in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS"; do
     i=$((i+1))
-    timeout 900 rocprofv3 --pmc $set --output-format csv -d $O/step_pmc_${half}_$i -- python3 $R/bench.py --half $half --steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1 --sustain-s 0 > /dev/null 2> $O/step_pmc_${half}_$i.err
+    timeout 900 rocprofv3 --pmc $set --output-format csv -d $O/step_pmc_${half}_$i -- python3 $R/bench.py --full --half $half --steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1 --sustain-s 0 > /dev/null 2> $O/step_pmc_${half}_$i.err
   done
 done
 cd $R; python3 - <<'PY' > gpurun_out/r05_step_pmc.txt
 import csv, glob, collections
 CLS = [("qkv", ("mixed_kernel<0,", "mixed_kernel<11,")), ("fc1", ("mixed_kernel<1,", "mixed_kernel<12,")), ("out-proj + fc2", ("mixed_kernel<9,", "mixed_kernel<13,")),
        ("attention", ("attn_fwd_v5_kernel",)), ("layernorm", ("layernorm_h16_strip",)), ("row statistics", ("row_stats_h16",)), ("key hook", ("big_kernel<4,",)), ("patch embedding", ("big_kernel<10,", "big_kernel<14,"))]
-print("# rocprofv3 --pmc over `bench.py --half <h> --steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1` (tools/r05_step_pmc.sh), means per launch")
+print("# rocprofv3 --pmc over `bench.py --full --half <h> --steps 2 --warmup 1 --no-cpu-baseline --lora-steps -1 --no-pipeline --streams 1` (tools/r05_step_pmc.sh), means per launch")
 print("# MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (SQ_BUSY_CYCLES / 32 * 1024): fraction of the chip's matrix-pipe cycles in use while the kernel runs")
 for half in ("f16", "bf16"):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))

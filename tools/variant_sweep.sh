@@ -1,6 +1,6 @@
 #!/bin/bash
 run() {
-  python bench.py "$@" --lora-steps 0 --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > /tmp/b.json
+  python bench.py --full "$@" --lora-steps 0 --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | tail -1 > /tmp/b.json
   python - "$*" <<'PY'
 import json, sys
 try:
