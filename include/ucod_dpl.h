@@ -105,6 +105,15 @@ enum {
   UCOD_EPI_BIAS_GELU_SPLIT2 = 15,    /* split-operand pass, two terms (csrc/split.hip): out bf16 [M, 3 N] = the A-side split operand (segments hi | hi | lo) of
                                         gelu_erf(C + bias[n]) -- fc1 + GELU + the split in ONE launch instead of UCOD_EPI_BIAS_F32 + ucod_split_rows(op 1): no f32
                                         round trip of the MLP hidden.  bf16 library; N % 8 == 0 */
+  UCOD_EPI_BIAS_SWIGLU_BF16 = 16,    /* DINOv2 ViT-g MLP (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315: hidden = silu(x1) * x2, (x1, x2) = weights_in(x).chunk(2)).
+                                        B = weights_in with its rows INTERLEAVED in blocks of 4 (ucod_dpl_amd/swiglu.py): GEMM column 8k+e (e < 4) holds x1 unit 4k+e,
+                                        column 8k+4+e holds x2 unit 4k+e.  out 16-bit [M, N/2] = silu(C+bias)[8k+e] * (C+bias)[8k+4+e] at column 4k+e; every
+                                        pair sits inside one 8-column chunk of a tile, so nothing crosses a tile.  silu(x) = x / (1 + exp(-x)); -0 for x -> -inf,
+                                        NaN propagates.  N % 8 == 0.  Both libraries */
+  UCOD_EPI_LNFOLD_SWIGLU_BF16 = 17,  /* ucod_gemm_lnfold only.  The LayerNorm fold of UCOD_EPI_LNFOLD_GELU_BF16 (norm2 -> weights_in, modeling_dinov2.py:365-373,300-315),
+                                        then the SwiGLU of UCOD_EPI_BIAS_SWIGLU_BF16: out fp16 [M, N/2] */
+  UCOD_EPI_BIAS_SWIGLU_SPLIT2 = 18,  /* split-operand pass, two terms: out bf16 [M, 3 N/2] = the A-side split operand (segments hi | hi | lo, N/2 apart) of the SwiGLU
+                                        of UCOD_EPI_BIAS_SWIGLU_BF16 (modeling_dinov2.py:300-315), SiLU to f32 accuracy.  bf16 library; N % 8 == 0 */
   UCOD_EPI_QKV_FP8 = 8               /* QKV projection of the fp8 attention path (BASELINE configs[4]): out = e4m3 bytes
                                         [3 (q|k|v)][Bimg*heads][Npad][64], Npad = tokens rounded up to 64, value = clamp((C + bias[n]) *
                                         scale[n], +-448); N = 3*heads*64, M = Bimg*tokens_per_image; large-tile kernel only */
@@ -345,7 +354,9 @@ int ucod_vit_forward(const ucod_vit_desc* d, const void* const* table_host, cons
  * bf16 [M, P K], P = ucod_split_products(terms) = 3 / 6, segment p of an A-side operand (role 0) holding term {0,0,1,1,0,2}[p] and of a B-side operand (role 1)
  * term {0,1,0,1,2,0}[p].  libucod_dpl.so only (bf16 MFMA); the fp16 build returns UCOD_EINVAL.  csrc/split.hip. */
 int ucod_split_products(int terms);
-/* in f32 [M, K] with row pitch ld_in floats -> out bf16 [M, P K].  op 0: the values; 1: exact-erf GELU of them (modeling_dinov2.py:289); 2: times alpha.  K % 8 == 0 */
+/* in f32 [M, K] with row pitch ld_in floats -> out bf16 [M, P K].  op 0: the values; 1: exact-erf GELU of them (modeling_dinov2.py:289); 2: times alpha;
+ * 3: SwiGLU (modeling_dinov2.py:300-315) of rows 2 K wide interleaved as for UCOD_EPI_BIAS_SWIGLU_BF16 (input column 8k+e is x1, 8k+4+e is x2 of output
+ * column 4k+e; ld_in >= 2 K).  K % 8 == 0 */
 int ucod_split_rows(const float* in, long ld_in, void* out_bf16, int M, int K, int terms, int role, int op, float alpha, void* stream);
 /* nn.LayerNorm (two-pass f32) of f32 rows, written as the split operand of the next GEMM: out bf16 [rows, P D].  D % 128 == 0, D <= 1536 */
 int ucod_layernorm_split(const float* x, const float* gamma, const float* beta, void* out_bf16, int rows, int D, float eps, int terms, int role, void* stream);
@@ -370,6 +381,23 @@ size_t ucod_vit_split_workspace_bytes(const ucod_vit_desc* d, int terms);
 size_t ucod_vit_split_stream_offset(const ucod_vit_desc* d, int terms);
 int ucod_vit_forward_split(const ucod_vit_desc* d, int terms, const void* const* table_host, const float* img, float* key_out, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* MLP kind of a backbone pass (the _mlp entry points; ucod_vit_desc is unchanged and the entry points without the suffix are the UCOD_MLP_GELU case):
+ * UCOD_MLP_GELU: fc1 -> exact-erf GELU -> fc2 (Dinov2MLP, modeling_dinov2.py:281-297).
+ * UCOD_MLP_SWIGLU: weights_in -> SwiGLU -> weights_out (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315; DINOv2 ViT-g/14).  Table entries +9 / +10 hold weights_in
+ * [2F, D] (split form [2F, P D]) and its bias [2F] with the rows interleaved in blocks of 4 (UCOD_EPI_BIAS_SWIGLU_BF16), +15 (ln_fold) its column sums [2F],
+ * +11 weights_out [D, F] (split [D, P F]); d->F is the hidden width after padding (zero rows / columns: exact, silu(0) 0 = 0), F % 128 == 0.  The fc1 launch
+ * writes the hidden [M, F] straight from its epilogue (UCOD_EPI_BIAS_SWIGLU_BF16 / UCOD_EPI_LNFOLD_SWIGLU_BF16 / UCOD_EPI_BIAS_SWIGLU_SPLIT2); the three-term
+ * split pass goes through UCOD_EPI_BIAS_F32 [M, 2F] and ucod_split_rows op 3. */
+enum { UCOD_MLP_GELU = 0, UCOD_MLP_SWIGLU = 1 };
+size_t ucod_vit_workspace_bytes_mlp(const ucod_vit_desc* d, int mlp);
+int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void* const* table_host, const float* img, float* key_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t ucod_vit_last_ln1_offset_mlp(const ucod_vit_desc* d, int mlp);
+size_t ucod_vit_split_workspace_bytes_mlp(const ucod_vit_desc* d, int terms, int mlp);
+size_t ucod_vit_split_stream_offset_mlp(const ucod_vit_desc* d, int terms, int mlp);
+int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int mlp, const void* const* table_host, const float* img, float* key_out,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backbone-backward mode, whole passes (row B9; operand formats in ucod_dpl_amd/csrc/vit_train.hip).
  * T = the table of ucod_vit_forward; TT = per-layer training table (HOST array of DEVICE pointers), layer l at

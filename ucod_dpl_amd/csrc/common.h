@@ -155,6 +155,12 @@ __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + ex
 // the DBA gate's sigmoid (128 per pixel in heads_fwd / dba_bwd, which were bound by expf + the IEEE division of sigmoid_acc): v_exp_f32 of
 // the scaled argument and v_rcp_f32 -- 1 ulp each plus |x| * 6e-8 from the argument's rounding, against the 5e-5 the step is pinned to
 __device__ __forceinline__ float sigmoid_gate(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
+// silu(x) = x / (1 + exp(-x)) at f32 accuracy (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315; the split-operand SwiGLU epilogue and ucod_split_rows op 3): expf
+// (range-reduced, ~1 ulp) and an IEEE division, ~2e-7 relative.  -0 where exp(-x) overflows (x -> -inf, where x / inf would be NaN at x = -inf); NaN stays NaN
+__device__ __forceinline__ float silu_f32(float x) {
+  const float e = expf(-x);
+  return e == __builtin_inff() ? -0.f : x / (1.0f + e);
+}
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

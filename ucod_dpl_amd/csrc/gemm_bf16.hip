@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs a) {
 
   // C/D map of v_mfma_f32_16x16x32: col = lane&15, row = (lane>>4)*4 + reg.  Drain through LDS (see drain_rows).
   __syncthreads();
-  if ((a.N & 3) == 0) {
+  if (kSwiglu<EPI> || (a.N & 3) == 0) {                            // (SwiGLU: launch() guarantees N % 8 == 0; no element-wise form exists)
     constexpr int WT = T / 2;                                      // the wave's square sub-tile
     char* wbase = smem + wave * (WT * WT * 4);
 #pragma unroll
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs a) {
           *reinterpret_cast<float*>(wbase + (i * 16 + (lane >> 4) * 4 + rg) * (WT * 4) + (j * 16 + (lane & 15)) * 4) = acc[i][j][rg];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     drain_rows<EPI, WT, WT>(a, wbase, m0 + wr * WT, n0 + wc * WT, lane);
-  } else {
+  } else if constexpr (!kSwiglu<EPI>) {
 #pragma unroll
     for (int i = 0; i < FI; ++i)
 #pragma unroll
@@ -374,14 +374,15 @@ static void apply_order_tuning(GemmArgs& a) {
 template <int EPI>
 static int launch(GemmArgs a, int variant, hipStream_t s) {
   constexpr bool kTrainEpi = (EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16);
-  constexpr bool kPatchEpi = !kTrainEpi && !kFold<EPI>;        // (leftover-as-patches: not for the LayerNorm-folded epilogues, whose row scalars live in the tile's LDS table)
+  // (leftover-as-patches: not for the LayerNorm-folded epilogues, whose row scalars live in the tile's LDS table, nor for SwiGLU, whose patches would drain one column at a time)
+  constexpr bool kPatchEpi = !kTrainEpi && !kFold<EPI> && !kSwiglu<EPI>;
   const bool auto_small = variant == 0;                       // only `auto` may pick the 64 x 64 tile by itself
   if (variant == 0) {
     variant = 2;
     // large tiles when either dimension is long enough to fill the chip with 256-row tiles (the key hook has M = channels = 768
     // but N = all tokens: 3 x 172 tiles)
     const bool big_enough = a.M >= 2048 || (a.M >= 512 && (long)a.M * a.N >= (1L << 24));
-    if (big_enough && a.K >= 128 && (a.N & 3) == 0 && (!(kBiasLike<EPI> || kGeluLike<EPI>) || (a.N & 7) == 0)) {
+    if (big_enough && a.K >= 128 && (a.N & 3) == 0 && (!(kBiasLike<EPI> || kGeluLike<EPI> || kSwiglu<EPI>) || (a.N & 7) == 0)) {
       // two 32-MFMA barrier intervals per K-tile (variants 9/10) beat four 16-MFMA ones (5/6) by 2-4 % and the persistent
       // form (7/8) by 1-5 % on every backbone shape (tools/gemm_bench.py); the width with the shorter modelled makespan
       variant = (!kFold<EPI> && big_plan(a.M, a.N, a.K, 192, kPatchEpi).cost < big_plan(a.M, a.N, a.K, 256, kPatchEpi).cost) ? 10 : 9;
@@ -395,7 +396,10 @@ static int launch(GemmArgs a, int variant, hipStream_t s) {
     if (kTrainEpi && ((a.N & 7) != 0 || a.K < 128)) return UCOD_EINVAL;
     if (variant < 3) variant = (big_plan(a.M, a.N, a.K, 192, kPatchEpi).cost < big_plan(a.M, a.N, a.K, 256, kPatchEpi).cost) ? 10 : 9;
   }
-  constexpr bool kBf16Out = (kBiasLike<EPI> || kGeluLike<EPI> || kTrainEpi);
+  constexpr bool kBf16Out = (kBiasLike<EPI> || kGeluLike<EPI> || kSwiglu<EPI> || kTrainEpi);
+  if constexpr (kSwiglu<EPI>) {                                   // pairs live in 8-column chunks: every path must drain row-major (see kSwiglu)
+    if ((a.N & 7) != 0) return UCOD_EINVAL;
+  }
   if ((variant >= 3 && variant <= 8) || variant == 11 || variant > 14 || variant < 0) return UCOD_EINVAL;   // 3-8: laboratory variants (variants/gemm_bf16_lab.hip)
   if constexpr (kFold<EPI>) {                                    // the LayerNorm-folded epilogues exist for 64-column waves only: the 256-wide forms
     if (variant == 10) variant = 9;
@@ -584,7 +588,8 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.nslot = nslot;
   a.eps = eps;
   a.ovf = (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS ||
-           epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16)
+           epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 ||
+           epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16)
               ? resid16_overflow_counter() : nullptr;           // (the folded consumers count rows outside the fold's range into the same word: fold_finish)
   a.stamps = nullptr;
 #ifdef UCOD_GEMM_STAMPS
@@ -608,7 +613,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.group_m = 8;
   a.col_fast = 0;
   hipStream_t s = (hipStream_t)stream;
-  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : PROF_GEMM_EPI7)), s);
+  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : PROF_GEMM_EPI7)), s);
   switch (epilogue) {
     case UCOD_EPI_BIAS_BF16:                                   // NULL bias (plain product) only in the large-tile kernels
       if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
@@ -619,6 +624,15 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
     case UCOD_EPI_BIAS_GELU_SPLIT2:                                 // rows of 3 N bf16: the drains address them with 31-bit byte offsets
       if (!bias || (N & 7) != 0 || (long)M * 3 * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_GELU_SPLIT2>(a, variant, s);
+    case UCOD_EPI_BIAS_SWIGLU_BF16:                                 // out [M, N / 2] (modeling_dinov2.py:300-315)
+      if (!bias || (N & 7) != 0) return UCOD_EINVAL;
+      return launch<UCOD_EPI_BIAS_SWIGLU_BF16>(a, variant, s);
+    case UCOD_EPI_BIAS_SWIGLU_SPLIT2:                               // rows of 3 N / 2 bf16, 31-bit byte offsets (and the drains' sentinels above them)
+#ifdef UCOD_HALF_F16
+      return UCOD_EINVAL;                                           // (split operands are bf16: the bf16 library only)
+#endif
+      if (!bias || (N & 7) != 0 || (long)M * 3 * N >= (1L << 31) - 16) return UCOD_EINVAL;
+      return launch<UCOD_EPI_BIAS_SWIGLU_SPLIT2>(a, variant, s);
     case UCOD_EPI_BIAS_SCALE_RESID_F32:
       if (!bias || !scale || !resid) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_SCALE_RESID_F32>(a, variant, s);
@@ -634,9 +648,11 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
     case UCOD_EPI_QKV_FP8: return launch_qkv_fp8(a, s);
     case UCOD_EPI_LNFOLD_BIAS_BF16:
     case UCOD_EPI_LNFOLD_GELU_BF16:
+    case UCOD_EPI_LNFOLD_SWIGLU_BF16:
       if (!bias || (!stats && !part_in) || !colsum || (N & 7) != 0) return UCOD_EINVAL;
       if (part_in && (nslot < 2 || nslot > 2 * FOLD_MAX_SLOT_PAIRS || (nslot & 1) || K < 128 || (long)M * nslot * 8 >= (1L << 32) - 16)) return UCOD_EINVAL;
       if (!part_in && (long)M * 8 >= (1L << 32) - 16) return UCOD_EINVAL;
+      if (epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16) return launch<UCOD_EPI_LNFOLD_SWIGLU_BF16>(a, variant, s);
       return epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? launch<UCOD_EPI_LNFOLD_BIAS_BF16>(a, variant, s) : launch<UCOD_EPI_LNFOLD_GELU_BF16>(a, variant, s);
     case UCOD_EPI_BIAS_SCALE_RESID_H16_STATS:
       if (!bias || !scale || !resid || !a.ovf || !part_out) return UCOD_EINVAL;
@@ -662,7 +678,7 @@ extern "C" int ucod_gemm_bf16(int epilogue, const void* A, const void* B, void* 
                               const float* scale, const float* resid, const float* pos, int tokens_per_image, int variant,
                               void* stream) {
   if (epilogue == UCOD_EPI_GELU_BWD_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SAVE_BF16) return UCOD_EINVAL;   // need ucod_gemm_bf16_train
-  if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
+  if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
   if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;   // need ucod_gemm_bf16_stats
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream, nullptr, nullptr);
 }
@@ -682,8 +698,8 @@ extern "C" int ucod_gemm_lnfold(int epilogue, const void* x_f16, const void* w_f
 #ifndef UCOD_HALF_F16
   return UCOD_EINVAL;
 #else
-  if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && epilogue != UCOD_EPI_LNFOLD_GELU_BF16) return UCOD_EINVAL;
-  if (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 && scale) return UCOD_EINVAL;
+  if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && epilogue != UCOD_EPI_LNFOLD_GELU_BF16 && epilogue != UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;
+  if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && scale) return UCOD_EINVAL;
   return gemm_entry(epilogue, x_f16, w_folded, out, M, N, K, bias_folded, scale, nullptr, nullptr, 0, variant, stream, nullptr, nullptr, stats, colsum,
                     row_partials, nullptr, nslot, eps);
 #endif

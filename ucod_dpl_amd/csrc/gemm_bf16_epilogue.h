@@ -25,7 +25,7 @@ constexpr int BM = 128, BN = 128, BK = 64;
 // norm2 -> mlp).  The epilogue applies the two per-row scalars s = rstd, u = -mean * rstd:  out = s * acc + (u * c[n] + b'[n]).  The 16-bit
 // rounding of the LayerNorm output and the LayerNorm launch itself disappear.
 template <int EPI>
-constexpr bool kFold = (EPI == UCOD_EPI_LNFOLD_BIAS_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16);
+constexpr bool kFold = (EPI == UCOD_EPI_LNFOLD_BIAS_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16);
 // The residual-stream producers that also leave row statistics for the next LayerNorm-folded consumer (round 5, step B): every wave adds up
 // the 64 values of a row it has just rounded to fp16 -- sum and sum of squared deviations from the slot's own mean, of the ROUNDED values (what the consumer's MFMA will read) -- and
 // stores the pair into slot (column / 64) of the row: no statistics launch, no atomics, one fixed order of additions.
@@ -44,6 +44,28 @@ template <int EPI>
 constexpr int kOutPitchMul = kSplit2Out<EPI> ? 3 : 1;              // output row pitch in units of N elements
 template <int EPI>
 constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || kSplit2Out<EPI>);   // erf-GELU, 16-bit output
+// DINOv2 ViT-g's SwiGLU MLP (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) on weights_in rows interleaved in blocks of 4 (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_BF16):
+// the 8 consecutive columns 8k .. 8k+7 that a lane of a row-major drain holds are x1 | x2 of the hidden units 4k .. 4k+3, so the product needs no other lane and no
+// other tile.  Output column = GEMM column / 2: one 8-byte store per lane and segment.  Only the row-major drains implement it (epilogue_store8_bf16 and the
+// large-tile drain); launch() keeps these epilogues away from the element-wise ones (N % 8 == 0, no leftover-as-patches tiles).
+template <int EPI>
+constexpr bool kSwiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2);
+template <int EPI>
+constexpr bool kSwigluSplit2 = (EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2);   // output = the A-side split operand hi | hi | lo, segments N / 2 apart in a row of 3 N / 2
+// silu(x) = x / (1 + exp(-x)).  16-bit outputs: v_exp_f32 and v_rcp_f32.  exp(-x) overflows for x below ~-88 and s = 0, where x * s would be NaN at x = -inf:
+// -0 there (the limit).  A NaN stays a NaN (s is NaN, not 0).
+__device__ __forceinline__ float silu_fast(float x) {
+  const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+  return s == 0.f ? -0.f : x * s;
+}
+// (the split epilogue feeds an f32-equivalent pass: silu_f32 of common.h, shared with ucod_split_rows op 3)
+template <int EPI>
+__device__ __forceinline__ f32x4 swiglu4(f32x4 x1, f32x4 x2) {
+  f32x4 h;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) h[e] = (kSwigluSplit2<EPI> ? silu_f32(x1[e]) : silu_fast(x1[e])) * x2[e];
+  return h;
+}
 // (hi, lo) bf16 terms of two f32 values, packed pairwise: v = hi + lo up to 2^-17 |v|
 __device__ __forceinline__ u32x2 split2_pack(float a, float b) {   // -> (hi pair, lo pair)
   const unsigned hi = pack_bf16x2(a, b);
@@ -161,6 +183,8 @@ __device__ __forceinline__ f32x2 gelu_grad2(f32x2 x) {
 
 template <int EPI>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, float v) {
+  // one column alone has no SwiGLU partner: the call sites exclude these epilogues at compile time (row-major drains only)
+  static_assert(!kSwiglu<EPI>, "SwiGLU epilogues drain 8-column chunks only");
   if (m >= a.M || n >= a.N) return;
   if constexpr (kFold<EPI>) {
     const float s = a.stats[2 * (size_t)m], u = a.stats[2 * (size_t)m + 1];
@@ -211,6 +235,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
 // Four consecutive columns n..n+3 of output row m (n % 4 == 0, N % 4 == 0): vector loads / stores.
 template <int EPI>
 __device__ __forceinline__ void epilogue_store4(const GemmArgs& a, int m, int n, f32x4 v) {
+  static_assert(!kSwiglu<EPI>, "SwiGLU epilogues drain 8-column chunks only");
   if (m >= a.M || n >= a.N) return;
   if constexpr (EPI == UCOD_EPI_KEY_NCHW_F32) {
     // four consecutive tokens of one image, none of them CLS: one dword-aligned 16-byte store into [B, C, tok-1] (row starts are
@@ -316,6 +341,20 @@ __device__ __forceinline__ void epilogue_store8_bf16(const GemmArgs& a, int m, i
       o0 = o0 * *reinterpret_cast<const f32x4*>(a.scale + n);
       o1 = o1 * *reinterpret_cast<const f32x4*>(a.scale + n + 4);
     }
+  } else if constexpr (kSwiglu<EPI>) {                            // o0 = x1, o1 = x2 of hidden units n / 2 .. n / 2 + 3
+    const f32x4 h = swiglu4<EPI>(o0, o1);
+    const int nh = a.N >> 1;
+    bf16_raw* row = reinterpret_cast<bf16_raw*>(a.out) + (size_t)m * (kSwigluSplit2<EPI> ? 3 : 1) * nh + (n >> 1);
+    if constexpr (kSwigluSplit2<EPI>) {
+      const u32x2 t0 = split2_pack(h[0], h[1]), t1 = split2_pack(h[2], h[3]);
+      const u32x2 hi = {t0[0], t1[0]}, lo = {t0[1], t1[1]};
+      *reinterpret_cast<u32x2*>(row) = hi;
+      *reinterpret_cast<u32x2*>(row + nh) = hi;
+      *reinterpret_cast<u32x2*>(row + 2 * (size_t)nh) = lo;
+    } else {
+      *reinterpret_cast<u32x2*>(row) = (u32x2){pack_h2(h[0], h[1]), pack_h2(h[2], h[3])};
+    }
+    return;
   } else {
     const f32x2 g0 = gelu_erf2((f32x2){o0[0], o0[1]}), g1 = gelu_erf2((f32x2){o0[2], o0[3]});
     const f32x2 g2 = gelu_erf2((f32x2){o1[0], o1[1]}), g3 = gelu_erf2((f32x2){o1[2], o1[3]});
@@ -347,10 +386,12 @@ __device__ __forceinline__ void epilogue_store8_bf16(const GemmArgs& a, int m, i
 // by 16-byte-per-lane instructions (4-8x fewer, wider instructions than storing straight from the accumulator layout).
 template <int EPI, int WCOLS, int ROWS>
 __device__ __forceinline__ void drain_rows(const GemmArgs& a, const char* wbase, int m_first, int n_first, int lane) {
-  constexpr bool BF16_OUT = (kBiasLike<EPI> || kGeluLike<EPI>);
+  constexpr bool BF16_OUT = (kBiasLike<EPI> || kGeluLike<EPI> || kSwiglu<EPI>);
+  // SwiGLU: the 8-column path is the only one (launch() refuses N % 8 != 0); the 4-column fallback below is not compiled for it
+  static_assert(!kSwiglu<EPI> || ((WCOLS % 8) == 0 && (ROWS * (WCOLS / 8)) % 64 == 0), "SwiGLU needs the 8-column drain");
   if constexpr (BF16_OUT && (WCOLS % 8) == 0 && (ROWS * (WCOLS / 8)) % 64 == 0) {
     constexpr int CH = WCOLS / 8;                     // 32-byte (8 x f32) chunks per row -> 16-byte bf16 stores
-    if ((a.N & 7) == 0) {
+    if (kSwiglu<EPI> || (a.N & 7) == 0) {
 #pragma unroll
       for (int it = 0; it < ROWS * CH / 64; ++it) {
         const int idx = it * 64 + lane, r = idx / CH, c = idx - r * CH;
@@ -361,13 +402,15 @@ __device__ __forceinline__ void drain_rows(const GemmArgs& a, const char* wbase,
       return;
     }
   }
-  constexpr int CH = WCOLS / 4;                       // 16-byte chunks per row
-  static_assert((ROWS * CH) % 64 == 0, "whole wave instructions");
+  if constexpr (!kSwiglu<EPI>) {
+    constexpr int CH = WCOLS / 4;                     // 16-byte chunks per row
+    static_assert((ROWS * CH) % 64 == 0, "whole wave instructions");
 #pragma unroll
-  for (int it = 0; it < ROWS * CH / 64; ++it) {
-    const int idx = it * 64 + lane, r = idx / CH, c = idx - r * CH;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(wbase + r * EPI_PITCH(WCOLS) + c * 16);
-    epilogue_store4<EPI>(a, m_first + r, n_first + c * 4, v);
+    for (int it = 0; it < ROWS * CH / 64; ++it) {
+      const int idx = it * 64 + lane, r = idx / CH, c = idx - r * CH;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(wbase + r * EPI_PITCH(WCOLS) + c * 16);
+      epilogue_store4<EPI>(a, m_first + r, n_first + c * 4, v);
+    }
   }
 }
 
@@ -556,7 +599,7 @@ __device__ __forceinline__ void fold_rank_one(f32x4 (&acc)[NI][NT], const float*
 template <int EPI>
 constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kSplit2Out<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
                             EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16 ||
-                            EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI>);
+                            EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI> || kSwiglu<EPI>);
 template <int EPI>
 constexpr bool kF32Out = (EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 || EPI == UCOD_EPI_BIAS_F32);
 
@@ -752,7 +795,8 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     // buffer descriptors over [first row of this wave's tile, end of the matrix) -- rows past M fail the range check and
     // are dropped (loads return 0) -- and columns past N get an offset beyond any descriptor.
     constexpr unsigned OOB = 0xFFFFFFF0u;
-    constexpr int ELT = (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;   // bytes per output column of a row's pitch (the split epilogue's rows are 3 N wide)
+    // bytes per GEMM column of an output row's pitch (the split epilogue's rows are 3 N wide; a SwiGLU row holds N / 2 16-bit values, 3 N / 2 in the split form)
+    constexpr int ELT = kSwiglu<EPI> ? (kSwigluSplit2<EPI> ? 3 : 1) : (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;
     const long rows_left = (long)a.M - m_first;
     const unsigned long left = rows_left > 0 ? (unsigned long)rows_left * a.N * ELT : 0ul;
     const unsigned records = left > 0xFFFFFFFFul ? 0xFFFFFFFFu : (unsigned)left;
@@ -853,13 +897,14 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
       // (row, chunk) of wave instruction `it`: recomputed where needed -- index arrays cost registers the persistent kernel lacks
       auto lrow = [&](int it) { return (it * 64 + lane) / CH; };
       auto lchk = [&](int it) { return (it * 64 + lane) - lrow(it) * CH; };
-      const unsigned off0 = (n_first + (lane & 7) * 8 < a.N) ? (unsigned)(lane >> 3) * row_bytes + (unsigned)(n_first + (lane & 7) * 8) * 2u : DROP;
+      constexpr unsigned CB = kSwiglu<EPI> ? 1u : 2u;            // bytes of a segment per GEMM column (SwiGLU: two columns -> one 16-bit value)
+      const unsigned off0 = (n_first + (lane & 7) * 8 < a.N) ? (unsigned)(lane >> 3) * row_bytes + (unsigned)(n_first + (lane & 7) * 8) * CB : DROP;
       const char* lds0 = wbase + (lane >> 3) * EPI_PITCH(WCOLS) + (lane & 7) * 32;
       auto live = [&](int it, int pass) { return !FAST || it * 8 < rows_in(pass); };   // (compile-time after unrolling) rows 16..31 of a 16-row last pass
       auto at = [&](int it, int pass) -> unsigned {
         if constexpr (FAST) return off0 + (unsigned)(pass * PR + it * 8) * row_bytes;
         const int n = n_first + lchk(it) * 8;
-        return (n < a.N && lrow(it) < rows_in(pass)) ? (unsigned)(pass * PR + lrow(it)) * row_bytes + (unsigned)n * 2u : OOB;
+        return (n < a.N && lrow(it) < rows_in(pass)) ? (unsigned)(pass * PR + lrow(it)) * row_bytes + (unsigned)n * CB : OOB;
       };
       auto lds_at = [&](int it) -> const char* {
         if constexpr (FAST) return lds0 + it * 8 * EPI_PITCH(WCOLS);
@@ -923,6 +968,24 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
               if (e < 2) { v0[2 * e] *= g[0]; v0[2 * e + 1] *= g[1]; }
               else { v1[2 * (e - 2)] *= g[0]; v1[2 * (e - 2) + 1] *= g[1]; }
             }
+          }
+          if constexpr (kSwiglu<EPI>) {                           // v0 = x1, v1 = x2 of 4 hidden units: one 8-byte store per segment
+            const f32x4 h = swiglu4<EPI>(v0, v1);
+            const unsigned o = at(it, pass);
+            if constexpr (kSwigluSplit2<EPI>) {                   // hi | hi | lo, N / 2 elements (N bytes) apart
+              const u32x2 t0 = split2_pack(h[0], h[1]), t1 = split2_pack(h[2], h[3]);
+              const u32x2 hi = {t0[0], t1[0]}, lo = {t0[1], t1[1]};
+              // a dropped chunk's offset is a sentinel >= 2^31 (DROP + tile offset, or OOB); the segments keep it instead of adding N / 2 N to it, which would
+              // wrap OOB back into range (live offsets stay below 2^31: gemm_entry bounds M * 3 N)
+              const bool dead = o >= 0x80000000u;
+              __builtin_amdgcn_raw_buffer_store_b64(hi, rs_o, o, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b64(hi, rs_o, dead ? o : o + (unsigned)a.N, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b64(lo, rs_o, dead ? o : o + 2u * (unsigned)a.N, 0, AUX);
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b64((u32x2){pack_h2(h[0], h[1]), pack_h2(h[2], h[3])}, rs_o, o, 0, AUX);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            continue;
           }
           u32x4 w;
           if constexpr (RH16) {                                   // x_new = x_old + lambda (acc + b), all in IEEE fp16 storage

@@ -82,7 +82,8 @@ __device__ __forceinline__ void store_terms8(const float (&v)[8], bf16_raw* __re
   for (int s = 0; s < TERMS; ++s) *reinterpret_cast<u32x4*>(seg0 + (long)s * seg_stride) = (u32x4){w[s][0], w[s][1], w[s][2], w[s][3]};
 }
 
-// ---- f32 [M, K] (row pitch ld_in) -> bf16 [M, P K]; op 0: the values, 1: exact-erf GELU of them, 2: times `alpha`
+// ---- f32 [M, K] (row pitch ld_in) -> bf16 [M, P K]; op 0: the values, 1: exact-erf GELU of them, 2: times `alpha`,
+// 3: SwiGLU of rows 2 K wide interleaved in blocks of 4 (input columns 8k+e / 8k+4+e = x1 / x2 of output column 4k+e: include/ucod_dpl.h, UCOD_EPI_BIAS_SWIGLU_BF16)
 template <int TERMS>
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ in, long ld_in, bf16_raw* __restrict__ out, int M, int K, int role, int op, float alpha) {
   constexpr int P = products_of(TERMS);
@@ -91,9 +92,18 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long m = i / k8;
     const int c = (int)(i - m * k8) * 8;
+    float v[8];
+    if (op == 3) {                                                 // output columns c .. c+7 <- input columns 2c .. 2c+15: (x1 | x2) of c .. c+3, then of c+4 .. c+7
+      const float4* src = reinterpret_cast<const float4*>(in + m * ld_in + 2 * c);
+      const float4 x1a = src[0], x2a = src[1], x1b = src[2], x2b = src[3];
+      v[0] = silu_f32(x1a.x) * x2a.x; v[1] = silu_f32(x1a.y) * x2a.y; v[2] = silu_f32(x1a.z) * x2a.z; v[3] = silu_f32(x1a.w) * x2a.w;
+      v[4] = silu_f32(x1b.x) * x2b.x; v[5] = silu_f32(x1b.y) * x2b.y; v[6] = silu_f32(x1b.z) * x2b.z; v[7] = silu_f32(x1b.w) * x2b.w;
+      store_split8<TERMS>(v, out + m * (long)P * K + c, K, role);
+      continue;
+    }
     const float4* src = reinterpret_cast<const float4*>(in + m * ld_in + c);
     const float4 a = src[0], b = src[1];
-    float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     if (op == 1) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = gelu_exact(v[e]);
@@ -558,7 +568,8 @@ extern "C" int ucod_split_products(int terms) { return terms_ok(terms) ? product
 
 extern "C" int ucod_split_rows(const float* in, long ld_in, void* out, int M, int K, int terms, int role, int op, float alpha, void* stream) {
   UCOD_BF16_ONLY();
-  if (!in || !out || M <= 0 || K <= 0 || (K & 7) != 0 || ld_in < K || (ld_in & 3) != 0 || !terms_ok(terms) || (role != 0 && role != 1) || op < 0 || op > 2) return UCOD_EINVAL;
+  if (!in || !out || M <= 0 || K <= 0 || (K & 7) != 0 || ld_in < K || (ld_in & 3) != 0 || !terms_ok(terms) || (role != 0 && role != 1) || op < 0 || op > 3) return UCOD_EINVAL;
+  if (op == 3 && ld_in < 2L * K) return UCOD_EINVAL;             // (op 3 reads rows 2 K wide)
   UCOD_PROF(PROF_SPLIT, stream);
   const int blocks = blocks_for((long)M * (K >> 3));
   if (terms == 2) hipLaunchKernelGGL(split_rows_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, ld_in, (bf16_raw*)out, M, K, role, op, alpha);
@@ -655,7 +666,7 @@ struct SplitPlan {
   int M, tok, P;
 };
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-SplitPlan split_plan(const ucod_vit_desc* d, int terms) {
+SplitPlan split_plan(const ucod_vit_desc* d, int terms, int mlp) {
   SplitPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
   p.tok = gh * gw + 1;
@@ -668,14 +679,15 @@ SplitPlan split_plan(const ucod_vit_desc* d, int terms) {
   p.off_qkv = take((size_t)p.M * 3 * d->D * 4);
   p.off_att = take(ucod_attention_split_operand_bytes(d->B, p.tok, d->heads, terms));
   p.off_a = take((size_t)p.M * p.P * d->D * 2);
-  p.off_f1 = take(terms == 2 ? 0 : (size_t)p.M * d->F * 4);       // (two terms: fc1 + GELU + split in one launch, no f32 copy of the MLP hidden)
+  // (two terms: fc1 + GELU / SwiGLU + split in one launch, no f32 copy of the MLP hidden; three: fc1's f32 output, 2 F wide for SwiGLU)
+  p.off_f1 = take(terms == 2 ? 0 : (size_t)p.M * d->F * (mlp == UCOD_MLP_SWIGLU ? 2 : 1) * 4);
   p.off_g = take((size_t)p.M * p.P * d->F * 2);
   p.off_patch = take((size_t)d->B * gh * gw * p.P * d->Kpad * 2);
   p.total = o;
   return p;
 }
-bool split_valid(const ucod_vit_desc* d, int terms) {
-  return d && terms_ok(terms) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
+bool split_valid(const ucod_vit_desc* d, int terms, int mlp) {
+  return d && terms_ok(terms) && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->D <= 1536 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          d->full_last_layer == 0 && (long)d->B * d->heads <= 65535;
 }
@@ -687,16 +699,19 @@ bool split_valid(const ucod_vit_desc* d, int terms) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_split_workspace_bytes(const ucod_vit_desc* d, int terms) { return split_valid(d, terms) ? split_plan(d, terms).total : 0; }
+extern "C" size_t ucod_vit_split_workspace_bytes_mlp(const ucod_vit_desc* d, int terms, int mlp) { return split_valid(d, terms, mlp) ? split_plan(d, terms, mlp).total : 0; }
+extern "C" size_t ucod_vit_split_workspace_bytes(const ucod_vit_desc* d, int terms) { return ucod_vit_split_workspace_bytes_mlp(d, terms, UCOD_MLP_GELU); }
 // byte offset, inside the workspace, of the f32 residual stream x [B tok, D]: after a key-minimal pass it holds the INPUT of the pass's last layer (the last layer
 // only runs LayerNorm 1 and the key hook), which is what the CLS-attention row of the pseudo-label generator is computed from
-extern "C" size_t ucod_vit_split_stream_offset(const ucod_vit_desc* d, int terms) { return split_valid(d, terms) ? split_plan(d, terms).off_x : (size_t)-1; }
+extern "C" size_t ucod_vit_split_stream_offset_mlp(const ucod_vit_desc* d, int terms, int mlp) { return split_valid(d, terms, mlp) ? split_plan(d, terms, mlp).off_x : (size_t)-1; }
+extern "C" size_t ucod_vit_split_stream_offset(const ucod_vit_desc* d, int terms) { return ucod_vit_split_stream_offset_mlp(d, terms, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_split(const ucod_vit_desc* d, int terms, const void* const* T, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+extern "C" int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int mlp, const void* const* T, const float* img, float* key_out, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!split_valid(d, terms) || !T || !img || !key_out || !workspace) return UCOD_EINVAL;
-  const SplitPlan p = split_plan(d, terms);
+  if (!split_valid(d, terms, mlp) || !T || !img || !key_out || !workspace) return UCOD_EINVAL;
+  const SplitPlan p = split_plan(d, terms, mlp);
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   float* x = (float*)(ws + p.off_x);
@@ -726,7 +741,15 @@ extern "C" int ucod_vit_forward_split(const ucod_vit_desc* d, int terms, const v
     RUN(ucod_attention_split_fwd(att, a, d->B, tok, d->heads, terms, stream));
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, a, W[4], x, M, D, P * D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
     RUN(ucod_layernorm_split(x, (const float*)W[7], (const float*)W[8], h, M, D, d->eps, terms, 0, stream));
-    if (terms == 2) {
+    if (swiglu) {
+      // SwiGLU (modeling_dinov2.py:300-315): weights_in is 2 F rows, interleaved in blocks of 4 (include/ucod_dpl.h); two terms: one launch, SiLU at f32 accuracy in the
+      // epilogue; three terms: f32 [M, 2 F] then ucod_split_rows op 3
+      if (terms == 2) RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SWIGLU_SPLIT2, h, W[9], g, M, 2 * F, P * D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+      else {
+        RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[9], f1, M, 2 * F, P * D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+        RUN(ucod_split_rows(f1, 2L * F, g, M, F, terms, 0, 3, 1.f, stream));
+      }
+    } else if (terms == 2) {
       // two terms: fc1 + GELU + the split of its result in ONE launch (UCOD_EPI_BIAS_GELU_SPLIT2: the epilogue's minimax erf-GELU, |err| <= 7.1e-7, is an order of
       // magnitude below the 2^-17 of a two-term operand); three terms keep the exact-erf kernel behind an f32 round trip
       RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_SPLIT2, h, W[9], g, M, F, P * D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
@@ -737,4 +760,9 @@ extern "C" int ucod_vit_forward_split(const ucod_vit_desc* d, int terms, const v
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, g, W[11], x, M, D, P * F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
   }
   return UCOD_OK;
+}
+
+extern "C" int ucod_vit_forward_split(const ucod_vit_desc* d, int terms, const void* const* T, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return ucod_vit_forward_split_mlp(d, terms, UCOD_MLP_GELU, T, img, key_out, workspace, workspace_bytes, stream);
 }

@@ -51,8 +51,8 @@ Plan make_plan(const ucod_vit_desc* d) {
 inline bool attn_variant_known(int av) { return av == 0 || av == 1 || av == 2 || av == 8 || av == 5 || av == 66; }
 inline bool attn_variant_takes_prescaled_q(int av) { return av != 1; }
 
-bool valid(const ucod_vit_desc* d) {
-  return d && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 &&
+bool valid(const ucod_vit_desc* d, int mlp = UCOD_MLP_GELU) {
+  return d && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 &&
          d->heads > 0 && d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 &&
          d->Kpad >= d->C * d->P * d->P && (d->resid16 == 0 || d->resid16 == 1) && attn_variant_known(d->attn_variant) &&
          (d->ln_fold == 0 || (d->ln_fold == 1 && d->resid16 == 1 && d->attn_variant != 8 && UCOD_HALF_IS_F16 && d->D % 256 == 0 && d->D <= 1536));
@@ -66,12 +66,17 @@ bool valid(const ucod_vit_desc* d) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d) { return valid(d) ? make_plan(d).total : 0; }
-extern "C" size_t ucod_vit_last_ln1_offset(const ucod_vit_desc* d) { return valid(d) ? make_plan(d).off_h : (size_t)-1; }
+// (the SwiGLU MLP writes its hidden [M, F] straight from the fc1 epilogue: the same workspace as GELU's)
+extern "C" size_t ucod_vit_workspace_bytes_mlp(const ucod_vit_desc* d, int mlp) { return valid(d, mlp) ? make_plan(d).total : 0; }
+extern "C" size_t ucod_vit_last_ln1_offset_mlp(const ucod_vit_desc* d, int mlp) { return valid(d, mlp) ? make_plan(d).off_h : (size_t)-1; }
+extern "C" size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d) { return ucod_vit_workspace_bytes_mlp(d, UCOD_MLP_GELU); }
+extern "C" size_t ucod_vit_last_ln1_offset(const ucod_vit_desc* d) { return ucod_vit_last_ln1_offset_mlp(d, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward(const ucod_vit_desc* d, const void* const* T, const float* img, float* key_out, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  if (!valid(d) || !T || !img || !key_out || !workspace) return UCOD_EINVAL;
+extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void* const* T, const float* img, float* key_out, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (!valid(d, mlp) || !T || !img || !key_out || !workspace) return UCOD_EINVAL;
+  // SwiGLU (modeling_dinov2.py:300-315): fc1 = weights_in, 2 F rows interleaved in blocks of 4 (include/ucod_dpl.h); its epilogue writes silu(x1) * x2 [M, F]
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const Plan p = make_plan(d);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
@@ -171,15 +176,20 @@ extern "C" int ucod_vit_forward(const ucod_vit_desc* d, const void* const* T, co
     RUN(resid_gemm(a, W[4], (const float*)W[5], (const float*)W[6], D, fold));
     if (fold) {
       if (!have_part) RUN(ucod_row_stats_h16(x, stats, M, D, d->eps, stream));
-      RUN(ucod_gemm_lnfold(UCOD_EPI_LNFOLD_GELU_BF16, x, W[9], g, M, F, D, (const float*)W[10], (const float*)W[15], have_part ? nullptr : stats,
+      RUN(ucod_gemm_lnfold(swiglu ? UCOD_EPI_LNFOLD_SWIGLU_BF16 : UCOD_EPI_LNFOLD_GELU_BF16, x, W[9], g, M, swiglu ? 2 * F : F, D, (const float*)W[10], (const float*)W[15], have_part ? nullptr : stats,
                            have_part ? part : nullptr, nslot, d->eps, nullptr, gv, stream));
     } else {
       RUN(layernorm((const float*)W[7], (const float*)W[8]));
-      RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_gemm_bf16(swiglu ? UCOD_EPI_BIAS_SWIGLU_BF16 : UCOD_EPI_BIAS_GELU_BF16, h, W[9], g, M, swiglu ? 2 * F : F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     }
     RUN(resid_gemm(g, W[11], (const float*)W[12], (const float*)W[13], F, next_fold));
   }
   return UCOD_OK;
+}
+
+extern "C" int ucod_vit_forward(const ucod_vit_desc* d, const void* const* T, const float* img, float* key_out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_mlp(d, UCOD_MLP_GELU, T, img, key_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" const char* ucod_half_name(void) { return UCOD_HALF_NAME; }

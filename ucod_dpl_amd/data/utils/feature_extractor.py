@@ -26,20 +26,34 @@ ARCHS = {
     "dinov2_vits14": (384, 6, 12, 14, 518, True),
     "dinov2_vitb14": (768, 12, 12, 14, 518, True),
     "dinov2_vitl14": (1024, 16, 24, 14, 518, True),
+    "dinov2_vitg14": (1536, 24, 40, 14, 518, True),
     "dino_vits8": (384, 6, 12, 8, 224, False),
     "dino_vitb8": (768, 12, 12, 8, 224, False),
 }
 HUB_TO_ARCH = {"facebook/dinov2-small": "dinov2_vits14", "facebook/dinov2-base": "dinov2_vitb14", "facebook/dinov2-large": "dinov2_vitl14",
-               "facebook/dino-vits8": "dino_vits8", "facebook/dino-vitb8": "dino_vitb8"}
+               "facebook/dinov2-giant": "dinov2_vitg14", "facebook/dino-vits8": "dino_vits8", "facebook/dino-vitb8": "dino_vitb8"}
+# architectures whose MLP is Dinov2SwiGLUFFN (config.use_swiglu_ffn, modeling_dinov2.py:300-315,355): weights_in [2F, D] / weights_out [D, F] instead of fc1 / fc2
+SWIGLU_ARCHS = {"dinov2_vitg14"}
 
 
-def random_state_dict(arch, seed=0, image_size=None):
+def swiglu_hidden(D, mlp_ratio=4):
+    """HF's SwiGLU hidden width (modeling_dinov2.py:304-305): 4096 at D = 1536."""
+    return (int(int(D * mlp_ratio) * 2 / 3) + 7) // 8 * 8
+
+
+def random_state_dict(arch, seed=0, image_size=None, device=None):
     """Seeded HF-layout state dict with the architecture's shapes (trunc-normal sigma 0.02, HF init); throughput and
-    parity tests do not depend on trained weights."""
+    parity tests do not depend on trained weights.  ``device="meta"``: shapes only (no allocation)."""
+    if device is not None and torch.device(device).type == "meta":
+        with torch.device("meta"):
+            return _random_state_dict(arch, seed, image_size, lambda *s: torch.empty(*s))
+    g = torch.Generator().manual_seed(seed)
+    return _random_state_dict(arch, seed, image_size, lambda *s: torch.nn.init.trunc_normal_(torch.empty(*s), std=0.02, a=-0.04, b=0.04, generator=g))
+
+
+def _random_state_dict(arch, seed, image_size, tn):
     D, heads, L, P, img, ls = ARCHS[arch]
     img = image_size or img
-    g = torch.Generator().manual_seed(seed)
-    tn = lambda *s: torch.nn.init.trunc_normal_(torch.empty(*s), std=0.02, a=-0.04, b=0.04, generator=g)  # noqa: E731
     n = (img // P) ** 2
     sd = {"embeddings.cls_token": tn(1, 1, D), "embeddings.position_embeddings": tn(1, n + 1, D),
           "embeddings.patch_embeddings.projection.weight": tn(D, 3, P, P), "embeddings.patch_embeddings.projection.bias": torch.zeros(D)}
@@ -48,8 +62,13 @@ def random_state_dict(arch, seed=0, image_size=None):
         for nm in ("query", "key", "value"):
             sd[p + f"attention.attention.{nm}.weight"], sd[p + f"attention.attention.{nm}.bias"] = tn(D, D), tn(D)
         sd[p + "attention.output.dense.weight"], sd[p + "attention.output.dense.bias"] = tn(D, D), tn(D)
-        sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = tn(4 * D, D), tn(4 * D)
-        sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = tn(D, 4 * D), tn(D)
+        if arch in SWIGLU_ARCHS:
+            F = swiglu_hidden(D)
+            sd[p + "mlp.weights_in.weight"], sd[p + "mlp.weights_in.bias"] = tn(2 * F, D), tn(2 * F)
+            sd[p + "mlp.weights_out.weight"], sd[p + "mlp.weights_out.bias"] = tn(D, F), tn(D)
+        else:
+            sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = tn(4 * D, D), tn(4 * D)
+            sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = tn(D, 4 * D), tn(D)
         for nm in ("norm1", "norm2"):
             sd[p + nm + ".weight"], sd[p + nm + ".bias"] = torch.ones(D) + tn(D), tn(D)
         if ls:

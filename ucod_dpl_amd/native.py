@@ -26,6 +26,9 @@ EPI_BIAS_SCALE_RESID_H16, EPI_PATCH_TOKENS_H16 = 9, 10     # f16 residual stream
 EPI_LNFOLD_BIAS_BF16, EPI_LNFOLD_GELU_BF16 = 11, 12        # ucod_gemm_lnfold only (LayerNorm folded into QKV / fc1; the fp16-operand build)
 EPI_BIAS_SCALE_RESID_H16_STATS, EPI_PATCH_TOKENS_H16_STATS = 13, 14   # ucod_gemm_bf16_stats only (the producers that leave row partials)
 EPI_BIAS_GELU_SPLIT2 = 15                                  # fc1 + GELU + two-term split of the result in one launch (the split-operand pass; bf16 library)
+# SwiGLU MLP of DINOv2 ViT-g/14 on interleaved weights_in rows (include/ucod_dpl.h): 16-bit [M, N/2] (both libraries); the LayerNorm-folded form (ucod_gemm_lnfold,
+# fp16-operand build); the two-term split operand of the result (bf16 library)
+EPI_BIAS_SWIGLU_BF16, EPI_LNFOLD_SWIGLU_BF16, EPI_BIAS_SWIGLU_SPLIT2 = 16, 17, 18
 VIT_LAYER_STRIDE = 16
 VIT_TRAIN_STRIDE = 7
 LORA_AUG = 64
@@ -55,6 +58,8 @@ class DiscGrads(C.Structure):
     _fields_ = [(n, vp) for n in ("w1", "g1", "b1", "w2", "g2", "b2", "w3", "g3", "b3", "lin_w", "lin_b")]
 
 
+UCOD_MLP_GELU, UCOD_MLP_SWIGLU = 0, 1        # MLP kind of the _mlp backbone entry points (include/ucod_dpl.h)
+
 # name -> (restype, argtypes); must list EVERY symbol include/ucod_dpl.h declares (tests/test_abi.py checks)
 SIGNATURES = {
     "ucod_abi_version": (ci, []),
@@ -75,6 +80,9 @@ SIGNATURES = {
     "ucod_vit_split_workspace_bytes": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_split_stream_offset": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_forward_split": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_split_workspace_bytes_mlp": (sz, [C.POINTER(VitDesc), ci, ci]),
+    "ucod_vit_split_stream_offset_mlp": (sz, [C.POINTER(VitDesc), ci, ci]),
+    "ucod_vit_forward_split_mlp": (ci, [C.POINTER(VitDesc), ci, ci, C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),
@@ -99,6 +107,9 @@ SIGNATURES = {
     "ucod_cast_f32_bf16": (ci, [vp, vp, sz, vp]),
     "ucod_vit_workspace_bytes": (sz, [C.POINTER(VitDesc)]),
     "ucod_vit_forward": (ci, [C.POINTER(VitDesc), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_workspace_bytes_mlp": (sz, [C.POINTER(VitDesc), ci]),
+    "ucod_vit_forward_mlp": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_last_ln1_offset_mlp": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_train_workspace_bytes": (sz, [C.POINTER(VitTrainDesc)]),
     "ucod_vit_forward_train": (ci, [C.POINTER(VitTrainDesc), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_vit_backward": (ci, [C.POINTER(VitTrainDesc), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),

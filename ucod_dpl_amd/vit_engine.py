@@ -45,7 +45,9 @@ def _interp_pos_dinov1(pos, gh, gw):
 def normalize_state_dict(sd):
     """Map any supported checkpoint layout to a canonical dict:
     patch_w [D,C,P,P], patch_b, cls [D], pos [1,1+n,D], kind ('dinov2'|'dinov1'),
-    layers: list of dict(ln1_g, ln1_b, qkv_w [3D,D], qkv_b, proj_w, proj_b, ls1|None, ln2_g, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b, ls2|None)."""
+    layers: list of dict(ln1_g, ln1_b, qkv_w [3D,D], qkv_b, proj_w, proj_b, ls1|None, ln2_g, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b, ls2|None).
+    A SwiGLU checkpoint (DINOv2 ViT-g/14: mlp.weights_in / mlp.weights_out, modeling_dinov2.py:300-315) also sets ``mlp = "swiglu"``; its fc1_w / fc1_b are
+    weights_in [2F, D] / [2F] in HF's row order (x1 rows, then x2 rows) and fc2_w is weights_out [D, F] (swiglu.prepare pads and interleaves them)."""
     sd = {k: v for k, v in sd.items()}
     out = {"layers": []}
     if "cls_token" in sd and "pos_embed" in sd:                      # in-repo DINO
@@ -74,6 +76,9 @@ def normalize_state_dict(sd):
     out["kind"] = "dinov2" if has_ls else "dinov1"
     lay = "encoder.layer." if any(k.startswith(pref + "encoder.layer.") for k in sd) else "encoder.layers."
     L = 1 + max(int(k[len(pref + lay):].split(".")[0]) for k in sd if k.startswith(pref + lay))
+    swiglu = pref + lay + "0.mlp.weights_in.weight" in sd
+    if swiglu:
+        out["mlp"] = "swiglu"
     for i in range(L):
         p = f"{lay}{i}."
 
@@ -91,10 +96,26 @@ def normalize_state_dict(sd):
             proj_w=first("attention.output.dense.weight", "attention.o_proj.weight"), proj_b=first("attention.output.dense.bias", "attention.o_proj.bias"),
             ls1=first("layer_scale1.lambda1") if has_ls else None,
             ln2_g=first("norm2.weight", "layernorm_after.weight"), ln2_b=first("norm2.bias", "layernorm_after.bias"),
-            fc1_w=first("mlp.fc1.weight", "intermediate.dense.weight"), fc1_b=first("mlp.fc1.bias", "intermediate.dense.bias"),
-            fc2_w=first("mlp.fc2.weight", "output.dense.weight"), fc2_b=first("mlp.fc2.bias", "output.dense.bias"),
+            fc1_w=first("mlp.weights_in.weight") if swiglu else first("mlp.fc1.weight", "intermediate.dense.weight"),
+            fc1_b=first("mlp.weights_in.bias") if swiglu else first("mlp.fc1.bias", "intermediate.dense.bias"),
+            fc2_w=first("mlp.weights_out.weight") if swiglu else first("mlp.fc2.weight", "output.dense.weight"),
+            fc2_b=first("mlp.weights_out.bias") if swiglu else first("mlp.fc2.bias", "output.dense.bias"),
             ls2=first("layer_scale2.lambda1") if has_ls else None))
     return out
+
+
+def _prepare_mlp(c):
+    """(MLP kind for the library's _mlp entry points, canonical dict whose fc1 / fc2 entries are what the tables hold).  SwiGLU: weights_in / its bias padded to
+    F % 128 == 0 and interleaved in blocks of 4, weights_out padded (swiglu.prepare; host f32); GELU: ``c`` unchanged."""
+    if c.get("mlp", "gelu") != "swiglu":
+        return N.UCOD_MLP_GELU, c
+    from .swiglu import prepare
+    cpu = lambda t: t.detach().to("cpu", torch.float32)  # noqa: E731
+    layers = []
+    for l in c["layers"]:
+        w_in, b_in, w_out = prepare(cpu(l["fc1_w"]), cpu(l["fc1_b"]), cpu(l["fc2_w"]))
+        layers.append(dict(l, fc1_w=w_in, fc1_b=b_in, fc2_w=w_out))
+    return N.UCOD_MLP_SWIGLU, dict(c, layers=layers)
 
 
 class ViTEngine:
@@ -128,7 +149,7 @@ class ViTEngine:
         if resid not in ("auto", "f32", "f16"):
             raise ValueError(f"resid must be 'auto', 'f32' or 'f16', got {resid!r}")
         self.resid = resid
-        c = normalize_state_dict(state_dict)
+        self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
         D0 = c["patch_w"].shape[0]
         fold_shape = half == "f16" and D0 % 256 == 0 and D0 <= 1536 and attn_variant != 8       # where ucod_gemm_lnfold exists
         self.resid16 = bool(resid == "f16" or (resid == "auto" and (half == "bf16" or (fold_shape and ln_fold is not False))))
@@ -146,7 +167,7 @@ class ViTEngine:
         if self.D != heads * 64:
             raise ValueError(f"head_dim must be 64 (D={self.D}, heads={heads})")
         self.L = len(c["layers"])
-        self.F = c["layers"][0]["fc1_w"].shape[0]
+        self.F = c["layers"][0]["fc2_w"].shape[1]                  # the MLP hidden width (SwiGLU: after padding; fc1 then has 2 F rows)
         self.eps = float(eps)
         self.full_last_layer = bool(full_last_layer)
         self.gemm_variant, self.attn_variant = gemm_variant, attn_variant
@@ -315,13 +336,13 @@ class ViTEngine:
         ns = max(1, min(int(getattr(self, "streams", 1)), B))
         if ns == 1 and not _async:
             d = self._desc(B, H, W, n_layers)
-            need = lib.ucod_vit_workspace_bytes(C.byref(d))
+            need = lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp)
             if need == 0:
                 raise ValueError("unsupported ViT geometry")
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             with self._own_counter():
-                N.check(lib.ucod_vit_forward(C.byref(d), table, N.ptr(img), N.ptr(key), N.ptr(self._ws), self._ws.numel(), N.stream()),
+                N.check(lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(self._ws), self._ws.numel(), N.stream()),
                         "ucod_vit_forward")
             self._arm_overflow_check(torch.cuda.current_stream(self.device))
             if self._sync_check:
@@ -345,7 +366,7 @@ class ViTEngine:
         for i in range(ns):
             b0, b1 = bounds[i], bounds[i + 1]
             d = self._desc(b1 - b0, H, W, n_layers)
-            need = lib.ucod_vit_workspace_bytes(C.byref(d))
+            need = lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp)
             if need == 0:
                 raise ValueError("unsupported ViT geometry")
             if self._side_ws[i] is None or self._side_ws[i].numel() < need:
@@ -356,8 +377,8 @@ class ViTEngine:
             key.record_stream(st)                                  # caching allocator from recycling them before this stream is done
             with torch.cuda.stream(st):
                 with self._own_counter():
-                    N.check(lib.ucod_vit_forward(C.byref(d), table, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(self._side_ws[i]),
-                                                 self._side_ws[i].numel(), N.stream()), "ucod_vit_forward")
+                    N.check(lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(self._side_ws[i]),
+                                                     self._side_ws[i].numel(), N.stream()), "ucod_vit_forward")
                 self._arm_overflow_check(st)
                 done = torch.cuda.Event()
                 done.record(st)
@@ -385,7 +406,7 @@ class ViTEngine:
         B, _, H, W = img.shape
         lib = self.lib
         d = self._desc(B, H, W)
-        off = lib.ucod_vit_last_ln1_offset(C.byref(d))
+        off = lib.ucod_vit_last_ln1_offset_mlp(C.byref(d), self.mlp)
         tok = key.shape[-2] * key.shape[-1] + 1
         last = self.layers[-1]
         q = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
@@ -422,13 +443,13 @@ class SplitViTEngine:
         self.terms, self.half = int(terms), f"bf16x{int(terms)}"
         self.lib = N.load("bf16")                                 # (bf16 MFMA; the fp16 build refuses the split entry points)
         self.nprod = ops.split_products(terms)
-        c = normalize_state_dict(state_dict)
+        self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
         self.kind, self.device = c["kind"], torch.device(device)
         self.D, self.C, self.P = c["patch_w"].shape[0], c["patch_w"].shape[1], c["patch_w"].shape[2]
         self.heads = heads
         if self.D != heads * 64:
             raise ValueError(f"head_dim must be 64 (D={self.D}, heads={heads})")
-        self.L, self.F, self.eps = len(c["layers"]), c["layers"][0]["fc1_w"].shape[0], float(eps)
+        self.L, self.F, self.eps = len(c["layers"]), c["layers"][0]["fc2_w"].shape[1], float(eps)
         self.gemm_variant, self.streams = gemm_variant, 1
         self.resid16 = self.ln_fold = self.full_last_layer = False
         self.resid, self.attn_variant = "f32", 0
@@ -475,14 +496,15 @@ class SplitViTEngine:
         B, _, H, W = img.shape
         d = self._desc(B, H, W, n_layers)
         d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        need = self.lib.ucod_vit_split_workspace_bytes(C.byref(d), self.terms)
+        need = self.lib.ucod_vit_split_workspace_bytes_mlp(C.byref(d), self.terms, self.mlp)
         if need == 0:
             raise ValueError("unsupported ViT geometry")
         ws = ws_slot[0]
         if ws is None or ws.numel() < need:
             ws = ws_slot[0] = torch.empty(need, dtype=torch.uint8, device=self.device)
         table, _keep = self._table(H // self.P, W // self.P)
-        N.check(self.lib.ucod_vit_forward_split(C.byref(d), self.terms, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_forward_split")
+        N.check(self.lib.ucod_vit_forward_split_mlp(C.byref(d), self.terms, self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
+                "ucod_vit_forward_split")
 
     def forward(self, img, out=None, _async=False, n_layers=None):
         if n_layers is not None and not 1 <= n_layers <= self.L:
@@ -524,7 +546,7 @@ class SplitViTEngine:
         B, _, H, W = img.shape
         d = self._desc(B, H, W)
         d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        off = self.lib.ucod_vit_split_stream_offset(C.byref(d), self.terms)
+        off = self.lib.ucod_vit_split_stream_offset_mlp(C.byref(d), self.terms, self.mlp)
         tok = key.shape[-2] * key.shape[-1] + 1
         x = self._ws[0][off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
         L_ = self._last
@@ -555,6 +577,9 @@ class ViTLoRAEngine(ViTEngine):
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto"):
+        if normalize_state_dict(state_dict).get("mlp") == "swiglu":
+            raise NotImplementedError("backbone-backward (LoRA) mode has no backward of the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315): "
+                                      "use the frozen-backbone engines (ViTEngine / SplitViTEngine) for this checkpoint")
         # resid: as ViTEngine ("auto" = the fp16 residual stream with bf16 operands).  Round 4: the training pass SAVES the stream in that
         # type and LayerNorm backward reads it (ucod_layernorm_bwd_ex); resid="f32" keeps the round-3 path.
         super().__init__(state_dict, heads, eps=eps, device=device, full_last_layer=False, gemm_variant=gemm_variant, attn_variant=2, resid=resid,
