@@ -247,41 +247,42 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
   return (1.f - t) * x + fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x)));
 }
 
-// grid (cdiv(HW,256), B)
-__global__ __launch_bounds__(256) void apm_bce_kernel(const float* __restrict__ pl, const float* __restrict__ teacher,
-                                                      const float* __restrict__ fg, const float* __restrict__ bg,
-                                                      const float* __restrict__ p_s, const float* __restrict__ p_p, float epoch_frac,
-                                                      float gscale, float* __restrict__ wout, float* __restrict__ merged,
-                                                      float* __restrict__ gfg, float* __restrict__ gbg, float* __restrict__ losses,
-                                                      int B, int HW) {
+// grid (B): one workgroup per image, whose two BCE sums reach `losses` as ONE f32 atomic each.  (One workgroup per 256 pixels added
+// B * HW / 256 = 608 atomics into each loss at the step's size: their order-dependent rounding reached 1.2e-6 of the loss over 300 launches,
+// past the 8-ulp bound of tests/test_gpu_train_kernels.py::test_apm_bce_at_the_headline_size; profiles/r08_apm_bce_loss_spread_ab.jsonl.)
+constexpr int APM_THREADS = 1024;
+__global__ __launch_bounds__(APM_THREADS) void apm_bce_kernel(const float* __restrict__ pl, const float* __restrict__ teacher,
+                                                              const float* __restrict__ fg, const float* __restrict__ bg,
+                                                              const float* __restrict__ p_s, const float* __restrict__ p_p, float epoch_frac,
+                                                              float gscale, float* __restrict__ wout, float* __restrict__ merged,
+                                                              float* __restrict__ gfg, float* __restrict__ gbg, float* __restrict__ losses,
+                                                              int B, int HW) {
   __shared__ float red[16];
-  const int b = blockIdx.y, tid = threadIdx.x;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const float ps = p_s[b], pp = p_p[b];
   float w = 0.5f * (1.f + cosf(fabsf(ps - pp) * 3.14159265358979323846f)) + epoch_frac;
   w = fminf(fmaxf(w, 0.f), 1.f);
-  const int p = blockIdx.x * 256 + tid;
   float l1 = 0.f, l2 = 0.f;
-  const float inv_n = 1.f / ((float)B * (float)HW);
-  if (p < HW) {
+  const float n = (float)B * (float)HW;
+  const float inv_n = 1.f / n;
+  for (int p = tid; p < HW; p += APM_THREADS) {
     const long i = (long)b * HW + p;
     const float pt = sigmoid_acc(teacher[i]) > 0.5f ? 1.f : 0.f;
     const float t = pl[i] * (1.f - w) + pt * w;
     merged[i] = t;
     const float xf = fg[i], xb = bg[i];
-    l1 = bce_logits(xf, t);
-    l2 = bce_logits(xb, 1.f - t);
+    l1 += bce_logits(xf, t);
+    l2 += bce_logits(xb, 1.f - t);
     gfg[i] = (sigmoid_acc(xf) - t) * inv_n * gscale;
     gbg[i] = (sigmoid_acc(xb) - (1.f - t)) * inv_n * gscale;
   }
   l1 = block_sum(l1, red);
   l2 = block_sum(l2, red);
   if (tid == 0) {
-    atomicAdd(&losses[0], l1 * inv_n);
-    atomicAdd(&losses[1], l2 * inv_n);
-    if (blockIdx.x == 0) {
-      wout[b] = w;
-      atomicAdd(&losses[2], -fmaxf(logf(1.f - ps), -100.f) / (float)B);  // BCELoss(p_s, 0), torch clamps log at -100
-    }
+    atomicAdd(&losses[0], l1 / n);
+    atomicAdd(&losses[1], l2 / n);
+    wout[b] = w;
+    atomicAdd(&losses[2], -fmaxf(logf(1.f - ps), -100.f) / (float)B);  // BCELoss(p_s, 0), torch clamps log at -100
   }
 }
 
@@ -375,7 +376,7 @@ extern "C" int ucod_apm_bce(const float* pl, const float* teacher, const float* 
     hipError_t e = hipMemsetAsync(losses, 0, 4 * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(apm_bce_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, s, pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale, w, merged, gfg, gbg, losses, B, HW);
+  hipLaunchKernelGGL(apm_bce_kernel, dim3(B), dim3(APM_THREADS), 0, s, pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale, w, merged, gfg, gbg, losses, B, HW);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
