@@ -399,6 +399,48 @@ size_t ucod_vit_split_stream_offset_mlp(const ucod_vit_desc* d, int terms, int m
 int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int mlp, const void* const* table_host, const float* img, float* key_out,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ the split-operand pass on fp16 TERMS ("split2h"; csrc/split16.hip)
+ * The same three fp32 passes of the reference (data/datasets/base_dataset.py:124-138, generate_pseudo_label.py:71-89, data/datasets/lr_dataset.py:97-157; arithmetic
+ * modeling_dinov2.py:38-149,153-235,238-297,300-315,342-381) with every f32 operand v as TWO IEEE fp16 terms of a power-of-two multiple of it,
+ *   hi = fp16(s v),  lo = fp16(s v - hi):   |v - (hi + lo) / s| <= max(2^-22 |v|, 2^-25 / s),
+ * and every product as the three partial products hi hi + hi lo + lo hi on the fp16 MFMA: 22 significand bits per operand at the matrix work of the two-term bf16
+ * form (16 bits), half that of the three-term one (24 bits).  An [M, K] operand is fp16 [M, 3 K]: role 0 (A side) hi | hi | lo, role 1 (B side) hi | lo | hi; the
+ * GEMMs are ucod_gemm_bf16 of libucod_dpl_f16.so with K' = 3 K, whose accumulator then holds s_a s_b times the product (csrc/split16.hip says how the factor
+ * leaves through the existing epilogues' bias / scale arguments, exactly).  `scale` arguments must be powers of two (UCOD_EINVAL otherwise).  |s v| > 65504 is
+ * clamped and COUNTED into the saturation counter of the fp16 stream (ucod_resid16_overflow_*).  libucod_dpl_f16.so only; the bf16 build returns UCOD_EINVAL
+ * (and the fp16 build keeps refusing ucod_split_* / ucod_vit_forward_split*). */
+enum { UCOD_SPLIT16_LN = 0, UCOD_SPLIT16_QKV = 1, UCOD_SPLIT16_PROB = 2, UCOD_SPLIT16_ATT = 3, UCOD_SPLIT16_HIDDEN = 4, UCOD_SPLIT16_PATCH = 5, UCOD_SPLIT16_NUM_CLASSES = 6 };
+/* the scale the pass gives an activation operand class (LayerNorm output, q / k / v, probabilities, attention output, MLP hidden, patches); 0 for an unknown class */
+float ucod_split16_class_scale(int cls);
+/* f32 [M, K] (row pitch ld_in elements) -> fp16 [M, 3 K] of scale * f(in); op 0: f = identity, 1: exact-erf GELU of alpha * in, 2: alpha * in, 3: SwiGLU of alpha *
+ * rows 2 K wide interleaved as for UCOD_EPI_BIAS_SWIGLU_BF16.  K % 8 == 0, ld_in % 4 == 0 */
+int ucod_split16_rows(const float* in, long ld_in, void* out_f16, int M, int K, int role, int op, float alpha, float scale, void* stream);
+/* nn.LayerNorm (two-pass f32) of f32 rows times `scale`, as a split operand fp16 [rows, 3 D].  D / 128 in {1, 2, 3, 4, 5, 6, 8, 10, 12} */
+int ucod_split16_layernorm(const float* x, const float* gamma, const float* beta, void* out_f16, int rows, int D, float eps, int role, float scale, void* stream);
+/* ucod_patch_im2col with split output: patches fp16 [B gh gw, 3 Kpad] (A side) of scale * pixel */
+int ucod_split16_patch_im2col(const float* img, void* patches_f16, int B, int C, int H, int W, int P, int Kpad, float scale, void* stream);
+/* in place x[i] *= alpha, alpha a power of two (the operand scales leaving the token rows / the key map) */
+int ucod_split16_scale_f32(float* x, size_t n, float alpha, void* stream);
+/* f32 qkv [B tok, 3 heads 64] times in_mul -> the attention kernel's operands (ucod_split16_attention_operand_bytes): Qc | Kc fp16 [B heads][tok_pad][2 64]
+ * (hi | lo; Q times qscale), Vt fp16 [2][B heads][64][tok_pad]; every value times `scale` before its split; tok_pad = tok rounded up to 32, pad rows zero */
+size_t ucod_split16_attention_operand_bytes(int B, int tok, int heads);
+int ucod_split16_qkv(const float* qkv, void* operands, int B, int tok, int heads, float in_mul, float qscale, float scale, void* stream);
+/* softmax(Q K^T) V (modeling_dinov2.py:153-179; the softmax scale and log2 e are inside Q) on those operands (`scale` = the one ucod_split16_qkv was given), f32
+ * online softmax, probabilities times 2^14 as two fp16 terms.  out fp16 [B tok, 3 heads 64]: out_scale times the result as the A-side operand of the out-projection */
+int ucod_split16_attention_fwd(const void* operands, void* out_split_f16, int B, int tok, int heads, float scale, float out_scale, void* stream);
+/* out2_dev[0] = 2^-24 (the smallest fp16 subnormal) times 2^14 and out2_dev[1] = 2^-14 (the smallest normal) times 2^14, each as one v_mfma_f32_32x32x16_f16:
+ * 2^-10 / 1 if the matrix pipe keeps subnormal fp16 inputs, 0 / 1 if it flushes them */
+int ucod_split16_mfma_subnormal_probe(float* out2_dev, void* stream);
+/* The whole key-minimal pass (as ucod_vit_forward_split_mlp).  Table as there with fp16 split weights, each scaled by wscale_host[...] (1 + 4 L powers of two: patch_w,
+ * then per layer qkv_w (also the +14 key rows), proj_w, fc1_w, fc2_w), and with the f32 vectors of a GEMM carrying its operand scales S = s_act s_w:
+ *   +1 patch_b, +2 cls, +3 pos times S_patch;  +3 qkv_b times S_qkv;  +5 proj_b times S_proj, +6 LayerScale 1 / S_proj;  +10 fc1_b times S_fc1;
+ *   +12 fc2_b times S_fc2, +13 LayerScale 2 / S_fc2       (s_act = ucod_split16_class_scale of PATCH, LN, ATT, LN, HIDDEN)
+ * No allocation, no synchronisation.  ucod_vit_split16_stream_offset: as ucod_vit_split_stream_offset. */
+size_t ucod_vit_split16_workspace_bytes(const ucod_vit_desc* d, int mlp);
+size_t ucod_vit_split16_stream_offset(const ucod_vit_desc* d, int mlp);
+int ucod_vit_forward_split16(const ucod_vit_desc* d, int mlp, const void* const* table_host, const float* wscale_host, int n_wscale, const float* img, float* key_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backbone-backward mode, whole passes (row B9; operand formats in ucod_dpl_amd/csrc/vit_train.hip).
  * T = the table of ucod_vit_forward; TT = per-layer training table (HOST array of DEVICE pointers), layer l at
  * UCOD_VIT_TRAIN_STRIDE*l:

@@ -18,6 +18,7 @@ For every class: the logit max-abs error against the all-f32 forward with ONLY t
 ("all but").  The decoder runs in f32 (its device form is f32-equivalent: gemm_split.hip).  Output: one JSON object per line + a table.
 
     python tools/error_budget.py [--half f16|bf16] [--images 2] [--out profiles/r06_error_budget.json]
+    python tools/error_budget.py --half f16 --terms 2 --scaled      # the fp16-term split pass ("split2h"): two fp16 terms of a power-of-two multiple
 """
 import argparse
 import json
@@ -36,20 +37,29 @@ from ucod_dpl_amd.data.utils.feature_extractor import trained_like_state_dict, r
 CLASSES = ("patch", "stream", "qkv", "qk", "pv", "proj", "fc1", "fc2", "key")
 
 
-def split_round(t, dtype, terms):
-    """t as the sum of `terms` values of `dtype` (hi + lo [+ lo2]): what the split-operand kernels multiply by."""
+def split_round(t, dtype, terms, scale_top=None):
+    """t as the sum of `terms` values of `dtype` (hi + lo [+ lo2]): what the split-operand kernels multiply by.  With scale_top (--scaled: 14) the operand is first multiplied by
+    the power of two that puts its largest magnitude into [2^13, 2^14) (the per-tensor rule of the fp16-term pass's weights; its activations use fixed class
+    scales chosen for range, which cost more only for values far below their class's typical magnitude) and the sum divided by it again: fp16's subnormal floor
+    2^-25 then sits 2^-39 below the largest element."""
+    if scale_top is not None:
+        m = float(t.abs().max())
+        s = 2.0 ** (scale_top - math.frexp(m)[1]) if m > 0 else 1.0
+        t = t * s
+    else:
+        s = 1.0
     out = torch.zeros_like(t)
     rest = t
     for _ in range(terms):
         part = rest.to(dtype).float()
         out = out + part
         rest = rest - part
-    return out
+    return out / s
 
 
-def forward(img, sd, heads, on, dtype, patch=14, eps=1e-6, terms=1):
+def forward(img, sd, heads, on, dtype, patch=14, eps=1e-6, terms=1, scale_top=None):
     """Device-like forward: `on` = set of classes whose rounding points are active; terms > 1 = split operands (hi + lo ...)."""
-    r = lambda c: ((lambda t: split_round(t, dtype, terms)) if c in on else (lambda t: t))  # noqa: E731
+    r = lambda c: ((lambda t: split_round(t, dtype, terms, scale_top)) if c in on else (lambda t: t))  # noqa: E731
     rs = (lambda t: t.to(torch.float16).float()) if "stream" in on else (lambda t: t)
     B, _, H, W = img.shape
     pre = "embeddings."
@@ -92,10 +102,13 @@ def main():
     ap.add_argument("--images", type=int, default=2)
     ap.add_argument("--weights", default="trained_like", choices=["trained_like", "flat"])
     ap.add_argument("--terms", type=int, default=1, help="operands as a sum of this many 16-bit values (split-operand kernels)")
+    ap.add_argument("--scaled", action="store_true", help="power-of-two operand scales in front of the split (the fp16-term pass: --half f16 --terms 2 --scaled)")
+    ap.add_argument("--only-all", action="store_true", help="only the case with every class rounded")
     ap.add_argument("--sets", default="", help="extra class sets to evaluate, e.g. 'qk+pv,qkv+qk' (rounded classes)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dtype = torch.float16 if a.half == "f16" else torch.bfloat16
+    scale_top = 14 if a.scaled else None
     arch = "dinov2_vitb14"
     D, heads, L, P, _, _ = ARCHS[arch]
     sd = (trained_like_state_dict if a.weights == "trained_like" else random_state_dict)(arch, 0, 518)
@@ -115,18 +128,18 @@ def main():
         print(f"# restated forward vs oracle (no rounding): logit max-abs {base:.2e}; one forward {time.time() - t0:.0f} s", flush=True)
 
         def run(name, on, terms=a.terms):
-            key = forward(img, sd, heads, set(on), dtype, terms=terms)
+            key = forward(img, sd, heads, set(on), dtype, terms=terms, scale_top=scale_top)
             fg = logits(key)
-            row = dict(case=name, rounded=sorted(on), half=a.half, terms=terms, weights=a.weights, logit_max_abs=float((fg - fg0).abs().max()),
+            row = dict(case=name, rounded=sorted(on), half=a.half, terms=terms, scaled=bool(a.scaled), weights=a.weights, logit_max_abs=float((fg - fg0).abs().max()),
                        key_rel_l2=float(((key - key_ref).double().norm() / key_ref.double().norm())),
                        mask_flipped_fraction=float(((fg > 0) != (fg0 > 0)).float().mean()), ref_logit_abs_max=float(fg0.abs().max()))
             rows.append(row)
             print(json.dumps(row), flush=True)
 
         run("all", CLASSES)
-        for c in CLASSES:
+        for c in () if a.only_all else CLASSES:
             run(f"alone:{c}", (c,))
-        for c in CLASSES:
+        for c in () if a.only_all else CLASSES:
             run(f"all_but:{c}", tuple(x for x in CLASSES if x != c))
         for s in filter(None, a.sets.split(",")):
             run(f"set:{s}", tuple(s.split("+")))

@@ -59,6 +59,8 @@ class DiscGrads(C.Structure):
 
 
 UCOD_MLP_GELU, UCOD_MLP_SWIGLU = 0, 1        # MLP kind of the _mlp backbone entry points (include/ucod_dpl.h)
+# activation operand classes of the fp16-term split pass (ucod_split16_class_scale)
+SPLIT16_LN, SPLIT16_QKV, SPLIT16_PROB, SPLIT16_ATT, SPLIT16_HIDDEN, SPLIT16_PATCH = range(6)
 
 # name -> (restype, argtypes); must list EVERY symbol include/ucod_dpl.h declares (tests/test_abi.py checks)
 SIGNATURES = {
@@ -83,6 +85,19 @@ SIGNATURES = {
     "ucod_vit_split_workspace_bytes_mlp": (sz, [C.POINTER(VitDesc), ci, ci]),
     "ucod_vit_split_stream_offset_mlp": (sz, [C.POINTER(VitDesc), ci, ci]),
     "ucod_vit_forward_split_mlp": (ci, [C.POINTER(VitDesc), ci, ci, C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # the split-operand pass on fp16 terms ("split2h", csrc/split16.hip): libucod_dpl_f16.so; the bf16 build returns UCOD_EINVAL
+    "ucod_split16_class_scale": (cf, [ci]),
+    "ucod_split16_rows": (ci, [vp, C.c_long, vp, ci, ci, ci, ci, cf, cf, vp]),
+    "ucod_split16_layernorm": (ci, [vp, vp, vp, vp, ci, ci, cf, ci, cf, vp]),
+    "ucod_split16_patch_im2col": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
+    "ucod_split16_scale_f32": (ci, [vp, sz, cf, vp]),
+    "ucod_split16_attention_operand_bytes": (sz, [ci, ci, ci]),
+    "ucod_split16_qkv": (ci, [vp, vp, ci, ci, ci, cf, cf, cf, vp]),
+    "ucod_split16_attention_fwd": (ci, [vp, vp, ci, ci, ci, cf, cf, vp]),
+    "ucod_split16_mfma_subnormal_probe": (ci, [vp, vp]),
+    "ucod_vit_split16_workspace_bytes": (sz, [C.POINTER(VitDesc), ci]),
+    "ucod_vit_split16_stream_offset": (sz, [C.POINTER(VitDesc), ci]),
+    "ucod_vit_forward_split16": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),

@@ -64,37 +64,112 @@ def split_products(terms):
     return n
 
 
-def split_rows(x, terms, role, op=0, alpha=1.0):
+def _term16(term, terms):
+    """True for the fp16-term form ("split2h", csrc/split16.hip: two terms, three products, libucod_dpl_f16.so), False for the bf16-term form of csrc/split.hip."""
+    if term not in ("bf16", "f16"):
+        raise ValueError(f"term must be 'bf16' or 'f16', got {term!r}")
+    if term == "f16" and int(terms) != 2:
+        raise ValueError(f"term='f16' is the two-term form (terms=2), got terms={terms!r}")
+    return term == "f16"
+
+
+def pow2_scale(t, top=14):
+    """The power of two s with max |s t| in [2^(top-1), 2^top): the per-tensor scale of an fp16-term operand (1.0 for an all-zero tensor)."""
+    import math
+    m = float(t.detach().abs().max())
+    if not (m > 0.0 and math.isfinite(m)):
+        return 1.0
+    return 2.0 ** (top - math.frexp(m)[1])
+
+
+def split16_class_scale(cls):
+    s = float(N.load("f16").ucod_split16_class_scale(int(cls)))
+    if s == 0.0:
+        raise ValueError(f"unknown operand class {cls}")
+    return s
+
+
+def _gemm_f16(epilogue, A, Bm, out, M, Nn, K, bias=None, scale=None, resid=None, pos=None, tok=0, variant=0):
+    """ucod_gemm_bf16 of the fp16-operand library (the GEMMs of the fp16-term split pass)."""
+    if A.dtype != torch.float16 or Bm.dtype != torch.float16:
+        raise TypeError(f"expected float16 operands, got {A.dtype} / {Bm.dtype}")
+    if variant not in N.GEMM_PRODUCT_VARIANTS:
+        raise ValueError(f"variant must be one of {N.GEMM_PRODUCT_VARIANTS}")
+    check(N.load("f16").ucod_gemm_bf16(epilogue, ptr(A), ptr(Bm), ptr(out), M, Nn, K, ptr(bias), ptr(scale), ptr(resid), ptr(pos), tok, variant, stream()), "ucod_gemm_bf16 (f16)")
+    return out
+
+
+def split_rows(x, terms, role, op=0, alpha=1.0, term="bf16", scale=1.0):
     """x f32 [M,K] (rows may be strided) -> bf16 [M, P K]: segment p holds term {0,0,1,1,0,2}[p] (role 0, the A side) / {0,1,0,1,2,0}[p] (role 1, the B side)
-    of x = x0 + x1 (+ x2).  op 1: exact-erf GELU of x first; op 2: x * alpha first."""
+    of x = x0 + x1 (+ x2).  op 1: exact-erf GELU of x first; op 2: x * alpha first.
+    ``term="f16"`` (terms = 2): fp16 [M, 3 K] = hi | hi | lo (role 0) / hi | lo | hi (role 1) of ``scale`` * f(x), ``scale`` a power of two (csrc/split16.hip; op 1 and
+    op 3 apply ``alpha`` to their argument too); values with |scale * f| > 65504 are clamped and counted (ucod_resid16_overflow_*)."""
+    f16 = _term16(term, terms)
     _f32(x)
     if x.dim() != 2 or x.stride(1) != 1:
         raise ValueError("split_rows takes a 2-d tensor with contiguous rows")
     if not x.is_cuda:
         raise RuntimeError("ucod_dpl_amd: tensor is not on a GPU; the HIP path has no CPU fallback")
     M, K = x.shape
+    if f16:
+        if op == 3:
+            K //= 2
+        out = torch.empty(M, 3 * K, dtype=torch.float16, device=x.device)
+        check(N.load("f16").ucod_split16_rows(x.data_ptr(), x.stride(0), ptr(out), M, K, int(role), int(op), float(alpha), float(scale), stream()), "ucod_split16_rows")
+        return out
+    if scale != 1.0:
+        raise ValueError("scale belongs to term='f16'")
     out = torch.empty(M, split_products(terms) * K, dtype=torch.bfloat16, device=x.device)
     check(N.load().ucod_split_rows(x.data_ptr(), x.stride(0), ptr(out), M, K, int(terms), int(role), int(op), float(alpha), stream()), "ucod_split_rows")
     return out
 
 
-def linear_split(x, w, b, terms, variant=0):
-    """f32-equivalent x w^T + b on the bf16 matrix pipe: x f32 [M,K], w f32 [N,K], b f32 [N] -> f32 [M,N] (ucod_gemm_bf16 over the K-concatenated split operands)."""
+def linear_split(x, w, b, terms, variant=0, term="bf16", x_scale=None, w_scale=None):
+    """f32-equivalent x w^T + b on the bf16 matrix pipe: x f32 [M,K], w f32 [N,K], b f32 [N] -> f32 [M,N] (ucod_gemm_bf16 over the K-concatenated split operands).
+    ``term="f16"``: the same on two fp16 terms per operand; ``x_scale`` / ``w_scale`` default to the per-tensor power of two that puts the largest magnitude in
+    [2^13, 2^14).  The accumulator holds x_scale w_scale times the product: the bias goes in times that factor and one exact in-place pass takes it out."""
     M, K = x.shape
+    if _term16(term, terms):
+        sx = pow2_scale(x) if x_scale is None else float(x_scale)
+        sw = pow2_scale(w) if w_scale is None else float(w_scale)
+        out = torch.empty(M, w.shape[0], dtype=torch.float32, device=x.device)
+        _gemm_f16(N.EPI_BIAS_F32, split_rows(x, 2, 0, term="f16", scale=sx), split_rows(w, 2, 1, term="f16", scale=sw), out, M, w.shape[0], 3 * K,
+                  bias=(_f32(b) * (sx * sw)).contiguous(), variant=variant)
+        check(N.load("f16").ucod_split16_scale_f32(ptr(out), out.numel(), 1.0 / (sx * sw), stream()), "ucod_split16_scale_f32")
+        return out
     P = split_products(terms)
     out = torch.empty(M, w.shape[0], dtype=torch.float32, device=x.device)
     return gemm_bf16(N.EPI_BIAS_F32, split_rows(x, terms, 0), split_rows(w, terms, 1), out, M, w.shape[0], P * K, bias=_f32(b), variant=variant)
 
 
-def layernorm_split(x, gamma, beta, eps, terms, role=0):
+def layernorm_split(x, gamma, beta, eps, terms, role=0, term="bf16", scale=None):
+    """``term="f16"``: fp16 [rows, 3 D] of ``scale`` (default: the pass's LayerNorm class scale) times the LayerNorm output."""
     rows, D = x.shape
+    if _term16(term, terms):
+        scale = split16_class_scale(N.SPLIT16_LN) if scale is None else float(scale)
+        out = torch.empty(rows, 3 * D, dtype=torch.float16, device=x.device)
+        check(N.load("f16").ucod_split16_layernorm(ptr(_f32(x)), ptr(_f32(gamma)), ptr(_f32(beta)), ptr(out), rows, D, float(eps), int(role), scale, stream()),
+              "ucod_split16_layernorm")
+        return out
     out = torch.empty(rows, split_products(terms) * D, dtype=torch.bfloat16, device=x.device)
     check(N.load().ucod_layernorm_split(ptr(_f32(x)), ptr(_f32(gamma)), ptr(_f32(beta)), ptr(out), rows, D, float(eps), int(terms), int(role), stream()), "ucod_layernorm_split")
     return out
 
 
-def attention_split(qkv, B, tok, heads, terms, qscale=0.125 * 1.4426950408889634):
-    """qkv f32 [B*tok, 3*heads*64] -> the attention output as the A-side split operand bf16 [B*tok, P*heads*64] (softmax(Q K^T / 8) V, f32-equivalent)."""
+def attention_split(qkv, B, tok, heads, terms, qscale=0.125 * 1.4426950408889634, term="bf16", in_mul=1.0):
+    """qkv f32 [B*tok, 3*heads*64] -> the attention output as the A-side split operand bf16 [B*tok, P*heads*64] (softmax(Q K^T / 8) V, f32-equivalent).
+    ``term="f16"``: fp16 [B*tok, 3*heads*64] carrying the pass's attention-output class scale; ``in_mul`` (a power of two) multiplies qkv as it is read."""
+    if _term16(term, terms):
+        lib = N.load("f16")
+        need = lib.ucod_split16_attention_operand_bytes(B, tok, heads)
+        if need == 0:
+            raise ValueError("unsupported attention geometry")
+        opnd = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+        out = torch.empty(B * tok, 3 * heads * 64, dtype=torch.float16, device=qkv.device)
+        s_qkv, s_att = split16_class_scale(N.SPLIT16_QKV), split16_class_scale(N.SPLIT16_ATT)
+        check(lib.ucod_split16_qkv(ptr(_f32(qkv)), ptr(opnd), B, tok, heads, float(in_mul), float(qscale), s_qkv, stream()), "ucod_split16_qkv")
+        check(lib.ucod_split16_attention_fwd(ptr(opnd), ptr(out), B, tok, heads, s_qkv, s_att, stream()), "ucod_split16_attention_fwd")
+        return out
     lib = N.load()
     need = lib.ucod_attention_split_operand_bytes(B, tok, heads, int(terms))
     if need == 0:
@@ -106,8 +181,12 @@ def attention_split(qkv, B, tok, heads, terms, qscale=0.125 * 1.4426950408889634
     return out
 
 
-def unsplit(xs, terms, role, K):
-    """The f32 value a split operand [M, P K] stands for (sum of its distinct terms): test helper, torch arithmetic on the device."""
+def unsplit(xs, terms, role, K, term="bf16", scale=1.0):
+    """The f32 value a split operand [M, P K] stands for (sum of its distinct terms): test helper, torch arithmetic on the device.
+    ``term="f16"``: (hi + lo) / scale of an fp16-term operand (the sum rounded to f32; the division by a power of two is exact)."""
+    if _term16(term, terms):
+        seg = xs.view(xs.shape[0], 3, K).float()
+        return (seg[:, 0] + seg[:, 2 if role == 0 else 1]) / float(scale)
     P = split_products(terms)
     seg = xs.view(xs.shape[0], P, K).float()
     order = ([0, 0, 1, 1, 0, 2] if role == 0 else [0, 1, 0, 1, 2, 0])[:P]

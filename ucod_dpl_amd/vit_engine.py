@@ -291,14 +291,26 @@ class ViTEngine:
     def check_overflow(self, wait=False):
         """Raise FloatingPointError if any finished pass saturated the fp16 residual stream.  ``wait``: block until every pass enqueued so far
         has finished (otherwise only passes that already have)."""
-        if self._ovf_host is None:                              # no pass of this engine has used the fp16 stream
-            return
+        n = self._take_overflow_count(wait)
+        if n > 0:
+            how = "build the engine with resid='f32'" if self.resid16 else "call forward_nograd(..., resid16=False)"
+            raise FloatingPointError(f"the fp16 residual stream of this engine saturated at +-65504 (or met a NaN) in {n} wave-lane(s)"
+                                     + (" -- or a folded LayerNorm met a row with |mean| > 256 sigma (outside the fold's range)" if getattr(self, "ln_fold", False) else "")
+                                     + f": the activations do not fit this configuration; {how}.  The counter is polled without blocking: the pass (or, for a training engine, the "
+                                     f"optimiser step or steps) that consumed the clamped activations has already been applied -- discard its results "
+                                     f"(UCOD_CHECK_RESID=1 checks synchronously after every pass).")
+
+    def _take_overflow_count(self, wait=False):
+        """The saturation count of the passes that have finished (``wait``: of every pass enqueued so far).  A non-zero count is handed out ONCE: the device word
+        and its host copy are cleared before it is returned."""
+        if self._ovf_host is None:                              # no pass of this engine has counted anything
+            return 0
         if wait:
             for ev in self._ovf_events:
                 ev.synchronize()
             self._ovf_events = []
         elif not any(ev.query() for ev in self._ovf_events):
-            return
+            return 0
         n = int(self._ovf_host[0])
         if n > 0:
             # before the reset: every fetch still queued on a side stream must have landed, or its (stale, non-zero) count would arrive
@@ -310,12 +322,7 @@ class ViTEngine:
                 N.check(self.lib.ucod_resid16_overflow_reset(N.stream()), "ucod_resid16_overflow_reset")
             torch.cuda.current_stream(self.device).synchronize()
             self._ovf_host.zero_()
-            how = "build the engine with resid='f32'" if self.resid16 else "call forward_nograd(..., resid16=False)"
-            raise FloatingPointError(f"the fp16 residual stream of this engine saturated at +-65504 (or met a NaN) in {n} wave-lane(s)"
-                                     + (" -- or a folded LayerNorm met a row with |mean| > 256 sigma (outside the fold's range)" if getattr(self, "ln_fold", False) else "")
-                                     + f": the activations do not fit this configuration; {how}.  The counter is polled without blocking: the pass (or, for a training engine, the "
-                                     f"optimiser step or steps) that consumed the clamped activations has already been applied -- discard its results "
-                                     f"(UCOD_CHECK_RESID=1 checks synchronously after every pass).")
+        return n
 
     _sync_check = os.environ.get("UCOD_CHECK_RESID") == "1"    # debug: check the saturation counter synchronously after every pass
 
@@ -437,11 +444,20 @@ class SplitViTEngine:
 
     Same call interface as ``ViTEngine`` (``forward`` / ``forward_async`` / ``__call__``, ``D``, ``P``, ``streams``); key-minimal pass only."""
 
-    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0):
+    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0, term="bf16"):
+        """``term="f16"`` (with ``terms=2``; precision name "split2h"): the two terms of every operand are IEEE fp16 values of a power-of-two multiple of it and the three
+        partial products run on the fp16 MFMA (csrc/split16.hip, libucod_dpl_f16.so) -- 22 significand bits per operand at the matrix work of ``terms=2``.  Weights are
+        scaled per tensor at load (largest magnitude into [2^13, 2^14)), activations per operand class (``ops.split16_class_scale``); a value beyond fp16's range
+        is clamped and counted on the device, and ``check_overflow`` raises for a pass that met one."""
         if terms not in (2, 3):
             raise ValueError(f"terms must be 2 or 3, got {terms!r}")
-        self.terms, self.half = int(terms), f"bf16x{int(terms)}"
-        self.lib = N.load("bf16")                                 # (bf16 MFMA; the fp16 build refuses the split entry points)
+        if term not in ("bf16", "f16"):
+            raise ValueError(f"term must be 'bf16' or 'f16', got {term!r}")
+        if term == "f16" and terms != 2:
+            raise ValueError(f"term='f16' is the two-term form: terms must be 2, got {terms!r}")
+        self.terms, self.term, self.half = int(terms), term, f"{term}x{int(terms)}"
+        f16 = term == "f16"
+        self.lib = N.load("f16" if f16 else "bf16")               # (each term type has its MFMA; either build refuses the other's split entry points)
         self.nprod = ops.split_products(terms)
         self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
         self.kind, self.device = c["kind"], torch.device(device)
@@ -453,38 +469,77 @@ class SplitViTEngine:
         self.gemm_variant, self.streams = gemm_variant, 1
         self.resid16 = self.ln_fold = self.full_last_layer = False
         self.resid, self.attn_variant = "f32", 0
+        self._ovf_host, self._ovf_events, self._ovf_dev = None, [], None
         K = self.C * self.P * self.P
         self.Kpad = (K + 63) // 64 * 64
         dev = self.device
         f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        sw = lambda t, role=1: ops.split_rows(f32(t), self.terms, role)  # noqa: E731      (weights: the B side of y = x W^T)
         pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=dev)
         pw[:, :K] = f32(c["patch_w"]).reshape(self.D, K)
         self._pos_src, self._pos_cache = c["pos"].detach().float().cpu(), {}
-        self.patch_w, self.patch_b, self.cls = sw(pw), f32(c["patch_b"]), f32(c["cls"])
         ones = torch.ones(self.D, dtype=torch.float32, device=dev)
         self.layers = []
         D = self.D
-        for l in c["layers"]:
-            self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), sw(l["qkv_w"]), f32(l["qkv_b"]), sw(l["proj_w"]), f32(l["proj_b"]),
-                                f32(l["ls1"]) if l["ls1"] is not None else ones, f32(l["ln2_g"]), f32(l["ln2_b"]), sw(l["fc1_w"]),
-                                f32(l["fc1_b"]), sw(l["fc2_w"]), f32(l["fc2_b"]), f32(l["ls2"]) if l["ls2"] is not None else ones,
-                                sw(l["qkv_w"][D:2 * D], role=0), None])      # +14: the K rows as the A side of the key hook's GEMM
+        if f16:
+            # S = (activation class scale) x (weight scale) of each GEMM: its bias (and, for the patch embedding, the CLS and position rows) goes in times S, its
+            # LayerScale vector divided by S -- powers of two, so the stream is bit for bit what the unscaled product would give (csrc/split16.hip)
+            cls_s = {k: ops.split16_class_scale(getattr(N, "SPLIT16_" + k)) for k in ("LN", "ATT", "HIDDEN", "PATCH")}
+            sw16 = lambda t, s, role=1: ops.split_rows(f32(t), 2, role, term="f16", scale=s)  # noqa: E731
+            s_pw = ops.pow2_scale(pw)
+            self._S_patch = cls_s["PATCH"] * s_pw
+            self.wscale = [s_pw]
+            self.patch_w, self.patch_b, self.cls = sw16(pw, s_pw), f32(c["patch_b"]) * self._S_patch, f32(c["cls"]) * self._S_patch
+            for l in c["layers"]:
+                s_qkv, s_proj, s_fc1, s_fc2 = (ops.pow2_scale(l[k]) for k in ("qkv_w", "proj_w", "fc1_w", "fc2_w"))
+                S_qkv, S_proj, S_fc1, S_fc2 = cls_s["LN"] * s_qkv, cls_s["ATT"] * s_proj, cls_s["LN"] * s_fc1, cls_s["HIDDEN"] * s_fc2
+                self.wscale += [s_qkv, s_proj, s_fc1, s_fc2]
+                ls1 = f32(l["ls1"]) if l["ls1"] is not None else ones
+                ls2 = f32(l["ls2"]) if l["ls2"] is not None else ones
+                self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), sw16(l["qkv_w"], s_qkv), f32(l["qkv_b"]) * S_qkv, sw16(l["proj_w"], s_proj), f32(l["proj_b"]) * S_proj,
+                                    ls1 / S_proj, f32(l["ln2_g"]), f32(l["ln2_b"]), sw16(l["fc1_w"], s_fc1), f32(l["fc1_b"]) * S_fc1, sw16(l["fc2_w"], s_fc2),
+                                    f32(l["fc2_b"]) * S_fc2, ls2 / S_fc2, sw16(l["qkv_w"][D:2 * D], s_qkv, role=0), None])
+            self._wscale_c = (C.c_float * len(self.wscale))(*self.wscale)
+        else:
+            sw = lambda t, role=1: ops.split_rows(f32(t), self.terms, role)  # noqa: E731      (weights: the B side of y = x W^T)
+            self.patch_w, self.patch_b, self.cls = sw(pw), f32(c["patch_b"]), f32(c["cls"])
+            for l in c["layers"]:
+                self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), sw(l["qkv_w"]), f32(l["qkv_b"]), sw(l["proj_w"]), f32(l["proj_b"]),
+                                    f32(l["ls1"]) if l["ls1"] is not None else ones, f32(l["ln2_g"]), f32(l["ln2_b"]), sw(l["fc1_w"]),
+                                    f32(l["fc1_b"]), sw(l["fc2_w"]), f32(l["fc2_b"]), f32(l["ls2"]) if l["ls2"] is not None else ones,
+                                    sw(l["qkv_w"][D:2 * D], role=0), None])      # +14: the K rows as the A side of the key hook's GEMM
         last = c["layers"][-1]                                   # f32 copies for forward_with_cls_attention: the CLS query / key of the LAST layer
         self._last = dict(ln_g=f32(last["ln1_g"]), ln_b=f32(last["ln1_b"]), wq=f32(last["qkv_w"][:D]), bq=f32(last["qkv_b"][:D]),
                           wk=f32(last["qkv_w"][D:2 * D]), bk=f32(last["qkv_b"][D:2 * D]))
         self._ws = None
         self._side = self._side_ws = None
 
-    _pos = ViTEngine._pos
     _desc = ViTEngine._desc
+    _own_counter = ViTEngine._own_counter
+    _arm_overflow_check = ViTEngine._arm_overflow_check
+
+    def _pos(self, gh, gw):
+        """(fp16 terms: the position rows times the patch embedding's operand scales, like its bias)"""
+        key = (gh, gw)
+        if key not in self._pos_cache:
+            pos = ViTEngine._pos(self, gh, gw)
+            self._pos_cache[key] = pos * self._S_patch if self.term == "f16" else pos
+        return self._pos_cache[key]
 
     def param_bytes(self):
         return self.patch_w.numel() * 2 + sum(t.numel() * t.element_size() for l in self.layers for t in l if t is not None)
 
     def check_overflow(self, wait=False):
-        """(interface of ViTEngine: the f32 stream has nothing to saturate)"""
-        return None
+        """bf16 terms: nothing can saturate (bf16 has f32's range; interface of ViTEngine).  fp16 terms: raise FloatingPointError if a finished pass clamped an
+        operand to +-65504 (or met a NaN) -- its key map is wrong and must be discarded.  ``wait``: block until every pass enqueued so far has finished."""
+        if self.term != "f16":
+            return None
+        n = self._take_overflow_count(wait)
+        if n > 0:
+            raise FloatingPointError(f"the fp16-term split pass (split2h) clamped {n} operand element(s) to +-65504 (or met a NaN): an activation exceeded the bound of its "
+                                     f"operand class (csrc/split16.hip) and the key maps of that pass are wrong -- use precision='split3' ('f32eq') for this checkpoint / "
+                                     f"input.  The counter is polled without blocking; check_overflow(wait=True) checks every pass enqueued so far.")
+
+    _take_overflow_count = ViTEngine._take_overflow_count
 
     def _table(self, gh, gw):
         ptrs = [self.patch_w, self.patch_b, self.cls, self._pos(gh, gw)]
@@ -492,17 +547,35 @@ class SplitViTEngine:
             ptrs += l
         return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), ptrs
 
+    def _ws_bytes(self, d):
+        if self.term == "f16":
+            return self.lib.ucod_vit_split16_workspace_bytes(C.byref(d), self.mlp)
+        return self.lib.ucod_vit_split_workspace_bytes_mlp(C.byref(d), self.terms, self.mlp)
+
+    def _stream_offset(self, d):
+        if self.term == "f16":
+            return self.lib.ucod_vit_split16_stream_offset(C.byref(d), self.mlp)
+        return self.lib.ucod_vit_split_stream_offset_mlp(C.byref(d), self.terms, self.mlp)
+
     def _run(self, img, key, ws_slot, n_layers=None):
         B, _, H, W = img.shape
         d = self._desc(B, H, W, n_layers)
         d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        need = self.lib.ucod_vit_split_workspace_bytes_mlp(C.byref(d), self.terms, self.mlp)
+        need = self._ws_bytes(d)
         if need == 0:
             raise ValueError("unsupported ViT geometry")
         ws = ws_slot[0]
         if ws is None or ws.numel() < need:
             ws = ws_slot[0] = torch.empty(need, dtype=torch.uint8, device=self.device)
         table, _keep = self._table(H // self.P, W // self.P)
+        if self.term == "f16":
+            L = d.L
+            self.check_overflow()                                  # (non-blocking) passes that have finished since the last call
+            with self._own_counter():
+                N.check(self.lib.ucod_vit_forward_split16(C.byref(d), self.mlp, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_forward_split16")
+            self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=True)
+            return
         N.check(self.lib.ucod_vit_forward_split_mlp(C.byref(d), self.terms, self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
                 "ucod_vit_forward_split")
 
@@ -546,13 +619,21 @@ class SplitViTEngine:
         B, _, H, W = img.shape
         d = self._desc(B, H, W)
         d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        off = self.lib.ucod_vit_split_stream_offset_mlp(C.byref(d), self.terms, self.mlp)
+        off = self._stream_offset(d)
         tok = key.shape[-2] * key.shape[-1] + 1
         x = self._ws[0][off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
         L_ = self._last
         h_cls = ops.layernorm(x[:, 0].contiguous(), L_["ln_g"], L_["ln_b"], self.eps, out_f32=True)
-        q = ops.linear_split(h_cls, L_["wq"], L_["bq"], self.terms)
-        k = ops.linear_split(h_cls, L_["wk"], L_["bk"], self.terms)
+        if self.term == "f16":
+            # the scales of the pass itself, known at load: the LayerNorm class scale for the rows, the last layer's QKV weight scale (no device-to-host read here)
+            sc = dict(term="f16", x_scale=ops.split16_class_scale(N.SPLIT16_LN), w_scale=self.wscale[-4])
+            with self._own_counter():
+                q = ops.linear_split(h_cls, L_["wq"], L_["bq"], 2, **sc)
+                k = ops.linear_split(h_cls, L_["wk"], L_["bk"], 2, **sc)
+            self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=True)
+        else:
+            q = ops.linear_split(h_cls, L_["wq"], L_["bq"], self.terms)
+            k = ops.linear_split(h_cls, L_["wk"], L_["bk"], self.terms)
         att = torch.empty(B, self.heads, tok - 1, dtype=torch.float32, device=self.device)
         N.check(self.lib.ucod_cls_attention(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, tok - 1, 0.125, N.stream()), "ucod_cls_attention")
         return key, att
