@@ -114,6 +114,10 @@ enum {
                                         then the SwiGLU of UCOD_EPI_BIAS_SWIGLU_BF16: out fp16 [M, N/2] */
   UCOD_EPI_BIAS_SWIGLU_SPLIT2 = 18,  /* split-operand pass, two terms: out bf16 [M, 3 N/2] = the A-side split operand (segments hi | hi | lo, N/2 apart) of the SwiGLU
                                         of UCOD_EPI_BIAS_SWIGLU_BF16 (modeling_dinov2.py:300-315), SiLU to f32 accuracy.  bf16 library; N % 8 == 0 */
+  UCOD_EPI_BIAS_GELU_SPLIT16 = 19,   /* ucod_split16_gemm_act only (ucod_gemm_bf16 refuses it).  fp16-term split pass: out fp16 [M, 3 N] = the A-side split operand
+                                        (hi | hi | lo) of scale * gelu_exact(alpha * (C + bias[n])), saturation counted.  libucod_dpl_f16.so; N % 8 == 0 */
+  UCOD_EPI_BIAS_SWIGLU_SPLIT16 = 20, /* ucod_split16_gemm_act only.  The same for the SwiGLU of UCOD_EPI_BIAS_SWIGLU_BF16's column layout, SiLU to f32 accuracy: out fp16
+                                        [M, 3 N/2], segments N/2 apart */
   UCOD_EPI_QKV_FP8 = 8               /* QKV projection of the fp8 attention path (BASELINE configs[4]): out = e4m3 bytes
                                         [3 (q|k|v)][Bimg*heads][Npad][64], Npad = tokens rounded up to 64, value = clamp((C + bias[n]) *
                                         scale[n], +-448); N = 3*heads*64, M = Bimg*tokens_per_image; large-tile kernel only */
@@ -440,6 +444,23 @@ size_t ucod_vit_split16_workspace_bytes(const ucod_vit_desc* d, int mlp);
 size_t ucod_vit_split16_stream_offset(const ucod_vit_desc* d, int mlp);
 int ucod_vit_forward_split16(const ucod_vit_desc* d, int mlp, const void* const* table_host, const float* wscale_host, int n_wscale, const float* img, float* key_out,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* fc1 + activation + split in ONE launch: out = the A-side split operand (hi | hi | lo) of scale * f(alpha * (A B^T + bias)), where A [M, K3] and B [N, K3] are
+ * K-concatenated fp16 split operands, bias_scaled [N] is the bias times the operands' scales S = s_a s_w and alpha = 1 / S.  op as ucod_split16_rows: 1 exact-erf GELU
+ * (out fp16 [M, 3 N]), 3 SwiGLU of the interleaved x1 / x2 columns of UCOD_EPI_BIAS_SWIGLU_BF16 (out fp16 [M, 3 N/2], segments N/2 apart); others refused.  The drain
+ * calls the activation and the split of ucod_split16_rows on the same f32 value, so the result equals ucod_gemm_bf16(UCOD_EPI_BIAS_F32) + ucod_split16_rows bit for
+ * bit wherever the two GEMMs sum K in the same order (every tile path of one `variant`; the leftover patches of variants 9 / 10 exist for op 1 only).  Values beyond
+ * +-65504 and NaN are clamped and counted like there.  alpha and scale powers of two, N % 8 == 0, K3 % 64 == 0, M * 3 N * 2 bytes (op 3: M * 3 N) below 2^31;
+ * variant as ucod_gemm_bf16 (0, 1, 2, 12, 9, 10, 13, 14) */
+int ucod_split16_gemm_act(int op, const void* a_f16, const void* b_f16, void* out_f16, int M, int N, int K3, const float* bias_scaled, float alpha, float scale,
+                          int variant, void* stream);
+/* The pass with options.  flags = 0: ucod_vit_forward_split16 launch for launch (the three entry points above are this case).  UCOD_SPLIT16_FUSE_MLP: fc1 runs as ONE
+ * ucod_split16_gemm_act instead of UCOD_EPI_BIAS_F32 + ucod_split16_rows, and the workspace holds no f32 fc1 buffer (M F 4 bytes less, M 2F 4 for SwiGLU).  Unknown
+ * flag bits: UCOD_EINVAL (sizes: 0, offset: (size_t)-1) */
+enum { UCOD_SPLIT16_FUSE_MLP = 1 };
+size_t ucod_vit_split16_workspace_bytes_ex(const ucod_vit_desc* d, int mlp, int flags);
+size_t ucod_vit_split16_stream_offset_ex(const ucod_vit_desc* d, int mlp, int flags);
+int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int flags, const void* const* table_host, const float* wscale_host, int n_wscale, const float* img,
+                                float* key_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backbone-backward mode, whole passes (row B9; operand formats in ucod_dpl_amd/csrc/vit_train.hip).
  * T = the table of ucod_vit_forward; TT = per-layer training table (HOST array of DEVICE pointers), layer l at

@@ -4,6 +4,8 @@
     python tools/gemm_bench.py [variants]          ViT-B shapes, the given variants (default 2,3,4,5,6)
     python tools/gemm_bench.py --swiglu [half]     DINOv2 ViT-g/14's fc1 (weights_in 1536 -> 8192) at 32 x 1370 rows, interleaved A/B of the fused SwiGLU epilogue
                                                    against the GELU epilogue on the same GEMM and against UCOD_EPI_BIAS_F32 + an unfused rows pass (half: bf16 / f16)
+    python tools/gemm_bench.py --split16-fused     fp16-term split pass: interleaved A/B of ucod_split16_gemm_act (fc1 + activation + split in one launch) against the
+                                                   pair it replaces, UCOD_EPI_BIAS_F32 + ucod_split16_rows, at ViT-B's fc1 (GELU) and ViT-g's (SwiGLU), 32 x 1370 rows
 """
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -76,7 +78,62 @@ def swiglu_ab(half="bf16", M=32 * 1370, Nn=8192, K=1536, rounds=7, iters=10):
     return res
 
 
+def split16_fused_ab(op, M, Nn, D, rounds=7, iters=10, variant=0):
+    """Interleaved A/B on the fp16 library, K-concatenated fp16 split operands (K3 = 3 D), every form timed in every round: min and median over the rounds, in us.
+      fused     ucod_split16_gemm_act                       -> fp16 [M, 3 N] (op 1, GELU) / [M, 3 N / 2] (op 3, SwiGLU)
+      f32       UCOD_EPI_BIAS_F32                           -> f32 [M, N]      (the GEMM of the unfused pair alone)
+      rows      ucod_split16_rows on that f32 buffer                           (the row pass alone)
+      f32+rows  the two back to back                                           (what the unfused pass runs per layer)"""
+    dev = "cuda"
+    lib = N.load("f16")
+    g = torch.Generator().manual_seed(Nn)
+    x, w = torch.randn(M, D, generator=g).to(dev), (torch.randn(Nn, D, generator=g) * D ** -0.5).to(dev)
+    s_ln, s_hid, sw = ops.split16_class_scale(N.SPLIT16_LN), ops.split16_class_scale(N.SPLIT16_HIDDEN), ops.pow2_scale(w)
+    S = s_ln * sw
+    xs, ws = ops.split_rows(x, 2, 0, term="f16", scale=s_ln), ops.split_rows(w, 2, 1, term="f16", scale=sw)
+    del x, w
+    b = torch.randn(Nn, generator=g).to(dev) * S
+    Ko = Nn if op == 1 else Nn // 2
+    o32 = torch.empty(M, Nn, device=dev, dtype=torch.float32)
+    osp = torch.empty(M, 3 * Ko, device=dev, dtype=torch.float16)
+    ofu = torch.empty(M, 3 * Ko, device=dev, dtype=torch.float16)
+    fused = lambda: N.check(lib.ucod_split16_gemm_act(op, N.ptr(xs), N.ptr(ws), N.ptr(ofu), M, Nn, 3 * D, N.ptr(b), 1.0 / S, s_hid, variant, N.stream()), "gemm_act")  # noqa: E731
+    f32 = lambda: N.check(lib.ucod_gemm_bf16(N.EPI_BIAS_F32, N.ptr(xs), N.ptr(ws), N.ptr(o32), M, Nn, 3 * D, N.ptr(b), None, None, None, 0, variant, N.stream()), "gemm")  # noqa: E731
+    rows = lambda: N.check(lib.ucod_split16_rows(N.ptr(o32), Nn, N.ptr(osp), M, Ko, 0, op, 1.0 / S, s_hid, N.stream()), "rows")  # noqa: E731
+
+    def pair():
+        f32()
+        rows()
+    forms = {"fused": fused, "f32": f32, "rows": rows, "f32+rows": pair}
+    res = {k: [] for k in forms}
+    for fn in forms.values():
+        fn()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(ofu, osp))
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters): fn()
+            e1.record(); torch.cuda.synchronize()
+            res[k].append(e0.elapsed_time(e1) / iters * 1e3)
+    fl = 2.0 * M * Nn * D
+    print(f"fp16 terms, op {op} ({'GELU' if op == 1 else 'SwiGLU'}), M={M} N={Nn} K={D} x 3 products ({fl / 1e9:.1f} GFLOP algorithmic), {rounds} interleaved rounds x {iters} "
+          f"launches, variant {variant}; fused output bit-identical to the pair's: {same}")
+    for k, t in res.items():
+        t = sorted(t)
+        print(f"  {k:9s} min {t[0]:8.1f} us  median {t[len(t) // 2]:8.1f} us  {fl / (t[0] * 1e-6) / 1e12:6.1f} TF/s algorithmic")
+    med = lambda k: sorted(res[k])[len(res[k]) // 2]  # noqa: E731
+    print(f"  fused / (f32 + rows) = {med('fused') / med('f32+rows'):.3f} (medians)   fused - f32 GEMM alone = {med('fused') - med('f32'):+.1f} us   rows alone = {med('rows'):.1f} us",
+          flush=True)
+    return res
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--split16-fused":
+        split16_fused_ab(1, 32 * 1370, 3072, 768)                # ViT-B/14 fc1 at C2
+        split16_fused_ab(3, 32 * 1370, 8192, 1536)               # ViT-g/14 weights_in
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "--swiglu":
         for half in (sys.argv[2:] or ["bf16", "f16"]):
             swiglu_ab(half)

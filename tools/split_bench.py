@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """The split-operand pass at BASELINE configs[1]'s shape (32 x 1370 tokens, D = 768).
 
-    python tools/split_bench.py [--terms 2|3] [--precision split2|split3|split2h] [--batch 32]      per-kernel times of one precision
-    python tools/split_bench.py --engines split3,split2,split2h --rounds 5 --json out.json         whole-pass images/s, the precisions INTERLEAVED round by round
+    python tools/split_bench.py [--terms 2|3] [--precision split2|split3|split2h|split2hf] [--batch 32]      per-kernel times of one precision
+    python tools/split_bench.py --engines split3,split2,split2h,split2hf --rounds 5 --json out.json         whole-pass images/s, the precisions INTERLEAVED round by round
 
-HIP events around `iters` back-to-back launches of each piece (or whole passes), after a warm-up.  "split2h" is the fp16-term form (csrc/split16.hip)."""
+HIP events around `iters` back-to-back launches of each piece (or whole passes), after a warm-up.  "split2h" is the fp16-term form (csrc/split16.hip), "split2hf" the
+same with fc1 + GELU + split fused into one launch (ucod_split16_gemm_act)."""
 import argparse
 import json
 import os
@@ -18,7 +19,7 @@ from ucod_dpl_amd import native as N, ops  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--terms", type=int, default=2)
-ap.add_argument("--precision", default="", choices=["", "split2", "split3", "split2h"], help="overrides --terms")
+ap.add_argument("--precision", default="", choices=["", "split2", "split3", "split2h", "split2hf"], help="overrides --terms")
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--engines", default="", help="comma-separated precisions: whole-pass images/s of SplitViTEngine on ViT-B/14 at 518 x 518, interleaved")
@@ -27,7 +28,8 @@ ap.add_argument("--json", default="")
 a = ap.parse_args()
 if a.precision:
     a.terms = 3 if a.precision == "split3" else 2
-H16 = a.precision == "split2h"
+H16 = a.precision in ("split2h", "split2hf")
+FUSED = a.precision == "split2hf"
 dev, T, B, tok, heads, D, F = "cuda", a.terms, a.batch, 1370, 12, 768, 3072
 M, P = B * tok, ops.split_products(a.terms)
 g = torch.Generator().manual_seed(0)
@@ -54,7 +56,7 @@ def timed(name, fn, flops=None, nbytes=None):
 def engines_mode():
     from ucod_dpl_amd.vit_engine import SplitViTEngine
     from ucod_dpl_amd.data.utils.feature_extractor import random_state_dict, ARCHS
-    kw = {"split2": dict(terms=2), "split3": dict(terms=3), "split2h": dict(terms=2, term="f16")}
+    kw = {"split2": dict(terms=2), "split3": dict(terms=3), "split2h": dict(terms=2, term="f16"), "split2hf": dict(terms=2, term="f16", fuse_mlp=True)}
     names = [n for n in a.engines.split(",") if n]
     sd = random_state_dict("dinov2_vitb14", 0, 518)
     img = torch.randn(B, 3, 518, 518, generator=g).to(dev)
@@ -105,11 +107,12 @@ if H16:
     need = lib.ucod_split16_attention_operand_bytes(B, tok, heads)
     opnd = torch.empty(need, dtype=torch.uint8, device=dev)
     aout, hs, gs = (torch.empty(M, 3 * n, dtype=torch.float16, device=dev) for n in (D, D, F))
-    print(f"# split-operand pieces, fp16 terms (split2h, P = 3), {B} x {tok} tokens, D = {D}")
+    print(f"# split-operand pieces, fp16 terms ({a.precision}, P = 3), {B} x {tok} tokens, D = {D}")
     timed("layernorm_split16", lambda: N.check(lib.ucod_split16_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hs.data_ptr(), M, D, 1e-6, 0, 64.0, st()), "ln"), nbytes=M * D * (4 + 6))
     timed("qkv_split16", lambda: N.check(lib.ucod_split16_qkv(qkv.data_ptr(), opnd.data_ptr(), B, tok, heads, 1.0, 0.18, 32.0, st()), "qs"), nbytes=M * 3 * D * 4 + need)
     timed("attention_split16_fwd", lambda: N.check(lib.ucod_split16_attention_fwd(opnd.data_ptr(), aout.data_ptr(), B, tok, heads, 32.0, 32.0, st()), "att"), flops=4.0 * B * heads * tok * tok * 64)
-    timed("split16_rows(gelu) fc1 out", lambda: N.check(lib.ucod_split16_rows(f1.data_ptr(), F, gs.data_ptr(), M, F, 0, 1, 1.0, 16.0, st()), "sg"), nbytes=M * F * (4 + 6))
+    if not FUSED:                                               # (split2hf has no row pass behind fc1: see the fused GEMM row below)
+        timed("split16_rows(gelu) fc1 out", lambda: N.check(lib.ucod_split16_rows(f1.data_ptr(), F, gs.data_ptr(), M, F, 0, 1, 1.0, 16.0, st()), "sg"), nbytes=M * F * (4 + 6))
     timed("split16_scale_f32 (tokens)", lambda: N.check(lib.ucod_split16_scale_f32(x.data_ptr(), M * D, 1.0, st()), "sc"), nbytes=M * D * 8)
     sw = lambda t: ops.split_rows(t, 2, 1, term="f16", scale=ops.pow2_scale(t))  # noqa: E731
     gemm = ops._gemm_f16
@@ -127,11 +130,16 @@ else:
     gemm = ops.gemm_bf16
 wq = sw(torch.randn(3 * D, D, generator=g).to(dev) * 0.02)
 wp = sw(torch.randn(D, D, generator=g).to(dev) * 0.02)
-w1 = sw(torch.randn(F, D, generator=g).to(dev) * 0.02)
+w1_raw = torch.randn(F, D, generator=g).to(dev) * 0.02
+w1 = sw(w1_raw)
+alpha1 = 1.0 / (64.0 * ops.pow2_scale(w1_raw)) if H16 else 1.0  # what leaves fc1's accumulator in the fp16-term pass: the LayerNorm class scale times the weight's
 w2 = sw(torch.randn(D, F, generator=g).to(dev) * 0.02)
 timed("GEMM qkv  (BIAS_F32)", lambda: gemm(N.EPI_BIAS_F32, hs, wq, oq, M, 3 * D, P * D, bias=bq), flops=2.0 * M * 3 * D * D)
-timed("GEMM fc1  (BIAS_F32)", lambda: gemm(N.EPI_BIAS_F32, hs, w1, f1, M, F, P * D, bias=b1), flops=2.0 * M * F * D)
-if T == 2 and not H16:                                          # (the fp16-term pass has no fused fc1 epilogue: it runs BIAS_F32 + split16_rows(gelu))
+if not FUSED:
+    timed("GEMM fc1  (BIAS_F32)", lambda: gemm(N.EPI_BIAS_F32, hs, w1, f1, M, F, P * D, bias=b1), flops=2.0 * M * F * D)
+if FUSED:                                                       # fc1 + exact-erf GELU + fp16-term split in one launch (ucod_split16_gemm_act)
+    timed("GEMM fc1  (GELU_SPLIT16: fused)", lambda: ops.gemm_act_split16(hs, w1, b1, 1, alpha1, 16.0, out=gs), flops=2.0 * M * F * D)
+if T == 2 and not H16:                                          # (the bf16-term pass's fused fc1 epilogue)
     timed("GEMM fc1  (GELU_SPLIT2: fused)", lambda: gemm(N.EPI_BIAS_GELU_SPLIT2, hs, w1, gs, M, F, P * D, bias=b1), flops=2.0 * M * F * D)
 timed("GEMM proj (SCALE_RESID_F32)", lambda: gemm(N.EPI_BIAS_SCALE_RESID_F32, aout, wp, x, M, D, P * D, bias=bp, scale=ls, resid=x), flops=2.0 * M * D * D)
 timed("GEMM fc2  (SCALE_RESID_F32)", lambda: gemm(N.EPI_BIAS_SCALE_RESID_F32, gs, w2, x, M, D, P * F, bias=bp, scale=ls, resid=x), flops=2.0 * M * D * F)

@@ -162,10 +162,28 @@ __device__ __forceinline__ float silu_f32(float x) {
   return e == __builtin_inff() ? -0.f : x / (1.0f + e);
 }
 
+// ---- fp16-term split (csrc/split16.hip documents the error model): shared by the row / LayerNorm / attention writers there and by the fused fc1 drain of the
+// fp16-build GEMM (gemm_bf16_epilogue.h: UCOD_EPI_BIAS_GELU_SPLIT16 / UCOD_EPI_BIAS_SWIGLU_SPLIT16), so that the two compute the same bits
+namespace s16 {
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }   // transformers ACT2FN["gelu"], modeling_dinov2.py:289
+// (hi pair, lo pair) of two ALREADY SCALED values; every value beyond fp16's range (or NaN) is counted and clamped
+__device__ __forceinline__ u32x2 split_pair(float a, float b, unsigned& sat) {
+  sat += (unsigned)beyond_f16(a) + (unsigned)beyond_f16(b);
+  a = clamp_f16(a);
+  b = clamp_f16(b);
+  const unsigned hi = pack_f16x2(a, b);
+  float ha, hb;
+  unpack_f16x2(hi, ha, hb);
+  return (u32x2){hi, pack_f16x2(a - ha, b - hb)};
+}
+}  // namespace s16
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // device address of the f16-residual-stream saturation counter of the current device (vit_misc.hip)
 unsigned* resid16_overflow_counter();
+// the GEMM of ucod_split16_gemm_act (gemm_bf16.hip; fp16 build): epilogue = UCOD_EPI_BIAS_GELU_SPLIT16 / UCOD_EPI_BIAS_SWIGLU_SPLIT16
+int gemm_split16_act(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias, float alpha, float scale, int variant, void* stream);
 // ucod_accumulators_prezeroed (elementwise.hip): the caller has zeroed the accumulating outputs of the calls it issues next from this host thread
 // (one ucod_zero_segments launch per step instead of a memset in front of every producer)
 bool accumulators_prezeroed();

@@ -575,10 +575,12 @@ static int launch_patch_h16_stats(ucod::GemmArgs a, hipStream_t s) {
 static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias,
                       const float* scale, const float* resid, const float* pos, int tokens_per_image, int variant,
                       void* stream, const void* aux, void* out2, const float* stats = nullptr, const float* colsum = nullptr,
-                      const float* part_in = nullptr, float* part_out = nullptr, int nslot = 0, float eps = 0.f) {
+                      const float* part_in = nullptr, float* part_out = nullptr, int nslot = 0, float eps = 0.f, float act_alpha = 1.f, float act_scale = 1.f) {
   using namespace ucod;
   if (!A || !B || !out || M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0) return UCOD_EINVAL;
   GemmArgs a;
+  a.act_alpha = act_alpha;
+  a.act_scale = act_scale;
   a.aux = aux;
   a.out2 = out2;
   a.stats = stats;
@@ -589,7 +591,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.eps = eps;
   a.ovf = (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS ||
            epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 ||
-           epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16)
+           epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16)
               ? resid16_overflow_counter() : nullptr;           // (the folded consumers count rows outside the fold's range into the same word: fold_finish)
   a.stamps = nullptr;
 #ifdef UCOD_GEMM_STAMPS
@@ -613,7 +615,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.group_m = 8;
   a.col_fast = 0;
   hipStream_t s = (hipStream_t)stream;
-  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : PROF_GEMM_EPI7)), s);
+  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : PROF_GEMM_EPI7)), s);
   switch (epilogue) {
     case UCOD_EPI_BIAS_BF16:                                   // NULL bias (plain product) only in the large-tile kernels
       if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
@@ -633,6 +635,15 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
 #endif
       if (!bias || (N & 7) != 0 || (long)M * 3 * N >= (1L << 31) - 16) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_SWIGLU_SPLIT2>(a, variant, s);
+#ifdef UCOD_HALF_F16
+    // fp16-term split pass (ucod_split16_gemm_act): rows of 3 N (SwiGLU: 3 N / 2) fp16, addressed with 31-bit byte offsets below the drains' sentinels
+    case UCOD_EPI_BIAS_GELU_SPLIT16:
+      if (!bias || !a.ovf || (N & 7) != 0 || (long)M * 3 * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
+      return launch<UCOD_EPI_BIAS_GELU_SPLIT16>(a, variant, s);
+    case UCOD_EPI_BIAS_SWIGLU_SPLIT16:
+      if (!bias || !a.ovf || (N & 7) != 0 || (long)M * 3 * N >= (1L << 31) - 16) return UCOD_EINVAL;
+      return launch<UCOD_EPI_BIAS_SWIGLU_SPLIT16>(a, variant, s);
+#endif
     case UCOD_EPI_BIAS_SCALE_RESID_F32:
       if (!bias || !scale || !resid) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_SCALE_RESID_F32>(a, variant, s);
@@ -680,6 +691,7 @@ extern "C" int ucod_gemm_bf16(int epilogue, const void* A, const void* B, void* 
   if (epilogue == UCOD_EPI_GELU_BWD_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SAVE_BF16) return UCOD_EINVAL;   // need ucod_gemm_bf16_train
   if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
   if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;   // need ucod_gemm_bf16_stats
+  if (epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) return UCOD_EINVAL;   // need ucod_split16_gemm_act
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream, nullptr, nullptr);
 }
 
@@ -713,6 +725,19 @@ extern "C" int ucod_gemm_bf16_stats(int epilogue, const void* A, const void* B, 
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, (const float*)resid, pos, tokens_per_image, 0, stream, nullptr, nullptr, nullptr, nullptr,
                     nullptr, row_partials, nslot, 0.f);
 }
+
+// The GEMM behind ucod_split16_gemm_act (split16.hip validates op, alpha and scale): the fp16-term split epilogues on this file's kernels.
+namespace ucod {
+int gemm_split16_act(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias, float alpha, float scale, int variant, void* stream) {
+#ifndef UCOD_HALF_F16
+  return UCOD_EINVAL;
+#else
+  if (epilogue != UCOD_EPI_BIAS_GELU_SPLIT16 && epilogue != UCOD_EPI_BIAS_SWIGLU_SPLIT16) return UCOD_EINVAL;
+  return gemm_entry(epilogue, A, B, out, M, N, K, bias, nullptr, nullptr, nullptr, 0, variant, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, alpha,
+                    scale);
+#endif
+}
+}  // namespace ucod
 
 // Re-read the UCOD_GEMM_* tuning variables (gemm_bf16_plan.h): they are read once per process, not per launch.
 extern "C" void ucod_gemm_reload_tuning(void) { ucod::tuning() = ucod::read_gemm_tuning(); }

@@ -40,18 +40,31 @@ constexpr bool kBiasLike = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_LNFOLD_
 // fc1 of the two-term split-operand pass: GELU, then the result as the A-side split operand of fc2 -- three bf16 segments (hi | hi | lo) of a row 3 N wide
 template <int EPI>
 constexpr bool kSplit2Out = (EPI == UCOD_EPI_BIAS_GELU_SPLIT2);
+// fc1 of the fp16-term split pass (csrc/split16.hip; fp16 build, ucod_split16_gemm_act): out = the A-side split operand of act_scale * f(act_alpha * (C + bias)) as two
+// fp16 terms, saturation counted -- gelu_exact / silu_f32 and split_pair of common.h on the f32 value the unfused pair (UCOD_EPI_BIAS_F32 + ucod_split16_rows) passes
+// through memory, so the two agree bit for bit.  Row layouts: those of kSplit2Out (GELU) and kSwigluSplit2 (SwiGLU).  Row-major 8-column drains only, like SwiGLU.
 template <int EPI>
-constexpr int kOutPitchMul = kSplit2Out<EPI> ? 3 : 1;              // output row pitch in units of N elements
+constexpr bool kSplit16Gelu = (EPI == UCOD_EPI_BIAS_GELU_SPLIT16);
 template <int EPI>
-constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || kSplit2Out<EPI>);   // erf-GELU, 16-bit output
+constexpr bool kSplit16Swiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT16);
+template <int EPI>
+constexpr bool kSplit16 = kSplit16Gelu<EPI> || kSplit16Swiglu<EPI>;
+template <int EPI>
+constexpr int kOutPitchMul = (kSplit2Out<EPI> || kSplit16Gelu<EPI>) ? 3 : 1;              // output row pitch in units of N elements
+// (kSplit16Gelu is listed for the routing only -- 16-bit output, N % 8 == 0, row-major 8-column drains; every drain branches to split16_act8 / gelu_exact BEFORE
+// the gelu_erf2 calls that kGeluLike selects, and must keep doing so: the minimax form is three times too coarse for a 22-bit operand)
+template <int EPI>
+constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || kSplit2Out<EPI> || kSplit16Gelu<EPI>);   // erf-GELU, 16-bit output
 // DINOv2 ViT-g's SwiGLU MLP (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) on weights_in rows interleaved in blocks of 4 (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_BF16):
 // the 8 consecutive columns 8k .. 8k+7 that a lane of a row-major drain holds are x1 | x2 of the hidden units 4k .. 4k+3, so the product needs no other lane and no
 // other tile.  Output column = GEMM column / 2: one 8-byte store per lane and segment.  Only the row-major drains implement it (epilogue_store8_bf16 and the
 // large-tile drain); launch() keeps these epilogues away from the element-wise ones (N % 8 == 0, no leftover-as-patches tiles).
 template <int EPI>
-constexpr bool kSwiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2);
+constexpr bool kSwiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || kSplit16Swiglu<EPI>);
 template <int EPI>
 constexpr bool kSwigluSplit2 = (EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2);   // output = the A-side split operand hi | hi | lo, segments N / 2 apart in a row of 3 N / 2
+template <int EPI>
+constexpr bool kSwigluSplitRow = kSwigluSplit2<EPI> || kSplit16Swiglu<EPI>;   // (the row layout of either term type)
 // silu(x) = x / (1 + exp(-x)).  16-bit outputs: v_exp_f32 and v_rcp_f32.  exp(-x) overflows for x below ~-88 and s = 0, where x * s would be NaN at x = -inf:
 // -0 there (the limit).  A NaN stays a NaN (s is NaN, not 0).
 __device__ __forceinline__ float silu_fast(float x) {
@@ -98,6 +111,7 @@ struct GemmArgs {
   const void* aux;    // GELU_BWD: bf16 [M,N] pre-activation of the forward fc1
   void* out2;         // BIAS_GELU_SAVE: bf16 [M,N] pre-activation output
   unsigned* ovf;      // f16 residual-stream epilogues: saturation counter (common.h: resid16_overflow_counter)
+  float act_alpha, act_scale;   // kSplit16 epilogues: out = split of act_scale * f(act_alpha * (C + bias)), both powers of two
   const float* stats;   // LayerNorm-folded epilogues: per-row (rstd, -mean * rstd) of the A rows, f32 [M][2] (used when part_in is NULL)
   const float* colsum;  // LayerNorm-folded epilogues: c[n] = sum_k B[n][k] (of the ROUNDED folded weight), f32 [N]
   const float* part_in; // LayerNorm-folded epilogues: per-row partial (sum, M2 about the slot mean) of the A rows, f32 [M][nslot][2], written by the producer's
@@ -113,6 +127,38 @@ struct GemmArgs {
   int group_m;         // large-tile kernels: row-tiles per group of the tile order inside an XCD's chunk (see tile_of)
   int col_fast;        // 1: column-tile fastest inside a group (one A panel's N-sweep back to back), 0: row-tile fastest
 };
+
+// kSplit16: eight GEMM columns (bias inside) -> the scaled activation values, in the words of split16_rows_kernel (csrc/split16.hip): 8 for GELU, 4 for SwiGLU
+// (v0 = x1, v1 = x2 of four hidden units), then hi / lo words; values beyond fp16's range are clamped and counted into `sat`
+template <int EPI>
+__device__ __forceinline__ void split16_act8(const GemmArgs& a, f32x4 v0, f32x4 v1, u32x4& hi, u32x4& lo, unsigned& sat) {
+  const float alpha = a.act_alpha, scale = a.act_scale;
+  if constexpr (kSplit16Swiglu<EPI>) {
+    float h[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = silu_f32(v0[e] * alpha) * (v1[e] * alpha) * scale;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const u32x2 t = s16::split_pair(h[2 * e], h[2 * e + 1], sat);
+      hi[e] = t[0];
+      lo[e] = t[1];
+    }
+    hi[2] = hi[3] = lo[2] = lo[3] = 0u;
+  } else {
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      g[e] = s16::gelu_exact(v0[e] * alpha) * scale;
+      g[4 + e] = s16::gelu_exact(v1[e] * alpha) * scale;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const u32x2 t = s16::split_pair(g[2 * e], g[2 * e + 1], sat);
+      hi[e] = t[0];
+      lo[e] = t[1];
+    }
+  }
+}
 
 // Tile order of the large-tile kernels inside one XCD's contiguous chunk of the grid: groups of `group_m` row-tiles x all column-tiles.
 // row-tile fastest (col_fast = 0): the 32 workgroups resident on an XCD share group_m A panels and 32/group_m B panels;
@@ -201,6 +247,16 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
     row[0] = hi;
     row[a.N] = hi;
     row[2 * (size_t)a.N] = lo;
+  } else if constexpr (kSplit16Gelu<EPI>) {                      // (leftover patches of the large-tile kernels: one element per thread)
+    // one atomic per CLAMPED element, on purpose: the staged drain sums per wave, but a pass that saturates is one check_overflow rejects, so this path
+    // stays free of a wave reduction and costs nothing while the counter stays at zero
+    unsigned sat = 0;
+    const u32x2 t = s16::split_pair(s16::gelu_exact((v + a.bias[n]) * a.act_alpha) * a.act_scale, 0.f, sat);
+    if (sat) atomicAdd(a.ovf, sat);
+    h_raw* row = reinterpret_cast<h_raw*>(a.out) + (size_t)m * 3 * a.N + n;
+    row[0] = (h_raw)(t[0] & 0xFFFFu);
+    row[a.N] = (h_raw)(t[0] & 0xFFFFu);
+    row[2 * (size_t)a.N] = (h_raw)(t[1] & 0xFFFFu);
   } else if constexpr (EPI == UCOD_EPI_BIAS_GELU_BF16) {
     reinterpret_cast<bf16_raw*>(a.out)[(size_t)m * a.N + n] = f32_to_h(gelu_erf(v + a.bias[n]));
   } else if constexpr (EPI == UCOD_EPI_BIAS_SCALE_RESID_F32) {
@@ -235,7 +291,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
 // Four consecutive columns n..n+3 of output row m (n % 4 == 0, N % 4 == 0): vector loads / stores.
 template <int EPI>
 __device__ __forceinline__ void epilogue_store4(const GemmArgs& a, int m, int n, f32x4 v) {
-  static_assert(!kSwiglu<EPI>, "SwiGLU epilogues drain 8-column chunks only");
+  static_assert(!kSwiglu<EPI> && !kSplit16<EPI>, "SwiGLU and fp16-term split epilogues drain 8-column chunks only");
   if (m >= a.M || n >= a.N) return;
   if constexpr (EPI == UCOD_EPI_KEY_NCHW_F32) {
     // four consecutive tokens of one image, none of them CLS: one dword-aligned 16-byte store into [B, C, tok-1] (row starts are
@@ -326,6 +382,25 @@ __device__ __forceinline__ void epilogue_store8_bf16(const GemmArgs& a, int m, i
   if (m >= a.M || n >= a.N) return;
   f32x4 o0 = v0 + *reinterpret_cast<const f32x4*>(a.bias + n);
   f32x4 o1 = v1 + *reinterpret_cast<const f32x4*>(a.bias + n + 4);
+  if constexpr (kSplit16<EPI>) {
+    u32x4 hi, lo;
+    unsigned sat = 0;
+    split16_act8<EPI>(a, o0, o1, hi, lo, sat);
+    if (sat) atomicAdd(a.ovf, sat);
+    if constexpr (kSplit16Swiglu<EPI>) {
+      const int nh = a.N >> 1;
+      h_raw* row = reinterpret_cast<h_raw*>(a.out) + (size_t)m * 3 * nh + (n >> 1);
+      *reinterpret_cast<u32x2*>(row) = (u32x2){hi[0], hi[1]};
+      *reinterpret_cast<u32x2*>(row + nh) = (u32x2){hi[0], hi[1]};
+      *reinterpret_cast<u32x2*>(row + 2 * (size_t)nh) = (u32x2){lo[0], lo[1]};
+    } else {
+      h_raw* row = reinterpret_cast<h_raw*>(a.out) + (size_t)m * 3 * a.N + n;
+      *reinterpret_cast<u32x4*>(row) = hi;
+      *reinterpret_cast<u32x4*>(row + a.N) = hi;
+      *reinterpret_cast<u32x4*>(row + 2 * (size_t)a.N) = lo;
+    }
+    return;
+  }
   if constexpr (kFold<EPI>) {
     const float s = a.stats[2 * (size_t)m], u = a.stats[2 * (size_t)m + 1];
     const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + n), b1 = *reinterpret_cast<const f32x4*>(a.bias + n + 4);
@@ -388,10 +463,10 @@ template <int EPI, int WCOLS, int ROWS>
 __device__ __forceinline__ void drain_rows(const GemmArgs& a, const char* wbase, int m_first, int n_first, int lane) {
   constexpr bool BF16_OUT = (kBiasLike<EPI> || kGeluLike<EPI> || kSwiglu<EPI>);
   // SwiGLU: the 8-column path is the only one (launch() refuses N % 8 != 0); the 4-column fallback below is not compiled for it
-  static_assert(!kSwiglu<EPI> || ((WCOLS % 8) == 0 && (ROWS * (WCOLS / 8)) % 64 == 0), "SwiGLU needs the 8-column drain");
+  static_assert(!(kSwiglu<EPI> || kSplit16<EPI>) || ((WCOLS % 8) == 0 && (ROWS * (WCOLS / 8)) % 64 == 0), "SwiGLU / fp16-term split need the 8-column drain");
   if constexpr (BF16_OUT && (WCOLS % 8) == 0 && (ROWS * (WCOLS / 8)) % 64 == 0) {
     constexpr int CH = WCOLS / 8;                     // 32-byte (8 x f32) chunks per row -> 16-byte bf16 stores
-    if (kSwiglu<EPI> || (a.N & 7) == 0) {
+    if (kSwiglu<EPI> || kSplit16<EPI> || (a.N & 7) == 0) {
 #pragma unroll
       for (int it = 0; it < ROWS * CH / 64; ++it) {
         const int idx = it * 64 + lane, r = idx / CH, c = idx - r * CH;
@@ -402,7 +477,7 @@ __device__ __forceinline__ void drain_rows(const GemmArgs& a, const char* wbase,
       return;
     }
   }
-  if constexpr (!kSwiglu<EPI>) {
+  if constexpr (!kSwiglu<EPI> && !kSplit16<EPI>) {
     constexpr int CH = WCOLS / 4;                     // 16-byte chunks per row
     static_assert((ROWS * CH) % 64 == 0, "whole wave instructions");
 #pragma unroll
@@ -597,7 +672,7 @@ __device__ __forceinline__ void fold_rank_one(f32x4 (&acc)[NI][NT], const float*
 //   * the f32 residual is double buffered: the loads of pass p+1 are issued BEFORE the stores of pass p, and vmcnt retires
 //     in order, so the wait for them leaves pass p's stores in flight.  (out may alias resid: passes touch disjoint rows.)
 template <int EPI>
-constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kSplit2Out<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
+constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kSplit2Out<EPI> || kSplit16<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
                             EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16 ||
                             EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI> || kSwiglu<EPI>);
 template <int EPI>
@@ -796,7 +871,7 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     // are dropped (loads return 0) -- and columns past N get an offset beyond any descriptor.
     constexpr unsigned OOB = 0xFFFFFFF0u;
     // bytes per GEMM column of an output row's pitch (the split epilogue's rows are 3 N wide; a SwiGLU row holds N / 2 16-bit values, 3 N / 2 in the split form)
-    constexpr int ELT = kSwiglu<EPI> ? (kSwigluSplit2<EPI> ? 3 : 1) : (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;
+    constexpr int ELT = kSwiglu<EPI> ? (kSwigluSplitRow<EPI> ? 3 : 1) : (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;
     const long rows_left = (long)a.M - m_first;
     const unsigned long left = rows_left > 0 ? (unsigned long)rows_left * a.N * ELT : 0ul;
     const unsigned records = left > 0xFFFFFFFFul ? 0xFFFFFFFFu : (unsigned)left;
@@ -911,6 +986,7 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
         return wbase + lrow(it) * EPI_PITCH(WCOLS) + lchk(it) * 32;
       };
       float amax = 0.f;                                             // RH16: largest |x_new| this lane produced (saturation test after the stores)
+      unsigned sat16 = 0;                                           // kSplit16: elements of live chunks this lane clamped
       // *_STATS: this launch's rows of the partial-sum table [M][nslot][2] f32, descriptor from the wave tile's first row (rows past M are dropped)
       const unsigned part_row_bytes = kStats<EPI> ? (unsigned)a.nslot * 8u : 0u, part_slot_off = kStats<EPI> ? (unsigned)(n_first >> 6) * 8u : 0u;
       const unsigned long part_left = kStats<EPI> && rows_left > 0 ? (unsigned long)rows_left * part_row_bytes : 0ul;
@@ -940,6 +1016,29 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
           if (!live(it, pass)) continue;
           f32x4 v0 = *reinterpret_cast<const f32x4*>(lds_at(it));
           f32x4 v1 = *reinterpret_cast<const f32x4*>(lds_at(it) + 16);
+          if constexpr (kSplit16<EPI>) {                          // fp16 terms: activation and split of split16_rows_kernel on the staged f32 value
+            u32x4 hi, lo;
+            unsigned s1 = 0;
+            split16_act8<EPI>(a, v0, v1, hi, lo, s1);
+            // a dropped chunk (columns past N, rows past M or past a 16-row last pass) lies at or beyond the descriptor's end: its clamps are not counted, and its
+            // segments keep the offset instead of adding to a sentinel >= 2^31, which would wrap back into range (live offsets stay below 2^31: the entry bounds M * 3 N)
+            const unsigned o = at(it, pass);
+            const bool alive = o < rec16;
+            sat16 += alive ? s1 : 0u;
+            const unsigned seg = kSplit16Swiglu<EPI> ? (unsigned)a.N : 2u * (unsigned)a.N;    // bytes between two segments
+            const unsigned o1 = alive ? o + seg : o, o2 = alive ? o + 2u * seg : o;
+            if constexpr (kSplit16Swiglu<EPI>) {
+              __builtin_amdgcn_raw_buffer_store_b64((u32x2){hi[0], hi[1]}, rs_o, o, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b64((u32x2){hi[0], hi[1]}, rs_o, o1, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b64((u32x2){lo[0], lo[1]}, rs_o, o2, 0, AUX);
+            } else {
+              __builtin_amdgcn_raw_buffer_store_b128(hi, rs_o, o, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b128(hi, rs_o, o1, 0, AUX);
+              __builtin_amdgcn_raw_buffer_store_b128(lo, rs_o, o2, 0, AUX);
+            }
+            __builtin_amdgcn_sched_barrier(0);                    // chunks in order, as at the end of this loop's body: erff of a hoisted pass would not fit the registers
+            continue;
+          }
           if constexpr (SAVE) {                                   // pre-activation out first
             u32x4 w;
             w[0] = pack_h2(v0[0], v0[1]);
@@ -1012,9 +1111,11 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
             { const u32x2 t2 = split2_pack(v0[2], v0[3]); w[1] = t2[0]; lo[1] = t2[1]; }
             { const u32x2 t2 = split2_pack(v1[0], v1[1]); w[2] = t2[0]; lo[2] = t2[1]; }
             { const u32x2 t2 = split2_pack(v1[2], v1[3]); w[3] = t2[0]; lo[3] = t2[1]; }
+            // a dropped chunk's offset is a sentinel >= 2^31 (DROP + tile offset, or OOB on the 192-wide tiles): the segments keep it -- OOB + 2 N would wrap back
+            // into the wave's first rows (live offsets stay below 2^31: gemm_entry bounds M * 3 N * 2)
             const unsigned o = at(it, pass);
-            __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, o + (unsigned)a.N * 2u, 0, AUX);
-            __builtin_amdgcn_raw_buffer_store_b128(lo, rs_o, o + (unsigned)a.N * 4u, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(w, rs_o, o >= 0x80000000u ? o : o + (unsigned)a.N * 2u, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, rs_o, o >= 0x80000000u ? o : o + (unsigned)a.N * 4u, 0, AUX);
           } else {
             w[0] = pack_h2(v0[0], v0[1]);
             w[1] = pack_h2(v0[2], v0[3]);
@@ -1028,6 +1129,9 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
       }
       if constexpr (RH16) {                                         // after the last store: nothing waits on this
         if (!(amax <= F16_MAX)) atomicAdd(a.ovf, 1u);          // true for NaN too (beyond_f16's convention, common.h)
+      }
+      if constexpr (kSplit16<EPI>) {
+        if (sat16 != 0u) atomicAdd(a.ovf, sat16);
       }
     }
   }

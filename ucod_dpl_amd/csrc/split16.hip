@@ -20,6 +20,9 @@
 //                                   by 1 / (s_a s_b) as it reads
 //   UCOD_EPI_PATCH_TOKENS_F32       bias', pos' (and the CLS rows) times s_a s_b, then one in-place pass x *= 1 / (s_a s_b)       (ucod_split16_scale_f32)
 //   UCOD_EPI_KEY_NCHW_F32           bias' = s_a s_b bias, then the same in-place pass over the key map
+// fc1 can also leave as the split operand of fc2 straight from the GEMM's drain (ucod_split16_gemm_act; UCOD_SPLIT16_FUSE_MLP in the pass):
+//   UCOD_EPI_BIAS_GELU_SPLIT16 /    bias' = s_a s_b bias, act_alpha = 1 / (s_a s_b), act_scale = the HIDDEN class scale: the drain calls gelu_exact / silu_f32 and
+//   UCOD_EPI_BIAS_SWIGLU_SPLIT16    split_pair (common.h) on the f32 value the pair above passes through memory -- the same bits, one launch, no f32 [M, F] buffer
 // Everything between the GEMMs is f32 as in split.hip: residual stream, two-pass LayerNorm, exact-erf GELU / f32 SiLU, softmax.
 //
 // Attention (attn_split16_kernel): attn_split_kernel<2, 1> of split.hip on v_mfma_f32_32x32x16_f16 -- same LDS layout, software pipeline and register budget (a
@@ -70,18 +73,7 @@ namespace s16 {
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }   // transformers ACT2FN["gelu"], modeling_dinov2.py:289
-
-// (hi pair, lo pair) of two ALREADY SCALED values; every value beyond fp16's range (or NaN) is counted and clamped
-__device__ __forceinline__ u32x2 split_pair(float a, float b, unsigned& sat) {
-  sat += (unsigned)beyond_f16(a) + (unsigned)beyond_f16(b);
-  a = clamp_f16(a);
-  b = clamp_f16(b);
-  const unsigned hi = pack_f16x2(a, b);
-  float ha, hb;
-  unpack_f16x2(hi, ha, hb);
-  return (u32x2){hi, pack_f16x2(a - ha, b - hb)};
-}
+// gelu_exact and split_pair -- (hi pair, lo pair) of two already scaled values, counted and clamped -- live in common.h: the fused fc1 drain shares them
 // probabilities and other values known to lie inside the range: no clamp, no count
 __device__ __forceinline__ u32x2 split_pair_inrange(float a, float b) {
   const unsigned hi = pack_f16x2(a, b);
@@ -542,6 +534,16 @@ extern "C" int ucod_split16_rows(const float* in, long ld_in, void* out, int M, 
 #endif
 }
 
+extern "C" int ucod_split16_gemm_act(int op, const void* a_f16, const void* b_f16, void* out_f16, int M, int N, int K3, const float* bias_scaled, float alpha, float scale,
+                                     int variant, void* stream) {
+  S16_F16_ONLY();
+#ifdef UCOD_HALF_F16
+  if (!a_f16 || !b_f16 || !out_f16 || !bias_scaled || M <= 0 || N <= 0 || (N & 7) != 0 || K3 <= 0 || (op != 1 && op != 3) || !s16::pow2_ok(alpha) || !s16::pow2_ok(scale))
+    return UCOD_EINVAL;
+  return gemm_split16_act(op == 1 ? UCOD_EPI_BIAS_GELU_SPLIT16 : UCOD_EPI_BIAS_SWIGLU_SPLIT16, a_f16, b_f16, out_f16, M, N, K3, bias_scaled, alpha, scale, variant, stream);
+#endif
+}
+
 extern "C" int ucod_split16_layernorm(const float* x, const float* gamma, const float* beta, void* out, int rows, int D, float eps, int role, float scale, void* stream) {
   S16_F16_ONLY();
 #ifdef UCOD_HALF_F16
@@ -649,7 +651,7 @@ struct Plan16 {
   int M, tok;
 };
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-Plan16 plan16(const ucod_vit_desc* d, int mlp) {
+Plan16 plan16(const ucod_vit_desc* d, int mlp, int flags) {
   Plan16 p;
   const int gh = d->H / d->P, gw = d->W / d->P;
   p.tok = gh * gw + 1;
@@ -661,15 +663,16 @@ Plan16 plan16(const ucod_vit_desc* d, int mlp) {
   p.off_qkv = take((size_t)p.M * 3 * d->D * 4);
   p.off_att = take(ucod_split16_attention_operand_bytes(d->B, p.tok, d->heads));
   p.off_a = take((size_t)p.M * 3 * d->D * 2);
-  p.off_f1 = take((size_t)p.M * d->F * (mlp == UCOD_MLP_SWIGLU ? 2 : 1) * 4);     // fc1's f32 output (2 F wide for SwiGLU)
+  // fc1's f32 output (2 F wide for SwiGLU); not with UCOD_SPLIT16_FUSE_MLP, where fc1 writes the split hidden itself
+  p.off_f1 = (flags & UCOD_SPLIT16_FUSE_MLP) ? o : take((size_t)p.M * d->F * (mlp == UCOD_MLP_SWIGLU ? 2 : 1) * 4);
   p.off_g = take((size_t)p.M * 3 * d->F * 2);
   p.off_patch = take((size_t)d->B * gh * gw * 3 * d->Kpad * 2);
   p.total = o;
   return p;
 }
 // (the LayerNorm widths are asked of the LayerNorm launcher's own predicate: a geometry this accepts is one every kernel of the pass takes)
-bool valid16(const ucod_vit_desc* d, int mlp) {
-  return d && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->heads > 0 &&
+bool valid16(const ucod_vit_desc* d, int mlp, int flags) {
+  return d && (flags & ~UCOD_SPLIT16_FUSE_MLP) == 0 && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->heads > 0 &&
          d->D == d->heads * 64 && s16::ln_width_ok(d->D) && d->F > 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          d->full_last_layer == 0 && (long)d->B * d->heads <= 65535;
 }
@@ -681,18 +684,25 @@ bool valid16(const ucod_vit_desc* d, int mlp) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_split16_workspace_bytes(const ucod_vit_desc* d, int mlp) { return valid16(d, mlp) ? plan16(d, mlp).total : 0; }
-extern "C" size_t ucod_vit_split16_stream_offset(const ucod_vit_desc* d, int mlp) { return valid16(d, mlp) ? plan16(d, mlp).off_x : (size_t)-1; }
+extern "C" size_t ucod_vit_split16_workspace_bytes_ex(const ucod_vit_desc* d, int mlp, int flags) { return valid16(d, mlp, flags) ? plan16(d, mlp, flags).total : 0; }
+extern "C" size_t ucod_vit_split16_stream_offset_ex(const ucod_vit_desc* d, int mlp, int flags) { return valid16(d, mlp, flags) ? plan16(d, mlp, flags).off_x : (size_t)-1; }
+extern "C" size_t ucod_vit_split16_workspace_bytes(const ucod_vit_desc* d, int mlp) { return ucod_vit_split16_workspace_bytes_ex(d, mlp, 0); }
+extern "C" size_t ucod_vit_split16_stream_offset(const ucod_vit_desc* d, int mlp) { return ucod_vit_split16_stream_offset_ex(d, mlp, 0); }
 
 extern "C" int ucod_vit_forward_split16(const ucod_vit_desc* d, int mlp, const void* const* T, const float* wscale, int n_wscale, const float* img, float* key_out, void* workspace,
                                         size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_split16_ex(d, mlp, 0, T, wscale, n_wscale, img, key_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int flags, const void* const* T, const float* wscale, int n_wscale, const float* img, float* key_out,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
   S16_F16_ONLY();
 #ifdef UCOD_HALF_F16
-  if (!valid16(d, mlp) || !T || !wscale || n_wscale != 1 + 4 * d->L || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid16(d, mlp, flags) || !T || !wscale || n_wscale != 1 + 4 * d->L || !img || !key_out || !workspace) return UCOD_EINVAL;
   for (int i = 0; i < n_wscale; ++i)
     if (!s16::pow2_ok(wscale[i])) return UCOD_EINVAL;
-  const Plan16 p = plan16(d, mlp);
-  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
+  const Plan16 p = plan16(d, mlp, flags);
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU, fuse_mlp = (flags & UCOD_SPLIT16_FUSE_MLP) != 0;
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   float* x = (float*)(ws + p.off_x);
@@ -728,9 +738,14 @@ extern "C" int ucod_vit_forward_split16(const ucod_vit_desc* d, int mlp, const v
     RUN(ucod_split16_attention_fwd(att, a, d->B, tok, d->heads, sQKV, sATT, stream));
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, a, W[4], x, M, D, 3 * D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
     RUN(ucod_split16_layernorm(x, (const float*)W[7], (const float*)W[8], h, M, D, d->eps, 0, sLN, stream));
-    // fc1 through the f32 epilogue, then activation + split in one row pass (exact-erf GELU / f32 SiLU on the unscaled value)
-    RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[9], f1, M, swiglu ? 2 * F : F, 3 * D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
-    RUN(ucod_split16_rows(f1, swiglu ? 2L * F : F, g, M, F, 0, swiglu ? 3 : 1, 1.0f / (sLN * ws_l[2]), sHID, stream));
+    if (fuse_mlp) {
+      // fc1, activation and split in one launch: the drain runs what the row pass below runs, on the same f32 value
+      RUN(ucod_split16_gemm_act(swiglu ? 3 : 1, h, W[9], g, M, swiglu ? 2 * F : F, 3 * D, (const float*)W[10], 1.0f / (sLN * ws_l[2]), sHID, gv, stream));
+    } else {
+      // fc1 through the f32 epilogue, then activation + split in one row pass (exact-erf GELU / f32 SiLU on the unscaled value)
+      RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[9], f1, M, swiglu ? 2 * F : F, 3 * D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_split16_rows(f1, swiglu ? 2L * F : F, g, M, F, 0, swiglu ? 3 : 1, 1.0f / (sLN * ws_l[2]), sHID, stream));
+    }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, g, W[11], x, M, D, 3 * F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
   }
   return UCOD_OK;

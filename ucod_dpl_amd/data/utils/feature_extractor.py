@@ -150,21 +150,23 @@ class backbone(nn.Module):
         self._siblings = {}
         self.precision, self.engine = self._make_engine(engine_kw.pop("precision", None), engine_kw)
 
-    PRECISIONS = {"split2": 2, "split3": 3, "f32eq": 3, "split2h": 2}
-    TERM_TYPES = {"split2h": "f16"}                              # (every other split precision: bf16 terms)
+    PRECISIONS = {"split2": 2, "split3": 3, "f32eq": 3, "split2h": 2, "split2hf": 2}
+    TERM_TYPES = {"split2h": "f16", "split2hf": "f16"}           # (every other split precision: bf16 terms)
+    FUSED_MLP = {"split2hf"}                                     # fc1 + activation + split in one launch (SplitViTEngine(fuse_mlp=True))
 
     def _make_engine(self, precision, engine_kw):
         """``precision``: None / "f16" / "bf16" -> the 16-bit ``ViTEngine`` (``half`` = that; None = the engine's default, fp16); "split2" / "split3" / "f32eq"
         (= split3) -> ``SplitViTEngine``: every matrix product on split bf16 operands with an f32 residual stream -- the reference's cached-feature pass runs the
         backbone in plain fp32 (data/datasets/base_dataset.py:124-138) and this is the engine that reproduces it to f32 rounding.  "split2h": the same engine on two
-        fp16 terms per operand (22 significand bits at split2's three products; opt-in -- "f32eq" still means split3)."""
+        fp16 terms per operand (22 significand bits at split2's three products; opt-in -- "f32eq" still means split3).  "split2hf": split2h with fc1, its activation and
+        the split of the result fused into one launch (``fuse_mlp=True``; opt-in as well)."""
         state_dict, heads, eps, device = self._src
         if precision in self.PRECISIONS:
             extra = {k: v for k, v in engine_kw.items() if k not in ("gemm_variant",)}
             if extra:
                 raise ValueError(f"precision={precision!r} takes no {sorted(extra)}: the split-operand engine has one residual stream (f32) and one attention path")
             return precision, SplitViTEngine(state_dict, heads=heads, eps=eps, device=device, terms=self.PRECISIONS[precision],
-                                             term=self.TERM_TYPES.get(precision, "bf16"), **engine_kw)
+                                             term=self.TERM_TYPES.get(precision, "bf16"), fuse_mlp=precision in self.FUSED_MLP, **engine_kw)
         if precision not in (None, "f16", "bf16"):
             raise ValueError(f"precision must be one of None, 'f16', 'bf16', {sorted(self.PRECISIONS)}; got {precision!r}")
         if precision is not None:

@@ -61,6 +61,7 @@ class DiscGrads(C.Structure):
 UCOD_MLP_GELU, UCOD_MLP_SWIGLU = 0, 1        # MLP kind of the _mlp backbone entry points (include/ucod_dpl.h)
 # activation operand classes of the fp16-term split pass (ucod_split16_class_scale)
 SPLIT16_LN, SPLIT16_QKV, SPLIT16_PROB, SPLIT16_ATT, SPLIT16_HIDDEN, SPLIT16_PATCH = range(6)
+SPLIT16_FUSE_MLP = 1                            # flag of the ucod_vit_*_split16_ex entry points: fc1 + activation + split in one launch
 
 # name -> (restype, argtypes); must list EVERY symbol include/ucod_dpl.h declares (tests/test_abi.py checks)
 SIGNATURES = {
@@ -98,6 +99,11 @@ SIGNATURES = {
     "ucod_vit_split16_workspace_bytes": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_split16_stream_offset": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_forward_split16": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, sz, vp]),
+    # fc1 + activation + split in one launch, and the pass with options (UCOD_SPLIT16_FUSE_MLP: "split2hf")
+    "ucod_split16_gemm_act": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, cf, cf, ci, vp]),
+    "ucod_vit_split16_workspace_bytes_ex": (sz, [C.POINTER(VitDesc), ci, ci]),
+    "ucod_vit_split16_stream_offset_ex": (sz, [C.POINTER(VitDesc), ci, ci]),
+    "ucod_vit_forward_split16_ex": (ci, [C.POINTER(VitDesc), ci, ci, C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),

@@ -99,6 +99,30 @@ def _gemm_f16(epilogue, A, Bm, out, M, Nn, K, bias=None, scale=None, resid=None,
     return out
 
 
+def gemm_act_split16(xs, ws, bias, op, alpha, scale, variant=0, out=None):
+    """fc1 + activation + fp16-term split in ONE launch (ucod_split16_gemm_act): ``xs`` fp16 [M, 3 K] (A side), ``ws`` fp16 [N, 3 K] (B side), ``bias`` f32 [N] already
+    times the operands' scales S, ``alpha`` = 1 / S, ``scale`` the scale of the result (powers of two).  op 1: exact-erf GELU -> fp16 [M, 3 N]; op 3: SwiGLU of the
+    interleaved x1 / x2 columns -> fp16 [M, 3 N / 2].  The same bits as _gemm_f16(EPI_BIAS_F32) + split_rows(term="f16", op=op) wherever both sum K in one order."""
+    if xs.dtype != torch.float16 or ws.dtype != torch.float16:
+        raise TypeError(f"expected float16 split operands, got {xs.dtype} / {ws.dtype}")
+    if op not in (1, 3):
+        raise ValueError(f"op must be 1 (GELU) or 3 (SwiGLU), got {op!r}")
+    if variant not in N.GEMM_PRODUCT_VARIANTS:
+        raise ValueError(f"variant must be one of {N.GEMM_PRODUCT_VARIANTS}")
+    M, K3 = xs.shape
+    Nn = ws.shape[0]
+    if ws.shape[1] != K3:
+        raise ValueError(f"operand widths differ: {K3} / {ws.shape[1]}")
+    width = 3 * Nn if op == 1 else 3 * Nn // 2
+    if out is None:
+        out = torch.empty(M, width, dtype=torch.float16, device=xs.device)
+    elif out.dtype != torch.float16 or out.numel() < M * width:
+        raise ValueError(f"out must hold {M} x {width} float16 values")
+    check(N.load("f16").ucod_split16_gemm_act(int(op), ptr(xs), ptr(ws), ptr(out), M, Nn, K3, ptr(_f32(bias)), float(alpha), float(scale), int(variant), stream()),
+          "ucod_split16_gemm_act")
+    return out
+
+
 def split_rows(x, terms, role, op=0, alpha=1.0, term="bf16", scale=1.0):
     """x f32 [M,K] (rows may be strided) -> bf16 [M, P K]: segment p holds term {0,0,1,1,0,2}[p] (role 0, the A side) / {0,1,0,1,2,0}[p] (role 1, the B side)
     of x = x0 + x1 (+ x2).  op 1: exact-erf GELU of x first; op 2: x * alpha first.

@@ -444,18 +444,25 @@ class SplitViTEngine:
 
     Same call interface as ``ViTEngine`` (``forward`` / ``forward_async`` / ``__call__``, ``D``, ``P``, ``streams``); key-minimal pass only."""
 
-    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0, term="bf16"):
+    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0, term="bf16", fuse_mlp=False):
         """``term="f16"`` (with ``terms=2``; precision name "split2h"): the two terms of every operand are IEEE fp16 values of a power-of-two multiple of it and the three
         partial products run on the fp16 MFMA (csrc/split16.hip, libucod_dpl_f16.so) -- 22 significand bits per operand at the matrix work of ``terms=2``.  Weights are
         scaled per tensor at load (largest magnitude into [2^13, 2^14)), activations per operand class (``ops.split16_class_scale``); a value beyond fp16's range
-        is clamped and counted on the device, and ``check_overflow`` raises for a pass that met one."""
+        is clamped and counted on the device, and ``check_overflow`` raises for a pass that met one.
+        ``fuse_mlp=True`` (fp16 terms only; precision name "split2hf"): fc1, its activation and the split of the result run as ONE launch (ucod_split16_gemm_act)
+        instead of the f32 GEMM epilogue followed by a row pass, and the workspace holds no f32 fc1 buffer.  The drain calls the row pass's own functions on the same
+        f32 value: the key map is that of ``fuse_mlp=False`` up to the summation order of fc1's leftover tiles."""
         if terms not in (2, 3):
             raise ValueError(f"terms must be 2 or 3, got {terms!r}")
         if term not in ("bf16", "f16"):
             raise ValueError(f"term must be 'bf16' or 'f16', got {term!r}")
         if term == "f16" and terms != 2:
             raise ValueError(f"term='f16' is the two-term form: terms must be 2, got {terms!r}")
+        if fuse_mlp and term != "f16":
+            raise ValueError(f"fuse_mlp=True exists for the fp16-term form only (terms=2, term='f16'), got terms={terms!r}, term={term!r}")
         self.terms, self.term, self.half = int(terms), term, f"{term}x{int(terms)}"
+        self.fuse_mlp = bool(fuse_mlp)
+        self._flags = N.SPLIT16_FUSE_MLP if self.fuse_mlp else 0
         f16 = term == "f16"
         self.lib = N.load("f16" if f16 else "bf16")               # (each term type has its MFMA; either build refuses the other's split entry points)
         self.nprod = ops.split_products(terms)
@@ -535,7 +542,7 @@ class SplitViTEngine:
             return None
         n = self._take_overflow_count(wait)
         if n > 0:
-            raise FloatingPointError(f"the fp16-term split pass (split2h) clamped {n} operand element(s) to +-65504 (or met a NaN): an activation exceeded the bound of its "
+            raise FloatingPointError(f"the fp16-term split pass (split2h / split2hf) clamped {n} operand element(s) to +-65504 (or met a NaN): an activation exceeded the bound of its "
                                      f"operand class (csrc/split16.hip) and the key maps of that pass are wrong -- use precision='split3' ('f32eq') for this checkpoint / "
                                      f"input.  The counter is polled without blocking; check_overflow(wait=True) checks every pass enqueued so far.")
 
@@ -548,11 +555,15 @@ class SplitViTEngine:
         return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), ptrs
 
     def _ws_bytes(self, d):
+        if self.fuse_mlp:
+            return self.lib.ucod_vit_split16_workspace_bytes_ex(C.byref(d), self.mlp, self._flags)
         if self.term == "f16":
             return self.lib.ucod_vit_split16_workspace_bytes(C.byref(d), self.mlp)
         return self.lib.ucod_vit_split_workspace_bytes_mlp(C.byref(d), self.terms, self.mlp)
 
     def _stream_offset(self, d):
+        if self.fuse_mlp:
+            return self.lib.ucod_vit_split16_stream_offset_ex(C.byref(d), self.mlp, self._flags)
         if self.term == "f16":
             return self.lib.ucod_vit_split16_stream_offset(C.byref(d), self.mlp)
         return self.lib.ucod_vit_split_stream_offset_mlp(C.byref(d), self.terms, self.mlp)
@@ -572,8 +583,12 @@ class SplitViTEngine:
             L = d.L
             self.check_overflow()                                  # (non-blocking) passes that have finished since the last call
             with self._own_counter():
-                N.check(self.lib.ucod_vit_forward_split16(C.byref(d), self.mlp, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
-                        "ucod_vit_forward_split16")
+                if self.fuse_mlp:
+                    N.check(self.lib.ucod_vit_forward_split16_ex(C.byref(d), self.mlp, self._flags, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws),
+                                                                 ws.numel(), N.stream()), "ucod_vit_forward_split16_ex")
+                else:
+                    N.check(self.lib.ucod_vit_forward_split16(C.byref(d), self.mlp, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(),
+                                                              N.stream()), "ucod_vit_forward_split16")
             self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=True)
             return
         N.check(self.lib.ucod_vit_forward_split_mlp(C.byref(d), self.terms, self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
