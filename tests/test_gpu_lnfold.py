@@ -380,7 +380,7 @@ def test_engine_with_the_fold_at_vit_l_width():
         _, ref = OV.dinov2_forward(img[:2], sd, heads=16, patch=14, eps=1e-6, full_last_layer=False)
     fold = ViTEngine(sd, heads=16, device=DEV, half="f16", resid="f16")
     plain = ViTEngine(sd, heads=16, device=DEV, half="f16", resid="f16", ln_fold=False)
-    assert fold.ln_fold and fold.fold_layers[0][14].numel() == 3072 and fold.fold_layers[0][15].numel() == 4096
+    assert fold.ln_fold and fold.fold_layers[0][N.QKV_COLSUM].numel() == 3072 and fold.fold_layers[0][N.FC1_COLSUM].numel() == 4096
     kf, kp = fold(img.to(DEV)).cpu()[:2], plain(img.to(DEV)).cpu()[:2]
     fold.check_overflow(wait=True)
     assert rel_l2(kf, ref) < 1.5e-3 and rel_l2(kf, ref) <= 1.25 * rel_l2(kp, ref) + 1e-4, (rel_l2(kf, ref), rel_l2(kp, ref))

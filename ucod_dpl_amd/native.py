@@ -30,7 +30,15 @@ EPI_BIAS_GELU_SPLIT2 = 15                                  # fc1 + GELU + two-te
 # fp16-operand build); the two-term split operand of the result (bf16 library)
 EPI_BIAS_SWIGLU_BF16, EPI_LNFOLD_SWIGLU_BF16, EPI_BIAS_SWIGLU_SPLIT2 = 16, 17, 18
 VIT_LAYER_STRIDE = 16
+# the slots of one layer's row of the pointer table, in table order (include/ucod_dpl.h: ucod_vit_forward); "_w" entries are 16-bit (or split) matrices, the rest f32
+VIT_LAYER_SLOTS = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2", "aux0", "aux1")
+LN1_G, LN1_B, QKV_W, QKV_B, PROJ_W, PROJ_B, LS1, LN2_G, LN2_B, FC1_W, FC1_B, FC2_W, FC2_B, LS2, AUX0, AUX1 = range(VIT_LAYER_STRIDE)
+QKV_COLSUM, FC1_COLSUM = AUX0, AUX1                        # ln_fold tables: column sums of the folded QKV / fc1 weights (unused without the fold)
+KEY_ROWS_A, SPLIT_UNUSED = AUX0, AUX1                      # split tables: the K rows of qkv_w as an A-side operand (key hook); +15 is never read there
 VIT_TRAIN_STRIDE = 7
+# one layer's row of the training table (ucod_vit_forward_train): five frozen weights the engine keeps, then the LoRA parameters and gradients of the pass
+VIT_TRAIN_SLOTS = ("qkv_w_aug", "qkv_wt_aug", "proj_wt", "fc1_wt", "fc2_wt", "lora", "lora_grad")
+T_QKV_W_AUG, T_QKV_WT_AUG, T_PROJ_WT, T_FC1_WT, T_FC2_WT, T_LORA, T_LORA_GRAD = range(VIT_TRAIN_STRIDE)
 LORA_AUG = 64
 
 vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t

@@ -1,5 +1,5 @@
-"""Frozen ViT backbone engine: owns bf16/f32 device copies of the weights, the pointer table the C driver
-walks, and a reusable workspace.  Accepts both checkpoint layouts the reference can meet:
+"""ViT backbone engines: each owns device copies of the weights in its operand form, the pointer table the C driver
+walks, and reusable workspaces.  Accepts both checkpoint layouts the reference can meet:
 
 * HuggingFace ``Dinov2Model`` / ``ViTModel`` state dicts (data/utils/feature_extractor.py:20,25) with
   ``attention.attention.{query,key,value}`` or (transformers>=5 ViT) ``attention.{q,k,v}_proj`` names;
@@ -7,7 +7,13 @@ walks, and a reusable workspace.  Accepts both checkpoint layouts the reference 
 
 Only what the key hook needs is computed by default (feature_extractor.py:46-47,55-58); see
 ``ucod_vit_forward`` in include/ucod_dpl.h.
+
+``_BackboneEngine`` holds what the engines share (geometry, position rows, descriptor, table header, input checks, workspaces,
+side-stream fan-out, one ``_SaturationGuard`` each); ``ViTEngine`` (16-bit operands) and ``SplitViTEngine`` (split operands) derive from it,
+``ViTLoRAEngine`` (backbone-backward mode) is a ``ViTEngine``.  A layer is one 16-slot row built by ``layer_row`` and read by the slot
+names of native.py (``N.QKV_W`` ...), never by number.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -118,7 +124,201 @@ def _prepare_mlp(c):
     return N.UCOD_MLP_SWIGLU, dict(c, layers=layers)
 
 
-class ViTEngine:
+_GEMMS = ("qkv", "proj", "fc1", "fc2")                       # the four GEMMs of a layer, in the order of SplitViTEngine.wscale
+
+
+def layer_row(l, weight, vector, scales=None, aux=(None, None)):
+    """One layer's row of the pointer table (native.VIT_LAYER_SLOTS) from a canonical layer dict: ``weight(t, name)`` converts the four matrices, ``vector(t)`` the ten
+    vectors (ones for a missing LayerScale).  ``scales`` = (S_qkv, S_proj, S_fc1, S_fc2), the operand scales of the fp16-term split pass: each GEMM's bias goes in
+    times its S, the LayerScale behind the out-projection / fc2 divided by it (include/ucod_dpl.h: ucod_vit_forward_split16).  ``aux``: what +14 / +15 hold."""
+    row = []
+    for name in N.VIT_LAYER_SLOTS[:N.AUX0]:
+        if name.endswith("_w"):
+            row.append(weight(l[name], name))
+        else:
+            row.append(vector(torch.ones(l["proj_b"].shape[0], dtype=torch.float32) if l[name] is None else l[name]))
+    if scales is not None:
+        S_qkv, S_proj, S_fc1, S_fc2 = scales
+        for b, S in ((N.QKV_B, S_qkv), (N.PROJ_B, S_proj), (N.FC1_B, S_fc1), (N.FC2_B, S_fc2)):
+            row[b] = row[b] * S
+        row[N.LS1], row[N.LS2] = row[N.LS1] / S_proj, row[N.LS2] / S_fc2
+    return row + list(aux)
+
+
+class _SaturationGuard:
+    """The saturation counter of ONE engine's fp16 values (the fp16 residual stream, the operands of the fp16-term split pass): the device word the library's kernels
+    count into while it is bound, its pinned host copy, and the events behind the copies still in flight.  Engines never share one, so that a saturation is
+    reported by the engine that caused it."""
+
+    def __init__(self, lib, device):
+        self.lib, self.device = lib, device
+        self.dev = self.host = None
+        self.events = []
+
+    @contextlib.contextmanager
+    def bind(self):
+        """The library's fp16 kernels launched from this thread count into THIS guard's device word (ucod_resid16_overflow_bind)."""
+        if self.dev is None:
+            self.dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+        N.check(self.lib.ucod_resid16_overflow_bind(self.dev.data_ptr()), "ucod_resid16_overflow_bind")
+        try:
+            yield
+        finally:
+            self.lib.ucod_resid16_overflow_bind(None)
+
+    def arm(self, stream):
+        """Enqueue an asynchronous copy of the device word behind the pass just launched on ``stream``."""
+        if self.host is None:
+            self.host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        with self.bind():
+            N.check(self.lib.ucod_resid16_overflow_fetch(self.host.data_ptr(), stream.cuda_stream), "ucod_resid16_overflow_fetch")
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self.events.append(ev)
+        del self.events[:-8]                                     # (only the latest copies matter: the counter never decreases)
+
+    def take(self, wait=False):
+        """The saturation count of the passes that have finished (``wait``: of every pass enqueued so far).  A non-zero count is handed out ONCE: the device word
+        and its host copy are cleared before it is returned."""
+        if self.host is None:                                    # no pass has counted anything
+            return 0
+        if wait:
+            self._drain()
+        elif not any(ev.query() for ev in self.events):
+            return 0
+        n = int(self.host[0])
+        if n > 0:
+            # before the reset: every fetch still queued on a side stream must have landed, or its (stale, non-zero) count would arrive
+            # AFTER the host word is cleared and raise a second time for the same saturation
+            self._drain()
+            with self.bind():
+                N.check(self.lib.ucod_resid16_overflow_reset(N.stream()), "ucod_resid16_overflow_reset")
+            torch.cuda.current_stream(self.device).synchronize()
+            self.host.zero_()
+        return n
+
+    def _drain(self):
+        for ev in self.events:
+            ev.synchronize()
+        self.events = []
+
+
+def _chunk_bounds(B, ns):
+    """B images as ns image-parallel sub-batches [(b0, b1), ...]."""
+    return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
+
+
+class _BackboneEngine:
+    """What every engine shares: the geometry of the checkpoint, the header of the pointer table (patch embedding, CLS, position rows) in front of its 16-slot layer
+    rows (``layer_row``), the descriptor, input checks, workspaces, side streams and the saturation guard.  The defaults below are the split pass's (f32 stream,
+    LayerNorm kernels, key-minimal); ``ViTEngine`` sets its own."""
+
+    def _setup(self, state_dict, heads, eps, device, gemm_variant, lib_half):
+        """Load the ``lib_half`` library and take the geometry from the checkpoint.  Returns (canonical dict with the MLP entries the tables hold, patch weight [D, Kpad]
+        f32 on the device, k zero-padded): the subclass converts them to its operand form."""
+        self.lib = N.load(lib_half)
+        self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
+        self.kind, self.device = c["kind"], torch.device(device)
+        self.D, self.C, self.P = c["patch_w"].shape[:3]
+        self.heads = heads
+        if self.D != heads * 64:
+            raise ValueError(f"head_dim must be 64 (D={self.D}, heads={heads})")
+        self.L = len(c["layers"])
+        self.F = c["layers"][0]["fc2_w"].shape[1]                  # the MLP hidden width (SwiGLU: after padding; fc1 then has 2 F rows)
+        self.eps, self.gemm_variant = float(eps), gemm_variant
+        self.resid, self.resid16, self.ln_fold, self.full_last_layer, self.attn_variant = "f32", False, False, False, 0
+        self.streams = 1                                           # image-parallel sub-batches on side streams (ViTEngine.forward)
+        K = self.C * self.P * self.P
+        self.Kpad = (K + 63) // 64 * 64
+        pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=self.device)
+        pw[:, :K] = self._f32(c["patch_w"]).reshape(self.D, K)
+        self._pos_src, self._pos_cache, self._pos_scale = c["pos"].detach().float().cpu(), {}, None
+        self._guard = _SaturationGuard(self.lib, self.device)
+        self._ws = self._side = self._side_ws = None
+        self.layers = []
+        return c, pw
+
+    def _f32(self, t):
+        return t.detach().to(self.device, torch.float32).contiguous()
+
+    def _pos(self, gh, gw):
+        """The position rows of a gh x gw grid (cached), times ``_pos_scale`` where the patch embedding's operands carry a scale (fp16 terms)."""
+        key = (gh, gw)
+        if key not in self._pos_cache:
+            fn = _interp_pos_dinov2 if self.kind == "dinov2" else _interp_pos_dinov1
+            pos = fn(self._pos_src, gh, gw)[0].to(self.device, torch.float32).contiguous()
+            self._pos_cache[key] = pos if self._pos_scale is None else pos * self._pos_scale
+        return self._pos_cache[key]
+
+    def _desc(self, B, H, W, L=None):
+        d = N.VitDesc()
+        d.B, d.C, d.H, d.W, d.P = B, self.C, H, W, self.P
+        d.D, d.heads, d.F, d.L, d.Kpad = self.D, self.heads, self.F, (self.L if L is None else L), self.Kpad
+        d.eps = self.eps
+        d.full_last_layer = int(self.full_last_layer)
+        d.gemm_variant, d.attn_variant = self.gemm_variant, self.attn_variant
+        d.resid16, d.ln_fold = int(self.resid16), int(self.ln_fold)
+        return d
+
+    def _table(self, gh, gw, rows=None):
+        """(ctypes table, tensors kept alive): the header, then ``rows`` (default: ``self.layers``)."""
+        ptrs = [self.patch_w, self.patch_b, self.cls, self._pos(gh, gw)]
+        for row in self.layers if rows is None else rows:
+            ptrs += row
+        return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), ptrs
+
+    def param_bytes(self):
+        return self.patch_w.numel() * 2 + sum(t.numel() * t.element_size() for l in self.layers for t in l if t is not None)
+
+    def _inputs(self, who, img, out, n_layers=None):
+        """(img as contiguous f32, key map to write, H, W) of a pass; ``who`` names the engine in the message."""
+        if n_layers is not None and not 1 <= n_layers <= self.L:
+            raise ValueError(f"n_layers must be in [1, {self.L}]")
+        if not img.is_cuda:
+            raise RuntimeError(f"{who} needs a CUDA(ROCm) tensor; there is no CPU path")
+        img = img.to(torch.float32).contiguous()
+        B, _, H, W = img.shape
+        key = out if out is not None else torch.empty(B, self.D, H // self.P, W // self.P, dtype=torch.float32, device=self.device)
+        return img, key, H, W
+
+    def _workspace(self, ws, need):
+        """``ws`` if it holds ``need`` bytes, else a new buffer that does (the caller stores it back in its slot)."""
+        if need == 0:
+            raise ValueError("unsupported ViT geometry")
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _fan_out(self, streams, bounds, fn, tensors, wait=True):
+        """Run fn(i, b0, b1) for chunk i = bounds[i] on streams[i], after everything already enqueued on the current stream.  ``tensors``: caller-stream tensors the
+        side streams touch (recorded on them so that the caching allocator does not recycle their memory early).  Returns one event per chunk; ``wait``: the
+        current stream waits for them."""
+        cur = torch.cuda.current_stream(self.device)
+        start = torch.cuda.Event()
+        start.record(cur)
+        events = []
+        for i, (st, (b0, b1)) in enumerate(zip(streams, bounds)):
+            st.wait_event(start)
+            for t in tensors:
+                t.record_stream(st)
+            with torch.cuda.stream(st):
+                fn(i, b0, b1)
+                done = torch.cuda.Event()
+                done.record(st)
+            events.append(done)
+        if wait:
+            for done in events:
+                cur.wait_event(done)
+        return events
+
+    def forward_async(self, img, out=None):
+        """Enqueue the pass on the side streams WITHOUT making the current stream wait: returns (key, events); the consumer
+        calls ``torch.cuda.current_stream().wait_event(e)`` for each event before reading ``key``.  The side streams start
+        after everything already enqueued on the current stream (so a ring of key buffers is safe to reuse)."""
+        return self.forward(img, out=out, _async=True)
+
+
+class ViTEngine(_BackboneEngine):
     """HIP ViT forward -> last-layer key map [B, D, H/P, W/P] (f32)."""
 
     def __init__(self, state_dict, heads, eps=1e-6, device="cuda", full_last_layer=False, gemm_variant=0, attn_variant=0, half="f16",
@@ -144,57 +344,25 @@ class ViTEngine:
         activations do not fit fp16 is reported instead of producing inf -> NaN key maps.
         No 16-bit configuration meets 1e-3 on trained-like weights (profiles/r06_error_budget_f16.json: every op class carries ~1e-3 of it);
         ``SplitViTEngine`` (split-operand MFMA, f32 stream: f32-equivalent) is the one that does -- the feature-cache pass uses it."""
-        self.half = half
-        self.lib = N.load(half)
         if resid not in ("auto", "f32", "f16"):
             raise ValueError(f"resid must be 'auto', 'f32' or 'f16', got {resid!r}")
-        self.resid = resid
-        self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
-        D0 = c["patch_w"].shape[0]
-        fold_shape = half == "f16" and D0 % 256 == 0 and D0 <= 1536 and attn_variant != 8       # where ucod_gemm_lnfold exists
-        self.resid16 = bool(resid == "f16" or (resid == "auto" and (half == "bf16" or (fold_shape and ln_fold is not False))))
-        self._ovf_host, self._ovf_events, self._ovf_dev = None, [], None
         if attn_variant not in (0, 1, 2, 8, 5, 66):
             raise ValueError(f"attn_variant must be 0, 1, 2, 5, 8 or 66 (laboratory kernels are reached through ops.attention(variant=...) / ops.attention_asm), got {attn_variant}")
         if ln_fold not in ("auto", True, False):
             raise ValueError(f"ln_fold must be 'auto', True or False, got {ln_fold!r}")
-        self.kind = c["kind"]
-        self.device = torch.device(device)
-        self.D = c["patch_w"].shape[0]
-        self.C = c["patch_w"].shape[1]
-        self.P = c["patch_w"].shape[2]
-        self.heads = heads
-        if self.D != heads * 64:
-            raise ValueError(f"head_dim must be 64 (D={self.D}, heads={heads})")
-        self.L = len(c["layers"])
-        self.F = c["layers"][0]["fc2_w"].shape[1]                  # the MLP hidden width (SwiGLU: after padding; fc1 then has 2 F rows)
-        self.eps = float(eps)
-        self.full_last_layer = bool(full_last_layer)
-        self.gemm_variant, self.attn_variant = gemm_variant, attn_variant
-        self.streams = 1                                           # image-parallel sub-batches on side streams (see forward)
-        K = self.C * self.P * self.P
-        self.Kpad = (K + 63) // 64 * 64
-        dev = self.device
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        bf = lambda t: ops.cast_bf16(f32(t), lib=self.lib)  # noqa: E731
-        pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=dev)
-        pw[:, :K] = f32(c["patch_w"]).reshape(self.D, K)
-        self._keep = []
-        self._pos_src = c["pos"].detach().float().cpu()
-        self._pos_cache = {}
-        self.patch_w, self.patch_b, self.cls = bf(pw), f32(c["patch_b"]), f32(c["cls"])
-        ones = torch.ones(self.D, dtype=torch.float32, device=dev)
-        self.layers = []
-        for l in c["layers"]:
-            self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), bf(l["qkv_w"]), f32(l["qkv_b"]), bf(l["proj_w"]), f32(l["proj_b"]),
-                                f32(l["ls1"]) if l["ls1"] is not None else ones, f32(l["ln2_g"]), f32(l["ln2_b"]), bf(l["fc1_w"]),
-                                f32(l["fc1_b"]), bf(l["fc2_w"]), f32(l["fc2_b"]), f32(l["ls2"]) if l["ls2"] is not None else ones])
-        for l in self.layers:
-            l += [None, None]                                      # +14 / +15: column sums of the folded weights (ln_fold tables only)
+        self.half = half
+        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, half)
+        self.resid, self.full_last_layer, self.attn_variant = resid, bool(full_last_layer), attn_variant
+        fold_shape = half == "f16" and self.D % 256 == 0 and self.D <= 1536 and attn_variant != 8       # where ucod_gemm_lnfold exists
+        self.resid16 = bool(resid == "f16" or (resid == "auto" and (half == "bf16" or (fold_shape and ln_fold is not False))))
         can_fold = fold_shape and self.resid16
         if ln_fold is True and not can_fold:
             raise ValueError("ln_fold needs half='f16' with the fp16 residual stream (resid='f16' or 'auto'), D % 256 == 0 and a 16-bit attention path")
         self.ln_fold = bool(can_fold and ln_fold is not False)
+        f32, dev = self._f32, self.device
+        bf = lambda t, name=None: ops.cast_bf16(f32(t), lib=self.lib)  # noqa: E731
+        self.patch_w, self.patch_b, self.cls = bf(pw), f32(c["patch_b"]), f32(c["cls"])
+        self.layers = [layer_row(l, bf, f32) for l in c["layers"]]
         self.fold_layers = None
         if self.ln_fold:
             self.fold_layers = []
@@ -206,13 +374,10 @@ class ViTEngine:
                 qs = torch.ones(3 * self.D, dtype=torch.float32)
                 if attn_variant != 1:
                     qs[:self.D] = 0.125 * 1.4426950408889634
-                qw, qb, qc = (t.to(dev) for t in self._fold(cpu(src["ln1_g"]), cpu(src["ln1_b"]), cpu(src["qkv_w"]), cpu(src["qkv_b"]), row_scale=qs))
-                fw, fb, fc = (t.to(dev) for t in self._fold(cpu(src["ln2_g"]), cpu(src["ln2_b"]), cpu(src["fc1_w"]), cpu(src["fc1_b"])))
                 fl = list(l)
-                fl[2], fl[3], fl[9], fl[10], fl[14], fl[15] = qw, qb, fw, fb, qc, fc
+                fl[N.QKV_W], fl[N.QKV_B], fl[N.QKV_COLSUM] = (t.to(dev) for t in self._fold(cpu(src["ln1_g"]), cpu(src["ln1_b"]), cpu(src["qkv_w"]), cpu(src["qkv_b"]), row_scale=qs))
+                fl[N.FC1_W], fl[N.FC1_B], fl[N.FC1_COLSUM] = (t.to(dev) for t in self._fold(cpu(src["ln2_g"]), cpu(src["ln2_b"]), cpu(src["fc1_w"]), cpu(src["fc1_b"])))
                 self.fold_layers.append(fl)
-        self._ws = None
-        self._ws_key = None
 
     def _fold(self, gamma, beta, w, b, row_scale=None):
         """LayerNorm(gamma, beta) followed by Linear(w, b) [* row_scale per output] as one GEMM on the un-normalised rows (include/ucod_dpl.h:
@@ -220,180 +385,76 @@ class ViTEngine:
         from .fold import fold_layernorm_linear
         return fold_layernorm_linear(gamma, beta, w, b, row_scale=row_scale, half=torch.float16)      # (the fold exists in the fp16-operand build only)
 
-    def _table(self, gh, gw, L=None):
-        """(ctypes table, tensors kept alive) of a pass over the first L layers.  With ln_fold every layer but the last OF THE PASS contributes its
-        folded entries; the last keeps the plain ones (its LayerNorm 1 runs as a kernel and feeds the key hook)."""
-        L = self.L if L is None else L
-        ptrs = [self.patch_w, self.patch_b, self.cls, self._pos(gh, gw)]
-        for i, l in enumerate(self.layers):
-            ptrs += self.fold_layers[i] if (self.ln_fold and i != L - 1) else l
-        return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), ptrs
+    def _rows(self, L=None):
+        """The rows of a pass over the first L layers.  With ln_fold every layer but the last OF THE PASS contributes its folded entries; the last keeps the
+        plain ones (its LayerNorm 1 runs as a kernel and feeds the key hook)."""
+        if not self.ln_fold:
+            return self.layers
+        last = (self.L if L is None else L) - 1
+        return [l if i == last else fl for i, (l, fl) in enumerate(zip(self.layers, self.fold_layers))]
 
     def param_bytes(self):
-        n = self.patch_w.numel() * 2
-        for l in self.layers:
-            n += sum(t.numel() * t.element_size() for t in l if t is not None)
         # the folded tables are a SECOND copy of every layer's QKV / fc1 weights (+ their folded biases and column sums); the plain copies stay because
         # the last layer of a (possibly truncated) pass runs unfolded (ADVICE r5)
-        for fl, l in zip(self.fold_layers or (), self.layers):
-            n += sum(t.numel() * t.element_size() for t, t0 in zip(fl, l) if t is not None and t is not t0)
-        return n
-
-    def _pos(self, gh, gw):
-        key = (gh, gw)
-        if key not in self._pos_cache:
-            fn = _interp_pos_dinov2 if self.kind == "dinov2" else _interp_pos_dinov1
-            self._pos_cache[key] = fn(self._pos_src, gh, gw)[0].to(self.device, torch.float32).contiguous()
-        return self._pos_cache[key]
-
-    def _desc(self, B, H, W, L=None):
-        d = N.VitDesc()
-        d.B, d.C, d.H, d.W, d.P = B, self.C, H, W, self.P
-        d.D, d.heads, d.F, d.L, d.Kpad = self.D, self.heads, self.F, (self.L if L is None else L), self.Kpad
-        d.eps = self.eps
-        d.full_last_layer = int(self.full_last_layer)
-        d.gemm_variant, d.attn_variant = self.gemm_variant, self.attn_variant
-        d.resid16 = int(self.resid16)
-        d.ln_fold = int(getattr(self, "ln_fold", False))
-        return d
-
-    # ---- fp16 residual stream: saturation guard --------------------------------------------------------------------------------
-    def _own_counter(self):
-        """Context: the library's fp16-stream kernels launched from this thread count into THIS engine's device word (ucod_resid16_overflow_bind),
-        so that one engine's saturation is never reported by another engine that shares the GPU."""
-        eng = self
-
-        class _Bound:
-            def __enter__(self_):
-                if eng._ovf_dev is None:
-                    eng._ovf_dev = torch.zeros(1, dtype=torch.int32, device=eng.device)
-                N.check(eng.lib.ucod_resid16_overflow_bind(eng._ovf_dev.data_ptr()), "ucod_resid16_overflow_bind")
-
-            def __exit__(self_, *exc):
-                eng.lib.ucod_resid16_overflow_bind(None)
-                return False
-        return _Bound()
-
-    def _arm_overflow_check(self, stream, used_resid16=None):
-        """Enqueue an asynchronous copy of the device's saturation counter behind the pass just launched on ``stream``.  ``used_resid16``:
-        whether THAT pass ran the fp16 stream (default: the engine's setting; the LoRA engine's no-grad teacher pass says so itself)."""
-        if not (self.resid16 if used_resid16 is None else used_resid16):
-            return
-        if self._ovf_host is None:
-            self._ovf_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        with self._own_counter():
-            N.check(self.lib.ucod_resid16_overflow_fetch(self._ovf_host.data_ptr(), stream.cuda_stream), "ucod_resid16_overflow_fetch")
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        self._ovf_events.append(ev)
-        del self._ovf_events[:-8]                                # (only the latest copies matter: the counter never decreases)
+        return super().param_bytes() + sum(t.numel() * t.element_size() for fl, l in zip(self.fold_layers or (), self.layers)
+                                           for t, t0 in zip(fl, l) if t is not None and t is not t0)
 
     def check_overflow(self, wait=False):
         """Raise FloatingPointError if any finished pass saturated the fp16 residual stream.  ``wait``: block until every pass enqueued so far
         has finished (otherwise only passes that already have)."""
-        n = self._take_overflow_count(wait)
+        n = self._guard.take(wait)
         if n > 0:
             how = "build the engine with resid='f32'" if self.resid16 else "call forward_nograd(..., resid16=False)"
             raise FloatingPointError(f"the fp16 residual stream of this engine saturated at +-65504 (or met a NaN) in {n} wave-lane(s)"
-                                     + (" -- or a folded LayerNorm met a row with |mean| > 256 sigma (outside the fold's range)" if getattr(self, "ln_fold", False) else "")
+                                     + (" -- or a folded LayerNorm met a row with |mean| > 256 sigma (outside the fold's range)" if self.ln_fold else "")
                                      + f": the activations do not fit this configuration; {how}.  The counter is polled without blocking: the pass (or, for a training engine, the "
                                      f"optimiser step or steps) that consumed the clamped activations has already been applied -- discard its results "
                                      f"(UCOD_CHECK_RESID=1 checks synchronously after every pass).")
-
-    def _take_overflow_count(self, wait=False):
-        """The saturation count of the passes that have finished (``wait``: of every pass enqueued so far).  A non-zero count is handed out ONCE: the device word
-        and its host copy are cleared before it is returned."""
-        if self._ovf_host is None:                              # no pass of this engine has counted anything
-            return 0
-        if wait:
-            for ev in self._ovf_events:
-                ev.synchronize()
-            self._ovf_events = []
-        elif not any(ev.query() for ev in self._ovf_events):
-            return 0
-        n = int(self._ovf_host[0])
-        if n > 0:
-            # before the reset: every fetch still queued on a side stream must have landed, or its (stale, non-zero) count would arrive
-            # AFTER the host word is cleared and raise a second time for the same saturation
-            for ev in self._ovf_events:
-                ev.synchronize()
-            self._ovf_events = []
-            with self._own_counter():
-                N.check(self.lib.ucod_resid16_overflow_reset(N.stream()), "ucod_resid16_overflow_reset")
-            torch.cuda.current_stream(self.device).synchronize()
-            self._ovf_host.zero_()
-        return n
 
     _sync_check = os.environ.get("UCOD_CHECK_RESID") == "1"    # debug: check the saturation counter synchronously after every pass
 
     def forward(self, img, out=None, _async=False, n_layers=None):
         """``n_layers``: stop after that many encoder layers and return THAT layer's key map (diagnostics: the per-layer error
         table of bench.py); default = the whole backbone."""
-        if n_layers is not None and not 1 <= n_layers <= self.L:
-            raise ValueError(f"n_layers must be in [1, {self.L}]")
-        if not img.is_cuda:
-            raise RuntimeError("ViTEngine needs a CUDA(ROCm) tensor; there is no CPU path")
-        img = img.to(torch.float32).contiguous()
-        B, Cc, H, W = img.shape
-        gh, gw = H // self.P, W // self.P
-        lib = self.lib
-        table, _keep = self._table(gh, gw, n_layers)
-        key = out if out is not None else torch.empty(B, self.D, gh, gw, dtype=torch.float32, device=self.device)
+        img, key, H, W = self._inputs("ViTEngine", img, out, n_layers)
+        B = img.shape[0]
+        table, _keep = self._table(H // self.P, W // self.P, self._rows(n_layers))
         self.check_overflow()                                      # (non-blocking) passes that have finished since the last call
-        ns = max(1, min(int(getattr(self, "streams", 1)), B))
-        if ns == 1 and not _async:
-            d = self._desc(B, H, W, n_layers)
-            need = lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp)
-            if need == 0:
-                raise ValueError("unsupported ViT geometry")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            with self._own_counter():
-                N.check(lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(self._ws), self._ws.numel(), N.stream()),
+
+        def launch(b0, b1, ws):
+            """images b0..b1 on the current stream, in ``ws`` or a larger workspace, which is returned"""
+            d = self._desc(b1 - b0, H, W, n_layers)
+            ws = self._workspace(ws, self.lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp))
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
                         "ucod_vit_forward")
-            self._arm_overflow_check(torch.cuda.current_stream(self.device))
+            if self.resid16:
+                self._guard.arm(torch.cuda.current_stream(self.device))
+            return ws
+
+        ns = max(1, min(int(self.streams), B))
+        if ns == 1 and not _async:
+            self._ws = launch(0, B, self._ws)
             if self._sync_check:
                 self.check_overflow(wait=True)
             return key
         # Image-parallel sub-batches on independent HIP streams: every kernel of the pass is per-image, so the halves are
         # independent and the tail of one stream's GEMM (a partial last round of 256-row tiles leaves most CUs idle) is filled by
         # the other stream's next kernel.  Results are identical to the single-stream pass (same kernels, same per-image math).
-        if getattr(self, "_side", None) is None or len(self._side) != ns:
+        if self._side is None or len(self._side) != ns:
             # Normal priority.  High-priority side streams (UCOD_SIDE_PRIORITY=-1) were measured: nothing on the pipelined frozen-backbone
             # step (10.16 vs 10.19 ms) and MINUS 17 % in backbone-backward mode (585 vs 702 images/s: the EMA teacher's pass on these
             # streams then starves the student's forward / backward on the training streams).
             prio = int(os.environ.get("UCOD_SIDE_PRIORITY", "0"))
             self._side = [torch.cuda.Stream(device=self.device, priority=prio) for _ in range(ns)]
             self._side_ws = [None] * ns
-        cur = torch.cuda.current_stream(self.device)
-        start = torch.cuda.Event()
-        start.record(cur)
-        bounds = [B * i // ns for i in range(ns + 1)]
-        events = []
-        for i in range(ns):
-            b0, b1 = bounds[i], bounds[i + 1]
-            d = self._desc(b1 - b0, H, W, n_layers)
-            need = lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp)
-            if need == 0:
-                raise ValueError("unsupported ViT geometry")
-            if self._side_ws[i] is None or self._side_ws[i].numel() < need:
-                self._side_ws[i] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            st = self._side[i]
-            st.wait_event(start)
-            img.record_stream(st)                                  # allocated on the caller's stream, consumed on this one: keep the
-            key.record_stream(st)                                  # caching allocator from recycling them before this stream is done
-            with torch.cuda.stream(st):
-                with self._own_counter():
-                    N.check(lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(self._side_ws[i]),
-                                                     self._side_ws[i].numel(), N.stream()), "ucod_vit_forward")
-                self._arm_overflow_check(st)
-                done = torch.cuda.Event()
-                done.record(st)
-            events.append(done)
+
+        def run(i, b0, b1):
+            self._side_ws[i] = launch(b0, b1, self._side_ws[i])
+
+        events = self._fan_out(self._side, _chunk_bounds(B, ns), run, (img, key), wait=not _async)
         if _async:
             return key, events
-        for done in events:
-            cur.wait_event(done)
         if self._sync_check:
             self.check_overflow(wait=True)
         return key
@@ -418,21 +479,15 @@ class ViTEngine:
         last = self.layers[-1]
         q = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
         k = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
-        N.check(lib.ucod_cls_qk(self._ws.data_ptr() + off, N.ptr(last[2]), N.ptr(last[3]), N.ptr(q), N.ptr(k), B, tok, self.D, N.stream()), "ucod_cls_qk")
+        N.check(lib.ucod_cls_qk(self._ws.data_ptr() + off, N.ptr(last[N.QKV_W]), N.ptr(last[N.QKV_B]), N.ptr(q), N.ptr(k), B, tok, self.D, N.stream()), "ucod_cls_qk")
         att = torch.empty(B, self.heads, tok - 1, dtype=torch.float32, device=self.device)
         N.check(lib.ucod_cls_attention(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, tok - 1, 0.125, N.stream()), "ucod_cls_attention")
         return key, att
 
-    def forward_async(self, img, out=None):
-        """Enqueue the pass on the side streams WITHOUT making the current stream wait: returns (key, events); the consumer
-        calls ``torch.cuda.current_stream().wait_event(e)`` for each event before reading ``key``.  The side streams start
-        after everything already enqueued on the current stream (so a ring of key buffers is safe to reuse)."""
-        return self.forward(img, out=out, _async=True)
-
     __call__ = forward
 
 
-class SplitViTEngine:
+class SplitViTEngine(_BackboneEngine):
     """The frozen backbone at the REFERENCE's cached-feature precision: HIP ViT forward -> last-layer key map [B, D, H/P, W/P] (f32) with every matrix product
     computed on split operands (include/ucod_dpl.h: "split-operand backbone pass"; csrc/split.hip) -- f32 residual stream, f32 LayerNorm, exact-erf GELU,
     f32 softmax, each f32 GEMM / attention operand as a sum of ``terms`` bf16 values on the bf16 MFMA:
@@ -464,166 +519,84 @@ class SplitViTEngine:
         self.fuse_mlp = bool(fuse_mlp)
         self._flags = N.SPLIT16_FUSE_MLP if self.fuse_mlp else 0
         f16 = term == "f16"
-        self.lib = N.load("f16" if f16 else "bf16")               # (each term type has its MFMA; either build refuses the other's split entry points)
+        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, "f16" if f16 else "bf16")    # (each term type has its MFMA; either build refuses the other's split entry points)
         self.nprod = ops.split_products(terms)
-        self.mlp, c = _prepare_mlp(normalize_state_dict(state_dict))
-        self.kind, self.device = c["kind"], torch.device(device)
-        self.D, self.C, self.P = c["patch_w"].shape[0], c["patch_w"].shape[1], c["patch_w"].shape[2]
-        self.heads = heads
-        if self.D != heads * 64:
-            raise ValueError(f"head_dim must be 64 (D={self.D}, heads={heads})")
-        self.L, self.F, self.eps = len(c["layers"]), c["layers"][0]["fc2_w"].shape[1], float(eps)
-        self.gemm_variant, self.streams = gemm_variant, 1
-        self.resid16 = self.ln_fold = self.full_last_layer = False
-        self.resid, self.attn_variant = "f32", 0
-        self._ovf_host, self._ovf_events, self._ovf_dev = None, [], None
-        K = self.C * self.P * self.P
-        self.Kpad = (K + 63) // 64 * 64
-        dev = self.device
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=dev)
-        pw[:, :K] = f32(c["patch_w"]).reshape(self.D, K)
-        self._pos_src, self._pos_cache = c["pos"].detach().float().cpu(), {}
-        ones = torch.ones(self.D, dtype=torch.float32, device=dev)
-        self.layers = []
-        D = self.D
+        f32, D = self._f32, self.D
+        sw = lambda t, s=1.0, role=1: ops.split_rows(f32(t), self.terms, role, term=term, scale=s)  # noqa: E731      (role 1: weights are the B side of y = x W^T)
+        # fp16 terms: every weight carries a power-of-two scale s_w, and S = (activation class scale) x s_w of each GEMM goes into its bias (for the patch embedding
+        # also the CLS and position rows) and out of its LayerScale vector, so that the stream is bit for bit what the unscaled product would give (csrc/split16.hip)
+        wscale = ops.pow2_scale if f16 else (lambda t: 1.0)
+        act = [ops.split16_class_scale(k) for k in (N.SPLIT16_LN, N.SPLIT16_ATT, N.SPLIT16_LN, N.SPLIT16_HIDDEN)] if f16 else None
+        self.wscale = [wscale(pw)]                                # [patch, (qkv, proj, fc1, fc2) x L]: what the fp16-term driver reads
+        self.patch_w, self.patch_b, self.cls = sw(pw, self.wscale[0]), f32(c["patch_b"]), f32(c["cls"])
         if f16:
-            # S = (activation class scale) x (weight scale) of each GEMM: its bias (and, for the patch embedding, the CLS and position rows) goes in times S, its
-            # LayerScale vector divided by S -- powers of two, so the stream is bit for bit what the unscaled product would give (csrc/split16.hip)
-            cls_s = {k: ops.split16_class_scale(getattr(N, "SPLIT16_" + k)) for k in ("LN", "ATT", "HIDDEN", "PATCH")}
-            sw16 = lambda t, s, role=1: ops.split_rows(f32(t), 2, role, term="f16", scale=s)  # noqa: E731
-            s_pw = ops.pow2_scale(pw)
-            self._S_patch = cls_s["PATCH"] * s_pw
-            self.wscale = [s_pw]
-            self.patch_w, self.patch_b, self.cls = sw16(pw, s_pw), f32(c["patch_b"]) * self._S_patch, f32(c["cls"]) * self._S_patch
-            for l in c["layers"]:
-                s_qkv, s_proj, s_fc1, s_fc2 = (ops.pow2_scale(l[k]) for k in ("qkv_w", "proj_w", "fc1_w", "fc2_w"))
-                S_qkv, S_proj, S_fc1, S_fc2 = cls_s["LN"] * s_qkv, cls_s["ATT"] * s_proj, cls_s["LN"] * s_fc1, cls_s["HIDDEN"] * s_fc2
-                self.wscale += [s_qkv, s_proj, s_fc1, s_fc2]
-                ls1 = f32(l["ls1"]) if l["ls1"] is not None else ones
-                ls2 = f32(l["ls2"]) if l["ls2"] is not None else ones
-                self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), sw16(l["qkv_w"], s_qkv), f32(l["qkv_b"]) * S_qkv, sw16(l["proj_w"], s_proj), f32(l["proj_b"]) * S_proj,
-                                    ls1 / S_proj, f32(l["ln2_g"]), f32(l["ln2_b"]), sw16(l["fc1_w"], s_fc1), f32(l["fc1_b"]) * S_fc1, sw16(l["fc2_w"], s_fc2),
-                                    f32(l["fc2_b"]) * S_fc2, ls2 / S_fc2, sw16(l["qkv_w"][D:2 * D], s_qkv, role=0), None])
-            self._wscale_c = (C.c_float * len(self.wscale))(*self.wscale)
-        else:
-            sw = lambda t, role=1: ops.split_rows(f32(t), self.terms, role)  # noqa: E731      (weights: the B side of y = x W^T)
-            self.patch_w, self.patch_b, self.cls = sw(pw), f32(c["patch_b"]), f32(c["cls"])
-            for l in c["layers"]:
-                self.layers.append([f32(l["ln1_g"]), f32(l["ln1_b"]), sw(l["qkv_w"]), f32(l["qkv_b"]), sw(l["proj_w"]), f32(l["proj_b"]),
-                                    f32(l["ls1"]) if l["ls1"] is not None else ones, f32(l["ln2_g"]), f32(l["ln2_b"]), sw(l["fc1_w"]),
-                                    f32(l["fc1_b"]), sw(l["fc2_w"]), f32(l["fc2_b"]), f32(l["ls2"]) if l["ls2"] is not None else ones,
-                                    sw(l["qkv_w"][D:2 * D], role=0), None])      # +14: the K rows as the A side of the key hook's GEMM
-        last = c["layers"][-1]                                   # f32 copies for forward_with_cls_attention: the CLS query / key of the LAST layer
+            self._pos_scale = ops.split16_class_scale(N.SPLIT16_PATCH) * self.wscale[0]
+            self.patch_b, self.cls = self.patch_b * self._pos_scale, self.cls * self._pos_scale
+        for l in c["layers"]:
+            s = {g + "_w": wscale(l[g + "_w"]) for g in _GEMMS}
+            self.wscale += s.values()
+            self.layers.append(layer_row(l, lambda t, name: sw(t, s[name]), f32, scales=[a * w for a, w in zip(act, s.values())] if f16 else None,
+                                         aux=(sw(l["qkv_w"][D:2 * D], s["qkv_w"], role=0), None)))       # +14: the K rows as the A side of the key hook's GEMM
+        self._wscale_c = (C.c_float * len(self.wscale))(*self.wscale)
+        last = c["layers"][-1]                        # f32 copies for forward_with_cls_attention: the CLS query / key of the LAST layer
         self._last = dict(ln_g=f32(last["ln1_g"]), ln_b=f32(last["ln1_b"]), wq=f32(last["qkv_w"][:D]), bq=f32(last["qkv_b"][:D]),
                           wk=f32(last["qkv_w"][D:2 * D]), bk=f32(last["qkv_b"][D:2 * D]))
-        self._ws = None
-        self._side = self._side_ws = None
 
-    _desc = ViTEngine._desc
-    _own_counter = ViTEngine._own_counter
-    _arm_overflow_check = ViTEngine._arm_overflow_check
-
-    def _pos(self, gh, gw):
-        """(fp16 terms: the position rows times the patch embedding's operand scales, like its bias)"""
-        key = (gh, gw)
-        if key not in self._pos_cache:
-            pos = ViTEngine._pos(self, gh, gw)
-            self._pos_cache[key] = pos * self._S_patch if self.term == "f16" else pos
-        return self._pos_cache[key]
-
-    def param_bytes(self):
-        return self.patch_w.numel() * 2 + sum(t.numel() * t.element_size() for l in self.layers for t in l if t is not None)
+    def _wscale_of(self, layer, gemm):
+        """the weight scale of ``layer``'s GEMM ``gemm`` (a name of _GEMMS) in ``wscale``"""
+        return self.wscale[1 + len(_GEMMS) * layer + _GEMMS.index(gemm)]
 
     def check_overflow(self, wait=False):
         """bf16 terms: nothing can saturate (bf16 has f32's range; interface of ViTEngine).  fp16 terms: raise FloatingPointError if a finished pass clamped an
         operand to +-65504 (or met a NaN) -- its key map is wrong and must be discarded.  ``wait``: block until every pass enqueued so far has finished."""
         if self.term != "f16":
             return None
-        n = self._take_overflow_count(wait)
+        n = self._guard.take(wait)
         if n > 0:
             raise FloatingPointError(f"the fp16-term split pass (split2h / split2hf) clamped {n} operand element(s) to +-65504 (or met a NaN): an activation exceeded the bound of its "
                                      f"operand class (csrc/split16.hip) and the key maps of that pass are wrong -- use precision='split3' ('f32eq') for this checkpoint / "
                                      f"input.  The counter is polled without blocking; check_overflow(wait=True) checks every pass enqueued so far.")
 
-    _take_overflow_count = ViTEngine._take_overflow_count
-
-    def _table(self, gh, gw):
-        ptrs = [self.patch_w, self.patch_b, self.cls, self._pos(gh, gw)]
-        for l in self.layers:
-            ptrs += l
-        return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), ptrs
-
     def _ws_bytes(self, d):
-        if self.fuse_mlp:
-            return self.lib.ucod_vit_split16_workspace_bytes_ex(C.byref(d), self.mlp, self._flags)
         if self.term == "f16":
-            return self.lib.ucod_vit_split16_workspace_bytes(C.byref(d), self.mlp)
+            return self.lib.ucod_vit_split16_workspace_bytes_ex(C.byref(d), self.mlp, self._flags)
         return self.lib.ucod_vit_split_workspace_bytes_mlp(C.byref(d), self.terms, self.mlp)
 
     def _stream_offset(self, d):
-        if self.fuse_mlp:
-            return self.lib.ucod_vit_split16_stream_offset_ex(C.byref(d), self.mlp, self._flags)
         if self.term == "f16":
-            return self.lib.ucod_vit_split16_stream_offset(C.byref(d), self.mlp)
+            return self.lib.ucod_vit_split16_stream_offset_ex(C.byref(d), self.mlp, self._flags)
         return self.lib.ucod_vit_split_stream_offset_mlp(C.byref(d), self.terms, self.mlp)
 
-    def _run(self, img, key, ws_slot, n_layers=None):
+    def _run(self, img, key, ws, n_layers=None):
+        """The pass on the current stream, in ``ws`` or a larger workspace, which is returned."""
         B, _, H, W = img.shape
         d = self._desc(B, H, W, n_layers)
-        d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        need = self._ws_bytes(d)
-        if need == 0:
-            raise ValueError("unsupported ViT geometry")
-        ws = ws_slot[0]
-        if ws is None or ws.numel() < need:
-            ws = ws_slot[0] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace(ws, self._ws_bytes(d))
         table, _keep = self._table(H // self.P, W // self.P)
         if self.term == "f16":
-            L = d.L
             self.check_overflow()                                  # (non-blocking) passes that have finished since the last call
-            with self._own_counter():
-                if self.fuse_mlp:
-                    N.check(self.lib.ucod_vit_forward_split16_ex(C.byref(d), self.mlp, self._flags, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws),
-                                                                 ws.numel(), N.stream()), "ucod_vit_forward_split16_ex")
-                else:
-                    N.check(self.lib.ucod_vit_forward_split16(C.byref(d), self.mlp, table, self._wscale_c, 1 + 4 * L, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(),
-                                                              N.stream()), "ucod_vit_forward_split16")
-            self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=True)
-            return
-        N.check(self.lib.ucod_vit_forward_split_mlp(C.byref(d), self.terms, self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
-                "ucod_vit_forward_split")
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_split16_ex(C.byref(d), self.mlp, self._flags, table, self._wscale_c, 1 + len(_GEMMS) * d.L, N.ptr(img), N.ptr(key),
+                                                             N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_forward_split16_ex")
+            self._guard.arm(torch.cuda.current_stream(self.device))
+        else:
+            N.check(self.lib.ucod_vit_forward_split_mlp(C.byref(d), self.terms, self.mlp, table, N.ptr(img), N.ptr(key), N.ptr(ws), ws.numel(), N.stream()),
+                    "ucod_vit_forward_split")
+        return ws
 
     def forward(self, img, out=None, _async=False, n_layers=None):
-        if n_layers is not None and not 1 <= n_layers <= self.L:
-            raise ValueError(f"n_layers must be in [1, {self.L}]")
-        if not img.is_cuda:
-            raise RuntimeError("SplitViTEngine needs a CUDA(ROCm) tensor; there is no CPU path")
-        img = img.to(torch.float32).contiguous()
-        B, _, H, W = img.shape
-        key = out if out is not None else torch.empty(B, self.D, H // self.P, W // self.P, dtype=torch.float32, device=self.device)
+        img, key, H, W = self._inputs("SplitViTEngine", img, out, n_layers)
         if not _async:
-            if self._ws is None:
-                self._ws = [None]
-            self._run(img, key, self._ws, n_layers)
+            self._ws = self._run(img, key, self._ws, n_layers)
             return key
         # forward_async: the whole pass on ONE side stream (its workspace is several GB at batch 32: no image-parallel halves here)
         if self._side is None:
-            self._side, self._side_ws = torch.cuda.Stream(device=self.device), [None]
-        cur = torch.cuda.current_stream(self.device)
-        start = torch.cuda.Event()
-        start.record(cur)
-        self._side.wait_event(start)
-        img.record_stream(self._side)
-        key.record_stream(self._side)
-        with torch.cuda.stream(self._side):
-            self._run(img, key, self._side_ws, n_layers)
-            done = torch.cuda.Event()
-            done.record(self._side)
-        return key, [done]
+            self._side, self._side_ws = [torch.cuda.Stream(device=self.device)], [None]
 
-    def forward_async(self, img, out=None):
-        return self.forward(img, out=out, _async=True)
+        def run(i, b0, b1):
+            self._side_ws[i] = self._run(img, key, self._side_ws[i], n_layers)
+
+        return key, self._fan_out(self._side, _chunk_bounds(img.shape[0], 1), run, (img, key), wait=False)
 
     def forward_with_cls_attention(self, img):
         """(key [B,D,h,w], att [B,heads,h*w]) like ``ViTEngine.forward_with_cls_attention``: the key map plus ``outputs.attentions[-1][:, :, 0, 1:]`` of the HF model
@@ -632,20 +605,18 @@ class SplitViTEngine:
         workspace, normalised by the f32 LayerNorm kernel, projected to the CLS query / key on split operands, and fed to the f32 attention-row kernel."""
         key = self.forward(img)
         B, _, H, W = img.shape
-        d = self._desc(B, H, W)
-        d.resid16 = d.ln_fold = d.full_last_layer = d.attn_variant = 0
-        off = self._stream_offset(d)
+        off = self._stream_offset(self._desc(B, H, W))
         tok = key.shape[-2] * key.shape[-1] + 1
-        x = self._ws[0][off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
+        x = self._ws[off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
         L_ = self._last
         h_cls = ops.layernorm(x[:, 0].contiguous(), L_["ln_g"], L_["ln_b"], self.eps, out_f32=True)
         if self.term == "f16":
             # the scales of the pass itself, known at load: the LayerNorm class scale for the rows, the last layer's QKV weight scale (no device-to-host read here)
-            sc = dict(term="f16", x_scale=ops.split16_class_scale(N.SPLIT16_LN), w_scale=self.wscale[-4])
-            with self._own_counter():
+            sc = dict(term="f16", x_scale=ops.split16_class_scale(N.SPLIT16_LN), w_scale=self._wscale_of(self.L - 1, "qkv"))
+            with self._guard.bind():
                 q = ops.linear_split(h_cls, L_["wq"], L_["bq"], 2, **sc)
                 k = ops.linear_split(h_cls, L_["wk"], L_["bk"], 2, **sc)
-            self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=True)
+            self._guard.arm(torch.cuda.current_stream(self.device))
         else:
             q = ops.linear_split(h_cls, L_["wq"], L_["bq"], self.terms)
             k = ops.linear_split(h_cls, L_["wk"], L_["bk"], self.terms)
@@ -657,6 +628,7 @@ class SplitViTEngine:
 
 
 _QKV = ("query", "key", "value")
+_MASK64 = 0xFFFFFFFFFFFFFFFF
 
 
 class ViTLoRAEngine(ViTEngine):
@@ -700,14 +672,14 @@ class ViTLoRAEngine(ViTEngine):
             self.lora[:, p * 2 * r * D:p * 2 * r * D + r * D] = a[:, p].to(dev)
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
-        self.train_layers = []
+        self.train_layers = []                          # rows of the training table without its two LoRA slots (native.VIT_TRAIN_SLOTS)
         for l in self.layers:
-            qkv_w, proj_w, fc1_w, fc2_w = l[2], l[4], l[9], l[11]
             w_aug = torch.zeros(3 * D, D + A, dtype=torch.bfloat16, device=dev)
-            w_aug[:, :D] = qkv_w
+            w_aug[:, :D] = l[N.QKV_W]
             wt_aug = torch.zeros(D, 3 * D + A, dtype=torch.bfloat16, device=dev)
-            wt_aug[:, :3 * D] = qkv_w.t()
-            self.train_layers.append([w_aug, wt_aug, proj_w.t().contiguous(), fc1_w.t().contiguous(), fc2_w.t().contiguous()])
+            wt_aug[:, :3 * D] = l[N.QKV_W].t()
+            self.train_layers.append([w_aug, wt_aug] + [l[w].t().contiguous() for w in (N.PROJ_W, N.FC1_W, N.FC2_W)])
+        self.train_streams = 2                          # image-parallel sub-batches of the training passes (_chunks)
         self._tside = None
         self._saved_for = None
         self.repack()
@@ -751,92 +723,69 @@ class ViTLoRAEngine(ViTEngine):
     def repack(self):
         """Refresh the LoRA columns of the augmented weights (call after every parameter update).  With dropout active the A^T
         columns of the dgrad weight are zero: the masked t A term is added by the LayerNorm-1 backward instead."""
-        lib = N.load()
         zero_a = int(self._drop_p() > 0.0)
         for i, tl in enumerate(self.train_layers):
-            N.check(lib.ucod_lora_pack(N.ptr(self.lora[i]), self.r, self.scaling, N.ptr(tl[0]), N.ptr(tl[1]), self.D, zero_a, N.stream()), "ucod_lora_pack")
+            N.check(self.lib.ucod_lora_pack(N.ptr(self.lora[i]), self.r, self.scaling, N.ptr(tl[N.T_QKV_W_AUG]), N.ptr(tl[N.T_QKV_WT_AUG]), self.D, zero_a, N.stream()),
+                    "ucod_lora_pack")
         self._packed_zero_a = zero_a
 
     # ---- passes -----------------------------------------------------------------------------------------------------
-    def _train_desc(self, B, H, W):
+    def _train_desc(self, B, H, W, seed):
         t = N.VitTrainDesc()
         t.vit = self._desc(B, H, W)
         t.lora_r, t.lora_scaling = self.r, self.scaling
-        t.lora_dropout, t.seed = self._drop_p(), self._step_seed
+        t.lora_dropout, t.seed = self._drop_p(), seed
         return t
 
-    def _tables(self, gh, gw, grad=None):
-        pos = self._pos(gh, gw)
-        ptrs = [self.patch_w, self.patch_b, self.cls, pos]
-        for l in self.layers:
-            ptrs += l
-        grad = self.lora_grad if grad is None else grad
+    def _tables(self, gh, gw, grad):
+        """(table of the plain rows, training table with ``grad`` [L, 6 r D] in its gradient slots, tensors kept alive)"""
+        T, keep = self._table(gh, gw)
         tptrs = []
         for i, tl in enumerate(self.train_layers):
             tptrs += tl + [self.lora[i], grad[i]]
-        keep = ptrs + tptrs
-        return (C.c_void_p * len(ptrs))(*[None if t is None else t.data_ptr() for t in ptrs]), (C.c_void_p * len(tptrs))(*[t.data_ptr() for t in tptrs]), keep
+        return T, (C.c_void_p * len(tptrs))(*[t.data_ptr() for t in tptrs]), keep + tptrs
 
     def _chunks(self, B):
         """Image-parallel sub-batches (``self.train_streams``, default 2): as in ViTEngine.forward, every kernel of both passes is
         per image except the LoRA-gradient reduction over rows, which is done per chunk into its own buffer and summed at the end."""
-        ns = max(1, min(int(getattr(self, "train_streams", 2)), B))
-        if getattr(self, "_tside", None) is None or len(self._tside) != ns:
+        ns = max(1, min(int(self.train_streams), B))
+        if self._tside is None or len(self._tside) != ns:
             self._tside = [torch.cuda.Stream(device=self.device) for _ in range(ns)]
-            self._tside_ws = [None] * ns
+            self._tside_ws, self._iside_ws = [None] * ns, [None] * ns          # workspaces of forward_train (+ backward) / forward_nograd
             self._tside_grad = [torch.zeros_like(self.lora) for _ in range(ns)]
             self._chunk_seed = [0] * ns
-        return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
+        return _chunk_bounds(B, ns)
 
-    def _fan_out(self, fn, tensors=()):
-        """Run fn(i, b0, b1) for every chunk on its side stream, between two events on the current stream.  ``tensors``: caller-stream
-        tensors the side streams touch (recorded on them so the caching allocator does not recycle their memory early)."""
-        cur = torch.cuda.current_stream(self.device)
-        start = torch.cuda.Event()
-        start.record(cur)
-        for i, (b0, b1) in enumerate(self._bounds):
-            st = self._tside[i]
-            st.wait_event(start)
-            for t in tensors:
-                t.record_stream(st)
-            with torch.cuda.stream(st):
-                fn(i, b0, b1)
-                done = torch.cuda.Event()
-                done.record(st)
-            cur.wait_event(done)
-
-    def forward_train(self, img, out=None):
-        if not img.is_cuda:
-            raise RuntimeError("ViTLoRAEngine needs a CUDA(ROCm) tensor; there is no CPU path")
-        img = img.to(torch.float32).contiguous()
-        B, _, H, W = img.shape
-        gh, gw = H // self.P, W // self.P
-        lib = N.load()
-        key = out if out is not None else torch.empty(B, self.D, gh, gw, dtype=torch.float32, device=self.device)
-        self.check_overflow()                                      # (non-blocking) training passes on the fp16 stream that have finished since the last call
+    def _begin_step(self, B):
+        """What every pass starts with: its chunks, the next step's dropout seed, and the augmented weights in the form the current mode needs."""
         self._bounds = self._chunks(B)
         self._step += 1
-        self._step_seed = (self._seed * 0x9E3779B97F4A7C15 + self._step) & 0xFFFFFFFFFFFFFFFF     # fresh masks every step
-        if int(self._drop_p() > 0.0) != getattr(self, "_packed_zero_a", 0):
+        self._step_seed = (self._seed * 0x9E3779B97F4A7C15 + self._step) & _MASK64      # fresh masks every step
+        if int(self._drop_p() > 0.0) != self._packed_zero_a:
             self.repack()                                           # train()/eval() changed which side carries the A term
 
-        def run(i, b0, b1):
-            t = self._train_desc(b1 - b0, H, W)
-            t.seed = (self._step_seed + 0x51ED270B * (i + 1) * int(b0 > 0)) & 0xFFFFFFFFFFFFFFFF   # (chunks index rows from 0: decorrelate them)
-            self._chunk_seed[i] = t.seed
-            need = lib.ucod_vit_train_workspace_bytes(C.byref(t))
-            if need == 0:
-                raise ValueError("unsupported ViT geometry")
-            if self._tside_ws[i] is None or self._tside_ws[i].numel() < need:
-                self._tside_ws[i] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
-            with self._own_counter():
-                N.check(lib.ucod_vit_forward_train(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(self._tside_ws[i]),
-                                                   self._tside_ws[i].numel(), N.stream()), "ucod_vit_forward_train")
-            self._arm_overflow_check(torch.cuda.current_stream(self.device))     # (no-op with the f32 stream)
+    def _seed_of_chunk(self, i, b0):
+        """(chunks index rows from 0: decorrelate them)"""
+        return (self._step_seed + 0x51ED270B * (i + 1) * int(b0 > 0)) & _MASK64
 
-        self._fan_out(run, (img, key))
-        self._saved_for = (B, H, W)
+    def forward_train(self, img, out=None):
+        img, key, H, W = self._inputs("ViTLoRAEngine", img, out)
+        gh, gw = H // self.P, W // self.P
+        self.check_overflow()                                      # (non-blocking) training passes on the fp16 stream that have finished since the last call
+        self._begin_step(img.shape[0])
+
+        def run(i, b0, b1):
+            t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
+            self._chunk_seed[i] = t.seed
+            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes(C.byref(t)))
+            T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_train(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_forward_train")
+            if self.resid16:
+                self._guard.arm(torch.cuda.current_stream(self.device))
+
+        self._fan_out(self._tside, self._bounds, run, (img, key))
+        self._saved_for = (img.shape[0], H, W)
         return key
 
     def forward_nograd(self, img, out=None, resid16=True):
@@ -844,41 +793,25 @@ class ViTLoRAEngine(ViTEngine):
         torch.no_grad()): same arithmetic as ``forward_train`` (LoRA aug columns, dropout masks of this engine's own seed stream when in
         train mode) with nothing saved, an inference-sized workspace and, by default, the fp16 residual stream of the frozen-backbone pass
         (bf16 operands: the stream's rounding is 8x finer than theirs).  Image-parallel chunks on the training side streams."""
-        if not img.is_cuda:
-            raise RuntimeError("ViTLoRAEngine needs a CUDA(ROCm) tensor; there is no CPU path")
-        img = img.to(torch.float32).contiguous()
-        B, _, H, W = img.shape
+        img, key, H, W = self._inputs("ViTLoRAEngine", img, out)
         gh, gw = H // self.P, W // self.P
-        lib = N.load()
-        key = out if out is not None else torch.empty(B, self.D, gh, gw, dtype=torch.float32, device=self.device)
-        self._bounds = self._chunks(B)
-        self._step += 1
-        self._step_seed = (self._seed * 0x9E3779B97F4A7C15 + self._step) & 0xFFFFFFFFFFFFFFFF
-        if int(self._drop_p() > 0.0) != getattr(self, "_packed_zero_a", 0):
-            self.repack()
-        if getattr(self, "_iside_ws", None) is None or len(self._iside_ws) != len(self._tside):
-            self._iside_ws = [None] * len(self._tside)
-
+        self._begin_step(img.shape[0])
         self.check_overflow()                                      # (non-blocking) teacher passes that have finished since the last call
 
         def run(i, b0, b1):
-            t = self._train_desc(b1 - b0, H, W)
+            t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             t.vit.resid16 = int(bool(resid16))
-            t.seed = (self._step_seed + 0x51ED270B * (i + 1) * int(b0 > 0)) & 0xFFFFFFFFFFFFFFFF
-            need = lib.ucod_vit_lora_infer_workspace_bytes(C.byref(t))
-            if need == 0:
-                raise ValueError("unsupported ViT geometry")
-            if self._iside_ws[i] is None or self._iside_ws[i].numel() < need:
-                self._iside_ws[i] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes(C.byref(t)))
             T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
-            with self._own_counter():
-                N.check(lib.ucod_vit_forward_lora_infer(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(self._iside_ws[i]),
-                                                        self._iside_ws[i].numel(), N.stream()), "ucod_vit_forward_lora_infer")
-            # this engine's own stream type is f32 (its backward reads it), but THIS pass may run the fp16 one: its saturation counter is
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_lora_infer(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_forward_lora_infer")
+            # this engine's own stream type may be f32 (its backward reads it), but THIS pass may run the fp16 one: its saturation counter is
             # fetched behind every chunk and polled by the next call / check_overflow(wait=True) at the loop's boundaries
-            self._arm_overflow_check(torch.cuda.current_stream(self.device), used_resid16=bool(resid16))
+            if resid16:
+                self._guard.arm(torch.cuda.current_stream(self.device))
 
-        self._fan_out(run, (img, key))
+        self._fan_out(self._tside, self._bounds, run, (img, key))
         return key
 
     def backward(self, dkey):
@@ -890,34 +823,37 @@ class ViTLoRAEngine(ViTEngine):
         dkey = dkey.to(torch.float32).contiguous()
         if tuple(dkey.shape) != (B, self.D, gh, gw):
             raise ValueError(f"dkey shape {tuple(dkey.shape)} != {(B, self.D, gh, gw)}")
-        lib = N.load()
 
         def run(i, b0, b1):
-            t = self._train_desc(b1 - b0, H, W)
-            t.seed = self._chunk_seed[i]
+            t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
             T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
-            N.check(lib.ucod_vit_backward(C.byref(t), T, TT, N.ptr(dkey[b0:b1]), N.ptr(self._tside_ws[i]), self._tside_ws[i].numel(), N.stream()),
-                    "ucod_vit_backward")
+            ws = self._tside_ws[i]
+            N.check(self.lib.ucod_vit_backward(C.byref(t), T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
 
-        self._fan_out(run, (dkey,))
-        torch.sum(torch.stack(self._tside_grad[:len(self._bounds)]), dim=0, out=self.lora_grad) if len(self._bounds) > 1 else self.lora_grad.copy_(self._tside_grad[0])
+        self._fan_out(self._tside, self._bounds, run, (dkey,))
+        if len(self._bounds) > 1:
+            torch.sum(torch.stack(self._tside_grad[:len(self._bounds)]), dim=0, out=self.lora_grad)
+        else:
+            self.lora_grad.copy_(self._tside_grad[0])
         self._saved_for = None
         return self.lora_grad
 
     # ---- torch.autograd / nn.Module integration ----------------------------------------------------------------------
     def clone_for_ema(self):
         """A second engine over the SAME frozen weight tensors with its own LoRA arena (models/modules/full_model.py:84:
-        ``backbone_ema = copy.deepcopy(backbone)``; only the LoRA matrices can ever differ, so only they are duplicated)."""
+        ``backbone_ema = copy.deepcopy(backbone)``; only the LoRA matrices can ever differ, so only they are duplicated) and its own
+        saturation guard: the clone's passes are reported by the clone."""
         other = object.__new__(ViTLoRAEngine)
         other.__dict__.update(self.__dict__)
         other.lora = self.lora.clone()
         other.lora_grad = torch.zeros_like(self.lora)
-        other.train_layers = [[tl[0].clone(), tl[1].clone()] + tl[2:] for tl in self.train_layers]
+        other.train_layers = [[t.clone() if s in (N.T_QKV_W_AUG, N.T_QKV_WT_AUG) else t for s, t in enumerate(tl)] for tl in self.train_layers]
         other._tside, other._saved_for = None, None
+        other._guard = _SaturationGuard(self.lib, self.device)
         other._pos_cache = dict(self._pos_cache)
         # The reference's teacher is a deepcopy that stays in train mode (full_model.py:84; nobody calls eval() on it), so its LoRA
         # dropout is active too, with masks drawn independently of the student's: own seed stream, own step counter.
-        other._seed = (self._seed * 0x2545F4914F6CDD1D + 0x5DEECE66D) & 0xFFFFFFFFFFFFFFFF
+        other._seed = (self._seed * 0x2545F4914F6CDD1D + 0x5DEECE66D) & _MASK64
         other._step, other._step_seed = 0, 0
         other.repack()
         return other
