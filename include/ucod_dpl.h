@@ -47,6 +47,8 @@ extern "C" {
 /* 5 (round 6): the row partials of the LayerNorm fold hold (sum, M2 about the slot mean) and are merged with Chan's formula (was: raw sums of squares);
  * the split-operand (f32-equivalent) backbone pass: ucod_split_rows, ucod_layernorm_split, ucod_patch_im2col_split, ucod_qkv_split,
  * ucod_attention_split_fwd, ucod_vit_forward_split (+ their size helpers); ucod_clock_probe; the measurement knobs left the product build (UCOD_LAB_KNOBS). */
+/* (still 5) backbone-backward mode on the SwiGLU MLP: epilogues 21 / 22 of ucod_gemm_bf16_train and the _mlp forms of the five training-pass entry points
+ * (ucod_vit_train_workspace_bytes_mlp ... ucod_vit_forward_lora_infer_mlp); additions only, nothing existing changed. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -118,6 +120,16 @@ enum {
                                         (hi | hi | lo) of scale * gelu_exact(alpha * (C + bias[n])), saturation counted.  libucod_dpl_f16.so; N % 8 == 0 */
   UCOD_EPI_BIAS_SWIGLU_SPLIT16 = 20, /* ucod_split16_gemm_act only.  The same for the SwiGLU of UCOD_EPI_BIAS_SWIGLU_BF16's column layout, SiLU to f32 accuracy: out fp16
                                         [M, 3 N/2], segments N/2 apart */
+  /* backbone-backward mode on the SwiGLU MLP (DINOv2 ViT-g/14, Dinov2SwiGLUFFN, modeling_dinov2.py:300-315), ucod_gemm_bf16_train only, bf16 library, large-tile
+     kernels; N % 8 == 0, K >= 128, every row set within 31-bit byte offsets (M * 2 N(hidden) * 2 < 2^31): */
+  UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 = 21, /* training-mode weights_in (B interleaved as for UCOD_EPI_BIAS_SWIGLU_BF16, N = 2 F): out bf16 [M, N/2] = exactly what
+                                        UCOD_EPI_BIAS_SWIGLU_BF16 writes for the same variant (same silu, bias added where that launch adds it), and out2 bf16 [M, N] =
+                                        C + bias[n] in the interleaved column order: the saved pre-activation (x1 | x2 of modeling_dinov2.py:311-312) */
+  UCOD_EPI_SWIGLU_BWD_BF16 = 22,     /* weights_out dgrad (B = weights_out^T [N = F, K]): with g = C[m][4k+e] the cotangent of hidden unit 4k+e (modeling_dinov2.py:313-314
+                                        differentiated), x1 = aux[m][8k+e], x2 = aux[m][8k+4+e] (aux = the saved pre-activation, bf16 [M, 2N]) and sig = 1/(1+exp(-x1)):
+                                        out bf16 [M, 2N]:  out[m][8k+e] = g x2 sig (1 + x1 (1 - sig)),  out[m][8k+4+e] = g x1 sig  -- the cotangent of the interleaved
+                                        weights_in output; f32 arithmetic, one bf16 rounding.  A lane's 8 GEMM columns drain into 32 contiguous bytes: no row of
+                                        weights_out^T is duplicated */
   UCOD_EPI_QKV_FP8 = 8               /* QKV projection of the fp8 attention path (BASELINE configs[4]): out = e4m3 bytes
                                         [3 (q|k|v)][Bimg*heads][Npad][64], Npad = tokens rounded up to 64, value = clamp((C + bias[n]) *
                                         scale[n], +-448); N = 3*heads*64, M = Bimg*tokens_per_image; large-tile kernel only */
@@ -234,7 +246,8 @@ int ucod_cast_f32_bf16(const float* src, void* dst_bf16, size_t n, void* stream)
  * One layer's LoRA parameters / gradients (f32): [A_q (r x D) | B_q (D x r) | A_k | B_k | A_v | B_v], 3r <= UCOD_LORA_AUG. */
 #define UCOD_LORA_AUG 64
 
-/* ucod_gemm_bf16 with the two training epilogues (large-tile kernels; N % 8 == 0, K >= 128).  For UCOD_EPI_BIAS_BF16 and
+/* ucod_gemm_bf16 with the training epilogues 6 / 7 (GELU) and 21 / 22 (SwiGLU) (large-tile kernels; N % 8 == 0, K >= 128; 21 / 22 take variant 0 / 1 / 2 (= auto
+ * among the large tiles), 9, 10, 13, 14 and refuse the others).  For UCOD_EPI_BIAS_BF16 and
  * UCOD_EPI_BIAS_F32 (either entry point) a NULL bias means a plain product (K >= 128, N % 4 == 0, variant not 1/2). */
 int ucod_gemm_bf16_train(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias,
                          const void* aux_bf16, void* out2_bf16, int variant, void* stream);
@@ -490,6 +503,21 @@ int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* table_hos
 size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t);
 int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* table_host, const void* const* train_table_host,
                                 const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The five entry points above with the MLP kind of the pass (UCOD_MLP_*; the ones without the suffix are the UCOD_MLP_GELU case and enqueue the same launches;
+ * an unknown kind: UCOD_EINVAL, sizes 0).  UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315; DINOv2 ViT-g/14): the table entries +9 / +10 / +11 are
+ * those of ucod_vit_forward_mlp (weights_in [2F, D] and its bias interleaved in blocks of 4, weights_out [D, F]; d->F the padded hidden width), and of the training
+ * table +3 is the transpose of that interleaved weights_in, bf16 [D, 2F] (its K order is the column order of the pre-activation's cotangent), +4 the transpose of
+ * weights_out, bf16 [F, D].  The training forward runs weights_in through UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 and saves the interleaved pre-activation bf16 [M, 2F] per
+ * layer (GELU: [M, F]); the backward runs the weights_out dgrad through UCOD_EPI_SWIGLU_BWD_BF16 into dpre bf16 [M, 2F] (which the hidden's buffer is sized for) and
+ * the plain weights_in dgrad with K = 2F; the no-grad pass uses UCOD_EPI_BIAS_SWIGLU_BF16.  Everything outside the MLP is the GELU pass's. */
+size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp);
+int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
+int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                          const float* dkey, void* workspace, size_t workspace_bytes, void* stream);
+size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp);
+int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ decoder / APM path (rows A1-A8) */
 

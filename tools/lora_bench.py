@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Backbone-backward (LoRA) mode at the headline size: forward_train + backward of DINOv2 ViT-B/14 @518, per-class kernel times."""
+"""Backbone-backward (LoRA) mode at the headline size: forward_train + backward of DINOv2 ViT-B/14 @518 (or, sixth argument dinov2_vitg14, of ViT-g/14 with its
+SwiGLU MLP), per-class kernel times.   lora_bench.py [B [steps [streams [dropout [resid [arch]]]]]]"""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,10 +14,15 @@ streams = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 lib = N.load()
 drop = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0   # the reference trains with lora_dropout 0.05 (configs/model/UCOD_DPL.py)
 resid = sys.argv[5] if len(sys.argv) > 5 else "auto"      # residual stream of the training pass: auto (fp16 with bf16 operands) / f32
-eng = ViTLoRAEngine(random_state_dict("dinov2_vitb14", seed=0), heads=12, device="cuda", lora_dropout=drop, resid=resid)
+arch = sys.argv[6] if len(sys.argv) > 6 else "dinov2_vitb14"
+if arch not in ("dinov2_vitb14", "dinov2_vitg14"):
+    sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14, got {arch}")
+giant = arch == "dinov2_vitg14"
+heads = 24 if giant else 12
+eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant)
 eng.train_streams = streams
 x = torch.randn(B, 3, 518, 518, device="cuda")
-dkey = torch.randn(B, 768, 37, 37, device="cuda")
+dkey = torch.randn(B, 64 * heads, 37, 37, device="cuda")
 for _ in range(2):
     eng.forward_train(x); eng.backward(dkey)
 torch.cuda.synchronize()
@@ -43,3 +49,34 @@ rows = [(lib.ucod_prof_class_name(i).decode(), cnt[i], tot[i]) for i in range(n)
 for name, c, t in sorted(rows, key=lambda r: -r[2]):
     print(f"  {name:34s} {c:4d} launches  {t:8.3f} ms total  {t / c * 1e3:8.1f} us avg")
 print(f"  sum {sum(r[2] for r in rows):.2f} ms")
+if giant:
+    # the two SwiGLU training launches alone at this pass's shapes, and beside them (orientation) the launches they extend: UCOD_EPI_BIAS_SWIGLU_BF16 at (M, 2F, D),
+    # which the SAVE form extends by one [M, 2F] store, and UCOD_EPI_GELU_BWD_BF16 at (M, F, D), which reads and writes half the bytes of the SwiGLU dgrad drain
+    M, D, F = B * 1370, eng.D, eng.F
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g).bfloat16()  # noqa: E731
+    A, w_in, w_out_t, b_in = rnd(M, D), rnd(2 * F, D) * D ** -0.5, rnd(F, D) * D ** -0.5, torch.randn(2 * F, device="cuda", generator=g)
+    pre2, pre1 = rnd(M, 2 * F), rnd(M, F)
+    hid, out2, out1 = torch.empty(M, F, dtype=torch.bfloat16, device="cuda"), torch.empty(M, 2 * F, dtype=torch.bfloat16, device="cuda"), torch.empty(M, F, dtype=torch.bfloat16, device="cuda")
+    p, st = N.ptr, N.stream
+    forms = [
+        ("swiglu_save   (M, 2F, D)", lambda: lib.ucod_gemm_bf16_train(N.EPI_BIAS_SWIGLU_SAVE_BF16, p(A), p(w_in), p(hid), M, 2 * F, D, p(b_in), None, p(out2), 0, st()), 2.0 * M * 2 * F * D),
+        ("swiglu (infer)(M, 2F, D)", lambda: lib.ucod_gemm_bf16(N.EPI_BIAS_SWIGLU_BF16, p(A), p(w_in), p(hid), M, 2 * F, D, p(b_in), None, None, None, 0, 0, st()), 2.0 * M * 2 * F * D),
+        ("swiglu_bwd    (M, F, D) ", lambda: lib.ucod_gemm_bf16_train(N.EPI_SWIGLU_BWD_BF16, p(A), p(w_out_t), p(out2), M, F, D, None, p(pre2), None, 0, st()), 2.0 * M * F * D),
+        ("gelu_bwd      (M, F, D) ", lambda: lib.ucod_gemm_bf16_train(N.EPI_GELU_BWD_BF16, p(A), p(w_out_t), p(out1), M, F, D, None, p(pre1), None, 0, st()), 2.0 * M * F * D),
+    ]
+    print(f"  isolated launches at M = {M}, D = {D}, F = {F} (median of 7 rounds x 10 launches, interleaved):")
+    times = {name: [] for name, _, _ in forms}
+    for rnd_i in range(8):
+        for name, fn, _ in forms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                N.check(fn(), name)
+            e1.record()
+            e1.synchronize()
+            if rnd_i:                                         # (round 0 warms up)
+                times[name].append(e0.elapsed_time(e1) / 10 * 1e3)
+    for name, _, flops in forms:
+        us = sorted(times[name])[len(times[name]) // 2]
+        print(f"    {name} {us:8.1f} us  {flops / us * 1e-6:7.1f} TF/s")

@@ -373,7 +373,8 @@ static void apply_order_tuning(GemmArgs& a) {
 // variant: 0 auto | 1 128^2 register staging | 2 128^2 LDS-DMA | 12 64^2 | 9 / 10 large tile 256 / 192 wide | 13 / 14 mixed-height 256 / 192 wide
 template <int EPI>
 static int launch(GemmArgs a, int variant, hipStream_t s) {
-  constexpr bool kTrainEpi = (EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16);
+  constexpr bool kTrainEpi = kTrainOnly<EPI>;
+  constexpr bool kSwigluTrain = kSwigluSave<EPI> || kSwigluBwd<EPI>;   // large-tile drains only: no 128 x 128 / 64 x 64 kernel is instantiated for them
   // (leftover-as-patches: not for the LayerNorm-folded epilogues, whose row scalars live in the tile's LDS table, nor for SwiGLU, whose patches would drain one column at a time)
   constexpr bool kPatchEpi = !kTrainEpi && !kFold<EPI> && !kSwiglu<EPI>;
   const bool auto_small = variant == 0;                       // only `auto` may pick the 64 x 64 tile by itself
@@ -394,8 +395,12 @@ static int launch(GemmArgs a, int variant, hipStream_t s) {
   }
   if (kTrainEpi || ((EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_F32) && !a.bias)) {   // large-tile kernels only
     if (kTrainEpi && ((a.N & 7) != 0 || a.K < 128)) return UCOD_EINVAL;
+    // (kSwigluSave: the caller's variant names a kernel that adds the bias behind the K sum -- the drain does the same, so that the hidden is bit for bit what
+    // UCOD_EPI_BIAS_SWIGLU_BF16 writes for that variant: see GemmArgs::bias_late)
+    if (variant >= 0 && variant < 3) a.bias_late = kSwigluSave<EPI> ? 1 : 0;
     if (variant < 3) variant = (big_plan(a.M, a.N, a.K, 192, kPatchEpi).cost < big_plan(a.M, a.N, a.K, 256, kPatchEpi).cost) ? 10 : 9;
   }
+  if (kSwigluTrain && variant != 9 && variant != 10 && variant != 13 && variant != 14) return UCOD_EINVAL;
   constexpr bool kBf16Out = (kBiasLike<EPI> || kGeluLike<EPI> || kSwiglu<EPI> || kTrainEpi);
   if constexpr (kSwiglu<EPI>) {                                   // pairs live in 8-column chunks: every path must drain row-major (see kSwiglu)
     if ((a.N & 7) != 0) return UCOD_EINVAL;
@@ -482,7 +487,9 @@ static int launch(GemmArgs a, int variant, hipStream_t s) {
     const int t128 = a.tiles_m * a.tiles_n;
     const bool small = variant == 12 || (variant == 2 && auto_small && t128 < device_cus());
     dim3 block(256);
-    if (small) {
+    if constexpr (kSwigluTrain) {
+      return UCOD_EINVAL;                                          // (not reached: refused above)
+    } else if (small) {
       a.tiles_m = cdiv(a.M, 64);
       a.tiles_n = cdiv(a.N, 64);
       hipLaunchKernelGGL((gemm_bf16_kernel<EPI, true, 64>), dim3(a.tiles_m * a.tiles_n), block, 0, s, a);
@@ -614,14 +621,30 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.patches_per_wg = 0;
   a.group_m = 8;
   a.col_fast = 0;
+  a.bias_late = 0;
   hipStream_t s = (hipStream_t)stream;
-  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : PROF_GEMM_EPI7)), s);
+  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 ? PROF_GEMM_EPI21 : epilogue == UCOD_EPI_SWIGLU_BWD_BF16 ? PROF_GEMM_EPI22 : PROF_GEMM_EPI7)), s);
   switch (epilogue) {
     case UCOD_EPI_BIAS_BF16:                                   // NULL bias (plain product) only in the large-tile kernels
       if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_BF16>(a, variant, s);
     case UCOD_EPI_GELU_BWD_BF16: if (!aux) return UCOD_EINVAL; return launch<UCOD_EPI_GELU_BWD_BF16>(a, variant, s);
     case UCOD_EPI_BIAS_GELU_SAVE_BF16: if (!bias || !out2) return UCOD_EINVAL; return launch<UCOD_EPI_BIAS_GELU_SAVE_BF16>(a, variant, s);
+    // backbone-backward mode on the SwiGLU MLP (bf16 library): the widest row set, [M, 2 F] bf16, addressed with 31-bit byte offsets below the drains' sentinels
+    case UCOD_EPI_BIAS_SWIGLU_SAVE_BF16:                            // N = 2 F: out [M, N / 2], out2 [M, N]
+#ifdef UCOD_HALF_F16
+      return UCOD_EINVAL;
+#else
+      if (!bias || !out2 || (N & 7) != 0 || K < 128 || (long)M * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
+      return launch<UCOD_EPI_BIAS_SWIGLU_SAVE_BF16>(a, variant, s);
+#endif
+    case UCOD_EPI_SWIGLU_BWD_BF16:                                  // N = F: aux and out [M, 2 N]
+#ifdef UCOD_HALF_F16
+      return UCOD_EINVAL;
+#else
+      if (!aux || (N & 7) != 0 || K < 128 || (long)M * 2 * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
+      return launch<UCOD_EPI_SWIGLU_BWD_BF16>(a, variant, s);
+#endif
     case UCOD_EPI_BIAS_GELU_BF16: if (!bias) return UCOD_EINVAL; return launch<UCOD_EPI_BIAS_GELU_BF16>(a, variant, s);
     case UCOD_EPI_BIAS_GELU_SPLIT2:                                 // rows of 3 N bf16: the drains address them with 31-bit byte offsets
       if (!bias || (N & 7) != 0 || (long)M * 3 * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
@@ -689,6 +712,7 @@ extern "C" int ucod_gemm_bf16(int epilogue, const void* A, const void* B, void* 
                               const float* scale, const float* resid, const float* pos, int tokens_per_image, int variant,
                               void* stream) {
   if (epilogue == UCOD_EPI_GELU_BWD_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SAVE_BF16) return UCOD_EINVAL;   // need ucod_gemm_bf16_train
+  if (epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 || epilogue == UCOD_EPI_SWIGLU_BWD_BF16) return UCOD_EINVAL;   // (the same)
   if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
   if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;   // need ucod_gemm_bf16_stats
   if (epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) return UCOD_EINVAL;   // need ucod_split16_gemm_act

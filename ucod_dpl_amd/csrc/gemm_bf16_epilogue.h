@@ -59,8 +59,21 @@ constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LN
 // the 8 consecutive columns 8k .. 8k+7 that a lane of a row-major drain holds are x1 | x2 of the hidden units 4k .. 4k+3, so the product needs no other lane and no
 // other tile.  Output column = GEMM column / 2: one 8-byte store per lane and segment.  Only the row-major drains implement it (epilogue_store8_bf16 and the
 // large-tile drain); launch() keeps these epilogues away from the element-wise ones (N % 8 == 0, no leftover-as-patches tiles).
+// Backbone-backward mode on that MLP (ucod_gemm_bf16_train, bf16 library, large-tile drain only; launch() instantiates no other kernel for them):
+//   kSwigluSave  the training-mode weights_in: the SwiGLU segment store above AND the interleaved pre-activation bf16 [M, N] (2 bytes per GEMM column where the hidden
+//                has 1, so its byte offset is twice the hidden's);
+//   kSwigluBwd   the weights_out dgrad, N = F hidden units: an EXPANDING drain -- a lane's 8 columns (hidden units 8j .. 8j+7) are the interleaved columns 16j .. 16j+15
+//                of the saved pre-activation and of the output, 32 contiguous bytes of each (4 bytes per GEMM column): two 16-byte loads, two 16-byte stores.
 template <int EPI>
-constexpr bool kSwiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || kSplit16Swiglu<EPI>);
+constexpr bool kSwigluSave = (EPI == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16);
+template <int EPI>
+constexpr bool kSwigluBwd = (EPI == UCOD_EPI_SWIGLU_BWD_BF16);
+// the epilogues of ucod_gemm_bf16_train: large-tile kernels only, never in leftover patches
+template <int EPI>
+constexpr bool kTrainOnly = (EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16 || kSwigluSave<EPI> || kSwigluBwd<EPI>);
+template <int EPI>
+constexpr bool kSwiglu = (EPI == UCOD_EPI_BIAS_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || kSplit16Swiglu<EPI> ||
+                          kSwigluSave<EPI>);
 template <int EPI>
 constexpr bool kSwigluSplit2 = (EPI == UCOD_EPI_BIAS_SWIGLU_SPLIT2);   // output = the A-side split operand hi | hi | lo, segments N / 2 apart in a row of 3 N / 2
 template <int EPI>
@@ -70,6 +83,24 @@ constexpr bool kSwigluSplitRow = kSwigluSplit2<EPI> || kSplit16Swiglu<EPI>;   //
 __device__ __forceinline__ float silu_fast(float x) {
   const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
   return s == 0.f ? -0.f : x * s;
+}
+// d/d(x1, x2) of silu(x1) * x2 times the hidden cotangent g (kSwigluBwd; modeling_dinov2.py:313 differentiated), four hidden units: with sig = 1 / (1 + exp(-x1))
+//   d1 = g x2 sig (1 + x1 (1 - sig)),   d2 = g x1 sig.   x1 far below zero: exp overflows, sig = 0, both are 0 (x1 is a saved bf16 value: finite).  x1 = x2 = 0
+// (padded hidden units): both exactly 0.  -> the two thirds' packed pairs in the interleaved order d1[0..3] | d2[0..3]
+__device__ __forceinline__ u32x4 swiglu_bwd4(f32x4 g, u32x4 pw) {
+  float x1[4], x2[4], d1[4], d2[4];
+  unpack_h2(pw[0], x1[0], x1[1]);
+  unpack_h2(pw[1], x1[2], x1[3]);
+  unpack_h2(pw[2], x2[0], x2[1]);
+  unpack_h2(pw[3], x2[2], x2[3]);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float sig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x1[e] * -1.4426950408889634f));
+    const float gs = g[e] * sig;
+    d1[e] = gs * x2[e] * fmaf(x1[e], 1.0f - sig, 1.0f);
+    d2[e] = gs * x1[e];
+  }
+  return (u32x4){pack_h2(d1[0], d1[1]), pack_h2(d1[2], d1[3]), pack_h2(d2[0], d2[1]), pack_h2(d2[2], d2[3])};
 }
 // (the split epilogue feeds an f32-equivalent pass: silu_f32 of common.h, shared with ucod_split_rows op 3)
 template <int EPI>
@@ -126,6 +157,8 @@ struct GemmArgs {
   int patches_per_wg;  // 16 x 32 patches of the remaining tiles each workgroup computes on the side
   int group_m;         // large-tile kernels: row-tiles per group of the tile order inside an XCD's chunk (see tile_of)
   int col_fast;        // 1: column-tile fastest inside a group (one A panel's N-sweep back to back), 0: row-tile fastest
+  int bias_late;       // kSwigluSave: 1 = add the bias in the drain, behind the K sum (where the 128 x 128 / 64 x 64 kernels add it), instead of starting the accumulators
+                       // from it -- set when the caller's variant names one of those kernels, so that the hidden equals UCOD_EPI_BIAS_SWIGLU_BF16's of that variant bit for bit
 };
 
 // kSplit16: eight GEMM columns (bias inside) -> the scaled activation values, in the words of split16_rows_kernel (csrc/split16.hip): 8 for GELU, 4 for SwiGLU
@@ -674,7 +707,7 @@ __device__ __forceinline__ void fold_rank_one(f32x4 (&acc)[NI][NT], const float*
 template <int EPI>
 constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kSplit2Out<EPI> || kSplit16<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
                             EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16 ||
-                            EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI> || kSwiglu<EPI>);
+                            EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI> || kSwiglu<EPI> || kSwigluBwd<EPI>);
 template <int EPI>
 constexpr bool kF32Out = (EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 || EPI == UCOD_EPI_BIAS_F32);
 
@@ -689,7 +722,7 @@ __device__ __forceinline__ void load_col_consts(const GemmArgs& a, int ncol0, fl
       n = n < a.N ? n : a.N - 1;
       if constexpr (EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_QKV_FP8) {
         cb[j] = (a.bias ? a.bias : reinterpret_cast<const float*>(a.B))[n];   // NULL bias = plain product (dgrad GEMMs): selected in finish_col_consts
-      } else if constexpr (EPI != UCOD_EPI_GELU_BWD_BF16) {
+      } else if constexpr (EPI != UCOD_EPI_GELU_BWD_BF16 && !kSwigluBwd<EPI>) {
         cb[j] = a.bias[n];
       }
       if constexpr (EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 || kResidH16<EPI>) cs[j] = a.scale[n];
@@ -709,6 +742,10 @@ __device__ __forceinline__ void finish_col_consts(const GemmArgs& a, float (&cb)
   if constexpr (EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_QKV_FP8) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) cb[j] = a.bias ? cb[j] : 0.f;
+  }
+  if constexpr (kSwigluSave<EPI>) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cb[j] = a.bias_late ? 0.f : cb[j];
   }
 }
 
@@ -871,7 +908,8 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     // are dropped (loads return 0) -- and columns past N get an offset beyond any descriptor.
     constexpr unsigned OOB = 0xFFFFFFF0u;
     // bytes per GEMM column of an output row's pitch (the split epilogue's rows are 3 N wide; a SwiGLU row holds N / 2 16-bit values, 3 N / 2 in the split form)
-    constexpr int ELT = kSwiglu<EPI> ? (kSwigluSplitRow<EPI> ? 3 : 1) : (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;
+    // (kSwigluBwd: two 16-bit values per GEMM column)
+    constexpr int ELT = kSwigluBwd<EPI> ? 4 : kSwiglu<EPI> ? (kSwigluSplitRow<EPI> ? 3 : 1) : (kF32Out<EPI> ? 4 : 2) * kOutPitchMul<EPI>;
     const long rows_left = (long)a.M - m_first;
     const unsigned long left = rows_left > 0 ? (unsigned long)rows_left * a.N * ELT : 0ul;
     const unsigned records = left > 0xFFFFFFFFul ? 0xFFFFFFFFu : (unsigned)left;
@@ -955,10 +993,11 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     } else {                                                      // bf16 out: 16-byte stores (launch() guarantees N % 8 == 0)
       constexpr bool GBWD = (EPI == UCOD_EPI_GELU_BWD_BF16), SAVE = (EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16);
       constexpr bool RH16 = (kResidH16<EPI>);   // second matrix = the f16 residual stream (may alias out)
+      constexpr bool SWSAVE = (kSwigluSave<EPI>), SWBWD = (kSwigluBwd<EPI>);
       constexpr int CH = WCOLS / 8, ITS = PR * CH / 64;
       static_assert((PR * CH) % 64 == 0, "whole wave instructions");
       // second bf16 [M,N] matrix with the same geometry: the saved pre-activation, read (GELU_BWD) or written (GELU_SAVE)
-      const void* second = GBWD ? a.aux : (SAVE ? (const void*)a.out2 : (RH16 ? (const void*)a.resid : (const void*)a.out));
+      const void* second = (GBWD || SWBWD) ? a.aux : (SAVE ? (const void*)a.out2 : (RH16 ? (const void*)a.resid : (const void*)a.out));
       // 64-column waves (CH == 8): wave instruction `it` covers rows it*8 + lane/8, chunk lane%8, so the lane's byte offset is ONE register
       // (its pass-0 / it-0 offset, or DROP when its columns lie past N) plus a wave-uniform term: one v_add per store instead of the ~11
       // vector instructions (one of them v_mul_lo_u32) of the generic (row, chunk) arithmetic -- the drain of fc1 is bound by its vector
@@ -968,11 +1007,16 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
       const unsigned rec16 = FAST ? (records > 0x7FFFFFF0u ? 0x7FFFFFF0u : records) : records;
       const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out) + base, 0, rec16, 0x00020000);
       const auto rs_2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(second)) + base, 0,
-                                                          (GBWD || SAVE || RH16) ? rec16 : 0u, 0x00020000);
+                                                          (GBWD || SAVE || RH16 || SWBWD) ? rec16 : 0u, 0x00020000);
+      // kSwigluSave: the pre-activation rows [M, N] bf16 from the wave tile's first row -- twice the hidden's bytes per row and per column, so a live chunk's
+      // offset there is twice its offset in `out` (launch() keeps M * N * 2 below 2^31; a dropped chunk keeps its sentinel)
+      const unsigned long left_s = SWSAVE ? left * 2ul : 0ul;
+      const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(SWSAVE ? a.out2 : a.out) + (SWSAVE ? base * 2 : 0), 0,
+                                                          left_s > 0x7FFFFFF0ul ? 0x7FFFFFF0u : (unsigned)left_s, 0x00020000);
       // (row, chunk) of wave instruction `it`: recomputed where needed -- index arrays cost registers the persistent kernel lacks
       auto lrow = [&](int it) { return (it * 64 + lane) / CH; };
       auto lchk = [&](int it) { return (it * 64 + lane) - lrow(it) * CH; };
-      constexpr unsigned CB = kSwiglu<EPI> ? 1u : 2u;            // bytes of a segment per GEMM column (SwiGLU: two columns -> one 16-bit value)
+      constexpr unsigned CB = kSwiglu<EPI> ? 1u : (SWBWD ? 4u : 2u);   // bytes of a segment per GEMM column (SwiGLU: two columns -> one 16-bit value; its dgrad: one -> two)
       const unsigned off0 = (n_first + (lane & 7) * 8 < a.N) ? (unsigned)(lane >> 3) * row_bytes + (unsigned)(n_first + (lane & 7) * 8) * CB : DROP;
       const char* lds0 = wbase + (lane >> 3) * EPI_PITCH(WCOLS) + (lane & 7) * 32;
       auto live = [&](int it, int pass) { return !FAST || it * 8 < rows_in(pass); };   // (compile-time after unrolling) rows 16..31 of a 16-row last pass
@@ -998,6 +1042,18 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
 #pragma unroll
         for (int it = 0; it < ITS; ++it) pre[0][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, at(it, 0), 0, 0);
       }
+      // kSwigluBwd: the second 16 bytes of a lane's 32 (hidden units 8j+4 .. 8j+7), for loads and stores alike.  A dropped chunk's offset is a sentinel >= 2^31 and
+      // stays one: adding to it could wrap back into range (live offsets stay below 2^31: gemm_entry bounds M * 2N * 2)
+      auto second16 = [](unsigned o) -> unsigned { return o >= 0x80000000u ? o : o + 16u; };
+      u32x4 pre_hi[SWBWD ? 2 : 1][SWBWD ? ITS : 1];             // (pre = the first 16 bytes)
+      if constexpr (SWBWD) {
+#pragma unroll
+        for (int it = 0; it < ITS; ++it) {
+          const unsigned o = at(it, 0);
+          pre[0][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, o, 0, 0);
+          pre_hi[0][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, second16(o), 0, 0);
+        }
+      }
 #pragma unroll
       for (int pass = 0; pass < NP; ++pass) {
         stage(pass);
@@ -1007,6 +1063,17 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
             for (int it = 0; it < ITS; ++it) {
               if (!live(it, pass + 1)) continue;
               pre[(pass + 1) & 1][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, at(it, pass + 1), 0, 0);
+            }
+          }
+        }
+        if constexpr (SWBWD) {
+          if (pass + 1 < NP) {
+#pragma unroll
+            for (int it = 0; it < ITS; ++it) {
+              if (!live(it, pass + 1)) continue;
+              const unsigned o = at(it, pass + 1);
+              pre[(pass + 1) & 1][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, o, 0, 0);
+              pre_hi[(pass + 1) & 1][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_2, second16(o), 0, 0);
             }
           }
         }
@@ -1038,6 +1105,28 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
             }
             __builtin_amdgcn_sched_barrier(0);                    // chunks in order, as at the end of this loop's body: erff of a hoisted pass would not fit the registers
             continue;
+          }
+          if constexpr (SWBWD) {                                  // v0 / v1 = the cotangents of hidden units 8j .. 8j+3 / 8j+4 .. 8j+7
+            const unsigned o = at(it, pass);
+            __builtin_amdgcn_raw_buffer_store_b128(swiglu_bwd4(v0, pre[pass & 1][it]), rs_o, o, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(swiglu_bwd4(v1, pre_hi[pass & 1][it]), rs_o, second16(o), 0, AUX);
+            __builtin_amdgcn_sched_barrier(0);
+            continue;
+          }
+          if constexpr (SWSAVE) {                                 // the interleaved pre-activation out first, then the SwiGLU segment below
+            if (a.bias_late) {                                    // (wave-uniform; small passes only: see GemmArgs)
+              const int nb = n_first + (FAST ? (lane & 7) : lchk(it)) * 8;
+              const float* bp = a.bias + (nb < a.N ? nb : 0);
+              v0 = v0 + *reinterpret_cast<const f32x4*>(bp);
+              v1 = v1 + *reinterpret_cast<const f32x4*>(bp + 4);
+            }
+            u32x4 w;
+            w[0] = pack_h2(v0[0], v0[1]);
+            w[1] = pack_h2(v0[2], v0[3]);
+            w[2] = pack_h2(v1[0], v1[1]);
+            w[3] = pack_h2(v1[2], v1[3]);
+            const unsigned o = at(it, pass);
+            __builtin_amdgcn_raw_buffer_store_b128(w, rs_s, o >= 0x80000000u ? o : o * 2u, 0, 0);
           }
           if constexpr (SAVE) {                                   // pre-activation out first
             u32x4 w;

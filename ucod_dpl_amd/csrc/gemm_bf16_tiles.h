@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
   stageA(0, 1);
   stageB(0, 0, Cfg::NB);
   if (nt > 1) stageB(1, 0, Cfg::NB);
-  if constexpr (EPI != UCOD_EPI_GELU_BWD_BF16 && EPI != UCOD_EPI_BIAS_GELU_SAVE_BF16 && !kSwiglu<EPI>) {   // (SwiGLU: never in patches, see launch())
+  if constexpr (!kTrainOnly<EPI> && !kSwiglu<EPI>) {              // (training epilogues and SwiGLU: never in patches, see launch())
     // scratch: the A0 slot of buffer 1, first written by the DMAs of K-tile 1 after the barrier below.  vmcnt retires in order,
     // so the patch's stores (older than every later DMA) never disturb the counted waits of the main loop.
     if (a.patches_per_wg > 0) patch_phase<EPI, Cfg::BN_>(a, smem + Cfg::BUF, orig, wave, lane);

@@ -794,7 +794,10 @@ extern "C" int ucod_lora_grad(void* dqkv_aug, const void* h_aug, const float* lo
   hipStream_t s = (hipStream_t)stream;
   constexpr int RW = 2;                                           // ranks per pass (the reference's r = 2 is one pass)
   static const int ns_env = [] { const char* e = ucod::lab_env("UCOD_LORA_GRAD_STREAMS"); return e ? atoi(e) : 0; }();   // measurement knob: 2 or 4 row streams per block
-  const int NSr = ns_env == 2 ? 2 : ns_env == 5 ? 5 : 4;
+  // D > 1024 (ViT-g: 1536): two row streams per block -- a wave's state is 2 * RW * (D / 64) accumulators + as many B values, 12 chunks of them only fit the
+  // registers of a 6-wave block (LGW below) -- and a block reduction buffer past 64 KiB, which the launch has to ask for
+  const bool wide = D > 1024;
+  const int NSr = wide ? 2 : ns_env == 2 ? 2 : ns_env == 5 ? 5 : 4;
   static const int nb_env = [] { const char* e = ucod::lab_env("UCOD_LORA_GRAD_NBLK"); return e ? atoi(e) : 0; }();       // measurement knob (<= LORA_GRAD_BLOCKS)
   // default: one block per CU (12 waves of 4 row streams x 3 projections), a whole round -- round 4: 512 blocks of 6 waves 158 us -> 109 us per launch at
   // ViT-B / 32 images (fewer partials to combine and to reduce; 384 blocks = 1.5 rounds: 140 us)
@@ -810,7 +813,22 @@ extern "C" int ucod_lora_grad(void* dqkv_aug, const void* h_aug, const float* lo
     else if (NSr == 5) hipLaunchKernelGGL((lora_grad_kernel<n, RW, vw, 5>), dim3(nblk), dim3(960), lds_bytes, s, (bf16_raw*)dqkv_aug, (const bf16_raw*)h_aug, lora_layer, r, j0, scaling, (float*)workspace, rows, D, drop); \
     else hipLaunchKernelGGL((lora_grad_kernel<n, RW, vw, 4>), dim3(nblk), dim3(768), lds_bytes, s, (bf16_raw*)dqkv_aug, (const bf16_raw*)h_aug, lora_layer, r, j0, scaling, (float*)workspace, rows, D, drop);     \
   } while (0)
-    if ((D % 256) == 0 && D <= 1024 && !narrow) {
+#define LGW(n)                                                                                                                                      \
+  do {                                                                                                                                              \
+    const void* kern = (const void*)lora_grad_kernel<n, RW, 2, 2>;                                                                                  \
+    if (lds_bytes > 65536) {                                                                                                                        \
+      const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);   /* (per device: asked for at every launch) */ \
+      if (e != hipSuccess) return (int)e;                                                                                                           \
+    }                                                                                                                                               \
+    hipLaunchKernelGGL((lora_grad_kernel<n, RW, 2, 2>), dim3(nblk), dim3(384), lds_bytes, s, (bf16_raw*)dqkv_aug, (const bf16_raw*)h_aug, lora_layer, r, j0, scaling, (float*)workspace, rows, D, drop); \
+  } while (0)
+    if (wide) {
+      switch (D / 128) {
+        case 10: LGW(10); break;
+        case 12: LGW(12); break;
+        default: return UCOD_EINVAL;
+      }
+    } else if ((D % 256) == 0 && D <= 1024 && !narrow) {
       switch (D / 256) {
         case 1: LG(1, 4); break;
         case 2: LG(2, 4); break;
@@ -826,6 +844,7 @@ extern "C" int ucod_lora_grad(void* dqkv_aug, const void* h_aug, const float* lo
       }
     }
 #undef LG
+#undef LGW
     UCOD_CHECK_LAUNCH();
     hipLaunchKernelGGL((lora_grad_reduce_kernel<RW>), dim3(cdiv(6 * RW * D, 32)), dim3(256), 0, s, (const float*)workspace, nblk, r, j0,
                        grad_layer, D, accumulate);

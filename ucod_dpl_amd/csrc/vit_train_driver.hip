@@ -4,6 +4,8 @@
 //                            f32, LN1 output + LoRA down-projection, qkv, attention output, log-sum-exp, fc1 pre-activation)
 //   ucod_vit_backward        cotangent of the key map -> LoRA gradients of every layer (all other weights are frozen, so no
 //                            weight-gradient GEMMs: dgrad only, ~2x the forward FLOPs with the recomputed attention scores)
+// The _mlp forms take the MLP kind: UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) saves the interleaved pre-activation [M, 2F] from the weights_in
+// drain (UCOD_EPI_BIAS_SWIGLU_SAVE_BF16) and turns the hidden cotangent into dpre [M, 2F] in the weights_out dgrad's drain (UCOD_EPI_SWIGLU_BWD_BF16).
 // No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
@@ -30,7 +32,9 @@ bool valid(const ucod_vit_train_desc* t) {
          (d->resid16 == 0 || d->resid16 == 1);                   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
 }
 
-TPlan make_plan(const ucod_vit_train_desc* t) {
+inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU; }
+
+TPlan make_plan(const ucod_vit_train_desc* t, int mlp) {
   const ucod_vit_desc* d = &t->vit;
   TPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
@@ -38,6 +42,7 @@ TPlan make_plan(const ucod_vit_train_desc* t) {
   p.M = d->B * p.tok;
   p.L = d->L;
   const size_t M = p.M, D = d->D, F = d->F, L = d->L;
+  const size_t FP = mlp == UCOD_MLP_SWIGLU ? 2 * F : F;      // width of the saved pre-activation and of its cotangent (SwiGLU: x1 | x2 interleaved)
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += up(bytes); return r; };
   p.s_x = up(M * D * (d->resid16 ? 2 : 4));
@@ -45,7 +50,7 @@ TPlan make_plan(const ucod_vit_train_desc* t) {
   p.s_qkv = up(M * 3 * D * 2);
   p.s_att = up(M * D * 2);
   p.s_lse = up((size_t)d->B * d->heads * p.tok * 4);
-  p.s_pre = up(M * F * 2);
+  p.s_pre = up(M * FP * 2);
   p.x_in = take(p.s_x * L);
   p.x_mid = take(p.s_x * (L - 1));
   p.h_aug = take(p.s_h * L);
@@ -54,7 +59,7 @@ TPlan make_plan(const ucod_vit_train_desc* t) {
   p.lse = take(p.s_lse * (L - 1));
   p.pre = take(p.s_pre * (L - 1));
   p.h2 = take(M * D * 2);
-  p.g = take(M * F * 2);
+  p.g = take(M * FP * 2);                                     // the hidden [M, F]; the backward's dpre [M, FP] aliases it
   p.patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
   p.qscale = take(3 * D * 4);
   p.dx = take(M * D * 4);
@@ -76,14 +81,16 @@ TPlan make_plan(const ucod_vit_train_desc* t) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return valid(t) ? make_plan(t).total : 0; }
+extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return valid(t) && known_mlp(mlp) ? make_plan(t, mlp).total : 0; }
+extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_train_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
-                                      float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
+                                          float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid(t) || !known_mlp(mlp) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
-  const TPlan p = make_plan(t);
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
+  const TPlan p = make_plan(t, mlp);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
@@ -130,10 +137,15 @@ extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* 
     RUN(ucod_gemm_bf16(epi_resid, att, W[4], x_mid, M, D, D, (const float*)W[5], (const float*)W[6], x_in, nullptr, tok, gv, stream));
     if (r16) RUN(ucod_layernorm_h16(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
     else RUN(ucod_layernorm(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-    RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
+    if (swiglu) RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_SWIGLU_SAVE_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, pre, gv, stream));
+    else RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x_next, M, D, F, (const float*)W[12], (const float*)W[13], x_mid, nullptr, tok, gv, stream));
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
+                                      float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_train_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -167,7 +179,7 @@ IPlan make_iplan(const ucod_vit_train_desc* t) {
   p.h2 = take(M * D * 2);
   p.qkv = take(M * 3 * D * 2);
   p.a = take(M * D * 2);
-  p.g = take(M * F * 2);
+  p.g = take(M * F * 2);                                      // (either kind: the hidden [M, F]; SwiGLU's weights_in output never reaches memory)
   p.patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
   p.qscale = take(3 * D * 4);
   p.total = o;
@@ -175,12 +187,14 @@ IPlan make_iplan(const ucod_vit_train_desc* t) {
 }
 }  // namespace
 
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return valid_infer(t) ? make_iplan(t).total : 0; }
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return valid_infer(t) && known_mlp(mlp) ? make_iplan(t).total : 0; }
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_lora_infer_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
-                                           float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
+                                               float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid_infer(t) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid_infer(t) || !known_mlp(mlp) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const ucod_vit_desc* d = &t->vit;
   const IPlan p = make_iplan(t);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
@@ -219,18 +233,24 @@ extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const v
     RUN(ucod_gemm_bf16(epi_resid, a, W[4], x, M, D, D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
     if (r16) RUN(ucod_layernorm_h16(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
     else RUN(ucod_layernorm(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-    RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+    if (swiglu) RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SWIGLU_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+    else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x, M, D, F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
   }
   return UCOD_OK;
 }
+extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
+                                           float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_lora_infer_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
+}
 
-extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* dkey,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
+  if (!valid(t) || !known_mlp(mlp) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
-  const TPlan p = make_plan(t);
+  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
+  const TPlan p = make_plan(t, mlp);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KQ = 3 * D + UCOD_LORA_AUG, r = t->lora_r;
@@ -294,8 +314,14 @@ extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const
     const float* lse = (const float*)(ws + p.lse + p.s_lse * l);
     const void* pre = ws + p.pre + p.s_pre * l;
     // MLP branch: s = ls2 * dx  ->  fc2 dgrad (x gelu')  ->  fc1 dgrad  ->  LN2 backward + residual
-    RUN(ucod_gemm_bf16_train(UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
-    RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, F, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    // (SwiGLU: the weights_out dgrad's drain writes the cotangent of the interleaved weights_in output, dpre [M, 2F]; X[3] = weights_in^T [D, 2F] in that column order)
+    if (swiglu) {
+      RUN(ucod_gemm_bf16_train(UCOD_EPI_SWIGLU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
+      RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, 2 * F, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    } else {
+      RUN(ucod_gemm_bf16_train(UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
+      RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, F, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    }
     RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
@@ -307,4 +333,8 @@ extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const
     }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* dkey,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_backward_mlp(t, UCOD_MLP_GELU, T, TT, dkey, workspace, workspace_bytes, stream);
 }

@@ -42,7 +42,8 @@ class LoRABackbone(nn.Module):
 
 
 def load_lora(config, state_dict, heads, device="cuda", generator=None):
-    """models/modules/full_model.py:47-72.  r == 0 is refused (the reference returns the bare model; use ``backbone`` then)."""
+    """models/modules/full_model.py:47-72.  r == 0 is refused (the reference returns the bare model; use ``backbone`` then).  Either MLP kind of DINOv2 is taken:
+    a SwiGLU checkpoint (facebook/dinov2-giant) trains through the engine's SwiGLU backward (``allow_swiglu``)."""
     r = getattr(config, "r", 2)
     if r == 0:
         raise ValueError("r == 0: no LoRA -- use data.utils.feature_extractor.backbone for the frozen path")
@@ -53,7 +54,7 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None):
     if getattr(config, "bias", "none") != "none":
         raise NotImplementedError("LoRA bias modes other than 'none' are not built")
     drop = float(getattr(config, "lora_dropout", 0.05))                      # :50
-    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, device=device, generator=generator, lora_dropout=drop))
+    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True))
 
 
 class full_model(nn.Module):

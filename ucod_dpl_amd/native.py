@@ -29,6 +29,9 @@ EPI_BIAS_GELU_SPLIT2 = 15                                  # fc1 + GELU + two-te
 # SwiGLU MLP of DINOv2 ViT-g/14 on interleaved weights_in rows (include/ucod_dpl.h): 16-bit [M, N/2] (both libraries); the LayerNorm-folded form (ucod_gemm_lnfold,
 # fp16-operand build); the two-term split operand of the result (bf16 library)
 EPI_BIAS_SWIGLU_BF16, EPI_LNFOLD_SWIGLU_BF16, EPI_BIAS_SWIGLU_SPLIT2 = 16, 17, 18
+# backbone-backward mode on the SwiGLU MLP (ucod_gemm_bf16_train only, bf16 library): the training-mode weights_in (hidden + saved interleaved pre-activation) and the
+# weights_out dgrad whose drain writes the cotangent of the interleaved weights_in output
+EPI_BIAS_SWIGLU_SAVE_BF16, EPI_SWIGLU_BWD_BF16 = 21, 22
 VIT_LAYER_STRIDE = 16
 # the slots of one layer's row of the pointer table, in table order (include/ucod_dpl.h: ucod_vit_forward); "_w" entries are 16-bit (or split) matrices, the rest f32
 VIT_LAYER_SLOTS = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2", "aux0", "aux1")
@@ -144,6 +147,12 @@ SIGNATURES = {
     "ucod_vit_backward": (ci, [C.POINTER(VitTrainDesc), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes": (sz, [C.POINTER(VitTrainDesc)]),
     "ucod_vit_forward_lora_infer": (ci, [C.POINTER(VitTrainDesc), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # the five training-pass entry points with the MLP kind (UCOD_MLP_*) behind the descriptor
+    "ucod_vit_train_workspace_bytes_mlp": (sz, [C.POINTER(VitTrainDesc), ci]),
+    "ucod_vit_forward_train_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_backward_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
+    "ucod_vit_lora_infer_workspace_bytes_mlp": (sz, [C.POINTER(VitTrainDesc), ci]),
+    "ucod_vit_forward_lora_infer_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16_train": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
     "ucod_layernorm_lora": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_lora_h16": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),

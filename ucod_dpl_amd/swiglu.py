@@ -52,3 +52,17 @@ def swiglu_interleaved(y):
     """The epilogue's arithmetic on the interleaved GEMM output y [..., 2F] -> [..., F] (checker form; any dtype)."""
     z = y.reshape(*y.shape[:-1], -1, 2, 4)
     return (torch.nn.functional.silu(z[..., 0, :]) * z[..., 1, :]).reshape(*y.shape[:-1], -1)
+
+
+def swiglu_interleaved_grad(pre, dhid):
+    """The backward of ``swiglu_interleaved``: interleaved pre-activation ``pre`` [..., 2F] and the hidden's cotangent ``dhid`` [..., F] -> the cotangent of ``pre``
+    [..., 2F] in the same interleaved order (checker form of UCOD_EPI_SWIGLU_BWD_BF16; the dtype of the inputs).  With g the cotangent of hidden unit 4k + e,
+    x1 = pre[8k + e], x2 = pre[8k + 4 + e] and sig = 1 / (1 + exp(-x1)):
+
+        d pre[8k + e] = g x2 sig (1 + x1 (1 - sig)),        d pre[8k + 4 + e] = g x1 sig
+    """
+    z = pre.reshape(*pre.shape[:-1], -1, 2, 4)
+    g = dhid.reshape(*dhid.shape[:-1], -1, 4)
+    x1, x2 = z[..., 0, :], z[..., 1, :]
+    sig = torch.sigmoid(x1)
+    return torch.stack((g * x2 * sig * (1 + x1 * (1 - sig)), g * x1 * sig), -2).reshape(pre.shape)

@@ -644,10 +644,14 @@ class ViTLoRAEngine(ViTEngine):
     in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel."""
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto"):
-        if normalize_state_dict(state_dict).get("mlp") == "swiglu":
-            raise NotImplementedError("backbone-backward (LoRA) mode has no backward of the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315): "
-                                      "use the frozen-backbone engines (ViTEngine / SplitViTEngine) for this checkpoint")
+                 seed=0, resid="auto", allow_swiglu=False):
+        """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
+        UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
+        (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on."""
+        if normalize_state_dict(state_dict).get("mlp") == "swiglu" and not allow_swiglu:
+            raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
+                                      "allow_swiglu=True (models/modules/full_model.py: load_lora passes it); the frozen-backbone engines (ViTEngine / "
+                                      "SplitViTEngine) take it as it is")
         # resid: as ViTEngine ("auto" = the fp16 residual stream with bf16 operands).  Round 4: the training pass SAVES the stream in that
         # type and LayerNorm backward reads it (ucod_layernorm_bwd_ex); resid="f32" keeps the round-3 path.
         super().__init__(state_dict, heads, eps=eps, device=device, full_last_layer=False, gemm_variant=gemm_variant, attn_variant=2, resid=resid,
@@ -678,6 +682,7 @@ class ViTLoRAEngine(ViTEngine):
             w_aug[:, :D] = l[N.QKV_W]
             wt_aug = torch.zeros(D, 3 * D + A, dtype=torch.bfloat16, device=dev)
             wt_aug[:, :3 * D] = l[N.QKV_W].t()
+            # (SwiGLU: fc1_w is the padded, interleaved weights_in [2F, D] -- its transpose's K order is the column order of the pre-activation's cotangent)
             self.train_layers.append([w_aug, wt_aug] + [l[w].t().contiguous() for w in (N.PROJ_W, N.FC1_W, N.FC2_W)])
         self.train_streams = 2                          # image-parallel sub-batches of the training passes (_chunks)
         self._tside = None
@@ -777,10 +782,11 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             self._chunk_seed[i] = t.seed
-            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes(C.byref(t)))
+            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_mlp(C.byref(t), self.mlp))
             T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
             with self._guard.bind():
-                N.check(self.lib.ucod_vit_forward_train(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_forward_train")
+                N.check(self.lib.ucod_vit_forward_train_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_forward_train")
             if self.resid16:
                 self._guard.arm(torch.cuda.current_stream(self.device))
 
@@ -801,10 +807,10 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             t.vit.resid16 = int(bool(resid16))
-            ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes(C.byref(t)))
+            ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_mlp(C.byref(t), self.mlp))
             T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
             with self._guard.bind():
-                N.check(self.lib.ucod_vit_forward_lora_infer(C.byref(t), T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                N.check(self.lib.ucod_vit_forward_lora_infer_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
                         "ucod_vit_forward_lora_infer")
             # this engine's own stream type may be f32 (its backward reads it), but THIS pass may run the fp16 one: its saturation counter is
             # fetched behind every chunk and polled by the next call / check_overflow(wait=True) at the loop's boundaries
@@ -828,7 +834,7 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
             T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
             ws = self._tside_ws[i]
-            N.check(self.lib.ucod_vit_backward(C.byref(t), T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
+            N.check(self.lib.ucod_vit_backward_mlp(C.byref(t), self.mlp, T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
 
         self._fan_out(self._tside, self._bounds, run, (dkey,))
         if len(self._bounds) > 1:
