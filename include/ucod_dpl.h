@@ -519,6 +519,52 @@ size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int
 int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
                                     const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* LoRA on the MLP input projection as well (models/modules/full_model.py:47-72: `target_modules` is handed to peft, so `fc1` -- `weights_in` on a SwiGLU
+ * checkpoint -- is an ordinary target there).  The projection's input is LayerNorm 2's output, so the module rides on the fc1 GEMM the way q / k / v ride on the
+ * QKV GEMM: 64 extra K columns, of which the first r are used.  N1 = F (GELU) or 2F (SwiGLU, the padded 4-interleaved row order of ucod_vit_forward_mlp).
+ * One layer's parameters / gradients (f32): [A_m (r x D) | B_m (N1 x r)], 1 <= r <= UCOD_LORA_MLP_MAX_R (the gradient kernel keeps a lane's B_m values and
+ * their accumulators in registers, two ranks per pass).  Dropout: the module's own mask is projection 0 of ucod_lora_dropout with layer = L + l.
+ *   forward   h2_aug [M, D+64] = [ LN2(x) | drop(LN2(x)) A_m^T (r values) | 0 ]              (ucod_layernorm_lora_mlp)
+ *             fc1_w_aug [N1, D+64] = [ fc1_w | alpha/r * B_m (dense rows) | 0 ]               (ucod_lora_mlp_pack)
+ *   backward  dpre [M, N1] has no aug columns (the fc2 dgrad's drain writes it), so t = alpha/r * dpre B_m goes to a scratch [M, 64] and the t A_m term of
+ *             d LN2 is added by the LayerNorm-2 backward (ucod_layernorm_bwd_lora_mlp), with or without dropout. */
+#define UCOD_LORA_MLP_MAX_R 8
+/* y_aug bf16 [rows, D+64] = [ LayerNorm(x) | dropout(LN(x)) A_m^T (r values) | 0 ]: ucod_layernorm_lora for ONE module, a_m f32 [r, D]; x_f16 != 0: x is the
+ * IEEE fp16 residual stream, else f32 (full_model.py:47-72) */
+int ucod_layernorm_lora_mlp(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_m, int r, void* y_aug_bf16, int rows, int D,
+                            float eps, const ucod_lora_dropout* dropout, void* stream);
+/* aug columns of fc1_w_aug bf16 [N1, D+64] from one layer's [A_m | B_m]: column D + j = alpha/r * B_m[:, j] for j < r, zero beyond (full_model.py:47-72) */
+int ucod_lora_mlp_pack(const float* lora_mlp, int r, float scaling, void* fc1_w_aug_bf16, int N1, int D, void* stream);
+/* One layer's gradients of the MLP module in one pass over dpre bf16 [rows, N1] and h2_aug bf16 [rows, D+64] per two ranks (full_model.py:47-72):
+ *   t bf16 [rows, 64] = alpha/r * dpre B_m (r values, the rest zero);  dB_m = alpha/r * dpre^T u (u = aug columns of h2_aug);  dA_m = t^T dropout(h2), from the
+ * bf16-rounded t.  grad_mlp f32 [r (D + N1)] is overwritten.  Deterministic: per-block partials in `workspace`, summed in a fixed order.  N1 % 128 == 0,
+ * N1 <= 8192, D % 128 == 0, D <= 1536. */
+size_t ucod_lora_mlp_grad_workspace_bytes(int N1, int D);
+int ucod_lora_mlp_grad(const void* dpre_bf16, const void* h2_aug_bf16, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
+                       void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream);
+/* ucod_layernorm_bwd_lora_ex for ONE module whose t lives anywhere (full_model.py:47-72):  dy += mask/(1-p) * (t A_m), t bf16 rows of length ldt (r values
+ * used), a_m f32 [r, D]; dropout NULL or p == 0: the unmasked term. */
+int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
+                                const ucod_lora_dropout* dropout, void* stream);
+/* The five whole-pass entry points with the MLP module's own per-layer table TM (HOST array of DEVICE pointers), layer l at UCOD_VIT_TRAIN_MLP_STRIDE*l
+ * (full_model.py:47-72):
+ *   +0 fc1_w_aug bf16 [N1, D+64] (aug columns maintained by ucod_lora_mlp_pack)   +1 LoRA parameters f32 [r (D + N1)]   +2 LoRA gradients f32 [r (D + N1)]
+ * TM == NULL: q / k / v only -- exactly the launches of the _mlp entry points.  Otherwise lora_r <= UCOD_LORA_MLP_MAX_R (else UCOD_EINVAL, sizes 0); per layer
+ * below the last the forward runs ucod_layernorm_lora_mlp and fc1 with K = D+64, the backward recomputes h2_aug from the saved residual stream, runs
+ * ucod_lora_mlp_grad and ucod_layernorm_bwd_lora_mlp.  The last layer's MLP never reaches the key map: its gradients are written as zeros. */
+#define UCOD_VIT_TRAIN_MLP_STRIDE 3
+size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host);
+int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                                    const void* const* mlp_table_host, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                               const void* const* mlp_table_host, const float* dkey, void* workspace, size_t workspace_bytes, void* stream);
+size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host);
+int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                                         const void* const* mlp_table_host, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
+                                         void* stream);
+
 /* ------------------------------------------------------------------ decoder / APM path (rows A1-A8) */
 
 /* F.interpolate(mode='bilinear', align_corners=False) on `planes` independent [ih,iw] maps

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Backbone-backward (LoRA) mode at the headline size: forward_train + backward of DINOv2 ViT-B/14 @518 (or, sixth argument dinov2_vitg14, of ViT-g/14 with its
-SwiGLU MLP), per-class kernel times.   lora_bench.py [B [steps [streams [dropout [resid [arch]]]]]]"""
+SwiGLU MLP), per-class kernel times.   lora_bench.py [B [steps [streams [dropout [resid [arch [targets]]]]]]]
+``targets``: comma list of LoRA target modules (default: the engine's query,key,value), e.g. query,key,value,fc1 or query,key,value,weights_in on ViT-g."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,7 +20,11 @@ if arch not in ("dinov2_vitb14", "dinov2_vitg14"):
     sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14, got {arch}")
 giant = arch == "dinov2_vitg14"
 heads = 24 if giant else 12
-eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant)
+targets = sys.argv[7].split(",") if len(sys.argv) > 7 and sys.argv[7] else None
+kw = {} if targets is None else dict(target_modules=targets)
+eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant, **kw)
+if targets is not None:
+    print(f"targets {targets}: arena [{eng.L}, {eng.lora.shape[1]}]")
 eng.train_streams = streams
 x = torch.randn(B, 3, 518, 518, device="cuda")
 dkey = torch.randn(B, 64 * heads, 37, 37, device="cuda")
@@ -49,6 +54,13 @@ rows = [(lib.ucod_prof_class_name(i).decode(), cnt[i], tot[i]) for i in range(n)
 for name, c, t in sorted(rows, key=lambda r: -r[2]):
     print(f"  {name:34s} {c:4d} launches  {t:8.3f} ms total  {t / c * 1e3:8.1f} us avg")
 print(f"  sum {sum(r[2] for r in rows):.2f} ms")
+if getattr(eng, "mlp_target", None) is not None:
+    # the MLP module's gradient kernel against the bytes it has to move: one pass over dpre [M, N1] and one over h2_aug [M, D+64], both bf16 (per two ranks)
+    M = B * 1370
+    byts = (M * eng.N1 * 2 + M * (eng.D + 64) * 2) * ((eng.r + 1) // 2)
+    for name, c, t in rows:
+        if name == "lora_mlp_grad":
+            print(f"  lora_mlp_grad: {byts / 1e6:.1f} MB per launch pair (grad + reduce), {t / c * 1e3:.1f} us -> {byts / (t / c * 1e-3) / 1e12:.2f} TB/s")
 if giant:
     # the two SwiGLU training launches alone at this pass's shapes, and beside them (orientation) the launches they extend: UCOD_EPI_BIAS_SWIGLU_BF16 at (M, 2F, D),
     # which the SAVE form extends by one [M, 2F] store, and UCOD_EPI_GELU_BWD_BF16 at (M, F, D), which reads and writes half the bytes of the SwiGLU dgrad drain

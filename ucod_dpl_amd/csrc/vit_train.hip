@@ -64,15 +64,16 @@ static Drop make_drop(const ucod_lora_dropout* dd) {
 // LayerNorm forward + LoRA down-projection.  One wave per row, D = 128*NCH, row in registers (as layernorm_kernel).
 // ---------------------------------------------------------------------------------------------------------------------
 // XH16: the residual stream is IEEE fp16 (the no-grad pass of the EMA teacher, ucod_vit_forward_lora_infer with resid16) instead of f32
-template <int NCH, bool XH16 = false>
+// NP: modules sharing the row -- 3 (query, key, value: `lora` is the layer's [A_q | B_q | A_k | B_k | A_v | B_v]) or 1 (the MLP input projection: `lora` is A_m)
+template <int NCH, bool XH16 = false, int NP = 3>
 __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x_, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, const float* __restrict__ lora,
                                                       int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop) {
   // the 3r LoRA A rows live in LDS for the whole block (they were re-read from L2 for every row: 92 us against 33 us for the plain
   // LayerNorm); each wave walks rows block-stride, two rows in flight (as layernorm_kernel)
-  extern __shared__ float a_lds[];                               // [3r][D]
+  extern __shared__ float a_lds[];                               // [NP r][D]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < 3 * r * D; i += 256) {
+  for (int i = threadIdx.x; i < NP * r * D; i += 256) {
     const int p = i / (r * D), rem = i - p * r * D;               // A_p at lora + p*2*r*D
     a_lds[i] = lora[(size_t)p * 2 * r * D + rem];
   }
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x
       }
       // u[j] = <dropout_p(LN(x)), A[j]>, j = p*r + rank
       float mine = 0.f;
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
         float2 vm[NCH];
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x
           if (lane == j) mine = d;
         }
       }
-      yr[D + lane] = f32_to_bf16(lane < 3 * r ? mine : 0.f);
+      yr[D + lane] = f32_to_bf16(lane < NP * r ? mine : 0.f);
     }
   }
 }
@@ -152,13 +153,13 @@ __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x
 // The same for D % 256 == 0 (ViT-B 768, ViT-L 1024) with a lane owning FOUR consecutive columns per chunk (round 4): 16-byte (f32) / 8-byte (fp16)
 // loads, 8-byte stores instead of 4-byte ones, and the dropout mix of an element computed ONCE for its three masks (in the form above the compiler
 // shared it between only some of the projections: 177 v_mul_lo_u32 per two rows instead of 72).
-template <int NV, bool XH16>
+template <int NV, bool XH16, int NP = 3>
 __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ x_, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, const float* __restrict__ lora,
                                                        int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop) {
-  extern __shared__ float a_lds[];                               // [3r][D]
+  extern __shared__ float a_lds[];                               // [NP r][D]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < 3 * r * D; i += 256) {
+  for (int i = threadIdx.x; i < NP * r * D; i += 256) {
     const int p = i / (r * D), rem = i - p * r * D;
     a_lds[i] = lora[(size_t)p * 2 * r * D + rem];
   }
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ 
       }
       float mine = 0.f;
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < NP; ++p) {
         f4 vm[NV];
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ 
           if (lane == j) mine = d;
         }
       }
-      yr[D + lane] = f32_to_bf16(lane < 3 * r ? mine : 0.f);
+      yr[D + lane] = f32_to_bf16(lane < NP * r ? mine : 0.f);
     }
   }
 }
@@ -262,7 +263,8 @@ __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ 
 // that one latency covers all three streams (round 3: 103 -> see profiles/r03_ln_bwd.txt).
 // DYB: dy arrives as bf16 (the dgrad GEMMs of the backward driver write their output in the 16-bit type: half the bytes on both sides).
 // XH: x (the saved LayerNorm input = the residual stream) is IEEE fp16 (training pass with vit.resid16).
-template <int NCH, int VW, bool LORA, bool DYB, bool XH>
+// LORA: 0, or the number of modules whose branch is added -- 3 (q / k / v: t at tq[p r + j], A_p at lora + p 2 r D) or 1 (the MLP input projection: lora = A_m)
+template <int NCH, int VW, int LORA, bool DYB, bool XH>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy_, const void* __restrict__ x_,
                                                      const float* __restrict__ gamma, const float* __restrict__ dres,
                                                      const float* __restrict__ scale, float* __restrict__ dx,
@@ -308,21 +310,21 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     vecf d = g[i];
-    if constexpr (LORA) {
+    if constexpr (LORA > 0) {
       const unsigned idx = (unsigned)row * (unsigned)D + (unsigned)VW * (unsigned)(lane + 64 * i);
       auto branch = [&](auto rc) {                                // rank known at compile time: the 3 r coefficient / A-row loads go out together
         constexpr int R = decltype(rc)::value;
-        vecf av[3][R];
-        float t[3][R];
+        vecf av[LORA][R];
+        float t[LORA][R];
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < LORA; ++p)
 #pragma unroll
           for (int jr = 0; jr < R; ++jr) {
             t[p][jr] = bf16_to_f32(tq[(size_t)row * ldt + p * R + jr]);
             av[p][jr] = reinterpret_cast<const vecf*>(lora + (size_t)p * 2 * R * D + (size_t)jr * D)[lane + 64 * i];
           }
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < LORA; ++p) {
           vecf acc = (vecf)(0.f);
 #pragma unroll
           for (int jr = 0; jr < R; ++jr) acc += t[p][jr] * av[p][jr];
@@ -334,7 +336,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
       else if (r == 4) branch(std::integral_constant<int, 4>{});
       else if (r == 1) branch(std::integral_constant<int, 1>{});
       else {
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < LORA; ++p) {
           vecf acc = (vecf)(0.f);
           for (int jr = 0; jr < r; ++jr) {
             const float t = bf16_to_f32(tq[(size_t)row * ldt + p * r + jr]);
@@ -634,24 +636,27 @@ constexpr int LORA_GRAD_BLOCKS = 512;                            // (1024 measur
 
 using namespace ucod;
 
+// np: 3 = the q / k / v modules of one layer (lora = the layer's arena row), 1 = the MLP input projection (lora = A_m)
 static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const float* beta, const float* lora, int r, void* y_aug, int rows, int D, float eps,
-                          const ucod_lora_dropout* dropout, void* stream) {
-  if (!x || !gamma || !beta || !lora || !y_aug || rows <= 0 || D <= 0 || (D % 128) != 0 || r < 1 || 3 * r > AUG) return UCOD_EINVAL;
+                          const ucod_lora_dropout* dropout, void* stream, int np = 3) {
+  if (!x || !gamma || !beta || !lora || !y_aug || rows <= 0 || D <= 0 || (D % 128) != 0 || r < 1 || np * r > AUG) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
-  UCOD_PROF(PROF_LN, stream);
+  UCOD_PROF(np == 1 ? PROF_LN_LORA_MLP : PROF_LN, stream);
   const Drop drop = make_drop(dropout);
   static const int lnl_env = [] { const char* e = ucod::lab_env("UCOD_LN_LORA_NBLK"); return e ? atoi(e) : 0; }();          // measurement knob
   const int lnl_max = lnl_env > 0 ? lnl_env : 2048;
   const int nblk = cdiv(rows, 8) < lnl_max ? cdiv(rows, 8) : lnl_max;   // block-stride over rows: the A rows are staged once per block
   dim3 grid(nblk), block(256);
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = (size_t)3 * r * D * sizeof(float);
+  const size_t lds = (size_t)np * r * D * sizeof(float);
   static const bool narrow = ucod::lab_env("UCOD_LN_LORA_NARROW") != nullptr;     // measurement knob: the 8-byte / 4-byte form
   if ((D % 256) == 0 && D <= 1536 && !narrow) {
     switch (D / 256) {
 #define C4(n)                                                                                                                                        \
   case n:                                                                                                                                            \
-    if (x_h16) hipLaunchKernelGGL((ln_lora4_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);     \
+    if (np == 1 && x_h16) hipLaunchKernelGGL((ln_lora4_kernel<n, true, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
+    else if (np == 1) hipLaunchKernelGGL((ln_lora4_kernel<n, false, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);    \
+    else if (x_h16) hipLaunchKernelGGL((ln_lora4_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
     else hipLaunchKernelGGL((ln_lora4_kernel<n, false>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);          \
     break;
       C4(1) C4(2) C4(3) C4(4) C4(5) C4(6)
@@ -663,7 +668,9 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   switch (D / 128) {
 #define C(n)                                                                                                                                         \
   case n:                                                                                                                                            \
-    if (x_h16) hipLaunchKernelGGL((ln_lora_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);      \
+    if (np == 1 && x_h16) hipLaunchKernelGGL((ln_lora_kernel<n, true, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
+    else if (np == 1) hipLaunchKernelGGL((ln_lora_kernel<n, false, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);    \
+    else if (x_h16) hipLaunchKernelGGL((ln_lora_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);      \
     else hipLaunchKernelGGL((ln_lora_kernel<n, false>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);           \
     break;
     C(1) C(2) C(3) C(4) C(5) C(6) C(8) C(10) C(12)
@@ -687,19 +694,22 @@ extern "C" int ucod_layernorm_lora_h16(const void* x_f16, const float* gamma, co
 }
 
 static int launch_ln_bwd(const void* dy, bool dy_bf16, const void* x, bool x_f16, const float* gamma, const float* dres, const float* next_scale, float* dx, void* s_bf16,
-                         int rows, int D, float eps, const bf16_raw* tq, int ldt, const float* lora, int r, const Drop& drop, hipStream_t s) {
+                         int rows, int D, float eps, const bf16_raw* tq, int ldt, const float* lora, int r, const Drop& drop, hipStream_t s, int np = 3) {
   dim3 grid(cdiv(rows, 4)), block(256);
   const bool lo = tq != nullptr;
   if (x_f16 && !dy_bf16) return UCOD_EINVAL;                // (the fp16 stream comes with bf16 dgrad outputs: the driver's only use)
 #define L(n, vw, lora_, dyb_, xh_) hipLaunchKernelGGL((ln_bwd_kernel<n, vw, lora_, dyb_, xh_>), grid, block, 0, s, dy, x, gamma, dres, next_scale, dx, (bf16_raw*)s_bf16, rows, D, eps, tq, ldt, lora, r, drop)
 #define C(n, vw)                                                                                                                               \
   case n:                                                                                                                                      \
-    if (lo && x_f16) L(n, vw, true, true, true);                                                                                               \
-    else if (lo && dy_bf16) L(n, vw, true, true, false);                                                                                       \
-    else if (lo) L(n, vw, true, false, false);                                                                                                 \
-    else if (x_f16) L(n, vw, false, true, true);                                                                                               \
-    else if (dy_bf16) L(n, vw, false, true, false);                                                                                            \
-    else L(n, vw, false, false, false);                                                                                                        \
+    if (lo && np == 1 && x_f16) L(n, vw, 1, true, true);                                                                                       \
+    else if (lo && np == 1 && dy_bf16) L(n, vw, 1, true, false);                                                                               \
+    else if (lo && np == 1) L(n, vw, 1, false, false);                                                                                         \
+    else if (lo && x_f16) L(n, vw, 3, true, true);                                                                                             \
+    else if (lo && dy_bf16) L(n, vw, 3, true, false);                                                                                          \
+    else if (lo) L(n, vw, 3, false, false);                                                                                                    \
+    else if (x_f16) L(n, vw, 0, true, true);                                                                                                   \
+    else if (dy_bf16) L(n, vw, 0, true, false);                                                                                                \
+    else L(n, vw, 0, false, false);                                                                                                            \
     break;
   if (D % 256 == 0) {                                      // 16-byte accesses
     switch (D / 256) {
@@ -851,4 +861,252 @@ extern "C" int ucod_lora_grad(void* dqkv_aug, const void* h_aug, const float* lo
     UCOD_CHECK_LAUNCH();
   }
   return UCOD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LoRA on the MLP input projection (fc1; weights_in of the SwiGLU MLP): ONE module of width N1 whose input is LayerNorm 2's output.
+//   forward   h2_aug [M, D+64] = [ LN2(x) | u = drop(LN2(x)) A_m^T (r values) | 0 ]          (ucod_layernorm_lora_mlp: ln_lora*_kernel with NP = 1)
+//             fc1_w_aug [N1, D+64] = [ fc1_w | alpha/r * B_m | 0 ]                            (ucod_lora_mlp_pack)
+//   backward  dpre [M, N1] comes out of the fc2 dgrad's drain without aug columns, so
+//             t = alpha/r * dpre B_m -> scratch [M, 64],  dB_m = alpha/r * dpre^T u,  dA_m = t^T drop(LN2(x))     (ucod_lora_mlp_grad)
+//             and the t A_m term of d LN2 is added by the LayerNorm-2 backward             (ucod_layernorm_bwd_lora_mlp: ln_bwd_kernel with LORA = 1)
+// Parameter layout of one layer (f32): [A_m (r x D) | B_m (N1 x r)].
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ucod {
+
+__global__ __launch_bounds__(256) void lora_mlp_pack_kernel(const float* __restrict__ lora, int r, float scaling, bf16_raw* __restrict__ w_aug, int N1, int D) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;                // one thread per (row, aug column)
+  if (idx >= N1 * AUG) return;
+  const int n = idx / AUG, j = idx - n * AUG;
+  const float v = j < r ? scaling * lora[(size_t)r * D + (size_t)n * r + j] : 0.f;              // B_m[n][j]
+  w_aug[(size_t)n * (D + AUG) + D + j] = f32_to_bf16(v);
+}
+
+constexpr int MLP_RB = 4;                                        // rows per iteration = waves per block (wave q writes row q's t)
+constexpr int MLP_RW = 2;                                        // ranks per pass, as lora_grad_kernel (the reference's r = 2 is one pass; r = 8 reads dpre four times)
+static inline int mlp_grad_max_blocks(int N1) { return N1 > 4096 ? 256 : 512; }   // one block per CU at 4 vectors per thread (256 VGPRs + AGPRs: one wave per SIMD), else two
+
+// Ranks [j0, j0 + 2) of the module in one pass over dpre and h2_aug.  The block's 256 threads share a row: thread `tid` owns the 16-byte vectors tid + 256 i of
+// the dpre row (its B_m values and dB accumulators stay in registers for all the block's rows) and the column pairs tid + 256 i of h2 (dA accumulators).  MLP_RB
+// rows are loaded together, their partial t summed over the block through LDS (one barrier per MLP_RB rows: two buffers in turn), rounded to bf16 as the
+// LayerNorm-2 backward will read it, and used for dA.  No element has two owners in a block, so the partials go straight to memory: [2][D] | [N1][2] per block,
+// summed in a fixed order by lora_mlp_grad_reduce_kernel.  Rows past the end load nothing and contribute zeros.
+// Measured: 2.0 TB/s at ViT-B and at ViT-g, where <4, *> takes 256 VGPRs + 125-145 AGPRs (one wave per SIMD) and nothing overlaps a group's loads.
+// h2 is the smaller operand (D+64 against N1 columns) and is read with 4-byte loads.
+template <int NVT, int NPT>
+__global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __restrict__ dpre, const bf16_raw* __restrict__ h, const float* __restrict__ lora,
+                                                            int r, int j0, float scaling, float* __restrict__ partial, bf16_raw* __restrict__ tout, int rows,
+                                                            int N1, int D, Drop drop) {
+  constexpr int RW = MLP_RW, RB = MLP_RB;
+  __shared__ float red[2][4][RB][RW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NV = N1 / 8, NP2 = D / 2, ldh = D + AUG;
+  const float* Bm = lora + (size_t)r * D;
+  float bw[NVT][8][RW], accB[NVT][8][RW], accA[RW][NPT][2];
+#pragma unroll
+  for (int i = 0; i < NVT; ++i) {
+    const int v = tid + 256 * i;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        bw[i][e][j] = (v < NV && j0 + j < r) ? Bm[(size_t)(8 * v + e) * r + j0 + j] : 0.f;
+        accB[i][e][j] = 0.f;
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < RW; ++j)
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) accA[j][i][0] = accA[j][i][1] = 0.f;
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  int buf = 0;
+  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB, buf ^= 1) {
+    u4 dw[RB][NVT];
+    unsigned hw_[RB][NPT];
+    float u[RB][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const bool live = row0 + q < rows;
+      const int row = live ? row0 + q : rows - 1;
+      const u4* dr = reinterpret_cast<const u4*>(dpre + (size_t)row * N1);
+      const unsigned* hr = reinterpret_cast<const unsigned*>(h + (size_t)row * ldh);
+#pragma unroll
+      for (int i = 0; i < NVT; ++i) dw[q][i] = (live && tid + 256 * i < NV) ? dr[tid + 256 * i] : (u4)(0u);
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) hw_[q][i] = (live && tid + 256 * i < NP2) ? hr[tid + 256 * i] : 0u;
+#pragma unroll
+      for (int j = 0; j < RW; ++j) u[q][j] = (live && j0 + j < r) ? bf16_to_f32(h[(size_t)row * ldh + D + j0 + j]) : 0.f;   // (block-uniform address)
+    }
+    float t[RB][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      float s[RW];
+#pragma unroll
+      for (int j = 0; j < RW; ++j) s[j] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NVT; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const float d0 = __uint_as_float(dw[q][i][w] << 16), d1 = __uint_as_float(dw[q][i][w] & 0xFFFF0000u);
+#pragma unroll
+          for (int j = 0; j < RW; ++j) {
+            s[j] += d0 * bw[i][2 * w][j] + d1 * bw[i][2 * w + 1][j];
+            accB[i][2 * w][j] += d0 * u[q][j];
+            accB[i][2 * w + 1][j] += d1 * u[q][j];
+          }
+        }
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        const float ws = wave_sum(s[j]);
+        if (lane == 0) red[buf][wave][q][j] = ws;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RB; ++q)
+#pragma unroll
+      for (int j = 0; j < RW; ++j)     // the LayerNorm-2 backward sees the bf16 value: use it for dA too
+        t[q][j] = bf16_to_f32(f32_to_bf16(scaling * ((red[buf][0][q][j] + red[buf][1][q][j]) + (red[buf][2][q][j] + red[buf][3][q][j]))));
+    // wave q writes the 64 t columns of row q: the first pass every column (zeros beyond the rank), later passes their two
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      if (q != wave || row0 + q >= rows) continue;
+      const int c = lane - j0;
+      const float val = (c == 0 && j0 < r) ? t[q][0] : (c == 1 && j0 + 1 < r) ? t[q][1] : 0.f;
+      if (j0 == 0 || (c >= 0 && c < RW && lane < r)) tout[(size_t)(row0 + q) * AUG + lane] = f32_to_bf16(val);
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q)
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        float h0 = __uint_as_float(hw_[q][i] << 16), h1 = __uint_as_float(hw_[q][i] & 0xFFFF0000u);
+        if (drop.thresh) {                                       // dA sees the SAME dropped input the forward's lora_A saw
+          const unsigned idx = (unsigned)(row0 + q) * (unsigned)D + 2u * (unsigned)(tid + 256 * i);
+          h0 *= drop_scale(drop, 0, idx);
+          h1 *= drop_scale(drop, 0, idx + 1u);
+        }
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+          accA[j][i][0] += t[q][j] * h0;
+          accA[j][i][1] += t[q][j] * h1;
+        }
+      }
+  }
+  float* out = partial + (size_t)blockIdx.x * (size_t)(RW * D + N1 * RW);
+#pragma unroll
+  for (int j = 0; j < RW; ++j)
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+      const int c = tid + 256 * i;
+      if (c < NP2) *reinterpret_cast<float2*>(out + (size_t)j * D + 2 * c) = make_float2(accA[j][i][0], accA[j][i][1]);
+    }
+  out += RW * D;
+#pragma unroll
+  for (int i = 0; i < NVT; ++i) {
+    const int v = tid + 256 * i;
+    if (v >= NV) continue;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int e = 0; e < 8; e += 2)       // rows 8v+e, 8v+e+1 of [N1][2]: four consecutive floats
+      *reinterpret_cast<f4*>(out + (size_t)(8 * v + e) * RW) =
+          (f4){scaling * accB[i][e][0], scaling * accB[i][e][1], scaling * accB[i][e + 1][0], scaling * accB[i][e + 1][1]};
+  }
+}
+
+// partial [nblk][2 D + 2 N1] -> grad [A_m (r x D) | B_m (N1 x r)], ranks [j0, j0 + 2): 32 elements x 8 slices of the block list per workgroup
+__global__ __launch_bounds__(256) void lora_mlp_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int r, int j0, float* __restrict__ grad, int N1,
+                                                                   int D) {
+  constexpr int RW = MLP_RW;
+  __shared__ float red[8][33];
+  const int nA = RW * D, n = nA + N1 * RW;
+  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + e;
+  float s = 0.f;
+  if (i < n) {
+#pragma unroll 4
+    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
+  }
+  red[sl][e] = s;
+  __syncthreads();
+  if (sl != 0 || i >= n) return;
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += red[k][e];
+  if (i < nA) {
+    const int j = i / D, d = i - j * D;
+    if (j0 + j < r) grad[(size_t)(j0 + j) * D + d] = s;
+  } else {
+    const int k = i - nA, row = k / RW, j = k - row * RW;
+    if (j0 + j < r) grad[(size_t)r * D + (size_t)row * r + j0 + j] = s;
+  }
+}
+
+}  // namespace ucod
+
+extern "C" int ucod_layernorm_lora_mlp(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_m, int r, void* y_aug, int rows, int D,
+                                       float eps, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (r < 1 || r > UCOD_LORA_MLP_MAX_R) return UCOD_EINVAL;
+  return launch_ln_lora(x, x_f16 != 0, gamma, beta, a_m, r, y_aug, rows, D, eps, dropout, stream, 1);
+}
+
+extern "C" int ucod_lora_mlp_pack(const float* lora_mlp, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!lora_mlp || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || D <= 0) return UCOD_EINVAL;
+  UCOD_PROF(PROF_LORA, stream);
+  hipLaunchKernelGGL(lora_mlp_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora_mlp, r, scaling, (bf16_raw*)fc1_w_aug, N1, D);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" size_t ucod_lora_mlp_grad_workspace_bytes(int N1, int D) {
+  if (N1 <= 0 || N1 > 8192 || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
+  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (D + N1)) * sizeof(float);
+}
+
+extern "C" int ucod_lora_mlp_grad(const void* dpre, const void* h2_aug, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
+                                  void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!dpre || !h2_aug || !lora_mlp || !grad_mlp || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
+  const size_t need = ucod_lora_mlp_grad_workspace_bytes(N1, D);
+  if (need == 0) return UCOD_EINVAL;
+  if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+  if (workspace_bytes < need) return UCOD_ENOMEM;
+  UCOD_PROF(PROF_LORA_MLP_GRAD, stream);
+  const Drop drop = make_drop(dropout);
+  hipStream_t s = (hipStream_t)stream;
+  const int cap = mlp_grad_max_blocks(N1);
+  const int nblk = cdiv(rows, MLP_RB) < cap ? cdiv(rows, MLP_RB) : cap;
+  const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors, 1..3 column pairs per thread
+  for (int j0 = 0; j0 < r; j0 += MLP_RW) {
+#define MG(v, p) hipLaunchKernelGGL((lora_mlp_grad_kernel<v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora_mlp, r, j0, \
+                                    scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
+#define MGP(v)                   \
+  do {                           \
+    if (npt == 1) MG(v, 1);      \
+    else if (npt == 2) MG(v, 2); \
+    else MG(v, 3);               \
+  } while (0)
+    if (nvt == 1) MGP(1);
+    else if (nvt == 2) MGP(2);
+    else MGP(4);                                                  // (3 vectors per thread run the 4-vector form: the fourth is never live)
+#undef MGP
+#undef MG
+    UCOD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, r, j0, grad_mlp, N1, D);
+    UCOD_CHECK_LAUNCH();
+  }
+  return UCOD_OK;
+}
+
+extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                           void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
+                                           const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!dy || !x || !gamma || (!dx && !s_bf16) || rows <= 0 || D <= 0 || (D % 128) != 0 || !t_bf16 || ldt < r || !a_m || r < 1 || r > UCOD_LORA_MLP_MAX_R ||
+      (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) || (flags & ~3))
+    return UCOD_EINVAL;
+  UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
+  return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
+                       (const bf16_raw*)t_bf16, ldt, a_m, r, make_drop(dropout), (hipStream_t)stream, 1);
 }

@@ -6,6 +6,9 @@
 //                            weight-gradient GEMMs: dgrad only, ~2x the forward FLOPs with the recomputed attention scores)
 // The _mlp forms take the MLP kind: UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) saves the interleaved pre-activation [M, 2F] from the weights_in
 // drain (UCOD_EPI_BIAS_SWIGLU_SAVE_BF16) and turns the hidden cotangent into dpre [M, 2F] in the weights_out dgrad's drain (UCOD_EPI_SWIGLU_BWD_BF16).
+// The _lora_mlp forms take the per-layer table of a LoRA module on the MLP input projection (fc1 / weights_in; full_model.py:47-72 hands target_modules to peft):
+// LayerNorm 2 then writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against fc1_w_aug, and the backward recomputes h2_aug from the
+// saved residual stream, takes the module's gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the LayerNorm-2 backward.  A NULL table is the _mlp form.
 // No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
@@ -18,12 +21,13 @@ struct TPlan {
   size_t s_x, s_h, s_qkv, s_att, s_lse, s_pre;
   size_t h2, g, patch, qscale;                             // forward transients
   size_t dx, dh, s, da, dqkv, delta, lgw;                  // backward scratch (dpre aliases g, s aliases h2)
+  size_t tm, mgw, mgw_bytes;                               // MLP LoRA module: t scratch [M, 64], partials of ucod_lora_mlp_grad
   size_t total;
 };
 
 inline size_t up(size_t v) { return (v + 255) / 256 * 256; }
 
-bool valid(const ucod_vit_train_desc* t) {
+bool valid_qkv(const ucod_vit_train_desc* t) {
   if (!t) return false;
   const ucod_vit_desc* d = &t->vit;
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
@@ -33,8 +37,14 @@ bool valid(const ucod_vit_train_desc* t) {
 }
 
 inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU; }
+inline int fc1_width(const ucod_vit_desc* d, int mlp) { return mlp == UCOD_MLP_SWIGLU ? 2 * d->F : d->F; }
+// mlpl: the pass carries a LoRA module on the MLP input projection (its rank limit and the widths its gradient kernel covers)
+inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl) {
+  return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && ucod_lora_mlp_grad_workspace_bytes(fc1_width(&t->vit, mlp), t->vit.D) != 0);
+}
+bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false) { return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl); }
 
-TPlan make_plan(const ucod_vit_train_desc* t, int mlp) {
+TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;
   TPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
@@ -58,7 +68,7 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp) {
   p.att = take(p.s_att * (L - 1));
   p.lse = take(p.s_lse * (L - 1));
   p.pre = take(p.s_pre * (L - 1));
-  p.h2 = take(M * D * 2);
+  p.h2 = take(M * (D + (mlpl ? UCOD_LORA_AUG : 0)) * 2);      // (MLP LoRA module: h2_aug; s [M, D] still fits)
   p.g = take(M * FP * 2);                                     // the hidden [M, F]; the backward's dpre [M, FP] aliases it
   p.patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
   p.qscale = take(3 * D * 4);
@@ -69,6 +79,12 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp) {
   p.dqkv = take(M * (3 * D + UCOD_LORA_AUG) * 2);
   p.delta = take((size_t)d->B * d->heads * p.tok * 4);
   p.lgw = take(ucod_lora_grad_workspace_bytes(d->D));
+  p.tm = p.mgw = p.mgw_bytes = 0;
+  if (mlpl) {
+    p.tm = take(M * UCOD_LORA_AUG * 2);
+    p.mgw_bytes = ucod_lora_mlp_grad_workspace_bytes((int)FP, d->D);
+    p.mgw = take(p.mgw_bytes);
+  }
   p.total = o;
   return p;
 }
@@ -81,16 +97,19 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return valid(t) && known_mlp(mlp) ? make_plan(t, mlp).total : 0; }
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
+  return valid(t, mlp, TM != nullptr) ? make_plan(t, mlp, TM != nullptr).total : 0;
+}
+extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_train_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_train_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
-                                          float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t) || !known_mlp(mlp) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp);
+  const TPlan p = make_plan(t, mlp, TM != nullptr);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
@@ -135,13 +154,26 @@ extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp,
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_attention_fwd_lse(qkv, att, lse, d->B, tok, d->heads, stream));
     RUN(ucod_gemm_bf16(epi_resid, att, W[4], x_mid, M, D, D, (const float*)W[5], (const float*)W[6], x_in, nullptr, tok, gv, stream));
-    if (r16) RUN(ucod_layernorm_h16(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
-    else RUN(ucod_layernorm(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-    if (swiglu) RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_SWIGLU_SAVE_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, pre, gv, stream));
-    else RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
+    if (TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug (its own mask: key L + l)
+      const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
+      const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
+      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D, d->eps,
+                                  t->lora_dropout > 0.f ? &drop_m : nullptr, stream));
+      RUN(ucod_gemm_bf16_train(swiglu ? UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 : UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, Y[0], g, M, fc1_width(d, mlp), KA, (const float*)W[10],
+                               nullptr, pre, gv, stream));
+    } else {
+      if (r16) RUN(ucod_layernorm_h16(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
+      else RUN(ucod_layernorm(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
+      if (swiglu) RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_SWIGLU_SAVE_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, pre, gv, stream));
+      else RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
+    }
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x_next, M, D, F, (const float*)W[12], (const float*)W[13], x_mid, nullptr, tok, gv, stream));
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
+                                          float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_train_lora_mlp(t, mlp, T, TT, nullptr, img, key_out, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
                                       float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -165,7 +197,7 @@ bool valid_infer(const ucod_vit_train_desc* t) {
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && (d->resid16 == 0 || d->resid16 == 1);
 }
-IPlan make_iplan(const ucod_vit_train_desc* t) {
+IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;
   IPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
@@ -176,7 +208,7 @@ IPlan make_iplan(const ucod_vit_train_desc* t) {
   auto take = [&](size_t bytes) { size_t r = o; o += up(bytes); return r; };
   p.x = take(M * D * (d->resid16 ? 2 : 4));
   p.h_aug = take(M * (D + UCOD_LORA_AUG) * 2);
-  p.h2 = take(M * D * 2);
+  p.h2 = take(M * (D + (mlpl ? UCOD_LORA_AUG : 0)) * 2);
   p.qkv = take(M * 3 * D * 2);
   p.a = take(M * D * 2);
   p.g = take(M * F * 2);                                      // (either kind: the hidden [M, F]; SwiGLU's weights_in output never reaches memory)
@@ -187,16 +219,19 @@ IPlan make_iplan(const ucod_vit_train_desc* t) {
 }
 }  // namespace
 
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return valid_infer(t) && known_mlp(mlp) ? make_iplan(t).total : 0; }
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
+  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) ? make_iplan(t, TM != nullptr).total : 0;
+}
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_lora_infer_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_lora_infer_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
-                                               float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid_infer(t) || !known_mlp(mlp) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const ucod_vit_desc* d = &t->vit;
-  const IPlan p = make_iplan(t);
+  const IPlan p = make_iplan(t, TM != nullptr);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
@@ -231,26 +266,39 @@ extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, 0.f, 0, stream));
     RUN(ucod_gemm_bf16(epi_resid, a, W[4], x, M, D, D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
-    if (r16) RUN(ucod_layernorm_h16(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
-    else RUN(ucod_layernorm(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-    if (swiglu) RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SWIGLU_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
-    else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+    if (TM) {
+      const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
+      const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
+      RUN(ucod_layernorm_lora_mlp(x, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D, d->eps,
+                                  t->lora_dropout > 0.f ? &drop_m : nullptr, stream));
+      RUN(ucod_gemm_bf16(swiglu ? UCOD_EPI_BIAS_SWIGLU_BF16 : UCOD_EPI_BIAS_GELU_BF16, h2, Y[0], g, M, fc1_width(d, mlp), KA, (const float*)W[10], nullptr, nullptr,
+                         nullptr, tok, gv, stream));
+    } else {
+      if (r16) RUN(ucod_layernorm_h16(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
+      else RUN(ucod_layernorm(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
+      if (swiglu) RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SWIGLU_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+      else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
+    }
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x, M, D, F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
+                                               float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_lora_infer_lora_mlp(t, mlp, T, TT, nullptr, img, key_out, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
                                            float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   return ucod_vit_forward_lora_infer_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
 }
 
-extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                          const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t) || !known_mlp(mlp) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp);
+  const TPlan p = make_plan(t, mlp, TM != nullptr);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KQ = 3 * D + UCOD_LORA_AUG, r = t->lora_r;
@@ -294,8 +342,12 @@ extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, cons
     return ln_bwd_plain(dy, x, gam, dres, next_scale);
   };
 
-  // last layer: only the key projection reaches the loss
+  // last layer: only the key projection reaches the loss (its MLP never runs: the module's gradients there are zeros, written as such)
   const int last = d->L - 1;
+  if (TM) {
+    const size_t n_m = (size_t)r * (size_t)(D + fc1_width(d, mlp)) * sizeof(float);
+    if (hipMemsetAsync(const_cast<void*>((TM + UCOD_VIT_TRAIN_MLP_STRIDE * last)[2]), 0, n_m, (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
+  }
   RUN(ucod_key_grad_tokens(dkey, dqkv, d->B, tok, D, stream));
   RUN(qkv_side(last));
   if (last == 0) return UCOD_OK;
@@ -317,12 +369,24 @@ extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, cons
     // (SwiGLU: the weights_out dgrad's drain writes the cotangent of the interleaved weights_in output, dpre [M, 2F]; X[3] = weights_in^T [D, 2F] in that column order)
     if (swiglu) {
       RUN(ucod_gemm_bf16_train(UCOD_EPI_SWIGLU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
-      RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, 2 * F, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     } else {
       RUN(ucod_gemm_bf16_train(UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
-      RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, F, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     }
-    RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
+    const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
+    const ucod_lora_dropout* dp_m = t->lora_dropout > 0.f ? &drop_m : nullptr;
+    const void* const* Y = TM ? TM + UCOD_VIT_TRAIN_MLP_STRIDE * l : nullptr;
+    if (TM) {
+      // LoRA on the MLP input projection.  `s` (the fc2 dgrad's operand) has been consumed: its buffer takes h2_aug, recomputed from the saved residual
+      // stream with the forward's launch (same mask), and is rewritten by the LayerNorm-2 backward below, after the gradient kernel has read it
+      void* h2_aug = ws + p.h2;
+      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D, d->eps, dp_m, stream));
+      RUN(ucod_lora_mlp_grad(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M,
+                             fc1_width(d, mlp), D, dp_m, stream));
+    }
+    RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, fc1_width(d, mlp), nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    if (TM) RUN(ucod_layernorm_bwd_lora_mlp(dh, x_mid, lnb_flags, (const float*)W[7], dx, (const float*)W[6], dx, s, M, D, d->eps, ws + p.tm, UCOD_LORA_AUG,
+                                            (const float*)Y[1], r, dp_m, stream));
+    else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_attention_bwd(qkv, att, da, lse, delta, dqkv, KQ, d->B, tok, d->heads, stream));
@@ -333,6 +397,10 @@ extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, cons
     }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_backward_lora_mlp(t, mlp, T, TT, nullptr, dkey, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* dkey,
                                  void* workspace, size_t workspace_bytes, void* stream) {

@@ -4,7 +4,7 @@ imported: it needs ``peft`` and a module, ``models/modules/ocm.py``, that is not
 Same names and call shapes: ``load_lora(cfg, model)``, ``get_full_model(cfg, checkpoint_path)``,
 ``full_model(config, backbone, decoder)(inputs, ema=False, get_hidden_feature=False)``, ``freeze_lora`` / ``active_lora``,
 ``load_state_dict`` (decoder only, :146-147).  What runs underneath is the HIP training engine (``ViTLoRAEngine``):
-LoRA r / lora_alpha / target modules as :47-72 (query, key, value; bias 'none'), the key hook of the last layer -> CLS
+LoRA r / lora_alpha / target modules as :47-72 (subsets of query, key, value, plus the MLP input projection; bias 'none'), the key hook of the last layer -> CLS
 dropped -> NCHW -> bilinear 68x68 (:95-106), student backbone differentiable w.r.t. its LoRA matrices, EMA backbone
 frozen.  ``enable_ocm`` is rejected: its module does not exist in the reference.  LoRA dropout (``lora_dropout``, 0.05 in the
 reference config) is applied in train mode with counter-based masks (it cannot reproduce torch's RNG stream).
@@ -20,7 +20,8 @@ from ..uscod import baseline
 
 
 class LoRABackbone(nn.Module):
-    """nn.Module face of a ViTLoRAEngine: ONE flat parameter ``lora`` [L, 6*r*D] that aliases the engine's arena."""
+    """nn.Module face of a ViTLoRAEngine: ONE flat parameter ``lora`` [L, P] that aliases the engine's arena (P = 6*r*D; with the MLP input projection
+    targeted, r*(D + N1) more)."""
 
     def __init__(self, engine: ViTLoRAEngine):
         super().__init__()
@@ -43,18 +44,21 @@ class LoRABackbone(nn.Module):
 
 def load_lora(config, state_dict, heads, device="cuda", generator=None):
     """models/modules/full_model.py:47-72.  r == 0 is refused (the reference returns the bare model; use ``backbone`` then).  Either MLP kind of DINOv2 is taken:
-    a SwiGLU checkpoint (facebook/dinov2-giant) trains through the engine's SwiGLU backward (``allow_swiglu``)."""
+    a SwiGLU checkpoint (facebook/dinov2-giant) trains through the engine's SwiGLU backward (``allow_swiglu``).  ``target_modules`` (:54,67: handed to peft as it
+    is) may name any non-empty subset of query / key / value and the MLP input projection (``fc1``; ``weights_in`` on a SwiGLU checkpoint), matched by peft's
+    suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets)."""
     r = getattr(config, "r", 2)
     if r == 0:
         raise ValueError("r == 0: no LoRA -- use data.utils.feature_extractor.backbone for the frozen path")
     alpha = getattr(config, "lora_alpha", 4)
-    targets = list(getattr(config, "target_modules", ["query", "value", "key"]))
-    if sorted(targets) != ["key", "query", "value"]:
-        raise NotImplementedError(f"target_modules {targets}: only query/key/value (the reference default) is built")
+    targets = getattr(config, "target_modules", None)                        # None: query / key / value, the reference's default
+    if targets is not None and not isinstance(targets, str):
+        targets = list(targets)
     if getattr(config, "bias", "none") != "none":
         raise NotImplementedError("LoRA bias modes other than 'none' are not built")
     drop = float(getattr(config, "lora_dropout", 0.05))                      # :50
-    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True))
+    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
+                                      target_modules=targets))
 
 
 class full_model(nn.Module):

@@ -43,6 +43,11 @@ VIT_TRAIN_STRIDE = 7
 VIT_TRAIN_SLOTS = ("qkv_w_aug", "qkv_wt_aug", "proj_wt", "fc1_wt", "fc2_wt", "lora", "lora_grad")
 T_QKV_W_AUG, T_QKV_WT_AUG, T_PROJ_WT, T_FC1_WT, T_FC2_WT, T_LORA, T_LORA_GRAD = range(VIT_TRAIN_STRIDE)
 LORA_AUG = 64
+# the per-layer table of a LoRA module on the MLP input projection (the _lora_mlp entry points): the augmented fc1 / weights_in weight, then its parameters and gradients
+VIT_TRAIN_MLP_STRIDE = 3
+VIT_TRAIN_MLP_SLOTS = ("fc1_w_aug", "lora_mlp", "lora_mlp_grad")
+M_FC1_W_AUG, M_LORA, M_LORA_GRAD = range(VIT_TRAIN_MLP_STRIDE)
+LORA_MLP_MAX_R = 8                                          # include/ucod_dpl.h: UCOD_LORA_MLP_MAX_R
 
 vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -153,6 +158,17 @@ SIGNATURES = {
     "ucod_vit_backward_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes_mlp": (sz, [C.POINTER(VitTrainDesc), ci]),
     "ucod_vit_forward_lora_infer_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # LoRA on the MLP input projection as well: its row kernels, and the five entry points with the module's own per-layer table (NULL = the _mlp forms)
+    "ucod_layernorm_lora_mlp": (ci, [vp, ci, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_mlp_pack": (ci, [vp, ci, cf, vp, ci, ci, vp]),
+    "ucod_lora_mlp_grad_workspace_bytes": (sz, [ci, ci]),
+    "ucod_lora_mlp_grad": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_layernorm_bwd_lora_mlp": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, vp, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_vit_train_workspace_bytes_lora_mlp": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp)]),
+    "ucod_vit_forward_train_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_backward_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
+    "ucod_vit_lora_infer_workspace_bytes_lora_mlp": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp)]),
+    "ucod_vit_forward_lora_infer_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16_train": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
     "ucod_layernorm_lora": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_lora_h16": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),

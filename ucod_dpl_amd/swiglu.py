@@ -48,6 +48,27 @@ def prepare(w_in, b_in, w_out):
     return wp[perm].contiguous(), bp[perm].contiguous(), wo.contiguous()
 
 
+def lora_b_to_engine(b_hf):
+    """LoRA B of ``weights_in`` in HF row order, [2 F0, r], -> the engine's rows [2 F, r]: padded like ``prepare`` pads the weight (zero rows) and interleaved."""
+    F0 = b_hf.shape[0] // 2
+    if b_hf.shape[0] != 2 * F0:
+        raise ValueError(f"lora_B of weights_in must have an even number of rows, got {tuple(b_hf.shape)}")
+    F = padded_hidden(F0)
+    bp = b_hf.new_zeros(2 * F, *b_hf.shape[1:])
+    bp[:F0], bp[F:F + F0] = b_hf[:F0], b_hf[F0:]
+    return bp[interleave_perm(F).to(b_hf.device)].contiguous()
+
+
+def lora_b_from_engine(b_eng, F0):
+    """The inverse of ``lora_b_to_engine``: rows [2 F, r] of the engine -> HF order, unpadded [2 F0, r] (padded rows are dropped)."""
+    F = b_eng.shape[0] // 2
+    if F != padded_hidden(F0):
+        raise ValueError(f"{tuple(b_eng.shape)} is not the padded form of a hidden width of {F0}")
+    bp = torch.empty_like(b_eng)
+    bp[interleave_perm(F).to(b_eng.device)] = b_eng
+    return torch.cat((bp[:F0], bp[F:F + F0]), 0).contiguous()
+
+
 def swiglu_interleaved(y):
     """The epilogue's arithmetic on the interleaved GEMM output y [..., 2F] -> [..., F] (checker form; any dtype)."""
     z = y.reshape(*y.shape[:-1], -1, 2, 4)

@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import native as N
+from .swiglu import lora_b_from_engine, lora_b_to_engine
 from . import ops
 
 
@@ -629,6 +630,57 @@ class SplitViTEngine(_BackboneEngine):
 
 _QKV = ("query", "key", "value")
 _MASK64 = 0xFFFFFFFFFFFFFFFF
+_MLP_IN = {"gelu": "fc1", "swiglu": "weights_in"}            # the MLP input projection by MLP kind (modeling_dinov2.py:281-297 / :300-315)
+# the Linear modules of one DINOv2 encoder layer (and the patch embedding's conv) by HF name: what peft's suffix match walks
+_LAYER_MODULES = ("attention.attention.query", "attention.attention.key", "attention.attention.value", "attention.output.dense", "mlp.{mlp_in}", "mlp.{mlp_out}")
+_REFUSED = {
+    "dense": "its input is written by the attention kernel, which has no leading-dimension argument for the 64 LoRA columns",
+    "fc2": "its input is written by the fc1 GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
+    "weights_out": "its input is written by the weights_in GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
+    "projection": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
+}
+
+
+def lora_targets(target_modules=None, mlp="gelu", n_layers=1):
+    """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> ((query, key, value) as booleans, the MLP
+    input projection's name or None).  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``.  Built: any
+    subset of query / key / value and the MLP input projection (``fc1`` on a GELU checkpoint, ``weights_in`` on a SwiGLU one) -- the modules whose input
+    is a LayerNorm output, which the LayerNorm kernel can extend by the LoRA down-projection.  None = the reference's query / key / value."""
+    if mlp not in _MLP_IN:
+        raise ValueError(f"mlp must be 'gelu' or 'swiglu', got {mlp!r}")
+    if target_modules is None:
+        return (True, True, True), None
+    if isinstance(target_modules, str):
+        raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
+    targets = list(target_modules)
+    if not targets:
+        raise ValueError("target_modules is empty: name at least one of query / key / value")
+    mlp_in, mlp_out = _MLP_IN[mlp], {"gelu": "fc2", "swiglu": "weights_out"}[mlp]
+    names = [f"encoder.layer.{i}." + m.format(mlp_in=mlp_in, mlp_out=mlp_out) for i in range(n_layers) for m in _LAYER_MODULES]
+    names.append("embeddings.patch_embeddings.projection")
+    hit = set()
+    for t in targets:
+        if not isinstance(t, str) or not t:
+            raise ValueError(f"target_modules entry {t!r} is not a module name")
+        found = [n for n in names if n == t or n.endswith("." + t)]
+        last = t.rsplit(".", 1)[-1]
+        if not found:
+            other = _MLP_IN["swiglu" if mlp == "gelu" else "gelu"]
+            if last == other:
+                raise ValueError(f"target module {t!r}: this checkpoint has the {mlp.upper() if mlp == 'gelu' else 'SwiGLU'} MLP, whose input projection is "
+                                 f"{mlp_in!r}, not {other!r}")
+            reason = _REFUSED.get(last, "no Linear module of the backbone has that name")
+            raise NotImplementedError(f"LoRA target module {t!r} is not built: {reason}")
+        for n in found:
+            leaf = n.rsplit(".", 1)[-1]
+            if leaf in _REFUSED:
+                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {_REFUSED[leaf]}")
+            hit.add(n)
+    per_layer = [{n.split(".", 3)[3] for n in hit if n.startswith(f"encoder.layer.{i}.")} for i in range(n_layers)]
+    if any(pl != per_layer[0] for pl in per_layer):
+        raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
+    qkv = tuple("attention.attention." + n in per_layer[0] for n in _QKV)
+    return qkv, (mlp_in if "mlp." + mlp_in in per_layer[0] else None)
 
 
 class ViTLoRAEngine(ViTEngine):
@@ -641,14 +693,23 @@ class ViTLoRAEngine(ViTEngine):
     hash mask on the LoRA branch's input in ``train()`` mode and off in ``eval()`` (include/ucod_dpl.h: ucod_lora_dropout).
 
     Parameters live in ONE flat f32 arena ``self.lora`` [L, 6*r*D] (layer-major: A_q | B_q | A_k | B_k | A_v | B_v), gradients
-    in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel."""
+    in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel.
+
+    ``target_modules`` (``lora_targets``): a subset of query / key / value keeps that block and holds the untargeted projections' A and B at zero -- their
+    gradients are then zero by structure (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero.  With the MLP
+    input projection (``fc1`` / ``weights_in``) the row grows to [6*r*D | A_m (r x D) | B_m (N1 x r)], N1 = F (GELU) or 2F in the engine's padded, interleaved row
+    order (SwiGLU), and the passes run the _lora_mlp entry points (include/ucod_dpl.h).  None = query / key / value: the engine as it always was."""
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto", allow_swiglu=False):
+                 seed=0, resid="auto", allow_swiglu=False, target_modules=None):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on."""
-        if normalize_state_dict(state_dict).get("mlp") == "swiglu" and not allow_swiglu:
+        canon = normalize_state_dict(state_dict)
+        mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
+        self.targets, self.mlp_target = lora_targets(target_modules, mlp_kind, len(canon["layers"]))
+        self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
+        if mlp_kind == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
                                       "allow_swiglu=True (models/modules/full_model.py: load_lora passes it); the frozen-backbone engines (ViTEngine / "
                                       "SplitViTEngine) take it as it is")
@@ -669,11 +730,22 @@ class ViTLoRAEngine(ViTEngine):
             raise ValueError(f"LoRA rank {r} unsupported (1 <= r <= {N.LORA_AUG // 3})")
         self.r, self.scaling = int(r), float(lora_alpha) / float(r)
         D, L, dev = self.D, self.L, self.device
-        self.lora = torch.zeros(L, 6 * r * D, dtype=torch.float32, device=dev)
+        self.N1 = (2 if self.mlp == N.UCOD_MLP_SWIGLU else 1) * self.F          # rows of fc1 / of the padded, interleaved weights_in
+        if self.mlp_target is not None:
+            if r > N.LORA_MLP_MAX_R:
+                raise ValueError(f"LoRA rank {r} unsupported with the MLP input projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its gradient kernel keeps a "
+                                 f"lane's B values and accumulators in registers)")
+            if self.lib.ucod_lora_mlp_grad_workspace_bytes(self.N1, D) == 0:
+                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= 8192 rows of {self.mlp_target}")
+        self.qkv_numel = 6 * r * D
+        self.lora = torch.zeros(L, self.qkv_numel + (r * (D + self.N1) if self.mlp_target is not None else 0), dtype=torch.float32, device=dev)
         bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
         for p in range(3):
-            self.lora[:, p * 2 * r * D:p * 2 * r * D + r * D] = a[:, p].to(dev)
+            if self.targets[p]:                         # (an untargeted projection keeps A = B = 0; the draws are made all the same)
+                self.lora[:, p * 2 * r * D:p * 2 * r * D + r * D] = a[:, p].to(dev)
+        if self.mlp_target is not None:                 # drawn after q / k / v: the default engine's stream is untouched
+            self.lora[:, self.qkv_numel:self.qkv_numel + r * D] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
         self.train_layers = []                          # rows of the training table without its two LoRA slots (native.VIT_TRAIN_SLOTS)
@@ -684,6 +756,12 @@ class ViTLoRAEngine(ViTEngine):
             wt_aug[:, :3 * D] = l[N.QKV_W].t()
             # (SwiGLU: fc1_w is the padded, interleaved weights_in [2F, D] -- its transpose's K order is the column order of the pre-activation's cotangent)
             self.train_layers.append([w_aug, wt_aug] + [l[w].t().contiguous() for w in (N.PROJ_W, N.FC1_W, N.FC2_W)])
+        self.mlp_layers = []                            # native.VIT_TRAIN_MLP_SLOTS without the two LoRA slots: the augmented fc1 / weights_in weight
+        if self.mlp_target is not None:
+            for l in self.layers:
+                w_aug = torch.zeros(self.N1, D + A, dtype=torch.bfloat16, device=dev)
+                w_aug[:, :D] = l[N.FC1_W]
+                self.mlp_layers.append([w_aug])
         self.train_streams = 2                          # image-parallel sub-batches of the training passes (_chunks)
         self._tside = None
         self._saved_for = None
@@ -694,25 +772,58 @@ class ViTLoRAEngine(ViTEngine):
         rD = self.r * self.D
         return slice(p * 2 * rD, p * 2 * rD + rD), slice(p * 2 * rD + rD, (p + 1) * 2 * rD)
 
+    def _mlp_slices(self):
+        """(A_m, B_m) of one layer's arena row."""
+        rD = self.r * self.D
+        return slice(self.qkv_numel, self.qkv_numel + rD), slice(self.qkv_numel + rD, self.qkv_numel + rD + self.N1 * self.r)
+
     def lora_state_dict(self, grads=False, prefix="encoder.layer."):
-        """peft-style names: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight"""
+        """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
+        projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded."""
         src = self.lora_grad if grads else self.lora
         out = {}
         for i in range(self.L):
             for p, name in enumerate(_QKV):
+                if not self.targets[p]:
+                    continue
                 sa, sb = self._slices(p)
                 base = f"{prefix}{i}.attention.attention.{name}."
                 out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
                 out[base + "lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
+            if self.mlp_target is not None:
+                sa, sb = self._mlp_slices()
+                base = f"{prefix}{i}.mlp.{self.mlp_target}."
+                b = src[i, sb].reshape(self.N1, self.r)
+                out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
+                out[base + "lora_B.weight"] = lora_b_from_engine(b, self._F0) if self.mlp == N.UCOD_MLP_SWIGLU else b.clone()
         return out
 
     def load_lora_state_dict(self, sd, prefix="encoder.layer."):
+        """The inverse of ``lora_state_dict``.  A LoRA key of a module this engine does not target is refused (its matrices are held at zero)."""
+        names = [f"attention.attention.{name}." for p, name in enumerate(_QKV) if self.targets[p]]
+        names += [f"mlp.{self.mlp_target}."] if self.mlp_target is not None else []
+        want = {f"{prefix}{i}.{n}lora_{ab}.weight" for i in range(self.L) for n in names for ab in "AB"}
+        extra = sorted(k for k in sd if ".lora_" in k and k.startswith(prefix) and k not in want)
+        if extra:
+            raise KeyError(f"LoRA matrices of modules this engine does not target ({', '.join(n.rstrip('.').rsplit('.', 1)[-1] for n in names)} are): {extra[:4]}"
+                           + (" ..." if len(extra) > 4 else ""))
+        take = lambda k: sd[k].to(self.device, torch.float32)  # noqa: E731
         for i in range(self.L):
             for p, name in enumerate(_QKV):
+                if not self.targets[p]:
+                    continue
                 sa, sb = self._slices(p)
                 base = f"{prefix}{i}.attention.attention.{name}."
-                self.lora[i, sa] = sd[base + "lora_A.weight"].to(self.device, torch.float32).reshape(-1)
-                self.lora[i, sb] = sd[base + "lora_B.weight"].to(self.device, torch.float32).reshape(-1)
+                self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
+                self.lora[i, sb] = take(base + "lora_B.weight").reshape(-1)
+            if self.mlp_target is not None:
+                sa, sb = self._mlp_slices()
+                base = f"{prefix}{i}.mlp.{self.mlp_target}."
+                b = take(base + "lora_B.weight")
+                if tuple(b.shape) != ((2 if self.mlp == N.UCOD_MLP_SWIGLU else 1) * self._F0, self.r):
+                    raise ValueError(f"{base}lora_B.weight has shape {tuple(b.shape)}")
+                self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
+                self.lora[i, sb] = (lora_b_to_engine(b) if self.mlp == N.UCOD_MLP_SWIGLU else b).reshape(-1)
         self.repack()
 
     def train(self, mode=True):
@@ -732,6 +843,9 @@ class ViTLoRAEngine(ViTEngine):
         for i, tl in enumerate(self.train_layers):
             N.check(self.lib.ucod_lora_pack(N.ptr(self.lora[i]), self.r, self.scaling, N.ptr(tl[N.T_QKV_W_AUG]), N.ptr(tl[N.T_QKV_WT_AUG]), self.D, zero_a, N.stream()),
                     "ucod_lora_pack")
+        for i, ml in enumerate(self.mlp_layers):               # the MLP module's B columns of fc1_w_aug (its A term is always added by the LayerNorm-2 backward)
+            N.check(self.lib.ucod_lora_mlp_pack(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()),
+                    "ucod_lora_mlp_pack")
         self._packed_zero_a = zero_a
 
     # ---- passes -----------------------------------------------------------------------------------------------------
@@ -743,12 +857,15 @@ class ViTLoRAEngine(ViTEngine):
         return t
 
     def _tables(self, gh, gw, grad):
-        """(table of the plain rows, training table with ``grad`` [L, 6 r D] in its gradient slots, tensors kept alive)"""
+        """(table of the plain rows, training table with ``grad`` [L, P] in its gradient slots, the MLP module's table or None, tensors kept alive)"""
         T, keep = self._table(gh, gw)
-        tptrs = []
+        tptrs, mptrs = [], []
         for i, tl in enumerate(self.train_layers):
             tptrs += tl + [self.lora[i], grad[i]]
-        return T, (C.c_void_p * len(tptrs))(*[t.data_ptr() for t in tptrs]), keep + tptrs
+        for i, ml in enumerate(self.mlp_layers):
+            mptrs += ml + [self.lora[i, self.qkv_numel:], grad[i, self.qkv_numel:]]
+        TM = (C.c_void_p * len(mptrs))(*[t.data_ptr() for t in mptrs]) if mptrs else None
+        return T, (C.c_void_p * len(tptrs))(*[t.data_ptr() for t in tptrs]), TM, keep + tptrs + mptrs
 
     def _chunks(self, B):
         """Image-parallel sub-batches (``self.train_streams``, default 2): as in ViTEngine.forward, every kernel of both passes is
@@ -782,11 +899,17 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             self._chunk_seed[i] = t.seed
-            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_mlp(C.byref(t), self.mlp))
-            T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
-            with self._guard.bind():
-                N.check(self.lib.ucod_vit_forward_train_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                        "ucod_vit_forward_train")
+            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
+            if TM is None:                                         # query / key / value only: the entry points (and launches) the engine always used
+                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_mlp(C.byref(t), self.mlp))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_train_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                            "ucod_vit_forward_train")
+            else:
+                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_mlp(C.byref(t), self.mlp, TM))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_train_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
+                                                                     N.stream()), "ucod_vit_forward_train_lora_mlp")
             if self.resid16:
                 self._guard.arm(torch.cuda.current_stream(self.device))
 
@@ -807,11 +930,17 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             t.vit.resid16 = int(bool(resid16))
-            ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_mlp(C.byref(t), self.mlp))
-            T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
-            with self._guard.bind():
-                N.check(self.lib.ucod_vit_forward_lora_infer_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                        "ucod_vit_forward_lora_infer")
+            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
+            if TM is None:
+                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_mlp(C.byref(t), self.mlp))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_lora_infer_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                            "ucod_vit_forward_lora_infer")
+            else:
+                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_mlp(C.byref(t), self.mlp, TM))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
+                                                                          N.stream()), "ucod_vit_forward_lora_infer_lora_mlp")
             # this engine's own stream type may be f32 (its backward reads it), but THIS pass may run the fp16 one: its saturation counter is
             # fetched behind every chunk and polled by the next call / check_overflow(wait=True) at the loop's boundaries
             if resid16:
@@ -821,7 +950,7 @@ class ViTLoRAEngine(ViTEngine):
         return key
 
     def backward(self, dkey):
-        """dkey [B, D, H/P, W/P] -> self.lora_grad (overwritten), returned as the flat [L, 6*r*D] tensor."""
+        """dkey [B, D, H/P, W/P] -> self.lora_grad (overwritten), returned as the flat [L, P] tensor (P = 6*r*D, plus r*(D + N1) with the MLP module)."""
         if self._saved_for is None:
             raise RuntimeError("backward() without a preceding forward_train()")
         B, H, W = self._saved_for
@@ -832,9 +961,13 @@ class ViTLoRAEngine(ViTEngine):
 
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
-            T, TT, keep = self._tables(gh, gw, self._tside_grad[i])
+            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
             ws = self._tside_ws[i]
-            N.check(self.lib.ucod_vit_backward_mlp(C.byref(t), self.mlp, T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
+            if TM is None:
+                N.check(self.lib.ucod_vit_backward_mlp(C.byref(t), self.mlp, T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
+            else:
+                N.check(self.lib.ucod_vit_backward_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_backward_lora_mlp")
 
         self._fan_out(self._tside, self._bounds, run, (dkey,))
         if len(self._bounds) > 1:
@@ -854,6 +987,7 @@ class ViTLoRAEngine(ViTEngine):
         other.lora = self.lora.clone()
         other.lora_grad = torch.zeros_like(self.lora)
         other.train_layers = [[t.clone() if s in (N.T_QKV_W_AUG, N.T_QKV_WT_AUG) else t for s, t in enumerate(tl)] for tl in self.train_layers]
+        other.mlp_layers = [[t.clone() for t in ml] for ml in self.mlp_layers]          # (the augmented fc1 weight carries the clone's own B_m)
         other._tside, other._saved_for = None, None
         other._guard = _SaturationGuard(self.lib, self.device)
         other._pos_cache = dict(self._pos_cache)
