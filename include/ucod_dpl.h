@@ -565,6 +565,23 @@ int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, 
                                          const void* const* mlp_table_host, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
                                          void* stream);
 
+/* The way out of LoRA mode: merging the trained matrices into ordinary weights (csrc/lora_merge.hip), so that every frozen-backbone engine runs the adapted model.
+ * peft's merge of a LoRA module (what merge_and_unload() does to each module models/modules/full_model.py:47-72 wraps):  W <- W + (lora_alpha / r) B A.
+ *   out[n][k] = f32( f64(w0[n][k]) + f64(scaling) * sum_{j < r, ascending} f64(B[n][j]) * f64(A[j][k]) )
+ * w0, out f32 [N, K] (distinct buffers); A f32 [r, K]; B f32 [N, r]; scaling = lora_alpha / r.  The kernel does not know the row order: the caller passes w0 and B in
+ * the same one (HF order for an export; the engine's padded, interleaved weights_in order for an in-place refresh, where the padded rows of B are zero and come out
+ * as w0's zeros).  In f64 every product of two f32 values is exact, so the result does not depend on FMA formation; one HBM pass over the weight.
+ * UCOD_EINVAL before any launch: a null pointer, r < 1, r > UCOD_LORA_AUG / 3, N < 1, K % 64 != 0 (or K < 64), w0 / A / out not 16-byte aligned.  Both builds. */
+int ucod_lora_merge_f32(const float* w0, const float* A, const float* B, int r, float scaling, float* out, int N, int K, void* stream);
+/* The device form of the LayerNorm fold (fold.py: fold_layernorm_linear; ucod_gemm_lnfold's operands) for a weight that was just merged by ucod_lora_merge_f32
+ * (full_model.py:47-72; W + (lora_alpha / r) B A is `w` here), with the host's rounding sequence, q[n] = row_scale[n] or 1:
+ *   wf[n][k]  = fp16( f32( (f64(w[n][k]) * f64(gamma[k])) * f64(q[n]) ) )          colsum[n] = f32( sum_k f64(wf[n][k]) )   (of the ROUNDED values; exact in f64)
+ *   bias_f[n] = f32( (sum_k f64(w[n][k]) * f64(beta[k]) + f64(b[n])) * f64(q[n]) )                                          (f64 partial sums, shuffle reduce)
+ * w f32 [N, K]; gamma, beta f32 [K]; b f32 [N]; row_scale f32 [N] or NULL; wf fp16 [N, K]; bias_f, colsum f32 [N].  libucod_dpl_f16.so only -- the bf16 build
+ * returns UCOD_EINVAL, like ucod_gemm_lnfold.  UCOD_EINVAL also for a null pointer, N < 1, K % 64 != 0 (or K < 64), w / gamma / beta not 16-byte aligned. */
+int ucod_fold_ln_linear(const float* w, const float* gamma, const float* beta, const float* b, const float* row_scale_or_null, void* wf_f16, float* bias_f,
+                        float* colsum, int N, int K, void* stream);
+
 /* ------------------------------------------------------------------ decoder / APM path (rows A1-A8) */
 
 /* F.interpolate(mode='bilinear', align_corners=False) on `planes` independent [ih,iw] maps

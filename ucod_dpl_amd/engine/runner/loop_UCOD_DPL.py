@@ -299,6 +299,7 @@ class TrainLoop(BaseLoop):
                                       "featureConv is not implemented (use dis_use_features=False, as every shipped config does)")
         self.lora_engine = engine
         self.lora_engine_ema = engine.clone_for_ema()
+        r.lora_engine, r.lora_engine_ema = self.lora_engine, self.lora_engine_ema      # the runner checkpoints and validates them (save_checkpoint, launch_val_look_twice)
         # stream budget of the forward phase: student in `engine.train_streams` image-parallel halves + the teacher on one more
         # stream (more than three concurrent passes lose to cache and CU contention: 602 vs 668 images/s with 2 + 2)
         self.lora_engine_ema.train_streams = int(os.environ.get("UCOD_TEACHER_STREAMS", "1"))

@@ -54,6 +54,7 @@ class StandardRunner:
         self.train_dataloader = train_dataloader if train_dataloader is not None else []
         self.val_dataloader = val_dataloader if val_dataloader is not None else []
         self._saved = {}
+        self.lora_engine = self.lora_engine_ema = self._val_backbone = None      # backbone-backward mode (TrainLoop.attach_lora_backbone sets the engines)
         self._build_model()
         self._build_optimizer()
 
@@ -98,6 +99,10 @@ class StandardRunner:
             path = os.path.join(self.config.log_cfg.log_path, "ckp", f"epoch{epoch}.pth")
             os.makedirs(path, exist_ok=True)
             save_file({k: v.detach().cpu().contiguous() for k, v in self.model.state_dict().items()}, os.path.join(path, "model.safetensors"))
+            if self.lora_engine is not None:                   # backbone-backward mode: the trained LoRA matrices, student and EMA copy, as peft adapter folders
+                from ...models.modules.full_model import save_lora_adapter
+                save_lora_adapter(self.lora_engine, os.path.join(path, "lora"))
+                save_lora_adapter(self.lora_engine_ema, os.path.join(path, "lora_ema"))
 
     def load_checkpoint(self, checkpoint_path):
         from safetensors.torch import load_file
@@ -111,9 +116,30 @@ class StandardRunner:
         self.trainloop = TrainLoop(self.config, self)
         self.trainloop.run()
 
-    def launch_val_look_twice(self):
+    def val_feature_extractor(self, lora_backbone="student"):
+        """Backbone-backward mode: the frozen ``backbone`` of the unmodified config (built once) carrying the CURRENT LoRA matrices of the student
+        (``lora_backbone="ema"``: of the EMA copy) -- merged into its live engine in place (``ViTLoRAEngine.merge_into``); a split-precision config is rebuilt from
+        the merged state dict instead.  None without ``TrainLoop.attach_lora_backbone``: validation then builds the frozen backbone as ever."""
+        if lora_backbone not in ("student", "ema"):
+            raise ValueError(f"lora_backbone must be 'student' or 'ema', got {lora_backbone!r}")
+        if self.lora_engine is None:
+            return None
+        from ...data.utils.feature_extractor import backbone
+        from ...vit_engine import SplitViTEngine
+        eng = self.lora_engine if lora_backbone == "student" else self.lora_engine_ema
+        if self._val_backbone is None:
+            self._val_backbone = backbone(self.config.dataset_cfg.feature_extractor_cfg, device=self.device)
+        fe = self._val_backbone
+        if isinstance(fe.engine, SplitViTEngine):
+            _, heads, eps, device = fe._src
+            return backbone.from_state_dict(eng.merged_state_dict(), heads, eps=eps, device=device, precision=fe.precision)
+        eng.merge_into(fe.engine)
+        return fe
+
+    def launch_val_look_twice(self, lora_backbone="student"):
+        """``lora_backbone``: which LoRA backbone is validated in backbone-backward mode -- the student's by default (the reference validates the student decoder)."""
         from .loop_look_twice import ValLoop_Look_Twice
-        return ValLoop_Look_Twice(self.config, self).run()
+        return ValLoop_Look_Twice(self.config, self, feature_extractor=self.val_feature_extractor(lora_backbone)).run()
 
 
 class LocalRefineRunner(StandardRunner):

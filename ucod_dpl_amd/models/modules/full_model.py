@@ -8,7 +8,11 @@ LoRA r / lora_alpha / target modules as :47-72 (subsets of query, key, value, pl
 dropped -> NCHW -> bilinear 68x68 (:95-106), student backbone differentiable w.r.t. its LoRA matrices, EMA backbone
 frozen.  ``enable_ocm`` is rejected: its module does not exist in the reference.  LoRA dropout (``lora_dropout``, 0.05 in the
 reference config) is applied in train mode with counter-based masks (it cannot reproduce torch's RNG stream).
+
+The way out of LoRA mode is here too: ``merge_and_unload`` (peft's name: W <- W + (lora_alpha / r) B A, then an ordinary frozen ``backbone`` at any precision) and
+``save_lora_adapter`` / ``load_lora_adapter`` (peft's adapter folder: adapter_model.safetensors + adapter_config.json).
 """
+import json
 import os
 
 import torch
@@ -40,6 +44,55 @@ class LoRABackbone(nn.Module):
     def sync(self):
         """Re-derive the LoRA columns of the augmented GEMM weights after ``lora`` changed (optimiser step / EMA / load)."""
         self.engine.repack()
+
+    def merge_and_unload(self, precision=None, **engine_kw):
+        """peft's ``merge_and_unload()``: the trained matrices merged into the base weights (``ViTLoRAEngine.merged_state_dict``), returned as an ordinary frozen
+        ``data.utils.feature_extractor.backbone`` at ``precision`` (None: the fp16 folded default; "bf16"; "split3" / "f32eq" ...).  This module is left as it is."""
+        from ...data.utils.feature_extractor import backbone
+        eng = self.engine
+        return backbone.from_state_dict(eng.merged_state_dict(), eng.heads, eps=eng.eps, device=eng.device, precision=precision, **engine_kw)
+
+
+ADAPTER_PREFIX = "base_model.model.ViT.encoder.layer."      # peft's key prefix for the reference's wrapper (ViTLoraWrapper holds the HF model as ``ViT``)
+ADAPTER_WEIGHTS, ADAPTER_CONFIG = "adapter_model.safetensors", "adapter_config.json"
+
+
+def _adapter_targets(engine):
+    """target_modules of an engine as peft lists them: the leaf names"""
+    names = [n for n, on in zip(("query", "key", "value"), engine.targets) if on]
+    return names + ([engine.mlp_target] if engine.mlp_target is not None else [])
+
+
+def save_lora_adapter(engine, folder):
+    """Write the LoRA matrices of ``engine`` as a peft adapter folder: ``adapter_model.safetensors`` with the keys
+    ``base_model.model.ViT.encoder.layer.{i}.attention.attention.query.lora_A.weight`` ... (shapes: ``lora_state_dict()``'s; B of ``weights_in`` in HF row order,
+    unpadded) and ``adapter_config.json`` with r, lora_alpha, lora_dropout, bias "none" and target_modules (models/modules/full_model.py:47-72).
+    peft is not a dependency of this package: the layout is restated from peft's documented adapter format and has not been checked against the library."""
+    from safetensors.torch import save_file
+    os.makedirs(folder, exist_ok=True)
+    sd = engine.lora_state_dict(prefix=ADAPTER_PREFIX)
+    save_file({k: v.detach().cpu().contiguous() for k, v in sd.items()}, os.path.join(folder, ADAPTER_WEIGHTS))
+    alpha = float(engine.scaling) * int(engine.r)
+    cfg = {"peft_type": "LORA", "r": int(engine.r), "lora_alpha": int(alpha) if alpha == int(alpha) else alpha,
+           "lora_dropout": float(getattr(engine, "lora_dropout", 0.0)), "bias": "none", "target_modules": _adapter_targets(engine)}
+    with open(os.path.join(folder, ADAPTER_CONFIG), "w") as f:
+        json.dump(cfg, f, indent=2, sort_keys=True)
+    return folder
+
+
+def load_lora_adapter(engine, folder):
+    """The inverse of ``save_lora_adapter``: read the folder into ``engine``'s arena.  An adapter whose r, lora_alpha or target_modules differ from the engine's is
+    refused (both sides are named): its matrices would not fit, or would be applied with another scale."""
+    from safetensors.torch import load_file
+    with open(os.path.join(folder, ADAPTER_CONFIG)) as f:
+        cfg = json.load(f)
+    mine = {"r": int(engine.r), "lora_alpha": float(engine.scaling) * int(engine.r), "target_modules": sorted(_adapter_targets(engine))}
+    theirs = {"r": int(cfg["r"]), "lora_alpha": float(cfg["lora_alpha"]), "target_modules": sorted(cfg["target_modules"])}
+    for k in ("r", "target_modules", "lora_alpha"):
+        if mine[k] != theirs[k]:
+            raise ValueError(f"LoRA adapter {folder}: {k} is {theirs[k]!r} in {ADAPTER_CONFIG}, {mine[k]!r} in the engine")
+    engine.load_lora_state_dict(load_file(os.path.join(folder, ADAPTER_WEIGHTS)), prefix=ADAPTER_PREFIX)
+    return engine
 
 
 def load_lora(config, state_dict, heads, device="cuda", generator=None):
@@ -114,6 +167,10 @@ class full_model(nn.Module):
 
     def load_state_dict(self, state_dict, strict=True):
         return self.decoder.load_state_dict(state_dict, strict=strict)
+
+    def merge_and_unload(self, ema=False, precision=None):
+        """The student's (``ema``: the EMA copy's) backbone with its LoRA matrices merged, as a frozen ``backbone`` at ``precision`` (LoRABackbone.merge_and_unload)."""
+        return (self.backbone_ema if ema else self.backbone).merge_and_unload(precision=precision)
 
 
 def get_full_model(cfg, backbone_state_dict, heads, checkpoint_path=None, device="cuda"):

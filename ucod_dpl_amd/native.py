@@ -169,6 +169,9 @@ SIGNATURES = {
     "ucod_vit_backward_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes_lora_mlp": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp)]),
     "ucod_vit_forward_lora_infer_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # merging trained LoRA matrices into ordinary weights, and the device form of the LayerNorm fold (fp16-operand build) for the merged weight
+    "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
+    "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     "ucod_gemm_bf16_train": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
     "ucod_layernorm_lora": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_lora_h16": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),

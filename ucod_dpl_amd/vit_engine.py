@@ -365,6 +365,7 @@ class ViTEngine(_BackboneEngine):
         self.patch_w, self.patch_b, self.cls = bf(pw), f32(c["patch_b"]), f32(c["cls"])
         self.layers = [layer_row(l, bf, f32) for l in c["layers"]]
         self.fold_layers = None
+        self.q_row_scale = None                                    # [3D] f32 on the device: the row scale the folded QKV entries were built with (merge_into refolds with it)
         if self.ln_fold:
             self.fold_layers = []
             for l, src in zip(self.layers, c["layers"]):
@@ -379,6 +380,7 @@ class ViTEngine(_BackboneEngine):
                 fl[N.QKV_W], fl[N.QKV_B], fl[N.QKV_COLSUM] = (t.to(dev) for t in self._fold(cpu(src["ln1_g"]), cpu(src["ln1_b"]), cpu(src["qkv_w"]), cpu(src["qkv_b"]), row_scale=qs))
                 fl[N.FC1_W], fl[N.FC1_B], fl[N.FC1_COLSUM] = (t.to(dev) for t in self._fold(cpu(src["ln2_g"]), cpu(src["ln2_b"]), cpu(src["fc1_w"]), cpu(src["fc1_b"])))
                 self.fold_layers.append(fl)
+            self.q_row_scale = qs.to(dev)                          # (attn_variant == 1 takes Q unscaled: all ones then)
 
     def _fold(self, gamma, beta, w, b, row_scale=None):
         """LayerNorm(gamma, beta) followed by Linear(w, b) [* row_scale per output] as one GEMM on the un-normalised rows (include/ucod_dpl.h:
@@ -706,6 +708,8 @@ class ViTLoRAEngine(ViTEngine):
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on."""
         canon = normalize_state_dict(state_dict)
+        self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
+        self._merge_buf = self._mlp_src_rows = None
         mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
         self.targets, self.mlp_target = lora_targets(target_modules, mlp_kind, len(canon["layers"]))
         self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
@@ -977,6 +981,127 @@ class ViTLoRAEngine(ViTEngine):
         self._saved_for = None
         return self.lora_grad
 
+    # ---- merging: the way out of LoRA mode ---------------------------------------------------------------------------
+    def _targeted(self):
+        """(module name below ``encoder.layer.{i}.``, its index among query / key / value or None for the MLP input projection) of every targeted module"""
+        mods = [(f"attention.attention.{name}", p) for p, name in enumerate(_QKV) if self.targets[p]]
+        return mods + ([(f"mlp.{self.mlp_target}", None)] if self.mlp_target is not None else [])
+
+    @staticmethod
+    def _hf_prefix(sd):
+        for pref in ("", "dinov2.", "vit."):
+            if pref + "encoder.layer.0.attention.attention.query.weight" in sd:
+                return pref
+        raise NotImplementedError("merging takes a HuggingFace DINOv2 state dict (encoder.layer.{i}.attention.attention.{query,key,value}): the names "
+                                  "target_modules are matched against")
+
+    def _stage(self, numel):
+        """The reusable f32 staging buffer, at least ``numel`` elements."""
+        if self._merge_buf is None or self._merge_buf.numel() < numel:
+            self._merge_buf = torch.empty(numel, dtype=torch.float32, device=self.device)
+        return self._merge_buf
+
+    def _merge(self, lib, w0, A, B, out):
+        n, k = w0.shape
+        N.check(lib.ucod_lora_merge_f32(N.ptr(w0), A.data_ptr(), N.ptr(B), self.r, self.scaling, N.ptr(out), n, k, N.stream()), "ucod_lora_merge_f32")
+
+    def merged_state_dict(self, base_state_dict=None):
+        """peft's ``merge_and_unload()`` as a state dict: a copy of the HF-named base state dict (default: the one this engine was built from) in which ``weight``
+        of every targeted module is the merged f32 matrix  W + (lora_alpha / r) B A  (ucod_lora_merge_f32: f64 arithmetic, one rounding to f32); every other entry
+        is the same tensor.  Any frozen-backbone engine built from it runs the adapted model.  Merging is the eval-mode function: dropout plays no part.  A SwiGLU
+        checkpoint's ``weights_in`` is merged in HF row order, unpadded.  One module at a time through a reusable device buffer: stage, merge, copy back."""
+        base = self._base_sd if base_state_dict is None else base_state_dict
+        pref = self._hf_prefix(base)
+        out = dict(base)
+        swiglu = self.mlp == N.UCOD_MLP_SWIGLU
+        for i in range(self.L):
+            for name, p in self._targeted():
+                key = f"{pref}encoder.layer.{i}.{name}.weight"
+                w = base[key]
+                n, k = w.shape
+                if k != self.D:
+                    raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine has D = {self.D}")
+                if p is not None:
+                    sa, sb = self._slices(p)
+                    B = self.lora[i, sb]
+                else:
+                    sa, sb = self._mlp_slices()
+                    B = self.lora[i, sb].reshape(self.N1, self.r)
+                    B = lora_b_from_engine(B, self._F0) if swiglu else B
+                if B.numel() != n * self.r:
+                    raise ValueError(f"{key} has {n} rows, the LoRA B matrix of this engine {B.numel() // self.r}")
+                buf = self._stage(2 * n * k)
+                w0, merged = buf[:n * k].view(n, k), buf[n * k:2 * n * k].view(n, k)
+                w0.copy_(w.detach())
+                self._merge(self.lib, w0, self.lora[i, sa], B, merged)
+                out[key] = merged.to(w.device, copy=True)
+        return out
+
+    def _engine_row_source(self):
+        """SwiGLU: for every row of the engine's padded, interleaved weights_in the HF row it holds, or 2 F0 (a zero row behind the staged HF weight) for padding."""
+        if self._mlp_src_rows is None:
+            from .swiglu import interleave_perm
+            F, F0 = self.F, self._F0
+            j = interleave_perm(F)
+            src = torch.where(j < F, j, j - F + F0)
+            src = torch.where((j % F) < F0, src, torch.full_like(src, 2 * F0))
+            self._mlp_src_rows = src.to(self.device)
+        return self._mlp_src_rows
+
+    def merge_into(self, engine):
+        """Refresh a live ``ViTEngine`` of the same checkpoint IN PLACE with this engine's current LoRA matrices: for every targeted module of every layer the merged
+        f32 weight (from the f32 base weights, never from ``engine``'s current ones: refreshing after every optimiser step cannot drift) goes to a staging buffer and is
+        cast into the existing 16-bit tensor of ``engine.layers``; with ``engine.ln_fold`` it is also folded (ucod_fold_ln_linear) into the existing tensors of
+        ``engine.fold_layers``, with the Q-row pre-scale the engine was built with (``engine.q_row_scale``).  No tensor of ``engine`` is reallocated, untargeted tensors
+        (and the rows of untargeted projections in the fused QKV weight) are not written.  Runs on the current stream, ordered with ``engine``'s passes there."""
+        if isinstance(engine, SplitViTEngine):
+            raise NotImplementedError("merge_into refreshes the 16-bit ViTEngine only; build a SplitViTEngine from merged_state_dict() (its operands are split "
+                                      "per tensor with their own scales)")
+        if not isinstance(engine, ViTEngine) or isinstance(engine, ViTLoRAEngine):
+            raise TypeError(f"merge_into takes a frozen-backbone ViTEngine, got {type(engine).__name__}")
+        mine, theirs = (self.D, self.L, self.F, self.heads, self.mlp), (engine.D, engine.L, engine.F, engine.heads, engine.mlp)
+        if mine != theirs:
+            raise ValueError(f"merge_into: the engines differ in (D, L, F, heads, MLP kind): {mine} here, {theirs} there")
+        if engine.patch_w.device != self.lora.device:
+            raise ValueError(f"merge_into: this engine is on {self.lora.device}, the other on {engine.patch_w.device}")
+        base, lib, D, r = self._base_sd, engine.lib, self.D, self.r
+        pref = self._hf_prefix(base)
+        swiglu = self.mlp == N.UCOD_MLP_SWIGLU
+        st = N.stream
+        for i in range(self.L):
+            row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
+            for name, p in self._targeted():
+                w = base[f"{pref}encoder.layer.{i}.{name}.weight"]
+                if p is not None:
+                    n, r0, (sa, sb) = D, p * D, self._slices(p)
+                    slot_w, slot_b, slot_c, g, be = N.QKV_W, N.QKV_B, N.QKV_COLSUM, row[N.LN1_G], row[N.LN1_B]
+                else:
+                    n, r0, (sa, sb) = self.N1, 0, self._mlp_slices()
+                    slot_w, slot_b, slot_c, g, be = N.FC1_W, N.FC1_B, N.FC1_COLSUM, row[N.LN2_G], row[N.LN2_B]
+                if p is None and swiglu:                         # stage HF rows (+ one zero row), gather them into the engine's row order
+                    n_hf = 2 * self._F0
+                    buf = self._stage((n_hf + 1 + 2 * n) * D)
+                    hf, rest = buf[:(n_hf + 1) * D].view(n_hf + 1, D), buf[(n_hf + 1) * D:]
+                    hf[:n_hf].copy_(w.detach())
+                    hf[n_hf].zero_()
+                    w0, merged = rest[:n * D].view(n, D), rest[n * D:2 * n * D].view(n, D)
+                    torch.index_select(hf, 0, self._engine_row_source(), out=w0)
+                else:
+                    if tuple(w.shape) != (n, D):
+                        raise ValueError(f"encoder.layer.{i}.{name}.weight has shape {tuple(w.shape)}, expected {(n, D)}")
+                    buf = self._stage(2 * n * D)
+                    w0, merged = buf[:n * D].view(n, D), buf[n * D:2 * n * D].view(n, D)
+                    w0.copy_(w.detach())
+                self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
+                plain = row[slot_w]
+                N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), plain.data_ptr() + r0 * D * plain.element_size(), n * D, st()), "ucod_cast_f32_bf16")
+                if fl is not None:
+                    wf, bf, cs = fl[slot_w], fl[slot_b], fl[slot_c]
+                    q = engine.q_row_scale.data_ptr() + r0 * 4 if p is not None else None
+                    N.check(lib.ucod_fold_ln_linear(N.ptr(merged), N.ptr(g), N.ptr(be), row[slot_b].data_ptr() + r0 * 4, q, wf.data_ptr() + r0 * D * wf.element_size(),
+                                                    bf.data_ptr() + r0 * 4, cs.data_ptr() + r0 * 4, n, D, st()), "ucod_fold_ln_linear")
+        return engine
+
     # ---- torch.autograd / nn.Module integration ----------------------------------------------------------------------
     def clone_for_ema(self):
         """A second engine over the SAME frozen weight tensors with its own LoRA arena (models/modules/full_model.py:84:
@@ -989,6 +1114,7 @@ class ViTLoRAEngine(ViTEngine):
         other.train_layers = [[t.clone() if s in (N.T_QKV_W_AUG, N.T_QKV_WT_AUG) else t for s, t in enumerate(tl)] for tl in self.train_layers]
         other.mlp_layers = [[t.clone() for t in ml] for ml in self.mlp_layers]          # (the augmented fc1 weight carries the clone's own B_m)
         other._tside, other._saved_for = None, None
+        other._merge_buf = None                                    # (its own staging buffer; the f32 base weights ``_base_sd`` are shared)
         other._guard = _SaturationGuard(self.lib, self.device)
         other._pos_cache = dict(self._pos_cache)
         # The reference's teacher is a deepcopy that stays in train mode (full_model.py:84; nobody calls eval() on it), so its LoRA
