@@ -49,6 +49,9 @@ extern "C" {
  * ucod_attention_split_fwd, ucod_vit_forward_split (+ their size helpers); ucod_clock_probe; the measurement knobs left the product build (UCOD_LAB_KNOBS). */
 /* (still 5) backbone-backward mode on the SwiGLU MLP: epilogues 21 / 22 of ucod_gemm_bf16_train and the _mlp forms of the five training-pass entry points
  * (ucod_vit_train_workspace_bytes_mlp ... ucod_vit_forward_lora_infer_mlp); additions only, nothing existing changed. */
+/* (still 5) DINOv2 with registers: ucod_vit_desc gained a trailing n_reg (0 = every caller that zero-fills the descriptor, as the ctypes binding does: the passes
+ * are then launch for launch and bit for bit what they were) and the *_reg forms of the row-mapped GEMM drains, the leading-row kernels, the key-gradient scatter and
+ * the CLS attention row were added.  ucod_vit_train_desc embeds the descriptor, so its LoRA fields moved by one int; callers build both from this header. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -144,6 +147,15 @@ enum {
 int ucod_gemm_bf16(int epilogue, const void* A_bf16, const void* B_bf16, void* out, int M, int N, int K,
                    const float* bias, const float* scale, const float* resid, const float* pos,
                    int tokens_per_image, int variant, void* stream);
+/* The two row-mapped drains for a checkpoint with register tokens (DINOv2 with registers, modeling_dinov2_with_registers.py): an image's tokens are
+ * [CLS | n_reg registers | n patches], tokens_per_image = 1 + n_reg + n counts all of them (n_reg is NEVER packed into it).
+ *   UCOD_EPI_PATCH_TOKENS_F32 / _H16: GEMM row b n + p -> token row b tok + 1 + n_reg + p, + pos row 1 + p (`pos` has 1 + n rows: registers have none); the
+ *     CLS and register rows of `out` are not touched (ucod_cls_rows_reg writes them);
+ *   UCOD_EPI_KEY_NCHW_F32: token column t of an image -> key-map column t - 1 - n_reg; CLS and register columns are dropped; out f32 [B, C, n].
+ * Every output bound is formed from n.  Any other epilogue is parameterised by rows alone and is accepted with n_reg = 0 only, where this IS ucod_gemm_bf16. */
+int ucod_gemm_bf16_reg(int epilogue, const void* A_bf16, const void* B_bf16, void* out, int M, int N, int K,
+                       const float* bias, const float* scale, const float* resid, const float* pos,
+                       int tokens_per_image, int n_reg, int variant, void* stream);
 /* LayerNorm folded into its consumer GEMM (epilogues UCOD_EPI_LNFOLD_*; libucod_dpl_f16.so only -- an MFMA takes both operands in one type and
  * the A operand here is the IEEE fp16 residual stream itself; the bf16 build returns UCOD_EINVAL).  Replaces nn.LayerNorm + nn.Linear of
  * modeling_dinov2.py:348-381 (norm1 -> attention, norm2 -> mlp) and dino.py:127-131:
@@ -166,6 +178,11 @@ int ucod_gemm_bf16_stats(int epilogue, const void* A_bf16, const void* B_bf16, v
                          const void* resid_f16, const float* pos, int tokens_per_image, float* row_partials, int nslot, void* stream);
 /* ucod_cls_rows_h16 that also writes the CLS rows' partials, slot by slot like the other rows' (nslot = D / 64) */
 int ucod_cls_rows_h16_stats(void* x_f16, const float* cls, const float* pos, float* row_partials, int nslot, int B, int tok, int D, void* stream);
+/* the same with register tokens: UCOD_EPI_PATCH_TOKENS_H16_STATS as in ucod_gemm_bf16_reg (the residual producer takes n_reg = 0 only: it has no row map), and the
+ * leading rows -- CLS and the n_reg register rows of every image -- with their (S, M2) partials (cls_reg as in ucod_cls_rows_reg) */
+int ucod_gemm_bf16_stats_reg(int epilogue, const void* A_bf16, const void* B_bf16, void* out, int M, int N, int K, const float* bias, const float* scale,
+                             const void* resid_f16, const float* pos, int tokens_per_image, int n_reg, float* row_partials, int nslot, void* stream);
+int ucod_cls_rows_h16_stats_reg(void* x_f16, const float* cls_reg, const float* pos, float* row_partials, int nslot, int B, int tok, int D, int n_reg, void* stream);
 /* Row statistics of the fp16 residual stream for the folded epilogues: stats[m] = (rstd, -mean * rstd), two-pass in f32 over the row held in
  * registers, biased variance + eps like nn.LayerNorm.  x f16 [rows,D], D % 256 == 0, D <= 1536.
  * Range of the fold: x W'^T and mean * colsum cancel in f32, which costs ~2^-24 sqrt(K) |mean| / sigma of the output scale (0.2 fp16 ulp at 100 sigma).  Both
@@ -187,6 +204,7 @@ int ucod_resid16_overflow_bind(unsigned* device_counter);
 
 /* nn.LayerNorm over the last dim (modeling_dinov2.py:348,353,365,373,441; dino.py:127,131,184):
  * x f32 [rows,D] -> y bf16 [rows,D] (or f32 when out_f32 != 0).  D % 128 == 0. */
+/* (register tokens: a row kernel over `rows` = B tok rows; tok = 1 + n_reg + n needs nothing here) */
 int ucod_layernorm(const float* x, const float* gamma, const float* beta, void* y, int rows, int D, float eps,
                    int out_f32, void* stream);
 /* the same with the residual stream in IEEE fp16 (ucod_vit_desc.resid16): x f16 [rows,D] -> y bf16 [rows,D]; statistics in f32 */
@@ -200,6 +218,7 @@ int ucod_layernorm_h16(const void* x_f16, const float* gamma, const float* beta,
  * max, probabilities fed back as MFMA operands from registers, f32 row sums, 16-byte output stores; query rows and 32-key blocks past
  * the last token are not computed.  variant: 0 or 2 (the same kernels), 5 / 66 = attn_fwd_v5_kernel / attn_fwd_v6_kernel by name; every other number is a laboratory variant
  * (ucod_attention_fwd_lab of libucod_dpl_variants.so) and is refused.  tok * heads * 384 must fit 32 bits. */
+/* (register tokens: parameterised by `tok` alone -- registers are ordinary tokens of the sequence, tok = 1 + n_reg + n; unchanged) */
 int ucod_attention_fwd(const void* qkv_bf16, void* out_bf16, int B, int tok, int heads, float scale, int variant,
                        void* stream);
 
@@ -217,6 +236,7 @@ size_t ucod_attention_fp8_workspace_bytes(int B, int tok, int heads);
  * half the QKV output bytes.  ucod_attention_fp8_zero_pad clears the rows tokens..Npad-1 of all three tensors (once per workspace:
  * nothing writes them afterwards; a NaN byte there would survive the multiplication by a zero probability). */
 int ucod_attention_fp8_zero_pad(void* q8k8v8, int B, int tok, int heads, void* stream);
+/* (register tokens: parameterised by `tok` alone; unchanged) */
 int ucod_attention_fwd_fp8_fused(const void* q8k8v8, void* out_bf16, int B, int tok, int heads, int q_exp, int k_exp, int v_exp, void* stream);
 int ucod_attention_fwd_fp8(const void* qkv_bf16, void* out_bf16, void* workspace, size_t workspace_bytes, int B, int tok, int heads,
                            int q_exp, int k_exp, int v_exp, void* stream);
@@ -228,6 +248,11 @@ int ucod_patch_im2col(const float* img, void* patches_bf16, int B, int C, int H,
 /* x f32 [B*tok, D]: row b*tok = cls + pos[0]  (modeling_dinov2.py:107-112; dino.py:227-232) */
 int ucod_cls_rows(float* x, const float* cls, const float* pos, int B, int tok, int D, void* stream);
 int ucod_cls_rows_h16(void* x_f16, const float* cls, const float* pos, int B, int tok, int D, void* stream);
+/* the leading rows of an image with register tokens (Dinov2WithRegistersEmbeddings.forward): row b*tok = cls_reg[0] + pos[0], rows b*tok + 1 .. + n_reg =
+ * cls_reg[1 .. n_reg] as they are (a register token has no position row).  cls_reg f32 [(1 + n_reg), D]: the CLS row followed by the register rows (table slot +2);
+ * tok = 1 + n_reg + n.  n_reg = 0 is ucod_cls_rows / ucod_cls_rows_h16. */
+int ucod_cls_rows_reg(float* x, const float* cls_reg, const float* pos, int B, int tok, int D, int n_reg, void* stream);
+int ucod_cls_rows_h16_reg(void* x_f16, const float* cls_reg, const float* pos, int B, int tok, int D, int n_reg, void* stream);
 
 /* v[0..D) = c, v[D..3D) = 1: the per-column factor of the fused QKV epilogue */
 int ucod_fill_qscale(float* v, int D, float c, void* stream);
@@ -297,6 +322,7 @@ int ucod_layernorm_bwd_lora_ex(const void* dy, const void* x, int flags, const f
 
 /* Attention forward that also returns the base-2 log-sum-exp of the scaled scores, lse f32 [B, heads, tok]
  * (Q must carry head_dim^-0.5 * log2(e), as for ucod_attention_fwd with scale == 0). */
+/* (register tokens: ucod_attention_fwd_lse / ucod_attention_bwd take `tok` = 1 + n_reg + n like any other token count; unchanged) */
 int ucod_attention_fwd_lse(const void* qkv_bf16, void* out_bf16, float* lse, int B, int tok, int heads, void* stream);
 
 /* Attention backward (eager_attention_forward of modeling_dinov2.py:153-179 differentiated): qkv as in the forward
@@ -308,6 +334,9 @@ int ucod_attention_bwd(const void* qkv_bf16, const void* out_bf16, const void* d
 /* dkey f32 [B, D, tok-1] (cotangent of the key hook) -> rows of dqkv_aug bf16 [B*tok, 3D+64]: k third = dkey^T (CLS row 0),
  * q and v thirds and the aug columns zero. */
 int ucod_key_grad_tokens(const float* dkey, void* dqkv_aug_bf16, int B, int tok, int D, void* stream);
+/* the same for tok = 1 + n_reg + n tokens per image: dkey f32 [B, D, n] goes to the K third of token rows 1 + n_reg .. tok - 1; the CLS row and the n_reg register
+ * rows, which the key hook drops, get zeros there like the q / v thirds */
+int ucod_key_grad_tokens_reg(const float* dkey, void* dqkv_aug_bf16, int B, int tok, int D, int n_reg, void* stream);
 
 /* Fill the aug columns of Wqkv_aug bf16 [3D, D+64] (alpha/r * B_q|B_k|B_v on the block diagonal) and of WqkvT_aug bf16
  * [D, 3D+64] (A_q^T|A_k^T|A_v^T; zeros when zero_a_columns != 0, the dropout case) from one layer's LoRA parameters.  Either
@@ -318,6 +347,7 @@ int ucod_lora_pack(const float* lora_layer, int r, float scaling, void* w_aug_bf
 /* One layer's LoRA gradients from dqkv_aug [rows, 3D+64] and h_aug [rows, D+64]; also writes t = alpha/r * dqkv B into the
  * aug columns of dqkv_aug (consumed by the dgrad GEMM).  grad_layer has the parameter layout; accumulate != 0 adds. */
 size_t ucod_lora_grad_workspace_bytes(int D);
+/* (register tokens: the LoRA row kernels -- ucod_layernorm_lora*, ucod_lora_grad, ucod_layernorm_bwd*, the _lora_mlp forms -- work on M = B tok rows; unchanged) */
 int ucod_lora_grad(void* dqkv_aug_bf16, const void* h_aug_bf16, const float* lora_layer, int r, float scaling, float* grad_layer,
                    int accumulate, void* workspace, size_t workspace_bytes, int rows, int D, const ucod_lora_dropout* dropout, void* stream);
 
@@ -357,6 +387,11 @@ typedef struct {
   int ln_fold;            /* 1 (libucod_dpl_f16.so with resid16 = 1 only): LayerNorm 1 / 2 of every layer but the last are folded into the QKV / fc1
                              GEMMs (ucod_gemm_lnfold): the fp16 stream is the A operand, no LayerNorm output is written or rounded.  The table then
                              carries folded weights (see the table layout).  0: LayerNorm kernels. */
+  int n_reg;              /* register tokens of the checkpoint (DINOv2 with registers: 4; 0 otherwise).  Every whole-pass driver (ucod_vit_forward*, _split*, _split16*,
+                             _forward_train* / _backward* / _forward_lora_infer*) then runs tok = 1 + n_reg + n tokens per image, [CLS | registers | patches]: table slot +2
+                             is f32 [(1 + n_reg), D] (the CLS row, then the register rows; fp16-term pass: times S_patch like CLS / pos), slot +3 stays [1 + n, D];
+                             workspace sizes, ucod_vit_last_ln1_offset* and the stream offsets count tok rows; key_out stays [B, D, H/P, W/P] (patch tokens only).
+                             0: launch for launch and bit for bit the pass without the field. */
 } ucod_vit_desc;
 size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d);
 int ucod_vit_forward(const ucod_vit_desc* d, const void* const* table_host, const float* img, float* key_out,
@@ -755,6 +790,11 @@ int ucod_pil_resize_u8_host(const uint8_t* src_host, int h, int w, uint8_t* dst_
 size_t ucod_vit_last_ln1_offset(const ucod_vit_desc* d);
 int ucod_cls_qk(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_cls, int B, int tok, int D, void* stream);
 int ucod_cls_attention(const float* q_cls, const float* k_cls, const float* key_map, float* att, int B, int heads, int hw, float scale, void* stream);
+/* With register tokens (tok = 1 + n_reg + hw): ucod_cls_qk_reg also projects the keys of tokens 1 .. n_reg into k_lead f32 [B, 1 + n_reg, D] (row 0 = the CLS key);
+ * ucod_cls_attention_reg = outputs.attentions[-1][:, :, 0, 1 + n_reg:] -- the softmax runs over all tok keys (the n_reg + 1 of k_lead in its maximum and
+ * denominator, the patch keys from the key map), the patch columns are returned, so a row sums to less than 1 by the CLS and register weights. */
+int ucod_cls_qk_reg(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_lead, int B, int tok, int D, int n_reg, void* stream);
+int ucod_cls_attention_reg(const float* q_cls, const float* k_lead, const float* key_map, float* att, int B, int heads, int hw, int n_reg, float scale, void* stream);
 int ucod_bkg_seg(const float* att, const float* key_map, float th_bkg, float epsilon, int apply_weights, float* bkg_mask, float* sim_map,
                  float* cos_row, int* seed, float* beta, void* scratch4, int B, int heads, int hw, void* stream);
 

@@ -16,9 +16,9 @@ lib = N.load()
 drop = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0   # the reference trains with lora_dropout 0.05 (configs/model/UCOD_DPL.py)
 resid = sys.argv[5] if len(sys.argv) > 5 else "auto"      # residual stream of the training pass: auto (fp16 with bf16 operands) / f32
 arch = sys.argv[6] if len(sys.argv) > 6 else "dinov2_vitb14"
-if arch not in ("dinov2_vitb14", "dinov2_vitg14"):
-    sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14, got {arch}")
-giant = arch == "dinov2_vitg14"
+if arch not in ("dinov2_vitb14", "dinov2_vitg14", "dinov2_vitb14_reg", "dinov2_vitg14_reg"):        # (_reg: DINOv2 with registers, 4 register tokens per image)
+    sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14 (or their _reg forms), got {arch}")
+giant = arch.startswith("dinov2_vitg14")
 heads = 24 if giant else 12
 targets = sys.argv[7].split(",") if len(sys.argv) > 7 and sys.argv[7] else None
 kw = {} if targets is None else dict(target_modules=targets)

@@ -450,11 +450,12 @@ static int launch(GemmArgs a, int variant, hipStream_t s) {
   }
   if constexpr (kRowMapped<EPI>) {                               // the 256-wide kernel drains these with 32-bit buffer offsets and 16-byte stores
     if (variant == 9) {
-      const int tok = a.tok > 1 ? a.tok : 2;
-      const unsigned long out_bytes = EPI == UCOD_EPI_KEY_NCHW_F32 ? (unsigned long)(a.N / tok) * a.M * (tok - 1) * 4ul
-                                                                   : (unsigned long)(a.M / (tok - 1)) * tok * a.N * (EPI == UCOD_EPI_PATCH_TOKENS_H16 ? 2ul : 4ul);
-      const bool whole = EPI == UCOD_EPI_KEY_NCHW_F32 ? (a.N % tok) == 0 : (a.M % (tok - 1)) == 0;   // whole images (the drains size the output from them)
-      const bool ok = a.tok > 1 && whole && out_bytes < 0x7FFFFFF0ul && (unsigned long)a.tok * a.N * 4ul < 0x7FFFFFF0ul &&
+      const int tok = a.tok > 1 + a.nreg ? a.tok : 2 + a.nreg;
+      const int np = tok - 1 - a.nreg;                            // patch tokens per image: what every output bound is formed from (never tok - 1)
+      const unsigned long out_bytes = EPI == UCOD_EPI_KEY_NCHW_F32 ? (unsigned long)(a.N / tok) * a.M * np * 4ul
+                                                                   : (unsigned long)(a.M / np) * tok * a.N * (EPI == UCOD_EPI_PATCH_TOKENS_H16 ? 2ul : 4ul);
+      const bool whole = EPI == UCOD_EPI_KEY_NCHW_F32 ? (a.N % tok) == 0 : (a.M % np) == 0;   // whole images (the drains size the output from them)
+      const bool ok = a.tok > 1 + a.nreg && whole && out_bytes < 0x7FFFFFF0ul && (unsigned long)a.tok * a.N * 4ul < 0x7FFFFFF0ul &&
                       (EPI != UCOD_EPI_PATCH_TOKENS_H16 || (a.N & 7) == 0);
       if (!ok) variant = 10;                                      // (192-wide tiles keep the chunk-by-chunk drain)
     }
@@ -563,8 +564,8 @@ static int launch_resid_h16(ucod::GemmArgs a, hipStream_t s) {
 // plain epilogue and ucod_row_stats_h16.
 static int launch_patch_h16_stats(ucod::GemmArgs a, hipStream_t s) {
   using namespace ucod;
-  if (!a.bias || !a.pos || a.tok < 2 || !a.part_out || (a.N & 63) != 0 || a.nslot != a.N / 64 || a.K < 128 || a.M < 2048) return UCOD_EINVAL;
-  const int np = a.tok - 1;
+  if (!a.bias || !a.pos || a.tok < 2 + a.nreg || !a.part_out || (a.N & 63) != 0 || a.nslot != a.N / 64 || a.K < 128 || a.M < 2048) return UCOD_EINVAL;
+  const int np = a.tok - 1 - a.nreg;
   const unsigned long out_bytes = (unsigned long)(a.M / np) * a.tok * a.N * 2ul;
   if ((a.M % np) != 0 || out_bytes >= 0x7FFFFFF0ul || (unsigned long)a.tok * a.N * 4ul >= 0x7FFFFFF0ul ||
       (unsigned long)(a.M / np) * a.tok * a.nslot * 8ul >= 0x7FFFFFF0ul) return UCOD_EINVAL;
@@ -582,9 +583,10 @@ static int launch_patch_h16_stats(ucod::GemmArgs a, hipStream_t s) {
 static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias,
                       const float* scale, const float* resid, const float* pos, int tokens_per_image, int variant,
                       void* stream, const void* aux, void* out2, const float* stats = nullptr, const float* colsum = nullptr,
-                      const float* part_in = nullptr, float* part_out = nullptr, int nslot = 0, float eps = 0.f, float act_alpha = 1.f, float act_scale = 1.f) {
+                      const float* part_in = nullptr, float* part_out = nullptr, int nslot = 0, float eps = 0.f, float act_alpha = 1.f, float act_scale = 1.f,
+                      int n_reg = 0) {
   using namespace ucod;
-  if (!A || !B || !out || M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0) return UCOD_EINVAL;
+  if (!A || !B || !out || M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || n_reg < 0) return UCOD_EINVAL;
   GemmArgs a;
   a.act_alpha = act_alpha;
   a.act_scale = act_scale;
@@ -615,6 +617,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.N = N;
   a.K = K;
   a.tok = tokens_per_image;
+  a.nreg = n_reg;
   a.tiles_m = cdiv(M, BM);
   a.tiles_n = cdiv(N, BN);
   a.main_tiles = 0;
@@ -671,10 +674,10 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       if (!bias || !scale || !resid) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_SCALE_RESID_F32>(a, variant, s);
     case UCOD_EPI_PATCH_TOKENS_F32:
-      if (!bias || !pos || tokens_per_image < 2) return UCOD_EINVAL;
+      if (!bias || !pos || tokens_per_image < 2 + n_reg) return UCOD_EINVAL;
       return launch<UCOD_EPI_PATCH_TOKENS_F32>(a, variant, s);
     case UCOD_EPI_KEY_NCHW_F32:
-      if (!bias || tokens_per_image < 2) return UCOD_EINVAL;
+      if (!bias || tokens_per_image < 2 + n_reg) return UCOD_EINVAL;
       return launch<UCOD_EPI_KEY_NCHW_F32>(a, variant, s);
     case UCOD_EPI_BIAS_F32:
       if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
@@ -702,7 +705,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       if (M >= 2048 && K >= 128 && (N & 7) == 0 && (long)M * K * 2 < (1L << 32) && (long)N * K * 2 < (1L << 32)) return launch_resid_h16(a, s);
       return launch<UCOD_EPI_BIAS_SCALE_RESID_H16>(a, variant == 0 || variant == 1 || variant == 2 || variant == 12 ? variant : 0, s);
     case UCOD_EPI_PATCH_TOKENS_H16:
-      if (!bias || !pos || tokens_per_image < 2 || !a.ovf) return UCOD_EINVAL;
+      if (!bias || !pos || tokens_per_image < 2 + n_reg || !a.ovf) return UCOD_EINVAL;
       return launch<UCOD_EPI_PATCH_TOKENS_H16>(a, variant, s);
     default: return UCOD_EINVAL;
   }
@@ -717,6 +720,18 @@ extern "C" int ucod_gemm_bf16(int epilogue, const void* A, const void* B, void* 
   if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;   // need ucod_gemm_bf16_stats
   if (epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) return UCOD_EINVAL;   // need ucod_split16_gemm_act
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream, nullptr, nullptr);
+}
+
+// ucod_gemm_bf16 for the two row-mapped drains of a checkpoint with register tokens (DINOv2 with registers): an image's tokens are [CLS | n_reg registers |
+// patches], tokens_per_image counts all of them, and the patch embedding / key hook skip 1 + n_reg rows per image instead of 1.  Every other epilogue is
+// parameterised by rows alone and takes n_reg = 0 only.
+extern "C" int ucod_gemm_bf16_reg(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias, const float* scale,
+                                  const float* resid, const float* pos, int tokens_per_image, int n_reg, int variant, void* stream) {
+  const bool row_mapped = epilogue == UCOD_EPI_PATCH_TOKENS_F32 || epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_KEY_NCHW_F32;
+  if (n_reg < 0 || (n_reg > 0 && !row_mapped)) return UCOD_EINVAL;
+  if (!row_mapped) return ucod_gemm_bf16(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream);
+  return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f,
+                    1.f, 1.f, n_reg);
 }
 
 extern "C" int ucod_gemm_bf16_train(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias,
@@ -748,6 +763,15 @@ extern "C" int ucod_gemm_bf16_stats(int epilogue, const void* A, const void* B, 
   if (!row_partials || nslot <= 0) return UCOD_EINVAL;
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, (const float*)resid, pos, tokens_per_image, 0, stream, nullptr, nullptr, nullptr, nullptr,
                     nullptr, row_partials, nslot, 0.f);
+}
+
+// ucod_gemm_bf16_stats with register tokens (UCOD_EPI_PATCH_TOKENS_H16_STATS skips 1 + n_reg rows per image; the residual producer takes n_reg = 0 only)
+extern "C" int ucod_gemm_bf16_stats_reg(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias, const float* scale,
+                                        const void* resid, const float* pos, int tokens_per_image, int n_reg, float* row_partials, int nslot, void* stream) {
+  if (epilogue != UCOD_EPI_BIAS_SCALE_RESID_H16_STATS && epilogue != UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;
+  if (!row_partials || nslot <= 0 || n_reg < 0 || (n_reg > 0 && epilogue != UCOD_EPI_PATCH_TOKENS_H16_STATS)) return UCOD_EINVAL;
+  return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, (const float*)resid, pos, tokens_per_image, 0, stream, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, row_partials, nslot, 0.f, 1.f, 1.f, n_reg);
 }
 
 // The GEMM behind ucod_split16_gemm_act (split16.hip validates op, alpha and scale): the fp16-term split epilogues on this file's kernels.

@@ -151,7 +151,8 @@ struct GemmArgs {
   int nslot;            // partial slots per row of part_in / part_out
   float eps;            // LayerNorm eps (part_in)
   int M, N, K;
-  int tok;   // tokens per image incl. CLS (PATCH / KEY epilogues)
+  int tok;   // tokens per image incl. CLS and register tokens (PATCH / KEY epilogues)
+  int nreg;  // register tokens per image between CLS and the first patch token (DINOv2 with registers; 0 otherwise): patches are tokens 1 + nreg .. tok - 1
   int tiles_m, tiles_n;
   int main_tiles;      // large-tile kernel, leftover-as-patches mode (see patch_phase): workgroups launched = whole tiles computed; 0 = off
   int patches_per_wg;  // 16 x 32 patches of the remaining tiles each workgroup computes on the side
@@ -296,26 +297,26 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, int m, int n, 
     const size_t i = (size_t)m * a.N + n;
     reinterpret_cast<float*>(a.out)[i] = a.resid[i] + a.scale[n] * (v + a.bias[n]);
   } else if constexpr (EPI == UCOD_EPI_PATCH_TOKENS_F32) {
-    // row m = b*(tok-1)+p  ->  token row b*tok + 1 + p ; + bias + position embedding of token 1+p
-    const int np = a.tok - 1;
+    // row m = b*n_patch+p  ->  token row b*tok + 1 + nreg + p ; + bias + position row 1+p (register tokens have no position row)
+    const int np = a.tok - 1 - a.nreg;
     const int b = m / np, p = m - b * np;
-    reinterpret_cast<float*>(a.out)[((size_t)b * a.tok + 1 + p) * a.N + n] = v + a.bias[n] + a.pos[(size_t)(1 + p) * a.N + n];
+    reinterpret_cast<float*>(a.out)[((size_t)b * a.tok + 1 + a.nreg + p) * a.N + n] = v + a.bias[n] + a.pos[(size_t)(1 + p) * a.N + n];
   } else if constexpr (kPatchH16<EPI>) {
-    const int np = a.tok - 1;
+    const int np = a.tok - 1 - a.nreg;
     const int b = m / np, p = m - b * np;
     const float o = v + a.bias[n] + a.pos[(size_t)(1 + p) * a.N + n];
     if (beyond_f16(o)) atomicAdd(a.ovf, 1u);
-    reinterpret_cast<unsigned short*>(a.out)[((size_t)b * a.tok + 1 + p) * a.N + n] = __builtin_bit_cast(unsigned short, (_Float16)clamp_f16(o));
+    reinterpret_cast<unsigned short*>(a.out)[((size_t)b * a.tok + 1 + a.nreg + p) * a.N + n] = __builtin_bit_cast(unsigned short, (_Float16)clamp_f16(o));
   } else if constexpr (kResidH16<EPI>) {
     const size_t i = (size_t)m * a.N + n;
     const float o = (float)reinterpret_cast<const _Float16*>(a.resid)[i] + a.scale[n] * (v + a.bias[n]);
     if (beyond_f16(o)) atomicAdd(a.ovf, 1u);
     reinterpret_cast<unsigned short*>(a.out)[i] = __builtin_bit_cast(unsigned short, (_Float16)clamp_f16(o));
   } else if constexpr (EPI == UCOD_EPI_KEY_NCHW_F32) {
-    // m = channel, n = global token index; drop CLS, write [B, C, tok-1]
+    // m = channel, n = global token index; drop CLS and the register tokens, write [B, C, n_patch]
     const int b = n / a.tok, t = n - b * a.tok;
-    if (t == 0) return;
-    reinterpret_cast<float*>(a.out)[((size_t)b * a.M + m) * (a.tok - 1) + (t - 1)] = v + a.bias[m];
+    if (t <= a.nreg) return;
+    reinterpret_cast<float*>(a.out)[((size_t)b * a.M + m) * (a.tok - 1 - a.nreg) + (t - 1 - a.nreg)] = v + a.bias[m];
   } else if constexpr (EPI == UCOD_EPI_BIAS_F32) {
     reinterpret_cast<float*>(a.out)[(size_t)m * a.N + n] = v + a.bias[n];
   }
@@ -327,13 +328,13 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& a, int m, int n,
   static_assert(!kSwiglu<EPI> && !kSplit16<EPI>, "SwiGLU and fp16-term split epilogues drain 8-column chunks only");
   if (m >= a.M || n >= a.N) return;
   if constexpr (EPI == UCOD_EPI_KEY_NCHW_F32) {
-    // four consecutive tokens of one image, none of them CLS: one dword-aligned 16-byte store into [B, C, tok-1] (row starts are
-    // only 4-byte aligned there: tok-1 is odd); groups that touch a CLS token or straddle two images go token by token
+    // four consecutive tokens of one image, none of them CLS or a register: one dword-aligned 16-byte store into [B, C, n_patch] (row starts are
+    // only 4-byte aligned there: n_patch may be odd); groups that touch a CLS / register token or straddle two images go token by token
     const int b = n / a.tok, t = n - b * a.tok;
-    if (t >= 1 && t + 3 < a.tok && n + 3 < a.N) {
+    if (t > a.nreg && t + 3 < a.tok && n + 3 < a.N) {
       typedef f32x4 f32x4_u __attribute__((aligned(4)));
       const float bm = a.bias[m];
-      *reinterpret_cast<f32x4_u*>(reinterpret_cast<float*>(a.out) + ((size_t)b * a.M + m) * (a.tok - 1) + (t - 1)) = v + (f32x4){bm, bm, bm, bm};
+      *reinterpret_cast<f32x4_u*>(reinterpret_cast<float*>(a.out) + ((size_t)b * a.M + m) * (a.tok - 1 - a.nreg) + (t - 1 - a.nreg)) = v + (f32x4){bm, bm, bm, bm};
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) epilogue_store<EPI>(a, m, n + e, v[e]);
@@ -388,7 +389,7 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& a, int m, int n,
       w[1] = pack_f16x2(clamp_f16(o[2]), clamp_f16(o[3]));
       *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(a.out) + i) = w;
     } else if constexpr (EPI == UCOD_EPI_PATCH_TOKENS_F32 || kPatchH16<EPI>) {
-      const int np = a.tok - 1;
+      const int np = a.tok - 1 - a.nreg;
       const int bi = m / np, p = m - bi * np;
       const f32x4 ps = *reinterpret_cast<const f32x4*>(a.pos + (size_t)(1 + p) * a.N + n);
       const f32x4 o = v + b + ps;
@@ -397,9 +398,9 @@ __device__ __forceinline__ void epilogue_store4(const GemmArgs& a, int m, int n,
         u32x2 w;
         w[0] = pack_f16x2(clamp_f16(o[0]), clamp_f16(o[1]));
         w[1] = pack_f16x2(clamp_f16(o[2]), clamp_f16(o[3]));
-        *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(a.out) + ((size_t)bi * a.tok + 1 + p) * a.N + n) = w;
+        *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(a.out) + ((size_t)bi * a.tok + 1 + a.nreg + p) * a.N + n) = w;
       } else {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + ((size_t)bi * a.tok + 1 + p) * a.N + n) = o;
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + ((size_t)bi * a.tok + 1 + a.nreg + p) * a.N + n) = o;
       }
     } else {
       *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + (size_t)m * a.N + n) = v + b;
@@ -751,7 +752,7 @@ __device__ __forceinline__ void finish_col_consts(const GemmArgs& a, float (&cb)
 
 // acc: the wave's 128 x 16*NT tile (8 row-tiles x NT column-tiles, C layout col = lane&15, row = (lane>>4)*4 + reg), bias
 // already inside for the fused epilogues; cs = per-column scale.  wbase: wave-private 32 x WCOLS f32 staging area.  Four passes of 32 rows.
-// kRowMapped: the key hook (rows = channels, columns = tokens written as [B, C, tok-1]) and the patch embedding (rows remapped past the CLS
+// kRowMapped: the key hook (rows = channels, columns = tokens written as [B, C, tok-1-nreg]) and the patch embedding (rows remapped past the CLS and register
 // rows, + position embedding).  With 64-column waves the large-tile kernel drains them with the offset scheme of the fused epilogues
 // (FASTRM: what a pass needs from memory -- the per-channel bias rows of the key hook, the position rows of the patch embedding -- is
 // requested before the pass is staged, so no load sits between two stores; round 3: their chunk-by-chunk drain had a bias / position load
@@ -775,12 +776,12 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
   static_assert(NI == 8 || kColFused<EPI>, "odd row-tile counts only in the column-fused epilogues");
   auto rows_in = [&](int pass) { return (NI - 2 * pass) >= 2 ? 32 : 16; };
   if constexpr (FASTRM && EPI == UCOD_EPI_KEY_NCHW_F32) {
-    // out f32 [B, C = M, tok-1]; the lane's four tokens (columns) are the same for every row, so its byte offset is one register plus a
-    // wave-uniform row term.  Four consecutive tokens of one image, none of them CLS: one 16-byte store (rows start 4-byte aligned only:
-    // tok-1 is odd); chunks that hold a CLS token or straddle two images go element by element, in a branch the whole wave takes or skips.
+    // out f32 [B, C = M, n_patch], n_patch = tok - 1 - nreg; the lane's four tokens (columns) are the same for every row, so its byte offset is one register plus a
+    // wave-uniform row term.  Four consecutive tokens of one image, none of them CLS or a register token: one 16-byte store (rows start 4-byte aligned
+    // only: n_patch may be odd); chunks that hold a CLS / register token or straddle two images go element by element, in a branch the whole wave takes or skips.
     static_assert(WCOLS == 64 && NI == 8, "64-column waves");
     constexpr unsigned DROP = 0x80000000u;
-    const int tok = a.tok, np1 = tok - 1;
+    const int tok = a.tok, nreg = a.nreg, np1 = tok - 1 - nreg;   // (np1: patch tokens per image; every bound below is formed from it)
     const unsigned total = (unsigned)(a.N / tok) * (unsigned)a.M * (unsigned)np1 * 4u;         // (launch(): < 2^31)
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out), 0, total, 0x00020000);
     const unsigned row_bytes = (unsigned)np1 * 4u;
@@ -788,13 +789,13 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     const int lrow = m_first + (lane >> 4);
     const unsigned lane_row = (unsigned)lrow * row_bytes;
     const int b = n / tok, t = n - b * tok;
-    const bool clean = n + 3 < a.N && t >= 1 && t + 3 < tok;
-    const unsigned off_w = clean ? ((unsigned)b * (unsigned)a.M * (unsigned)np1 + (unsigned)(t - 1)) * 4u + lane_row : DROP;
+    const bool clean = n + 3 < a.N && t > nreg && t + 3 < tok;
+    const unsigned off_w = clean ? ((unsigned)b * (unsigned)a.M * (unsigned)np1 + (unsigned)(t - 1 - nreg)) * 4u + lane_row : DROP;
     unsigned off_e[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int ne = n + e, be = ne / tok, te = ne - be * tok;
-      off_e[e] = (!clean && ne < a.N && te != 0) ? ((unsigned)be * (unsigned)a.M * (unsigned)np1 + (unsigned)(te - 1)) * 4u + lane_row : DROP;
+      off_e[e] = (!clean && ne < a.N && te > nreg) ? ((unsigned)be * (unsigned)a.M * (unsigned)np1 + (unsigned)(te - 1 - nreg)) * 4u + lane_row : DROP;
     }
     const bool ragged = __any(!clean && n < a.N);                 // (wave-uniform)
 #pragma unroll
@@ -825,7 +826,8 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
   } else if constexpr (FASTRM && (EPI == UCOD_EPI_PATCH_TOKENS_F32 || kPatchH16<EPI>)) {
-    // row m = image * (tok-1) + p  ->  token row image * tok + 1 + p = m + image + 1, + position embedding of token 1 + p.  The position
+    // row m = image * n_patch + p  ->  token row image * tok + 1 + nreg + p = m + (image + 1) * (1 + nreg), + position row 1 + p (the position table has
+    // 1 + n_patch rows: register tokens have none).  The position
     // rows of a pass are requested before its accumulators are staged; nothing else is loaded, so the wait in front of a pass's stores is
     // the only one (it also retires the previous pass's stores: four round trips per tile instead of one per store).
     static_assert(WCOLS == 64 && NI == 8, "64-column waves");
@@ -833,10 +835,10 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
     constexpr unsigned DROP = 0x80000000u;
     constexpr int EW = H16 ? 8 : 4;                               // columns per lane and store
     constexpr int CH = WCOLS / EW, RPI = 64 / CH, ITS = PR / RPI; // chunks per row, rows per wave instruction, instructions per pass
-    const int np = a.tok - 1;
+    const int np = a.tok - 1 - a.nreg, skip = 1 + a.nreg;         // patch tokens per image; CLS + register rows in front of an image's patches
     const unsigned out_bytes = (unsigned)(a.M / np) * (unsigned)a.tok * (unsigned)a.N * (H16 ? 2u : 4u);   // (launch(): < 2^31)
     const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out), 0, out_bytes, 0x00020000);
-    const auto rs_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.pos)), 0, (unsigned)a.tok * (unsigned)a.N * 4u, 0x00020000);
+    const auto rs_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.pos)), 0, (unsigned)(np + 1) * (unsigned)a.N * 4u, 0x00020000);
     const auto rs_q = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(kStats<EPI> ? (void*)a.part_out : a.out), 0,
                                                         kStats<EPI> ? (unsigned)(a.M / np) * (unsigned)a.tok * (unsigned)a.nslot * 8u : 0u, 0x00020000);
     const int n = n_first + (lane % CH) * EW;
@@ -859,8 +861,8 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
         const int m = lrow + pass * PR + it * RPI;
         const int bi = m / np, p = m - bi * np;
         const bool ok = col_ok && m < a.M;
-        o_off[it] = ok ? ((unsigned)(m + bi + 1) * (unsigned)a.N + (unsigned)n) * (H16 ? 2u : 4u) : DROP;
-        if constexpr (kStats<EPI>) q_off[it] = (ok && (lane % CH) == 0) ? ((unsigned)(m + bi + 1) * (unsigned)a.nslot + (unsigned)(n_first >> 6)) * 8u : DROP;
+        o_off[it] = ok ? ((unsigned)(m + (bi + 1) * skip) * (unsigned)a.N + (unsigned)n) * (H16 ? 2u : 4u) : DROP;
+        if constexpr (kStats<EPI>) q_off[it] = (ok && (lane % CH) == 0) ? ((unsigned)(m + (bi + 1) * skip) * (unsigned)a.nslot + (unsigned)(n_first >> 6)) * 8u : DROP;
         const unsigned p_off = ok ? ((unsigned)(1 + p) * (unsigned)a.N + (unsigned)n) * 4u : DROP;
         pv[it][0] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, p_off, 0, 0);
         if constexpr (H16) pv[it][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, p_off + 16u, 0, 0);

@@ -42,29 +42,31 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return s;
 }
 
-// one block per image; wave per output row of [Wq ; Wk]
+// grid (B, 1 + nreg): one block per image and leading token r (0 = CLS, 1 .. nreg = register tokens); wave per output row of [Wq ; Wk].  The CLS block writes
+// q [B, D] and row 0 of k [B, 1 + nreg, D]; a register token's block its key row only (rows D .. 2D-1 of the weight: its query is never read)
 __global__ __launch_bounds__(256) void cls_qk_kernel(const bf16_raw* __restrict__ h, const bf16_raw* __restrict__ w, const float* __restrict__ bias,
                                                      float* __restrict__ q, float* __restrict__ k, int tok, int D) {
-  extern __shared__ float x[];                               // LN1(x_cls) as f32
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const bf16_raw* hr = h + (size_t)b * tok * D;
+  extern __shared__ float x[];                               // LN1(x_r) as f32
+  const int b = blockIdx.x, r = blockIdx.y, lead = gridDim.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const bf16_raw* hr = h + ((size_t)b * tok + r) * D;
   for (int i = threadIdx.x; i < D; i += 256) x[i] = h_to_f32(hr[i]);
   __syncthreads();
-  for (int n = wv; n < 2 * D; n += 4) {
+  for (int n = (r == 0 ? 0 : D) + wv; n < 2 * D; n += 4) {
     const bf16_raw* wr = w + (size_t)n * D;
     float s = 0.f;
     for (int i = lane; i < D; i += 64) s += h_to_f32(wr[i]) * x[i];
     s = wave_sum(s) + bias[n];
     if (lane == 0) {
       if (n < D) q[(size_t)b * D + n] = s;
-      else k[(size_t)b * D + n - D] = s;
+      else k[((size_t)b * lead + r) * D + n - D] = s;
     }
   }
 }
 
-// grid (B, heads); att[b][h][j] for patches j (CLS column dropped after the softmax)
+// grid (B, heads); att[b][h][j] for patches j (the CLS column and the `lead - 1` register-token columns dropped after the softmax, whose maximum and
+// denominator include them: kc f32 [B, lead, D] holds their keys, CLS first)
 __global__ __launch_bounds__(256) void cls_attention_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ key,
-                                                            float* __restrict__ att, int heads, int hw, float scale) {
+                                                            float* __restrict__ att, int heads, int hw, float scale, int lead) {
   extern __shared__ float sc[];                              // hw scores, then 8 floats of reduction space
   float* red = sc + hw;
   const int b = blockIdx.x, hd = blockIdx.y, D = heads * 64;
@@ -79,17 +81,21 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const float* __restr
     sc[j] = s;
     mx = fmaxf(mx, s);
   }
-  float s_cls = 0.f;
-  for (int d = 0; d < 64; ++d) s_cls += qh[d] * kc[(size_t)b * D + hd * 64 + d];
-  s_cls *= scale;
-  mx = fmaxf(block_max(mx, red), s_cls);
+  mx = block_max(mx, red);
+  auto lead_score = [&](int r) {                             // (wave-uniform, recomputed for the denominator: `lead` is 1 or a handful)
+    float s = 0.f;
+    for (int d = 0; d < 64; ++d) s += qh[d] * kc[((size_t)b * lead + r) * D + hd * 64 + d];
+    return s * scale;
+  };
+  for (int r = 0; r < lead; ++r) mx = fmaxf(mx, lead_score(r));
   float sum = 0.f;
   for (int j = threadIdx.x; j < hw; j += 256) {
     const float e = __expf(sc[j] - mx);
     sc[j] = e;
     sum += e;
   }
-  sum = block_sum(sum, red) + __expf(s_cls - mx);
+  sum = block_sum(sum, red);
+  for (int r = 0; r < lead; ++r) sum += __expf(lead_score(r) - mx);
   const float inv = 1.0f / sum;
   float* out = att + ((size_t)b * heads + hd) * hw;
   for (int j = threadIdx.x; j < hw; j += 256) out[j] = sc[j] * inv;
@@ -184,22 +190,30 @@ __global__ __launch_bounds__(256) void bkg_finalize_kernel(const float* __restri
 
 using namespace ucod;
 
-extern "C" int ucod_cls_qk(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_cls, int B, int tok, int D,
-                           void* stream) {
-  if (!h_ln1_bf16 || !qkv_w_bf16 || !qkv_b || !q_cls || !k_cls || B <= 0 || tok <= 0 || D <= 0) return UCOD_EINVAL;
-  hipLaunchKernelGGL(cls_qk_kernel, dim3(B), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, (const bf16_raw*)h_ln1_bf16,
-                     (const bf16_raw*)qkv_w_bf16, qkv_b, q_cls, k_cls, tok, D);
+extern "C" int ucod_cls_qk_reg(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_lead, int B, int tok, int D, int n_reg,
+                               void* stream) {
+  if (!h_ln1_bf16 || !qkv_w_bf16 || !qkv_b || !q_cls || !k_lead || B <= 0 || tok <= 0 || D <= 0 || n_reg < 0 || n_reg >= tok || n_reg > 1023) return UCOD_EINVAL;
+  hipLaunchKernelGGL(cls_qk_kernel, dim3(B, 1 + n_reg), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, (const bf16_raw*)h_ln1_bf16,
+                     (const bf16_raw*)qkv_w_bf16, qkv_b, q_cls, k_lead, tok, D);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
+extern "C" int ucod_cls_qk(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_cls, int B, int tok, int D,
+                           void* stream) {
+  return ucod_cls_qk_reg(h_ln1_bf16, qkv_w_bf16, qkv_b, q_cls, k_cls, B, tok, D, 0, stream);
+}
 
-extern "C" int ucod_cls_attention(const float* q_cls, const float* k_cls, const float* key_map, float* att, int B, int heads, int hw, float scale,
-                                  void* stream) {
-  if (!q_cls || !k_cls || !key_map || !att || B <= 0 || heads <= 0 || hw <= 0 || hw > 12000) return UCOD_EINVAL;
-  hipLaunchKernelGGL(cls_attention_kernel, dim3(B, heads), dim3(256), (size_t)(hw + 8) * sizeof(float), (hipStream_t)stream, q_cls, k_cls, key_map, att,
-                     heads, hw, scale);
+extern "C" int ucod_cls_attention_reg(const float* q_cls, const float* k_lead, const float* key_map, float* att, int B, int heads, int hw, int n_reg, float scale,
+                                      void* stream) {
+  if (!q_cls || !k_lead || !key_map || !att || B <= 0 || heads <= 0 || hw <= 0 || hw > 12000 || n_reg < 0 || n_reg > 1023) return UCOD_EINVAL;
+  hipLaunchKernelGGL(cls_attention_kernel, dim3(B, heads), dim3(256), (size_t)(hw + 8) * sizeof(float), (hipStream_t)stream, q_cls, k_lead, key_map, att,
+                     heads, hw, scale, 1 + n_reg);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+extern "C" int ucod_cls_attention(const float* q_cls, const float* k_cls, const float* key_map, float* att, int B, int heads, int hw, float scale,
+                                  void* stream) {
+  return ucod_cls_attention_reg(q_cls, k_cls, key_map, att, B, heads, hw, 0, scale, stream);
 }
 
 extern "C" int ucod_bkg_seg(const float* att, const float* key_map, float th_bkg, float epsilon, int apply_weights, float* bkg_mask, float* sim_map,

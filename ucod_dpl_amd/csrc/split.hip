@@ -669,7 +669,7 @@ inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 SplitPlan split_plan(const ucod_vit_desc* d, int terms, int mlp) {
   SplitPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1;
+  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
   p.M = d->B * p.tok;
   p.P = products_of(terms);
   size_t o = 0;
@@ -689,7 +689,7 @@ SplitPlan split_plan(const ucod_vit_desc* d, int terms, int mlp) {
 bool split_valid(const ucod_vit_desc* d, int terms, int mlp) {
   return d && terms_ok(terms) && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->D <= 1536 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         d->full_last_layer == 0 && (long)d->B * d->heads <= 65535;
+         d->full_last_layer == 0 && (long)d->B * d->heads <= 65535 && d->n_reg >= 0 && d->n_reg <= 1023;
 }
 }  // namespace
 
@@ -722,10 +722,10 @@ extern "C" int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int
   float* f1 = (float*)(ws + p.off_f1);
   void* g = ws + p.off_g;
   void* patches = ws + p.off_patch;
-  const int M = p.M, tok = p.tok, D = d->D, F = d->F, P = p.P, gv = d->gemm_variant;
+  const int M = p.M, tok = p.tok, D = d->D, F = d->F, P = p.P, gv = d->gemm_variant, R = d->n_reg, np = tok - 1 - R;
   RUN(ucod_patch_im2col_split(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, terms, stream));
-  RUN(ucod_gemm_bf16(UCOD_EPI_PATCH_TOKENS_F32, patches, T[0], x, d->B * (tok - 1), D, P * d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, gv, stream));
-  RUN(ucod_cls_rows(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
+  RUN(ucod_gemm_bf16_reg(UCOD_EPI_PATCH_TOKENS_F32, patches, T[0], x, d->B * np, D, P * d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, R, gv, stream));
+  RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, R, stream));
   for (int l = 0; l < d->L; ++l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
     const bool last = (l == d->L - 1);
@@ -733,7 +733,7 @@ extern "C" int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int
     if (last) {
       // key hook (feature_extractor.py:42,46-47,55-58): rows = channels (A = the K rows of the split QKV weight, A side), columns = tokens (B side)
       if (!W[14]) return UCOD_EINVAL;
-      RUN(ucod_gemm_bf16(UCOD_EPI_KEY_NCHW_F32, W[14], h, key_out, D, M, P * D, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, W[14], h, key_out, D, M, P * D, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, R, gv, stream));
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[2], qkv, M, 3 * D, P * D, (const float*)W[3], nullptr, nullptr, nullptr, tok, gv, stream));

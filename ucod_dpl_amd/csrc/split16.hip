@@ -654,7 +654,7 @@ inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 Plan16 plan16(const ucod_vit_desc* d, int mlp, int flags) {
   Plan16 p;
   const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1;
+  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
   p.M = d->B * p.tok;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = up256(o + bytes); return r; };
@@ -674,7 +674,7 @@ Plan16 plan16(const ucod_vit_desc* d, int mlp, int flags) {
 bool valid16(const ucod_vit_desc* d, int mlp, int flags) {
   return d && (flags & ~UCOD_SPLIT16_FUSE_MLP) == 0 && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->heads > 0 &&
          d->D == d->heads * 64 && s16::ln_width_ok(d->D) && d->F > 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         d->full_last_layer == 0 && (long)d->B * d->heads <= 65535;
+         d->full_last_layer == 0 && (long)d->B * d->heads <= 65535 && d->n_reg >= 0 && d->n_reg <= 1023;
 }
 }  // namespace
 
@@ -713,13 +713,14 @@ extern "C" int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int 
   float* f1 = (float*)(ws + p.off_f1);
   void* g = ws + p.off_g;
   void* patches = ws + p.off_patch;
-  const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant;
+  const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, R = d->n_reg, np = tok - 1 - R;
   const float sLN = s16::kScale[UCOD_SPLIT16_LN], sQKV = s16::kScale[UCOD_SPLIT16_QKV], sATT = s16::kScale[UCOD_SPLIT16_ATT], sHID = s16::kScale[UCOD_SPLIT16_HIDDEN],
               sPATCH = s16::kScale[UCOD_SPLIT16_PATCH];
+  // (the register rows of slot +2 carry S_patch like the CLS row: one in-place pass removes it from every token row)
   // the table's biases / position rows / CLS row / LayerScale vectors carry the operand scales of their GEMM (file header); the driver removes what is left
   RUN(ucod_split16_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, sPATCH, stream));
-  RUN(ucod_gemm_bf16(UCOD_EPI_PATCH_TOKENS_F32, patches, T[0], x, d->B * (tok - 1), D, 3 * d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, gv, stream));
-  RUN(ucod_cls_rows(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
+  RUN(ucod_gemm_bf16_reg(UCOD_EPI_PATCH_TOKENS_F32, patches, T[0], x, d->B * np, D, 3 * d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, R, gv, stream));
+  RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, R, stream));
   RUN(ucod_split16_scale_f32(x, (size_t)M * D, 1.0f / (sPATCH * wscale[0]), stream));
   for (int l = 0; l < d->L; ++l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
@@ -729,8 +730,8 @@ extern "C" int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int 
     if (last) {
       // key hook (feature_extractor.py:42,46-47,55-58): rows = channels (A = the K rows of the split QKV weight, A side), columns = tokens (B side)
       if (!W[14]) return UCOD_EINVAL;
-      RUN(ucod_gemm_bf16(UCOD_EPI_KEY_NCHW_F32, W[14], h, key_out, D, M, 3 * D, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, gv, stream));
-      RUN(ucod_split16_scale_f32(key_out, (size_t)d->B * D * (tok - 1), 1.0f / (sLN * ws_l[0]), stream));
+      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, W[14], h, key_out, D, M, 3 * D, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, R, gv, stream));
+      RUN(ucod_split16_scale_f32(key_out, (size_t)d->B * D * np, 1.0f / (sLN * ws_l[0]), stream));
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[2], qkv, M, 3 * D, 3 * D, (const float*)W[3], nullptr, nullptr, nullptr, tok, gv, stream));

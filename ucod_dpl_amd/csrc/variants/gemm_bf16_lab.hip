@@ -912,6 +912,7 @@ extern "C" int ucod_gemm_bf16_lab(int epilogue, const void* A, const void* B, vo
   a.N = N;
   a.K = K;
   a.tok = tokens_per_image;
+  a.nreg = 0;
   a.tiles_m = cdiv(M, BM);
   a.tiles_n = cdiv(N, BN);
   a.main_tiles = 0;

@@ -25,7 +25,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 Plan make_plan(const ucod_vit_desc* d) {
   Plan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1;
+  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches] (n_reg = 0: every checkpoint but DINOv2 with registers)
   p.M = d->B * p.tok;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
@@ -54,7 +54,7 @@ inline bool attn_variant_takes_prescaled_q(int av) { return av != 1; }
 bool valid(const ucod_vit_desc* d, int mlp = UCOD_MLP_GELU) {
   return d && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 &&
          d->heads > 0 && d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 &&
-         d->Kpad >= d->C * d->P * d->P && (d->resid16 == 0 || d->resid16 == 1) && attn_variant_known(d->attn_variant) &&
+         d->Kpad >= d->C * d->P * d->P && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) && attn_variant_known(d->attn_variant) &&
          (d->ln_fold == 0 || (d->ln_fold == 1 && d->resid16 == 1 && d->attn_variant != 8 && UCOD_HALF_IS_F16 && d->D % 256 == 0 && d->D <= 1536));
 }
 
@@ -87,6 +87,7 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
   void* g = ws + p.off_g;
   void* patches = ws + p.off_patch;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, av = d->attn_variant;
+  const int R = d->n_reg, np = tok - 1 - R;                           // register tokens, patch tokens per image
   const float scale = 0.125f;  // head_dim^-0.5, head_dim = 64
   // attn_variant 0 / 2: fold head_dim^-0.5 * log2(e) into the Q third of the QKV epilogue (before its 16-bit rounding)
   // attn_variant 8: the fp8 (e4m3, block-scaled MFMA) attention path of BASELINE configs[4]; same pre-scaled Q
@@ -121,21 +122,21 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
   RUN(ucod_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, stream));
   // (the patch embedding's *_STATS form runs without the leftover-as-patches mode: worth it only when its 256 x 256 tiles come out as nearly whole
   // rounds of the chip; at 32 x 1369 rows -- 516 tiles on 256 CUs -- the plain launch plus one statistics launch is 11 us faster)
-  const int patch_tiles = ucod::cdiv((long)d->B * (tok - 1), 256) * ucod::cdiv(D, 256), n_cu = ucod::device_cus();
+  const int patch_tiles = ucod::cdiv((long)d->B * np, 256) * ucod::cdiv(D, 256), n_cu = ucod::device_cus();
   const bool patch_whole_rounds = patch_tiles >= n_cu && (patch_tiles % n_cu == 0 || patch_tiles % n_cu >= n_cu / 2);
   if (d->ln_fold && d->L > 1 && !no_part && patch_whole_rounds) {
-    const int rc = ucod_gemm_bf16_stats(UCOD_EPI_PATCH_TOKENS_H16_STATS, patches, T[0], x, d->B * (tok - 1), D, d->Kpad, (const float*)T[1], nullptr, nullptr,
-                                        (const float*)T[3], tok, part, nslot, stream);
+    const int rc = ucod_gemm_bf16_stats_reg(UCOD_EPI_PATCH_TOKENS_H16_STATS, patches, T[0], x, d->B * np, D, d->Kpad, (const float*)T[1], nullptr, nullptr,
+                                            (const float*)T[3], tok, R, part, nslot, stream);
     if (rc == UCOD_OK) have_part = true;
     else if (rc != UCOD_EINVAL) return rc;
   }
   if (have_part) {
-    RUN(ucod_cls_rows_h16_stats(x, (const float*)T[2], (const float*)T[3], part, nslot, d->B, tok, D, stream));
+    RUN(ucod_cls_rows_h16_stats_reg(x, (const float*)T[2], (const float*)T[3], part, nslot, d->B, tok, D, R, stream));
   } else {
-    RUN(ucod_gemm_bf16(epi_patch, patches, T[0], x, d->B * (tok - 1), D, d->Kpad, (const float*)T[1], nullptr, nullptr,
-                       (const float*)T[3], tok, gv, stream));
-    if (r16) RUN(ucod_cls_rows_h16(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
-    else RUN(ucod_cls_rows(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
+    RUN(ucod_gemm_bf16_reg(epi_patch, patches, T[0], x, d->B * np, D, d->Kpad, (const float*)T[1], nullptr, nullptr,
+                           (const float*)T[3], tok, R, gv, stream));
+    if (r16) RUN(ucod_cls_rows_h16_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, R, stream));
+    else RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, R, stream));
   }
   // out-projection / fc2 (+ LayerScale + residual) into x; `want_part`: a folded consumer reads x next
   auto resid_gemm = [&](const void* act, const void* w, const float* b, const float* ls, int K, bool want_part) -> int {
@@ -161,7 +162,7 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
       // key hook: only the K slice (rows D..2D-1) of the fused qkv weight; output written as [B,D,h,w]
       const char* wk = (const char*)W[2] + (size_t)D * D * 2;
       const float* bk = (const float*)W[3] + D;
-      RUN(ucod_gemm_bf16(UCOD_EPI_KEY_NCHW_F32, wk, h, key_out, D, M, D, bk, nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, wk, h, key_out, D, M, D, bk, nullptr, nullptr, nullptr, tok, R, gv, stream));
       if (!d->full_last_layer) break;
     }
     if (av == 8) {

@@ -409,22 +409,31 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restric
   }
 }
 
+// The rows in front of an image's patch tokens: token 0 = cls + pos[0], tokens 1 .. nreg = the register tokens as they are (rows 1 .. nreg of the
+// [(1 + nreg), D] table `cls`; a register token has no position row: modeling_dinov2_with_registers.py, Dinov2WithRegistersEmbeddings.forward).
+// nreg = 0: the CLS row alone, as before.
+__device__ __forceinline__ float lead_row_value(const float* __restrict__ cls, const float* __restrict__ pos, int r, int j, int D) {
+  return r == 0 ? cls[j] + pos[j] : cls[(size_t)r * D + j];
+}
+
 __global__ void cls_rows_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos, int B,
-                                int tok, int D) {
+                                int tok, int D, int nreg) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * D) return;
-  const int b = i / D, j = i - b * D;
-  x[(size_t)b * tok * D + j] = cls[j] + pos[j];
+  const int lead = (1 + nreg) * D;
+  if (i >= B * lead) return;
+  const int b = i / lead, rj = i - b * lead, r = rj / D, j = rj - r * D;
+  x[((size_t)b * tok + r) * D + j] = lead_row_value(cls, pos, r, j, D);
 }
 
 __global__ void cls_rows_h16_kernel(unsigned short* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos, int B,
-                                    int tok, int D, unsigned* __restrict__ ovf) {
+                                    int tok, int D, int nreg, unsigned* __restrict__ ovf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * D) return;
-  const int b = i / D, j = i - b * D;
-  const float o = cls[j] + pos[j];
+  const int lead = (1 + nreg) * D;
+  if (i >= B * lead) return;
+  const int b = i / lead, rj = i - b * lead, r = rj / D, j = rj - r * D;
+  const float o = lead_row_value(cls, pos, r, j, D);
   if (beyond_f16(o)) atomicAdd(ovf, 1u);
-  x[(size_t)b * tok * D + j] = __builtin_bit_cast(unsigned short, (_Float16)clamp_f16(o));
+  x[((size_t)b * tok + r) * D + j] = __builtin_bit_cast(unsigned short, (_Float16)clamp_f16(o));
 }
 
 // CLS rows of the fp16 stream WITH their row partials for the LayerNorm-folded consumer (gemm_bf16_epilogue.h: kStats): one workgroup per image.  A wave's 64
@@ -432,17 +441,17 @@ __global__ void cls_rows_h16_kernel(unsigned short* __restrict__ x, const float*
 // format row_partial8 writes for the other rows (D % 64 == 0: the launcher checks).
 __global__ __launch_bounds__(256) void cls_rows_h16_stats_kernel(unsigned short* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
                                                                  float2* __restrict__ part, int nslot, int tok, int D, unsigned* __restrict__ ovf) {
-  const int b = blockIdx.x;
+  const int b = blockIdx.x, r = blockIdx.y;                       // image, leading row (0 = CLS, 1 .. nreg = register tokens)
   bool sat = false;
-  float2* row = part + (size_t)b * tok * nslot;
+  float2* row = part + ((size_t)b * tok + r) * nslot;
   for (int j = threadIdx.x; j < D; j += 256) {                    // (D % 64 == 0: whole waves)
-    const float o = cls[j] + pos[j];
+    const float o = lead_row_value(cls, pos, r, j, D);
     sat |= beyond_f16(o);
     const _Float16 h = (_Float16)clamp_f16(o);
-    x[(size_t)b * tok * D + j] = __builtin_bit_cast(unsigned short, h);
-    const float r = (float)h;
-    const float s = wave_sum(r);
-    const float d = r - s * (1.0f / 64.0f);
+    x[((size_t)b * tok + r) * D + j] = __builtin_bit_cast(unsigned short, h);
+    const float hv = (float)h;
+    const float s = wave_sum(hv);
+    const float d = hv - s * (1.0f / 64.0f);
     const float m2 = wave_sum(d * d);
     if ((threadIdx.x & 63) == 0) row[j >> 6] = make_float2(s, m2);
   }
@@ -571,21 +580,33 @@ extern "C" int ucod_row_stats_h16(const void* x, float* stats, int rows, int D, 
   return UCOD_OK;
 }
 
-extern "C" int ucod_cls_rows_h16(void* x, const float* cls, const float* pos, int B, int tok, int D, void* stream) {
-  if (!x || !cls || !pos || B <= 0 || tok <= 0 || D <= 0) return UCOD_EINVAL;
+// (tok > n_reg: the 1 + n_reg leading rows lie inside the image's tok rows; B * (1 + n_reg) * D below 2^31: the kernels index with int)
+static bool lead_rows_ok(int B, int tok, int D, int n_reg) {
+  return B > 0 && tok > 0 && D > 0 && n_reg >= 0 && n_reg < tok && (long)B * (1 + n_reg) * D < (1L << 31) && (1 + n_reg) <= 65535;
+}
+
+extern "C" int ucod_cls_rows_h16_reg(void* x, const float* cls_reg, const float* pos, int B, int tok, int D, int n_reg, void* stream) {
+  if (!x || !cls_reg || !pos || !lead_rows_ok(B, tok, D, n_reg)) return UCOD_EINVAL;
   UCOD_PROF(ucod::PROF_CLS, stream);
-  hipLaunchKernelGGL(ucod::cls_rows_h16_kernel, dim3(ucod::cdiv((long)B * D, 256)), dim3(256), 0, (hipStream_t)stream, (unsigned short*)x, cls, pos, B, tok, D, ucod::resid16_overflow_counter());
+  hipLaunchKernelGGL(ucod::cls_rows_h16_kernel, dim3(ucod::cdiv((long)B * (1 + n_reg) * D, 256)), dim3(256), 0, (hipStream_t)stream, (unsigned short*)x, cls_reg, pos, B, tok, D,
+                     n_reg, ucod::resid16_overflow_counter());
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
+extern "C" int ucod_cls_rows_h16(void* x, const float* cls, const float* pos, int B, int tok, int D, void* stream) {
+  return ucod_cls_rows_h16_reg(x, cls, pos, B, tok, D, 0, stream);
+}
 
-extern "C" int ucod_cls_rows_h16_stats(void* x, const float* cls, const float* pos, float* row_partials, int nslot, int B, int tok, int D, void* stream) {
-  if (!x || !cls || !pos || !row_partials || nslot <= 0 || nslot > 256 || B <= 0 || tok <= 0 || D <= 0 || (D % 64) != 0 || nslot != D / 64) return UCOD_EINVAL;
+extern "C" int ucod_cls_rows_h16_stats_reg(void* x, const float* cls_reg, const float* pos, float* row_partials, int nslot, int B, int tok, int D, int n_reg, void* stream) {
+  if (!x || !cls_reg || !pos || !row_partials || nslot <= 0 || nslot > 256 || !lead_rows_ok(B, tok, D, n_reg) || (D % 64) != 0 || nslot != D / 64) return UCOD_EINVAL;
   UCOD_PROF(ucod::PROF_CLS, stream);
-  hipLaunchKernelGGL(ucod::cls_rows_h16_stats_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (unsigned short*)x, cls, pos, (float2*)row_partials, nslot, tok, D,
+  hipLaunchKernelGGL(ucod::cls_rows_h16_stats_kernel, dim3(B, 1 + n_reg), dim3(256), 0, (hipStream_t)stream, (unsigned short*)x, cls_reg, pos, (float2*)row_partials, nslot, tok, D,
                      ucod::resid16_overflow_counter());
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+extern "C" int ucod_cls_rows_h16_stats(void* x, const float* cls, const float* pos, float* row_partials, int nslot, int B, int tok, int D, void* stream) {
+  return ucod_cls_rows_h16_stats_reg(x, cls, pos, row_partials, nslot, B, tok, D, 0, stream);
 }
 
 extern "C" int ucod_patch_im2col(const float* img, void* patches, int B, int C, int H, int W, int P, int Kpad, void* stream) {
@@ -606,12 +627,15 @@ extern "C" int ucod_patch_im2col(const float* img, void* patches, int B, int C, 
   return UCOD_OK;
 }
 
-extern "C" int ucod_cls_rows(float* x, const float* cls, const float* pos, int B, int tok, int D, void* stream) {
-  if (!x || !cls || !pos || B <= 0 || tok <= 0 || D <= 0) return UCOD_EINVAL;
+extern "C" int ucod_cls_rows_reg(float* x, const float* cls_reg, const float* pos, int B, int tok, int D, int n_reg, void* stream) {
+  if (!x || !cls_reg || !pos || !lead_rows_ok(B, tok, D, n_reg)) return UCOD_EINVAL;
   UCOD_PROF(ucod::PROF_CLS, stream);
-  hipLaunchKernelGGL(ucod::cls_rows_kernel, dim3(ucod::cdiv((long)B * D, 256)), dim3(256), 0, (hipStream_t)stream, x, cls, pos, B, tok, D);
+  hipLaunchKernelGGL(ucod::cls_rows_kernel, dim3(ucod::cdiv((long)B * (1 + n_reg) * D, 256)), dim3(256), 0, (hipStream_t)stream, x, cls_reg, pos, B, tok, D, n_reg);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+extern "C" int ucod_cls_rows(float* x, const float* cls, const float* pos, int B, int tok, int D, void* stream) {
+  return ucod_cls_rows_reg(x, cls, pos, B, tok, D, 0, stream);
 }
 
 extern "C" int ucod_cast_f32_bf16(const float* src, void* dst, size_t n, void* stream) {

@@ -392,14 +392,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Cotangent of the key hook, [B, D, h*w] f32 (CLS dropped, NCHW) -> token-major rows of dqkv_aug: the k third gets the
-// transposed values (CLS row 0), the q and v thirds are zero (the last layer's q / v never reach the loss).
-// Block = (image, 32 tokens); 32x32 LDS transposes over the channel axis.
+// transposed values (CLS row 0, and the nreg register-token rows behind it, which the key hook drops too), the q and v thirds are zero (the last
+// layer's q / v never reach the loss).  Block = (image, 32 tokens); 32x32 LDS transposes over the channel axis.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void key_grad_tokens_kernel(const float* __restrict__ dkey, bf16_raw* __restrict__ dqkv, int tok,
-                                                              int D) {
+                                                              int D, int nreg) {
   __shared__ float tile[32][33];
   const int b = blockIdx.y, t0 = blockIdx.x * 32;
-  const int hw = tok - 1, ld = 3 * D + AUG;
+  const int hw = tok - 1 - nreg, ld = 3 * D + AUG;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;        // 32 x 8
   bf16_raw* base = dqkv + (size_t)b * tok * ld;
   // zero q, v (and aug) of these rows
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(256) void key_grad_tokens_kernel(const float* __res
     for (int k = 0; k < 4; ++k) {
       const int c = c0 + ty + 8 * k, t = t0 + tx;                 // read: tokens contiguous
       float v = 0.f;
-      if (t >= 1 && t < tok) v = dkey[((size_t)b * D + c) * hw + (t - 1)];
+      if (t > nreg && t < tok) v = dkey[((size_t)b * D + c) * hw + (t - 1 - nreg)];
       tile[ty + 8 * k][tx] = v;
     }
     __syncthreads();
@@ -769,13 +769,16 @@ extern "C" int ucod_layernorm_bwd_lora_ex(const void* dy, const void* x, int fla
                        (const bf16_raw*)dqkv_aug + 3 * D, 3 * D + AUG, lora_layer, r, make_drop(dropout), (hipStream_t)stream);
 }
 
-extern "C" int ucod_key_grad_tokens(const float* dkey, void* dqkv_aug, int B, int tok, int D, void* stream) {
+extern "C" int ucod_key_grad_tokens_reg(const float* dkey, void* dqkv_aug, int B, int tok, int D, int n_reg, void* stream) {
   UCOD_BF16_ONLY();
-  if (!dkey || !dqkv_aug || B <= 0 || tok < 2 || D <= 0 || (D % 32) != 0) return UCOD_EINVAL;
+  if (!dkey || !dqkv_aug || B <= 0 || n_reg < 0 || tok < 2 + n_reg || D <= 0 || (D % 32) != 0 || B > 65535) return UCOD_EINVAL;
   UCOD_PROF(PROF_LORA, stream);
-  hipLaunchKernelGGL(key_grad_tokens_kernel, dim3(cdiv(tok, 32), B), dim3(256), 0, (hipStream_t)stream, dkey, (bf16_raw*)dqkv_aug, tok, D);
+  hipLaunchKernelGGL(key_grad_tokens_kernel, dim3(cdiv(tok, 32), B), dim3(256), 0, (hipStream_t)stream, dkey, (bf16_raw*)dqkv_aug, tok, D, n_reg);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+extern "C" int ucod_key_grad_tokens(const float* dkey, void* dqkv_aug, int B, int tok, int D, void* stream) {
+  return ucod_key_grad_tokens_reg(dkey, dqkv_aug, B, tok, D, 0, stream);
 }
 
 extern "C" int ucod_lora_pack(const float* lora_layer, int r, float scaling, void* w_aug, void* wt_aug, int D, int zero_a_columns, void* stream) {

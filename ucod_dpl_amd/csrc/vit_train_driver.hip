@@ -33,7 +33,7 @@ bool valid_qkv(const ucod_vit_train_desc* t) {
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
-         (d->resid16 == 0 || d->resid16 == 1);                   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
+         d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
 }
 
 inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU; }
@@ -48,7 +48,7 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;
   TPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1;
+  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
   p.M = d->B * p.tok;
   p.L = d->L;
   const size_t M = p.M, D = d->D, F = d->F, L = d->L;
@@ -124,10 +124,10 @@ extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int
   const int epi_resid = r16 ? UCOD_EPI_BIAS_SCALE_RESID_H16 : UCOD_EPI_BIAS_SCALE_RESID_F32;
   float* x0 = (float*)(ws + p.x_in);
   RUN(ucod_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, stream));
-  RUN(ucod_gemm_bf16(epi_patch, patches, T[0], x0, d->B * (tok - 1), D, d->Kpad, (const float*)T[1], nullptr, nullptr,
-                     (const float*)T[3], tok, gv, stream));
-  if (r16) RUN(ucod_cls_rows_h16(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
-  else RUN(ucod_cls_rows(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
+  RUN(ucod_gemm_bf16_reg(epi_patch, patches, T[0], x0, d->B * (tok - 1 - d->n_reg), D, d->Kpad, (const float*)T[1], nullptr, nullptr,
+                         (const float*)T[3], tok, d->n_reg, gv, stream));
+  if (r16) RUN(ucod_cls_rows_h16_reg(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
+  else RUN(ucod_cls_rows_reg(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
 
   for (int l = 0; l < d->L; ++l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
@@ -142,7 +142,7 @@ extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int
                                  t->lora_dropout > 0.f ? &drop : nullptr, stream));
     if (last) {   // key hook: K rows of the augmented qkv weight; [B,D,h,w] out
       const char* wk = (const char*)X[0] + (size_t)D * KA * 2;
-      RUN(ucod_gemm_bf16(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, d->n_reg, gv, stream));
       break;
     }
     float* x_mid = (float*)(ws + p.x_mid + p.s_x * l);
@@ -195,13 +195,13 @@ bool valid_infer(const ucod_vit_train_desc* t) {
   const ucod_vit_desc* d = &t->vit;
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && (d->resid16 == 0 || d->resid16 == 1);
+         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);
 }
 IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;
   IPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1;
+  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
   p.M = d->B * p.tok;
   const size_t M = p.M, D = d->D, F = d->F;
   size_t o = 0;
@@ -248,9 +248,9 @@ extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t
   const int epi_resid = r16 ? UCOD_EPI_BIAS_SCALE_RESID_H16 : UCOD_EPI_BIAS_SCALE_RESID_F32;
   RUN(ucod_fill_qscale(qscale, D, 0.125f * 1.4426950408889634f, stream));
   RUN(ucod_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, stream));
-  RUN(ucod_gemm_bf16(epi_patch, patches, T[0], x, d->B * (tok - 1), D, d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, gv, stream));
-  if (r16) RUN(ucod_cls_rows_h16(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
-  else RUN(ucod_cls_rows(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, stream));
+  RUN(ucod_gemm_bf16_reg(epi_patch, patches, T[0], x, d->B * (tok - 1 - d->n_reg), D, d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, d->n_reg, gv, stream));
+  if (r16) RUN(ucod_cls_rows_h16_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
+  else RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
   for (int l = 0; l < d->L; ++l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
     const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
@@ -260,7 +260,7 @@ extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t
     else RUN(ucod_layernorm_lora(x, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps, dp, stream));
     if (l == d->L - 1) {
       const char* wk = (const char*)X[0] + (size_t)D * KA * 2;
-      RUN(ucod_gemm_bf16(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, gv, stream));
+      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, d->n_reg, gv, stream));
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
@@ -348,7 +348,7 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     const size_t n_m = (size_t)r * (size_t)(D + fc1_width(d, mlp)) * sizeof(float);
     if (hipMemsetAsync(const_cast<void*>((TM + UCOD_VIT_TRAIN_MLP_STRIDE * last)[2]), 0, n_m, (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
   }
-  RUN(ucod_key_grad_tokens(dkey, dqkv, d->B, tok, D, stream));
+  RUN(ucod_key_grad_tokens_reg(dkey, dqkv, d->B, tok, D, d->n_reg, stream));
   RUN(qkv_side(last));
   if (last == 0) return UCOD_OK;
   {

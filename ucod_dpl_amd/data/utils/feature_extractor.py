@@ -29,11 +29,20 @@ ARCHS = {
     "dinov2_vitg14": (1536, 24, 40, 14, 518, True),
     "dino_vits8": (384, 6, 12, 8, 224, False),
     "dino_vitb8": (768, 12, 12, 8, 224, False),
+    # DINOv2 with registers (HF Dinov2WithRegistersModel, model_type "dinov2_with_registers"): the tuples of their plain siblings; the register count is in REGISTER_ARCHS
+    "dinov2_vits14_reg": (384, 6, 12, 14, 518, True),
+    "dinov2_vitb14_reg": (768, 12, 12, 14, 518, True),
+    "dinov2_vitl14_reg": (1024, 16, 24, 14, 518, True),
+    "dinov2_vitg14_reg": (1536, 24, 40, 14, 518, True),
 }
+# architectures with register tokens -> how many (embeddings.register_tokens [1, R, D]: R tokens between CLS and the patches, no position rows)
+REGISTER_ARCHS = {"dinov2_vits14_reg": 4, "dinov2_vitb14_reg": 4, "dinov2_vitl14_reg": 4, "dinov2_vitg14_reg": 4}
 HUB_TO_ARCH = {"facebook/dinov2-small": "dinov2_vits14", "facebook/dinov2-base": "dinov2_vitb14", "facebook/dinov2-large": "dinov2_vitl14",
-               "facebook/dinov2-giant": "dinov2_vitg14", "facebook/dino-vits8": "dino_vits8", "facebook/dino-vitb8": "dino_vitb8"}
+               "facebook/dinov2-giant": "dinov2_vitg14", "facebook/dino-vits8": "dino_vits8", "facebook/dino-vitb8": "dino_vitb8",
+               "facebook/dinov2-with-registers-small": "dinov2_vits14_reg", "facebook/dinov2-with-registers-base": "dinov2_vitb14_reg",
+               "facebook/dinov2-with-registers-large": "dinov2_vitl14_reg", "facebook/dinov2-with-registers-giant": "dinov2_vitg14_reg"}
 # architectures whose MLP is Dinov2SwiGLUFFN (config.use_swiglu_ffn, modeling_dinov2.py:300-315,355): weights_in [2F, D] / weights_out [D, F] instead of fc1 / fc2
-SWIGLU_ARCHS = {"dinov2_vitg14"}
+SWIGLU_ARCHS = {"dinov2_vitg14", "dinov2_vitg14_reg"}
 
 
 def swiglu_hidden(D, mlp_ratio=4):
@@ -74,6 +83,10 @@ def _random_state_dict(arch, seed, image_size, tn):
         if ls:
             sd[p + "layer_scale1.lambda1"], sd[p + "layer_scale2.lambda1"] = torch.ones(D), torch.ones(D)
     sd["layernorm.weight"], sd["layernorm.bias"] = torch.ones(D), torch.zeros(D)
+    if arch in REGISTER_ARCHS:
+        # drawn like every other tensor and LAST (the plain sibling's tensors are the same draws), NOT HF's zero init: a pass that dropped zero registers would still
+        # differ from the plain model by four constant tokens only, one that dropped these is visibly wrong
+        sd["embeddings.register_tokens"] = tn(1, REGISTER_ARCHS[arch], D)
     return sd
 
 
@@ -135,8 +148,16 @@ class backbone(nn.Module):
             heads = heads or hf_cfg.get("num_attention_heads") or ARCHS[HUB_TO_ARCH[config.backbone]][1]
             if eps is None:
                 # transformers' defaults when config.json omits the key: ViTConfig (the DINOv1 checkpoints) 1e-12, Dinov2Config 1e-6
-                is_v2 = hf_cfg.get("model_type", "dinov2" if "dinov2" in config.type or "dinov2" in str(config.backbone) else "vit") == "dinov2"
+                is_v2 = hf_cfg.get("model_type", "dinov2" if "dinov2" in config.type or "dinov2" in str(config.backbone) else "vit") in ("dinov2", "dinov2_with_registers")
                 eps = hf_cfg.get("layer_norm_eps", 1e-6 if is_v2 else 1e-12)
+            if "num_register_tokens" in hf_cfg or hf_cfg.get("model_type") == "dinov2_with_registers":
+                # config.json against the tensor: a checkpoint whose two halves disagree would run with the wrong token count
+                # (Dinov2WithRegistersConfig's default when the key is absent: 4)
+                said = int(hf_cfg.get("num_register_tokens", 4))
+                reg = next((v for k, v in state_dict.items() if k.endswith("embeddings.register_tokens")), None)
+                have = 0 if reg is None else int(reg.shape[1])
+                if said != have:
+                    raise ValueError(f"config.json says num_register_tokens = {said}, the checkpoint's embeddings.register_tokens holds {have}")
         if heads is None:
             raise ValueError("heads is required with an explicit state_dict")
         if config is not None:

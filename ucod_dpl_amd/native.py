@@ -54,7 +54,7 @@ vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 class VitDesc(C.Structure):
     _fields_ = [(n, ci) for n in ("B", "C", "H", "W", "P", "D", "heads", "F", "L", "Kpad")] + [("eps", cf)] + \
-               [(n, ci) for n in ("full_last_layer", "gemm_variant", "attn_variant", "resid16", "ln_fold")]
+               [(n, ci) for n in ("full_last_layer", "gemm_variant", "attn_variant", "resid16", "ln_fold", "n_reg")]      # (ctypes zero-fills: n_reg = 0 unless set)
 
 
 class VitTrainDesc(C.Structure):
@@ -121,6 +121,15 @@ SIGNATURES = {
     "ucod_vit_split16_stream_offset_ex": (sz, [C.POINTER(VitDesc), ci, ci]),
     "ucod_vit_forward_split16_ex": (ci, [C.POINTER(VitDesc), ci, ci, C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
+    # DINOv2 with registers: the row-mapped drains, leading-row kernels, key-gradient scatter and CLS attention row for tok = 1 + n_reg + n tokens per image
+    "ucod_gemm_bf16_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
+    "ucod_gemm_bf16_stats_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, ci, vp]),
+    "ucod_cls_rows_reg": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ucod_cls_rows_h16_reg": (ci, [vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ucod_cls_rows_h16_stats_reg": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ucod_key_grad_tokens_reg": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+    "ucod_cls_qk_reg": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "ucod_cls_attention_reg": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),
     "ucod_cls_rows_h16_stats": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp]),

@@ -26,14 +26,17 @@ from .swiglu import lora_b_from_engine, lora_b_to_engine
 from . import ops
 
 
-def _interp_pos_dinov2(pos, gh, gw):
-    """transformers modeling_dinov2.py:57-95 (bicubic, size=, align_corners=False, computed in f32)."""
+def _interp_pos_dinov2(pos, gh, gw, antialias=False):
+    """transformers modeling_dinov2.py:57-95 (bicubic, size=, align_corners=False, computed in f32).  ``antialias``: what Dinov2WithRegistersEmbeddings
+    .interpolate_pos_encoding passes (modeling_dinov2_with_registers.py: antialias=True) -- torch's antialiased bicubic filter widens where the target grid is
+    SMALLER than the stored one (224 px on a 518-px checkpoint) and uses the cubic coefficient -0.5 instead of -0.75 everywhere, so the rows differ on every
+    interpolated grid."""
     n0 = pos.shape[1] - 1
     if n0 == gh * gw and gh == gw:
         return pos
     s = int(n0 ** 0.5)
     pp = pos[:, 1:].reshape(1, s, s, -1).permute(0, 3, 1, 2).float()
-    pp = F.interpolate(pp, size=(gh, gw), mode="bicubic", align_corners=False)
+    pp = F.interpolate(pp, size=(gh, gw), mode="bicubic", align_corners=False, antialias=bool(antialias))
     return torch.cat((pos[:, :1], pp.permute(0, 2, 3, 1).reshape(1, gh * gw, -1)), 1)
 
 
@@ -54,11 +57,17 @@ def normalize_state_dict(sd):
     patch_w [D,C,P,P], patch_b, cls [D], pos [1,1+n,D], kind ('dinov2'|'dinov1'),
     layers: list of dict(ln1_g, ln1_b, qkv_w [3D,D], qkv_b, proj_w, proj_b, ls1|None, ln2_g, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b, ls2|None).
     A SwiGLU checkpoint (DINOv2 ViT-g/14: mlp.weights_in / mlp.weights_out, modeling_dinov2.py:300-315) also sets ``mlp = "swiglu"``; its fc1_w / fc1_b are
-    weights_in [2F, D] / [2F] in HF's row order (x1 rows, then x2 rows) and fc2_w is weights_out [D, F] (swiglu.prepare pads and interleaves them)."""
+    weights_in [2F, D] / [2F] in HF's row order (x1 rows, then x2 rows) and fc2_w is weights_out [D, F] (swiglu.prepare pads and interleaves them).
+    A DINOv2-with-registers checkpoint (HF Dinov2WithRegistersModel: embeddings.register_tokens [1, R, D], placed between CLS and the patch tokens, without
+    position rows) also sets ``reg`` -- the register tokens [R, D], None for a [1, 0, D] tensor (R = 0) -- and ``pos_antialias = True``: that model interpolates
+    its position rows with antialias=True, plain DINOv2 does not.  Read both with ``.get``: a dict without the key has neither entry and means R = 0, no
+    antialias.  Register tokens on a DINOv1 layout are a ValueError."""
     sd = {k: v for k, v in sd.items()}
     out = {"layers": []}
     if "cls_token" in sd and "pos_embed" in sd:                      # in-repo DINO
         out["kind"] = "dinov1"
+        if any(k.split(".")[-1] in ("register_tokens", "reg_token") for k in sd):
+            raise ValueError("register tokens in a DINOv1 (in-repo VisionTransformer) state dict: only DINOv2 with registers has them")
         out["patch_w"], out["patch_b"] = sd["patch_embed.proj.weight"], sd["patch_embed.proj.bias"]
         out["cls"], out["pos"] = sd["cls_token"].reshape(-1), sd["pos_embed"]
         L = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
@@ -81,6 +90,15 @@ def normalize_state_dict(sd):
     out["cls"], out["pos"] = g("embeddings.cls_token").reshape(-1), g("embeddings.position_embeddings")
     has_ls = any("layer_scale1" in k for k in sd)
     out["kind"] = "dinov2" if has_ls else "dinov1"
+    if pref + "embeddings.register_tokens" in sd:
+        reg = g("embeddings.register_tokens")
+        if reg.dim() != 3 or reg.shape[0] != 1 or reg.shape[2] != out["cls"].shape[0]:
+            raise ValueError(f"embeddings.register_tokens has shape {tuple(reg.shape)}, expected [1, R, {out['cls'].shape[0]}]")
+        if out["kind"] != "dinov2":
+            raise ValueError("register tokens in a DINOv1 (ViTModel, no LayerScale) state dict: only DINOv2 with registers has them")
+        # (the key alone marks Dinov2WithRegistersModel, R = 0 included: its embeddings interpolate with antialias=True whatever R is)
+        out["pos_antialias"] = True
+        out["reg"] = reg[0] if reg.shape[1] > 0 else None
     lay = "encoder.layer." if any(k.startswith(pref + "encoder.layer.") for k in sd) else "encoder.layers."
     L = 1 + max(int(k[len(pref + lay):].split(".")[0]) for k in sd if k.startswith(pref + lay))
     swiglu = pref + lay + "0.mlp.weights_in.weight" in sd
@@ -234,6 +252,11 @@ class _BackboneEngine:
         pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=self.device)
         pw[:, :K] = self._f32(c["patch_w"]).reshape(self.D, K)
         self._pos_src, self._pos_cache, self._pos_scale = c["pos"].detach().float().cpu(), {}, None
+        self._pos_antialias = bool(c.get("pos_antialias", False))
+        # register tokens (DINOv2 with registers): R rows between CLS and the patches; table slot +2 is then [(1 + R), D], the CLS row first (``_lead_rows``)
+        reg = c.get("reg")
+        self.R = 0 if reg is None else int(reg.shape[0])
+        self._lead_src = c["cls"].reshape(1, -1) if self.R == 0 else torch.cat((c["cls"].reshape(1, -1).float(), reg.float().to(c["cls"].device)), 0)
         self._guard = _SaturationGuard(self.lib, self.device)
         self._ws = self._side = self._side_ws = None
         self.layers = []
@@ -242,12 +265,23 @@ class _BackboneEngine:
     def _f32(self, t):
         return t.detach().to(self.device, torch.float32).contiguous()
 
+    def _lead_rows(self):
+        """f32 [(1 + R), D] on the device: the CLS token followed by the register tokens (R = 0: the CLS row alone, [1, D])."""
+        return self._f32(self._lead_src)
+
+    def tokens(self, gh, gw):
+        """tokens per image of a gh x gw grid: [CLS | R registers | gh gw patches]"""
+        return 1 + self.R + gh * gw
+
     def _pos(self, gh, gw):
         """The position rows of a gh x gw grid (cached), times ``_pos_scale`` where the patch embedding's operands carry a scale (fp16 terms)."""
         key = (gh, gw)
         if key not in self._pos_cache:
-            fn = _interp_pos_dinov2 if self.kind == "dinov2" else _interp_pos_dinov1
-            pos = fn(self._pos_src, gh, gw)[0].to(self.device, torch.float32).contiguous()
+            if self.kind == "dinov2":
+                pos = _interp_pos_dinov2(self._pos_src, gh, gw, antialias=self._pos_antialias)
+            else:
+                pos = _interp_pos_dinov1(self._pos_src, gh, gw)
+            pos = pos[0].to(self.device, torch.float32).contiguous()
             self._pos_cache[key] = pos if self._pos_scale is None else pos * self._pos_scale
         return self._pos_cache[key]
 
@@ -259,6 +293,7 @@ class _BackboneEngine:
         d.full_last_layer = int(self.full_last_layer)
         d.gemm_variant, d.attn_variant = self.gemm_variant, self.attn_variant
         d.resid16, d.ln_fold = int(self.resid16), int(self.ln_fold)
+        d.n_reg = self.R
         return d
 
     def _table(self, gh, gw, rows=None):
@@ -362,7 +397,7 @@ class ViTEngine(_BackboneEngine):
         self.ln_fold = bool(can_fold and ln_fold is not False)
         f32, dev = self._f32, self.device
         bf = lambda t, name=None: ops.cast_bf16(f32(t), lib=self.lib)  # noqa: E731
-        self.patch_w, self.patch_b, self.cls = bf(pw), f32(c["patch_b"]), f32(c["cls"])
+        self.patch_w, self.patch_b, self.cls = bf(pw), f32(c["patch_b"]), self._lead_rows()
         self.layers = [layer_row(l, bf, f32) for l in c["layers"]]
         self.fold_layers = None
         self.q_row_scale = None                                    # [3D] f32 on the device: the row scale the folded QKV entries were built with (merge_into refolds with it)
@@ -478,13 +513,14 @@ class ViTEngine(_BackboneEngine):
         lib = self.lib
         d = self._desc(B, H, W)
         off = lib.ucod_vit_last_ln1_offset_mlp(C.byref(d), self.mlp)
-        tok = key.shape[-2] * key.shape[-1] + 1
+        hw, R = key.shape[-2] * key.shape[-1], self.R
+        tok = self.tokens(key.shape[-2], key.shape[-1])
         last = self.layers[-1]
         q = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
-        k = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
-        N.check(lib.ucod_cls_qk(self._ws.data_ptr() + off, N.ptr(last[N.QKV_W]), N.ptr(last[N.QKV_B]), N.ptr(q), N.ptr(k), B, tok, self.D, N.stream()), "ucod_cls_qk")
-        att = torch.empty(B, self.heads, tok - 1, dtype=torch.float32, device=self.device)
-        N.check(lib.ucod_cls_attention(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, tok - 1, 0.125, N.stream()), "ucod_cls_attention")
+        k = torch.empty(B, 1 + R, self.D, dtype=torch.float32, device=self.device)      # the keys of CLS and of the R register tokens (in the softmax, not in the row)
+        N.check(lib.ucod_cls_qk_reg(self._ws.data_ptr() + off, N.ptr(last[N.QKV_W]), N.ptr(last[N.QKV_B]), N.ptr(q), N.ptr(k), B, tok, self.D, R, N.stream()), "ucod_cls_qk")
+        att = torch.empty(B, self.heads, hw, dtype=torch.float32, device=self.device)
+        N.check(lib.ucod_cls_attention_reg(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()), "ucod_cls_attention")
         return key, att
 
     __call__ = forward
@@ -531,7 +567,7 @@ class SplitViTEngine(_BackboneEngine):
         wscale = ops.pow2_scale if f16 else (lambda t: 1.0)
         act = [ops.split16_class_scale(k) for k in (N.SPLIT16_LN, N.SPLIT16_ATT, N.SPLIT16_LN, N.SPLIT16_HIDDEN)] if f16 else None
         self.wscale = [wscale(pw)]                                # [patch, (qkv, proj, fc1, fc2) x L]: what the fp16-term driver reads
-        self.patch_w, self.patch_b, self.cls = sw(pw, self.wscale[0]), f32(c["patch_b"]), f32(c["cls"])
+        self.patch_w, self.patch_b, self.cls = sw(pw, self.wscale[0]), f32(c["patch_b"]), self._lead_rows()
         if f16:
             self._pos_scale = ops.split16_class_scale(N.SPLIT16_PATCH) * self.wscale[0]
             self.patch_b, self.cls = self.patch_b * self._pos_scale, self.cls * self._pos_scale
@@ -609,22 +645,25 @@ class SplitViTEngine(_BackboneEngine):
         key = self.forward(img)
         B, _, H, W = img.shape
         off = self._stream_offset(self._desc(B, H, W))
-        tok = key.shape[-2] * key.shape[-1] + 1
+        hw, R = key.shape[-2] * key.shape[-1], self.R
+        tok = self.tokens(key.shape[-2], key.shape[-1])
         x = self._ws[off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
         L_ = self._last
-        h_cls = ops.layernorm(x[:, 0].contiguous(), L_["ln_g"], L_["ln_b"], self.eps, out_f32=True)
+        # the CLS row and the R register rows of every image: all of them are keys of the CLS query's softmax, only the CLS row is a query
+        h_lead = ops.layernorm(x[:, :1 + R].reshape(B * (1 + R), self.D).contiguous(), L_["ln_g"], L_["ln_b"], self.eps, out_f32=True)
+        h_cls = h_lead if R == 0 else h_lead.view(B, 1 + R, self.D)[:, 0].contiguous()
         if self.term == "f16":
             # the scales of the pass itself, known at load: the LayerNorm class scale for the rows, the last layer's QKV weight scale (no device-to-host read here)
             sc = dict(term="f16", x_scale=ops.split16_class_scale(N.SPLIT16_LN), w_scale=self._wscale_of(self.L - 1, "qkv"))
             with self._guard.bind():
                 q = ops.linear_split(h_cls, L_["wq"], L_["bq"], 2, **sc)
-                k = ops.linear_split(h_cls, L_["wk"], L_["bk"], 2, **sc)
+                k = ops.linear_split(h_lead, L_["wk"], L_["bk"], 2, **sc)
             self._guard.arm(torch.cuda.current_stream(self.device))
         else:
             q = ops.linear_split(h_cls, L_["wq"], L_["bq"], self.terms)
-            k = ops.linear_split(h_cls, L_["wk"], L_["bk"], self.terms)
-        att = torch.empty(B, self.heads, tok - 1, dtype=torch.float32, device=self.device)
-        N.check(self.lib.ucod_cls_attention(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, tok - 1, 0.125, N.stream()), "ucod_cls_attention")
+            k = ops.linear_split(h_lead, L_["wk"], L_["bk"], self.terms)
+        att = torch.empty(B, self.heads, hw, dtype=torch.float32, device=self.device)
+        N.check(self.lib.ucod_cls_attention_reg(N.ptr(q), N.ptr(k.contiguous()), N.ptr(key), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()), "ucod_cls_attention")
         return key, att
 
     __call__ = forward
@@ -1062,6 +1101,8 @@ class ViTLoRAEngine(ViTEngine):
         mine, theirs = (self.D, self.L, self.F, self.heads, self.mlp), (engine.D, engine.L, engine.F, engine.heads, engine.mlp)
         if mine != theirs:
             raise ValueError(f"merge_into: the engines differ in (D, L, F, heads, MLP kind): {mine} here, {theirs} there")
+        if self.R != engine.R:
+            raise ValueError(f"merge_into: this engine has {self.R} register tokens, the other {engine.R}: they were not built from the same checkpoint")
         if engine.patch_w.device != self.lora.device:
             raise ValueError(f"merge_into: this engine is on {self.lora.device}, the other on {engine.patch_w.device}")
         base, lib, D, r = self._base_sd, engine.lib, self.D, self.r
