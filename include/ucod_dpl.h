@@ -52,6 +52,8 @@ extern "C" {
 /* (still 5) DINOv2 with registers: ucod_vit_desc gained a trailing n_reg (0 = every caller that zero-fills the descriptor, as the ctypes binding does: the passes
  * are then launch for launch and bit for bit what they were) and the *_reg forms of the row-mapped GEMM drains, the leading-row kernels, the key-gradient scatter and
  * the CLS attention row were added.  ucod_vit_train_desc embeds the descriptor, so its LoRA fields moved by one int; callers build both from this header. */
+/* (still 5) DINOv3 (rotary position embedding): ucod_vit_desc gained a trailing `rope` pointer (NULL = every caller that zero-fills the descriptor: the passes are then
+ * launch for launch and bit for bit what they were) and ucod_rope_qk was added; the training-pass drivers refuse a non-NULL table. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -392,7 +394,25 @@ typedef struct {
                              is f32 [(1 + n_reg), D] (the CLS row, then the register rows; fp16-term pass: times S_patch like CLS / pos), slot +3 stays [1 + n, D];
                              workspace sizes, ucod_vit_last_ln1_offset* and the stream offsets count tok rows; key_out stays [B, D, H/P, W/P] (patch tokens only).
                              0: launch for launch and bit for bit the pass without the field. */
+  const float* rope;      /* DINOv3 (HF DINOv3ViTModel): device pointer to the rotary table of THIS grid, f32 [n, 64] = cos[0:32] | sin[0:32] per patch token (ucod_rope_qk);
+                             NULL = no rotary embedding (every checkpoint but DINOv3): launch for launch and bit for bit the pass without the field.  With a table
+                             ucod_vit_forward* runs one ucod_rope_qk launch between the QKV GEMM (plain or LayerNorm-folded) and the attention kernel of every layer that runs
+                             attention, on the 16-bit QKV buffer; the split passes (_split*, _split16*) run it on the f32 QKV output in front of ucod_qkv_split /
+                             ucod_split16_qkv (split terms are never rotated).  The key hook is the last layer's K projection BEFORE rotation, so a key-minimal pass
+                             runs no rotation in its last layer.  Table slot +3 then holds zeros [1 + n, D] (DINOv3 has no position table).  attn_variant == 8 with a
+                             table is UCOD_EINVAL (the fp8 epilogue writes e4m3 Q / K straight from the GEMM drain), and so are the training-pass drivers
+                             (ucod_vit_forward_train* / _backward* / _forward_lora_infer*: attention backward would need the inverse rotation of dq / dk). */
 } ucod_vit_desc;
+/* Rotary position embedding of DINOv3 (transformers modeling_dinov3_vit.py: apply_rotary_pos_emb with rotate_half) on the Q and K thirds of the PATCH rows of a
+ * QKV buffer [B tok, 3 heads 64], in place.  tok = 1 + n_reg + n; token row t >= 1 + n_reg of an image is patch p = t - 1 - n_reg and uses table row p of
+ * cos_sin f32 [n, 64] = cos[0:32] | sin[0:32] (the model's cos / sin are that half tiled twice); for i < 32 of every head of Q and of K:
+ *   out[i] = v[i] cos[i] - v[i + 32] sin[i],  out[i + 32] = v[i + 32] cos[i] + v[i] sin[i]
+ * in f32, rounded once to the element type.  elem: UCOD_ROPE_ELEM_HALF = the library's 16-bit operand type (ucod_half_name), UCOD_ROPE_ELEM_F32 = f32 (the QKV
+ * output of the split passes).  CLS rows, register rows and the V third are neither read nor written.  The map is linear in v: it commutes with the softmax
+ * pre-scale on the Q rows and (exactly) with a power-of-two operand scale.  B, tok, heads > 0, 0 <= n_reg < tok - 1.  csrc/rope.hip. */
+#define UCOD_ROPE_ELEM_HALF 0
+#define UCOD_ROPE_ELEM_F32 1
+int ucod_rope_qk(void* qkv, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, void* stream);
 size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d);
 int ucod_vit_forward(const ucod_vit_desc* d, const void* const* table_host, const float* img, float* key_out,
                      void* workspace, size_t workspace_bytes, void* stream);

@@ -737,6 +737,8 @@ extern "C" int ucod_vit_forward_split_mlp(const ucod_vit_desc* d, int terms, int
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[2], qkv, M, 3 * D, P * D, (const float*)W[3], nullptr, nullptr, nullptr, tok, gv, stream));
+    // DINOv3: the rotation runs on the f32 projection; the terms below are split from the rotated values
+    if (d->rope) RUN(ucod_rope_qk(qkv, UCOD_ROPE_ELEM_F32, d->rope, d->B, tok, R, d->heads, stream));
     RUN(ucod_qkv_split(qkv, att, d->B, tok, d->heads, terms, 0.125f * 1.4426950408889634f, stream));
     RUN(ucod_attention_split_fwd(att, a, d->B, tok, d->heads, terms, stream));
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, a, W[4], x, M, D, P * D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));

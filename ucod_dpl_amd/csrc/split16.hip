@@ -735,6 +735,8 @@ extern "C" int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int 
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_F32, h, W[2], qkv, M, 3 * D, 3 * D, (const float*)W[3], nullptr, nullptr, nullptr, tok, gv, stream));
+    // DINOv3: the rotation runs on the f32 projection, which still carries the power-of-two operand scales (they pass through a linear map exactly)
+    if (d->rope) RUN(ucod_rope_qk(qkv, UCOD_ROPE_ELEM_F32, d->rope, d->B, tok, R, d->heads, stream));
     RUN(ucod_split16_qkv(qkv, att, d->B, tok, d->heads, 1.0f / (sLN * ws_l[0]), 0.125f * 1.4426950408889634f, sQKV, stream));
     RUN(ucod_split16_attention_fwd(att, a, d->B, tok, d->heads, sQKV, sATT, stream));
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SCALE_RESID_F32, a, W[4], x, M, D, 3 * D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));

@@ -55,6 +55,7 @@ bool valid(const ucod_vit_desc* d, int mlp = UCOD_MLP_GELU) {
   return d && (mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU) && d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 &&
          d->heads > 0 && d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 &&
          d->Kpad >= d->C * d->P * d->P && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) && attn_variant_known(d->attn_variant) &&
+         (d->rope == nullptr || d->attn_variant != 8) &&              // (the fp8 epilogue writes e4m3 Q / K straight from the GEMM drain: nothing to rotate)
          (d->ln_fold == 0 || (d->ln_fold == 1 && d->resid16 == 1 && d->attn_variant != 8 && UCOD_HALF_IS_F16 && d->D % 256 == 0 && d->D <= 1536));
 }
 
@@ -172,6 +173,8 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
       if (fold) RUN(ucod_gemm_lnfold(UCOD_EPI_LNFOLD_BIAS_BF16, x, W[2], qkv, M, 3 * D, D, (const float*)W[3], (const float*)W[14], have_part ? nullptr : stats,
                                      have_part ? part : nullptr, nslot, d->eps, nullptr /* the folded Q rows carry the softmax pre-scale */, gv, stream));
       else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h, W[2], qkv, M, 3 * D, D, (const float*)W[3], prescale ? qscale : nullptr, nullptr, nullptr, tok, gv, stream));
+      // DINOv3: rotate q and k of the patch tokens (linear: the pre-scale in the Q rows passes through); the key hook above took k before rotation
+      if (d->rope) RUN(ucod_rope_qk(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, R, d->heads, stream));
       RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, prescale ? 0.f : scale, (av == 5 || av == 66) ? av : 0, stream));
     }
     RUN(resid_gemm(a, W[4], (const float*)W[5], (const float*)W[6], D, fold));

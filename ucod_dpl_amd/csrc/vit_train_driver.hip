@@ -33,6 +33,7 @@ bool valid_qkv(const ucod_vit_train_desc* t) {
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
+         d->rope == nullptr &&                                      // DINOv3: attention backward would need the inverse rotation of dq / dk -- not built, refused
          d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
 }
 
@@ -195,7 +196,8 @@ bool valid_infer(const ucod_vit_train_desc* t) {
   const ucod_vit_desc* d = &t->vit;
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);
+         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&
+         d->rope == nullptr;                                        // (DINOv3 runs on the frozen engines only)
 }
 IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;

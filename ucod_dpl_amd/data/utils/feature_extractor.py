@@ -18,7 +18,7 @@ from pathlib import Path
 import torch
 from torch import nn
 
-from ...vit_engine import ViTEngine, SplitViTEngine
+from ...vit_engine import ViTEngine, SplitViTEngine, is_dinov3
 from ...engine.registry import BACKBONE_REGISTRY
 
 # name -> (width D, heads, layers, patch, pretrain image size, layerscale?)
@@ -34,15 +34,29 @@ ARCHS = {
     "dinov2_vitb14_reg": (768, 12, 12, 14, 518, True),
     "dinov2_vitl14_reg": (1024, 16, 24, 14, 518, True),
     "dinov2_vitg14_reg": (1536, 24, 40, 14, 518, True),
+    # DINOv3 (HF DINOv3ViTModel, model_type "dinov3_vit"): patch 16, 4 register tokens, no position table (rotary position embedding), MLP width 4 D -- GELU, or
+    # gated SiLU for the "plus" models (SWIGLU_ARCHS).  ViT-7B/16 is left out: its head dimension is 128.
+    "dinov3_vits16": (384, 6, 12, 16, 224, True),
+    "dinov3_vitb16": (768, 12, 12, 16, 224, True),
+    "dinov3_vitl16": (1024, 16, 24, 16, 224, True),
+    "dinov3_vits16plus": (384, 6, 12, 16, 224, True),
+    "dinov3_vith16plus": (1280, 20, 32, 16, 224, True),
 }
+# the DINOv3 architectures -> their register tokens (every released ViT has 4).  A table of its own, not entries of REGISTER_ARCHS: that table holds
+# exactly the DINOv2-with-registers names, each the twin of a plain architecture, and tests/test_registers_host.py::test_register_archs pins it to those four
+DINOV3_ARCHS = {"dinov3_vits16": 4, "dinov3_vitb16": 4, "dinov3_vitl16": 4, "dinov3_vits16plus": 4, "dinov3_vith16plus": 4}
 # architectures with register tokens -> how many (embeddings.register_tokens [1, R, D]: R tokens between CLS and the patches, no position rows)
 REGISTER_ARCHS = {"dinov2_vits14_reg": 4, "dinov2_vitb14_reg": 4, "dinov2_vitl14_reg": 4, "dinov2_vitg14_reg": 4}
 HUB_TO_ARCH = {"facebook/dinov2-small": "dinov2_vits14", "facebook/dinov2-base": "dinov2_vitb14", "facebook/dinov2-large": "dinov2_vitl14",
                "facebook/dinov2-giant": "dinov2_vitg14", "facebook/dino-vits8": "dino_vits8", "facebook/dino-vitb8": "dino_vitb8",
                "facebook/dinov2-with-registers-small": "dinov2_vits14_reg", "facebook/dinov2-with-registers-base": "dinov2_vitb14_reg",
-               "facebook/dinov2-with-registers-large": "dinov2_vitl14_reg", "facebook/dinov2-with-registers-giant": "dinov2_vitg14_reg"}
+               "facebook/dinov2-with-registers-large": "dinov2_vitl14_reg", "facebook/dinov2-with-registers-giant": "dinov2_vitg14_reg",
+               "facebook/dinov3-vits16-pretrain-lvd1689m": "dinov3_vits16", "facebook/dinov3-vits16plus-pretrain-lvd1689m": "dinov3_vits16plus",
+               "facebook/dinov3-vitb16-pretrain-lvd1689m": "dinov3_vitb16", "facebook/dinov3-vitl16-pretrain-lvd1689m": "dinov3_vitl16",
+               "facebook/dinov3-vitl16-pretrain-sat493m": "dinov3_vitl16", "facebook/dinov3-vith16plus-pretrain-lvd1689m": "dinov3_vith16plus"}
 # architectures whose MLP is Dinov2SwiGLUFFN (config.use_swiglu_ffn, modeling_dinov2.py:300-315,355): weights_in [2F, D] / weights_out [D, F] instead of fc1 / fc2
-SWIGLU_ARCHS = {"dinov2_vitg14", "dinov2_vitg14_reg"}
+# (DINOv3 "plus": config.use_gated_mlp, mlp.gate_proj / up_proj / down_proj with the intermediate width 4 D -- arithmetically the same MLP)
+SWIGLU_ARCHS = {"dinov2_vitg14", "dinov2_vitg14_reg", "dinov3_vits16plus", "dinov3_vith16plus"}
 
 
 def swiglu_hidden(D, mlp_ratio=4):
@@ -60,7 +74,32 @@ def random_state_dict(arch, seed=0, image_size=None, device=None):
     return _random_state_dict(arch, seed, image_size, lambda *s: torch.nn.init.trunc_normal_(torch.empty(*s), std=0.02, a=-0.04, b=0.04, generator=g))
 
 
+def _random_state_dict_dinov3(arch, tn):
+    """HF DINOv3ViTModel's layout (transformers 5.x) without ``embeddings.mask_token``: no position table, ``k_proj`` without a bias, MLP width 4 D (gated or not),
+    register tokens drawn non-zero like every other tensor."""
+    D, heads, L, P, _, _ = ARCHS[arch]
+    F = 4 * D
+    sd = {"embeddings.cls_token": tn(1, 1, D), "embeddings.register_tokens": tn(1, DINOV3_ARCHS[arch], D),
+          "embeddings.patch_embeddings.weight": tn(D, 3, P, P), "embeddings.patch_embeddings.bias": torch.zeros(D)}
+    for i in range(L):
+        p = f"model.layer.{i}."
+        sd[p + "norm1.weight"], sd[p + "norm1.bias"] = torch.ones(D) + tn(D), tn(D)
+        sd[p + "attention.k_proj.weight"] = tn(D, D)
+        for nm in ("v_proj", "q_proj", "o_proj"):
+            sd[p + f"attention.{nm}.weight"], sd[p + f"attention.{nm}.bias"] = tn(D, D), tn(D)
+        sd[p + "layer_scale1.lambda1"] = torch.ones(D)
+        sd[p + "norm2.weight"], sd[p + "norm2.bias"] = torch.ones(D) + tn(D), tn(D)
+        for nm in (("gate_proj", "up_proj") if arch in SWIGLU_ARCHS else ("up_proj",)):
+            sd[p + f"mlp.{nm}.weight"], sd[p + f"mlp.{nm}.bias"] = tn(F, D), tn(F)
+        sd[p + "mlp.down_proj.weight"], sd[p + "mlp.down_proj.bias"] = tn(D, F), tn(D)
+        sd[p + "layer_scale2.lambda1"] = torch.ones(D)
+    sd["norm.weight"], sd["norm.bias"] = torch.ones(D), torch.zeros(D)
+    return sd
+
+
 def _random_state_dict(arch, seed, image_size, tn):
+    if arch in DINOV3_ARCHS:
+        return _random_state_dict_dinov3(arch, tn)
     D, heads, L, P, img, ls = ARCHS[arch]
     img = image_size or img
     n = (img // P) ** 2
@@ -100,16 +139,23 @@ def trained_like_state_dict(arch, seed=0, image_size=None, qk_gain=4.0, layer_sc
     D, heads, L, P, img, ls = ARCHS[arch]
     sd = random_state_dict(arch, seed, image_size)
     g = torch.Generator().manual_seed(seed + 7919)
+    v3 = arch in DINOV3_ARCHS
     for i in range(L):
-        p = f"encoder.layer.{i}."
+        p = f"model.layer.{i}." if v3 else f"encoder.layer.{i}."
         for nm in ("query", "key"):
-            sd[p + f"attention.attention.{nm}.weight"] *= qk_gain
-            sd[p + f"attention.attention.{nm}.bias"] *= qk_gain
+            for k in ((f"attention.{nm[0]}_proj.weight", f"attention.{nm[0]}_proj.bias") if v3 else (f"attention.attention.{nm}.weight", f"attention.attention.{nm}.bias")):
+                if p + k in sd:                                   # (DINOv3: k_proj has no bias)
+                    sd[p + k] *= qk_gain
         if ls:
             lo, hi = layer_scale
             sd[p + "layer_scale1.lambda1"] = lo + (hi - lo) * torch.rand(D, generator=g)
             sd[p + "layer_scale2.lambda1"] = lo + (hi - lo) * torch.rand(D, generator=g)
-    if massive:
+    if massive and v3:
+        # no position table: the massive channels sit in the CLS and register tokens (where a trained model with registers keeps them)
+        for t in (sd["embeddings.cls_token"], sd["embeddings.register_tokens"]):
+            t[0, :, 5 % D] = massive
+            t[0, :, (D * 3) // 4] = -0.75 * massive
+    elif massive:
         pos = sd["embeddings.position_embeddings"]
         n = pos.shape[1]
         for t in (0, 17 % n, 100 % n, n - 1):
@@ -146,6 +192,11 @@ class backbone(nn.Module):
                 raise ValueError(f"Unsupported model type: {config.type}")
             state_dict, hf_cfg = _read_checkpoint(config.backbone_weights)
             heads = heads or hf_cfg.get("num_attention_heads") or ARCHS[HUB_TO_ARCH[config.backbone]][1]
+            if hf_cfg.get("model_type") == "dinov3_vit" or is_dinov3(state_dict):
+                # DINOv3ViTConfig's defaults: layer_norm_eps 1e-5, rope_theta 100 (the inv_freq buffer is not in the checkpoint)
+                if eps is None:
+                    eps = hf_cfg.get("layer_norm_eps", 1e-5)
+                engine_kw.setdefault("rope_theta", float(hf_cfg.get("rope_theta", 100.0)))
             if eps is None:
                 # transformers' defaults when config.json omits the key: ViTConfig (the DINOv1 checkpoints) 1e-12, Dinov2Config 1e-6
                 is_v2 = hf_cfg.get("model_type", "dinov2" if "dinov2" in config.type or "dinov2" in str(config.backbone) else "vit") in ("dinov2", "dinov2_with_registers")
@@ -169,6 +220,7 @@ class backbone(nn.Module):
                     engine_kw[k] = config[k]
         self._src = (state_dict, heads, eps or 1e-6, device)       # (references, not copies) what with_precision() rebuilds a sibling engine from
         self._siblings = {}
+        self._rope_theta = float(engine_kw.pop("rope_theta", 100.0))      # a property of the checkpoint (DINOv3), so every sibling engine of with_precision() gets it
         self.precision, self.engine = self._make_engine(engine_kw.pop("precision", None), engine_kw)
 
     PRECISIONS = {"split2": 2, "split3": 3, "f32eq": 3, "split2h": 2, "split2hf": 2}
@@ -182,8 +234,9 @@ class backbone(nn.Module):
         fp16 terms per operand (22 significand bits at split2's three products; opt-in -- "f32eq" still means split3).  "split2hf": split2h with fc1, its activation and
         the split of the result fused into one launch (``fuse_mlp=True``; opt-in as well)."""
         state_dict, heads, eps, device = self._src
+        engine_kw = dict(engine_kw, rope_theta=self._rope_theta)
         if precision in self.PRECISIONS:
-            extra = {k: v for k, v in engine_kw.items() if k not in ("gemm_variant",)}
+            extra = {k: v for k, v in engine_kw.items() if k not in ("gemm_variant", "rope_theta")}
             if extra:
                 raise ValueError(f"precision={precision!r} takes no {sorted(extra)}: the split-operand engine has one residual stream (f32) and one attention path")
             return precision, SplitViTEngine(state_dict, heads=heads, eps=eps, device=device, terms=self.PRECISIONS[precision],
@@ -205,17 +258,22 @@ class backbone(nn.Module):
             other = object.__new__(type(self))
             nn.Module.__init__(other)
             other.config, other.key, other._src, other._siblings = self.config, None, self._src, self._siblings
+            other._rope_theta = self._rope_theta
             other.precision, other.engine = other._make_engine(precision, {})
             self._siblings[precision] = other
         return self._siblings[precision]
 
     @classmethod
-    def from_state_dict(cls, state_dict, heads, eps=1e-6, device="cuda", **kw):
+    def from_state_dict(cls, state_dict, heads, eps=None, device="cuda", **kw):
+        """``eps=None``: the LayerNorm epsilon of the checkpoint's model class -- DINOv3ViTConfig's default 1e-5 for a DINOv3 state dict, 1e-6 otherwise."""
+        if eps is None:
+            eps = 1e-5 if is_dinov3(state_dict) else 1e-6
         return cls(None, state_dict=state_dict, heads=heads, eps=eps, device=device, **kw)
 
     @classmethod
     def random_init(cls, arch, seed=0, image_size=None, device="cuda", **kw):
-        return cls(None, state_dict=random_state_dict(arch, seed, image_size), heads=ARCHS[arch][1], eps=1e-6, device=device, **kw)
+        # (eps: Dinov2Config's default 1e-6, DINOv3ViTConfig's 1e-5)
+        return cls(None, state_dict=random_state_dict(arch, seed, image_size), heads=ARCHS[arch][1], eps=1e-5 if arch in DINOV3_ARCHS else 1e-6, device=device, **kw)
 
     def forward(self, input, reshape_keys=True):
         with torch.no_grad():

@@ -54,7 +54,8 @@ vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 class VitDesc(C.Structure):
     _fields_ = [(n, ci) for n in ("B", "C", "H", "W", "P", "D", "heads", "F", "L", "Kpad")] + [("eps", cf)] + \
-               [(n, ci) for n in ("full_last_layer", "gemm_variant", "attn_variant", "resid16", "ln_fold", "n_reg")]      # (ctypes zero-fills: n_reg = 0 unless set)
+               [(n, ci) for n in ("full_last_layer", "gemm_variant", "attn_variant", "resid16", "ln_fold", "n_reg")] + \
+               [("rope", vp)]             # (ctypes zero-fills: n_reg = 0 and rope = NULL -- no registers, no rotary embedding -- unless set)
 
 
 class VitTrainDesc(C.Structure):
@@ -74,6 +75,7 @@ class DiscGrads(C.Structure):
     _fields_ = [(n, vp) for n in ("w1", "g1", "b1", "w2", "g2", "b2", "w3", "g3", "b3", "lin_w", "lin_b")]
 
 
+ROPE_ELEM_HALF, ROPE_ELEM_F32 = 0, 1          # element type of ucod_rope_qk's buffer: the library's 16-bit operand type / f32
 UCOD_MLP_GELU, UCOD_MLP_SWIGLU = 0, 1        # MLP kind of the _mlp backbone entry points (include/ucod_dpl.h)
 # activation operand classes of the fp16-term split pass (ucod_split16_class_scale)
 SPLIT16_LN, SPLIT16_QKV, SPLIT16_PROB, SPLIT16_ATT, SPLIT16_HIDDEN, SPLIT16_PATCH = range(6)
@@ -121,6 +123,8 @@ SIGNATURES = {
     "ucod_vit_split16_stream_offset_ex": (sz, [C.POINTER(VitDesc), ci, ci]),
     "ucod_vit_forward_split16_ex": (ci, [C.POINTER(VitDesc), ci, ci, C.POINTER(vp), C.POINTER(cf), ci, vp, vp, vp, sz, vp]),
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
+    # DINOv3: rotary position embedding on the Q and K thirds of the patch rows of a QKV buffer, in place (csrc/rope.hip); elem = ROPE_ELEM_HALF / ROPE_ELEM_F32
+    "ucod_rope_qk": (ci, [vp, ci, vp, ci, ci, ci, ci, vp]),
     # DINOv2 with registers: the row-mapped drains, leading-row kernels, key-gradient scatter and CLS attention row for tok = 1 + n_reg + n tokens per image
     "ucod_gemm_bf16_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_gemm_bf16_stats_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, ci, vp]),

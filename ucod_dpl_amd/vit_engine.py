@@ -3,6 +3,7 @@ walks, and reusable workspaces.  Accepts both checkpoint layouts the reference c
 
 * HuggingFace ``Dinov2Model`` / ``ViTModel`` state dicts (data/utils/feature_extractor.py:20,25) with
   ``attention.attention.{query,key,value}`` or (transformers>=5 ViT) ``attention.{q,k,v}_proj`` names;
+* HuggingFace ``DINOv3ViTModel`` state dicts (no position table: rotary position embedding on the patch tokens' q and k, ``rope_table``);
 * the in-repo DINO ``VisionTransformer`` (models/backbones/dino.py) with fused ``attn.qkv``.
 
 Only what the key hook needs is computed by default (feature_extractor.py:46-47,55-58); see
@@ -52,6 +53,68 @@ def _interp_pos_dinov1(pos, gh, gw):
     return torch.cat((pos[:, :1], pp.permute(0, 2, 3, 1).reshape(1, gh * gw, -1)), 1)
 
 
+def is_dinov3(sd):
+    """True for a HuggingFace DINOv3ViTModel state dict: a patch convolution named ``embeddings.patch_embeddings.weight`` and no position table."""
+    return any(k.endswith("embeddings.patch_embeddings.weight") for k in sd) and not any(k.endswith("embeddings.position_embeddings") for k in sd)
+
+
+def rope_table(gh, gw, theta=100.0):
+    """The rotary table of a gh x gw patch grid, f32 [gh gw, 64] = cos[0:32] | sin[0:32] (what ucod_rope_qk reads): the operations of transformers'
+    DINOv3ViTRopePositionEmbedding.forward in eval mode (modeling_dinov3_vit.py:95-121,153-200), in the same order and type, on the CPU -- bit for bit the first
+    halves of the model's ``cos`` / ``sin`` (which are these 32 values tiled twice; the duplicate is not stored).  Row p = r gw + c: angles 2 pi y inv_freq
+    (16 values), then 2 pi x inv_freq (16 values), y = 2 (r + 0.5) / gh - 1, x = 2 (c + 0.5) / gw - 1, inv_freq[j] = theta^-(4 j / 64)."""
+    inv_freq = 1 / float(theta) ** torch.arange(0, 1, 4 / 64, dtype=torch.float32)
+    coords_h = torch.arange(0.5, gh, dtype=torch.float32) / gh
+    coords_w = torch.arange(0.5, gw, dtype=torch.float32) / gw
+    coords = torch.stack(torch.meshgrid(coords_h, coords_w, indexing="ij"), dim=-1).flatten(0, 1)
+    coords = 2.0 * coords - 1.0
+    angles = (2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]).flatten(1, 2)
+    return torch.cat((torch.cos(angles), torch.sin(angles)), 1).contiguous()
+
+
+def _normalize_dinov3(sd, out):
+    """The DINOv3ViTModel layout (transformers 5.x: ``model.layer.{i}.``; checkpoints written by 4.56: ``layer.{i}.``): q / k / v / o_proj, ``k_proj`` without a
+    bias (config.key_bias = False), ``mlp.up_proj`` -> GELU -> ``mlp.down_proj`` or the gated ``down_proj(silu(gate_proj(x)) * up_proj(x))``, which is DINOv2's
+    SwiGLU with weights_in = cat(gate_proj, up_proj).  Any absent bias is zeros."""
+    pref = next(k[:-len("embeddings.patch_embeddings.weight")] for k in sd if k.endswith("embeddings.patch_embeddings.weight"))
+    g = lambda k: sd[pref + k]  # noqa: E731
+    out["kind"], out["rope"], out["pos"] = "dinov3", True, None
+    out["patch_w"], out["cls"] = g("embeddings.patch_embeddings.weight"), g("embeddings.cls_token").reshape(-1)
+    D = out["cls"].shape[0]
+    zeros = lambda n, like: torch.zeros(n, dtype=like.dtype, device=like.device)  # noqa: E731
+    out["patch_b"] = sd.get(pref + "embeddings.patch_embeddings.bias", zeros(D, out["patch_w"]))
+    reg = sd.get(pref + "embeddings.register_tokens")
+    if reg is not None and (reg.dim() != 3 or reg.shape[0] != 1 or reg.shape[2] != D):
+        raise ValueError(f"embeddings.register_tokens has shape {tuple(reg.shape)}, expected [1, R, {D}]")
+    out["reg"] = reg[0] if reg is not None and reg.shape[1] > 0 else None
+    lay = "model.layer." if any(k.startswith(pref + "model.layer.") for k in sd) else "layer."
+    L = 1 + max(int(k[len(pref + lay):].split(".")[0]) for k in sd if k.startswith(pref + lay))
+    gated = pref + lay + "0.mlp.gate_proj.weight" in sd
+    if gated:
+        out["mlp"] = "swiglu"
+    for i in range(L):
+        p = f"{pref}{lay}{i}."
+
+        def lin(name):
+            w = sd[p + name + ".weight"]
+            return w, sd.get(p + name + ".bias", zeros(w.shape[0], w))
+
+        (q_w, q_b), (k_w, k_b), (v_w, v_b) = (lin(f"attention.{n}_proj") for n in "qkv")
+        proj_w, proj_b = lin("attention.o_proj")
+        up_w, up_b = lin("mlp.up_proj")
+        fc2_w, fc2_b = lin("mlp.down_proj")
+        if gated:
+            gate_w, gate_b = lin("mlp.gate_proj")
+            fc1_w, fc1_b = torch.cat((gate_w, up_w), 0), torch.cat((gate_b, up_b), 0)       # HF SwiGLU row order: the silu rows, then the linear rows
+        else:
+            fc1_w, fc1_b = up_w, up_b
+        out["layers"].append(dict(
+            ln1_g=sd[p + "norm1.weight"], ln1_b=sd[p + "norm1.bias"], qkv_w=torch.cat((q_w, k_w, v_w), 0), qkv_b=torch.cat((q_b, k_b, v_b), 0),
+            proj_w=proj_w, proj_b=proj_b, ls1=sd[p + "layer_scale1.lambda1"], ln2_g=sd[p + "norm2.weight"], ln2_b=sd[p + "norm2.bias"],
+            fc1_w=fc1_w, fc1_b=fc1_b, fc2_w=fc2_w, fc2_b=fc2_b, ls2=sd[p + "layer_scale2.lambda1"]))
+    return out
+
+
 def normalize_state_dict(sd):
     """Map any supported checkpoint layout to a canonical dict:
     patch_w [D,C,P,P], patch_b, cls [D], pos [1,1+n,D], kind ('dinov2'|'dinov1'),
@@ -61,9 +124,14 @@ def normalize_state_dict(sd):
     A DINOv2-with-registers checkpoint (HF Dinov2WithRegistersModel: embeddings.register_tokens [1, R, D], placed between CLS and the patch tokens, without
     position rows) also sets ``reg`` -- the register tokens [R, D], None for a [1, 0, D] tensor (R = 0) -- and ``pos_antialias = True``: that model interpolates
     its position rows with antialias=True, plain DINOv2 does not.  Read both with ``.get``: a dict without the key has neither entry and means R = 0, no
-    antialias.  Register tokens on a DINOv1 layout are a ValueError."""
+    antialias.  Register tokens on a DINOv1 layout are a ValueError.
+    A DINOv3 checkpoint (HF DINOv3ViTModel; ``is_dinov3``) sets ``kind = "dinov3"``, ``rope = True``, ``pos = None`` (there is no position table: the engines
+    rotate q and k of the patch tokens, ``rope_table``) and always ``reg`` (None for R = 0); a missing bias (``k_proj`` has none) is zeros, and a gated MLP is
+    ``mlp = "swiglu"`` with fc1_w = cat(gate_proj, up_proj)."""
     sd = {k: v for k, v in sd.items()}
     out = {"layers": []}
+    if is_dinov3(sd):
+        return _normalize_dinov3(sd, out)
     if "cls_token" in sd and "pos_embed" in sd:                      # in-repo DINO
         out["kind"] = "dinov1"
         if any(k.split(".")[-1] in ("register_tokens", "reg_token") for k in sd):
@@ -222,6 +290,11 @@ class _SaturationGuard:
         self.events = []
 
 
+# (forward_with_cls_attention on DINOv3) why the CLS attention row is refused
+_CLS_ROW_ON_ROPE = ("the CLS query's softmax row needs the ROTATED patch keys of the last layer, and the key map -- the hook's output, taken before the rotation -- "
+                    "does not hold them")
+
+
 def _chunk_bounds(B, ns):
     """B images as ns image-parallel sub-batches [(b0, b1), ...]."""
     return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
@@ -232,7 +305,7 @@ class _BackboneEngine:
     rows (``layer_row``), the descriptor, input checks, workspaces, side streams and the saturation guard.  The defaults below are the split pass's (f32 stream,
     LayerNorm kernels, key-minimal); ``ViTEngine`` sets its own."""
 
-    def _setup(self, state_dict, heads, eps, device, gemm_variant, lib_half):
+    def _setup(self, state_dict, heads, eps, device, gemm_variant, lib_half, rope_theta=100.0):
         """Load the ``lib_half`` library and take the geometry from the checkpoint.  Returns (canonical dict with the MLP entries the tables hold, patch weight [D, Kpad]
         f32 on the device, k zero-padded): the subclass converts them to its operand form."""
         self.lib = N.load(lib_half)
@@ -251,7 +324,9 @@ class _BackboneEngine:
         self.Kpad = (K + 63) // 64 * 64
         pw = torch.zeros(self.D, self.Kpad, dtype=torch.float32, device=self.device)
         pw[:, :K] = self._f32(c["patch_w"]).reshape(self.D, K)
-        self._pos_src, self._pos_cache, self._pos_scale = c["pos"].detach().float().cpu(), {}, None
+        # DINOv3: no position table (slot +3 of the header holds zeros, so the patch and CLS kernels are what they are) but a rotary table per grid (``_rope``)
+        self.rope, self.rope_theta, self._rope_cache = bool(c.get("rope", False)), float(rope_theta), {}
+        self._pos_src, self._pos_cache, self._pos_scale = (None if self.rope else c["pos"].detach().float().cpu()), {}, None
         self._pos_antialias = bool(c.get("pos_antialias", False))
         # register tokens (DINOv2 with registers): R rows between CLS and the patches; table slot +2 is then [(1 + R), D], the CLS row first (``_lead_rows``)
         reg = c.get("reg")
@@ -277,6 +352,9 @@ class _BackboneEngine:
         """The position rows of a gh x gw grid (cached), times ``_pos_scale`` where the patch embedding's operands carry a scale (fp16 terms)."""
         key = (gh, gw)
         if key not in self._pos_cache:
+            if self.rope:
+                self._pos_cache[key] = torch.zeros(1 + gh * gw, self.D, dtype=torch.float32, device=self.device)
+                return self._pos_cache[key]
             if self.kind == "dinov2":
                 pos = _interp_pos_dinov2(self._pos_src, gh, gw, antialias=self._pos_antialias)
             else:
@@ -284,6 +362,17 @@ class _BackboneEngine:
             pos = pos[0].to(self.device, torch.float32).contiguous()
             self._pos_cache[key] = pos if self._pos_scale is None else pos * self._pos_scale
         return self._pos_cache[key]
+
+    def _rope(self, gh, gw):
+        """The rotary table of a gh x gw grid on the device (cached like the position rows): f32 [gh gw, 64], ``rope_table``."""
+        key = (gh, gw)
+        if key not in self._rope_cache:
+            self._rope_cache[key] = rope_table(gh, gw, self.rope_theta).to(self.device)
+        return self._rope_cache[key]
+
+    def _refuse_rope(self, what, why):
+        if self.rope:
+            raise NotImplementedError(f"{what} is not built for a DINOv3 checkpoint (rotary position embedding, RoPE): {why}")
 
     def _desc(self, B, H, W, L=None):
         d = N.VitDesc()
@@ -294,6 +383,7 @@ class _BackboneEngine:
         d.gemm_variant, d.attn_variant = self.gemm_variant, self.attn_variant
         d.resid16, d.ln_fold = int(self.resid16), int(self.ln_fold)
         d.n_reg = self.R
+        d.rope = self._rope(H // self.P, W // self.P).data_ptr() if self.rope else None      # (the cache keeps the table alive)
         return d
 
     def _table(self, gh, gw, rows=None):
@@ -358,8 +448,10 @@ class ViTEngine(_BackboneEngine):
     """HIP ViT forward -> last-layer key map [B, D, H/P, W/P] (f32)."""
 
     def __init__(self, state_dict, heads, eps=1e-6, device="cuda", full_last_layer=False, gemm_variant=0, attn_variant=0, half="f16",
-                 resid="auto", ln_fold="auto"):
-        """``half``: 16-bit type of the GEMM / attention operands -- "f16" (default since round 6: IEEE fp16, what the reference's fp16-autocast
+                 resid="auto", ln_fold="auto", rope_theta=100.0):
+        """``rope_theta``: the base period of the rotary position embedding of a DINOv3 checkpoint (config.rope_theta; its inv_freq buffer is not in the state
+        dict); unused for every other checkpoint.
+        ``half``: 16-bit type of the GEMM / attention operands -- "f16" (default since round 6: IEEE fp16, what the reference's fp16-autocast
         launcher multiplies in; 8x finer rounding than bf16, logits within 1e-3 of the f32 reference at full depth on the flat init; the
         configuration bench.py's headline is measured on) or "bf16" (the dtype BASELINE configs[1] names; opt-in).  Each choice is its own build of
         the same kernels (native.load).
@@ -387,7 +479,10 @@ class ViTEngine(_BackboneEngine):
         if ln_fold not in ("auto", True, False):
             raise ValueError(f"ln_fold must be 'auto', True or False, got {ln_fold!r}")
         self.half = half
-        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, half)
+        if attn_variant == 8 and is_dinov3(state_dict):
+            raise NotImplementedError("attn_variant=8 (the fp8 attention path) is not built for a DINOv3 checkpoint (RoPE): its QKV epilogue writes e4m3 Q and K "
+                                      "straight from the GEMM drain, in front of the rotation")
+        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, half, rope_theta)
         self.resid, self.full_last_layer, self.attn_variant = resid, bool(full_last_layer), attn_variant
         fold_shape = half == "f16" and self.D % 256 == 0 and self.D <= 1536 and attn_variant != 8       # where ucod_gemm_lnfold exists
         self.resid16 = bool(resid == "f16" or (resid == "auto" and (half == "bf16" or (fold_shape and ln_fold is not False))))
@@ -502,6 +597,7 @@ class ViTEngine(_BackboneEngine):
         query's softmax row of the LAST layer, which is all the pseudo-label generator reads from the attentions
         (data/utils/found_bkg_mask.py:23; generate_pseudo_label.py:78-89).  Single-stream pass: the CLS projections are taken
         from the LayerNorm-1 output the pass leaves in its workspace."""
+        self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE)
         if self.full_last_layer:
             raise RuntimeError("forward_with_cls_attention needs the key-minimal pass (full_last_layer=False)")
         ns, self.streams = self.streams, 1
@@ -538,8 +634,9 @@ class SplitViTEngine(_BackboneEngine):
 
     Same call interface as ``ViTEngine`` (``forward`` / ``forward_async`` / ``__call__``, ``D``, ``P``, ``streams``); key-minimal pass only."""
 
-    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0, term="bf16", fuse_mlp=False):
-        """``term="f16"`` (with ``terms=2``; precision name "split2h"): the two terms of every operand are IEEE fp16 values of a power-of-two multiple of it and the three
+    def __init__(self, state_dict, heads, eps=1e-6, device="cuda", terms=3, gemm_variant=0, term="bf16", fuse_mlp=False, rope_theta=100.0):
+        """``rope_theta``: as ``ViTEngine``.
+        ``term="f16"`` (with ``terms=2``; precision name "split2h"): the two terms of every operand are IEEE fp16 values of a power-of-two multiple of it and the three
         partial products run on the fp16 MFMA (csrc/split16.hip, libucod_dpl_f16.so) -- 22 significand bits per operand at the matrix work of ``terms=2``.  Weights are
         scaled per tensor at load (largest magnitude into [2^13, 2^14)), activations per operand class (``ops.split16_class_scale``); a value beyond fp16's range
         is clamped and counted on the device, and ``check_overflow`` raises for a pass that met one.
@@ -558,7 +655,7 @@ class SplitViTEngine(_BackboneEngine):
         self.fuse_mlp = bool(fuse_mlp)
         self._flags = N.SPLIT16_FUSE_MLP if self.fuse_mlp else 0
         f16 = term == "f16"
-        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, "f16" if f16 else "bf16")    # (each term type has its MFMA; either build refuses the other's split entry points)
+        c, pw = self._setup(state_dict, heads, eps, device, gemm_variant, "f16" if f16 else "bf16", rope_theta)    # (each term type has its MFMA; either build refuses the other's split entry points)
         self.nprod = ops.split_products(terms)
         f32, D = self._f32, self.D
         sw = lambda t, s=1.0, role=1: ops.split_rows(f32(t), self.terms, role, term=term, scale=s)  # noqa: E731      (role 1: weights are the B side of y = x W^T)
@@ -642,6 +739,7 @@ class SplitViTEngine(_BackboneEngine):
         (data/utils/found_bkg_mask.py:23; generate_pseudo_label.py:78-89 -- a plain fp32 pass under torch.no_grad() in the reference, which is why the
         pseudo-label generator asks for this engine).  The CLS rows of the last layer's input are taken from the f32 residual stream the pass leaves in its
         workspace, normalised by the f32 LayerNorm kernel, projected to the CLS query / key on split operands, and fed to the f32 attention-row kernel."""
+        self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE)
         key = self.forward(img)
         B, _, H, W = img.shape
         off = self._stream_offset(self._desc(B, H, W))
@@ -747,6 +845,9 @@ class ViTLoRAEngine(ViTEngine):
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on."""
         canon = normalize_state_dict(state_dict)
+        if canon.get("rope"):
+            raise NotImplementedError("backbone-backward (LoRA) mode is not built for a DINOv3 checkpoint (rotary position embedding, RoPE): attention backward would "
+                                      "need the inverse rotation of dq and dk; the frozen-backbone engines (ViTEngine / SplitViTEngine) take it")
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
         mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
