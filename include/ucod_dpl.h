@@ -54,6 +54,8 @@ extern "C" {
  * the CLS attention row were added.  ucod_vit_train_desc embeds the descriptor, so its LoRA fields moved by one int; callers build both from this header. */
 /* (still 5) DINOv3 (rotary position embedding): ucod_vit_desc gained a trailing `rope` pointer (NULL = every caller that zero-fills the descriptor: the passes are then
  * launch for launch and bit for bit what they were) and ucod_rope_qk was added; the training-pass drivers refuse a non-NULL table. */
+/* (still 5) LoRA through DINOv3: ucod_rope_qk_ld (row pitch + direction) was added and ucod_vit_train_desc gained a trailing allow_rope (0 = every caller that
+ * zero-fills the descriptor: a table is refused as before); with it set the training-pass drivers rotate q / k forward and dq / dk back. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -400,8 +402,8 @@ typedef struct {
                              attention, on the 16-bit QKV buffer; the split passes (_split*, _split16*) run it on the f32 QKV output in front of ucod_qkv_split /
                              ucod_split16_qkv (split terms are never rotated).  The key hook is the last layer's K projection BEFORE rotation, so a key-minimal pass
                              runs no rotation in its last layer.  Table slot +3 then holds zeros [1 + n, D] (DINOv3 has no position table).  attn_variant == 8 with a
-                             table is UCOD_EINVAL (the fp8 epilogue writes e4m3 Q / K straight from the GEMM drain), and so are the training-pass drivers
-                             (ucod_vit_forward_train* / _backward* / _forward_lora_infer*: attention backward would need the inverse rotation of dq / dk). */
+                             table is UCOD_EINVAL (the fp8 epilogue writes e4m3 Q / K straight from the GEMM drain); the training-pass drivers
+                             (ucod_vit_forward_train* / _backward* / _forward_lora_infer*) take a table only with ucod_vit_train_desc.allow_rope = 1. */
 } ucod_vit_desc;
 /* Rotary position embedding of DINOv3 (transformers modeling_dinov3_vit.py: apply_rotary_pos_emb with rotate_half) on the Q and K thirds of the PATCH rows of a
  * QKV buffer [B tok, 3 heads 64], in place.  tok = 1 + n_reg + n; token row t >= 1 + n_reg of an image is patch p = t - 1 - n_reg and uses table row p of
@@ -413,6 +415,13 @@ typedef struct {
 #define UCOD_ROPE_ELEM_HALF 0
 #define UCOD_ROPE_ELEM_F32 1
 int ucod_rope_qk(void* qkv, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, void* stream);
+/* The same with a row pitch and a direction (backbone-backward mode).  buf [B tok, ld] with ld >= 3 heads 64 elements and ld * sizeof(element) a multiple of 16:
+ * columns 0 .. 2 D - 1 of the patch rows are rotated, the V third, the CLS / register rows and every column at or beyond 3 D (the 64 LoRA columns of dqkv_aug) are
+ * neither read nor written.  inverse = 0: ucod_rope_qk (which is this call with ld = 3 D).  inverse = 1: the transpose, i.e. the sine negated,
+ *   out[i] = v[i] cos[i] + v[i + 32] sin[i],  out[i + 32] = v[i + 32] cos[i] - v[i] sin[i]
+ * -- what takes the cotangents of rotated q / k back to those of the projection outputs.  f32 arithmetic, one rounding.  Every other refusal as ucod_rope_qk;
+ * UCOD_EINVAL before any launch. */
+int ucod_rope_qk_ld(void* buf, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, int ld, int inverse, void* stream);
 size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d);
 int ucod_vit_forward(const ucod_vit_desc* d, const void* const* table_host, const float* img, float* key_out,
                      void* workspace, size_t workspace_bytes, void* stream);
@@ -546,6 +555,10 @@ typedef struct {
   float lora_scaling;            /* lora_alpha / r = 4 / 2 */
   float lora_dropout;            /* full_model.py:50: 0.05 in the reference config; 0 = off (eval mode) */
   unsigned long long seed;       /* dropout seed of THIS step: forward_train and backward must be given the same value */
+  int allow_rope;                /* 1: the passes take vit.rope (DINOv3): every layer but the last runs one ucod_rope_qk_ld(qkv, HALF, rope, ..., 3 D, 0) between the QKV GEMM
+                                    and attention -- in the training pass on the SAVED qkv -- and ucod_vit_backward* one ucod_rope_qk_ld(dqkv_aug, HALF, rope, ..., 3 D + 64, 1)
+                                    between ucod_attention_bwd and the LoRA-gradient kernel; the last layer's key hook stays in front of any rotation.  0 (every caller
+                                    that zero-fills the descriptor): a non-NULL vit.rope is UCOD_EINVAL, sizes 0.  With vit.rope == NULL the flag changes nothing. */
 } ucod_vit_train_desc;
 size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t);
 int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* table_host, const void* const* train_table_host,

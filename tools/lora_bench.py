@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Backbone-backward (LoRA) mode at the headline size: forward_train + backward of DINOv2 ViT-B/14 @518 (or, sixth argument dinov2_vitg14, of ViT-g/14 with its
-SwiGLU MLP), per-class kernel times.   lora_bench.py [B [steps [streams [dropout [resid [arch [targets]]]]]]]
-``targets``: comma list of LoRA target modules (default: the engine's query,key,value), e.g. query,key,value,fc1 or query,key,value,weights_in on ViT-g."""
+SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both passes, @512), per-class kernel times.
+    lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side]]]]]]]]
+``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
+on ViT-g.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ucod_dpl_amd import native as N
 from ucod_dpl_amd.vit_engine import ViTLoRAEngine
-from ucod_dpl_amd.data.utils.feature_extractor import random_state_dict
+from ucod_dpl_amd.data.utils.feature_extractor import random_state_dict, ARCHS, DINOV3_ARCHS, SWIGLU_ARCHS
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -16,18 +18,25 @@ lib = N.load()
 drop = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0   # the reference trains with lora_dropout 0.05 (configs/model/UCOD_DPL.py)
 resid = sys.argv[5] if len(sys.argv) > 5 else "auto"      # residual stream of the training pass: auto (fp16 with bf16 operands) / f32
 arch = sys.argv[6] if len(sys.argv) > 6 else "dinov2_vitb14"
-if arch not in ("dinov2_vitb14", "dinov2_vitg14", "dinov2_vitb14_reg", "dinov2_vitg14_reg"):        # (_reg: DINOv2 with registers, 4 register tokens per image)
-    sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14 (or their _reg forms), got {arch}")
+v3 = arch in DINOV3_ARCHS                                 # DINOv3: rotary embedding in both passes (allow_rope), patch 16, eps 1e-5
+if arch not in ("dinov2_vitb14", "dinov2_vitg14", "dinov2_vitb14_reg", "dinov2_vitg14_reg") and not v3:        # (_reg: DINOv2 with registers, 4 register tokens per image)
+    sys.exit(f"arch must be dinov2_vitb14 or dinov2_vitg14 (or their _reg forms) or one of {sorted(DINOV3_ARCHS)}, got {arch}")
 giant = arch.startswith("dinov2_vitg14")
-heads = 24 if giant else 12
+heads, patch = ARCHS[arch][1], ARCHS[arch][3]
 targets = sys.argv[7].split(",") if len(sys.argv) > 7 and sys.argv[7] else None
+side = int(sys.argv[8]) if len(sys.argv) > 8 else (512 if v3 else 518)
+if side % patch:
+    sys.exit(f"the image side must be a multiple of the patch size {patch}, got {side}")
+grid, n_lead = side // patch, 1 + (DINOV3_ARCHS[arch] if v3 else 4 if arch.endswith("_reg") else 0)
 kw = {} if targets is None else dict(target_modules=targets)
-eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant, **kw)
+if v3:
+    kw.update(allow_rope=True, eps=1e-5)
+eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
     print(f"targets {targets}: arena [{eng.L}, {eng.lora.shape[1]}]")
 eng.train_streams = streams
-x = torch.randn(B, 3, 518, 518, device="cuda")
-dkey = torch.randn(B, 64 * heads, 37, 37, device="cuda")
+x = torch.randn(B, 3, side, side, device="cuda")
+dkey = torch.randn(B, 64 * heads, grid, grid, device="cuda")
 for _ in range(2):
     eng.forward_train(x); eng.backward(dkey)
 torch.cuda.synchronize()
@@ -56,7 +65,7 @@ for name, c, t in sorted(rows, key=lambda r: -r[2]):
 print(f"  sum {sum(r[2] for r in rows):.2f} ms")
 if getattr(eng, "mlp_target", None) is not None:
     # the MLP module's gradient kernel against the bytes it has to move: one pass over dpre [M, N1] and one over h2_aug [M, D+64], both bf16 (per two ranks)
-    M = B * 1370
+    M = B * (n_lead + grid * grid)
     byts = (M * eng.N1 * 2 + M * (eng.D + 64) * 2) * ((eng.r + 1) // 2)
     for name, c, t in rows:
         if name == "lora_mlp_grad":
@@ -64,7 +73,7 @@ if getattr(eng, "mlp_target", None) is not None:
 if giant:
     # the two SwiGLU training launches alone at this pass's shapes, and beside them (orientation) the launches they extend: UCOD_EPI_BIAS_SWIGLU_BF16 at (M, 2F, D),
     # which the SAVE form extends by one [M, 2F] store, and UCOD_EPI_GELU_BWD_BF16 at (M, F, D), which reads and writes half the bytes of the SwiGLU dgrad drain
-    M, D, F = B * 1370, eng.D, eng.F
+    M, D, F = B * (n_lead + grid * grid), eng.D, eng.F
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g).bfloat16()  # noqa: E731
     A, w_in, w_out_t, b_in = rnd(M, D), rnd(2 * F, D) * D ** -0.5, rnd(F, D) * D ** -0.5, torch.randn(2 * F, device="cuda", generator=g)

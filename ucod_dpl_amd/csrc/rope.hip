@@ -7,6 +7,10 @@
 // for f32) -- and the matching 8 cosines and 8 sines of the token's table row (f32 [n, 64] = cos[0:32] | sin[0:32]; 256 KB at n = 1024: it lives in L2).  Four
 // lanes cover a head, 8 * heads lanes the Q and K thirds of a token row; the V third, the CLS row and the register rows are never addressed.  No LDS; the
 // grid is capped and grid-strided.
+//
+// ucod_rope_qk_ld is the same kernel with a row pitch and a direction, for backbone-backward mode: the transpose (the table with the sine negated) takes the
+// cotangents dq / dk of the rotated operands, in the first 3 D columns of dqkv_aug [B tok, 3 D + 64], back to those of the projection outputs.  The direction is a
+// template parameter: the forward instantiations compute exactly what they did.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
 
@@ -17,22 +21,24 @@ constexpr int ROPE_MAX_BLOCKS = 2048;                              // 8 blocks o
 
 struct Rot8 { float lo[8], hi[8]; };
 
-// out_lo = lo cos - hi sin, out_hi = hi cos + lo sin (f32; the products of the second term are rounded, the sum is one fma)
+// out_lo = lo cos - hi sin, out_hi = hi cos + lo sin (f32; the products of the second term are rounded, the sum is one fma); INV: the transpose, sin -> -sin
+template <bool INV>
 __device__ __forceinline__ void rotate8(Rot8& v, const float* __restrict__ cs) {
   const f32x4 c0 = *(const f32x4*)cs, c1 = *(const f32x4*)(cs + 4), s0 = *(const f32x4*)(cs + 32), s1 = *(const f32x4*)(cs + 36);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float c = e < 4 ? c0[e] : c1[e - 4], s = e < 4 ? s0[e] : s1[e - 4];
+    const float c = e < 4 ? c0[e] : c1[e - 4], s0e = e < 4 ? s0[e] : s1[e - 4], s = INV ? -s0e : s0e;
     const float a = v.lo[e], b = v.hi[e];
     v.lo[e] = a * c - b * s;
     v.hi[e] = b * c + a * s;
   }
 }
 
-template <bool F32>
-__global__ __launch_bounds__(ROPE_BLOCK) void rope_qk_kernel(void* __restrict__ qkv, const float* __restrict__ cos_sin, unsigned items, int tok, int n_reg, int np, int heads) {
+template <bool F32, bool INV>
+__global__ __launch_bounds__(ROPE_BLOCK) void rope_qk_kernel(void* __restrict__ qkv, const float* __restrict__ cos_sin, unsigned items, int tok, int n_reg, int np, int heads,
+                                                             int ld_) {
   const unsigned per_row = 8u * heads;                             // lanes per token row: (Q | K) x heads x 4 column groups of 8
-  const size_t ld = (size_t)192 * heads;                           // 3 D
+  const size_t ld = (size_t)ld_;                                   // row pitch in elements, >= 3 D: columns at or beyond 2 D are never addressed
   // (items < 2^31 and the stride <= 2^19: the 32-bit index cannot wrap)
   for (unsigned i = blockIdx.x * ROPE_BLOCK + threadIdx.x; i < items; i += gridDim.x * ROPE_BLOCK) {
     const unsigned row = i / per_row, within = i - row * per_row;
@@ -46,7 +52,7 @@ __global__ __launch_bounds__(ROPE_BLOCK) void rope_qk_kernel(void* __restrict__ 
       const f32x4 l0 = *(const f32x4*)q, l1 = *(const f32x4*)(q + 4), h0 = *(const f32x4*)(q + 32), h1 = *(const f32x4*)(q + 36);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v.lo[e] = l0[e]; v.lo[4 + e] = l1[e]; v.hi[e] = h0[e]; v.hi[4 + e] = h1[e]; }
-      rotate8(v, cs);
+      rotate8<INV>(v, cs);
       *(f32x4*)q = (f32x4){v.lo[0], v.lo[1], v.lo[2], v.lo[3]};
       *(f32x4*)(q + 4) = (f32x4){v.lo[4], v.lo[5], v.lo[6], v.lo[7]};
       *(f32x4*)(q + 32) = (f32x4){v.hi[0], v.hi[1], v.hi[2], v.hi[3]};
@@ -59,7 +65,7 @@ __global__ __launch_bounds__(ROPE_BLOCK) void rope_qk_kernel(void* __restrict__ 
         ucod::unpack_h2(l[e], v.lo[2 * e], v.lo[2 * e + 1]);
         ucod::unpack_h2(h[e], v.hi[2 * e], v.hi[2 * e + 1]);
       }
-      rotate8(v, cs);
+      rotate8<INV>(v, cs);
       u32x4 ol, oh;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -74,16 +80,31 @@ __global__ __launch_bounds__(ROPE_BLOCK) void rope_qk_kernel(void* __restrict__ 
 
 }  // namespace
 
-extern "C" int ucod_rope_qk(void* qkv, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, void* stream) {
-  if (!qkv || !cos_sin || (elem != UCOD_ROPE_ELEM_HALF && elem != UCOD_ROPE_ELEM_F32) || B <= 0 || tok <= 0 || heads <= 0 || n_reg < 0 || n_reg >= tok - 1) return UCOD_EINVAL;
-  if ((((uintptr_t)qkv) | ((uintptr_t)cos_sin)) & 15) return UCOD_EINVAL;      // 16-byte loads and stores (the row pitch 3 D elements is a multiple of 16 bytes)
+extern "C" int ucod_rope_qk_ld(void* buf, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, int ld, int inverse, void* stream) {
+  if (!buf || !cos_sin || (elem != UCOD_ROPE_ELEM_HALF && elem != UCOD_ROPE_ELEM_F32) || B <= 0 || tok <= 0 || heads <= 0 || n_reg < 0 || n_reg >= tok - 1) return UCOD_EINVAL;
+  if (inverse != 0 && inverse != 1) return UCOD_EINVAL;
+  if (heads > 0x7FFFFFFF / 192 || ld < 192 * heads) return UCOD_EINVAL;                                    // ld >= 3 D
+  if (((size_t)ld * (elem == UCOD_ROPE_ELEM_F32 ? 4 : 2)) & 15) return UCOD_EINVAL;                          // every row starts on a 16-byte boundary
+  if ((((uintptr_t)buf) | ((uintptr_t)cos_sin)) & 15) return UCOD_EINVAL;      // 16-byte loads and stores
   const int np = tok - 1 - n_reg;
   const long items = (long)B * np * heads * 8;
   if (items > 0x7FFFFFFFL) return UCOD_EINVAL;                     // (the kernel's lane index is 32 bits; element offsets are 64)
   const long blocks = (items + ROPE_BLOCK - 1) / ROPE_BLOCK;
-  const int grid = (int)(blocks < ROPE_MAX_BLOCKS ? blocks : ROPE_MAX_BLOCKS);
-  if (elem == UCOD_ROPE_ELEM_F32) hipLaunchKernelGGL(rope_qk_kernel<true>, dim3(grid), dim3(ROPE_BLOCK), 0, (hipStream_t)stream, qkv, cos_sin, (unsigned)items, tok, n_reg, np, heads);
-  else hipLaunchKernelGGL(rope_qk_kernel<false>, dim3(grid), dim3(ROPE_BLOCK), 0, (hipStream_t)stream, qkv, cos_sin, (unsigned)items, tok, n_reg, np, heads);
+  const dim3 grid((unsigned)(blocks < ROPE_MAX_BLOCKS ? blocks : ROPE_MAX_BLOCKS)), block(ROPE_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned n = (unsigned)items;
+  if (elem == UCOD_ROPE_ELEM_F32) {
+    if (inverse) hipLaunchKernelGGL((rope_qk_kernel<true, true>), grid, block, 0, s, buf, cos_sin, n, tok, n_reg, np, heads, ld);
+    else hipLaunchKernelGGL((rope_qk_kernel<true, false>), grid, block, 0, s, buf, cos_sin, n, tok, n_reg, np, heads, ld);
+  } else {
+    if (inverse) hipLaunchKernelGGL((rope_qk_kernel<false, true>), grid, block, 0, s, buf, cos_sin, n, tok, n_reg, np, heads, ld);
+    else hipLaunchKernelGGL((rope_qk_kernel<false, false>), grid, block, 0, s, buf, cos_sin, n, tok, n_reg, np, heads, ld);
+  }
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+
+extern "C" int ucod_rope_qk(void* qkv, int elem, const float* cos_sin, int B, int tok, int n_reg, int heads, void* stream) {
+  if (heads <= 0 || heads > 0x7FFFFFFF / 192) return UCOD_EINVAL;
+  return ucod_rope_qk_ld(qkv, elem, cos_sin, B, tok, n_reg, heads, 192 * heads, 0, stream);      // ld = 3 D (a multiple of 16 bytes in either type), forward direction
 }

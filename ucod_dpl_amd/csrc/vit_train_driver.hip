@@ -9,6 +9,8 @@
 // The _lora_mlp forms take the per-layer table of a LoRA module on the MLP input projection (fc1 / weights_in; full_model.py:47-72 hands target_modules to peft):
 // LayerNorm 2 then writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against fc1_w_aug, and the backward recomputes h2_aug from the
 // saved residual stream, takes the module's gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the LayerNorm-2 backward.  A NULL table is the _mlp form.
+// DINOv3 (vit.rope with allow_rope = 1): every layer but the last rotates q / k of the patch rows in place between the QKV GEMM and attention (the last layer's key hook
+// is taken in front of any rotation), and the backward applies the transposed rotation to dq / dk behind ucod_attention_bwd (ucod_rope_qk_ld).  Plans do not change.
 // No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
@@ -33,7 +35,7 @@ bool valid_qkv(const ucod_vit_train_desc* t) {
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
-         d->rope == nullptr &&                                      // DINOv3: attention backward would need the inverse rotation of dq / dk -- not built, refused
+         (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
          d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
 }
 
@@ -153,6 +155,8 @@ extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int
     float* lse = (float*)(ws + p.lse + p.s_lse * l);
     void* pre = ws + p.pre + p.s_pre * l;
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
+    // DINOv3: q and k of the patch rows are rotated in the SAVED buffer, so that the backward's recomputed scores see the operands attention saw
+    if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
     RUN(ucod_attention_fwd_lse(qkv, att, lse, d->B, tok, d->heads, stream));
     RUN(ucod_gemm_bf16(epi_resid, att, W[4], x_mid, M, D, D, (const float*)W[5], (const float*)W[6], x_in, nullptr, tok, gv, stream));
     if (TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug (its own mask: key L + l)
@@ -197,7 +201,7 @@ bool valid_infer(const ucod_vit_train_desc* t) {
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
          t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&
-         d->rope == nullptr;                                        // (DINOv3 runs on the frozen engines only)
+         (d->rope == nullptr || t->allow_rope == 1);                // (DINOv3: as valid_qkv)
 }
 IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
   const ucod_vit_desc* d = &t->vit;
@@ -266,6 +270,7 @@ extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t
       break;
     }
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
+    if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
     RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, 0.f, 0, stream));
     RUN(ucod_gemm_bf16(epi_resid, a, W[4], x, M, D, D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
     if (TM) {
@@ -392,6 +397,9 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_attention_bwd(qkv, att, da, lse, delta, dqkv, KQ, d->B, tok, d->heads, stream));
+    // DINOv3: dq / dk above are the cotangents of the ROTATED operands; the LoRA-gradient kernel and the QKV dgrad want those of the projection outputs,
+    // d(pre) = R^T d(post) -- the same table with the sine negated, on the q | k thirds of dqkv_aug (attention_bwd.hip stores dq at 0, dk at D, dv at 2 D)
+    if (d->rope) RUN(ucod_rope_qk_ld(dqkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, KQ, 1, stream));
     RUN(qkv_side(l));
     if (l > 0) {
       const void* const* Wp = T + 4 + UCOD_VIT_LAYER_STRIDE * (l - 1);

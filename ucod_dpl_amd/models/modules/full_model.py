@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from ... import ops
-from ...vit_engine import ViTLoRAEngine
+from ...vit_engine import ViTLoRAEngine, is_dinov3
 from ..uscod import baseline
 
 
@@ -50,16 +50,24 @@ class LoRABackbone(nn.Module):
         ``data.utils.feature_extractor.backbone`` at ``precision`` (None: the fp16 folded default; "bf16"; "split3" / "f32eq" ...).  This module is left as it is."""
         from ...data.utils.feature_extractor import backbone
         eng = self.engine
+        if eng.rope:
+            engine_kw.setdefault("rope_theta", eng.rope_theta)     # (a property of the checkpoint that its state dict does not hold)
         return backbone.from_state_dict(eng.merged_state_dict(), eng.heads, eps=eng.eps, device=eng.device, precision=precision, **engine_kw)
 
 
 ADAPTER_PREFIX = "base_model.model.ViT.encoder.layer."      # peft's key prefix for the reference's wrapper (ViTLoraWrapper holds the HF model as ``ViT``)
+ADAPTER_ROOT = "base_model.model.ViT."                      # ... in front of the checkpoint's own layer path (a DINOv3 checkpoint: ``model.layer.`` / ``layer.``)
 ADAPTER_WEIGHTS, ADAPTER_CONFIG = "adapter_model.safetensors", "adapter_config.json"
 
 
+def _adapter_prefix(engine):
+    """(read with defaults, like ``lora_dropout`` below: anything with the engine's LoRA interface and DINOv2's names can be saved)"""
+    return ADAPTER_ROOT + getattr(engine, "_layer_path", "encoder.layer.")                   # (DINOv2: ADAPTER_PREFIX)
+
+
 def _adapter_targets(engine):
-    """target_modules of an engine as peft lists them: the leaf names"""
-    names = [n for n, on in zip(("query", "key", "value"), engine.targets) if on]
+    """target_modules of an engine as peft lists them: the leaf names (query / key / value; q_proj / k_proj / v_proj on a DINOv3 checkpoint)"""
+    names = [n for n, on in zip(getattr(engine, "_qkv_names", ("query", "key", "value")), engine.targets) if on]
     return names + ([engine.mlp_target] if engine.mlp_target is not None else [])
 
 
@@ -70,7 +78,7 @@ def save_lora_adapter(engine, folder):
     peft is not a dependency of this package: the layout is restated from peft's documented adapter format and has not been checked against the library."""
     from safetensors.torch import save_file
     os.makedirs(folder, exist_ok=True)
-    sd = engine.lora_state_dict(prefix=ADAPTER_PREFIX)
+    sd = engine.lora_state_dict(prefix=_adapter_prefix(engine))
     save_file({k: v.detach().cpu().contiguous() for k, v in sd.items()}, os.path.join(folder, ADAPTER_WEIGHTS))
     alpha = float(engine.scaling) * int(engine.r)
     cfg = {"peft_type": "LORA", "r": int(engine.r), "lora_alpha": int(alpha) if alpha == int(alpha) else alpha,
@@ -91,15 +99,18 @@ def load_lora_adapter(engine, folder):
     for k in ("r", "target_modules", "lora_alpha"):
         if mine[k] != theirs[k]:
             raise ValueError(f"LoRA adapter {folder}: {k} is {theirs[k]!r} in {ADAPTER_CONFIG}, {mine[k]!r} in the engine")
-    engine.load_lora_state_dict(load_file(os.path.join(folder, ADAPTER_WEIGHTS)), prefix=ADAPTER_PREFIX)
+    engine.load_lora_state_dict(load_file(os.path.join(folder, ADAPTER_WEIGHTS)), prefix=_adapter_prefix(engine))
     return engine
 
 
-def load_lora(config, state_dict, heads, device="cuda", generator=None):
+def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None):
     """models/modules/full_model.py:47-72.  r == 0 is refused (the reference returns the bare model; use ``backbone`` then).  Either MLP kind of DINOv2 is taken:
     a SwiGLU checkpoint (facebook/dinov2-giant) trains through the engine's SwiGLU backward (``allow_swiglu``).  ``target_modules`` (:54,67: handed to peft as it
     is) may name any non-empty subset of query / key / value and the MLP input projection (``fc1``; ``weights_in`` on a SwiGLU checkpoint), matched by peft's
-    suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets)."""
+    suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets).
+    A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
+    100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
+    otherwise, as ``backbone.from_state_dict``."""
     r = getattr(config, "r", 2)
     if r == 0:
         raise ValueError("r == 0: no LoRA -- use data.utils.feature_extractor.backbone for the frozen path")
@@ -110,8 +121,11 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None):
     if getattr(config, "bias", "none") != "none":
         raise NotImplementedError("LoRA bias modes other than 'none' are not built")
     drop = float(getattr(config, "lora_dropout", 0.05))                      # :50
-    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
-                                      target_modules=targets))
+    if eps is None:
+        eps = 1e-5 if is_dinov3(state_dict) else 1e-6
+    return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, eps=eps, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
+                                      target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
+                                      rope_theta=float(getattr(config, "rope_theta", 100.0))))
 
 
 class full_model(nn.Module):

@@ -59,7 +59,8 @@ class VitDesc(C.Structure):
 
 
 class VitTrainDesc(C.Structure):
-    _fields_ = [("vit", VitDesc), ("lora_r", ci), ("lora_scaling", cf), ("lora_dropout", cf), ("seed", C.c_ulonglong)]
+    _fields_ = [("vit", VitDesc), ("lora_r", ci), ("lora_scaling", cf), ("lora_dropout", cf), ("seed", C.c_ulonglong),
+                ("allow_rope", ci)]       # (zero-filled: a rotary table in ``vit`` is refused by the training-pass drivers unless this is 1)
 
 
 class LoraDropout(C.Structure):
@@ -125,6 +126,8 @@ SIGNATURES = {
     "ucod_gemm_bf16": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp]),
     # DINOv3: rotary position embedding on the Q and K thirds of the patch rows of a QKV buffer, in place (csrc/rope.hip); elem = ROPE_ELEM_HALF / ROPE_ELEM_F32
     "ucod_rope_qk": (ci, [vp, ci, vp, ci, ci, ci, ci, vp]),
+    # the same with a row pitch (elements) and a direction (1 = the transpose: cotangents of rotated q / k back to the projection outputs')
+    "ucod_rope_qk_ld": (ci, [vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]),
     # DINOv2 with registers: the row-mapped drains, leading-row kernels, key-gradient scatter and CLS attention row for tok = 1 + n_reg + n tokens per image
     "ucod_gemm_bf16_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_gemm_bf16_stats_reg": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, ci, vp]),

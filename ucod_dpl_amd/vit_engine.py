@@ -822,6 +822,58 @@ def lora_targets(target_modules=None, mlp="gelu", n_layers=1):
     return qkv, (mlp_in if "mlp." + mlp_in in per_layer[0] else None)
 
 
+_QKV3 = ("q_proj", "k_proj", "v_proj")                       # DINOv3ViTAttention's projections, in the order of _QKV
+_REFUSED3 = {
+    "o_proj": "its input is written by the attention kernel, which has no leading-dimension argument for the 64 LoRA columns",
+    "down_proj": "its input is written by the MLP input GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
+    "up_proj": "the MLP input projection of a DINOv3 checkpoint is not built yet (on the gated MLP it is one of two peft modules, with gate_proj, on the one fused "
+               "weights_in GEMM)",
+    "gate_proj": "the gated MLP's input is two peft modules (gate_proj, up_proj) on the one fused weights_in GEMM: a LoRA module on one of them alone is not built",
+    "patch_embeddings": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
+}
+_DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", "weights_out", "projection")
+
+
+def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer."):
+    """``lora_targets`` for a DINOv3 checkpoint, whose modules are ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj``
+    too): any non-empty subset of q_proj / k_proj / v_proj by peft's suffix rule, None = all three.  Returns the (q, k, v) booleans; no MLP module is built."""
+    if target_modules is None:
+        return (True, True, True)
+    if isinstance(target_modules, str):
+        raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
+    targets = list(target_modules)
+    if not targets:
+        raise ValueError("target_modules is empty: name at least one of q_proj / k_proj / v_proj")
+    mods = ["attention." + n for n in _QKV3 + ("o_proj",)] + ["mlp.up_proj", "mlp.down_proj"] + (["mlp.gate_proj"] if gated else [])
+    names = [f"{layer_path}{i}.{m}" for i in range(n_layers) for m in mods] + ["embeddings.patch_embeddings"]
+    hit = set()
+    for t in targets:
+        if not isinstance(t, str) or not t:
+            raise ValueError(f"target_modules entry {t!r} is not a module name")
+        found = [n for n in names if n == t or n.endswith("." + t)]
+        last = t.rsplit(".", 1)[-1]
+        if not found:
+            if last in _DINOV2_LEAVES:
+                raise ValueError(f"target module {t!r} is a DINOv2 name: a DINOv3 checkpoint's attention projections are q_proj / k_proj / v_proj "
+                                 f"({layer_path}{{i}}.attention.{{q,k,v}}_proj)")
+            raise NotImplementedError(f"LoRA target module {t!r} is not built: {_REFUSED3.get(last, 'no Linear module of the backbone has that name')}")
+        for n in found:
+            leaf = n.rsplit(".", 1)[-1]
+            if leaf in _REFUSED3:
+                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {_REFUSED3[leaf]}")
+            hit.add(n)
+    per_layer = [{n[len(f"{layer_path}{i}."):] for n in hit if n.startswith(f"{layer_path}{i}.")} for i in range(n_layers)]
+    if any(pl != per_layer[0] for pl in per_layer):
+        raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
+    return tuple("attention." + n in per_layer[0] for n in _QKV3)
+
+
+def _dinov3_paths(sd):
+    """(prefix in front of ``embeddings.``, layer path behind it) of a DINOv3 state dict: ("", "model.layer.") for transformers 5.x, "layer." for 4.56."""
+    pref = next(k[:-len("embeddings.patch_embeddings.weight")] for k in sd if k.endswith("embeddings.patch_embeddings.weight"))
+    return pref, ("model.layer." if any(k.startswith(pref + "model.layer.") for k in sd) else "layer.")
+
+
 class ViTLoRAEngine(ViTEngine):
 
     """Backbone-backward mode: the frozen ViT with peft-style LoRA on query / key / value of every
@@ -837,21 +889,36 @@ class ViTLoRAEngine(ViTEngine):
     ``target_modules`` (``lora_targets``): a subset of query / key / value keeps that block and holds the untargeted projections' A and B at zero -- their
     gradients are then zero by structure (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero.  With the MLP
     input projection (``fc1`` / ``weights_in``) the row grows to [6*r*D | A_m (r x D) | B_m (N1 x r)], N1 = F (GELU) or 2F in the engine's padded, interleaved row
-    order (SwiGLU), and the passes run the _lora_mlp entry points (include/ucod_dpl.h).  None = query / key / value: the engine as it always was."""
+    order (SwiGLU), and the passes run the _lora_mlp entry points (include/ucod_dpl.h).  None = query / key / value: the engine as it always was.
+
+    A DINOv3 checkpoint (``allow_rope=True``) has its own module names -- ``{model.,}layer.{i}.attention.{q,k,v}_proj`` -- which ``target_modules``, the state dicts,
+    the merges and the adapter folder use; the arena layout is the same (q | k | v).  No MLP module is built for it yet."""
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto", allow_swiglu=False, target_modules=None):
+                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
-        (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on."""
+        (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
+        ``allow_rope``: accept a DINOv3 checkpoint (rotary position embedding; ``rope_theta`` as ``ViTEngine``).  Its passes rotate q / k of the patch rows between
+        the QKV GEMM and attention and apply the transposed rotation to dq / dk behind attention backward (include/ucod_dpl.h: ucod_rope_qk_ld,
+        ucod_vit_train_desc.allow_rope).  Its modules are ``{model.,}layer.{i}.attention.{q,k,v}_proj`` (``lora_targets_dinov3``); a gated-MLP checkpoint
+        (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``."""
         canon = normalize_state_dict(state_dict)
-        if canon.get("rope"):
-            raise NotImplementedError("backbone-backward (LoRA) mode is not built for a DINOv3 checkpoint (rotary position embedding, RoPE): attention backward would "
-                                      "need the inverse rotation of dq and dk; the frozen-backbone engines (ViTEngine / SplitViTEngine) take it")
+        if canon.get("rope") and not allow_rope:
+            raise NotImplementedError("backbone-backward (LoRA) mode takes a DINOv3 checkpoint (rotary position embedding, RoPE: the passes rotate q / k and "
+                                      "rotate dq / dk back) only with allow_rope=True")
+        self.allow_rope = bool(allow_rope)
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
         mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
-        self.targets, self.mlp_target = lora_targets(target_modules, mlp_kind, len(canon["layers"]))
+        if canon.get("rope"):
+            # the checkpoint's own names: layer path, module path below it, leaf names (what lora_state_dict, the merges and the adapter folder use)
+            self._layer_path = _dinov3_paths(state_dict)[1]
+            self._qkv_names, self._qkv_dir = _QKV3, "attention."
+            self.targets, self.mlp_target = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path), None
+        else:
+            self._layer_path, self._qkv_names, self._qkv_dir = "encoder.layer.", _QKV, "attention.attention."
+            self.targets, self.mlp_target = lora_targets(target_modules, mlp_kind, len(canon["layers"]))
         self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
         if mlp_kind == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
@@ -860,7 +927,7 @@ class ViTLoRAEngine(ViTEngine):
         # resid: as ViTEngine ("auto" = the fp16 residual stream with bf16 operands).  Round 4: the training pass SAVES the stream in that
         # type and LayerNorm backward reads it (ucod_layernorm_bwd_ex); resid="f32" keeps the round-3 path.
         super().__init__(state_dict, heads, eps=eps, device=device, full_last_layer=False, gemm_variant=gemm_variant, attn_variant=2, resid=resid,
-                         half="bf16")                             # (the backbone-backward entry points exist in the bf16 build only: include/ucod_dpl.h, ucod_half_name)
+                         half="bf16", rope_theta=rope_theta)      # (the backbone-backward entry points exist in the bf16 build only: include/ucod_dpl.h, ucod_half_name)
         if not 0.0 <= lora_dropout < 1.0:
             raise ValueError("lora_dropout must be in [0, 1)")
         if 0.0 < lora_dropout < 1.0 / 1024:
@@ -921,17 +988,19 @@ class ViTLoRAEngine(ViTEngine):
         rD = self.r * self.D
         return slice(self.qkv_numel, self.qkv_numel + rD), slice(self.qkv_numel + rD, self.qkv_numel + rD + self.N1 * self.r)
 
-    def lora_state_dict(self, grads=False, prefix="encoder.layer."):
+    def lora_state_dict(self, grads=False, prefix=None):
         """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
-        projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded."""
+        projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded.  A DINOv3
+        checkpoint: {model.,}layer.{i}.attention.{q,k,v}_proj.lora_{A,B}.weight, the checkpoint's own layer path.  ``prefix`` replaces the layer path."""
+        prefix = self._layer_path if prefix is None else prefix
         src = self.lora_grad if grads else self.lora
         out = {}
         for i in range(self.L):
-            for p, name in enumerate(_QKV):
+            for p, name in enumerate(self._qkv_names):
                 if not self.targets[p]:
                     continue
                 sa, sb = self._slices(p)
-                base = f"{prefix}{i}.attention.attention.{name}."
+                base = f"{prefix}{i}.{self._qkv_dir}{name}."
                 out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
                 out[base + "lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
             if self.mlp_target is not None:
@@ -942,9 +1011,10 @@ class ViTLoRAEngine(ViTEngine):
                 out[base + "lora_B.weight"] = lora_b_from_engine(b, self._F0) if self.mlp == N.UCOD_MLP_SWIGLU else b.clone()
         return out
 
-    def load_lora_state_dict(self, sd, prefix="encoder.layer."):
+    def load_lora_state_dict(self, sd, prefix=None):
         """The inverse of ``lora_state_dict``.  A LoRA key of a module this engine does not target is refused (its matrices are held at zero)."""
-        names = [f"attention.attention.{name}." for p, name in enumerate(_QKV) if self.targets[p]]
+        prefix = self._layer_path if prefix is None else prefix
+        names = [f"{self._qkv_dir}{name}." for p, name in enumerate(self._qkv_names) if self.targets[p]]
         names += [f"mlp.{self.mlp_target}."] if self.mlp_target is not None else []
         want = {f"{prefix}{i}.{n}lora_{ab}.weight" for i in range(self.L) for n in names for ab in "AB"}
         extra = sorted(k for k in sd if ".lora_" in k and k.startswith(prefix) and k not in want)
@@ -953,11 +1023,11 @@ class ViTLoRAEngine(ViTEngine):
                            + (" ..." if len(extra) > 4 else ""))
         take = lambda k: sd[k].to(self.device, torch.float32)  # noqa: E731
         for i in range(self.L):
-            for p, name in enumerate(_QKV):
+            for p, name in enumerate(self._qkv_names):
                 if not self.targets[p]:
                     continue
                 sa, sb = self._slices(p)
-                base = f"{prefix}{i}.attention.attention.{name}."
+                base = f"{prefix}{i}.{self._qkv_dir}{name}."
                 self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
                 self.lora[i, sb] = take(base + "lora_B.weight").reshape(-1)
             if self.mlp_target is not None:
@@ -998,6 +1068,7 @@ class ViTLoRAEngine(ViTEngine):
         t.vit = self._desc(B, H, W)
         t.lora_r, t.lora_scaling = self.r, self.scaling
         t.lora_dropout, t.seed = self._drop_p(), seed
+        t.allow_rope = int(self.allow_rope)                        # (with a NULL table -- every checkpoint but DINOv3 -- the drivers never look at it)
         return t
 
     def _tables(self, gh, gw, grad):
@@ -1123,15 +1194,20 @@ class ViTLoRAEngine(ViTEngine):
 
     # ---- merging: the way out of LoRA mode ---------------------------------------------------------------------------
     def _targeted(self):
-        """(module name below ``encoder.layer.{i}.``, its index among query / key / value or None for the MLP input projection) of every targeted module"""
-        mods = [(f"attention.attention.{name}", p) for p, name in enumerate(_QKV) if self.targets[p]]
+        """(module name below the layer path ``encoder.layer.{i}.``, its index among query / key / value or None for the MLP input projection) of every targeted module"""
+        mods = [(f"{self._qkv_dir}{name}", p) for p, name in enumerate(self._qkv_names) if self.targets[p]]
         return mods + ([(f"mlp.{self.mlp_target}", None)] if self.mlp_target is not None else [])
 
     @staticmethod
     def _hf_prefix(sd):
+        """What stands in front of the layer path in ``sd``'s names, with that path: ``encoder.layer.`` behind "", "dinov2." or "vit."; a DINOv3 state dict's
+        own ``{model.,}layer.``."""
+        if is_dinov3(sd):
+            pref, lay = _dinov3_paths(sd)
+            return pref + lay
         for pref in ("", "dinov2.", "vit."):
             if pref + "encoder.layer.0.attention.attention.query.weight" in sd:
-                return pref
+                return pref + "encoder.layer."
         raise NotImplementedError("merging takes a HuggingFace DINOv2 state dict (encoder.layer.{i}.attention.attention.{query,key,value}): the names "
                                   "target_modules are matched against")
 
@@ -1156,7 +1232,7 @@ class ViTLoRAEngine(ViTEngine):
         swiglu = self.mlp == N.UCOD_MLP_SWIGLU
         for i in range(self.L):
             for name, p in self._targeted():
-                key = f"{pref}encoder.layer.{i}.{name}.weight"
+                key = f"{pref}{i}.{name}.weight"
                 w = base[key]
                 n, k = w.shape
                 if k != self.D:
@@ -1202,6 +1278,8 @@ class ViTLoRAEngine(ViTEngine):
         mine, theirs = (self.D, self.L, self.F, self.heads, self.mlp), (engine.D, engine.L, engine.F, engine.heads, engine.mlp)
         if mine != theirs:
             raise ValueError(f"merge_into: the engines differ in (D, L, F, heads, MLP kind): {mine} here, {theirs} there")
+        if self.rope != engine.rope:
+            raise ValueError("merge_into: one engine is a DINOv3 (rotary) one, the other is not: they were not built from the same checkpoint")
         if self.R != engine.R:
             raise ValueError(f"merge_into: this engine has {self.R} register tokens, the other {engine.R}: they were not built from the same checkpoint")
         if engine.patch_w.device != self.lora.device:
@@ -1213,7 +1291,7 @@ class ViTLoRAEngine(ViTEngine):
         for i in range(self.L):
             row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
             for name, p in self._targeted():
-                w = base[f"{pref}encoder.layer.{i}.{name}.weight"]
+                w = base[f"{pref}{i}.{name}.weight"]
                 if p is not None:
                     n, r0, (sa, sb) = D, p * D, self._slices(p)
                     slot_w, slot_b, slot_c, g, be = N.QKV_W, N.QKV_B, N.QKV_COLSUM, row[N.LN1_G], row[N.LN1_B]
@@ -1230,7 +1308,7 @@ class ViTLoRAEngine(ViTEngine):
                     torch.index_select(hf, 0, self._engine_row_source(), out=w0)
                 else:
                     if tuple(w.shape) != (n, D):
-                        raise ValueError(f"encoder.layer.{i}.{name}.weight has shape {tuple(w.shape)}, expected {(n, D)}")
+                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(n, D)}")
                     buf = self._stage(2 * n * D)
                     w0, merged = buf[:n * D].view(n, D), buf[n * D:2 * n * D].view(n, D)
                     w0.copy_(w.detach())
