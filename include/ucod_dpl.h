@@ -277,7 +277,7 @@ int ucod_cast_f32_bf16(const float* src, void* dst_bf16, size_t n, void* stream)
 
 /* ucod_gemm_bf16 with the training epilogues 6 / 7 (GELU) and 21 / 22 (SwiGLU) (large-tile kernels; N % 8 == 0, K >= 128; 21 / 22 take variant 0 / 1 / 2 (= auto
  * among the large tiles), 9, 10, 13, 14 and refuse the others).  For UCOD_EPI_BIAS_BF16 and
- * UCOD_EPI_BIAS_F32 (either entry point) a NULL bias means a plain product (K >= 128, N % 4 == 0, variant not 1/2). */
+ * UCOD_EPI_BIAS_F32 (either entry point) a NULL bias means a plain product (K >= 128, N % 4 == 0, variant not 1/2/12). */
 int ucod_gemm_bf16_train(int epilogue, const void* A, const void* B, void* out, int M, int N, int K, const float* bias,
                          const void* aux_bf16, void* out2_bf16, int variant, void* stream);
 

@@ -28,6 +28,7 @@ import torch
 
 import f16_ref as R
 from conftest import within
+from gemm_exact_ref import plan
 
 pytestmark = pytest.mark.gpu
 
@@ -122,9 +123,16 @@ def test_attention_deferred_max_branches(half, form, case):
 
 # ================================================================================================ GEMM epilogues of the fp16 library
 H = HALF_ULP["f16"]
-# (M, N, K, variant): 64 x 64 and 128 x 128 tiles, auto at one image (128 x 128), the one-shot large tile with leftover patches, the 192-wide one,
-# mixed-height tiles, a long K on the small tile
-GEMM_SHAPES = [(200, 256, 256, 12), (200, 256, 256, 2), (1370, 2304, 768, 0), (4111, 768, 768, 9), (5000, 768, 768, 10), (8220, 2304, 768, 13), (333, 128, 3072, 0)]
+# (M, N, K, variant) -> the kernel it launches on 256 CUs (gemm_exact_ref.plan, the mirror of launch(); asserted per case below): 64 x 64 and 128 x 128 tiles,
+# auto at one image (198 128-tiles < 256 CUs: the 64 x 64 kernel again), the one-shot 256-wide large tile (51 tiles: no whole round, so NO leftover patches), the 192-wide one, 13 on a shape whose
+# mixed-height plan is infeasible (33 tall tiles of 28: falls back to 9, a plain extra round), a long K on the small tile; then the shapes that DO reach the
+# leftover patches and the mixed-height kernel (the fp16 residual epilogue takes the mixed-height kernel from 2048 rows up, whatever the variant), and an
+# auto shape with 264 128-tiles, which does take the 128 x 128 kernel
+GEMM_SHAPES = [(200, 256, 256, 12), (200, 256, 256, 2), (1370, 2304, 768, 0), (4111, 768, 768, 9), (5000, 768, 768, 10), (8220, 2304, 768, 13), (333, 128, 3072, 0),
+               (21916, 768, 768, 9), (21916, 768, 768, 13), (1370, 3072, 768, 0)]
+GEMM_PATHS = {(200, 256, 256, 12): "t64", (200, 256, 256, 2): "t128", (1370, 2304, 768, 0): "t64", (4111, 768, 768, 9): "big256", (5000, 768, 768, 10): "big192",
+              (8220, 2304, 768, 13): "big256", (333, 128, 3072, 0): "t64", (21916, 768, 768, 9): "big256+patches", (21916, 768, 768, 13): "mixed256",
+              (1370, 3072, 768, 0): "t128"}
 
 
 def _kmul(K):
@@ -164,8 +172,10 @@ EPIS = {"bias16": N.EPI_BIAS_BF16, "gelu16": N.EPI_BIAS_GELU_BF16, "bias32": N.E
 def test_gemm_epilogues_against_the_f64_product(epi, M, Nn, K, variant):
     """out = epilogue(A W^T) on fp16 operands with f32 accumulation: the f64 product of the SAME operands, to one fp16 rounding of the output plus the f32
     accumulation (16-bit outputs) / the f32 accumulation alone (f32 outputs).  The two residual epilogues run IN PLACE (out aliases resid, as the driver
-    calls them); rows past M keep their guard value; none of these (shape, variant) pairs may be refused."""
+    calls them); rows past M keep their guard value; none of these (shape, variant) pairs may be refused, and each launches the kernel GEMM_PATHS names."""
     lib = N.load("f16")
+    path = plan(epi, M, Nn, K, variant, torch.cuda.get_device_properties(0).multi_processor_count).path
+    assert path == ("mixed256" if epi == "resid16" and M >= 2048 else GEMM_PATHS[(M, Nn, K, variant)]), (epi, M, Nn, K, variant, path)
     A, W, b, sc, resid, acc = _gemm_case(M, Nn, K)
     Ad, Wd, bd, scd = A.to(DEV), W.to(DEV), b.to(DEV), sc.to(DEV)
     f32_out = epi in ("bias32", "resid32")

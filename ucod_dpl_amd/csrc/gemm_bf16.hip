@@ -411,7 +411,8 @@ static int launch(GemmArgs a, int variant, hipStream_t s) {
     if (variant == 14) variant = 13;
     if (a.part_in && variant < 9) variant = 9;                    // row partials are summed by the large-tile kernels' prologue only
   }
-  if (variant >= 9 && variant <= 10 && ((a.N & 3) != 0 || (kBf16Out && (a.N & 7) != 0))) return UCOD_EINVAL;   // 16-byte row stores
+  // 16-byte row stores; 13 / 14 too: where the mixed-height plan does not apply they become 9 / 10 below, behind this check
+  if (((variant >= 9 && variant <= 10) || variant == 13 || variant == 14) && ((a.N & 3) != 0 || (kBf16Out && (a.N & 7) != 0))) return UCOD_EINVAL;
   if constexpr (kColFused<EPI>) {
     if (variant == 13 || variant == 14) {                     // mixed-height tiles; falls back to 9 / 10 when the plan is not feasible
       const MixedPlan mp = mixed_plan(a.M, a.N, variant == 13 ? 256 : 192);
@@ -629,7 +630,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 ? PROF_GEMM_EPI21 : epilogue == UCOD_EPI_SWIGLU_BWD_BF16 ? PROF_GEMM_EPI22 : PROF_GEMM_EPI7)), s);
   switch (epilogue) {
     case UCOD_EPI_BIAS_BF16:                                   // NULL bias (plain product) only in the large-tile kernels
-      if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
+      if (!bias && (variant == 1 || variant == 2 || variant == 12 || K < 128 || (N & 3))) return UCOD_EINVAL;   // (12: the 64 x 64 kernel reads the bias like 1 / 2)
       return launch<UCOD_EPI_BIAS_BF16>(a, variant, s);
     case UCOD_EPI_GELU_BWD_BF16: if (!aux) return UCOD_EINVAL; return launch<UCOD_EPI_GELU_BWD_BF16>(a, variant, s);
     case UCOD_EPI_BIAS_GELU_SAVE_BF16: if (!bias || !out2) return UCOD_EINVAL; return launch<UCOD_EPI_BIAS_GELU_SAVE_BF16>(a, variant, s);
@@ -680,7 +681,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       if (!bias || tokens_per_image < 2 + n_reg) return UCOD_EINVAL;
       return launch<UCOD_EPI_KEY_NCHW_F32>(a, variant, s);
     case UCOD_EPI_BIAS_F32:
-      if (!bias && (variant == 1 || variant == 2 || K < 128 || (N & 3))) return UCOD_EINVAL;
+      if (!bias && (variant == 1 || variant == 2 || variant == 12 || K < 128 || (N & 3))) return UCOD_EINVAL;   // (12: the 64 x 64 kernel reads the bias like 1 / 2)
       return launch<UCOD_EPI_BIAS_F32>(a, variant, s);
     case UCOD_EPI_QKV_FP8: return launch_qkv_fp8(a, s);
     case UCOD_EPI_LNFOLD_BIAS_BF16:
