@@ -56,6 +56,8 @@ extern "C" {
  * launch for launch and bit for bit what they were) and ucod_rope_qk was added; the training-pass drivers refuse a non-NULL table. */
 /* (still 5) LoRA through DINOv3: ucod_rope_qk_ld (row pitch + direction) was added and ucod_vit_train_desc gained a trailing allow_rope (0 = every caller that
  * zero-fills the descriptor: a table is refused as before); with it set the training-pass drivers rotate q / k forward and dq / dk back. */
+/* (still 5) LoRA on the output projections (dense / fc2; o_proj / down_proj): ucod_lora_out_fwd, ucod_lora_out_grad_s, ucod_lora_out_grad_x and the _lora_out forms of
+ * the five training-pass entry points were added; the _lora_mlp forms delegate to them with a NULL table and are launch for launch what they were. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -632,6 +634,56 @@ size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t
 int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
                                          const void* const* mlp_table_host, const float* img, float* key_out, void* workspace, size_t workspace_bytes,
                                          void* stream);
+
+/* LoRA on the output projections as well (models/modules/full_model.py:47-72: `target_modules` is handed to peft, so attention.output.dense / mlp.fc2 -- o_proj /
+ * down_proj on a DINOv3 checkpoint -- are ordinary targets there; peft's module computes  result = base(x) + scaling * B(A(dropout(x)))).  Their inputs are written by the
+ * attention kernel and by the fc1 drain, which have no room for 64 LoRA columns, so the module runs BESIDE its GEMM as row kernels.  For a module with input
+ * x_in bf16 [M, K] and layer scale lambda (K = D, lambda = ls1 for dense: x_in = the attention output; K = F, lambda = ls2 for fc2: x_in = the hidden):
+ *   forward   u [M, 8] f32 = drop(x_in) A^T (r values, zeros beyond);   x[m, :] += lambda * (scaling * u[m, :] B^T)   on the stream the GEMM has just written
+ *   backward  with s = bf16(lambda * dx), the operand the dgrad GEMM takes:   t [M, 8] f32 = scaling * s B,   dB = scaling * s^T u,   dA = t^T drop(x_in),
+ *             cotangent of x_in += mask/(1-p) * (t A)   (fc2: the cotangent buffer holds dpre = dg * gelu'(pre), so the term carries gelu'(pre) too)
+ * One module's parameters / gradients of one layer (f32): [A (r x K) | B (D x r)], 1 <= r <= UCOD_LORA_MLP_MAX_R (u and t rows are UCOD_LORA_OUT_W wide).
+ * K % 128 == 0, 128 <= K <= 4096 (a thread keeps the A values of its two 16-byte vectors in registers), D % 128 == 0, D <= 1536.
+ * Dropout keys: the mask is projection 0 of ucod_lora_dropout over idx = row * K + col with `layer` = 2 L + l for dense and 3 L + l for fc2 -- distinct from the
+ * q / k / v keys (l) and the MLP input projection's (L + l).  Every gradient is a sum of per-block partials in a fixed order: two runs are bit-identical. */
+#define UCOD_LORA_OUT_W 8
+#define UCOD_LORA_OUT_ACT_IDENTITY 0   /* x_in is the buffer itself (dense: the saved attention output) */
+#define UCOD_LORA_OUT_ACT_GELU 1       /* x_in = gelu(pre), the buffer is the saved pre-activation (fc2); gelu / gelu' are the fc1 drains' own fit */
+/* bytes of the per-block partials either gradient kernel needs; 0 for sizes outside the limits above */
+size_t ucod_lora_out_grad_workspace_bytes(int r, int K, int D);
+/* x_stream[m, :] += lambda * (scaling * (drop(x_in[m, :]) A^T) B^T), rows of D f32 (stream_f16 = 0) or IEEE fp16 (1: clamped and counted like the stream's other
+ * writers); lambda f32 [D] or NULL (ones); u_out f32 [rows, 8] receives u, or NULL (the no-grad pass).  Runs right behind the residual GEMM (full_model.py:47-72). */
+int ucod_lora_out_fwd(const void* x_in_bf16, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out,
+                      int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
+/* t f32 [rows, 8] = scaling * s B (zeros beyond r) and the B part of grad_out (overwritten): dB = scaling * s^T u; s bf16 [rows, D], u f32 [rows, 8].  Must run
+ * before the driver reuses s's buffer (full_model.py:47-72). */
+int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
+                         size_t workspace_bytes, int rows, int K, int D, void* stream);
+/* the A part of grad_out (overwritten): dA = t^T drop(x_in), and cot[m, :] += act'(.) * mask/(1-p) * (t[m, :] A) in place, cot bf16 [rows, K]; act = UCOD_LORA_OUT_ACT_*
+ * (GELU: x_in_bf16 is the saved pre-activation, x_in = gelu(pre) is recomputed, never stored) (full_model.py:47-72). */
+int ucod_lora_out_grad_x(const void* x_in_bf16, int act, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out, void* workspace,
+                         size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
+/* The five whole-pass entry points with the output modules' own per-layer table TO (HOST array of DEVICE pointers), layer l at UCOD_VIT_TRAIN_OUT_STRIDE*l
+ * (full_model.py:47-72; result = base(x) + scaling * B(A(dropout(x)))):
+ *   +0 dense parameters f32 [r (D + D)] or NULL   +1 dense gradients   +2 fc2 parameters f32 [r (F + D)] or NULL   +3 fc2 gradients
+ * A module is targeted when layer 0's parameter slot is not NULL (the same modules in every layer).  TO == NULL: exactly the launches and the workspace of the
+ * _lora_mlp entry points, which delegate here.  Otherwise lora_r <= UCOD_LORA_MLP_MAX_R and the sizes above hold (else UCOD_EINVAL, sizes 0); fc2 needs
+ * UCOD_MLP_GELU (the SwiGLU hidden would have to be recomputed from the interleaved, padded [M, 2F] pre-activation: not built).  Per layer below the last the
+ * forward runs one ucod_lora_out_fwd behind each targeted module's residual GEMM (the training pass saves u: M * 32 bytes per layer and module), the backward one
+ * ucod_lora_out_grad_s + ucod_lora_out_grad_x per module: fc2's behind the fc2 dgrad and in front of ucod_lora_mlp_grad / the fc1 dgrad, dense's between the
+ * out-proj dgrad and ucod_attention_bwd.  The last layer's attention output and MLP never reach the key map: their gradients are written as zeros. */
+#define UCOD_VIT_TRAIN_OUT_STRIDE 4
+size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host, const void* const* out_table_host);
+int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                                    const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                               const void* const* mlp_table_host, const void* const* out_table_host, const float* dkey, void* workspace, size_t workspace_bytes,
+                               void* stream);
+size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host, const void* const* out_table_host);
+int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
+                                         const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
+                                         size_t workspace_bytes, void* stream);
 
 /* The way out of LoRA mode: merging the trained matrices into ordinary weights (csrc/lora_merge.hip), so that every frozen-backbone engine runs the adapted model.
  * peft's merge of a LoRA module (what merge_and_unload() does to each module models/modules/full_model.py:47-72 wraps):  W <- W + (lora_alpha / r) B A.

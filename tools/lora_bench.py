@@ -3,7 +3,7 @@
 SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both passes, @512), per-class kernel times.
     lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side]]]]]]]]
 ``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
-on ViT-g.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16)."""
+on ViT-g; naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -31,6 +31,8 @@ grid, n_lead = side // patch, 1 + (DINOV3_ARCHS[arch] if v3 else 4 if arch.endsw
 kw = {} if targets is None else dict(target_modules=targets)
 if v3:
     kw.update(allow_rope=True, eps=1e-5)
+if targets is not None and any(t.rsplit(".", 1)[-1] in ("dense", "fc2", "o_proj", "down_proj") for t in targets):
+    kw.update(allow_out=True)                             # the output projections are opt-in (ViTLoRAEngine)
 eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
     print(f"targets {targets}: arena [{eng.L}, {eng.lora.shape[1]}]")
@@ -70,6 +72,17 @@ if getattr(eng, "mlp_target", None) is not None:
     for name, c, t in rows:
         if name == "lora_mlp_grad":
             print(f"  lora_mlp_grad: {byts / 1e6:.1f} MB per launch pair (grad + reduce), {t / c * 1e3:.1f} us -> {byts / (t / c * 1e-3) / 1e12:.2f} TB/s")
+if any(getattr(eng, "out_targets", ())):
+    # the output modules' three kernels against the bytes each has to move (per launch; grad_s / grad_x include their reduce launch): the forward reads x_in [M, K]
+    # bf16, reads and writes the stream row and writes u; grad_s reads s [M, D] and u, writes t; grad_x reads x_in and reads and writes its cotangent
+    M, D, sb = B * (n_lead + grid * grid), eng.D, 2 if eng.resid16 else 4
+    Ks = [K for K, on in zip((D, eng.F), eng.out_targets) if on]
+    per = {"lora_out_fwd": sum(M * K * 2 + 2 * M * D * sb + M * 32 for K in Ks), "lora_out_grad_s": sum(M * D * 2 + 2 * M * 32 for K in Ks),
+           "lora_out_grad_x": sum(3 * M * K * 2 + M * 32 for K in Ks)}
+    for name, c, t in rows:
+        if name in per:
+            byts = per[name] / len(Ks)                      # the mean over the targeted modules, as the average time is
+            print(f"  {name}: {byts / 1e6:.1f} MB per launch (mean of K = {Ks}), {t / c * 1e3:.1f} us -> {byts / (t / c * 1e-3) / 1e12:.2f} TB/s")
 if giant:
     # the two SwiGLU training launches alone at this pass's shapes, and beside them (orientation) the launches they extend: UCOD_EPI_BIAS_SWIGLU_BF16 at (M, 2F, D),
     # which the SAVE form extends by one [M, 2F] store, and UCOD_EPI_GELU_BWD_BF16 at (M, F, D), which reads and writes half the bytes of the SwiGLU dgrad drain

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "common.h"
 #include "../../include/ucod_dpl.h"
+#include "gemm_bf16_epilogue.h"   // gelu_erf2 / gelu_grad2: the fc1 drains' fit, which ucod_lora_out_grad_x recomputes the hidden with
 
 namespace ucod {
 
@@ -1112,4 +1113,370 @@ extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int fl
   UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
   return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
                        (const bf16_raw*)t_bf16, ldt, a_m, r, make_drop(dropout), (hipStream_t)stream, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LoRA on the output projections (attention.output.dense / o_proj, mlp.fc2 / down_proj; full_model.py:47-72 hands target_modules to peft, whose module computes
+// result = base(x) + scaling * B(A(dropout(x)))).  Their inputs -- the attention kernel's output, the fc1 drain's hidden -- have no room for aug columns, so the
+// module runs BESIDE its GEMM as row kernels:
+//   forward   u [M, 8] f32 = drop(x_in) A^T (r values, the rest zero);  x[m, :] += lambda * (alpha/r * u[m, :] B^T)  behind the residual GEMM      (ucod_lora_out_fwd)
+//   backward  s = bf16(lambda * dx), the dgrad GEMM's operand:  t [M, 8] f32 = alpha/r * s B,  dB = alpha/r * s^T u                                  (ucod_lora_out_grad_s)
+//             dA = t^T drop(x_in);  cotangent of x_in += act'(pre) * mask/(1-p) * (t A), in the bf16 buffer the dgrad GEMM wrote                     (ucod_lora_out_grad_x)
+// x_in is the saved attention output (identity) or gelu(pre) recomputed from the saved pre-activation with the drains' own fit (gelu_erf2 / gelu_grad2).
+// Parameter layout of one module of one layer (f32): [A (r x K) | B (D x r)], K = D (dense) or F (fc2).  Mask: projection 0 of the counter hash over [M, K].
+// Gradients: per-block partials, summed in a fixed order by lora_out_reduce_kernel -- no float atomics.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ucod {
+
+constexpr int OUT_W = UCOD_LORA_OUT_W;                            // floats per row of u and t
+constexpr int OUT_RB = 4;                                        // rows a block (grad_s) or a thread (grad_x) has in flight
+static inline int out_grad_s_blocks(int rows) { return cdiv(rows, OUT_RB) < 512 ? cdiv(rows, OUT_RB) : 512; }
+static inline int out_grad_x_blocks(int rows) { return cdiv(rows, OUT_RB) < 256 ? cdiv(rows, OUT_RB) : 256; }
+
+// A block's 256 threads share a row: thread `tid` owns the 16-byte vectors tid + 256 i of x_in (its A values stay in registers for all the block's rows); the r dot
+// products are summed over the block through LDS (one barrier per row: two buffers in turn), thread j < 8 stores u[row][j], then the D-wide row of the stream is
+// updated with lambda * alpha/r * B from LDS ([RW][D]: consecutive threads read consecutive 16 bytes).  XH16: the stream is IEEE fp16 (clamped and counted like
+// every writer of that stream).  u_out NULL (the no-grad pass): nothing is saved.
+template <int NVT, int RW, bool XH16>
+__global__ __launch_bounds__(256) void lora_out_fwd_kernel(const bf16_raw* __restrict__ x_in, const float* __restrict__ lora, const float* __restrict__ lam, int r,
+                                                           float scaling, void* __restrict__ xs, float* __restrict__ u_out, int rows, int K, int D, Drop drop,
+                                                           unsigned* __restrict__ ovf) {
+  extern __shared__ __attribute__((aligned(16))) float out_smem[];
+  float* sB = out_smem;                                          // [RW][D]
+  float* red = out_smem + RW * D;                                // [2][4][RW]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NV = K / 8;
+  const float* Bo = lora + (size_t)r * K;
+  float a[NVT][8][RW];
+#pragma unroll
+  for (int i = 0; i < NVT; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int j = 0; j < RW; ++j) a[i][e][j] = (tid + 256 * i < NV && j < r) ? lora[(size_t)j * K + 8 * (tid + 256 * i) + e] : 0.f;
+  for (int idx = tid; idx < RW * D; idx += 256) {
+    const int j = idx / D, d = idx - j * D;
+    sB[idx] = j < r ? (lam ? lam[d] : 1.f) * scaling * Bo[(size_t)d * r + j] : 0.f;
+  }
+  __syncthreads();
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  bool sat = false;
+  int buf = 0;
+  for (int row = blockIdx.x; row < rows; row += gridDim.x, buf ^= 1) {
+    const u32x4* xr = reinterpret_cast<const u32x4*>(x_in + (size_t)row * K);
+    float s[RW];
+#pragma unroll
+    for (int j = 0; j < RW; ++j) s[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NVT; ++i) {
+      const int v = tid + 256 * i;
+      const u32x4 w = v < NV ? xr[v] : (u32x4)(0u);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float x0 = __uint_as_float(w[q] << 16), x1 = __uint_as_float(w[q] & 0xFFFF0000u);
+        if (drop.thresh) {
+          const unsigned idx = (unsigned)row * (unsigned)K + 8u * (unsigned)v + 2u * (unsigned)q;
+          x0 *= drop_scale(drop, 0, idx);
+          x1 *= drop_scale(drop, 0, idx + 1u);
+        }
+#pragma unroll
+        for (int j = 0; j < RW; ++j) s[j] += x0 * a[i][2 * q][j] + x1 * a[i][2 * q + 1][j];
+      }
+    }
+    float* rb = red + buf * 4 * RW;
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+      const float ws = wave_sum(s[j]);
+      if (lane == 0) rb[wave * RW + j] = ws;
+    }
+    __syncthreads();
+    float u[RW];
+#pragma unroll
+    for (int j = 0; j < RW; ++j) u[j] = (rb[j] + rb[RW + j]) + (rb[2 * RW + j] + rb[3 * RW + j]);
+    if (u_out && tid < OUT_W) u_out[(size_t)row * OUT_W + tid] = tid < RW ? (rb[tid] + rb[RW + tid]) + (rb[2 * RW + tid] + rb[3 * RW + tid]) : 0.f;
+    for (int c = tid; c < D / 4; c += 256) {
+      f4 acc = (f4)(0.f);
+#pragma unroll
+      for (int j = 0; j < RW; ++j) acc += u[j] * *reinterpret_cast<const f4*>(sB + j * D + 4 * c);
+      if constexpr (XH16) {
+        u32x2* p = reinterpret_cast<u32x2*>(xs) + (size_t)row * (D / 4) + c;
+        const u32x2 w = *p;
+        float x0, x1, x2, x3;
+        unpack_f16x2(w[0], x0, x1);
+        unpack_f16x2(w[1], x2, x3);
+        x0 += acc[0], x1 += acc[1], x2 += acc[2], x3 += acc[3];
+        sat |= beyond_f16(x0) || beyond_f16(x1) || beyond_f16(x2) || beyond_f16(x3);
+        *p = (u32x2){pack_f16x2(clamp_f16(x0), clamp_f16(x1)), pack_f16x2(clamp_f16(x2), clamp_f16(x3))};
+      } else {
+        f4* p = reinterpret_cast<f4*>(xs) + (size_t)row * (D / 4) + c;
+        *p += acc;
+      }
+    }
+  }
+  if (XH16 && sat) atomicAdd(ovf, 1u);
+}
+
+// t and the partials of dB in one pass over s [rows, D] and u [rows, 8].  The block's threads share OUT_RB rows at a time: thread `tid` owns the column pairs
+// tid + 256 i of s (its B values and dB accumulators stay in registers), the partial t of the rows is summed through LDS (one barrier per OUT_RB rows), thread
+// 8 q + j stores t[row0 + q][j].  Partials [D][r] per block.
+template <int NPT, int RW>
+__global__ __launch_bounds__(256) void lora_out_grad_s_kernel(const bf16_raw* __restrict__ s, const float* __restrict__ u, const float* __restrict__ Bo, int r,
+                                                              float scaling, float* __restrict__ partial, float* __restrict__ tout, int rows, int D) {
+  constexpr int RB = OUT_RB;
+  __shared__ float red[2][4][RB][RW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NP2 = D / 2;
+  float bw[NPT][2][RW], accB[NPT][2][RW];
+#pragma unroll
+  for (int i = 0; i < NPT; ++i)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        bw[i][e][j] = (tid + 256 * i < NP2 && j < r) ? Bo[(size_t)(2 * (tid + 256 * i) + e) * r + j] : 0.f;
+        accB[i][e][j] = 0.f;
+      }
+  int buf = 0;
+  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB, buf ^= 1) {
+    unsigned sw[RB][NPT];
+    float uu[RB][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const bool live = row0 + q < rows;
+      const int row = live ? row0 + q : rows - 1;
+      const unsigned* sr = reinterpret_cast<const unsigned*>(s + (size_t)row * D);
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) sw[q][i] = (live && tid + 256 * i < NP2) ? sr[tid + 256 * i] : 0u;
+#pragma unroll
+      for (int j = 0; j < RW; ++j) uu[q][j] = (live && j < r) ? u[(size_t)row * OUT_W + j] : 0.f;      // (block-uniform address)
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      float ss[RW];
+#pragma unroll
+      for (int j = 0; j < RW; ++j) ss[j] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        const float d0 = __uint_as_float(sw[q][i] << 16), d1 = __uint_as_float(sw[q][i] & 0xFFFF0000u);
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+          ss[j] += d0 * bw[i][0][j] + d1 * bw[i][1][j];
+          accB[i][0][j] += d0 * uu[q][j];
+          accB[i][1][j] += d1 * uu[q][j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        const float ws = wave_sum(ss[j]);
+        if (lane == 0) red[buf][wave][q][j] = ws;
+      }
+    }
+    __syncthreads();
+    if (tid < RB * OUT_W) {
+      const int q = tid / OUT_W, j = tid - q * OUT_W;
+      if (row0 + q < rows)
+        tout[(size_t)(row0 + q) * OUT_W + j] = j < RW ? scaling * ((red[buf][0][q][j] + red[buf][1][q][j]) + (red[buf][2][q][j] + red[buf][3][q][j])) : 0.f;
+    }
+  }
+  float* out = partial + (size_t)blockIdx.x * (size_t)D * r;
+#pragma unroll
+  for (int i = 0; i < NPT; ++i) {
+    const int c = tid + 256 * i;
+    if (c >= NP2) continue;
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int j = 0; j < RW; ++j)
+        if (j < r) out[(size_t)(2 * c + e) * r + j] = scaling * accB[i][e][j];
+  }
+}
+
+// dA partials and the cotangent update in one pass over x_in [rows, K] and its cotangent [rows, K] (bf16, in place).  No row is shared: thread (blockIdx.y, tid)
+// owns ONE 16-byte vector of every row (its A values and dA accumulators stay in registers), the row's t comes from memory (block-uniform address), OUT_RB rows are
+// in flight.  GELU: x_in = gelu(pre) and the term carries gelu'(pre) -- the cotangent buffer already holds dpre = dg * gelu'(pre).  Partials [r][K] per blockIdx.x.
+template <int RW, bool GELU>
+__global__ __launch_bounds__(128) void lora_out_grad_x_kernel(const bf16_raw* __restrict__ xin, bf16_raw* __restrict__ cot, const float* __restrict__ t,
+                                                              const float* __restrict__ A, int r, float* __restrict__ partial, int rows, int K, Drop drop) {
+  constexpr int RB = OUT_RB;
+  const int v = blockIdx.y * 128 + threadIdx.x;
+  if (v >= K / 8) return;                                        // (no barrier below)
+  float a[8][RW], acc[8][RW];
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+      a[e][j] = j < r ? A[(size_t)j * K + 8 * v + e] : 0.f;
+      acc[e][j] = 0.f;
+    }
+  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB) {
+    u32x4 xw[RB], cw[RB];
+    float tt[RB][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const bool live = row0 + q < rows;
+      const size_t row = live ? row0 + q : rows - 1;
+      xw[q] = reinterpret_cast<const u32x4*>(xin + row * K)[v];
+      cw[q] = reinterpret_cast<const u32x4*>(cot + row * K)[v];
+#pragma unroll
+      for (int j = 0; j < RW; ++j) tt[q][j] = (live && j < r) ? t[row * OUT_W + j] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      if (row0 + q >= rows) break;
+      u32x4 o;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        float x0 = __uint_as_float(xw[q][w] << 16), x1 = __uint_as_float(xw[q][w] & 0xFFFF0000u);
+        float c0 = __uint_as_float(cw[q][w] << 16), c1 = __uint_as_float(cw[q][w] & 0xFFFF0000u);
+        float g0 = 1.f, g1 = 1.f;
+        if constexpr (GELU) {
+          const f32x2 gr = gelu_grad2((f32x2){x0, x1}), gx = gelu_erf2((f32x2){x0, x1});
+          g0 = gr[0], g1 = gr[1];
+          x0 = gx[0], x1 = gx[1];
+        }
+        if (drop.thresh) {
+          const unsigned idx = (unsigned)(row0 + q) * (unsigned)K + 8u * (unsigned)v + 2u * (unsigned)w;
+          const float m0 = drop_scale(drop, 0, idx), m1 = drop_scale(drop, 0, idx + 1u);
+          x0 *= m0, x1 *= m1;
+          g0 *= m0, g1 *= m1;
+        }
+        float ta0 = 0.f, ta1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+          ta0 += tt[q][j] * a[2 * w][j];
+          ta1 += tt[q][j] * a[2 * w + 1][j];
+          acc[2 * w][j] += tt[q][j] * x0;
+          acc[2 * w + 1][j] += tt[q][j] * x1;
+        }
+        o[w] = pack_bf16x2(c0 + g0 * ta0, c1 + g1 * ta1);
+      }
+      reinterpret_cast<u32x4*>(cot + (size_t)(row0 + q) * K)[v] = o;
+    }
+  }
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  float* out = partial + (size_t)blockIdx.x * (size_t)r * K + 8 * v;
+#pragma unroll
+  for (int j = 0; j < RW; ++j)
+    if (j < r) {
+      *reinterpret_cast<f4*>(out + (size_t)j * K) = (f4){acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
+      *reinterpret_cast<f4*>(out + (size_t)j * K + 4) = (f4){acc[4][j], acc[5][j], acc[6][j], acc[7][j]};
+    }
+}
+
+// partial [nblk][n] -> out [n], blocks in ascending order inside each of 8 slices, then the slices: 32 elements x 8 slices of the block list per workgroup
+__global__ __launch_bounds__(256) void lora_out_reduce_kernel(const float* __restrict__ partial, int nblk, int n, float* __restrict__ out) {
+  __shared__ float red[8][33];
+  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + e;
+  float s = 0.f;
+  if (i < n) {
+#pragma unroll 4
+    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
+  }
+  red[sl][e] = s;
+  __syncthreads();
+  if (sl != 0 || i >= n) return;
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += red[k][e];
+  out[i] = s;
+}
+
+static inline bool lora_out_dims_ok(int r, int K, int D) {
+  return r >= 1 && r <= UCOD_LORA_MLP_MAX_R && K >= 128 && K <= 4096 && (K % 128) == 0 && D >= 128 && D <= 1536 && (D % 128) == 0;
+}
+
+}  // namespace ucod
+
+extern "C" size_t ucod_lora_out_grad_workspace_bytes(int r, int K, int D) {
+  if (!lora_out_dims_ok(r, K, D)) return 0;
+  const size_t bs = (size_t)512 * (size_t)D * r, bx = (size_t)256 * (size_t)r * K;      // the most blocks either gradient kernel runs
+  return (bs > bx ? bs : bx) * sizeof(float);
+}
+
+extern "C" int ucod_lora_out_fwd(const void* x_in, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out,
+                                 int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!x_in || !lora_out || !x_stream || rows <= 0 || !lora_out_dims_ok(r, K, D) || (stream_f16 != 0 && stream_f16 != 1)) return UCOD_EINVAL;
+  if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+  UCOD_PROF(PROF_LORA_OUT_FWD, stream);
+  const Drop drop = make_drop(dropout);
+  const int rw = r <= 2 ? 2 : 8, nvt = K / 8 <= 256 ? 1 : 2;
+  const int nblk = rows < 2048 ? rows : 2048;
+  const size_t lds = (size_t)(rw * D + 2 * 4 * rw) * sizeof(float);
+  unsigned* ovf = stream_f16 ? resid16_overflow_counter() : nullptr;
+#define OF(v, w, h) hipLaunchKernelGGL((lora_out_fwd_kernel<v, w, h>), dim3(nblk), dim3(256), lds, (hipStream_t)stream, (const bf16_raw*)x_in, lora_out, lambda, r, \
+                                       scaling, x_stream, u_out, rows, K, D, drop, ovf)
+#define OFH(v, w)                 \
+  do {                            \
+    if (stream_f16) OF(v, w, true); \
+    else OF(v, w, false);         \
+  } while (0)
+  if (nvt == 1 && rw == 2) OFH(1, 2);
+  else if (nvt == 1) OFH(1, 8);
+  else if (rw == 2) OFH(2, 2);
+  else OFH(2, 8);
+#undef OFH
+#undef OF
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
+                                    size_t workspace_bytes, int rows, int K, int D, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!s_bf16 || !u || !lora_out || !grad_out || !t_out || !workspace || rows <= 0) return UCOD_EINVAL;
+  const size_t need = ucod_lora_out_grad_workspace_bytes(r, K, D);
+  if (need == 0) return UCOD_EINVAL;
+  if (workspace_bytes < need) return UCOD_ENOMEM;
+  UCOD_PROF(PROF_LORA_OUT_GRAD_S, stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = out_grad_s_blocks(rows), npt = cdiv(D / 2, 256);
+  const float* Bo = lora_out + (size_t)r * K;
+#define GS(p, w) hipLaunchKernelGGL((lora_out_grad_s_kernel<p, w>), dim3(nblk), dim3(256), 0, st, (const bf16_raw*)s_bf16, u, Bo, r, scaling, (float*)workspace, t_out, \
+                                    rows, D)
+#define GSW(p)            \
+  do {                    \
+    if (r <= 2) GS(p, 2); \
+    else GS(p, 8);        \
+  } while (0)
+  if (npt == 1) GSW(1);
+  else if (npt == 2) GSW(2);
+  else GSW(3);
+#undef GSW
+#undef GS
+  UCOD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(lora_out_reduce_kernel, dim3(cdiv((long)D * r, 32)), dim3(256), 0, st, (const float*)workspace, nblk, D * r, grad_out + (size_t)r * K);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" int ucod_lora_out_grad_x(const void* x_in, int act, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out, void* workspace,
+                                    size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!x_in || !cot_bf16 || !t || !lora_out || !grad_out || !workspace || rows <= 0 || (act != UCOD_LORA_OUT_ACT_IDENTITY && act != UCOD_LORA_OUT_ACT_GELU))
+    return UCOD_EINVAL;
+  const size_t need = ucod_lora_out_grad_workspace_bytes(r, K, D);
+  if (need == 0) return UCOD_EINVAL;
+  if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+  if (workspace_bytes < need) return UCOD_ENOMEM;
+  UCOD_PROF(PROF_LORA_OUT_GRAD_X, stream);
+  const Drop drop = make_drop(dropout);
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = out_grad_x_blocks(rows);
+  const dim3 grid(nblk, cdiv(K / 8, 128));
+#define GX(w, g) hipLaunchKernelGGL((lora_out_grad_x_kernel<w, g>), grid, dim3(128), 0, st, (const bf16_raw*)x_in, (bf16_raw*)cot_bf16, t, lora_out, r, \
+                                    (float*)workspace, rows, K, drop)
+  if (act == UCOD_LORA_OUT_ACT_GELU) {
+    if (r <= 2) GX(2, true);
+    else GX(8, true);
+  } else {
+    if (r <= 2) GX(2, false);
+    else GX(8, false);
+  }
+#undef GX
+  UCOD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(lora_out_reduce_kernel, dim3(cdiv((long)r * K, 32)), dim3(256), 0, st, (const float*)workspace, nblk, r * K, grad_out);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
 }

@@ -11,6 +11,10 @@
 // saved residual stream, takes the module's gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the LayerNorm-2 backward.  A NULL table is the _mlp form.
 // DINOv3 (vit.rope with allow_rope = 1): every layer but the last rotates q / k of the patch rows in place between the QKV GEMM and attention (the last layer's key hook
 // is taken in front of any rotation), and the backward applies the transposed rotation to dq / dk behind ucod_attention_bwd (ucod_rope_qk_ld).  Plans do not change.
+// The _lora_out forms take the per-layer table of the LoRA modules on the output projections (attention.output.dense / mlp.fc2; o_proj / down_proj): their inputs have
+// no aug columns, so each module is one row kernel behind its residual GEMM (ucod_lora_out_fwd: x += lambda * scaling * (drop(x_in) A^T) B^T, u saved) and two in the
+// backward (ucod_lora_out_grad_s on the dgrad GEMM's operand s, ucod_lora_out_grad_x on x_in and its cotangent).  Dropout keys 2L + l (dense) and 3L + l (fc2).
+// A NULL table is the _lora_mlp form.
 // No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
@@ -24,6 +28,7 @@ struct TPlan {
   size_t h2, g, patch, qscale;                             // forward transients
   size_t dx, dh, s, da, dqkv, delta, lgw;                  // backward scratch (dpre aliases g, s aliases h2)
   size_t tm, mgw, mgw_bytes;                               // MLP LoRA module: t scratch [M, 64], partials of ucod_lora_mlp_grad
+  size_t u_o, u_2, s_u, t_out, ogw, ogw_bytes;             // output modules: saved u [M, 8] per layer (dense, fc2), t scratch [M, 8], partials of ucod_lora_out_grad_*
   size_t total;
 };
 
@@ -45,9 +50,25 @@ inline int fc1_width(const ucod_vit_desc* d, int mlp) { return mlp == UCOD_MLP_S
 inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl) {
   return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && ucod_lora_mlp_grad_workspace_bytes(fc1_width(&t->vit, mlp), t->vit.D) != 0);
 }
-bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false) { return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl); }
+// the output modules a table names (layer 0's parameter slots: the same modules in every layer), and whether the pass can carry them
+struct OutMods { bool o, f; };
+inline OutMods out_mods(const void* const* TO) { return OutMods{TO && TO[0] != nullptr, TO && TO[2] != nullptr}; }
+inline size_t out_gw_bytes(const ucod_vit_train_desc* t, OutMods m) {
+  const size_t a = m.o ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) : 0, b = m.f ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) : 0;
+  return a > b ? a : b;
+}
+inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TO) {
+  const OutMods m = out_mods(TO);
+  if (!TO) return true;
+  if (!m.o && !m.f) return false;                                 // a table that names no module
+  if (m.f && mlp != UCOD_MLP_GELU) return false;                  // (SwiGLU: the hidden would have to be recomputed from the interleaved, padded [M, 2F] pre-activation)
+  return (!m.o || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) != 0) && (!m.f || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) != 0);
+}
+bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false, const void* const* TO = nullptr) {
+  return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl) && valid_out(t, mlp, TO);
+}
 
-TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false) {
+TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const void* const* TO = nullptr) {
   const ucod_vit_desc* d = &t->vit;
   TPlan p;
   const int gh = d->H / d->P, gw = d->W / d->P;
@@ -88,6 +109,16 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false) {
     p.mgw_bytes = ucod_lora_mlp_grad_workspace_bytes((int)FP, d->D);
     p.mgw = take(p.mgw_bytes);
   }
+  p.u_o = p.u_2 = p.s_u = p.t_out = p.ogw = p.ogw_bytes = 0;
+  if (TO) {                                                     // (behind everything else: without a table no offset and no byte differs)
+    const OutMods m = out_mods(TO);
+    p.s_u = up(M * UCOD_LORA_OUT_W * 4);
+    if (m.o) p.u_o = take(p.s_u * (L - 1));
+    if (m.f) p.u_2 = take(p.s_u * (L - 1));
+    p.t_out = take(M * UCOD_LORA_OUT_W * 4);
+    p.ogw_bytes = out_gw_bytes(t, m);
+    p.ogw = take(p.ogw_bytes);
+  }
   p.total = o;
   return p;
 }
@@ -100,19 +131,23 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false) {
     if (rc__ != 0) return rc__;  \
   } while (0)
 
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
+  return valid(t, mlp, TM != nullptr, TO) ? make_plan(t, mlp, TM != nullptr, TO).total : 0;
+}
 extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
-  return valid(t, mlp, TM != nullptr) ? make_plan(t, mlp, TM != nullptr).total : 0;
+  return ucod_vit_train_workspace_bytes_lora_out(t, mlp, TM, nullptr);
 }
 extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_train_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_train_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr, TO) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp, TM != nullptr);
+  const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
+  const OutMods om = out_mods(TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
@@ -159,6 +194,12 @@ extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int
     if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
     RUN(ucod_attention_fwd_lse(qkv, att, lse, d->B, tok, d->heads, stream));
     RUN(ucod_gemm_bf16(epi_resid, att, W[4], x_mid, M, D, D, (const float*)W[5], (const float*)W[6], x_in, nullptr, tok, gv, stream));
+    const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
+    if (om.o) {   // LoRA on the attention output projection: x_mid += ls1 * scaling * (drop(att) A_o^T) B_o^T, u saved (its own mask: key 2L + l)
+      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
+      RUN(ucod_lora_out_fwd(att, (const float*)Z[0], t->lora_r, t->lora_scaling, (const float*)W[6], x_mid, r16, (float*)(ws + p.u_o + p.s_u * l), M, D, D,
+                            t->lora_dropout > 0.f ? &drop_o : nullptr, stream));
+    }
     if (TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug (its own mask: key L + l)
       const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
       const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
@@ -173,8 +214,17 @@ extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int
       else RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
     }
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x_next, M, D, F, (const float*)W[12], (const float*)W[13], x_mid, nullptr, tok, gv, stream));
+    if (om.f) {   // LoRA on the MLP output projection: x_next += ls2 * scaling * (drop(g) A_2^T) B_2^T, u saved (key 3L + l)
+      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
+      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x_next, r16, (float*)(ws + p.u_2 + p.s_u * l), M, F, D,
+                            t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
+    }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_train_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
                                           float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -225,16 +275,21 @@ IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
 }
 }  // namespace
 
+// (the no-grad pass saves nothing: the output modules add no workspace byte)
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
+  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) && valid_out(t, mlp, TO) ? make_iplan(t, TM != nullptr).total : 0;
+}
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
-  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) ? make_iplan(t, TM != nullptr).total : 0;
+  return ucod_vit_lora_infer_workspace_bytes_lora_out(t, mlp, TM, nullptr);
 }
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_lora_infer_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_lora_infer_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !valid_out(t, mlp, TO) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  const OutMods om = out_mods(TO);
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const ucod_vit_desc* d = &t->vit;
   const IPlan p = make_iplan(t, TM != nullptr);
@@ -273,6 +328,12 @@ extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t
     if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
     RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, 0.f, 0, stream));
     RUN(ucod_gemm_bf16(epi_resid, a, W[4], x, M, D, D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
+    const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
+    if (om.o) {   // (as the training pass: same arithmetic, same mask keys, u not saved)
+      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
+      RUN(ucod_lora_out_fwd(a, (const float*)Z[0], t->lora_r, t->lora_scaling, (const float*)W[6], x, r16, nullptr, M, D, D, t->lora_dropout > 0.f ? &drop_o : nullptr,
+                            stream));
+    }
     if (TM) {
       const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
       const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
@@ -287,8 +348,17 @@ extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t
       else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     }
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x, M, D, F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
+    if (om.f) {
+      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
+      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x, r16, nullptr, M, F, D, t->lora_dropout > 0.f ? &drop_f : nullptr,
+                            stream));
+    }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_lora_infer_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
                                                float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -299,13 +369,14 @@ extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const v
   return ucod_vit_forward_lora_infer_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
 }
 
-extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                          const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                          const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr, TO) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp, TM != nullptr);
+  const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
+  const OutMods om = out_mods(TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KQ = 3 * D + UCOD_LORA_AUG, r = t->lora_r;
@@ -355,6 +426,11 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     const size_t n_m = (size_t)r * (size_t)(D + fc1_width(d, mlp)) * sizeof(float);
     if (hipMemsetAsync(const_cast<void*>((TM + UCOD_VIT_TRAIN_MLP_STRIDE * last)[2]), 0, n_m, (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
   }
+  if (TO) {   // (nor do its attention output and fc2: zeros, written as such)
+    const void* const* Z = TO + UCOD_VIT_TRAIN_OUT_STRIDE * last;
+    if (om.o && hipMemsetAsync(const_cast<void*>(Z[1]), 0, (size_t)r * (size_t)(D + D) * sizeof(float), (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
+    if (om.f && hipMemsetAsync(const_cast<void*>(Z[3]), 0, (size_t)r * (size_t)(F + D) * sizeof(float), (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
+  }
   RUN(ucod_key_grad_tokens_reg(dkey, dqkv, d->B, tok, D, d->n_reg, stream));
   RUN(qkv_side(last));
   if (last == 0) return UCOD_OK;
@@ -379,6 +455,17 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     } else {
       RUN(ucod_gemm_bf16_train(UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
     }
+    const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
+    if (om.f) {
+      // LoRA on the MLP output projection, while `s` (= bf16(ls2 * dx), the fc2 dgrad's operand) is still there: t = scaling * s B_2 and dB_2 from s and the saved u,
+      // then dA_2 from t and the hidden recomputed as gelu(pre), and dpre += gelu'(pre) * mask/(1-p) * (t A_2) -- completed before anything below reads dpre
+      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
+      float* gz = (float*)const_cast<void*>(Z[3]);
+      RUN(ucod_lora_out_grad_s(s, (const float*)(ws + p.u_2 + p.s_u * l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes,
+                               M, F, D, stream));
+      RUN(ucod_lora_out_grad_x(pre, UCOD_LORA_OUT_ACT_GELU, dpre, (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D,
+                               t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
+    }
     const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
     const ucod_lora_dropout* dp_m = t->lora_dropout > 0.f ? &drop_m : nullptr;
     const void* const* Y = TM ? TM + UCOD_VIT_TRAIN_MLP_STRIDE * l : nullptr;
@@ -396,6 +483,14 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    if (om.o) {   // LoRA on the attention output projection: s = bf16(ls1 * dx); da += mask/(1-p) * (t A_o) before attention backward reads it
+      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
+      float* gz = (float*)const_cast<void*>(Z[1]);
+      RUN(ucod_lora_out_grad_s(s, (const float*)(ws + p.u_o + p.s_u * l), (const float*)Z[0], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes,
+                               M, D, D, stream));
+      RUN(ucod_lora_out_grad_x(att, UCOD_LORA_OUT_ACT_IDENTITY, da, (const float*)(ws + p.t_out), (const float*)Z[0], r, gz, ws + p.ogw, p.ogw_bytes, M, D, D,
+                               t->lora_dropout > 0.f ? &drop_o : nullptr, stream));
+    }
     RUN(ucod_attention_bwd(qkv, att, da, lse, delta, dqkv, KQ, d->B, tok, d->heads, stream));
     // DINOv3: dq / dk above are the cotangents of the ROTATED operands; the LoRA-gradient kernel and the QKV dgrad want those of the projection outputs,
     // d(pre) = R^T d(post) -- the same table with the sine negated, on the q | k thirds of dqkv_aug (attention_bwd.hip stores dq at 0, dk at D, dv at 2 D)
@@ -407,6 +502,10 @@ extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp,
     }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                          const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_backward_lora_out(t, mlp, T, TT, TM, nullptr, dkey, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey,
                                      void* workspace, size_t workspace_bytes, void* stream) {

@@ -66,9 +66,11 @@ def _adapter_prefix(engine):
 
 
 def _adapter_targets(engine):
-    """target_modules of an engine as peft lists them: the leaf names (query / key / value; q_proj / k_proj / v_proj on a DINOv3 checkpoint)"""
+    """target_modules of an engine as peft lists them: the leaf names (query / key / value; q_proj / k_proj / v_proj on a DINOv3 checkpoint; with the output
+    projections targeted also dense / fc2, or o_proj / down_proj)"""
     names = [n for n, on in zip(getattr(engine, "_qkv_names", ("query", "key", "value")), engine.targets) if on]
-    return names + ([engine.mlp_target] if engine.mlp_target is not None else [])
+    names += [engine.mlp_target] if engine.mlp_target is not None else []
+    return names + [path.rsplit(".", 1)[-1] for path, on in zip(getattr(engine, "_out_paths", ()), getattr(engine, "out_targets", ())) if on]
 
 
 def save_lora_adapter(engine, folder):
@@ -107,7 +109,9 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     """models/modules/full_model.py:47-72.  r == 0 is refused (the reference returns the bare model; use ``backbone`` then).  Either MLP kind of DINOv2 is taken:
     a SwiGLU checkpoint (facebook/dinov2-giant) trains through the engine's SwiGLU backward (``allow_swiglu``).  ``target_modules`` (:54,67: handed to peft as it
     is) may name any non-empty subset of query / key / value and the MLP input projection (``fc1``; ``weights_in`` on a SwiGLU checkpoint), matched by peft's
-    suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets).
+    suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets) -- unless the build-only key ``allow_out`` (default
+    False) is set: then ``dense`` and ``fc2`` (``o_proj`` and the non-gated ``down_proj`` on a DINOv3 checkpoint) are built as row kernels beside their GEMMs, and
+    only the SwiGLU MLP's output projection stays refused.
     A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
     100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
@@ -125,7 +129,7 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
         eps = 1e-5 if is_dinov3(state_dict) else 1e-6
     return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, eps=eps, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
-                                      rope_theta=float(getattr(config, "rope_theta", 100.0))))
+                                      rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False))))
 
 
 class full_model(nn.Module):

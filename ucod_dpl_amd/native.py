@@ -48,6 +48,13 @@ VIT_TRAIN_MLP_STRIDE = 3
 VIT_TRAIN_MLP_SLOTS = ("fc1_w_aug", "lora_mlp", "lora_mlp_grad")
 M_FC1_W_AUG, M_LORA, M_LORA_GRAD = range(VIT_TRAIN_MLP_STRIDE)
 LORA_MLP_MAX_R = 8                                          # include/ucod_dpl.h: UCOD_LORA_MLP_MAX_R
+# the per-layer table of the LoRA modules on the output projections (the _lora_out entry points): parameters and gradients of dense / o_proj, then of fc2 / down_proj;
+# an untargeted module's two slots are NULL
+VIT_TRAIN_OUT_STRIDE = 4
+VIT_TRAIN_OUT_SLOTS = ("lora_dense", "lora_dense_grad", "lora_fc2", "lora_fc2_grad")
+O_LORA_DENSE, O_LORA_DENSE_GRAD, O_LORA_FC2, O_LORA_FC2_GRAD = range(VIT_TRAIN_OUT_STRIDE)
+LORA_OUT_W = 8                                              # include/ucod_dpl.h: UCOD_LORA_OUT_W (floats per row of the saved u and of t)
+LORA_OUT_ACT_IDENTITY, LORA_OUT_ACT_GELU = 0, 1
 
 vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -185,6 +192,16 @@ SIGNATURES = {
     "ucod_vit_backward_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes_lora_mlp": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp)]),
     "ucod_vit_forward_lora_infer_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # LoRA on the output projections (dense / fc2; o_proj / down_proj): its row kernels, and the five entry points with the modules' own per-layer table (NULL = _lora_mlp)
+    "ucod_lora_out_grad_workspace_bytes": (sz, [ci, ci, ci]),
+    "ucod_lora_out_fwd": (ci, [vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_out_grad_s": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, vp]),
+    "ucod_lora_out_grad_x": (ci, [vp, ci, vp, vp, vp, ci, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_vit_train_workspace_bytes_lora_out": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_forward_train_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_backward_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
+    "ucod_vit_lora_infer_workspace_bytes_lora_out": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_forward_lora_infer_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     # merging trained LoRA matrices into ordinary weights, and the device form of the LayerNorm fold (fp16-operand build) for the merged weight
     "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
     "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),

@@ -778,17 +778,23 @@ _REFUSED = {
     "weights_out": "its input is written by the weights_in GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
     "projection": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
 }
+_OUT = ("dense", "fc2")                                      # the output projections ``allow_out`` builds, by leaf name (attention.output.dense, mlp.fc2)
+_SWIGLU_OUT = ("its input, the SwiGLU hidden, is not a saved activation: it would have to be recomputed from the interleaved, padded [M, 2F] pre-activation, "
+               "which is not built yet")
 
 
-def lora_targets(target_modules=None, mlp="gelu", n_layers=1):
+def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False):
     """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> ((query, key, value) as booleans, the MLP
     input projection's name or None).  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``.  Built: any
     subset of query / key / value and the MLP input projection (``fc1`` on a GELU checkpoint, ``weights_in`` on a SwiGLU one) -- the modules whose input
-    is a LayerNorm output, which the LayerNorm kernel can extend by the LoRA down-projection.  None = the reference's query / key / value."""
+    is a LayerNorm output, which the LayerNorm kernel can extend by the LoRA down-projection.  None = the reference's query / key / value.
+    ``allow_out=True`` also accepts the output projections ``dense`` (attention.output.dense) and, on a GELU checkpoint, ``fc2`` -- row kernels beside their GEMMs
+    (include/ucod_dpl.h: ucod_lora_out_fwd) -- and returns a third element: the accepted ones of ("dense", "fc2"), in that order.  ``weights_out`` stays refused."""
     if mlp not in _MLP_IN:
         raise ValueError(f"mlp must be 'gelu' or 'swiglu', got {mlp!r}")
     if target_modules is None:
-        return (True, True, True), None
+        return ((True, True, True), None, ()) if allow_out else ((True, True, True), None)
+    refused = dict({k: v for k, v in _REFUSED.items() if k not in _OUT}, weights_out=_SWIGLU_OUT) if allow_out else _REFUSED
     if isinstance(target_modules, str):
         raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
     targets = list(target_modules)
@@ -808,18 +814,21 @@ def lora_targets(target_modules=None, mlp="gelu", n_layers=1):
             if last == other:
                 raise ValueError(f"target module {t!r}: this checkpoint has the {mlp.upper() if mlp == 'gelu' else 'SwiGLU'} MLP, whose input projection is "
                                  f"{mlp_in!r}, not {other!r}")
-            reason = _REFUSED.get(last, "no Linear module of the backbone has that name")
+            reason = refused.get(last, "no Linear module of the backbone has that name")
             raise NotImplementedError(f"LoRA target module {t!r} is not built: {reason}")
         for n in found:
             leaf = n.rsplit(".", 1)[-1]
-            if leaf in _REFUSED:
-                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {_REFUSED[leaf]}")
+            if leaf in refused:
+                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {refused[leaf]}")
             hit.add(n)
     per_layer = [{n.split(".", 3)[3] for n in hit if n.startswith(f"encoder.layer.{i}.")} for i in range(n_layers)]
     if any(pl != per_layer[0] for pl in per_layer):
         raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
     qkv = tuple("attention.attention." + n in per_layer[0] for n in _QKV)
-    return qkv, (mlp_in if "mlp." + mlp_in in per_layer[0] else None)
+    mlp_hit = mlp_in if "mlp." + mlp_in in per_layer[0] else None
+    if not allow_out:
+        return qkv, mlp_hit
+    return qkv, mlp_hit, tuple(leaf for leaf, path in zip(_OUT, ("attention.output.dense", "mlp.fc2")) if path in per_layer[0])
 
 
 _QKV3 = ("q_proj", "k_proj", "v_proj")                       # DINOv3ViTAttention's projections, in the order of _QKV
@@ -834,11 +843,21 @@ _REFUSED3 = {
 _DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", "weights_out", "projection")
 
 
-def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer."):
+_OUT3 = ("o_proj", "down_proj")                             # DINOv3's names of the two output projections, in the order of _OUT
+
+
+def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False):
     """``lora_targets`` for a DINOv3 checkpoint, whose modules are ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj``
-    too): any non-empty subset of q_proj / k_proj / v_proj by peft's suffix rule, None = all three.  Returns the (q, k, v) booleans; no MLP module is built."""
+    too): any non-empty subset of q_proj / k_proj / v_proj by peft's suffix rule, None = all three.  Returns the (q, k, v) booleans; no MLP input module is built.
+    ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` (``lora_targets``) and returns ((q, k, v), the accepted ones of
+    ("o_proj", "down_proj")); the gated MLP's ``down_proj`` stays refused."""
     if target_modules is None:
-        return (True, True, True)
+        return ((True, True, True), ()) if allow_out else (True, True, True)
+    refused = _REFUSED3
+    if allow_out:
+        refused = {k: v for k, v in _REFUSED3.items() if k not in _OUT3}
+        if gated:
+            refused["down_proj"] = _SWIGLU_OUT
     if isinstance(target_modules, str):
         raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
     targets = list(target_modules)
@@ -856,16 +875,19 @@ def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path
             if last in _DINOV2_LEAVES:
                 raise ValueError(f"target module {t!r} is a DINOv2 name: a DINOv3 checkpoint's attention projections are q_proj / k_proj / v_proj "
                                  f"({layer_path}{{i}}.attention.{{q,k,v}}_proj)")
-            raise NotImplementedError(f"LoRA target module {t!r} is not built: {_REFUSED3.get(last, 'no Linear module of the backbone has that name')}")
+            raise NotImplementedError(f"LoRA target module {t!r} is not built: {refused.get(last, 'no Linear module of the backbone has that name')}")
         for n in found:
             leaf = n.rsplit(".", 1)[-1]
-            if leaf in _REFUSED3:
-                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {_REFUSED3[leaf]}")
+            if leaf in refused:
+                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {refused[leaf]}")
             hit.add(n)
     per_layer = [{n[len(f"{layer_path}{i}."):] for n in hit if n.startswith(f"{layer_path}{i}.")} for i in range(n_layers)]
     if any(pl != per_layer[0] for pl in per_layer):
         raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
-    return tuple("attention." + n in per_layer[0] for n in _QKV3)
+    qkv = tuple("attention." + n in per_layer[0] for n in _QKV3)
+    if not allow_out:
+        return qkv
+    return qkv, tuple(leaf for leaf, path in zip(_OUT3, ("attention.o_proj", "mlp.down_proj")) if path in per_layer[0])
 
 
 def _dinov3_paths(sd):
@@ -892,17 +914,26 @@ class ViTLoRAEngine(ViTEngine):
     order (SwiGLU), and the passes run the _lora_mlp entry points (include/ucod_dpl.h).  None = query / key / value: the engine as it always was.
 
     A DINOv3 checkpoint (``allow_rope=True``) has its own module names -- ``{model.,}layer.{i}.attention.{q,k,v}_proj`` -- which ``target_modules``, the state dicts,
-    the merges and the adapter folder use; the arena layout is the same (q | k | v).  No MLP module is built for it yet."""
+    the merges and the adapter folder use; the arena layout is the same (q | k | v).  No MLP input module is built for it yet.
+
+    ``allow_out=True`` also takes the output projections -- ``dense`` (attention.output.dense) and ``fc2`` on a DINOv2 GELU checkpoint, ``o_proj`` and ``down_proj``
+    on a non-gated DINOv3 one -- as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x; the _lora_out entry points).  The arena
+    row then ends in [A_o (r x D) | B_o (D x r)] and [A_2 (r x F) | B_2 (D x r)], for the targeted ones only; 1 <= r <= 8.  The SwiGLU MLP's output projection stays
+    refused.  With the flag off, or on with neither module named, every pass is launch for launch what it was."""
+
+    # (defaults of an engine built without ``allow_out``: no output projection is targeted)
+    allow_out, out_targets, out_off, _out_paths = False, (False, False), (None, None), ("attention.output.dense", "mlp.fc2")
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0):
+                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
         ``allow_rope``: accept a DINOv3 checkpoint (rotary position embedding; ``rope_theta`` as ``ViTEngine``).  Its passes rotate q / k of the patch rows between
         the QKV GEMM and attention and apply the transposed rotation to dq / dk behind attention backward (include/ucod_dpl.h: ucod_rope_qk_ld,
         ucod_vit_train_desc.allow_rope).  Its modules are ``{model.,}layer.{i}.attention.{q,k,v}_proj`` (``lora_targets_dinov3``); a gated-MLP checkpoint
-        (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``."""
+        (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``.
+        ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``."""
         canon = normalize_state_dict(state_dict)
         if canon.get("rope") and not allow_rope:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a DINOv3 checkpoint (rotary position embedding, RoPE: the passes rotate q / k and "
@@ -915,10 +946,16 @@ class ViTLoRAEngine(ViTEngine):
             # the checkpoint's own names: layer path, module path below it, leaf names (what lora_state_dict, the merges and the adapter folder use)
             self._layer_path = _dinov3_paths(state_dict)[1]
             self._qkv_names, self._qkv_dir = _QKV3, "attention."
-            self.targets, self.mlp_target = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path), None
+            self._out_paths, out_leaves = ("attention.o_proj", "mlp.down_proj"), _OUT3
+            hit = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path, **({"allow_out": True} if allow_out else {}))
+            (self.targets, out_hit), self.mlp_target = (hit if allow_out else (hit, ())), None
         else:
             self._layer_path, self._qkv_names, self._qkv_dir = "encoder.layer.", _QKV, "attention.attention."
-            self.targets, self.mlp_target = lora_targets(target_modules, mlp_kind, len(canon["layers"]))
+            self._out_paths, out_leaves = ("attention.output.dense", "mlp.fc2"), _OUT
+            hit = lora_targets(target_modules, mlp_kind, len(canon["layers"]), **({"allow_out": True} if allow_out else {}))
+            self.targets, self.mlp_target, out_hit = hit if allow_out else hit + ((),)
+        self.allow_out = bool(allow_out)
+        self.out_targets = tuple(leaf in out_hit for leaf in out_leaves)          # (attention output projection, MLP output projection)
         self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
         if mlp_kind == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
@@ -949,7 +986,17 @@ class ViTLoRAEngine(ViTEngine):
             if self.lib.ucod_lora_mlp_grad_workspace_bytes(self.N1, D) == 0:
                 raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= 8192 rows of {self.mlp_target}")
         self.qkv_numel = 6 * r * D
-        self.lora = torch.zeros(L, self.qkv_numel + (r * (D + self.N1) if self.mlp_target is not None else 0), dtype=torch.float32, device=dev)
+        numel = self.qkv_numel + (r * (D + self.N1) if self.mlp_target is not None else 0)
+        self.out_off = [None, None]                     # where [A | B] of each targeted output module starts in a layer's arena row
+        for m, K in enumerate((D, self.F)):
+            if not self.out_targets[m]:
+                continue
+            if r > N.LORA_MLP_MAX_R:
+                raise ValueError(f"LoRA rank {r} unsupported with an output projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its kernels keep u and t {N.LORA_OUT_W} wide)")
+            if self.lib.ucod_lora_out_grad_workspace_bytes(r, K, D) == 0:
+                raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {K}")
+            self.out_off[m], numel = numel, numel + r * (K + D)
+        self.lora = torch.zeros(L, numel, dtype=torch.float32, device=dev)
         bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
         for p in range(3):
@@ -957,6 +1004,9 @@ class ViTLoRAEngine(ViTEngine):
                 self.lora[:, p * 2 * r * D:p * 2 * r * D + r * D] = a[:, p].to(dev)
         if self.mlp_target is not None:                 # drawn after q / k / v: the default engine's stream is untouched
             self.lora[:, self.qkv_numel:self.qkv_numel + r * D] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
+        for m, K in enumerate((D, self.F)):             # drawn after everything else: every engine without them keeps its stream (A: U(+-1/sqrt(fan_in)), B zeros)
+            if self.out_targets[m]:
+                self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = ((torch.rand(L, r * K, generator=generator) * 2 - 1) / math.sqrt(K)).to(dev)
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
         self.train_layers = []                          # rows of the training table without its two LoRA slots (native.VIT_TRAIN_SLOTS)
@@ -988,6 +1038,11 @@ class ViTLoRAEngine(ViTEngine):
         rD = self.r * self.D
         return slice(self.qkv_numel, self.qkv_numel + rD), slice(self.qkv_numel + rD, self.qkv_numel + rD + self.N1 * self.r)
 
+    def _out_slices(self, m):
+        """(A, B) of output module ``m`` (0 = attention output projection [r, D], 1 = MLP output projection [r, F]; B is [D, r]) in one layer's arena row."""
+        o, rK = self.out_off[m], self.r * (self.D, self.F)[m]
+        return slice(o, o + rK), slice(o + rK, o + rK + self.D * self.r)
+
     def lora_state_dict(self, grads=False, prefix=None):
         """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
         projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded.  A DINOv3
@@ -1009,6 +1064,11 @@ class ViTLoRAEngine(ViTEngine):
                 b = src[i, sb].reshape(self.N1, self.r)
                 out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
                 out[base + "lora_B.weight"] = lora_b_from_engine(b, self._F0) if self.mlp == N.UCOD_MLP_SWIGLU else b.clone()
+            for m, path in enumerate(self._out_paths):
+                if self.out_targets[m]:
+                    sa, sb = self._out_slices(m)
+                    out[f"{prefix}{i}.{path}.lora_A.weight"] = src[i, sa].reshape(self.r, -1).clone()
+                    out[f"{prefix}{i}.{path}.lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
         return out
 
     def load_lora_state_dict(self, sd, prefix=None):
@@ -1016,6 +1076,7 @@ class ViTLoRAEngine(ViTEngine):
         prefix = self._layer_path if prefix is None else prefix
         names = [f"{self._qkv_dir}{name}." for p, name in enumerate(self._qkv_names) if self.targets[p]]
         names += [f"mlp.{self.mlp_target}."] if self.mlp_target is not None else []
+        names += [path + "." for m, path in enumerate(self._out_paths) if self.out_targets[m]]
         want = {f"{prefix}{i}.{n}lora_{ab}.weight" for i in range(self.L) for n in names for ab in "AB"}
         extra = sorted(k for k in sd if ".lora_" in k and k.startswith(prefix) and k not in want)
         if extra:
@@ -1038,6 +1099,13 @@ class ViTLoRAEngine(ViTEngine):
                     raise ValueError(f"{base}lora_B.weight has shape {tuple(b.shape)}")
                 self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
                 self.lora[i, sb] = (lora_b_to_engine(b) if self.mlp == N.UCOD_MLP_SWIGLU else b).reshape(-1)
+            for m, path in enumerate(self._out_paths):
+                if self.out_targets[m]:
+                    sa, sb = self._out_slices(m)
+                    a, b = take(f"{prefix}{i}.{path}.lora_A.weight"), take(f"{prefix}{i}.{path}.lora_B.weight")
+                    if tuple(a.shape) != (self.r, (self.D, self.F)[m]) or tuple(b.shape) != (self.D, self.r):
+                        raise ValueError(f"{prefix}{i}.{path}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
+                    self.lora[i, sa], self.lora[i, sb] = a.reshape(-1), b.reshape(-1)
         self.repack()
 
     def train(self, mode=True):
@@ -1082,6 +1150,17 @@ class ViTLoRAEngine(ViTEngine):
         TM = (C.c_void_p * len(mptrs))(*[t.data_ptr() for t in mptrs]) if mptrs else None
         return T, (C.c_void_p * len(tptrs))(*[t.data_ptr() for t in tptrs]), TM, keep + tptrs + mptrs
 
+    def _out_table(self, grad):
+        """The output modules' table (native.VIT_TRAIN_OUT_SLOTS; an untargeted module's two slots are NULL) with ``grad`` [L, P] in its gradient slots, or None when
+        neither is targeted -- the passes then run the entry points, and the launches, they always did."""
+        if not any(self.out_targets):
+            return None
+        ptrs = []
+        for i in range(self.L):
+            for o in self.out_off:
+                ptrs += [None, None] if o is None else [self.lora[i, o:].data_ptr(), grad[i, o:].data_ptr()]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
     def _chunks(self, B):
         """Image-parallel sub-batches (``self.train_streams``, default 2): as in ViTEngine.forward, every kernel of both passes is
         per image except the LoRA-gradient reduction over rows, which is done per chunk into its own buffer and summed at the end."""
@@ -1115,7 +1194,13 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             self._chunk_seed[i] = t.seed
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
-            if TM is None:                                         # query / key / value only: the entry points (and launches) the engine always used
+            TO = self._out_table(self._tside_grad[i])
+            if TO is not None:                                     # an output projection is targeted: the _lora_out entry points (TM may be NULL there)
+                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_train_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
+                                                                     N.stream()), "ucod_vit_forward_train_lora_out")
+            elif TM is None:                                       # query / key / value only: the entry points (and launches) the engine always used
                 ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_mlp(C.byref(t), self.mlp))
                 with self._guard.bind():
                     N.check(self.lib.ucod_vit_forward_train_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
@@ -1146,7 +1231,13 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             t.vit.resid16 = int(bool(resid16))
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
-            if TM is None:
+            TO = self._out_table(self._tside_grad[i])
+            if TO is not None:
+                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
+                                                                          N.stream()), "ucod_vit_forward_lora_infer_lora_out")
+            elif TM is None:
                 ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_mlp(C.byref(t), self.mlp))
                 with self._guard.bind():
                     N.check(self.lib.ucod_vit_forward_lora_infer_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
@@ -1165,7 +1256,8 @@ class ViTLoRAEngine(ViTEngine):
         return key
 
     def backward(self, dkey):
-        """dkey [B, D, H/P, W/P] -> self.lora_grad (overwritten), returned as the flat [L, P] tensor (P = 6*r*D, plus r*(D + N1) with the MLP module)."""
+        """dkey [B, D, H/P, W/P] -> self.lora_grad (overwritten), returned as the flat [L, P] tensor (P = 6*r*D, plus r*(D + N1) with the MLP module, plus r*2D and
+        r*(F + D) with the output modules)."""
         if self._saved_for is None:
             raise RuntimeError("backward() without a preceding forward_train()")
         B, H, W = self._saved_for
@@ -1177,8 +1269,12 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
+            TO = self._out_table(self._tside_grad[i])
             ws = self._tside_ws[i]
-            if TM is None:
+            if TO is not None:
+                N.check(self.lib.ucod_vit_backward_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_backward_lora_out")
+            elif TM is None:
                 N.check(self.lib.ucod_vit_backward_mlp(C.byref(t), self.mlp, T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
             else:
                 N.check(self.lib.ucod_vit_backward_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
@@ -1196,7 +1292,8 @@ class ViTLoRAEngine(ViTEngine):
     def _targeted(self):
         """(module name below the layer path ``encoder.layer.{i}.``, its index among query / key / value or None for the MLP input projection) of every targeted module"""
         mods = [(f"{self._qkv_dir}{name}", p) for p, name in enumerate(self._qkv_names) if self.targets[p]]
-        return mods + ([(f"mlp.{self.mlp_target}", None)] if self.mlp_target is not None else [])
+        mods += [(f"mlp.{self.mlp_target}", None)] if self.mlp_target is not None else []
+        return mods + [(path, ("out", m)) for m, path in enumerate(self._out_paths) if self.out_targets[m]]     # (an output projection: ("out", 0 or 1))
 
     @staticmethod
     def _hf_prefix(sd):
@@ -1235,9 +1332,14 @@ class ViTLoRAEngine(ViTEngine):
                 key = f"{pref}{i}.{name}.weight"
                 w = base[key]
                 n, k = w.shape
-                if k != self.D:
+                if isinstance(p, tuple):                           # an output projection: W [D, K], A [r, K], B [D, r]; neither padded nor reordered
+                    if (n, k) != (self.D, (self.D, self.F)[p[1]]):
+                        raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine expects {(self.D, (self.D, self.F)[p[1]])}")
+                    sa, sb = self._out_slices(p[1])
+                    B = self.lora[i, sb]
+                elif k != self.D:
                     raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine has D = {self.D}")
-                if p is not None:
+                elif p is not None:
                     sa, sb = self._slices(p)
                     B = self.lora[i, sb]
                 else:
@@ -1292,6 +1394,17 @@ class ViTLoRAEngine(ViTEngine):
             row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
             for name, p in self._targeted():
                 w = base[f"{pref}{i}.{name}.weight"]
+                if isinstance(p, tuple):                           # an output projection: merged, cast into the live tensor; no LayerNorm stands in front of it, so no fold
+                    K = (D, self.F)[p[1]]
+                    if tuple(w.shape) != (D, K):
+                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(D, K)}")
+                    sa, sb = self._out_slices(p[1])
+                    buf = self._stage(2 * D * K)
+                    w0, merged = buf[:D * K].view(D, K), buf[D * K:2 * D * K].view(D, K)
+                    w0.copy_(w.detach())
+                    self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
+                    N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), row[(N.PROJ_W, N.FC2_W)[p[1]]].data_ptr(), D * K, st()), "ucod_cast_f32_bf16")
+                    continue
                 if p is not None:
                     n, r0, (sa, sb) = D, p * D, self._slices(p)
                     slot_w, slot_b, slot_c, g, be = N.QKV_W, N.QKV_B, N.QKV_COLSUM, row[N.LN1_G], row[N.LN1_B]
