@@ -58,6 +58,8 @@ extern "C" {
  * zero-fills the descriptor: a table is refused as before); with it set the training-pass drivers rotate q / k forward and dq / dk back. */
 /* (still 5) LoRA on the output projections (dense / fc2; o_proj / down_proj): ucod_lora_out_fwd, ucod_lora_out_grad_s, ucod_lora_out_grad_x and the _lora_out forms of
  * the five training-pass entry points were added; the _lora_mlp forms delegate to them with a NULL table and are launch for launch what they were. */
+/* (still 5) The MLP hidden in MFMA-fragment order ("BLK16" below): epilogues 23 / 24, ucod_gemm_bf16_blk16a, ucod_gemm_blk16_pair_ok and
+ * ucod_vit_forward_blk16 were added; the hidden's workspace slot is sized for 16 ceil(M / 16) rows; nothing existing changed. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -139,6 +141,11 @@ enum {
                                         out bf16 [M, 2N]:  out[m][8k+e] = g x2 sig (1 + x1 (1 - sig)),  out[m][8k+4+e] = g x1 sig  -- the cotangent of the interleaved
                                         weights_in output; f32 arithmetic, one bf16 rounding.  A lane's 8 GEMM columns drain into 32 contiguous bytes: no row of
                                         weights_out^T is duplicated */
+  /* fc1 + GELU with the hidden in BLK16 (MFMA-fragment) order, the A operand of ucod_gemm_bf16_blk16a -- see "BLK16" below.  Large-tile kernels only (variant 0, 9 or
+   * 13; N % 64 == 0, K >= 128, 16 ceil(M / 16) N 2 < 2^31); anything else is UCOD_EINVAL and the caller runs the row-major pair.  Every stored value is bit for bit
+   * what the row-major epilogue of the same variant stores. */
+  UCOD_EPI_LNFOLD_GELU_BLK16 = 23,   /* ucod_gemm_lnfold only: UCOD_EPI_LNFOLD_GELU_BF16, out 16-bit [16 ceil(M / 16), N] in BLK16 order */
+  UCOD_EPI_BIAS_GELU_BLK16 = 24,     /* ucod_gemm_bf16: UCOD_EPI_BIAS_GELU_BF16, out 16-bit [16 ceil(M / 16), N] in BLK16 order */
   UCOD_EPI_QKV_FP8 = 8               /* QKV projection of the fp8 attention path (BASELINE configs[4]): out = e4m3 bytes
                                         [3 (q|k|v)][Bimg*heads][Npad][64], Npad = tokens rounded up to 64, value = clamp((C + bias[n]) *
                                         scale[n], +-448); N = 3*heads*64, M = Bimg*tokens_per_image; large-tile kernel only */
@@ -162,6 +169,21 @@ int ucod_gemm_bf16(int epilogue, const void* A_bf16, const void* B_bf16, void* o
 int ucod_gemm_bf16_reg(int epilogue, const void* A_bf16, const void* B_bf16, void* out, int M, int N, int K,
                        const float* bias, const float* scale, const float* resid, const float* pos,
                        int tokens_per_image, int n_reg, int variant, void* stream);
+/* BLK16: an activation [M, F] of 16-bit values, F % 64 == 0, stored as the A operands of v_mfma_f32_16x16x32 instead of row-major, so that the producer (fc1) stores
+ * its accumulators straight from registers and the consumer (fc2) copies whole operands into LDS.  Rows are padded to Mp = 16 ceil(M / 16); the buffer holds Mp F values.
+ *   chunk (m, s, g): token row m, k-step s = 0 .. F/32 - 1, g = 0 .. 3: 16 bytes at byte offset  (((m / 16) (F / 32) + s) 64 + g 16 + (m % 16)) 16;
+ *   element e = 0 .. 7 of the chunk is hidden unit  pi(32 s + 8 g + e) = 32 s + 16 (e >> 2) + 4 g + (e & 3).
+ * One (m / 16, s) block is 1 KB in lane order (lane = 16 g + m % 16): one complete MFMA A operand.  pi permutes each group of 32 hidden units; the consumer's weight
+ * carries the same permutation on its K axis, W'[n][k] = W[n][pi(k)] (a dot product does not depend on the order of k).  Rows M .. Mp - 1 of the last block are
+ * UNSPECIFIED: they feed only output rows that are never stored, and the consumer keeps them out of its saturation test.
+ * ucod_gemm_bf16_blk16a: UCOD_EPI_BIAS_SCALE_RESID_H16 (row_partials NULL, nslot 0) or UCOD_EPI_BIAS_SCALE_RESID_H16_STATS with A in BLK16 order [Mp, K] and B = W'.
+ * M >= 2048, K >= 128, K % 64 == 0, N % 8 == 0 (STATS: N % 64 == 0), Mp K 2 < 2^31; UCOD_EINVAL otherwise.  Results differ from the row-major launch only by the order
+ * of the f32 additions over K. */
+int ucod_gemm_bf16_blk16a(int epilogue, const void* A_blk16, const void* B_perm, void* out, int M, int N, int K, const float* bias, const float* scale,
+                          const void* resid, float* row_partials, int nslot, void* stream);
+/* 1 when a BLK16 fc1 (N = F, K = D) and ucod_gemm_bf16_blk16a (N = D, K = F) on M rows both take a large-tile kernel for this ucod_gemm_bf16 variant, else 0 */
+int ucod_gemm_blk16_pair_ok(int M, int F, int D, int gemm_variant);
+
 /* LayerNorm folded into its consumer GEMM (epilogues UCOD_EPI_LNFOLD_*; libucod_dpl_f16.so only -- an MFMA takes both operands in one type and
  * the A operand here is the IEEE fp16 residual stream itself; the bf16 build returns UCOD_EINVAL).  Replaces nn.LayerNorm + nn.Linear of
  * modeling_dinov2.py:348-381 (norm1 -> attention, norm2 -> mlp) and dino.py:127-131:
@@ -476,6 +498,13 @@ enum { UCOD_MLP_GELU = 0, UCOD_MLP_SWIGLU = 1 };
 size_t ucod_vit_workspace_bytes_mlp(const ucod_vit_desc* d, int mlp);
 int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void* const* table_host, const float* img, float* key_out,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* ucod_vit_forward_mlp with the MLP hidden in BLK16 order where it pays (see "BLK16" above).  fc2_perm_host: NULL (= ucod_vit_forward_mlp), or d->L host pointers,
+ * each NULL or that layer's fc2 weight with the BLK16 column permutation, W'[n][k] = W[n][pi(k)], 16-bit [D, F].  A layer with an entry whose fc1 is LayerNorm-folded
+ * GELU (ln_fold, not the last layer of the pass) and whose two launches both take a large-tile kernel (ucod_gemm_blk16_pair_ok) writes its hidden with
+ * UCOD_EPI_LNFOLD_GELU_BLK16 and reads it with ucod_gemm_bf16_blk16a; every other layer, a small pass (Look-Twice at batch 1) and the SwiGLU MLP run the row-major pair
+ * on table entry +11.  Same workspace (ucod_vit_workspace_bytes_mlp).  Key maps differ from the row-major pass only by the order of fc2's f32 additions over K. */
+int ucod_vit_forward_blk16(const ucod_vit_desc* d, int mlp, const void* const* table_host, const void* const* fc2_perm_host, const float* img, float* key_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
 size_t ucod_vit_last_ln1_offset_mlp(const ucod_vit_desc* d, int mlp);
 size_t ucod_vit_split_workspace_bytes_mlp(const ucod_vit_desc* d, int terms, int mlp);
 size_t ucod_vit_split_stream_offset_mlp(const ucod_vit_desc* d, int terms, int mlp);

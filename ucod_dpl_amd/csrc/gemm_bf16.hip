@@ -178,7 +178,10 @@ __device__ __forceinline__ void wait_vmcnt_n() { asm volatile("s_waitcnt vmcnt(%
 #else
 #define UCOD_MIXED_BARRIER() __builtin_amdgcn_s_barrier()
 #endif
-template <int EPI, int NT, int XT, int AUX>
+// ABLK: the A operand is in BLK16 order (include/ucod_dpl.h; what fc1's blocked drain writes): a 16-row tile's two k-steps of a K-tile are 2 KB of contiguous
+// memory, copied by two whole-wave DMAs of 1 KB each into the slot in block order (16-row tile, k-step), and a fragment read is base + 16 lane: no swizzle.
+// Blocks past 16 ceil(M / 16) rows fail the descriptor's range check and arrive as zeros.  Everything else -- B side, K loop, waits, drain -- is unchanged.
+template <int EPI, int NT, int XT, int AUX, bool ABLK = false>
 __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0, int n0, int wave, int lane) {
   using Cfg = MixCfg<NT, XT>;
   constexpr int NPH = Cfg::NPH, IT = Cfg::IT, NI = Cfg::NI;
@@ -188,7 +191,7 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
   // group's slot, a third -- waves 0 and 1 only -- the 16 extra rows; rows past the end of the matrix fail the range check and arrive
   // as zeros; the K-tile offset rides in the scalar offset).  Half the address registers of per-lane 64-bit pointers: the kernel has
   // to stay at 224 VGPRs so that 64 per SIMD lane remain for the small kernels of a concurrent stream (decoder step, LayerNorm).
-  const unsigned long bytesA = (unsigned long)a.M * K * 2ul, bytesB = (unsigned long)a.N * K * 2ul;
+  const unsigned long bytesA = (unsigned long)(ABLK ? (a.M + 15) & ~15 : a.M) * K * 2ul, bytesB = (unsigned long)a.N * K * 2ul;
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_raw*>(a.A), 0, bytesA > 0xFFFFFFFFul ? 0xFFFFFFFFu : (unsigned)bytesA, 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_raw*>(a.B), 0, bytesB > 0xFFFFFFFFul ? 0xFFFFFFFFu : (unsigned)bytesB, 0x00020000);
   unsigned offA[2][2 + XT], offB[Cfg::NB];
@@ -197,7 +200,12 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
 #pragma unroll
     for (int i = 0; i < 2 + XT; ++i) {
       const int r = (i * 8 + wave) * 8 + (lane >> 3);
-      offA[h][i] = ((unsigned)(m0 + h * Cfg::RG + r) * (unsigned)K + (unsigned)swz(r, lane & 7) * 8u) * 2u;
+      if constexpr (ABLK) {                                     // slot block b = i * 8 + wave = (16-row tile b >> 1, k-step b & 1) of the group
+        const int b = i * 8 + wave;
+        offA[h][i] = ((unsigned)((m0 >> 4) + h * NI + (b >> 1)) * (unsigned)(K >> 5) + (unsigned)(b & 1)) * 1024u + (unsigned)lane * 16u;
+      } else {
+        offA[h][i] = ((unsigned)(m0 + h * Cfg::RG + r) * (unsigned)K + (unsigned)swz(r, lane & 7) * 8u) * 2u;
+      }
     }
 #pragma unroll
   for (int i = 0; i < Cfg::NB; ++i) {
@@ -206,7 +214,7 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
   }
   auto stageA = [&](int t, int h) {
     char* slot = smem + (t & 1) * Cfg::BUF + h * Cfg::SLOT;
-    const unsigned kt = (unsigned)t * (BK * 2);
+    const unsigned kt = (unsigned)t * (ABLK ? 2048u : BK * 2);   // (BLK16: two 1 KB blocks per K-tile)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(slot + (i * 8 + wave) * 1024), 16, offA[h][i], kt, 0, UCOD_LD_AUX_A);
@@ -230,6 +238,16 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
   FoldCtx<NT> fold;
   FoldReq freq;
   char* const fold_tab = smem + 2 * MixCfg<NT, 1>::BUF;
+  Blk16ColReq creq;
+  f32x4 cbq[kBlk16Out<EPI> && !kFold<EPI> ? NT : 1];           // blocked drain, unfolded: the bias of the lane's four columns per 16-wide tile (accumulator start)
+  if constexpr (kBlk16Out<EPI>) {
+    blk16_cols_request<EPI>(a, n0, wave, lane, creq);
+    if constexpr (!kFold<EPI>) {
+      const int nw = n0 + wn * 16 * NT;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) cbq[j] = *reinterpret_cast<const f32x4*>(a.bias + (nw < a.N ? nw + j * 16 + (lane >> 4) * 4 : 0));
+    }
+  }
   if constexpr (kFold<EPI>) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -262,6 +280,7 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
   float craw[NT];                                // the folded epilogues' column sums as loaded (the rank-one MFMA runs before the column scale)
   if constexpr (kFold<EPI>) {                   // table written here, read in the epilogue: every barrier of the K loop lies in between
     fold_finish(a, fold_tab, 2 * Cfg::RG, wave, lane, freq);
+    if constexpr (kBlk16Out<EPI>) blk16_cols_finish<EPI>(fold_tab + FOLD_TAB_BYTES, wave, lane, creq);
     fold.tab = reinterpret_cast<const float*>(fold_tab) + wm * Cfg::RG;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -275,7 +294,10 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){cb[j], cb[j], cb[j], cb[j]};
+    for (int j = 0; j < NT; ++j) {
+      if constexpr (kBlk16Out<EPI> && !kFold<EPI>) acc[i][j] = cbq[j];
+      else acc[i][j] = (f32x4){cb[j], cb[j], cb[j], cb[j]};
+    }
   UCOD_MIXED_BARRIER();
   if (wm == 1) UCOD_MIXED_BARRIER();            // staggered wave groups (see gemm_bf16_big_kernel)
 
@@ -310,7 +332,8 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const int r = ph * (IT * 16) + i * 16 + (lane & 15);
-          fa[i][ks] = *reinterpret_cast<const hx8*>(bufA + r * 128 + swz(r, ks * 4 + (lane >> 4)) * 16);
+          if constexpr (ABLK) fa[i][ks] = *reinterpret_cast<const hx8*>(bufA + ((ph * IT + i) * 2 + ks) * 1024 + lane * 16);
+          else fa[i][ks] = *reinterpret_cast<const hx8*>(bufA + r * 128 + swz(r, ks * 4 + (lane >> 4)) * 16);
         }
       if (ph == NPH - 1) {                               // RAW: every wave retires its tile-(t+1) DMAs before the barrier ahead of the first read
         if (more2) wait_vmcnt<Cfg::NB>(); else wait_vmcnt<0>();
@@ -325,7 +348,8 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
         for (int i = 0; i < IT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            acc[ph * IT + i][j] = UCOD_MFMA16(fa[i][ks], fb[j][ks], acc[ph * IT + i][j]);
+            acc[ph * IT + i][j] = kBlk16Out<EPI> ? UCOD_MFMA16(fb[j][ks], fa[i][ks], acc[ph * IT + i][j])     // C^T: see kBlk16Out
+                                                 : UCOD_MFMA16(fa[i][ks], fb[j][ks], acc[ph * IT + i][j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       UCOD_MIXED_BARRIER();
@@ -334,7 +358,11 @@ __device__ __forceinline__ void mixed_body(const GemmArgs& a, char* smem, int m0
   }
   if (wm == 0) UCOD_MIXED_BARRIER();
   if constexpr (kFold<EPI> && UCOD_FOLD_RANK1) fold_rank_one<NT, NI>(acc, fold.tab, craw, lane);
-  big_epilogue<EPI, NT, NI, AUX>(a, acc, cs, smem + wave * (32 * EPI_PITCH(16 * NT)), m0 + wm * Cfg::RG, n0 + wn * 16 * NT, lane, &fold);
+  if constexpr (kBlk16Out<EPI>) {
+    blk16_epilogue<EPI, NT, NI, AUX>(a, acc, fold.tab, reinterpret_cast<const float*>(fold_tab + FOLD_TAB_BYTES) + wn * 16 * NT, m0 + wm * Cfg::RG, n0 + wn * 16 * NT, lane);
+  } else {
+    big_epilogue<EPI, NT, NI, AUX, false, ABLK>(a, acc, cs, smem + wave * (32 * EPI_PITCH(16 * NT)), m0 + wm * Cfg::RG, n0 + wn * 16 * NT, lane, &fold);
+  }
 }
 
 // first row of row-tile tm when every `stride`-th row-tile (n_tall of them in all) is 32 rows taller
@@ -345,9 +373,9 @@ __device__ __forceinline__ int mixed_row0(int tm, int n_tall, int stride, bool& 
   return tm * 256 + nb * 32;
 }
 
-template <int EPI, int NT, int AUX = 0>
+template <int EPI, int NT, int AUX = 0, bool ABLK = false>
 __global__ __launch_bounds__(512) void gemm_bf16_mixed_kernel(const GemmArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * MixCfg<NT, 1>::BUF + (kFold<EPI> ? FOLD_TAB_BYTES : 0)];   // (+ the folded epilogues' row table)
+  __shared__ __attribute__((aligned(16))) char smem[2 * MixCfg<NT, 1>::BUF + kFoldSmemBytes<EPI>];   // (+ the folded epilogues' row table)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nwg = a.tiles_m * a.tiles_n;
@@ -359,8 +387,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_mixed_kernel(const GemmArgs a) 
   bool tall;
   const int m0 = mixed_row0(tm, a.main_tiles /* n_tall */, a.patches_per_wg /* stride */, tall);
   const int n0 = tn * MixCfg<NT, 0>::BN_;
-  if (tall) mixed_body<EPI, NT, 1, AUX>(a, smem, m0, n0, wave, lane);
-  else mixed_body<EPI, NT, 0, AUX>(a, smem, m0, n0, wave, lane);
+  if (tall) mixed_body<EPI, NT, 1, AUX, ABLK>(a, smem, m0, n0, wave, lane);
+  else mixed_body<EPI, NT, 0, AUX, ABLK>(a, smem, m0, n0, wave, lane);
 }
 
 // tile-order knobs of the large-tile launches (tuning(): read once per process)
@@ -530,11 +558,50 @@ static int launch_qkv_fp8(ucod::GemmArgs a, hipStream_t s) {
   return UCOD_OK;
 }
 
+// fc1 + GELU with the hidden in BLK16 order (kBlk16Out): the 256-wide large-tile kernels only -- one-shot (9) or mixed-height (13), chosen as launch() chooses for
+// the LayerNorm-folded row-major epilogue; no leftover patches (they would write row-major).  Anything else is refused: the caller then runs the row-major pair.
+template <int EPI>
+static int launch_blk16(ucod::GemmArgs a, int variant, hipStream_t s) {
+  using namespace ucod;
+  static_assert(kBlk16Out<EPI>, "blocked drain");
+  const long Mp = ((long)a.M + 15) & ~15L;
+  if (!a.bias || (a.N & 63) != 0 || a.K < 128 || Mp * a.N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
+  if ((long)a.M * a.K * 2 >= (1L << 32) || (long)a.N * a.K * 2 >= (1L << 32)) return UCOD_EINVAL;      // 32-bit operand offsets
+  if (variant != 0 && variant != 9 && variant != 13) return UCOD_EINVAL;
+  const MixedPlan mp = mixed_plan(a.M, a.N, 256);
+  if (variant == 0) {
+    if (!(a.M >= 2048 || (a.M >= 512 && (long)a.M * a.N >= (1L << 24)))) return UCOD_EINVAL;         // (launch(): big_enough)
+    variant = (mp.feasible && mp.rounds >= 3 && !tuning().no_mixed) ? 13 : 9;
+  }
+  a.tiles_n = cdiv(a.N, 256);
+  a.main_tiles = 0;
+  a.patches_per_wg = 0;
+  if (variant == 13 && mp.feasible) {
+    a.tiles_m = mp.tiles_m;
+    a.main_tiles = mp.n_tall;
+    a.patches_per_wg = mp.stride;
+    a.col_fast = a.tiles_n <= 4;
+    apply_order_tuning(a);
+    hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4, 2>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);   // (non-temporal stores, like the row-major hidden)
+  } else {
+    a.tiles_m = cdiv(a.M, 256);
+    a.col_fast = a.tiles_n <= 4;
+    apply_order_tuning(a);
+    hipLaunchKernelGGL((gemm_bf16_big_kernel<EPI, 4, true, 2>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
+  }
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
 // Out-projection / fc2 with the f16 residual stream (UCOD_EPI_BIAS_SCALE_RESID_H16): the mixed-height large-tile kernel, 256 wide.
-template <int EPI = UCOD_EPI_BIAS_SCALE_RESID_H16>
+// ABLK: the A operand in BLK16 order (fc2 behind fc1's blocked drain; B then carries the BLK16 column permutation).
+template <int EPI = UCOD_EPI_BIAS_SCALE_RESID_H16, bool ABLK = false>
 static int launch_resid_h16(ucod::GemmArgs a, hipStream_t s) {
   using namespace ucod;
   if ((a.N & 7) != 0 || a.K < 128 || !a.bias || !a.scale || !a.resid) return UCOD_EINVAL;
+  if constexpr (ABLK) {                                           // (tile overshoot included: block offsets stay far below 2^32)
+    if ((((long)a.M + 15) & ~15L) * a.K * 2 >= (1L << 31)) return UCOD_EINVAL;
+  }
   if constexpr (kStats<EPI>) {                                    // whole 64-column slots; the table's byte offsets fit the descriptors
     if ((a.N & 63) != 0 || !a.part_out || a.nslot != a.N / 64 || (long)a.M * a.nslot * 8 >= (1L << 31)) return UCOD_EINVAL;
   }
@@ -554,8 +621,12 @@ static int launch_resid_h16(ucod::GemmArgs a, hipStream_t s) {
   apply_order_tuning(a);
   // store policy of the new stream: default (kept in L2: the next launch reads it) or, UCOD_RESID16_NT=1, non-temporal (measurement switch, round 5)
   static const bool nt = [] { const char* e = ucod::lab_env("UCOD_RESID16_NT"); return e && e[0] == '1'; }();
-  if (nt) hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4, 2>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
-  else hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
+  if constexpr (ABLK) {
+    hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4, 0, true>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
+  } else {
+    if (nt) hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4, 2>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((gemm_bf16_mixed_kernel<EPI, 4>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
+  }
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
@@ -585,7 +656,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
                       const float* scale, const float* resid, const float* pos, int tokens_per_image, int variant,
                       void* stream, const void* aux, void* out2, const float* stats = nullptr, const float* colsum = nullptr,
                       const float* part_in = nullptr, float* part_out = nullptr, int nslot = 0, float eps = 0.f, float act_alpha = 1.f, float act_scale = 1.f,
-                      int n_reg = 0) {
+                      int n_reg = 0, bool a_blk16 = false) {
   using namespace ucod;
   if (!A || !B || !out || M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || n_reg < 0) return UCOD_EINVAL;
   GemmArgs a;
@@ -600,7 +671,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.nslot = nslot;
   a.eps = eps;
   a.ovf = (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS ||
-           epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 ||
+           epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BLK16 ||
            epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16)
               ? resid16_overflow_counter() : nullptr;           // (the folded consumers count rows outside the fold's range into the same word: fold_finish)
   a.stamps = nullptr;
@@ -627,7 +698,7 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
   a.col_fast = 0;
   a.bias_late = 0;
   hipStream_t s = (hipStream_t)stream;
-  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 ? PROF_GEMM_EPI21 : epilogue == UCOD_EPI_SWIGLU_BWD_BF16 ? PROF_GEMM_EPI22 : PROF_GEMM_EPI7)), s);
+  UCOD_PROF(epilogue == UCOD_EPI_QKV_FP8 || epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? 0 : (epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BLK16 || epilogue == UCOD_EPI_BIAS_GELU_BLK16 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT2 || epilogue == UCOD_EPI_BIAS_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT2 || epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) ? 1 : (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16 || epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) ? 2 : (epilogue == UCOD_EPI_PATCH_TOKENS_H16 || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) ? 3 : (epilogue >= 0 && epilogue <= 5 ? epilogue : (epilogue == UCOD_EPI_GELU_BWD_BF16 ? PROF_GEMM_EPI6 : epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 ? PROF_GEMM_EPI21 : epilogue == UCOD_EPI_SWIGLU_BWD_BF16 ? PROF_GEMM_EPI22 : PROF_GEMM_EPI7)), s);
   switch (epilogue) {
     case UCOD_EPI_BIAS_BF16:                                   // NULL bias (plain product) only in the large-tile kernels
       if (!bias && (variant == 1 || variant == 2 || variant == 12 || K < 128 || (N & 3))) return UCOD_EINVAL;   // (12: the 64 x 64 kernel reads the bias like 1 / 2)
@@ -650,6 +721,16 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       return launch<UCOD_EPI_SWIGLU_BWD_BF16>(a, variant, s);
 #endif
     case UCOD_EPI_BIAS_GELU_BF16: if (!bias) return UCOD_EINVAL; return launch<UCOD_EPI_BIAS_GELU_BF16>(a, variant, s);
+    case UCOD_EPI_BIAS_GELU_BLK16: return launch_blk16<UCOD_EPI_BIAS_GELU_BLK16>(a, variant, s);
+    case UCOD_EPI_LNFOLD_GELU_BLK16:
+#ifndef UCOD_HALF_F16
+      return UCOD_EINVAL;
+#else
+      if (!bias || (!stats && !part_in) || !colsum) return UCOD_EINVAL;
+      if (part_in && (nslot < 2 || nslot > 2 * FOLD_MAX_SLOT_PAIRS || (nslot & 1) || (long)M * nslot * 8 >= (1L << 32) - 16)) return UCOD_EINVAL;
+      if (!part_in && (long)M * 8 >= (1L << 32) - 16) return UCOD_EINVAL;
+      return launch_blk16<UCOD_EPI_LNFOLD_GELU_BLK16>(a, variant, s);
+#endif
     case UCOD_EPI_BIAS_GELU_SPLIT2:                                 // rows of 3 N bf16: the drains address them with 31-bit byte offsets
       if (!bias || (N & 7) != 0 || (long)M * 3 * N * 2 >= (1L << 31) - 16) return UCOD_EINVAL;
       return launch<UCOD_EPI_BIAS_GELU_SPLIT2>(a, variant, s);
@@ -694,6 +775,10 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       return epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 ? launch<UCOD_EPI_LNFOLD_BIAS_BF16>(a, variant, s) : launch<UCOD_EPI_LNFOLD_GELU_BF16>(a, variant, s);
     case UCOD_EPI_BIAS_SCALE_RESID_H16_STATS:
       if (!bias || !scale || !resid || !a.ovf || !part_out) return UCOD_EINVAL;
+      if (a_blk16) {
+        if (M >= 2048 && K >= 128 && (N & 7) == 0 && (long)N * K * 2 < (1L << 32)) return launch_resid_h16<UCOD_EPI_BIAS_SCALE_RESID_H16_STATS, true>(a, s);
+        return UCOD_EINVAL;
+      }
       if (M >= 2048 && K >= 128 && (N & 7) == 0 && (long)M * K * 2 < (1L << 32) && (long)N * K * 2 < (1L << 32)) return launch_resid_h16<UCOD_EPI_BIAS_SCALE_RESID_H16_STATS>(a, s);
       return UCOD_EINVAL;                                          // (small passes: the caller takes the plain epilogue + ucod_row_stats_h16)
     case UCOD_EPI_PATCH_TOKENS_H16_STATS:
@@ -701,6 +786,10 @@ static int gemm_entry(int epilogue, const void* A, const void* B, void* out, int
       return launch_patch_h16_stats(a, s);
     case UCOD_EPI_BIAS_SCALE_RESID_H16:
       if (!bias || !scale || !resid || !a.ovf) return UCOD_EINVAL;
+      if (a_blk16) {                                                // large-tile kernel only: a small pass stays row-major (the caller's choice)
+        if (M >= 2048 && K >= 128 && (N & 7) == 0 && (long)N * K * 2 < (1L << 32)) return launch_resid_h16<UCOD_EPI_BIAS_SCALE_RESID_H16, true>(a, s);
+        return UCOD_EINVAL;
+      }
       // large passes: the mixed-height large-tile kernel; small ones (a batch-1 Look-Twice pass) the 128 x 128 / 64 x 64 kernel, so that the
       // stream type is a property of the engine and not of the batch size
       if (M >= 2048 && K >= 128 && (N & 7) == 0 && (long)M * K * 2 < (1L << 32) && (long)N * K * 2 < (1L << 32)) return launch_resid_h16(a, s);
@@ -717,7 +806,7 @@ extern "C" int ucod_gemm_bf16(int epilogue, const void* A, const void* B, void* 
                               void* stream) {
   if (epilogue == UCOD_EPI_GELU_BWD_BF16 || epilogue == UCOD_EPI_BIAS_GELU_SAVE_BF16) return UCOD_EINVAL;   // need ucod_gemm_bf16_train
   if (epilogue == UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 || epilogue == UCOD_EPI_SWIGLU_BWD_BF16) return UCOD_EINVAL;   // (the same)
-  if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
+  if (epilogue == UCOD_EPI_LNFOLD_BIAS_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BF16 || epilogue == UCOD_EPI_LNFOLD_SWIGLU_BF16 || epilogue == UCOD_EPI_LNFOLD_GELU_BLK16) return UCOD_EINVAL;   // need ucod_gemm_lnfold
   if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS || epilogue == UCOD_EPI_PATCH_TOKENS_H16_STATS) return UCOD_EINVAL;   // need ucod_gemm_bf16_stats
   if (epilogue == UCOD_EPI_BIAS_GELU_SPLIT16 || epilogue == UCOD_EPI_BIAS_SWIGLU_SPLIT16) return UCOD_EINVAL;   // need ucod_split16_gemm_act
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, resid, pos, tokens_per_image, variant, stream, nullptr, nullptr);
@@ -750,7 +839,7 @@ extern "C" int ucod_gemm_lnfold(int epilogue, const void* x_f16, const void* w_f
 #ifndef UCOD_HALF_F16
   return UCOD_EINVAL;
 #else
-  if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && epilogue != UCOD_EPI_LNFOLD_GELU_BF16 && epilogue != UCOD_EPI_LNFOLD_SWIGLU_BF16) return UCOD_EINVAL;
+  if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && epilogue != UCOD_EPI_LNFOLD_GELU_BF16 && epilogue != UCOD_EPI_LNFOLD_SWIGLU_BF16 && epilogue != UCOD_EPI_LNFOLD_GELU_BLK16) return UCOD_EINVAL;
   if (epilogue != UCOD_EPI_LNFOLD_BIAS_BF16 && scale) return UCOD_EINVAL;
   return gemm_entry(epilogue, x_f16, w_folded, out, M, N, K, bias_folded, scale, nullptr, nullptr, 0, variant, stream, nullptr, nullptr, stats, colsum,
                     row_partials, nullptr, nslot, eps);
@@ -773,6 +862,33 @@ extern "C" int ucod_gemm_bf16_stats_reg(int epilogue, const void* A, const void*
   if (!row_partials || nslot <= 0 || n_reg < 0 || (n_reg > 0 && epilogue != UCOD_EPI_PATCH_TOKENS_H16_STATS)) return UCOD_EINVAL;
   return gemm_entry(epilogue, A, B, out, M, N, K, bias, scale, (const float*)resid, pos, tokens_per_image, 0, stream, nullptr, nullptr, nullptr, nullptr,
                     nullptr, row_partials, nslot, 0.f, 1.f, 1.f, n_reg);
+}
+
+// Out-projection / fc2 onto the fp16 residual stream with the A operand in BLK16 order (what UCOD_EPI_*_GELU_BLK16 wrote) and B with the BLK16 column permutation:
+// UCOD_EPI_BIAS_SCALE_RESID_H16 (row_partials NULL, nslot 0) or UCOD_EPI_BIAS_SCALE_RESID_H16_STATS.  Large passes only (the mixed-height large-tile kernel):
+// UCOD_EINVAL otherwise, nothing launched.
+extern "C" int ucod_gemm_bf16_blk16a(int epilogue, const void* A_blk16, const void* B_perm, void* out, int M, int N, int K, const float* bias, const float* scale,
+                                     const void* resid, float* row_partials, int nslot, void* stream) {
+  if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16) {
+    if (row_partials || nslot != 0) return UCOD_EINVAL;
+  } else if (epilogue == UCOD_EPI_BIAS_SCALE_RESID_H16_STATS) {
+    if (!row_partials || nslot <= 0) return UCOD_EINVAL;
+  } else {
+    return UCOD_EINVAL;
+  }
+  if ((K & 63) != 0) return UCOD_EINVAL;
+  return gemm_entry(epilogue, A_blk16, B_perm, out, M, N, K, bias, scale, (const float*)resid, nullptr, 0, 0, stream, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, row_partials, nslot, 0.f, 1.f, 1.f, 0, true);
+}
+
+// 1 when fc1 [M, F] <- [M, D] with a BLK16 epilogue and fc2 [M, D] <- [M, F] through ucod_gemm_bf16_blk16a BOTH take a large-tile kernel for this gemm_variant
+// (the checks of launch_blk16 and of the blk16a entry); the ViT driver asks before it sends a layer's hidden in BLK16 order.
+extern "C" int ucod_gemm_blk16_pair_ok(int M, int F, int D, int gemm_variant) {
+  if (M < 2048 || F < 128 || D < 128 || (F & 63) != 0 || (D & 63) != 0) return 0;
+  if (gemm_variant != 0 && gemm_variant != 9 && gemm_variant != 13) return 0;
+  const long Mp = ((long)M + 15) & ~15L;
+  if (Mp * F * 2 >= (1L << 31) - 16 || (long)M * D * 2 >= (1L << 32) || (long)F * D * 2 >= (1L << 32)) return 0;
+  return 1;
 }
 
 // The GEMM behind ucod_split16_gemm_act (split16.hip validates op, alpha and scale): the fp16-term split epilogues on this file's kernels.

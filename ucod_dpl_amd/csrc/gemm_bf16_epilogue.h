@@ -25,7 +25,12 @@ constexpr int BM = 128, BN = 128, BK = 64;
 // norm2 -> mlp).  The epilogue applies the two per-row scalars s = rstd, u = -mean * rstd:  out = s * acc + (u * c[n] + b'[n]).  The 16-bit
 // rounding of the LayerNorm output and the LayerNorm launch itself disappear.
 template <int EPI>
-constexpr bool kFold = (EPI == UCOD_EPI_LNFOLD_BIAS_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16);
+constexpr bool kFold = (EPI == UCOD_EPI_LNFOLD_BIAS_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_SWIGLU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BLK16);
+// fc1 + GELU with the hidden written in MFMA-fragment order (BLK16, include/ucod_dpl.h): the large-tile kernels call the MFMA with its operands exchanged, so that
+// the accumulators hold C^T -- a lane owns ONE row (lane & 15) and four consecutive columns per 16-wide tile -- and two adjacent column tiles of a lane are the 16
+// bytes fc2's A-operand fragment wants from that lane.  The drain is registers -> GELU -> one 16-byte store per lane and tile pair (blk16_epilogue): no LDS staging.
+template <int EPI>
+constexpr bool kBlk16Out = (EPI == UCOD_EPI_LNFOLD_GELU_BLK16 || EPI == UCOD_EPI_BIAS_GELU_BLK16);
 // The residual-stream producers that also leave row statistics for the next LayerNorm-folded consumer (round 5, step B): every wave adds up
 // the 64 values of a row it has just rounded to fp16 -- sum and sum of squared deviations from the slot's own mean, of the ROUNDED values (what the consumer's MFMA will read) -- and
 // stores the pair into slot (column / 64) of the row: no statistics launch, no atomics, one fixed order of additions.
@@ -54,7 +59,7 @@ constexpr int kOutPitchMul = (kSplit2Out<EPI> || kSplit16Gelu<EPI>) ? 3 : 1;    
 // (kSplit16Gelu is listed for the routing only -- 16-bit output, N % 8 == 0, row-major 8-column drains; every drain branches to split16_act8 / gelu_exact BEFORE
 // the gelu_erf2 calls that kGeluLike selects, and must keep doing so: the minimax form is three times too coarse for a 22-bit operand)
 template <int EPI>
-constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || kSplit2Out<EPI> || kSplit16Gelu<EPI>);   // erf-GELU, 16-bit output
+constexpr bool kGeluLike = (EPI == UCOD_EPI_BIAS_GELU_BF16 || EPI == UCOD_EPI_LNFOLD_GELU_BF16 || kSplit2Out<EPI> || kSplit16Gelu<EPI> || kBlk16Out<EPI>);   // erf-GELU, 16-bit output
 // DINOv2 ViT-g's SwiGLU MLP (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) on weights_in rows interleaved in blocks of 4 (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_BF16):
 // the 8 consecutive columns 8k .. 8k+7 that a lane of a row-major drain holds are x1 | x2 of the hidden units 4k .. 4k+3, so the product needs no other lane and no
 // other tile.  Output column = GEMM column / 2: one 8-byte store per lane and segment.  Only the row-major drains implement it (epilogue_store8_bf16 and the
@@ -575,6 +580,9 @@ constexpr int FOLD_TAB_ROWS = 288;                                 // >= rows of
 #define UCOD_FOLD_RANK1 0
 #endif
 constexpr int FOLD_TAB_BYTES = 3 * FOLD_TAB_ROWS * 4;              // s | u | -mean
+constexpr int FOLD_COL_BYTES = 2 * 256 * 4;                        // kFold && kBlk16Out: colsum | bias' of the tile's 256 columns behind the row table (blk16_epilogue reads quads)
+template <int EPI>
+constexpr int kFoldSmemBytes = kFold<EPI> ? FOLD_TAB_BYTES + (kBlk16Out<EPI> ? FOLD_COL_BYTES : 0) : 0;
 constexpr int FOLD_MAX_SLOT_PAIRS = 12;                            // nslot <= 24 (D <= 1536)
 template <int NT>
 struct FoldCtx {
@@ -706,7 +714,7 @@ __device__ __forceinline__ void fold_rank_one(f32x4 (&acc)[NI][NT], const float*
 //   * the f32 residual is double buffered: the loads of pass p+1 are issued BEFORE the stores of pass p, and vmcnt retires
 //     in order, so the wait for them leaves pass p's stores in flight.  (out may alias resid: passes touch disjoint rows.)
 template <int EPI>
-constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kSplit2Out<EPI> || kSplit16<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
+constexpr bool kColFused = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_GELU_BF16 || kBlk16Out<EPI> || kSplit2Out<EPI> || kSplit16<EPI> || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 ||
                             EPI == UCOD_EPI_BIAS_F32 || EPI == UCOD_EPI_GELU_BWD_BF16 || EPI == UCOD_EPI_BIAS_GELU_SAVE_BF16 ||
                             EPI == UCOD_EPI_QKV_FP8 || kResidH16<EPI> || kFold<EPI> || kSwiglu<EPI> || kSwigluBwd<EPI>);
 template <int EPI>
@@ -769,7 +777,7 @@ template <int EPI>
 constexpr bool kStageScaled = (EPI == UCOD_EPI_BIAS_BF16 || EPI == UCOD_EPI_BIAS_SCALE_RESID_F32 || EPI == UCOD_EPI_QKV_FP8 ||
                                kResidH16<EPI> || EPI == UCOD_EPI_LNFOLD_BIAS_BF16);
 
-template <int EPI, int NT, int NI, int AUX, bool FASTRM, class Stage>
+template <int EPI, int NT, int NI, int AUX, bool FASTRM, bool MASKDEAD = false, class Stage>
 __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Stage& stage, char* wbase, int m_first, int n_first, int lane) {
   constexpr int WCOLS = 16 * NT, PR = 32;
   constexpr int NP = (NI + 1) / 2;                    // passes of 32 rows; with NI odd the last pass holds 16 rows (rows 16..31 masked off)
@@ -1186,8 +1194,15 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
             float x[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { x[e] = v0[e] + r[e]; x[4 + e] = v1[e] + r[4 + e]; }
+            if constexpr (MASKDEAD) {                             // A in BLK16: the padding rows of its last 16-row block are unspecified -- only stored chunks count
+              float cm = 0.f;
 #pragma unroll
-            for (int e = 0; e < 8; e += 2) amax = __builtin_elementwise_maximum(amax, __builtin_elementwise_maximum(__builtin_fabsf(x[e]), __builtin_fabsf(x[e + 1])));   // (v_maximum3 with |.| modifiers; NaN-propagating)
+              for (int e = 0; e < 8; e += 2) cm = __builtin_elementwise_maximum(cm, __builtin_elementwise_maximum(__builtin_fabsf(x[e]), __builtin_fabsf(x[e + 1])));
+              amax = at(it, pass) < rec16 ? __builtin_elementwise_maximum(amax, cm) : amax;
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; e += 2) amax = __builtin_elementwise_maximum(amax, __builtin_elementwise_maximum(__builtin_fabsf(x[e]), __builtin_fabsf(x[e + 1])));   // (v_maximum3 with |.| modifiers; NaN-propagating)
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) w[e] = pack_f16x2(clamp_f16(x[2 * e]), clamp_f16(x[2 * e + 1]));
             if constexpr (kStats<EPI>) {                          // (sum, M2 about their mean) of the row's 64 ROUNDED values of this wave -> slot n_first / 64
@@ -1230,7 +1245,7 @@ __device__ __forceinline__ void big_epilogue_staged(const GemmArgs& a, const Sta
 
 
 // 16 x 16 accumulator tiles (C layout: col = lane & 15, row = 4 * (lane >> 4) + reg), bias already inside, cs = per-column scale
-template <int EPI, int NT, int NI = 8, int AUX = UCOD_ST_AUX, bool FASTRM = false>
+template <int EPI, int NT, int NI = 8, int AUX = UCOD_ST_AUX, bool FASTRM = false, bool MASKDEAD = false>
 __device__ __forceinline__ void big_epilogue(const GemmArgs& a, f32x4 (&acc)[NI][NT], const float (&cs)[NT], char* wbase,
                                              int m_first, int n_first, int lane, const FoldCtx<NT>* fold = nullptr) {
   constexpr int WCOLS = 16 * NT;
@@ -1272,7 +1287,81 @@ __device__ __forceinline__ void big_epilogue(const GemmArgs& a, f32x4 (&acc)[NI]
     }
     if ((pass + 1) * 2 < NI) fold_fetch(pass + 1);
   };
-  big_epilogue_staged<EPI, NT, NI, AUX, FASTRM>(a, stage, wbase, m_first, n_first, lane);
+  big_epilogue_staged<EPI, NT, NI, AUX, FASTRM, MASKDEAD>(a, stage, wbase, m_first, n_first, lane);
+}
+
+// ---- the blocked drain of fc1 (kBlk16Out) --------------------------------------------------------------------------------------------------
+// acc holds C^T: acc[i][j][r] = row m_first + 16 i + (lane & 15), column n_first + 16 j + 4 (lane >> 4) + r (the kernels exchange the MFMA's operands).  With
+// g = lane >> 4, the eight values {acc[i][2p][0..3], acc[i][2p+1][0..3]} are hidden units 32 s + 16 (e >> 2) + 4 g + (e & 3), e = 0..7, of k-step
+// s = n_first / 32 + p: chunk (m, s, g) of the BLK16 layout, at byte ((m / 16) (N / 32) + s) 1024 + 16 lane.  One wave store = one contiguous 1 KB block.
+// Same f32 operations on the same values as the row-major drain (the fold's fmaf pair, gelu_erf2, the conversion): the stored values are bit for bit its values.
+// The lane's row scalars (s, u) come from the tile's LDS row table, the column quads from the table behind it (written in the prologue: blk16_cols_finish).
+// Blocks whose first row lies at or past M, and waves whose columns lie past N (N % 64 == 0: a wave's 64 columns are all live or all dead), store nothing;
+// rows M .. 16 ceil(M / 16) - 1 of the last block are written with whatever the zero-filled operand rows give.
+struct Blk16ColReq { float c, b; };
+template <int EPI>
+__device__ __forceinline__ void blk16_cols_request(const GemmArgs& a, int n0, int wave, int lane, Blk16ColReq& r) {
+  if constexpr (kFold<EPI>) {
+    if (wave >= 4) return;
+    int n = n0 + wave * 64 + lane;
+    n = n < a.N ? n : a.N - 1;
+    r.c = a.colsum[n];
+    r.b = a.bias[n];
+  }
+}
+template <int EPI>
+__device__ __forceinline__ void blk16_cols_finish(char* col_tab, int wave, int lane, const Blk16ColReq& r) {
+  if constexpr (kFold<EPI>) {
+    if (wave >= 4) return;
+    float* t = reinterpret_cast<float*>(col_tab);
+    t[wave * 64 + lane] = r.c;
+    t[256 + wave * 64 + lane] = r.b;
+  }
+}
+template <int EPI, int NT, int NI, int AUX>
+__device__ __forceinline__ void blk16_epilogue(const GemmArgs& a, f32x4 (&acc)[NI][NT], const float* row_tab, const float* col_tab /* of this wave's columns */,
+                                               int m_first, int n_first, int lane) {
+  static_assert(NT == 4 && kBlk16Out<EPI>, "64-column waves");
+  constexpr unsigned DROP = 0xFFFFFFF0u;
+  const int Mp = (a.M + 15) & ~15;
+  const unsigned long bytes = (unsigned long)Mp * a.N * 2ul;                       // (launch(): < 2^31)
+  const auto rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(a.out), 0, (unsigned)bytes, 0x00020000);
+  const bool col_ok = n_first < a.N;
+  const unsigned blk_row = (unsigned)(a.N >> 5) * 1024u;                            // bytes of one 16-row block row
+  const unsigned off0 = (unsigned)(m_first >> 4) * blk_row + (unsigned)(n_first >> 5) * 1024u + (unsigned)lane * 16u;
+  f32x4 cq[NT], bq[NT];
+  if constexpr (kFold<EPI>) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      cq[j] = *reinterpret_cast<const f32x4*>(col_tab + j * 16 + (lane >> 4) * 4);
+      bq[j] = *reinterpret_cast<const f32x4*>(col_tab + 256 + j * 16 + (lane >> 4) * 4);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    float s = 1.f, u = 0.f;
+    if constexpr (kFold<EPI>) {
+      s = row_tab[i * 16 + (lane & 15)];
+      u = row_tab[FOLD_TAB_ROWS + i * 16 + (lane & 15)];
+    }
+    const bool live = col_ok && m_first + i * 16 < a.M;                             // (wave-uniform)
+#pragma unroll
+    for (int p = 0; p < NT / 2; ++p) {
+      u32x4 w;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 v = acc[i][2 * p + h];
+        if constexpr (kFold<EPI>) {
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) v[rg] = fmaf(s, v[rg], fmaf(u, cq[2 * p + h][rg], bq[2 * p + h][rg]));
+        }
+        const f32x2 g0 = gelu_erf2((f32x2){v[0], v[1]}), g1 = gelu_erf2((f32x2){v[2], v[3]});
+        w[2 * h] = pack_h2(g0[0], g0[1]);
+        w[2 * h + 1] = pack_h2(g1[0], g1[1]);
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(w, rs, live ? off0 + (unsigned)i * blk_row + (unsigned)p * 1024u : DROP, 0, AUX);
+    }
+  }
 }
 
 }  // namespace ucod

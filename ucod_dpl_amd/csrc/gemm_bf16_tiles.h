@@ -153,7 +153,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
   // 32-MFMA intervals instead of four 16-MFMA ones per K-tile and group) at the price of 16 more fragment registers.
   constexpr int IT = 8 / NPH;                                     // 16-row i-tiles per phase
   using Cfg = BigCfg<NT>;
-  __shared__ __attribute__((aligned(16))) char smem[2 * Cfg::BUF + (kFold<EPI> ? FOLD_TAB_BYTES : 0)];   // (+ the LayerNorm-folded epilogues' row table)
+  __shared__ __attribute__((aligned(16))) char smem[2 * Cfg::BUF + kFoldSmemBytes<EPI>];   // (+ the LayerNorm-folded epilogues' row table)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -217,6 +217,16 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
   FoldCtx<NT> fold;                                                // LayerNorm-folded epilogues: see gemm_bf16_epilogue.h
   FoldReq freq;
   char* const fold_tab = smem + 2 * Cfg::BUF;
+  Blk16ColReq creq;
+  f32x4 cbq[kBlk16Out<EPI> && !kFold<EPI> ? NT : 1];           // blocked drain, unfolded: the bias of the lane's four columns per 16-wide tile (accumulator start)
+  if constexpr (kBlk16Out<EPI>) {
+    blk16_cols_request<EPI>(a, n0, wave, lane, creq);
+    if constexpr (!kFold<EPI>) {
+      const int nw = n0 + wn * 16 * NT;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) cbq[j] = *reinterpret_cast<const f32x4*>(a.bias + (nw < a.N ? nw + j * 16 + (lane >> 4) * 4 : 0));
+    }
+  }
   if constexpr (kFold<EPI>) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -232,7 +242,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
   stageA(0, 1);
   stageB(0, 0, Cfg::NB);
   if (nt > 1) stageB(1, 0, Cfg::NB);
-  if constexpr (!kTrainOnly<EPI> && !kSwiglu<EPI>) {              // (training epilogues and SwiGLU: never in patches, see launch())
+  if constexpr (!kTrainOnly<EPI> && !kSwiglu<EPI> && !kBlk16Out<EPI>) {   // (training epilogues, SwiGLU and the blocked drain: never in patches, see launch())
     // scratch: the A0 slot of buffer 1, first written by the DMAs of K-tile 1 after the barrier below.  vmcnt retires in order,
     // so the patch's stores (older than every later DMA) never disturb the counted waits of the main loop.
     if (a.patches_per_wg > 0) patch_phase<EPI, Cfg::BN_>(a, smem + Cfg::BUF, orig, wave, lane);
@@ -242,6 +252,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
   float craw[NT];
   if constexpr (kFold<EPI>) {
     fold_finish(a, fold_tab, 256, wave, lane, freq);
+    if constexpr (kBlk16Out<EPI>) blk16_cols_finish<EPI>(fold_tab + FOLD_TAB_BYTES, wave, lane, creq);
     fold.tab = reinterpret_cast<const float*>(fold_tab) + wm * 128;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -255,7 +266,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){cb[j], cb[j], cb[j], cb[j]};
+    for (int j = 0; j < NT; ++j) {
+      if constexpr (kBlk16Out<EPI> && !kFold<EPI>) acc[i][j] = cbq[j];
+      else acc[i][j] = (f32x4){cb[j], cb[j], cb[j], cb[j]};
+    }
   __builtin_amdgcn_s_barrier();
   // STAGGER: the wm==1 waves run one barrier interval behind the wm==0 waves, so on every SIMD one wave is in its
   // MFMA interval while its partner is in its LDS-read / DMA-issue interval (two barriers per phase: R | M).
@@ -311,7 +325,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
         for (int i = 0; i < IT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            acc[ph * IT + i][j] = UCOD_MFMA16(fa[i][ks], fb[j][ks], acc[ph * IT + i][j]);
+            acc[ph * IT + i][j] = kBlk16Out<EPI> ? UCOD_MFMA16(fb[j][ks], fa[i][ks], acc[ph * IT + i][j])     // C^T: see kBlk16Out
+                                                 : UCOD_MFMA16(fa[i][ks], fb[j][ks], acc[ph * IT + i][j]);
       __builtin_amdgcn_s_setprio(0);
       if constexpr (!STAGGER) {
         if (ph == NPH - 1) {
@@ -327,7 +342,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_big_kernel(const GemmArgs a) {
 
   if constexpr (kFold<EPI> && UCOD_FOLD_RANK1) fold_rank_one<NT, 8>(acc, fold.tab, craw, lane);
   // epilogue through a wave-private LDS region (operand tiles are dead: last barrier passed)
-  big_epilogue<EPI, NT, 8, UCOD_ST_AUX, FASTRM>(a, acc, cs, smem + wave * (32 * EPI_PITCH(16 * NT)), m0 + wm * 128, n0 + wn * 16 * NT, lane, &fold);
+  if constexpr (kBlk16Out<EPI>) {
+    blk16_epilogue<EPI, NT, 8, UCOD_ST_AUX>(a, acc, fold.tab, reinterpret_cast<const float*>(fold_tab + FOLD_TAB_BYTES) + wn * 16 * NT, m0 + wm * 128, n0 + wn * 16 * NT, lane);
+  } else {
+    big_epilogue<EPI, NT, 8, UCOD_ST_AUX, FASTRM>(a, acc, cs, smem + wave * (32 * EPI_PITCH(16 * NT)), m0 + wm * 128, n0 + wn * 16 * NT, lane, &fold);
+  }
 }
 
 }  // namespace ucod

@@ -33,7 +33,7 @@ Plan make_plan(const ucod_vit_desc* d) {
   p.off_h = take((size_t)p.M * d->D * 2);
   p.off_qkv = take((size_t)p.M * 3 * d->D * 2);
   p.off_a = take((size_t)p.M * d->D * 2);
-  p.off_g = take((size_t)p.M * d->F * 2);
+  p.off_g = take((size_t)((p.M + 15) & ~15) * d->F * 2);           // (rows padded to whole 16-row blocks: the hidden may be written in BLK16 order)
   p.off_patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
   p.off_qscale = take((size_t)3 * d->D * 4);
   p.f8_bytes = d->attn_variant == 8 ? ucod_attention_fp8_workspace_bytes(d->B, p.tok, d->heads) : 0;   // Q8 | K8 | Vt8 of the fp8 attention path
@@ -73,8 +73,11 @@ extern "C" size_t ucod_vit_last_ln1_offset_mlp(const ucod_vit_desc* d, int mlp) 
 extern "C" size_t ucod_vit_workspace_bytes(const ucod_vit_desc* d) { return ucod_vit_workspace_bytes_mlp(d, UCOD_MLP_GELU); }
 extern "C" size_t ucod_vit_last_ln1_offset(const ucod_vit_desc* d) { return ucod_vit_last_ln1_offset_mlp(d, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void* const* T, const float* img, float* key_out, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
+// fc2_perm: NULL, or per layer the fc2 weight with the BLK16 column permutation (include/ucod_dpl.h) or NULL.  Where a layer has one, its LayerNorm-folded GELU fc1
+// and its fc2 both take a large-tile kernel (ucod_gemm_blk16_pair_ok) the hidden travels in BLK16 order: fc1 stores it from registers, fc2 copies whole MFMA operands.
+// Every other layer, pass size and MLP kind runs the row-major pair, as does every pass without the table.
+extern "C" int ucod_vit_forward_blk16(const ucod_vit_desc* d, int mlp, const void* const* T, const void* const* fc2_perm, const float* img, float* key_out,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
   if (!valid(d, mlp) || !T || !img || !key_out || !workspace) return UCOD_EINVAL;
   // SwiGLU (modeling_dinov2.py:300-315): fc1 = weights_in, 2 F rows interleaved in blocks of 4 (include/ucod_dpl.h); its epilogue writes silu(x1) * x2 [M, F]
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
@@ -140,15 +143,19 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
     else RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, R, stream));
   }
   // out-projection / fc2 (+ LayerScale + residual) into x; `want_part`: a folded consumer reads x next
-  auto resid_gemm = [&](const void* act, const void* w, const float* b, const float* ls, int K, bool want_part) -> int {
+  // (blk16: `act` is in BLK16 order and `w` carries its column permutation -- large-tile kernels only, so a refusal of the plain form is an error)
+  auto resid_gemm = [&](const void* act, const void* w, const float* b, const float* ls, int K, bool want_part, bool blk16 = false) -> int {
     have_part = false;
     if (want_part && !no_part) {
-      const int rc = ucod_gemm_bf16_stats(UCOD_EPI_BIAS_SCALE_RESID_H16_STATS, act, w, x, M, D, K, b, ls, x, nullptr, tok, part, nslot, stream);
+      const int rc = blk16 ? ucod_gemm_bf16_blk16a(UCOD_EPI_BIAS_SCALE_RESID_H16_STATS, act, w, x, M, D, K, b, ls, x, part, nslot, stream)
+                           : ucod_gemm_bf16_stats(UCOD_EPI_BIAS_SCALE_RESID_H16_STATS, act, w, x, M, D, K, b, ls, x, nullptr, tok, part, nslot, stream);
       if (rc == UCOD_OK) { have_part = true; return UCOD_OK; }
       if (rc != UCOD_EINVAL) return rc;
     }
+    if (blk16) return ucod_gemm_bf16_blk16a(UCOD_EPI_BIAS_SCALE_RESID_H16, act, w, x, M, D, K, b, ls, x, nullptr, 0, stream);
     return ucod_gemm_bf16(epi_resid, act, w, x, M, D, K, b, ls, x, nullptr, tok, gv, stream);
   };
+  const bool pair_fits = fc2_perm && !swiglu && r16 && ucod_gemm_blk16_pair_ok(M, F, D, gv) == 1;
 
   for (int l = 0; l < d->L; ++l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
@@ -178,17 +185,23 @@ extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void*
       RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, prescale ? 0.f : scale, (av == 5 || av == 66) ? av : 0, stream));
     }
     RUN(resid_gemm(a, W[4], (const float*)W[5], (const float*)W[6], D, fold));
+    const bool blk16 = fold && pair_fits && fc2_perm[l] != nullptr;
     if (fold) {
       if (!have_part) RUN(ucod_row_stats_h16(x, stats, M, D, d->eps, stream));
-      RUN(ucod_gemm_lnfold(swiglu ? UCOD_EPI_LNFOLD_SWIGLU_BF16 : UCOD_EPI_LNFOLD_GELU_BF16, x, W[9], g, M, swiglu ? 2 * F : F, D, (const float*)W[10], (const float*)W[15], have_part ? nullptr : stats,
+      RUN(ucod_gemm_lnfold(swiglu ? UCOD_EPI_LNFOLD_SWIGLU_BF16 : blk16 ? UCOD_EPI_LNFOLD_GELU_BLK16 : UCOD_EPI_LNFOLD_GELU_BF16, x, W[9], g, M, swiglu ? 2 * F : F, D, (const float*)W[10], (const float*)W[15], have_part ? nullptr : stats,
                            have_part ? part : nullptr, nslot, d->eps, nullptr, gv, stream));
     } else {
       RUN(layernorm((const float*)W[7], (const float*)W[8]));
       RUN(ucod_gemm_bf16(swiglu ? UCOD_EPI_BIAS_SWIGLU_BF16 : UCOD_EPI_BIAS_GELU_BF16, h, W[9], g, M, swiglu ? 2 * F : F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     }
-    RUN(resid_gemm(g, W[11], (const float*)W[12], (const float*)W[13], F, next_fold));
+    RUN(resid_gemm(g, blk16 ? fc2_perm[l] : W[11], (const float*)W[12], (const float*)W[13], F, next_fold, blk16));
   }
   return UCOD_OK;
+}
+
+extern "C" int ucod_vit_forward_mlp(const ucod_vit_desc* d, int mlp, const void* const* T, const float* img, float* key_out, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_blk16(d, mlp, T, nullptr, img, key_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ucod_vit_forward(const ucod_vit_desc* d, const void* const* T, const float* img, float* key_out, void* workspace,

@@ -32,6 +32,7 @@ EPI_BIAS_SWIGLU_BF16, EPI_LNFOLD_SWIGLU_BF16, EPI_BIAS_SWIGLU_SPLIT2 = 16, 17, 1
 # backbone-backward mode on the SwiGLU MLP (ucod_gemm_bf16_train only, bf16 library): the training-mode weights_in (hidden + saved interleaved pre-activation) and the
 # weights_out dgrad whose drain writes the cotangent of the interleaved weights_in output
 EPI_BIAS_SWIGLU_SAVE_BF16, EPI_SWIGLU_BWD_BF16 = 21, 22
+EPI_LNFOLD_GELU_BLK16, EPI_BIAS_GELU_BLK16 = 23, 24        # fc1 + GELU with the hidden in BLK16 (MFMA-fragment) order: the A operand of ucod_gemm_bf16_blk16a
 VIT_LAYER_STRIDE = 16
 # the slots of one layer's row of the pointer table, in table order (include/ucod_dpl.h: ucod_vit_forward); "_w" entries are 16-bit (or split) matrices, the rest f32
 VIT_LAYER_SLOTS = ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2", "aux0", "aux1")
@@ -145,6 +146,7 @@ SIGNATURES = {
     "ucod_cls_qk_reg": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ucod_cls_attention_reg": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
+    "ucod_gemm_bf16_blk16a": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),
     "ucod_cls_rows_h16_stats": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ucod_row_stats_h16": (ci, [vp, vp, ci, ci, cf, vp]),
@@ -169,6 +171,8 @@ SIGNATURES = {
     "ucod_vit_forward": (ci, [C.POINTER(VitDesc), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_vit_workspace_bytes_mlp": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_forward_mlp": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_forward_blk16": (ci, [C.POINTER(VitDesc), ci, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_gemm_blk16_pair_ok": (ci, [ci, ci, ci, ci]),
     "ucod_vit_last_ln1_offset_mlp": (sz, [C.POINTER(VitDesc), ci]),
     "ucod_vit_train_workspace_bytes": (sz, [C.POINTER(VitTrainDesc)]),
     "ucod_vit_forward_train": (ci, [C.POINTER(VitTrainDesc), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),

@@ -232,6 +232,10 @@ def layer_row(l, weight, vector, scales=None, aux=(None, None)):
     return row + list(aux)
 
 
+# UCOD_MLP_ROWMAJOR=1: the A/B switch of the BLK16 MLP hidden (ViTEngine.__init__), read once per process
+_MLP_ROWMAJOR = os.environ.get("UCOD_MLP_ROWMAJOR") == "1"
+
+
 class _SaturationGuard:
     """The saturation counter of ONE engine's fp16 values (the fp16 residual stream, the operands of the fp16-term split pass): the device word the library's kernels
     count into while it is bound, its pinned host copy, and the events behind the copies still in flight.  Engines never share one, so that a saturation is
@@ -511,6 +515,26 @@ class ViTEngine(_BackboneEngine):
                 fl[N.FC1_W], fl[N.FC1_B], fl[N.FC1_COLSUM] = (t.to(dev) for t in self._fold(cpu(src["ln2_g"]), cpu(src["ln2_b"]), cpu(src["fc1_w"]), cpu(src["fc1_b"])))
                 self.fold_layers.append(fl)
             self.q_row_scale = qs.to(dev)                          # (attn_variant == 1 takes Q unscaled: all ones then)
+        # The MLP hidden in MFMA-fragment order (blk16.py; include/ucod_dpl.h "BLK16"): fc2's weight once more with the layout's column permutation, built here
+        # because the weights are frozen.  The driver uses it for the layers whose fc1 is LayerNorm-folded GELU on passes large enough for the large-tile kernels and
+        # the plain weight everywhere else; UCOD_MLP_ROWMAJOR=1 (read once, at import) builds no permuted copy: every pass then runs the row-major pair.
+        self.fc2_perm = None
+        if self.ln_fold and self.mlp == N.UCOD_MLP_GELU and self.F % 64 == 0 and not _MLP_ROWMAJOR:
+            from .blk16 import pi
+            self._fc2_pi = pi(self.F).to(dev)
+            self.fc2_perm = [torch.index_select(l[N.FC2_W], 1, self._fc2_pi) for l in self.layers]
+
+    def refresh_fc2_perm(self, i):
+        """Rebuild layer i's permuted fc2 weight from the plain one, in place (``ViTLoRAEngine.merge_into`` after it has written a merged fc2 weight)."""
+        if self.fc2_perm is not None:
+            torch.index_select(self.layers[i][N.FC2_W], 1, self._fc2_pi, out=self.fc2_perm[i])
+
+    def _fc2_perm_table(self, n_layers=None):
+        """ctypes table of the permuted fc2 weights of a pass over the first n_layers layers, or None (the row-major pair)."""
+        if self.fc2_perm is None:
+            return None
+        L = self.L if n_layers is None else n_layers
+        return (C.c_void_p * L)(*[t.data_ptr() for t in self.fc2_perm[:L]])
 
     def _fold(self, gamma, beta, w, b, row_scale=None):
         """LayerNorm(gamma, beta) followed by Linear(w, b) [* row_scale per output] as one GEMM on the un-normalised rows (include/ucod_dpl.h:
@@ -529,8 +553,9 @@ class ViTEngine(_BackboneEngine):
     def param_bytes(self):
         # the folded tables are a SECOND copy of every layer's QKV / fc1 weights (+ their folded biases and column sums); the plain copies stay because
         # the last layer of a (possibly truncated) pass runs unfolded
+        # (+ the column-permuted copy of every fc2 weight: the BLK16 hidden)
         return super().param_bytes() + sum(t.numel() * t.element_size() for fl, l in zip(self.fold_layers or (), self.layers)
-                                           for t, t0 in zip(fl, l) if t is not None and t is not t0)
+                                           for t, t0 in zip(fl, l) if t is not None and t is not t0) + sum(t.numel() * t.element_size() for t in self.fc2_perm or ())
 
     def check_overflow(self, wait=False):
         """Raise FloatingPointError if any finished pass saturated the fp16 residual stream.  ``wait``: block until every pass enqueued so far
@@ -552,6 +577,7 @@ class ViTEngine(_BackboneEngine):
         img, key, H, W = self._inputs("ViTEngine", img, out, n_layers)
         B = img.shape[0]
         table, _keep = self._table(H // self.P, W // self.P, self._rows(n_layers))
+        perm = self._fc2_perm_table(n_layers)
         self.check_overflow()                                      # (non-blocking) passes that have finished since the last call
 
         def launch(b0, b1, ws):
@@ -559,7 +585,7 @@ class ViTEngine(_BackboneEngine):
             d = self._desc(b1 - b0, H, W, n_layers)
             ws = self._workspace(ws, self.lib.ucod_vit_workspace_bytes_mlp(C.byref(d), self.mlp))
             with self._guard.bind():
-                N.check(self.lib.ucod_vit_forward_mlp(C.byref(d), self.mlp, table, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                N.check(self.lib.ucod_vit_forward_blk16(C.byref(d), self.mlp, table, perm, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
                         "ucod_vit_forward")
             if self.resid16:
                 self._guard.arm(torch.cuda.current_stream(self.device))
@@ -1404,6 +1430,8 @@ class ViTLoRAEngine(ViTEngine):
                     w0.copy_(w.detach())
                     self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
                     N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), row[(N.PROJ_W, N.FC2_W)[p[1]]].data_ptr(), D * K, st()), "ucod_cast_f32_bf16")
+                    if p[1] == 1:
+                        engine.refresh_fc2_perm(i)                 # (the BLK16 copy of fc2 follows the plain one)
                     continue
                 if p is not None:
                     n, r0, (sa, sb) = D, p * D, self._slices(p)
