@@ -58,6 +58,8 @@ extern "C" {
  * zero-fills the descriptor: a table is refused as before); with it set the training-pass drivers rotate q / k forward and dq / dk back. */
 /* (still 5) LoRA on the output projections (dense / fc2; o_proj / down_proj): ucod_lora_out_fwd, ucod_lora_out_grad_s, ucod_lora_out_grad_x and the _lora_out forms of
  * the five training-pass entry points were added; the _lora_mlp forms delegate to them with a NULL table and are launch for launch what they were. */
+/* (still 5) LoRA on the SwiGLU MLP's output projection (weights_out; the gated down_proj): UCOD_LORA_OUT_ACT_SWIGLU of ucod_lora_out_grad_x_ex and the _lora_out_ex forms
+ * of the five training-pass entry points (one word of flags: UCOD_LORA_OUT_SWIGLU) were added; the _lora_out forms delegate to them with flags 0. */
 /* (still 5) The MLP hidden in MFMA-fragment order ("BLK16" below): epilogues 23 / 24, ucod_gemm_bf16_blk16a, ucod_gemm_blk16_pair_ok and
  * ucod_vit_forward_blk16 were added; the hidden's workspace slot is sized for 16 ceil(M / 16) rows; nothing existing changed. */
 #define UCOD_ABI_VERSION 5
@@ -678,6 +680,14 @@ int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, 
 #define UCOD_LORA_OUT_W 8
 #define UCOD_LORA_OUT_ACT_IDENTITY 0   /* x_in is the buffer itself (dense: the saved attention output) */
 #define UCOD_LORA_OUT_ACT_GELU 1       /* x_in = gelu(pre), the buffer is the saved pre-activation (fc2); gelu / gelu' are the fc1 drains' own fit */
+/* the SwiGLU MLP's output projection (Dinov2SwiGLUFFN.weights_out; the gated DINOv3 down_proj): K = the padded hidden width F, x_in_bf16 is the saved pre-activation
+ * [rows, 2K] interleaved in blocks of 4 (UCOD_EPI_BIAS_SWIGLU_BF16: columns 8k + e hold x1 of hidden unit 4k + e, columns 8k + 4 + e its x2), cot_bf16 is dpre
+ * [rows, 2K] in the same order, A is [r, K] in hidden-unit order, the mask index is row * K + unit.  The hidden h = silu(x1) * x2 is recomputed, never stored:
+ *   dA[j][u] += t[row][j] * m * h,   dg = m * sum_j t[row][j] A[j][u],   dpre(x1) += dg * x2 * sig * (1 + x1 (1 - sig)),   dpre(x2) += dg * x1 * sig
+ * with m = mask/(1-p), sig = sigmoid(x1); silu and the two factors are the weights_in / weights_out-dgrad drains' own.  Padded units (x1 = x2 = 0, zero A column)
+ * give exact zeros.  Its buffers are twice as wide as those of the other forms, so it has its own way in: ucod_lora_out_grad_x_ex with UCOD_LORA_OUT_SWIGLU in
+ * out_flags.  ucod_lora_out_grad_x itself, whose callers hold [rows, K] buffers, keeps refusing act = 2 as the invalid argument it always was. */
+#define UCOD_LORA_OUT_ACT_SWIGLU 2
 /* bytes of the per-block partials either gradient kernel needs; 0 for sizes outside the limits above */
 size_t ucod_lora_out_grad_workspace_bytes(int r, int K, int D);
 /* x_stream[m, :] += lambda * (scaling * (drop(x_in[m, :]) A^T) B^T), rows of D f32 (stream_f16 = 0) or IEEE fp16 (1: clamped and counted like the stream's other
@@ -692,6 +702,10 @@ int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const float* lora_o
  * (GELU: x_in_bf16 is the saved pre-activation, x_in = gelu(pre) is recomputed, never stored) (full_model.py:47-72). */
 int ucod_lora_out_grad_x(const void* x_in_bf16, int act, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out, void* workspace,
                          size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
+/* ucod_lora_out_grad_x with one word of flags behind `act` (UCOD_LORA_OUT_SWIGLU, defined below: needed for, and only meaningful with, UCOD_LORA_OUT_ACT_SWIGLU; an
+ * unknown bit is UCOD_EINVAL).  out_flags = 0 is ucod_lora_out_grad_x, which delegates here. */
+int ucod_lora_out_grad_x_ex(const void* x_in_bf16, int act, int out_flags, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out,
+                            void* workspace, size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
 /* The five whole-pass entry points with the output modules' own per-layer table TO (HOST array of DEVICE pointers), layer l at UCOD_VIT_TRAIN_OUT_STRIDE*l
  * (full_model.py:47-72; result = base(x) + scaling * B(A(dropout(x)))):
  *   +0 dense parameters f32 [r (D + D)] or NULL   +1 dense gradients   +2 fc2 parameters f32 [r (F + D)] or NULL   +3 fc2 gradients
@@ -700,7 +714,8 @@ int ucod_lora_out_grad_x(const void* x_in_bf16, int act, void* cot_bf16, const f
  * UCOD_MLP_GELU (the SwiGLU hidden would have to be recomputed from the interleaved, padded [M, 2F] pre-activation: not built).  Per layer below the last the
  * forward runs one ucod_lora_out_fwd behind each targeted module's residual GEMM (the training pass saves u: M * 32 bytes per layer and module), the backward one
  * ucod_lora_out_grad_s + ucod_lora_out_grad_x per module: fc2's behind the fc2 dgrad and in front of ucod_lora_mlp_grad / the fc1 dgrad, dense's between the
- * out-proj dgrad and ucod_attention_bwd.  The last layer's attention output and MLP never reach the key map: their gradients are written as zeros. */
+ * out-proj dgrad and ucod_attention_bwd.  The last layer's attention output and MLP never reach the key map: their gradients are written as zeros.
+ * (The SwiGLU MLP's output projection is taken by the _ex forms below with UCOD_LORA_OUT_SWIGLU; these five entry points refuse it as before.) */
 #define UCOD_VIT_TRAIN_OUT_STRIDE 4
 size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host, const void* const* out_table_host);
 int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
@@ -713,6 +728,29 @@ size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t
 int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
                                          const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
                                          size_t workspace_bytes, void* stream);
+/* The _ex forms take one more word of flags behind `mlp` (the idiom of ucod_vit_forward_split16_ex); out_flags = 0 is the entry point above, which delegates here,
+ * launch for launch and refusal for refusal.  An unknown bit: UCOD_EINVAL, sizes 0.
+ *   UCOD_LORA_OUT_SWIGLU   with UCOD_MLP_SWIGLU, slot +2 may be non-NULL: the LoRA module of the SwiGLU MLP's output projection (weights_out; the gated DINOv3
+ *                          down_proj), parameters f32 [r (F + D)] with F the padded hidden width (K = F <= 4096 as above: ViT-g and vits16plus; vith16plus's
+ *                          F = 5120 is refused).  Per layer below the last: one ucod_lora_out_fwd on the hidden [M, F] behind the weights_out residual GEMM (key
+ *                          3 L + l; the training pass saves u in the fc2 module's slots, so the workspace is the GELU formula with K = F); in the backward, behind
+ *                          the UCOD_EPI_SWIGLU_BWD_BF16 GEMM, ucod_lora_out_grad_s on s and ucod_lora_out_grad_x_ex(pre, UCOD_LORA_OUT_ACT_SWIGLU, dpre) in front of
+ *                          ucod_layernorm_lora_mlp / ucod_lora_mlp_grad and the weights_in dgrad.  The last layer's gradients are written as zeros.  With
+ *                          UCOD_MLP_GELU the flag changes nothing. */
+#define UCOD_LORA_OUT_SWIGLU 1
+size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,
+                                                  const void* const* out_table_host);
+int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
+                                       const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
+                                  const void* const* mlp_table_host, const void* const* out_table_host, const float* dkey, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+size_t ucod_vit_lora_infer_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,
+                                                       const void* const* out_table_host);
+int ucod_vit_forward_lora_infer_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
+                                            const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
+                                            size_t workspace_bytes, void* stream);
 
 /* The way out of LoRA mode: merging the trained matrices into ordinary weights (csrc/lora_merge.hip), so that every frozen-backbone engine runs the adapted model.
  * peft's merge of a LoRA module (what merge_and_unload() does to each module models/modules/full_model.py:47-72 wraps):  W <- W + (lora_alpha / r) B A.

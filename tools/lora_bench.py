@@ -31,8 +31,11 @@ grid, n_lead = side // patch, 1 + (DINOV3_ARCHS[arch] if v3 else 4 if arch.endsw
 kw = {} if targets is None else dict(target_modules=targets)
 if v3:
     kw.update(allow_rope=True, eps=1e-5)
-if targets is not None and any(t.rsplit(".", 1)[-1] in ("dense", "fc2", "o_proj", "down_proj") for t in targets):
+leaves = [t.rsplit(".", 1)[-1] for t in targets or ()]
+if any(t in ("dense", "fc2", "o_proj", "down_proj", "weights_out") for t in leaves):
     kw.update(allow_out=True)                             # the output projections are opt-in (ViTLoRAEngine)
+if "weights_out" in leaves or ("down_proj" in leaves and arch in SWIGLU_ARCHS):
+    kw.update(allow_swiglu_out=True)                      # ... and the SwiGLU MLP's has an opt-in of its own (the hidden is recomputed in the backward)
 eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
     print(f"targets {targets}: arena [{eng.L}, {eng.lora.shape[1]}]")
@@ -77,12 +80,19 @@ if any(getattr(eng, "out_targets", ())):
     # bf16, reads and writes the stream row and writes u; grad_s reads s [M, D] and u, writes t; grad_x reads x_in and reads and writes its cotangent
     M, D, sb = B * (n_lead + grid * grid), eng.D, 2 if eng.resid16 else 4
     Ks = [K for K, on in zip((D, eng.F), eng.out_targets) if on]
-    per = {"lora_out_fwd": sum(M * K * 2 + 2 * M * D * sb + M * 32 for K in Ks), "lora_out_grad_s": sum(M * D * 2 + 2 * M * 32 for K in Ks),
-           "lora_out_grad_x": sum(3 * M * K * 2 + M * 32 for K in Ks)}
+    # (the SwiGLU MLP's module: its grad_x has a profiler class of its own and moves twice the bytes per hidden unit -- pre and dpre are [M, 2F])
+    sw = bool(getattr(eng, "_out_flags", 0))
+    Kx = ([D] if eng.out_targets[0] else []) + ([eng.F] if eng.out_targets[1] and not sw else [])
+    per = {"lora_out_fwd": sum(M * K * 2 + 2 * M * D * sb + M * 32 for K in Ks) / len(Ks), "lora_out_grad_s": sum(M * D * 2 + 2 * M * 32 for K in Ks) / len(Ks)}
+    if Kx:
+        per["lora_out_grad_x"] = sum(3 * M * K * 2 + M * 32 for K in Kx) / len(Kx)
+    if sw:
+        per["lora_out_grad_x_swiglu"] = 3 * M * 2 * eng.F * 2 + M * 32
+    over = {"lora_out_grad_x": Kx, "lora_out_grad_x_swiglu": [eng.F]}
     for name, c, t in rows:
         if name in per:
-            byts = per[name] / len(Ks)                      # the mean over the targeted modules, as the average time is
-            print(f"  {name}: {byts / 1e6:.1f} MB per launch (mean of K = {Ks}), {t / c * 1e3:.1f} us -> {byts / (t / c * 1e-3) / 1e12:.2f} TB/s")
+            byts = per[name]                                # the mean over the modules that class runs for, as the average time is
+            print(f"  {name}: {byts / 1e6:.1f} MB per launch (mean of K = {over.get(name, Ks)}), {t / c * 1e3:.1f} us -> {byts / (t / c * 1e-3) / 1e12:.2f} TB/s")
 if giant:
     # the two SwiGLU training launches alone at this pass's shapes, and beside them (orientation) the launches they extend: UCOD_EPI_BIAS_SWIGLU_BF16 at (M, 2F, D),
     # which the SAVE form extends by one [M, 2F] store, and UCOD_EPI_GELU_BWD_BF16 at (M, F, D), which reads and writes half the bytes of the SwiGLU dgrad drain

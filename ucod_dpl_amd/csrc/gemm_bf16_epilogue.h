@@ -92,6 +92,13 @@ __device__ __forceinline__ float silu_fast(float x) {
 // d/d(x1, x2) of silu(x1) * x2 times the hidden cotangent g (kSwigluBwd; modeling_dinov2.py:313 differentiated), four hidden units: with sig = 1 / (1 + exp(-x1))
 //   d1 = g x2 sig (1 + x1 (1 - sig)),   d2 = g x1 sig.   x1 far below zero: exp overflows, sig = 0, both are 0 (x1 is a saved bf16 value: finite).  x1 = x2 = 0
 // (padded hidden units): both exactly 0.  -> the two thirds' packed pairs in the interleaved order d1[0..3] | d2[0..3]
+// (one hidden unit, f32 in and out: the form ucod_lora_out_grad_x's SwiGLU act shares with the drain below -- the same operations in the same order)
+__device__ __forceinline__ void swiglu_bwd1(float g, float x1, float x2, float& d1, float& d2) {
+  const float sig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x1 * -1.4426950408889634f));
+  const float gs = g * sig;
+  d1 = gs * x2 * fmaf(x1, 1.0f - sig, 1.0f);
+  d2 = gs * x1;
+}
 __device__ __forceinline__ u32x4 swiglu_bwd4(f32x4 g, u32x4 pw) {
   float x1[4], x2[4], d1[4], d2[4];
   unpack_h2(pw[0], x1[0], x1[1]);
@@ -99,12 +106,7 @@ __device__ __forceinline__ u32x4 swiglu_bwd4(f32x4 g, u32x4 pw) {
   unpack_h2(pw[2], x2[0], x2[1]);
   unpack_h2(pw[3], x2[2], x2[3]);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float sig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x1[e] * -1.4426950408889634f));
-    const float gs = g[e] * sig;
-    d1[e] = gs * x2[e] * fmaf(x1[e], 1.0f - sig, 1.0f);
-    d2[e] = gs * x1[e];
-  }
+  for (int e = 0; e < 4; ++e) swiglu_bwd1(g[e], x1[e], x2[e], d1[e], d2[e]);
   return (u32x4){pack_h2(d1[0], d1[1]), pack_h2(d1[2], d1[3]), pack_h2(d2[0], d2[1]), pack_h2(d2[2], d2[3])};
 }
 // (the split epilogue feeds an f32-equivalent pass: silu_f32 of common.h, shared with ucod_split_rows op 3)

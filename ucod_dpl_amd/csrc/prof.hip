@@ -13,7 +13,8 @@ static const char* kNames[PROF_NUM] = {
     "dba_colnorm", "dba_heads_fwd", "orth_gram_fwd", "dba_bwd", "dba_wgrad_f32", "disc_fwd", "disc_bwd", "apm_bce", "binarize",
     "adamw_ema", "crop_resize_norm", "cast", "layernorm_bwd", "lora_rowwise", "attention_bwd", "gemm_bf16_gelu_bwd",
     "gemm_bf16_fc1_gelu_save", "row_stats", "split_operands", "layernorm_split", "attention_split_fwd", "gemm_bf16_fc1_swiglu_save",
-    "gemm_bf16_swiglu_bwd", "layernorm_lora_mlp", "lora_mlp_grad", "layernorm_bwd_lora_mlp", "lora_out_fwd", "lora_out_grad_s", "lora_out_grad_x"};
+    "gemm_bf16_swiglu_bwd", "layernorm_lora_mlp", "lora_mlp_grad", "layernorm_bwd_lora_mlp", "lora_out_fwd", "lora_out_grad_s", "lora_out_grad_x",
+    "lora_out_grad_x_swiglu"};
 
 struct Rec { int cls; hipEvent_t a, b; };
 static std::mutex g_mu;

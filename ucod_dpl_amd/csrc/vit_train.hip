@@ -1363,6 +1363,75 @@ __global__ __launch_bounds__(128) void lora_out_grad_x_kernel(const bf16_raw* __
     }
 }
 
+// The SwiGLU form (UCOD_LORA_OUT_ACT_SWIGLU; Dinov2SwiGLUFFN's weights_out, the gated DINOv3 down_proj): the same structure over the saved interleaved
+// pre-activation [rows, 2K] and its cotangent dpre [rows, 2K] (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_BF16 -- 16 bytes hold x1 | x2 of four hidden units).  Thread
+// (blockIdx.y, tid) owns the 16-byte vector of hidden units 4v .. 4v+3 of every row: 4 x r values of A and 4 x r accumulators.  The hidden h = silu(x1) * x2 is
+// recomputed with the weights_in drain's silu_fast and never stored; the term's two derivative factors are the weights_out dgrad drain's own (swiglu_bwd1 with
+// g = mask/(1-p) * (t A)).  A padded unit has x1 = x2 = 0 and a zero A column: h, dA and both terms are exact zeros.  Partials [r][K] per blockIdx.x.
+template <int RW>
+__global__ __launch_bounds__(128) void lora_out_grad_x_swiglu_kernel(const bf16_raw* __restrict__ pre, bf16_raw* __restrict__ dpre, const float* __restrict__ t,
+                                                                     const float* __restrict__ A, int r, float* __restrict__ partial, int rows, int K, Drop drop) {
+  constexpr int RB = OUT_RB;
+  const int v = blockIdx.y * 128 + threadIdx.x;
+  if (v >= K / 4) return;                                        // (no barrier below)
+  float a[4][RW], acc[4][RW];
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+      a[e][j] = j < r ? A[(size_t)j * K + 4 * v + e] : 0.f;
+      acc[e][j] = 0.f;
+    }
+  const size_t ld = 2 * (size_t)K;
+  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB) {
+    u32x4 xw[RB], cw[RB];
+    float tt[RB][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const bool live = row0 + q < rows;
+      const size_t row = live ? row0 + q : rows - 1;
+      xw[q] = reinterpret_cast<const u32x4*>(pre + row * ld)[v];
+      cw[q] = reinterpret_cast<const u32x4*>(dpre + row * ld)[v];
+#pragma unroll
+      for (int j = 0; j < RW; ++j) tt[q][j] = (live && j < r) ? t[row * OUT_W + j] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      if (row0 + q >= rows) break;
+      float d1[4], d2[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {                              // words 0, 1: x1 of units 4v .. 4v+3; words 2, 3: x2
+        const unsigned w1 = xw[q][e >> 1], w2 = xw[q][2 + (e >> 1)];
+        const float x1 = __uint_as_float((e & 1) ? (w1 & 0xFFFF0000u) : (w1 << 16)), x2 = __uint_as_float((e & 1) ? (w2 & 0xFFFF0000u) : (w2 << 16));
+        float h = silu_fast(x1) * x2, m = 1.f;
+        if (drop.thresh) m = drop_scale(drop, 0, (unsigned)(row0 + q) * (unsigned)K + 4u * (unsigned)v + (unsigned)e);
+        h *= m;
+        float ta = 0.f;
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+          ta += tt[q][j] * a[e][j];
+          acc[e][j] += tt[q][j] * h;
+        }
+        swiglu_bwd1(m * ta, x1, x2, d1[e], d2[e]);
+      }
+      u32x4 o;
+#pragma unroll
+      for (int w = 0; w < 2; ++w) {
+        const float c10 = __uint_as_float(cw[q][w] << 16), c11 = __uint_as_float(cw[q][w] & 0xFFFF0000u);
+        const float c20 = __uint_as_float(cw[q][2 + w] << 16), c21 = __uint_as_float(cw[q][2 + w] & 0xFFFF0000u);
+        o[w] = pack_bf16x2(c10 + d1[2 * w], c11 + d1[2 * w + 1]);
+        o[2 + w] = pack_bf16x2(c20 + d2[2 * w], c21 + d2[2 * w + 1]);
+      }
+      reinterpret_cast<u32x4*>(dpre + (size_t)(row0 + q) * ld)[v] = o;
+    }
+  }
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  float* out = partial + (size_t)blockIdx.x * (size_t)r * K + 4 * v;
+#pragma unroll
+  for (int j = 0; j < RW; ++j)
+    if (j < r) *reinterpret_cast<f4*>(out + (size_t)j * K) = (f4){acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
+}
+
 // partial [nblk][n] -> out [n], blocks in ascending order inside each of 8 slices, then the slices: 32 elements x 8 slices of the block list per workgroup
 __global__ __launch_bounds__(256) void lora_out_reduce_kernel(const float* __restrict__ partial, int nblk, int n, float* __restrict__ out) {
   __shared__ float red[8][33];
@@ -1451,23 +1520,32 @@ extern "C" int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const fl
   return UCOD_OK;
 }
 
-extern "C" int ucod_lora_out_grad_x(const void* x_in, int act, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out, void* workspace,
-                                    size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+// (the SwiGLU form reads and writes rows of 2K values where the other forms have K: it is taken only with UCOD_LORA_OUT_SWIGLU in out_flags, so that a caller of
+//  ucod_lora_out_grad_x, whose buffers are [rows, K], can never reach it -- there act = 2 stays the invalid argument it was)
+extern "C" int ucod_lora_out_grad_x_ex(const void* x_in, int act, int out_flags, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out,
+                                       void* workspace, size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
   UCOD_BF16_ONLY();
-  if (!x_in || !cot_bf16 || !t || !lora_out || !grad_out || !workspace || rows <= 0 || (act != UCOD_LORA_OUT_ACT_IDENTITY && act != UCOD_LORA_OUT_ACT_GELU))
+  if (!x_in || !cot_bf16 || !t || !lora_out || !grad_out || !workspace || rows <= 0 || (out_flags & ~UCOD_LORA_OUT_SWIGLU) ||
+      (act != UCOD_LORA_OUT_ACT_IDENTITY && act != UCOD_LORA_OUT_ACT_GELU && !(act == UCOD_LORA_OUT_ACT_SWIGLU && (out_flags & UCOD_LORA_OUT_SWIGLU))))
     return UCOD_EINVAL;
   const size_t need = ucod_lora_out_grad_workspace_bytes(r, K, D);
   if (need == 0) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   if (workspace_bytes < need) return UCOD_ENOMEM;
-  UCOD_PROF(PROF_LORA_OUT_GRAD_X, stream);
+  const bool swiglu = act == UCOD_LORA_OUT_ACT_SWIGLU;
+  UCOD_PROF(swiglu ? PROF_LORA_OUT_GRAD_X_SWIGLU : PROF_LORA_OUT_GRAD_X, stream);
   const Drop drop = make_drop(dropout);
   hipStream_t st = (hipStream_t)stream;
   const int nblk = out_grad_x_blocks(rows);
-  const dim3 grid(nblk, cdiv(K / 8, 128));
+  const dim3 grid(nblk, cdiv(swiglu ? K / 4 : K / 8, 128));      // (SwiGLU: a row of the interleaved [rows, 2K] buffers has K / 4 16-byte vectors)
+#define GXS(w) hipLaunchKernelGGL((lora_out_grad_x_swiglu_kernel<w>), grid, dim3(128), 0, st, (const bf16_raw*)x_in, (bf16_raw*)cot_bf16, t, lora_out, r, \
+                                  (float*)workspace, rows, K, drop)
 #define GX(w, g) hipLaunchKernelGGL((lora_out_grad_x_kernel<w, g>), grid, dim3(128), 0, st, (const bf16_raw*)x_in, (bf16_raw*)cot_bf16, t, lora_out, r, \
                                     (float*)workspace, rows, K, drop)
-  if (act == UCOD_LORA_OUT_ACT_GELU) {
+  if (swiglu) {
+    if (r <= 2) GXS(2);
+    else GXS(8);
+  } else if (act == UCOD_LORA_OUT_ACT_GELU) {
     if (r <= 2) GX(2, true);
     else GX(8, true);
   } else {
@@ -1475,8 +1553,13 @@ extern "C" int ucod_lora_out_grad_x(const void* x_in, int act, void* cot_bf16, c
     else GX(8, false);
   }
 #undef GX
+#undef GXS
   UCOD_CHECK_LAUNCH();
   hipLaunchKernelGGL(lora_out_reduce_kernel, dim3(cdiv((long)r * K, 32)), dim3(256), 0, st, (const float*)workspace, nblk, r * K, grad_out);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+extern "C" int ucod_lora_out_grad_x(const void* x_in, int act, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out, void* workspace,
+                                    size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return ucod_lora_out_grad_x_ex(x_in, act, 0, cot_bf16, t, lora_out, r, grad_out, workspace, workspace_bytes, rows, K, D, dropout, stream);
 }

@@ -15,6 +15,9 @@
 // no aug columns, so each module is one row kernel behind its residual GEMM (ucod_lora_out_fwd: x += lambda * scaling * (drop(x_in) A^T) B^T, u saved) and two in the
 // backward (ucod_lora_out_grad_s on the dgrad GEMM's operand s, ucod_lora_out_grad_x on x_in and its cotangent).  Dropout keys 2L + l (dense) and 3L + l (fc2).
 // A NULL table is the _lora_mlp form.
+// The _lora_out_ex forms take one word of flags: with UCOD_LORA_OUT_SWIGLU the fc2 slots may be filled on the SwiGLU MLP too (Dinov2SwiGLUFFN.weights_out; the gated
+// DINOv3 down_proj): the forward kernel reads the hidden [M, F] as ever, the backward recomputes it from the saved interleaved pre-activation
+// (ucod_lora_out_grad_x_ex with UCOD_LORA_OUT_ACT_SWIGLU on pre / dpre [M, 2F]).  Flags 0 is the _lora_out form.
 // No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
@@ -57,15 +60,17 @@ inline size_t out_gw_bytes(const ucod_vit_train_desc* t, OutMods m) {
   const size_t a = m.o ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) : 0, b = m.f ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) : 0;
   return a > b ? a : b;
 }
-inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TO) {
+inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TO, int out_flags) {
   const OutMods m = out_mods(TO);
+  if (out_flags & ~UCOD_LORA_OUT_SWIGLU) return false;            // an unknown flag bit
   if (!TO) return true;
   if (!m.o && !m.f) return false;                                 // a table that names no module
-  if (m.f && mlp != UCOD_MLP_GELU) return false;                  // (SwiGLU: the hidden would have to be recomputed from the interleaved, padded [M, 2F] pre-activation)
+  // (SwiGLU: the hidden is recomputed from the interleaved, padded [M, 2F] pre-activation -- only with the _ex forms' UCOD_LORA_OUT_SWIGLU)
+  if (m.f && mlp != UCOD_MLP_GELU && !(out_flags & UCOD_LORA_OUT_SWIGLU)) return false;
   return (!m.o || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) != 0) && (!m.f || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) != 0);
 }
-bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false, const void* const* TO = nullptr) {
-  return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl) && valid_out(t, mlp, TO);
+bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false, const void* const* TO = nullptr, int out_flags = 0) {
+  return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl) && valid_out(t, mlp, TO, out_flags);
 }
 
 TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const void* const* TO = nullptr) {
@@ -131,8 +136,11 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const 
     if (rc__ != 0) return rc__;  \
   } while (0)
 
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO) {
+  return valid(t, mlp, TM != nullptr, TO, out_flags) ? make_plan(t, mlp, TM != nullptr, TO).total : 0;
+}
 extern "C" size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
-  return valid(t, mlp, TM != nullptr, TO) ? make_plan(t, mlp, TM != nullptr, TO).total : 0;
+  return ucod_vit_train_workspace_bytes_lora_out_ex(t, mlp, 0, TM, TO);
 }
 extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
   return ucod_vit_train_workspace_bytes_lora_out(t, mlp, TM, nullptr);
@@ -140,10 +148,11 @@ extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_d
 extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_train_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_train_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                               const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
+                                                  const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr, TO) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr, TO, out_flags) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
@@ -222,6 +231,10 @@ extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int
   }
   return UCOD_OK;
 }
+extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_train_lora_out_ex(t, mlp, 0, T, TT, TM, TO, img, key_out, workspace, workspace_bytes, stream);
+}
 extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
                                                const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   return ucod_vit_forward_train_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
@@ -276,8 +289,12 @@ IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
 }  // namespace
 
 // (the no-grad pass saves nothing: the output modules add no workspace byte)
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM,
+                                                                  const void* const* TO) {
+  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) && valid_out(t, mlp, TO, out_flags) ? make_iplan(t, TM != nullptr).total : 0;
+}
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
-  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) && valid_out(t, mlp, TO) ? make_iplan(t, TM != nullptr).total : 0;
+  return ucod_vit_lora_infer_workspace_bytes_lora_out_ex(t, mlp, 0, TM, TO);
 }
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
   return ucod_vit_lora_infer_workspace_bytes_lora_out(t, mlp, TM, nullptr);
@@ -285,10 +302,11 @@ extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_tr
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_lora_infer_workspace_bytes_lora_mlp(t, mlp, nullptr); }
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_lora_infer_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
 
-extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                                    const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_forward_lora_infer_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
+                                                       const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
+                                                       size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !valid_out(t, mlp, TO) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !valid_out(t, mlp, TO, out_flags) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const OutMods om = out_mods(TO);
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const ucod_vit_desc* d = &t->vit;
@@ -356,6 +374,10 @@ extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t
   }
   return UCOD_OK;
 }
+extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_forward_lora_infer_lora_out_ex(t, mlp, 0, T, TT, TM, TO, img, key_out, workspace, workspace_bytes, stream);
+}
 extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
                                                     const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   return ucod_vit_forward_lora_infer_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
@@ -369,10 +391,11 @@ extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const v
   return ucod_vit_forward_lora_infer_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
 }
 
-extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                          const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
+                                             const void* const* TM, const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr, TO) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
+  if (!valid(t, mlp, TM != nullptr, TO, out_flags) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
   const ucod_vit_desc* d = &t->vit;
   const bool swiglu = mlp == UCOD_MLP_SWIGLU;
   const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
@@ -459,12 +482,14 @@ extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp,
     if (om.f) {
       // LoRA on the MLP output projection, while `s` (= bf16(ls2 * dx), the fc2 dgrad's operand) is still there: t = scaling * s B_2 and dB_2 from s and the saved u,
       // then dA_2 from t and the hidden recomputed as gelu(pre), and dpre += gelu'(pre) * mask/(1-p) * (t A_2) -- completed before anything below reads dpre
+      // (SwiGLU, UCOD_LORA_OUT_SWIGLU: the hidden is silu(x1) * x2 of the interleaved pre [M, 2F], and dpre [M, 2F] takes the term through both derivative factors)
       const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
       float* gz = (float*)const_cast<void*>(Z[3]);
       RUN(ucod_lora_out_grad_s(s, (const float*)(ws + p.u_2 + p.s_u * l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes,
                                M, F, D, stream));
-      RUN(ucod_lora_out_grad_x(pre, UCOD_LORA_OUT_ACT_GELU, dpre, (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D,
-                               t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
+      RUN(ucod_lora_out_grad_x_ex(pre, swiglu ? UCOD_LORA_OUT_ACT_SWIGLU : UCOD_LORA_OUT_ACT_GELU, swiglu ? UCOD_LORA_OUT_SWIGLU : 0, dpre,
+                                  (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D,
+                                  t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
     }
     const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
     const ucod_lora_dropout* dp_m = t->lora_dropout > 0.f ? &drop_m : nullptr;
@@ -502,6 +527,10 @@ extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp,
     }
   }
   return UCOD_OK;
+}
+extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                          const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+  return ucod_vit_backward_lora_out_ex(t, mlp, 0, T, TT, TM, TO, dkey, workspace, workspace_bytes, stream);
 }
 extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
                                           const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {

@@ -67,7 +67,7 @@ def _adapter_prefix(engine):
 
 def _adapter_targets(engine):
     """target_modules of an engine as peft lists them: the leaf names (query / key / value; q_proj / k_proj / v_proj on a DINOv3 checkpoint; with the output
-    projections targeted also dense / fc2, or o_proj / down_proj)"""
+    projections targeted also dense / fc2 -- weights_out on a SwiGLU checkpoint --, or o_proj / down_proj)"""
     names = [n for n, on in zip(getattr(engine, "_qkv_names", ("query", "key", "value")), engine.targets) if on]
     names += [engine.mlp_target] if engine.mlp_target is not None else []
     return names + [path.rsplit(".", 1)[-1] for path, on in zip(getattr(engine, "_out_paths", ()), getattr(engine, "out_targets", ())) if on]
@@ -111,7 +111,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     is) may name any non-empty subset of query / key / value and the MLP input projection (``fc1``; ``weights_in`` on a SwiGLU checkpoint), matched by peft's
     suffix rule; ``dense`` / ``fc2`` / ``weights_out`` are refused with the reason (vit_engine.lora_targets) -- unless the build-only key ``allow_out`` (default
     False) is set: then ``dense`` and ``fc2`` (``o_proj`` and the non-gated ``down_proj`` on a DINOv3 checkpoint) are built as row kernels beside their GEMMs, and
-    only the SwiGLU MLP's output projection stays refused.
+    only the SwiGLU MLP's output projection stays refused.  The build-only key ``allow_swiglu_out`` (default False; needs ``allow_out``, and ``allow_rope`` on a
+    DINOv3 checkpoint) lifts that too: ``weights_out`` on DINOv2 ViT-g/14, ``down_proj`` on a gated DINOv3 checkpoint whose hidden width is at most 4096.
     A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
     100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
@@ -129,7 +130,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
         eps = 1e-5 if is_dinov3(state_dict) else 1e-6
     return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, eps=eps, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
-                                      rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False))))
+                                      rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False)),
+                                      allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False))))
 
 
 class full_model(nn.Module):

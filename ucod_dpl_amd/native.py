@@ -56,6 +56,8 @@ VIT_TRAIN_OUT_SLOTS = ("lora_dense", "lora_dense_grad", "lora_fc2", "lora_fc2_gr
 O_LORA_DENSE, O_LORA_DENSE_GRAD, O_LORA_FC2, O_LORA_FC2_GRAD = range(VIT_TRAIN_OUT_STRIDE)
 LORA_OUT_W = 8                                              # include/ucod_dpl.h: UCOD_LORA_OUT_W (floats per row of the saved u and of t)
 LORA_OUT_ACT_IDENTITY, LORA_OUT_ACT_GELU = 0, 1
+LORA_OUT_ACT_SWIGLU = 2                                     # include/ucod_dpl.h: UCOD_LORA_OUT_ACT_SWIGLU (x_in / cot are the interleaved [rows, 2K] pre-activation / dpre)
+LORA_OUT_SWIGLU = 1                                         # include/ucod_dpl.h: UCOD_LORA_OUT_SWIGLU (out_flags of the _lora_out_ex entry points)
 
 vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -201,11 +203,18 @@ SIGNATURES = {
     "ucod_lora_out_fwd": (ci, [vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, C.POINTER(LoraDropout), vp]),
     "ucod_lora_out_grad_s": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, vp]),
     "ucod_lora_out_grad_x": (ci, [vp, ci, vp, vp, vp, ci, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_out_grad_x_ex": (ci, [vp, ci, ci, vp, vp, vp, ci, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),      # (+ out_flags behind act: LORA_OUT_SWIGLU for act 2)
     "ucod_vit_train_workspace_bytes_lora_out": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp)]),
     "ucod_vit_forward_train_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_vit_backward_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes_lora_out": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp)]),
     "ucod_vit_forward_lora_infer_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # the same five with one word of flags behind `mlp` (LORA_OUT_SWIGLU: the SwiGLU MLP's output projection in the fc2 slots); flags 0 = the forms above
+    "ucod_vit_train_workspace_bytes_lora_out_ex": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_forward_train_lora_out_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    "ucod_vit_backward_lora_out_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
+    "ucod_vit_lora_infer_workspace_bytes_lora_out_ex": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_forward_lora_infer_lora_out_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     # merging trained LoRA matrices into ordinary weights, and the device form of the LayerNorm fold (fp16-operand build) for the merged weight
     "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
     "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),

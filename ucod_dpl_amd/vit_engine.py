@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import native as N
-from .swiglu import lora_b_from_engine, lora_b_to_engine
+from .swiglu import lora_b_from_engine, lora_b_to_engine, padded_hidden
 from . import ops
 
 
@@ -807,20 +807,43 @@ _REFUSED = {
 _OUT = ("dense", "fc2")                                      # the output projections ``allow_out`` builds, by leaf name (attention.output.dense, mlp.fc2)
 _SWIGLU_OUT = ("its input, the SwiGLU hidden, is not a saved activation: it would have to be recomputed from the interleaved, padded [M, 2F] pre-activation, "
                "which is not built yet")
+# (what the refusal says once that recomputation exists: the message above stays, with the way in behind it)
+_SWIGLU_OUT_OPT_IN = _SWIGLU_OUT + ".  That recomputation runs only with the opt-in allow_swiglu_out=True (beside allow_out and allow_swiglu)"
 
 
-def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False):
+LORA_OUT_MAX_K = 4096                                        # include/ucod_dpl.h: the widest input the output projections' LoRA kernels take
+
+
+def _check_swiglu_out(allow_out, allow_swiglu_out):
+    if allow_swiglu_out and not allow_out:
+        raise ValueError("allow_swiglu_out=True needs allow_out=True: the SwiGLU MLP's output projection is one of the output projections")
+
+
+def _check_swiglu_out_width(name, hidden):
+    """The SwiGLU MLP's output projection is targeted: refuse a hidden width the kernels do not cover, here, before anything touches the device."""
+    if hidden is not None and padded_hidden(hidden) > LORA_OUT_MAX_K:
+        raise NotImplementedError(f"LoRA target module {name!r} is not built for this checkpoint: its input width K = {padded_hidden(hidden)} (the MLP's hidden width "
+                                  f"{hidden}, padded) is beyond the kernels' K <= {LORA_OUT_MAX_K} -- a thread keeps the A values of its hidden units in registers")
+
+
+def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False, allow_swiglu_out=False, hidden=None):
     """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> ((query, key, value) as booleans, the MLP
     input projection's name or None).  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``.  Built: any
     subset of query / key / value and the MLP input projection (``fc1`` on a GELU checkpoint, ``weights_in`` on a SwiGLU one) -- the modules whose input
     is a LayerNorm output, which the LayerNorm kernel can extend by the LoRA down-projection.  None = the reference's query / key / value.
     ``allow_out=True`` also accepts the output projections ``dense`` (attention.output.dense) and, on a GELU checkpoint, ``fc2`` -- row kernels beside their GEMMs
-    (include/ucod_dpl.h: ucod_lora_out_fwd) -- and returns a third element: the accepted ones of ("dense", "fc2"), in that order.  ``weights_out`` stays refused."""
+    (include/ucod_dpl.h: ucod_lora_out_fwd) -- and returns a third element: the accepted ones of ("dense", "fc2"), in that order.  ``weights_out`` stays refused.
+    ``allow_swiglu_out=True`` (needs ``allow_out``; ValueError without it) accepts ``weights_out`` on a SwiGLU checkpoint as well -- the hidden is recomputed from
+    the saved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU) -- and the third element is then drawn from ("dense", "weights_out").  ``hidden``: the checkpoint's MLP
+    hidden width, when known; with it a ``weights_out`` whose padded width is beyond the kernels' 4096 is refused here (NotImplementedError)."""
     if mlp not in _MLP_IN:
         raise ValueError(f"mlp must be 'gelu' or 'swiglu', got {mlp!r}")
+    _check_swiglu_out(allow_out, allow_swiglu_out)
     if target_modules is None:
         return ((True, True, True), None, ()) if allow_out else ((True, True, True), None)
-    refused = dict({k: v for k, v in _REFUSED.items() if k not in _OUT}, weights_out=_SWIGLU_OUT) if allow_out else _REFUSED
+    refused = dict({k: v for k, v in _REFUSED.items() if k not in _OUT}, weights_out=_SWIGLU_OUT_OPT_IN) if allow_out else _REFUSED
+    if allow_swiglu_out:
+        refused = {k: v for k, v in refused.items() if k != "weights_out"}
     if isinstance(target_modules, str):
         raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
     targets = list(target_modules)
@@ -854,7 +877,9 @@ def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False):
     mlp_hit = mlp_in if "mlp." + mlp_in in per_layer[0] else None
     if not allow_out:
         return qkv, mlp_hit
-    return qkv, mlp_hit, tuple(leaf for leaf, path in zip(_OUT, ("attention.output.dense", "mlp.fc2")) if path in per_layer[0])
+    if mlp == "swiglu" and "mlp.weights_out" in per_layer[0]:
+        _check_swiglu_out_width("weights_out", hidden)
+    return qkv, mlp_hit, tuple(leaf for leaf, path in zip(("dense", mlp_out), ("attention.output.dense", "mlp." + mlp_out)) if path in per_layer[0])
 
 
 _QKV3 = ("q_proj", "k_proj", "v_proj")                       # DINOv3ViTAttention's projections, in the order of _QKV
@@ -872,18 +897,20 @@ _DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", 
 _OUT3 = ("o_proj", "down_proj")                             # DINOv3's names of the two output projections, in the order of _OUT
 
 
-def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False):
+def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False, allow_swiglu_out=False, hidden=None):
     """``lora_targets`` for a DINOv3 checkpoint, whose modules are ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj``
     too): any non-empty subset of q_proj / k_proj / v_proj by peft's suffix rule, None = all three.  Returns the (q, k, v) booleans; no MLP input module is built.
     ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` (``lora_targets``) and returns ((q, k, v), the accepted ones of
-    ("o_proj", "down_proj")); the gated MLP's ``down_proj`` stays refused."""
+    ("o_proj", "down_proj")); the gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well; ``hidden``
+    as in ``lora_targets`` (dinov3_vith16plus, 5120, is refused)."""
+    _check_swiglu_out(allow_out, allow_swiglu_out)
     if target_modules is None:
         return ((True, True, True), ()) if allow_out else (True, True, True)
     refused = _REFUSED3
     if allow_out:
         refused = {k: v for k, v in _REFUSED3.items() if k not in _OUT3}
-        if gated:
-            refused["down_proj"] = _SWIGLU_OUT
+        if gated and not allow_swiglu_out:
+            refused["down_proj"] = _SWIGLU_OUT_OPT_IN
     if isinstance(target_modules, str):
         raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
     targets = list(target_modules)
@@ -913,6 +940,8 @@ def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path
     qkv = tuple("attention." + n in per_layer[0] for n in _QKV3)
     if not allow_out:
         return qkv
+    if gated and "mlp.down_proj" in per_layer[0]:
+        _check_swiglu_out_width("down_proj", hidden)
     return qkv, tuple(leaf for leaf, path in zip(_OUT3, ("attention.o_proj", "mlp.down_proj")) if path in per_layer[0])
 
 
@@ -945,13 +974,20 @@ class ViTLoRAEngine(ViTEngine):
     ``allow_out=True`` also takes the output projections -- ``dense`` (attention.output.dense) and ``fc2`` on a DINOv2 GELU checkpoint, ``o_proj`` and ``down_proj``
     on a non-gated DINOv3 one -- as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x; the _lora_out entry points).  The arena
     row then ends in [A_o (r x D) | B_o (D x r)] and [A_2 (r x F) | B_2 (D x r)], for the targeted ones only; 1 <= r <= 8.  The SwiGLU MLP's output projection stays
-    refused.  With the flag off, or on with neither module named, every pass is launch for launch what it was."""
+    refused.  With the flag off, or on with neither module named, every pass is launch for launch what it was.
+
+    ``allow_swiglu_out=True`` (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``) lifts that refusal: ``weights_out`` of a DINOv2 SwiGLU
+    checkpoint, ``down_proj`` of a gated DINOv3 one.  The backward recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation
+    (UCOD_LORA_OUT_ACT_SWIGLU; the _lora_out_ex entry points with UCOD_LORA_OUT_SWIGLU, taken only when the module is targeted).  The arena row ends in
+    [A_2 (r x F) | B_2 (D x r)] with F the padded hidden width; the state dicts and the adapter folder carry A_2 as HF has it, [r, F0]: the padded columns are
+    zeros in the arena and absent outside it.  A hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers."""
 
     # (defaults of an engine built without ``allow_out``: no output projection is targeted)
     allow_out, out_targets, out_off, _out_paths = False, (False, False), (None, None), ("attention.output.dense", "mlp.fc2")
+    allow_swiglu_out, _out_flags = False, 0
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False):
+                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
@@ -959,28 +995,34 @@ class ViTLoRAEngine(ViTEngine):
         the QKV GEMM and attention and apply the transposed rotation to dq / dk behind attention backward (include/ucod_dpl.h: ucod_rope_qk_ld,
         ucod_vit_train_desc.allow_rope).  Its modules are ``{model.,}layer.{i}.attention.{q,k,v}_proj`` (``lora_targets_dinov3``); a gated-MLP checkpoint
         (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``.
-        ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``."""
+        ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``.
+        ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (class docstring).  Opt-in: ``lora_cfg.allow_swiglu_out``."""
         canon = normalize_state_dict(state_dict)
+        if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
+            raise ValueError("allow_swiglu_out=True needs allow_out=True and allow_swiglu=True" + (", and allow_rope=True on a DINOv3 checkpoint" if canon.get("rope") else ""))
+        mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
+        so = {"allow_swiglu_out": True, "hidden": canon["layers"][0]["fc1_w"].shape[0] // 2} if allow_swiglu_out and mlp_kind == "swiglu" else {}
         if canon.get("rope") and not allow_rope:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a DINOv3 checkpoint (rotary position embedding, RoPE: the passes rotate q / k and "
                                       "rotate dq / dk back) only with allow_rope=True")
         self.allow_rope = bool(allow_rope)
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
-        mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
         if canon.get("rope"):
             # the checkpoint's own names: layer path, module path below it, leaf names (what lora_state_dict, the merges and the adapter folder use)
             self._layer_path = _dinov3_paths(state_dict)[1]
             self._qkv_names, self._qkv_dir = _QKV3, "attention."
             self._out_paths, out_leaves = ("attention.o_proj", "mlp.down_proj"), _OUT3
-            hit = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path, **({"allow_out": True} if allow_out else {}))
+            hit = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path, **({"allow_out": True} if allow_out else {}), **so)
             (self.targets, out_hit), self.mlp_target = (hit if allow_out else (hit, ())), None
         else:
             self._layer_path, self._qkv_names, self._qkv_dir = "encoder.layer.", _QKV, "attention.attention."
             self._out_paths, out_leaves = ("attention.output.dense", "mlp.fc2"), _OUT
-            hit = lora_targets(target_modules, mlp_kind, len(canon["layers"]), **({"allow_out": True} if allow_out else {}))
+            if allow_swiglu_out and mlp_kind == "swiglu":          # (Dinov2SwiGLUFFN names its output projection weights_out)
+                self._out_paths, out_leaves = ("attention.output.dense", "mlp.weights_out"), ("dense", "weights_out")
+            hit = lora_targets(target_modules, mlp_kind, len(canon["layers"]), **({"allow_out": True} if allow_out else {}), **so)
             self.targets, self.mlp_target, out_hit = hit if allow_out else hit + ((),)
-        self.allow_out = bool(allow_out)
+        self.allow_out, self.allow_swiglu_out = bool(allow_out), bool(allow_swiglu_out)
         self.out_targets = tuple(leaf in out_hit for leaf in out_leaves)          # (attention output projection, MLP output projection)
         self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
         if mlp_kind == "swiglu" and not allow_swiglu:
@@ -1020,8 +1062,13 @@ class ViTLoRAEngine(ViTEngine):
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with an output projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its kernels keep u and t {N.LORA_OUT_W} wide)")
             if self.lib.ucod_lora_out_grad_workspace_bytes(r, K, D) == 0:
+                if m == 1 and self.mlp == N.UCOD_MLP_SWIGLU:
+                    raise NotImplementedError(f"LoRA on the SwiGLU MLP's output projection is not built for this hidden width: K = {K} is beyond the kernels' "
+                                              f"K <= 4096 (a thread keeps the A values of its hidden units in registers); D = {D} must be <= 1536")
                 raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {K}")
             self.out_off[m], numel = numel, numel + r * (K + D)
+        # (the flag of the _lora_out_ex entry points, which the passes take only with the SwiGLU MLP's output projection targeted)
+        self._out_flags = N.LORA_OUT_SWIGLU if self.out_targets[1] and self.mlp == N.UCOD_MLP_SWIGLU else 0
         self.lora = torch.zeros(L, numel, dtype=torch.float32, device=dev)
         bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
@@ -1031,7 +1078,10 @@ class ViTLoRAEngine(ViTEngine):
         if self.mlp_target is not None:                 # drawn after q / k / v: the default engine's stream is untouched
             self.lora[:, self.qkv_numel:self.qkv_numel + r * D] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
         for m, K in enumerate((D, self.F)):             # drawn after everything else: every engine without them keeps its stream (A: U(+-1/sqrt(fan_in)), B zeros)
-            if self.out_targets[m]:
+            if self.out_targets[m] and m == 1 and self._F0 != K:  # (SwiGLU, padded: fan_in is the checkpoint's own width F0, the padded columns stay zero)
+                a2 = (torch.rand(L, r, self._F0, generator=generator) * 2 - 1) / math.sqrt(self._F0)
+                self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = torch.nn.functional.pad(a2, (0, K - self._F0)).reshape(L, r * K).to(dev)
+            elif self.out_targets[m]:
                 self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = ((torch.rand(L, r * K, generator=generator) * 2 - 1) / math.sqrt(K)).to(dev)
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
@@ -1069,6 +1119,10 @@ class ViTLoRAEngine(ViTEngine):
         o, rK = self.out_off[m], self.r * (self.D, self.F)[m]
         return slice(o, o + rK), slice(o + rK, o + rK + self.D * self.r)
 
+    def _out_width(self, m):
+        """Input width of output module ``m`` as the checkpoint has it: D, or the MLP's own hidden width F0 (SwiGLU: before padding; otherwise F0 = F)."""
+        return (self.D, self._F0)[m]
+
     def lora_state_dict(self, grads=False, prefix=None):
         """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
         projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded.  A DINOv3
@@ -1093,7 +1147,7 @@ class ViTLoRAEngine(ViTEngine):
             for m, path in enumerate(self._out_paths):
                 if self.out_targets[m]:
                     sa, sb = self._out_slices(m)
-                    out[f"{prefix}{i}.{path}.lora_A.weight"] = src[i, sa].reshape(self.r, -1).clone()
+                    out[f"{prefix}{i}.{path}.lora_A.weight"] = src[i, sa].reshape(self.r, -1)[:, :self._out_width(m)].clone()      # (padded columns dropped)
                     out[f"{prefix}{i}.{path}.lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
         return out
 
@@ -1129,8 +1183,9 @@ class ViTLoRAEngine(ViTEngine):
                 if self.out_targets[m]:
                     sa, sb = self._out_slices(m)
                     a, b = take(f"{prefix}{i}.{path}.lora_A.weight"), take(f"{prefix}{i}.{path}.lora_B.weight")
-                    if tuple(a.shape) != (self.r, (self.D, self.F)[m]) or tuple(b.shape) != (self.D, self.r):
+                    if tuple(a.shape) != (self.r, self._out_width(m)) or tuple(b.shape) != (self.D, self.r):
                         raise ValueError(f"{prefix}{i}.{path}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
+                    a = torch.nn.functional.pad(a, (0, (self.D, self.F)[m] - a.shape[1]))      # (SwiGLU: the padded hidden units' columns load as zeros)
                     self.lora[i, sa], self.lora[i, sb] = a.reshape(-1), b.reshape(-1)
         self.repack()
 
@@ -1221,7 +1276,13 @@ class ViTLoRAEngine(ViTEngine):
             self._chunk_seed[i] = t.seed
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
             TO = self._out_table(self._tside_grad[i])
-            if TO is not None:                                     # an output projection is targeted: the _lora_out entry points (TM may be NULL there)
+            if TO is not None and self._out_flags:                 # the SwiGLU MLP's output projection is targeted: the _lora_out_ex entry points with their flag
+                fl = self._out_flags
+                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(C.byref(t), self.mlp, fl, TM, TO))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_train_lora_out_ex(C.byref(t), self.mlp, fl, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws),
+                                                                        ws.numel(), N.stream()), "ucod_vit_forward_train_lora_out_ex")
+            elif TO is not None:                                   # an output projection is targeted: the _lora_out entry points (TM may be NULL there)
                 ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
                 with self._guard.bind():
                     N.check(self.lib.ucod_vit_forward_train_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
@@ -1258,7 +1319,13 @@ class ViTLoRAEngine(ViTEngine):
             t.vit.resid16 = int(bool(resid16))
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
             TO = self._out_table(self._tside_grad[i])
-            if TO is not None:
+            if TO is not None and self._out_flags:
+                fl = self._out_flags
+                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out_ex(C.byref(t), self.mlp, fl, TM, TO))
+                with self._guard.bind():
+                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_out_ex(C.byref(t), self.mlp, fl, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws),
+                                                                             ws.numel(), N.stream()), "ucod_vit_forward_lora_infer_lora_out_ex")
+            elif TO is not None:
                 ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
                 with self._guard.bind():
                     N.check(self.lib.ucod_vit_forward_lora_infer_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
@@ -1297,7 +1364,10 @@ class ViTLoRAEngine(ViTEngine):
             T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
             TO = self._out_table(self._tside_grad[i])
             ws = self._tside_ws[i]
-            if TO is not None:
+            if TO is not None and self._out_flags:
+                N.check(self.lib.ucod_vit_backward_lora_out_ex(C.byref(t), self.mlp, self._out_flags, T, TT, TM, TO, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(),
+                                                               N.stream()), "ucod_vit_backward_lora_out_ex")
+            elif TO is not None:
                 N.check(self.lib.ucod_vit_backward_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
                         "ucod_vit_backward_lora_out")
             elif TM is None:
@@ -1358,11 +1428,14 @@ class ViTLoRAEngine(ViTEngine):
                 key = f"{pref}{i}.{name}.weight"
                 w = base[key]
                 n, k = w.shape
+                kp = k                                             # the width the merge runs at
                 if isinstance(p, tuple):                           # an output projection: W [D, K], A [r, K], B [D, r]; neither padded nor reordered
-                    if (n, k) != (self.D, (self.D, self.F)[p[1]]):
-                        raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine expects {(self.D, (self.D, self.F)[p[1]])}")
+                    if (n, k) != (self.D, self._out_width(p[1])):
+                        raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine expects {(self.D, self._out_width(p[1]))}")
                     sa, sb = self._out_slices(p[1])
                     B = self.lora[i, sb]
+                    kp = (self.D, self.F)[p[1]]                    # (SwiGLU weights_out [D, F0]: merged at the padded width -- the kernel wants K % 64 == 0 and A's
+                                                                   #  padded columns are zeros --, the first F0 columns are the HF weight: the same sum per element)
                 elif k != self.D:
                     raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine has D = {self.D}")
                 elif p is not None:
@@ -1374,11 +1447,13 @@ class ViTLoRAEngine(ViTEngine):
                     B = lora_b_from_engine(B, self._F0) if swiglu else B
                 if B.numel() != n * self.r:
                     raise ValueError(f"{key} has {n} rows, the LoRA B matrix of this engine {B.numel() // self.r}")
-                buf = self._stage(2 * n * k)
-                w0, merged = buf[:n * k].view(n, k), buf[n * k:2 * n * k].view(n, k)
-                w0.copy_(w.detach())
+                buf = self._stage(2 * n * kp)
+                w0, merged = buf[:n * kp].view(n, kp), buf[n * kp:2 * n * kp].view(n, kp)
+                if kp != k:
+                    w0.zero_()
+                w0[:, :k].copy_(w.detach())
                 self._merge(self.lib, w0, self.lora[i, sa], B, merged)
-                out[key] = merged.to(w.device, copy=True)
+                out[key] = merged[:, :k].contiguous().to(w.device, copy=True)
         return out
 
     def _engine_row_source(self):
@@ -1421,13 +1496,15 @@ class ViTLoRAEngine(ViTEngine):
             for name, p in self._targeted():
                 w = base[f"{pref}{i}.{name}.weight"]
                 if isinstance(p, tuple):                           # an output projection: merged, cast into the live tensor; no LayerNorm stands in front of it, so no fold
-                    K = (D, self.F)[p[1]]
-                    if tuple(w.shape) != (D, K):
-                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(D, K)}")
+                    K, K0 = (D, self.F)[p[1]], self._out_width(p[1])
+                    if tuple(w.shape) != (D, K0):
+                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(D, K0)}")
                     sa, sb = self._out_slices(p[1])
                     buf = self._stage(2 * D * K)
                     w0, merged = buf[:D * K].view(D, K), buf[D * K:2 * D * K].view(D, K)
-                    w0.copy_(w.detach())
+                    if K0 != K:                                    # (SwiGLU weights_out: the engine's tensor is zero-padded to [D, F]; A's padded columns are zeros)
+                        w0.zero_()
+                    w0[:, :K0].copy_(w.detach())
                     self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
                     N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), row[(N.PROJ_W, N.FC2_W)[p[1]]].data_ptr(), D * K, st()), "ucod_cast_f32_bf16")
                     if p[1] == 1:
