@@ -572,15 +572,10 @@ size_t ucod_vit_split16_stream_offset_ex(const ucod_vit_desc* d, int mlp, int fl
 int ucod_vit_forward_split16_ex(const ucod_vit_desc* d, int mlp, int flags, const void* const* table_host, const float* wscale_host, int n_wscale, const float* img,
                                 float* key_out, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Backbone-backward mode, whole passes (row B9; operand formats in ucod_dpl_amd/csrc/vit_train.hip).
- * T = the table of ucod_vit_forward; TT = per-layer training table (HOST array of DEVICE pointers), layer l at
- * UCOD_VIT_TRAIN_STRIDE*l:
- *   +0 qkv_w_aug bf16 [3D, D+64]   +1 qkv_wT_aug bf16 [D, 3D+64]   (aug columns maintained by ucod_lora_pack)
- *   +2 proj_w^T bf16 [D,D]   +3 fc1_w^T bf16 [D,F]   +4 fc2_w^T bf16 [F,D]   (frozen; transposed once by the host)
- *   +5 LoRA parameters f32 [6*r*D]   +6 LoRA gradients f32 [6*r*D] (overwritten by ucod_vit_backward)
- * forward_train saves its activations in `workspace`; backward must be given the same, untouched workspace.
- * dkey f32 [B, D, H/P, W/P] = cotangent of key_out.  gemm_variant of the embedded desc applies; attention is the
- * pre-scaled kernel.  With lora_dropout > 0 the aug A^T columns of qkv_wT_aug must have been packed as zeros (ucod_lora_pack). */
+/* Backbone-backward mode, whole passes (row B9; operand formats in ucod_dpl_amd/csrc/vit_train.hip): a training forward that saves its activations, the backward
+ * that turns the cotangent of the key map into LoRA gradients, and a no-grad forward.  The tables, the workspace and what each pass enqueues are described once, at
+ * the _lora_out_ex forms that close this section: new callers should use those.  The four older tiers of entry points remain, each the _lora_out_ex form with the
+ * arguments it lacks at their neutral values; one driver body serves them all (ucod_dpl_amd/csrc/vit_train_driver.hip). */
 #define UCOD_VIT_TRAIN_STRIDE 7
 typedef struct {
   ucod_vit_desc vit;
@@ -593,24 +588,16 @@ typedef struct {
                                     between ucod_attention_bwd and the LoRA-gradient kernel; the last layer's key hook stays in front of any rotation.  0 (every caller
                                     that zero-fills the descriptor): a non-NULL vit.rope is UCOD_EINVAL, sizes 0.  With vit.rope == NULL the flag changes nothing. */
 } ucod_vit_train_desc;
+/* The _lora_out_ex forms with mlp = UCOD_MLP_GELU, out_flags = 0, mlp_table_host = out_table_host = NULL. */
 size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t);
 int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* table_host, const void* const* train_table_host,
                            const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
 int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* table_host, const void* const* train_table_host,
                       const float* dkey, void* workspace, size_t workspace_bytes, void* stream);
-/* No-grad pass of the LoRA backbone -- the EMA teacher of models/modules/full_model.py:84,108-111 (backbone_ema under torch.no_grad()):
- * the arithmetic of ucod_vit_forward_train (LoRA as aug columns, the same dropout masks for the same seed) with nothing saved for a
- * backward; t->vit.resid16 may be 1 (fp16 residual stream, as ucod_vit_forward).  Own, inference-sized workspace. */
 size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t);
 int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* table_host, const void* const* train_table_host,
                                 const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
-/* The five entry points above with the MLP kind of the pass (UCOD_MLP_*; the ones without the suffix are the UCOD_MLP_GELU case and enqueue the same launches;
- * an unknown kind: UCOD_EINVAL, sizes 0).  UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315; DINOv2 ViT-g/14): the table entries +9 / +10 / +11 are
- * those of ucod_vit_forward_mlp (weights_in [2F, D] and its bias interleaved in blocks of 4, weights_out [D, F]; d->F the padded hidden width), and of the training
- * table +3 is the transpose of that interleaved weights_in, bf16 [D, 2F] (its K order is the column order of the pre-activation's cotangent), +4 the transpose of
- * weights_out, bf16 [F, D].  The training forward runs weights_in through UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 and saves the interleaved pre-activation bf16 [M, 2F] per
- * layer (GELU: [M, F]); the backward runs the weights_out dgrad through UCOD_EPI_SWIGLU_BWD_BF16 into dpre bf16 [M, 2F] (which the hidden's buffer is sized for) and
- * the plain weights_in dgrad with K = 2F; the no-grad pass uses UCOD_EPI_BIAS_SWIGLU_BF16.  Everything outside the MLP is the GELU pass's. */
+/* The _lora_out_ex forms with out_flags = 0, mlp_table_host = out_table_host = NULL (the MLP kind of the pass: UCOD_MLP_*). */
 size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp);
 int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
                                const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream);
@@ -648,12 +635,7 @@ int ucod_lora_mlp_grad(const void* dpre_bf16, const void* h2_aug_bf16, const flo
 int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
                                 void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
                                 const ucod_lora_dropout* dropout, void* stream);
-/* The five whole-pass entry points with the MLP module's own per-layer table TM (HOST array of DEVICE pointers), layer l at UCOD_VIT_TRAIN_MLP_STRIDE*l
- * (full_model.py:47-72):
- *   +0 fc1_w_aug bf16 [N1, D+64] (aug columns maintained by ucod_lora_mlp_pack)   +1 LoRA parameters f32 [r (D + N1)]   +2 LoRA gradients f32 [r (D + N1)]
- * TM == NULL: q / k / v only -- exactly the launches of the _mlp entry points.  Otherwise lora_r <= UCOD_LORA_MLP_MAX_R (else UCOD_EINVAL, sizes 0); per layer
- * below the last the forward runs ucod_layernorm_lora_mlp and fc1 with K = D+64, the backward recomputes h2_aug from the saved residual stream, runs
- * ucod_lora_mlp_grad and ucod_layernorm_bwd_lora_mlp.  The last layer's MLP never reaches the key map: its gradients are written as zeros. */
+/* The _lora_out_ex forms with out_table_host = NULL, out_flags = 0 (TM, the MLP module's own per-layer table, is described there; layer l at UCOD_VIT_TRAIN_MLP_STRIDE*l). */
 #define UCOD_VIT_TRAIN_MLP_STRIDE 3
 size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host);
 int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
@@ -706,16 +688,8 @@ int ucod_lora_out_grad_x(const void* x_in_bf16, int act, void* cot_bf16, const f
  * unknown bit is UCOD_EINVAL).  out_flags = 0 is ucod_lora_out_grad_x, which delegates here. */
 int ucod_lora_out_grad_x_ex(const void* x_in_bf16, int act, int out_flags, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out,
                             void* workspace, size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
-/* The five whole-pass entry points with the output modules' own per-layer table TO (HOST array of DEVICE pointers), layer l at UCOD_VIT_TRAIN_OUT_STRIDE*l
- * (full_model.py:47-72; result = base(x) + scaling * B(A(dropout(x)))):
- *   +0 dense parameters f32 [r (D + D)] or NULL   +1 dense gradients   +2 fc2 parameters f32 [r (F + D)] or NULL   +3 fc2 gradients
- * A module is targeted when layer 0's parameter slot is not NULL (the same modules in every layer).  TO == NULL: exactly the launches and the workspace of the
- * _lora_mlp entry points, which delegate here.  Otherwise lora_r <= UCOD_LORA_MLP_MAX_R and the sizes above hold (else UCOD_EINVAL, sizes 0); fc2 needs
- * UCOD_MLP_GELU (the SwiGLU hidden would have to be recomputed from the interleaved, padded [M, 2F] pre-activation: not built).  Per layer below the last the
- * forward runs one ucod_lora_out_fwd behind each targeted module's residual GEMM (the training pass saves u: M * 32 bytes per layer and module), the backward one
- * ucod_lora_out_grad_s + ucod_lora_out_grad_x per module: fc2's behind the fc2 dgrad and in front of ucod_lora_mlp_grad / the fc1 dgrad, dense's between the
- * out-proj dgrad and ucod_attention_bwd.  The last layer's attention output and MLP never reach the key map: their gradients are written as zeros.
- * (The SwiGLU MLP's output projection is taken by the _ex forms below with UCOD_LORA_OUT_SWIGLU; these five entry points refuse it as before.) */
+/* The _lora_out_ex forms with out_flags = 0: they refuse the fc2 slots on the SwiGLU MLP (TO, the output modules' own per-layer table, is described there; layer l at
+ * UCOD_VIT_TRAIN_OUT_STRIDE*l). */
 #define UCOD_VIT_TRAIN_OUT_STRIDE 4
 size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host, const void* const* out_table_host);
 int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
@@ -728,8 +702,48 @@ size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t
 int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* table_host, const void* const* train_table_host,
                                          const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
                                          size_t workspace_bytes, void* stream);
-/* The _ex forms take one more word of flags behind `mlp` (the idiom of ucod_vit_forward_split16_ex); out_flags = 0 is the entry point above, which delegates here,
- * launch for launch and refusal for refusal.  An unknown bit: UCOD_EINVAL, sizes 0.
+/* The whole passes, in full: the _lora_out_ex forms.  Every argument an older tier lacks has a neutral value here -- mlp = UCOD_MLP_GELU, out_flags = 0, a NULL
+ * mlp_table_host / out_table_host -- and with it the pass enqueues, launch for launch, and refuses, refusal for refusal, what that tier does; the size functions return
+ * the same bytes.  An unknown MLP kind or an unknown bit of out_flags: UCOD_EINVAL, sizes 0.  bf16 build only (ucod_half_name).
+ *
+ * Tables (HOST arrays of DEVICE pointers).  T = table_host, the table of ucod_vit_forward (UCOD_MLP_SWIGLU: +9 / +10 / +11 are those of ucod_vit_forward_mlp: weights_in
+ * [2F, D] and its bias interleaved in blocks of 4, weights_out [D, F]; d->F the padded hidden width).
+ *   TT = train_table_host, layer l at UCOD_VIT_TRAIN_STRIDE*l:
+ *     +0 qkv_w_aug bf16 [3D, D+64]   +1 qkv_wT_aug bf16 [D, 3D+64]   (aug columns maintained by ucod_lora_pack)
+ *     +2 proj_w^T bf16 [D,D]   +3 fc1_w^T bf16 [D,F]   +4 fc2_w^T bf16 [F,D]   (frozen; transposed once by the host)
+ *     +5 LoRA parameters f32 [6*r*D]   +6 LoRA gradients f32 [6*r*D] (overwritten by ucod_vit_backward*)
+ *     UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315; DINOv2 ViT-g/14): +3 is the transpose of the interleaved weights_in, bf16 [D, 2F] (its K order is
+ *     the column order of the pre-activation's cotangent), +4 the transpose of weights_out, bf16 [F, D].
+ *   TM = mlp_table_host or NULL, the LoRA module on the MLP input projection (full_model.py:47-72), layer l at UCOD_VIT_TRAIN_MLP_STRIDE*l:
+ *     +0 fc1_w_aug bf16 [N1, D+64] (aug columns maintained by ucod_lora_mlp_pack)   +1 LoRA parameters f32 [r (D + N1)]   +2 LoRA gradients f32 [r (D + N1)]
+ *     Needs lora_r <= UCOD_LORA_MLP_MAX_R (else UCOD_EINVAL, sizes 0).
+ *   TO = out_table_host or NULL, the LoRA modules on the output projections (full_model.py:47-72; result = base(x) + scaling * B(A(dropout(x)))), layer l at
+ *   UCOD_VIT_TRAIN_OUT_STRIDE*l:
+ *     +0 dense parameters f32 [r (D + D)] or NULL   +1 dense gradients   +2 fc2 parameters f32 [r (F + D)] or NULL   +3 fc2 gradients
+ *     A module is targeted when layer 0's parameter slot is not NULL (the same modules in every layer); a table that names none is UCOD_EINVAL.  Needs lora_r <=
+ *     UCOD_LORA_MLP_MAX_R and the sizes of ucod_lora_out_grad_workspace_bytes (else UCOD_EINVAL, sizes 0).  With UCOD_MLP_SWIGLU the fc2 slots need UCOD_LORA_OUT_SWIGLU.
+ *
+ * ucod_vit_forward_train*: image -> key_out, saving its activations in `workspace`; ucod_vit_backward* must be given the same, untouched workspace and the same
+ * descriptor (seed included).  dkey f32 [B, D, H/P, W/P] = cotangent of key_out.  gemm_variant of the embedded desc applies; attention is the pre-scaled kernel.  With
+ * lora_dropout > 0 the aug A^T columns of qkv_wT_aug must have been packed as zeros (ucod_lora_pack).  Saved per layer: the two residual-stream states (f32, or IEEE
+ * fp16 with vit.resid16), LayerNorm 1's output with the LoRA down-projection, qkv, the attention output, the log-sum-exp, the fc1 pre-activation bf16 [M, F] -- with
+ * UCOD_MLP_SWIGLU the interleaved one, bf16 [M, 2F], from UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 -- and, with TO, u of each targeted module (M * 32 bytes per layer and module).
+ * ucod_vit_forward_lora_infer*: the no-grad pass of the LoRA backbone -- the EMA teacher of models/modules/full_model.py:84,108-111 (backbone_ema under
+ * torch.no_grad()): the arithmetic of ucod_vit_forward_train* (the same launches but ucod_attention_fwd, the plain fc1 epilogues -- UCOD_EPI_BIAS_SWIGLU_BF16 for
+ * SwiGLU -- and no u stored; the same dropout masks for the same seed) with nothing saved for a backward; t->vit.resid16 may be 1 (fp16 residual stream, as
+ * ucod_vit_forward).  Own, inference-sized workspace, to which TO adds no byte.
+ *
+ * Per layer below the last (the last runs LayerNorm 1 and the key projection only; the gradients of its MLP and output modules are written as zeros):
+ *   q / k / v    ride on the QKV GEMM as 64 extra K columns; vit.rope (allow_rope) adds the rotations the descriptor describes.
+ *   SwiGLU       the backward runs the weights_out dgrad through UCOD_EPI_SWIGLU_BWD_BF16 into dpre bf16 [M, 2F] (which the hidden's buffer is sized for) and the plain
+ *                weights_in dgrad with K = 2F.  Everything outside the MLP is the GELU pass's.
+ *   TM           the forward runs ucod_layernorm_lora_mlp and fc1 with K = D+64; the backward recomputes h2_aug from the saved residual stream, runs ucod_lora_mlp_grad
+ *                and ucod_layernorm_bwd_lora_mlp.
+ *   TO           the forward runs one ucod_lora_out_fwd behind each targeted module's residual GEMM; the backward one ucod_lora_out_grad_s + ucod_lora_out_grad_x per
+ *                module: fc2's behind the fc2 dgrad and in front of ucod_lora_mlp_grad / the fc1 dgrad, dense's between the out-proj dgrad and ucod_attention_bwd.
+ * Dropout keys (`layer` of ucod_lora_dropout): kind * L + l with kind 0 = q / k / v, 1 = the MLP input projection, 2 = dense, 3 = fc2, in all three passes.
+ *
+ * out_flags:
  *   UCOD_LORA_OUT_SWIGLU   with UCOD_MLP_SWIGLU, slot +2 may be non-NULL: the LoRA module of the SwiGLU MLP's output projection (weights_out; the gated DINOv3
  *                          down_proj), parameters f32 [r (F + D)] with F the padded hidden width (K = F <= 4096 as above: ViT-g and vits16plus; vith16plus's
  *                          F = 5120 is refused).  Per layer below the last: one ucod_lora_out_fwd on the hidden [M, F] behind the weights_out residual GEMM (key

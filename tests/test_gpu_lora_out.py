@@ -4,7 +4,8 @@ ViTLoRAEngine (models/modules/full_model.py:47-72 hands ``target_modules`` to pe
 1-2  the three row kernels alone against f64 on the same 16-bit-rounded operands, with canary rows around every output, run twice;
 3-6  whole passes against f64 autograd through tests/lora_out_ref.py (pinned on the CPU by tests/test_lora_out_host.py, which also shows that these cases have teeth):
      the G8 DINOv2 model and the D = 256 GELU model on one and two streams, with registers (G21 ``native``), DINOv3 (G23 ``g46``), the EMA teacher's pass;
-7-8  merging and the adapter folder; one training step of the runner.
+7-8  merging and the adapter folder; one training step of the runner;
+9    the four older tiers of the pass entry points, called directly, against the engine's own passes (which run the _lora_out_ex tier), bit for bit.
 
 The bars are the ones tests/test_gpu_lora_targets.py holds the same quantities to (its tests 1-3 for the kernels, 5-6 for the passes), tests/test_gpu_dinov3_lora.py's
 for the DINOv3 model and tests/test_gpu_lora_merge.py's for the merge; none is taken from a run of this code.  Two bars have no counterpart there and are derived:
@@ -38,6 +39,7 @@ import dinov3_ref as R3  # noqa: E402
 import dinov3_lora_ref as RL  # noqa: E402
 import registers_ref as RR  # noqa: E402
 import lora_out_ref as RO  # noqa: E402
+import lora_swiglu_out_ref as RS  # noqa: E402
 
 DEV = "cuda"
 GUARD_ROWS = 16
@@ -357,7 +359,7 @@ def test_passes_vs_f64_autograd(D, streams, targets, p_drop):
 
 
 def test_flag_on_without_the_new_names_is_the_engine_it_was():
-    """allow_out with none of the four names targeted: arena, key map and gradients of the engine without the flag, bit for bit (the same entry points run)."""
+    """allow_out with none of the four names targeted: arena, key map and gradients of the engine without the flag, bit for bit (the same entry points run, with a NULL table)."""
     sd, heads, L, image, B = checkpoint(128)
     img, dkey = (t.to(DEV) for t in RO.case_inputs(B, 128, image))
     lora = RO.lora_for(sd, ("query", "value", "fc1"))
@@ -440,7 +442,7 @@ def test_passes_on_dinov3(p_drop, streams):
 
 # ------------------------------------------------------------------------------------------------ 6. the EMA teacher's pass
 def test_nograd_pass_equals_the_training_forward():
-    """forward_nograd (ucod_vit_forward_lora_infer_lora_out) against forward_train at dropout 0, on the checkpoint of the existing infer-vs-train test and under its
+    """forward_nograd (ucod_vit_forward_lora_infer_lora_out_ex) against forward_train at dropout 0, on the checkpoint of the existing infer-vs-train test and under its
     bars (tests/test_gpu_lora_targets.py test 6, the G8 model: relative L2 2e-3 on the f32 stream, 4e-3 on the fp16 one -- the bars belong to that model; a deeper one
     has no bar there); the clone for the EMA teacher runs the same pass with its own arena."""
     D = 128
@@ -576,3 +578,76 @@ def test_runner_trains_the_output_modules(tmp_path):
                 assert f"{pre}{i}.{p}.lora_{ab}.weight" in saved, (i, p, ab)
     assert torch.equal(saved[pre + "0.mlp.fc2.lora_B.weight"], eng.lora_state_dict()["encoder.layer.0.mlp.fc2.lora_B.weight"].cpu())
     assert json.load(open(os.path.join(path, "lora", "adapter_config.json")))["target_modules"] == ["query", "key", "value", "dense", "fc2"]
+
+
+# ------------------------------------------------------------------------------------------------ 9. the older tiers of the pass entry points
+def older_tiers(lib, mlp, TM, TO):
+    """{tier: (train size, forward_train, backward, no-grad size, forward_lora_infer)} of every tier below _lora_out_ex that can express the configuration, each with
+    the arguments between the descriptor and the image / dkey bound: f(t, T, TT, ...) for the passes, f(t) for the sizes."""
+    five = ("ucod_vit_train_workspace_bytes{}", "ucod_vit_forward_train{}", "ucod_vit_backward{}", "ucod_vit_lora_infer_workspace_bytes{}", "ucod_vit_forward_lora_infer{}")
+
+    def bind(suffix, lead, tabs):
+        fns = [getattr(lib, n.format(suffix)) for n in five]
+        size = lambda f: lambda t: f(t, *lead, *tabs)  # noqa: E731
+        run = lambda f: lambda t, T, TT, *rest: f(t, *lead, T, TT, *tabs, *rest)  # noqa: E731
+        return size(fns[0]), run(fns[1]), run(fns[2]), size(fns[3]), run(fns[4])
+
+    tiers = {"_lora_out": bind("_lora_out", (mlp,), (TM, TO))}
+    if TO is None:
+        tiers["_lora_mlp"] = bind("_lora_mlp", (mlp,), (TM,))
+    if TO is None and TM is None:
+        tiers["_mlp"] = bind("_mlp", (mlp,), ())
+    if TO is None and TM is None and mlp == N.UCOD_MLP_GELU:
+        tiers["plain"] = bind("", (), ())
+    return tiers
+
+
+@pytest.mark.parametrize("kind,targets,expect", [("gelu", ("query", "key", "value"), {"plain", "_mlp", "_lora_mlp", "_lora_out"}),
+                                                 ("gelu", ("query", "key", "value", "fc1"), {"_lora_mlp", "_lora_out"}),
+                                                 ("gelu", ("query", "key", "value", "dense", "fc2"), {"_lora_out"}),
+                                                 ("swiglu", ("query", "key", "value"), {"_mlp", "_lora_mlp", "_lora_out"})])
+def test_older_tiers_run_the_engines_passes(kind, targets, expect):
+    """The engine makes one call per pass, to the _lora_out_ex tier.  Every older tier that can express the engine's configuration -- the same descriptor, tables and
+    chunk seed, its own zeroed workspace and gradient buffer -- gives the engine's key map, gradients and no-grad key map bit for bit (the passes reproduce from run
+    to run, dropout on: test_flag_on_without_the_new_names_is_the_engine_it_was relies on the same), and its size functions the engine's workspace sizes."""
+    sd, heads, L, image, B = checkpoint(128) if kind == "gelu" else (RS.g24_state_dict("dinov2"), 2, 3, 70, 2)
+    ref = RO if kind == "gelu" else RS
+    lora = ref.lora_for(sd, targets)
+    eng = ViTLoRAEngine(sd, heads=heads, r=2, lora_alpha=4, device=DEV, generator=torch.Generator().manual_seed(3), target_modules=list(targets), allow_out=True,
+                        allow_swiglu=(kind == "swiglu"), lora_dropout=0.05, seed=1234)
+    eng.load_lora_state_dict(lora)
+    eng.train_streams = 1
+    D = eng.D
+    assert D == 128 and L == 3 and eng.mlp == (N.UCOD_MLP_SWIGLU if kind == "swiglu" else N.UCOD_MLP_GELU) and eng._out_flags == 0
+    x, dkey = (t.to(DEV) for t in RO.case_inputs(B, D, image))
+    key = eng.forward_train(x).clone()
+    seed_train = eng._chunk_seed[0]
+    grad = eng.backward(dkey).clone()
+    key_ng = eng.forward_nograd(x).clone()                        # (the fp16 residual stream, the teacher's default)
+    seed_ng = eng._seed_of_chunk(0, 0)
+    eng.check_overflow(wait=True)
+    torch.cuda.synchronize()
+    assert float(grad.abs().max()) > 0 and not torch.equal(key, key_ng)
+    n_train, n_ng = eng._tside_ws[0].numel(), eng._iside_ws[0].numel()
+    lib, gh, P, st = eng.lib, image // 14, N.ptr, N.stream()
+    g = torch.zeros_like(eng.lora_grad)
+    T, TT, TM, keep = eng._tables(gh, gh, g)
+    TO = eng._out_table(g)
+    assert (TM is not None) == ("fc1" in targets) and (TO is not None) == ("dense" in targets)
+    tiers = older_tiers(lib, eng.mlp, TM, TO)
+    assert set(tiers) == expect
+    t = eng._train_desc(B, image, image, seed_train)
+    tn = eng._train_desc(B, image, image, seed_ng)
+    tn.vit.resid16 = 1
+    for name, (train_bytes, fwd, bwd, ng_bytes, fwd_ng) in tiers.items():
+        assert train_bytes(C.byref(t)) == n_train and ng_bytes(C.byref(tn)) == n_ng, name
+        ws, ws_ng = torch.zeros(n_train, dtype=torch.uint8, device=DEV), torch.zeros(n_ng, dtype=torch.uint8, device=DEV)
+        k, k_ng = torch.full_like(key, 3.0), torch.full_like(key, 3.0)
+        g.zero_()
+        assert fwd(C.byref(t), T, TT, P(x), P(k), P(ws), n_train, st) == 0, name
+        assert bwd(C.byref(t), T, TT, P(dkey), P(ws), n_train, st) == 0, name
+        assert fwd_ng(C.byref(tn), T, TT, P(x), P(k_ng), P(ws_ng), n_ng, st) == 0, name
+        torch.cuda.synchronize()
+        assert torch.equal(k, key), name
+        assert torch.equal(g, grad), name
+        assert torch.equal(k_ng, key_ng), name

@@ -490,7 +490,7 @@ def test_merge_and_adapter_with_weights_out(tmp_path):
 # ------------------------------------------------------------------------------------------------ 7. flag off, or on with the module not targeted
 def test_flag_without_the_module_is_the_engine_it_was():
     """allow_swiglu_out with weights_out not among the targets: arena, key map, gradients, the no-grad pass and the workspace size of the engine without the flag, bit
-    for bit -- the entry points that engine runs (no _ex form is taken)."""
+    for bit -- the flags word both engines pass is 0."""
     sd, heads, L, image, B = checkpoint()
     img, dkey = (t.to(DEV) for t in case_inputs(B, 128, image))
     targets = ["query", "value", "weights_in", "dense"]

@@ -1,31 +1,43 @@
 // Host-side driver of the backbone-backward mode (models/modules/full_model.py:79-126: LoRA-wrapped
-// backbone -> last-layer key hook -> decoder).  Two C calls, each enqueues a whole pass on the caller's stream:
-//   ucod_vit_forward_train   image -> key map, saving what the backward needs (per layer: the two residual-stream states in
-//                            f32, LN1 output + LoRA down-projection, qkv, attention output, log-sum-exp, fc1 pre-activation)
-//   ucod_vit_backward        cotangent of the key map -> LoRA gradients of every layer (all other weights are frozen, so no
-//                            weight-gradient GEMMs: dgrad only, ~2x the forward FLOPs with the recomputed attention scores)
-// The _mlp forms take the MLP kind: UCOD_MLP_SWIGLU (Dinov2SwiGLUFFN, modeling_dinov2.py:300-315) saves the interleaved pre-activation [M, 2F] from the weights_in
-// drain (UCOD_EPI_BIAS_SWIGLU_SAVE_BF16) and turns the hidden cotangent into dpre [M, 2F] in the weights_out dgrad's drain (UCOD_EPI_SWIGLU_BWD_BF16).
-// The _lora_mlp forms take the per-layer table of a LoRA module on the MLP input projection (fc1 / weights_in; full_model.py:47-72 hands target_modules to peft):
-// LayerNorm 2 then writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against fc1_w_aug, and the backward recomputes h2_aug from the
-// saved residual stream, takes the module's gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the LayerNorm-2 backward.  A NULL table is the _mlp form.
-// DINOv3 (vit.rope with allow_rope = 1): every layer but the last rotates q / k of the patch rows in place between the QKV GEMM and attention (the last layer's key hook
-// is taken in front of any rotation), and the backward applies the transposed rotation to dq / dk behind ucod_attention_bwd (ucod_rope_qk_ld).  Plans do not change.
-// The _lora_out forms take the per-layer table of the LoRA modules on the output projections (attention.output.dense / mlp.fc2; o_proj / down_proj): their inputs have
-// no aug columns, so each module is one row kernel behind its residual GEMM (ucod_lora_out_fwd: x += lambda * scaling * (drop(x_in) A^T) B^T, u saved) and two in the
-// backward (ucod_lora_out_grad_s on the dgrad GEMM's operand s, ucod_lora_out_grad_x on x_in and its cotangent).  Dropout keys 2L + l (dense) and 3L + l (fc2).
-// A NULL table is the _lora_mlp form.
-// The _lora_out_ex forms take one word of flags: with UCOD_LORA_OUT_SWIGLU the fc2 slots may be filled on the SwiGLU MLP too (Dinov2SwiGLUFFN.weights_out; the gated
-// DINOv3 down_proj): the forward kernel reads the hidden [M, F] as ever, the backward recomputes it from the saved interleaved pre-activation
-// (ucod_lora_out_grad_x_ex with UCOD_LORA_OUT_ACT_SWIGLU on pre / dpre [M, 2F]).  Flags 0 is the _lora_out form.
-// No allocation, no sync.  Operand formats of the LoRA "aug" columns: vit_train.hip.
+// backbone -> last-layer key hook -> decoder).  Three passes, each enqueued whole on the caller's stream:
+//   forward, saving     image -> key map, keeping per layer what the backward needs: the two residual-stream states (f32, or fp16 with vit.resid16), LN1 output + LoRA
+//                       down-projection (h_aug), qkv (DINOv3: with q / k of the patch rows already rotated, so that the recomputed scores see the operands attention
+//                       saw), attention output, log-sum-exp, the fc1 pre-activation ([M, F]; SwiGLU: x1 | x2 interleaved, [M, 2F]) and u [M, 8] of each output module
+//   forward, not saving the same launches on one buffer of each kind, the residual stream updated in place: what the EMA teacher runs (full_model.py:84,108-111)
+//   backward            cotangent of the key map -> LoRA gradients of every layer (all other weights are frozen, so no weight-gradient GEMMs: dgrad only, ~2x the
+//                       forward FLOPs with the recomputed attention scores)
+// One body serves both forwards (`forward`; the four places where it asks `save` are all that differs), so they cannot drift apart: the same arithmetic, the same
+// dropout masks for the same seed.  A call is a Pass: the descriptor, the MLP kind, one word of flags and four tables, of which two are optional --
+//   T, TT   the plain rows and the training table: LoRA on q / k / v rides on the QKV GEMM as 64 extra K columns (operand formats of the "aug" columns: vit_train.hip)
+//   TM      LoRA on the MLP input projection (fc1 / weights_in): LayerNorm 2 writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against
+//           fc1_w_aug; the backward recomputes h2_aug from the saved residual stream, takes the gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the
+//           LayerNorm-2 backward
+//   TO      LoRA on the output projections (attention.output.dense / mlp.fc2; o_proj / down_proj): their inputs have no aug columns, so each module is one row kernel
+//           behind its residual GEMM (ucod_lora_out_fwd: x += lambda * scaling * (drop(x_in) A^T) B^T) and two in the backward (ucod_lora_out_grad_s on the dgrad GEMM's
+//           operand s, ucod_lora_out_grad_x_ex on x_in and its cotangent).  On the SwiGLU MLP the fc2 slots need UCOD_LORA_OUT_SWIGLU in the flags: the backward then
+//           recomputes the hidden from the saved interleaved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU on pre / dpre [M, 2F])
+// The last layer runs LayerNorm 1 and the key projection only: the gradients of its MLP and output modules are written as zeros.
+// Dropout: every module has its own mask, keyed kind * L + l (`dropout_of`: q / k / v, the MLP input, dense, fc2 = kinds 0 .. 3).
+// Every exported symbol -- five functions in five suffix tiers, the older tiers being the _lora_out_ex forms with NULL tables / flags 0 -- fills in a Pass and calls one
+// of the five functions below.  No allocation, no sync.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
 
 namespace {
 
-struct TPlan {
-  int M, tok, L;
+// what a call is (TM / TO NULL: that module is not in the pass; the size functions leave T and TT NULL)
+struct Pass {
+  const ucod_vit_train_desc* t;
+  int mlp, out_flags;
+  const void* const* T;
+  const void* const* TT;
+  const void* const* TM;
+  const void* const* TO;
+};
+
+struct Plan {
+  bool save;                                               // the training pass's plan: per-layer slots; else one buffer of each kind (strides 0) and no lse / pre / u
+  int M, tok;
   size_t x_in, x_mid, h_aug, qkv, att, lse, pre;           // per-layer arrays: base offset; stride below
   size_t s_x, s_h, s_qkv, s_att, s_lse, s_pre;
   size_t h2, g, patch, qscale;                             // forward transients
@@ -36,16 +48,6 @@ struct TPlan {
 };
 
 inline size_t up(size_t v) { return (v + 255) / 256 * 256; }
-
-bool valid_qkv(const ucod_vit_train_desc* t) {
-  if (!t) return false;
-  const ucod_vit_desc* d = &t->vit;
-  return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
-         d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
-         (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
-         d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1);   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
-}
 
 inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU; }
 inline int fc1_width(const ucod_vit_desc* d, int mlp) { return mlp == UCOD_MLP_SWIGLU ? 2 * d->F : d->F; }
@@ -65,23 +67,33 @@ inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* 
   if (out_flags & ~UCOD_LORA_OUT_SWIGLU) return false;            // an unknown flag bit
   if (!TO) return true;
   if (!m.o && !m.f) return false;                                 // a table that names no module
-  // (SwiGLU: the hidden is recomputed from the interleaved, padded [M, 2F] pre-activation -- only with the _ex forms' UCOD_LORA_OUT_SWIGLU)
+  // (SwiGLU: the hidden is recomputed from the interleaved, padded [M, 2F] pre-activation -- only with UCOD_LORA_OUT_SWIGLU)
   if (m.f && mlp != UCOD_MLP_GELU && !(out_flags & UCOD_LORA_OUT_SWIGLU)) return false;
   return (!m.o || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) != 0) && (!m.f || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) != 0);
 }
-bool valid(const ucod_vit_train_desc* t, int mlp = UCOD_MLP_GELU, bool mlpl = false, const void* const* TO = nullptr, int out_flags = 0) {
-  return valid_qkv(t) && known_mlp(mlp) && valid_mlpl(t, mlp, mlpl) && valid_out(t, mlp, TO, out_flags);
+bool valid(const Pass& c) {
+  const ucod_vit_train_desc* t = c.t;
+  if (!t) return false;
+  const ucod_vit_desc* d = &t->vit;
+  return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
+         d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
+         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
+         (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
+         d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
+         known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr) && valid_out(t, c.mlp, c.TO, c.out_flags);
 }
 
-TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const void* const* TO = nullptr) {
+Plan train_plan(const Pass& c) {
+  const ucod_vit_train_desc* t = c.t;
   const ucod_vit_desc* d = &t->vit;
-  TPlan p;
+  const bool mlpl = c.TM != nullptr;
+  Plan p;
+  p.save = true;
   const int gh = d->H / d->P, gw = d->W / d->P;
   p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
   p.M = d->B * p.tok;
-  p.L = d->L;
-  const size_t M = p.M, D = d->D, F = d->F, L = d->L;
-  const size_t FP = mlp == UCOD_MLP_SWIGLU ? 2 * F : F;      // width of the saved pre-activation and of its cotangent (SwiGLU: x1 | x2 interleaved)
+  const size_t M = p.M, D = d->D, L = d->L;
+  const size_t FP = fc1_width(d, c.mlp);                      // width of the saved pre-activation and of its cotangent (SwiGLU: x1 | x2 interleaved)
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += up(bytes); return r; };
   p.s_x = up(M * D * (d->resid16 ? 2 : 4));
@@ -115,8 +127,8 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const 
     p.mgw = take(p.mgw_bytes);
   }
   p.u_o = p.u_2 = p.s_u = p.t_out = p.ogw = p.ogw_bytes = 0;
-  if (TO) {                                                     // (behind everything else: without a table no offset and no byte differs)
-    const OutMods m = out_mods(TO);
+  if (c.TO) {                                                   // (behind everything else: without a table no offset and no byte differs)
+    const OutMods m = out_mods(c.TO);
     p.s_u = up(M * UCOD_LORA_OUT_W * 4);
     if (m.o) p.u_o = take(p.s_u * (L - 1));
     if (m.f) p.u_2 = take(p.s_u * (L - 1));
@@ -128,7 +140,69 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const 
   return p;
 }
 
-}  // namespace
+// The no-grad pass saves nothing: one residual buffer updated in place (x_in == x_mid, every stride 0), no log-sum-exp, no pre-activation, and the output modules add
+// no workspace byte.  Workspace ~ the inference pass's; the residual stream may be IEEE fp16 (vit.resid16) like the frozen-backbone pass's.
+Plan infer_plan(const Pass& c) {
+  const ucod_vit_desc* d = &c.t->vit;
+  Plan p = {};
+  const int gh = d->H / d->P, gw = d->W / d->P;
+  p.tok = gh * gw + 1 + d->n_reg;
+  p.M = d->B * p.tok;
+  const size_t M = p.M, D = d->D, F = d->F;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += up(bytes); return r; };
+  p.x_in = p.x_mid = take(M * D * (d->resid16 ? 2 : 4));
+  p.h_aug = take(M * (D + UCOD_LORA_AUG) * 2);
+  p.h2 = take(M * (D + (c.TM ? UCOD_LORA_AUG : 0)) * 2);
+  p.qkv = take(M * 3 * D * 2);
+  p.att = take(M * D * 2);
+  p.g = take(M * F * 2);                                      // (either kind: the hidden [M, F]; SwiGLU's weights_in output never reaches memory)
+  p.patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
+  p.qscale = take(3 * D * 4);
+  p.total = o;
+  return p;
+}
+
+// the per-layer pointers of a pass, from its plan
+struct Slots {
+  const Plan& p;
+  char* ws;
+  char* at(size_t base, size_t stride, int l) const { return ws + base + stride * l; }
+  float* x_in(int l) const { return (float*)at(p.x_in, p.s_x, l); }
+  float* x_mid(int l) const { return (float*)at(p.x_mid, p.s_x, l); }
+  float* x_next(int l) const { return x_in(l + 1); }                        // (not saving: the same buffer, the residual GEMMs run in place)
+  void* h_aug(int l) const { return at(p.h_aug, p.s_h, l); }
+  void* qkv(int l) const { return at(p.qkv, p.s_qkv, l); }
+  void* att(int l) const { return at(p.att, p.s_att, l); }
+  float* lse(int l) const { return p.save ? (float*)at(p.lse, p.s_lse, l) : nullptr; }
+  void* pre(int l) const { return p.save ? at(p.pre, p.s_pre, l) : nullptr; }
+  float* u_o(int l) const { return p.save ? (float*)at(p.u_o, p.s_u, l) : nullptr; }
+  float* u_2(int l) const { return p.save ? (float*)at(p.u_2, p.s_u, l) : nullptr; }
+};
+
+// The dropout mask of one module in one layer, or NULL with dropout off.  The key is kind * L + l: forward, no-grad forward and backward all take it from here.
+enum ModKind { MOD_QKV = 0, MOD_MLP_IN = 1, MOD_DENSE = 2, MOD_FC2 = 3 };
+struct Dropout {
+  ucod_lora_dropout desc;
+  bool on;
+  const ucod_lora_dropout* ptr() const { return on ? &desc : nullptr; }
+};
+inline Dropout dropout_of(const ucod_vit_train_desc* t, ModKind kind, int l) {
+  return Dropout{{t->lora_dropout, t->seed, (int)kind * t->vit.L + l}, t->lora_dropout > 0.f};
+}
+
+// the kernels that come in a pair, one per type of the residual stream (r16: IEEE fp16, else f32)
+inline int layernorm_lora(bool r16, const void* x, const float* gam, const float* bet, const float* lora, int r, void* y_aug, int M, int D, float eps,
+                          const ucod_lora_dropout* drop, void* stream) {
+  return r16 ? ucod_layernorm_lora_h16(x, gam, bet, lora, r, y_aug, M, D, eps, drop, stream)
+             : ucod_layernorm_lora((const float*)x, gam, bet, lora, r, y_aug, M, D, eps, drop, stream);
+}
+inline int layernorm(bool r16, const void* x, const float* gam, const float* bet, void* y, int M, int D, float eps, void* stream) {
+  return r16 ? ucod_layernorm_h16(x, gam, bet, y, M, D, eps, stream) : ucod_layernorm((const float*)x, gam, bet, y, M, D, eps, 0, stream);
+}
+inline int cls_rows(bool r16, float* x, const float* cls_reg, const float* pos, int B, int tok, int D, int n_reg, void* stream) {
+  return r16 ? ucod_cls_rows_h16_reg(x, cls_reg, pos, B, tok, D, n_reg, stream) : ucod_cls_rows_reg(x, cls_reg, pos, B, tok, D, n_reg, stream);
+}
 
 #define RUN(call)                \
   do {                           \
@@ -136,29 +210,21 @@ TPlan make_plan(const ucod_vit_train_desc* t, int mlp, bool mlpl = false, const 
     if (rc__ != 0) return rc__;  \
   } while (0)
 
-extern "C" size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO) {
-  return valid(t, mlp, TM != nullptr, TO, out_flags) ? make_plan(t, mlp, TM != nullptr, TO).total : 0;
-}
-extern "C" size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
-  return ucod_vit_train_workspace_bytes_lora_out_ex(t, mlp, 0, TM, TO);
-}
-extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
-  return ucod_vit_train_workspace_bytes_lora_out(t, mlp, TM, nullptr);
-}
-extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_train_workspace_bytes_lora_mlp(t, mlp, nullptr); }
-extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_train_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
+size_t train_bytes(const Pass& c) { return valid(c) ? train_plan(c).total : 0; }
+size_t infer_bytes(const Pass& c) { return valid(c) ? infer_plan(c).total : 0; }
 
-extern "C" int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
-                                                  const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
-                                                  size_t workspace_bytes, void* stream) {
+// Both forward passes.  `save`: the training pass (per-layer slots, log-sum-exp, the *_SAVE_BF16 fc1 drains, u of the output modules); else the no-grad pass.
+int forward(const Pass& c, bool save, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr, TO, out_flags) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  if (!valid(c) || !c.T || !c.TT || !img || !key_out || !workspace) return UCOD_EINVAL;
+  const ucod_vit_train_desc* t = c.t;
   const ucod_vit_desc* d = &t->vit;
-  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
-  const OutMods om = out_mods(TO);
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU;
+  const Plan p = save ? train_plan(c) : infer_plan(c);
+  const OutMods om = out_mods(c.TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
+  const Slots at{p, ws};
   const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
   float* qscale = (float*)(ws + p.qscale);
   void* h2 = ws + p.h2;
@@ -169,240 +235,75 @@ extern "C" int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, 
   const bool r16 = d->resid16 != 0;                               // fp16 residual stream (saved as such: half the bytes forward and backward)
   const int epi_patch = r16 ? UCOD_EPI_PATCH_TOKENS_H16 : UCOD_EPI_PATCH_TOKENS_F32;
   const int epi_resid = r16 ? UCOD_EPI_BIAS_SCALE_RESID_H16 : UCOD_EPI_BIAS_SCALE_RESID_F32;
-  float* x0 = (float*)(ws + p.x_in);
+  const int epi_fc1 = save ? (swiglu ? UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 : UCOD_EPI_BIAS_GELU_SAVE_BF16) : (swiglu ? UCOD_EPI_BIAS_SWIGLU_BF16 : UCOD_EPI_BIAS_GELU_BF16);
+  float* x0 = at.x_in(0);
   RUN(ucod_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, stream));
-  RUN(ucod_gemm_bf16_reg(epi_patch, patches, T[0], x0, d->B * (tok - 1 - d->n_reg), D, d->Kpad, (const float*)T[1], nullptr, nullptr,
-                         (const float*)T[3], tok, d->n_reg, gv, stream));
-  if (r16) RUN(ucod_cls_rows_h16_reg(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
-  else RUN(ucod_cls_rows_reg(x0, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
+  RUN(ucod_gemm_bf16_reg(epi_patch, patches, c.T[0], x0, d->B * (tok - 1 - d->n_reg), D, d->Kpad, (const float*)c.T[1], nullptr, nullptr,
+                         (const float*)c.T[3], tok, d->n_reg, gv, stream));
+  RUN(cls_rows(r16, x0, (const float*)c.T[2], (const float*)c.T[3], d->B, tok, D, d->n_reg, stream));
 
   for (int l = 0; l < d->L; ++l) {
-    const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
-    const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
-    const bool last = (l == d->L - 1);
-    float* x_in = (float*)(ws + p.x_in + p.s_x * l);
-    void* h_aug = ws + p.h_aug + p.s_h * l;
-    const ucod_lora_dropout drop{t->lora_dropout, t->seed, l};
-    if (r16) RUN(ucod_layernorm_lora_h16(x_in, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps,
-                                         t->lora_dropout > 0.f ? &drop : nullptr, stream));
-    else RUN(ucod_layernorm_lora(x_in, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps,
-                                 t->lora_dropout > 0.f ? &drop : nullptr, stream));
-    if (last) {   // key hook: K rows of the augmented qkv weight; [B,D,h,w] out
+    const void* const* W = c.T + 4 + UCOD_VIT_LAYER_STRIDE * l;
+    const void* const* X = c.TT + UCOD_VIT_TRAIN_STRIDE * l;
+    float* x_in = at.x_in(l);
+    void* h_aug = at.h_aug(l);
+    RUN(layernorm_lora(r16, x_in, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps, dropout_of(t, MOD_QKV, l).ptr(), stream));
+    if (l == d->L - 1) {   // key hook: K rows of the augmented qkv weight; [B,D,h,w] out
       const char* wk = (const char*)X[0] + (size_t)D * KA * 2;
       RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, d->n_reg, gv, stream));
       break;
     }
-    float* x_mid = (float*)(ws + p.x_mid + p.s_x * l);
-    float* x_next = (float*)(ws + p.x_in + p.s_x * (l + 1));
-    void* qkv = ws + p.qkv + p.s_qkv * l;
-    void* att = ws + p.att + p.s_att * l;
-    float* lse = (float*)(ws + p.lse + p.s_lse * l);
-    void* pre = ws + p.pre + p.s_pre * l;
+    float* x_mid = at.x_mid(l);
+    float* x_next = at.x_next(l);
+    void* qkv = at.qkv(l);
+    void* att = at.att(l);
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
     // DINOv3: q and k of the patch rows are rotated in the SAVED buffer, so that the backward's recomputed scores see the operands attention saw
     if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
-    RUN(ucod_attention_fwd_lse(qkv, att, lse, d->B, tok, d->heads, stream));
+    if (save) RUN(ucod_attention_fwd_lse(qkv, att, at.lse(l), d->B, tok, d->heads, stream));
+    else RUN(ucod_attention_fwd(qkv, att, d->B, tok, d->heads, 0.f, 0, stream));
     RUN(ucod_gemm_bf16(epi_resid, att, W[4], x_mid, M, D, D, (const float*)W[5], (const float*)W[6], x_in, nullptr, tok, gv, stream));
-    const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
-    if (om.o) {   // LoRA on the attention output projection: x_mid += ls1 * scaling * (drop(att) A_o^T) B_o^T, u saved (its own mask: key 2L + l)
-      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
-      RUN(ucod_lora_out_fwd(att, (const float*)Z[0], t->lora_r, t->lora_scaling, (const float*)W[6], x_mid, r16, (float*)(ws + p.u_o + p.s_u * l), M, D, D,
-                            t->lora_dropout > 0.f ? &drop_o : nullptr, stream));
-    }
-    if (TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug (its own mask: key L + l)
-      const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
-      const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
+    const void* const* Z = c.TO ? c.TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
+    if (om.o)   // LoRA on the attention output projection: x_mid += ls1 * scaling * (drop(att) A_o^T) B_o^T, u saved or dropped
+      RUN(ucod_lora_out_fwd(att, (const float*)Z[0], t->lora_r, t->lora_scaling, (const float*)W[6], x_mid, r16, at.u_o(l), M, D, D, dropout_of(t, MOD_DENSE, l).ptr(),
+                            stream));
+    const void* fc1_w = W[9];
+    int fc1_k = D;
+    if (c.TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug
+      const void* const* Y = c.TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
       RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D, d->eps,
-                                  t->lora_dropout > 0.f ? &drop_m : nullptr, stream));
-      RUN(ucod_gemm_bf16_train(swiglu ? UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 : UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, Y[0], g, M, fc1_width(d, mlp), KA, (const float*)W[10],
-                               nullptr, pre, gv, stream));
+                                  dropout_of(t, MOD_MLP_IN, l).ptr(), stream));
+      fc1_w = Y[0];
+      fc1_k = KA;
     } else {
-      if (r16) RUN(ucod_layernorm_h16(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
-      else RUN(ucod_layernorm(x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-      if (swiglu) RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_SWIGLU_SAVE_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, pre, gv, stream));
-      else RUN(ucod_gemm_bf16_train(UCOD_EPI_BIAS_GELU_SAVE_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, pre, gv, stream));
+      RUN(layernorm(r16, x_mid, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
     }
+    if (save) RUN(ucod_gemm_bf16_train(epi_fc1, h2, fc1_w, g, M, fc1_width(d, c.mlp), fc1_k, (const float*)W[10], nullptr, at.pre(l), gv, stream));
+    else RUN(ucod_gemm_bf16(epi_fc1, h2, fc1_w, g, M, fc1_width(d, c.mlp), fc1_k, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x_next, M, D, F, (const float*)W[12], (const float*)W[13], x_mid, nullptr, tok, gv, stream));
-    if (om.f) {   // LoRA on the MLP output projection: x_next += ls2 * scaling * (drop(g) A_2^T) B_2^T, u saved (key 3L + l)
-      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
-      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x_next, r16, (float*)(ws + p.u_2 + p.s_u * l), M, F, D,
-                            t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
-    }
+    if (om.f)   // LoRA on the MLP output projection: x_next += ls2 * scaling * (drop(g) A_2^T) B_2^T, u saved or dropped
+      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x_next, r16, at.u_2(l), M, F, D, dropout_of(t, MOD_FC2, l).ptr(),
+                            stream));
   }
   return UCOD_OK;
 }
-extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                               const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_train_lora_out_ex(t, mlp, 0, T, TT, TM, TO, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_train_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
-                                          float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_train_lora_mlp(t, mlp, T, TT, nullptr, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
-                                      float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_train_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
-}
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// No-grad pass of the LoRA backbone: what the EMA teacher of models/modules/full_model.py:84,108-111 runs (backbone_ema under
-// torch.no_grad()).  Same arithmetic as ucod_vit_forward_train -- LoRA as 64 extra K columns of the QKV / key GEMMs, dropout masks
-// from the same counter hash -- but nothing is saved: one residual buffer updated in place, plain GELU epilogue, no log-sum-exp, and
-// the residual stream may be IEEE fp16 (vit.resid16) like the frozen-backbone pass.  Workspace ~ the inference pass's.
-namespace {
-struct IPlan {
-  size_t x, h_aug, h2, qkv, a, g, patch, qscale, total;
-  int M, tok;
-};
-bool valid_infer(const ucod_vit_train_desc* t) {
-  if (!t) return false;
-  const ucod_vit_desc* d = &t->vit;
-  return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
-         d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f && d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&
-         (d->rope == nullptr || t->allow_rope == 1);                // (DINOv3: as valid_qkv)
-}
-IPlan make_iplan(const ucod_vit_train_desc* t, bool mlpl = false) {
-  const ucod_vit_desc* d = &t->vit;
-  IPlan p;
-  const int gh = d->H / d->P, gw = d->W / d->P;
-  p.tok = gh * gw + 1 + d->n_reg;                                  // [CLS | n_reg register tokens | patches]
-  p.M = d->B * p.tok;
-  const size_t M = p.M, D = d->D, F = d->F;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += up(bytes); return r; };
-  p.x = take(M * D * (d->resid16 ? 2 : 4));
-  p.h_aug = take(M * (D + UCOD_LORA_AUG) * 2);
-  p.h2 = take(M * (D + (mlpl ? UCOD_LORA_AUG : 0)) * 2);
-  p.qkv = take(M * 3 * D * 2);
-  p.a = take(M * D * 2);
-  p.g = take(M * F * 2);                                      // (either kind: the hidden [M, F]; SwiGLU's weights_in output never reaches memory)
-  p.patch = take((size_t)d->B * gh * gw * d->Kpad * 2);
-  p.qscale = take(3 * D * 4);
-  p.total = o;
-  return p;
-}
-}  // namespace
-
-// (the no-grad pass saves nothing: the output modules add no workspace byte)
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM,
-                                                                  const void* const* TO) {
-  return valid_infer(t) && known_mlp(mlp) && valid_mlpl(t, mlp, TM != nullptr) && valid_out(t, mlp, TO, out_flags) ? make_iplan(t, TM != nullptr).total : 0;
-}
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
-  return ucod_vit_lora_infer_workspace_bytes_lora_out_ex(t, mlp, 0, TM, TO);
-}
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
-  return ucod_vit_lora_infer_workspace_bytes_lora_out(t, mlp, TM, nullptr);
-}
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return ucod_vit_lora_infer_workspace_bytes_lora_mlp(t, mlp, nullptr); }
-extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return ucod_vit_lora_infer_workspace_bytes_mlp(t, UCOD_MLP_GELU); }
-
-extern "C" int ucod_vit_forward_lora_infer_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
-                                                       const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
-                                                       size_t workspace_bytes, void* stream) {
+int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
   UCOD_BF16_ONLY();
-  if (!valid_infer(t) || !known_mlp(mlp) || !valid_mlpl(t, mlp, TM != nullptr) || !valid_out(t, mlp, TO, out_flags) || !T || !TT || !img || !key_out || !workspace) return UCOD_EINVAL;
-  const OutMods om = out_mods(TO);
-  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
+  if (!valid(c) || !c.T || !c.TT || !dkey || !workspace) return UCOD_EINVAL;
+  const ucod_vit_train_desc* t = c.t;
   const ucod_vit_desc* d = &t->vit;
-  const IPlan p = make_iplan(t, TM != nullptr);
-  if (workspace_bytes < p.total) return UCOD_ENOMEM;
-  char* ws = (char*)workspace;
-  const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KA = D + UCOD_LORA_AUG;
-  const bool r16 = d->resid16 != 0;
-  float* x = (float*)(ws + p.x);
-  void* h_aug = ws + p.h_aug;
-  void* h2 = ws + p.h2;
-  void* qkv = ws + p.qkv;
-  void* a = ws + p.a;
-  void* g = ws + p.g;
-  void* patches = ws + p.patch;
-  float* qscale = (float*)(ws + p.qscale);
-  const int epi_patch = r16 ? UCOD_EPI_PATCH_TOKENS_H16 : UCOD_EPI_PATCH_TOKENS_F32;
-  const int epi_resid = r16 ? UCOD_EPI_BIAS_SCALE_RESID_H16 : UCOD_EPI_BIAS_SCALE_RESID_F32;
-  RUN(ucod_fill_qscale(qscale, D, 0.125f * 1.4426950408889634f, stream));
-  RUN(ucod_patch_im2col(img, patches, d->B, d->C, d->H, d->W, d->P, d->Kpad, stream));
-  RUN(ucod_gemm_bf16_reg(epi_patch, patches, T[0], x, d->B * (tok - 1 - d->n_reg), D, d->Kpad, (const float*)T[1], nullptr, nullptr, (const float*)T[3], tok, d->n_reg, gv, stream));
-  if (r16) RUN(ucod_cls_rows_h16_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
-  else RUN(ucod_cls_rows_reg(x, (const float*)T[2], (const float*)T[3], d->B, tok, D, d->n_reg, stream));
-  for (int l = 0; l < d->L; ++l) {
-    const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
-    const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
-    const ucod_lora_dropout drop{t->lora_dropout, t->seed, l};
-    const ucod_lora_dropout* dp = t->lora_dropout > 0.f ? &drop : nullptr;
-    if (r16) RUN(ucod_layernorm_lora_h16(x, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps, dp, stream));
-    else RUN(ucod_layernorm_lora(x, (const float*)W[0], (const float*)W[1], (const float*)X[5], t->lora_r, h_aug, M, D, d->eps, dp, stream));
-    if (l == d->L - 1) {
-      const char* wk = (const char*)X[0] + (size_t)D * KA * 2;
-      RUN(ucod_gemm_bf16_reg(UCOD_EPI_KEY_NCHW_F32, wk, h_aug, key_out, D, M, KA, (const float*)W[3] + D, nullptr, nullptr, nullptr, tok, d->n_reg, gv, stream));
-      break;
-    }
-    RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, h_aug, X[0], qkv, M, 3 * D, KA, (const float*)W[3], qscale, nullptr, nullptr, tok, gv, stream));
-    if (d->rope) RUN(ucod_rope_qk_ld(qkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, 3 * D, 0, stream));
-    RUN(ucod_attention_fwd(qkv, a, d->B, tok, d->heads, 0.f, 0, stream));
-    RUN(ucod_gemm_bf16(epi_resid, a, W[4], x, M, D, D, (const float*)W[5], (const float*)W[6], x, nullptr, tok, gv, stream));
-    const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
-    if (om.o) {   // (as the training pass: same arithmetic, same mask keys, u not saved)
-      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
-      RUN(ucod_lora_out_fwd(a, (const float*)Z[0], t->lora_r, t->lora_scaling, (const float*)W[6], x, r16, nullptr, M, D, D, t->lora_dropout > 0.f ? &drop_o : nullptr,
-                            stream));
-    }
-    if (TM) {
-      const void* const* Y = TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
-      const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
-      RUN(ucod_layernorm_lora_mlp(x, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D, d->eps,
-                                  t->lora_dropout > 0.f ? &drop_m : nullptr, stream));
-      RUN(ucod_gemm_bf16(swiglu ? UCOD_EPI_BIAS_SWIGLU_BF16 : UCOD_EPI_BIAS_GELU_BF16, h2, Y[0], g, M, fc1_width(d, mlp), KA, (const float*)W[10], nullptr, nullptr,
-                         nullptr, tok, gv, stream));
-    } else {
-      if (r16) RUN(ucod_layernorm_h16(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, stream));
-      else RUN(ucod_layernorm(x, (const float*)W[7], (const float*)W[8], h2, M, D, d->eps, 0, stream));
-      if (swiglu) RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_SWIGLU_BF16, h2, W[9], g, M, 2 * F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
-      else RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_GELU_BF16, h2, W[9], g, M, F, D, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
-    }
-    RUN(ucod_gemm_bf16(epi_resid, g, W[11], x, M, D, F, (const float*)W[12], (const float*)W[13], x, nullptr, tok, gv, stream));
-    if (om.f) {
-      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
-      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x, r16, nullptr, M, F, D, t->lora_dropout > 0.f ? &drop_f : nullptr,
-                            stream));
-    }
-  }
-  return UCOD_OK;
-}
-extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                                    const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_lora_infer_lora_out_ex(t, mlp, 0, T, TT, TM, TO, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_lora_infer_lora_out(t, mlp, T, TT, TM, nullptr, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img,
-                                               float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_lora_infer_lora_mlp(t, mlp, T, TT, nullptr, img, key_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img,
-                                           float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_forward_lora_infer_mlp(t, UCOD_MLP_GELU, T, TT, img, key_out, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
-                                             const void* const* TM, const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
-  UCOD_BF16_ONLY();
-  if (!valid(t, mlp, TM != nullptr, TO, out_flags) || !T || !TT || !dkey || !workspace) return UCOD_EINVAL;
-  const ucod_vit_desc* d = &t->vit;
-  const bool swiglu = mlp == UCOD_MLP_SWIGLU;
-  const TPlan p = make_plan(t, mlp, TM != nullptr, TO);
+  const void* const* T = c.T;
+  const void* const* TT = c.TT;
+  const void* const* TM = c.TM;
+  const void* const* TO = c.TO;
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU;
+  const Plan p = train_plan(c);
   const OutMods om = out_mods(TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
   char* ws = (char*)workspace;
-  const int M = p.M, tok = p.tok, D = d->D, F = d->F, gv = d->gemm_variant, KQ = 3 * D + UCOD_LORA_AUG, r = t->lora_r;
+  const Slots at{p, ws};
+  const int M = p.M, tok = p.tok, D = d->D, F = d->F, N1 = fc1_width(d, c.mlp), gv = d->gemm_variant, KQ = 3 * D + UCOD_LORA_AUG, r = t->lora_r;
   float* dx = (float*)(ws + p.dx);
   float* dh = (float*)(ws + p.dh);
   void* s = ws + p.s;
@@ -425,20 +326,17 @@ extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int m
   };
   auto qkv_side = [&](int l) -> int {   // dqkv_aug (k/q/v thirds filled) -> LoRA grads of layer l, dh = d LN1 output
     const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
-    const void* h_aug = ws + p.h_aug + p.s_h * l;
-    const ucod_lora_dropout drop{t->lora_dropout, t->seed, l};
-    RUN(ucod_lora_grad(dqkv, h_aug, (const float*)X[5], r, t->lora_scaling, (float*)X[6], 0, lgw, lgw_bytes, M, D,
-                       t->lora_dropout > 0.f ? &drop : nullptr, stream));
+    RUN(ucod_lora_grad(dqkv, at.h_aug(l), (const float*)X[5], r, t->lora_scaling, (float*)X[6], 0, lgw, lgw_bytes, M, D, dropout_of(t, MOD_QKV, l).ptr(), stream));
     RUN(ucod_gemm_bf16(epi_dh, dqkv, X[1], dh, M, D, KQ, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     return UCOD_OK;
   };
 
   // LayerNorm-1 backward of layer l: with dropout on, the masked LoRA branch t A is added here (it cannot ride on the dgrad GEMM)
   auto ln1_bwd = [&](int l, const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale) -> int {
-    if (t->lora_dropout > 0.f) {
-      const ucod_lora_dropout drop{t->lora_dropout, t->seed, l};
+    const Dropout drop = dropout_of(t, MOD_QKV, l);
+    if (drop.on) {
       const float* lora_l = (const float*)(TT + UCOD_VIT_TRAIN_STRIDE * l)[5];
-      return ucod_layernorm_bwd_lora_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s, M, D, d->eps, dqkv, lora_l, r, &drop, stream);
+      return ucod_layernorm_bwd_lora_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s, M, D, d->eps, dqkv, lora_l, r, drop.ptr(), stream);
     }
     return ln_bwd_plain(dy, x, gam, dres, next_scale);
   };
@@ -446,7 +344,7 @@ extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int m
   // last layer: only the key projection reaches the loss (its MLP never runs: the module's gradients there are zeros, written as such)
   const int last = d->L - 1;
   if (TM) {
-    const size_t n_m = (size_t)r * (size_t)(D + fc1_width(d, mlp)) * sizeof(float);
+    const size_t n_m = (size_t)r * (size_t)(D + N1) * sizeof(float);
     if (hipMemsetAsync(const_cast<void*>((TM + UCOD_VIT_TRAIN_MLP_STRIDE * last)[2]), 0, n_m, (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
   }
   if (TO) {   // (nor do its attention output and fc2: zeros, written as such)
@@ -460,63 +358,52 @@ extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int m
   {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * last;
     const void* const* Wp = T + 4 + UCOD_VIT_LAYER_STRIDE * (last - 1);
-    RUN(ln1_bwd(last, dh, (const float*)(ws + p.x_in + p.s_x * last), (const float*)W[0], nullptr, (const float*)Wp[13]));
+    RUN(ln1_bwd(last, dh, at.x_in(last), (const float*)W[0], nullptr, (const float*)Wp[13]));
   }
   for (int l = last - 1; l >= 0; --l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
     const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
-    const float* x_in = (const float*)(ws + p.x_in + p.s_x * l);
-    const float* x_mid = (const float*)(ws + p.x_mid + p.s_x * l);
-    const void* qkv = ws + p.qkv + p.s_qkv * l;
-    const void* att = ws + p.att + p.s_att * l;
-    const float* lse = (const float*)(ws + p.lse + p.s_lse * l);
-    const void* pre = ws + p.pre + p.s_pre * l;
+    const float* x_in = at.x_in(l);
+    const float* x_mid = at.x_mid(l);
+    const void* qkv = at.qkv(l);
+    const void* att = at.att(l);
+    const void* pre = at.pre(l);
     // MLP branch: s = ls2 * dx  ->  fc2 dgrad (x gelu')  ->  fc1 dgrad  ->  LN2 backward + residual
     // (SwiGLU: the weights_out dgrad's drain writes the cotangent of the interleaved weights_in output, dpre [M, 2F]; X[3] = weights_in^T [D, 2F] in that column order)
-    if (swiglu) {
-      RUN(ucod_gemm_bf16_train(UCOD_EPI_SWIGLU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
-    } else {
-      RUN(ucod_gemm_bf16_train(UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
-    }
+    RUN(ucod_gemm_bf16_train(swiglu ? UCOD_EPI_SWIGLU_BWD_BF16 : UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
     const void* const* Z = TO ? TO + UCOD_VIT_TRAIN_OUT_STRIDE * l : nullptr;
     if (om.f) {
       // LoRA on the MLP output projection, while `s` (= bf16(ls2 * dx), the fc2 dgrad's operand) is still there: t = scaling * s B_2 and dB_2 from s and the saved u,
       // then dA_2 from t and the hidden recomputed as gelu(pre), and dpre += gelu'(pre) * mask/(1-p) * (t A_2) -- completed before anything below reads dpre
       // (SwiGLU, UCOD_LORA_OUT_SWIGLU: the hidden is silu(x1) * x2 of the interleaved pre [M, 2F], and dpre [M, 2F] takes the term through both derivative factors)
-      const ucod_lora_dropout drop_f{t->lora_dropout, t->seed, 3 * d->L + l};
       float* gz = (float*)const_cast<void*>(Z[3]);
-      RUN(ucod_lora_out_grad_s(s, (const float*)(ws + p.u_2 + p.s_u * l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes,
-                               M, F, D, stream));
+      RUN(ucod_lora_out_grad_s(s, at.u_2(l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes, M, F, D, stream));
       RUN(ucod_lora_out_grad_x_ex(pre, swiglu ? UCOD_LORA_OUT_ACT_SWIGLU : UCOD_LORA_OUT_ACT_GELU, swiglu ? UCOD_LORA_OUT_SWIGLU : 0, dpre,
-                                  (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D,
-                                  t->lora_dropout > 0.f ? &drop_f : nullptr, stream));
+                                  (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D, dropout_of(t, MOD_FC2, l).ptr(), stream));
     }
-    const ucod_lora_dropout drop_m{t->lora_dropout, t->seed, d->L + l};
-    const ucod_lora_dropout* dp_m = t->lora_dropout > 0.f ? &drop_m : nullptr;
+    const Dropout drop_m = dropout_of(t, MOD_MLP_IN, l);
     const void* const* Y = TM ? TM + UCOD_VIT_TRAIN_MLP_STRIDE * l : nullptr;
     if (TM) {
       // LoRA on the MLP input projection.  `s` (the fc2 dgrad's operand) has been consumed: its buffer takes h2_aug, recomputed from the saved residual
       // stream with the forward's launch (same mask), and is rewritten by the LayerNorm-2 backward below, after the gradient kernel has read it
       void* h2_aug = ws + p.h2;
-      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D, d->eps, dp_m, stream));
-      RUN(ucod_lora_mlp_grad(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M,
-                             fc1_width(d, mlp), D, dp_m, stream));
+      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D, d->eps, drop_m.ptr(), stream));
+      RUN(ucod_lora_mlp_grad(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M, N1, D,
+                             drop_m.ptr(), stream));
     }
-    RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, fc1_width(d, mlp), nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, N1, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     if (TM) RUN(ucod_layernorm_bwd_lora_mlp(dh, x_mid, lnb_flags, (const float*)W[7], dx, (const float*)W[6], dx, s, M, D, d->eps, ws + p.tm, UCOD_LORA_AUG,
-                                            (const float*)Y[1], r, dp_m, stream));
+                                            (const float*)Y[1], r, drop_m.ptr(), stream));
     else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     if (om.o) {   // LoRA on the attention output projection: s = bf16(ls1 * dx); da += mask/(1-p) * (t A_o) before attention backward reads it
-      const ucod_lora_dropout drop_o{t->lora_dropout, t->seed, 2 * d->L + l};
       float* gz = (float*)const_cast<void*>(Z[1]);
-      RUN(ucod_lora_out_grad_s(s, (const float*)(ws + p.u_o + p.s_u * l), (const float*)Z[0], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes,
-                               M, D, D, stream));
+      RUN(ucod_lora_out_grad_s(s, at.u_o(l), (const float*)Z[0], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes, M, D, D, stream));
       RUN(ucod_lora_out_grad_x(att, UCOD_LORA_OUT_ACT_IDENTITY, da, (const float*)(ws + p.t_out), (const float*)Z[0], r, gz, ws + p.ogw, p.ogw_bytes, M, D, D,
-                               t->lora_dropout > 0.f ? &drop_o : nullptr, stream));
+                               dropout_of(t, MOD_DENSE, l).ptr(), stream));
     }
-    RUN(ucod_attention_bwd(qkv, att, da, lse, delta, dqkv, KQ, d->B, tok, d->heads, stream));
+    RUN(ucod_attention_bwd(qkv, att, da, at.lse(l), delta, dqkv, KQ, d->B, tok, d->heads, stream));
     // DINOv3: dq / dk above are the cotangents of the ROTATED operands; the LoRA-gradient kernel and the QKV dgrad want those of the projection outputs,
     // d(pre) = R^T d(post) -- the same table with the sine negated, on the q | k thirds of dqkv_aug (attention_bwd.hip stores dq at 0, dk at D, dv at 2 D)
     if (d->rope) RUN(ucod_rope_qk_ld(dqkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, KQ, 1, stream));
@@ -528,19 +415,98 @@ extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int m
   }
   return UCOD_OK;
 }
+
+}  // namespace
+
+// The exported symbols (include/ucod_dpl.h): five functions in five tiers.  Each fills in Pass{t, mlp, out_flags, T, TT, TM, TO} -- an older tier with UCOD_MLP_GELU,
+// 0 or NULL where it has no argument -- and calls its function above.
+extern "C" size_t ucod_vit_train_workspace_bytes(const ucod_vit_train_desc* t) { return train_bytes(Pass{t, UCOD_MLP_GELU, 0, nullptr, nullptr, nullptr, nullptr}); }
+extern "C" size_t ucod_vit_train_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) { return train_bytes(Pass{t, mlp, 0, nullptr, nullptr, nullptr, nullptr}); }
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
+  return train_bytes(Pass{t, mlp, 0, nullptr, nullptr, TM, nullptr});
+}
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
+  return train_bytes(Pass{t, mlp, 0, nullptr, nullptr, TM, TO});
+}
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO) {
+  return train_bytes(Pass{t, mlp, out_flags, nullptr, nullptr, TM, TO});
+}
+
+extern "C" int ucod_vit_forward_train(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img, float* key_out, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, UCOD_MLP_GELU, 0, T, TT, nullptr, nullptr}, true, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_train_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img, float* key_out,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, nullptr, nullptr}, true, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_train_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, TM, nullptr}, true, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_train_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                               const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, TM, TO}, true, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
+                                                  const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, out_flags, T, TT, TM, TO}, true, img, key_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* dkey, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  return backward(Pass{t, UCOD_MLP_GELU, 0, T, TT, nullptr, nullptr}, dkey, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  return backward(Pass{t, mlp, 0, T, TT, nullptr, nullptr}, dkey, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM, const float* dkey,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  return backward(Pass{t, mlp, 0, T, TT, TM, nullptr}, dkey, workspace, workspace_bytes, stream);
+}
 extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
                                           const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_backward_lora_out_ex(t, mlp, 0, T, TT, TM, TO, dkey, workspace, workspace_bytes, stream);
+  return backward(Pass{t, mlp, 0, T, TT, TM, TO}, dkey, workspace, workspace_bytes, stream);
 }
-extern "C" int ucod_vit_backward_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
-                                          const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_backward_lora_out(t, mlp, T, TT, TM, nullptr, dkey, workspace, workspace_bytes, stream);
+extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT, const void* const* TM,
+                                             const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+  return backward(Pass{t, mlp, out_flags, T, TT, TM, TO}, dkey, workspace, workspace_bytes, stream);
 }
-extern "C" int ucod_vit_backward_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* dkey,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_backward_lora_mlp(t, mlp, T, TT, nullptr, dkey, workspace, workspace_bytes, stream);
+
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return infer_bytes(Pass{t, UCOD_MLP_GELU, 0, nullptr, nullptr, nullptr, nullptr}); }
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_mlp(const ucod_vit_train_desc* t, int mlp) {
+  return infer_bytes(Pass{t, mlp, 0, nullptr, nullptr, nullptr, nullptr});
 }
-extern "C" int ucod_vit_backward(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* dkey,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return ucod_vit_backward_mlp(t, UCOD_MLP_GELU, T, TT, dkey, workspace, workspace_bytes, stream);
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* TM) {
+  return infer_bytes(Pass{t, mlp, 0, nullptr, nullptr, TM, nullptr});
+}
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO) {
+  return infer_bytes(Pass{t, mlp, 0, nullptr, nullptr, TM, TO});
+}
+extern "C" size_t ucod_vit_lora_infer_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO) {
+  return infer_bytes(Pass{t, mlp, out_flags, nullptr, nullptr, TM, TO});
+}
+
+extern "C" int ucod_vit_forward_lora_infer(const ucod_vit_train_desc* t, const void* const* T, const void* const* TT, const float* img, float* key_out,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, UCOD_MLP_GELU, 0, T, TT, nullptr, nullptr}, false, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_lora_infer_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const float* img, float* key_out,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, nullptr, nullptr}, false, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_lora_infer_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, TM, nullptr}, false, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, const void* const* T, const void* const* TT, const void* const* TM,
+                                                    const void* const* TO, const float* img, float* key_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, 0, T, TT, TM, TO}, false, img, key_out, workspace, workspace_bytes, stream);
+}
+extern "C" int ucod_vit_forward_lora_infer_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT,
+                                                       const void* const* TM, const void* const* TO, const float* img, float* key_out, void* workspace,
+                                                       size_t workspace_bytes, void* stream) {
+  return forward(Pass{t, mlp, out_flags, T, TT, TM, TO}, false, img, key_out, workspace, workspace_bytes, stream);
 }

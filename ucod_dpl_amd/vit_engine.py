@@ -956,8 +956,9 @@ class ViTLoRAEngine(ViTEngine):
     """Backbone-backward mode: the frozen ViT with peft-style LoRA on query / key / value of every
     encoder layer, as models/modules/full_model.py:47-72 configures it (r=2, lora_alpha=4, bias='none', target
     query/key/value; lora_A kaiming_uniform(a=sqrt 5), lora_B zeros).  ``forward_train`` saves activations,
-    ``backward`` turns the cotangent of the key map into LoRA gradients -- both entirely in the HIP library
-    (``ucod_vit_forward_train`` / ``ucod_vit_backward``).  LoRA dropout (``lora_dropout``, 0.05 in the reference config) is a counter-based
+    ``backward`` turns the cotangent of the key map into LoRA gradients -- both entirely in the HIP library.  Every pass is ONE call of a _lora_out_ex entry point
+    (``ucod_vit_forward_train_lora_out_ex`` / ``ucod_vit_backward_lora_out_ex`` / ``ucod_vit_forward_lora_infer_lora_out_ex``, include/ucod_dpl.h) with the MLP kind,
+    ``_out_flags`` and the tables of the targeted modules; an untargeted module's table is NULL, and the pass then enqueues the launches it would without it.  LoRA dropout (``lora_dropout``, 0.05 in the reference config) is a counter-based
     hash mask on the LoRA branch's input in ``train()`` mode and off in ``eval()`` (include/ucod_dpl.h: ucod_lora_dropout).
 
     Parameters live in ONE flat f32 arena ``self.lora`` [L, 6*r*D] (layer-major: A_q | B_q | A_k | B_k | A_v | B_v), gradients
@@ -966,19 +967,19 @@ class ViTLoRAEngine(ViTEngine):
     ``target_modules`` (``lora_targets``): a subset of query / key / value keeps that block and holds the untargeted projections' A and B at zero -- their
     gradients are then zero by structure (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero.  With the MLP
     input projection (``fc1`` / ``weights_in``) the row grows to [6*r*D | A_m (r x D) | B_m (N1 x r)], N1 = F (GELU) or 2F in the engine's padded, interleaved row
-    order (SwiGLU), and the passes run the _lora_mlp entry points (include/ucod_dpl.h).  None = query / key / value: the engine as it always was.
+    order (SwiGLU), and the passes are given the module's table (``mlp_table_host``, include/ucod_dpl.h).  None = query / key / value: the engine as it always was.
 
     A DINOv3 checkpoint (``allow_rope=True``) has its own module names -- ``{model.,}layer.{i}.attention.{q,k,v}_proj`` -- which ``target_modules``, the state dicts,
     the merges and the adapter folder use; the arena layout is the same (q | k | v).  No MLP input module is built for it yet.
 
     ``allow_out=True`` also takes the output projections -- ``dense`` (attention.output.dense) and ``fc2`` on a DINOv2 GELU checkpoint, ``o_proj`` and ``down_proj``
-    on a non-gated DINOv3 one -- as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x; the _lora_out entry points).  The arena
+    on a non-gated DINOv3 one -- as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x; the passes are given ``out_table_host``).  The arena
     row then ends in [A_o (r x D) | B_o (D x r)] and [A_2 (r x F) | B_2 (D x r)], for the targeted ones only; 1 <= r <= 8.  The SwiGLU MLP's output projection stays
     refused.  With the flag off, or on with neither module named, every pass is launch for launch what it was.
 
     ``allow_swiglu_out=True`` (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``) lifts that refusal: ``weights_out`` of a DINOv2 SwiGLU
     checkpoint, ``down_proj`` of a gated DINOv3 one.  The backward recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation
-    (UCOD_LORA_OUT_ACT_SWIGLU; the _lora_out_ex entry points with UCOD_LORA_OUT_SWIGLU, taken only when the module is targeted).  The arena row ends in
+    (UCOD_LORA_OUT_ACT_SWIGLU; the passes' flags carry UCOD_LORA_OUT_SWIGLU, set only when the module is targeted).  The arena row ends in
     [A_2 (r x F) | B_2 (D x r)] with F the padded hidden width; the state dicts and the adapter folder carry A_2 as HF has it, [r, F0]: the padded columns are
     zeros in the arena and absent outside it.  A hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers."""
 
@@ -988,7 +989,7 @@ class ViTLoRAEngine(ViTEngine):
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False):
-        """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run the _mlp entry points with
+        """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
         ``allow_rope``: accept a DINOv3 checkpoint (rotary position embedding; ``rope_theta`` as ``ViTEngine``).  Its passes rotate q / k of the patch rows between
@@ -1067,7 +1068,7 @@ class ViTLoRAEngine(ViTEngine):
                                               f"K <= 4096 (a thread keeps the A values of its hidden units in registers); D = {D} must be <= 1536")
                 raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {K}")
             self.out_off[m], numel = numel, numel + r * (K + D)
-        # (the flag of the _lora_out_ex entry points, which the passes take only with the SwiGLU MLP's output projection targeted)
+        # (the flags word of the passes: set only with the SwiGLU MLP's output projection targeted)
         self._out_flags = N.LORA_OUT_SWIGLU if self.out_targets[1] and self.mlp == N.UCOD_MLP_SWIGLU else 0
         self.lora = torch.zeros(L, numel, dtype=torch.float32, device=dev)
         bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
@@ -1233,7 +1234,7 @@ class ViTLoRAEngine(ViTEngine):
 
     def _out_table(self, grad):
         """The output modules' table (native.VIT_TRAIN_OUT_SLOTS; an untargeted module's two slots are NULL) with ``grad`` [L, P] in its gradient slots, or None when
-        neither is targeted -- the passes then run the entry points, and the launches, they always did."""
+        neither is targeted -- the passes then enqueue the launches they always did."""
         if not any(self.out_targets):
             return None
         ptrs = []
@@ -1241,6 +1242,13 @@ class ViTLoRAEngine(ViTEngine):
             for o in self.out_off:
                 ptrs += [None, None] if o is None else [self.lora[i, o:].data_ptr(), grad[i, o:].data_ptr()]
         return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def _pass_args(self, t, gh, gw, i):
+        """What the three passes of chunk ``i`` hand the _lora_out_ex entry points: the leading arguments (descriptor, MLP kind, flags), the tables (T, TT, TM, TO)
+        with the chunk's gradient buffer in their gradient slots -- TM / TO None when the module is not targeted; the size functions take these two alone -- and the
+        tensors kept alive."""
+        T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
+        return (C.byref(t), self.mlp, self._out_flags), (T, TT, TM, self._out_table(self._tside_grad[i])), keep
 
     def _chunks(self, B):
         """Image-parallel sub-batches (``self.train_streams``, default 2): as in ViTEngine.forward, every kernel of both passes is
@@ -1274,29 +1282,11 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             self._chunk_seed[i] = t.seed
-            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
-            TO = self._out_table(self._tside_grad[i])
-            if TO is not None and self._out_flags:                 # the SwiGLU MLP's output projection is targeted: the _lora_out_ex entry points with their flag
-                fl = self._out_flags
-                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(C.byref(t), self.mlp, fl, TM, TO))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_train_lora_out_ex(C.byref(t), self.mlp, fl, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws),
-                                                                        ws.numel(), N.stream()), "ucod_vit_forward_train_lora_out_ex")
-            elif TO is not None:                                   # an output projection is targeted: the _lora_out entry points (TM may be NULL there)
-                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_train_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
-                                                                     N.stream()), "ucod_vit_forward_train_lora_out")
-            elif TM is None:                                       # query / key / value only: the entry points (and launches) the engine always used
-                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_mlp(C.byref(t), self.mlp))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_train_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                            "ucod_vit_forward_train")
-            else:
-                ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_mlp(C.byref(t), self.mlp, TM))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_train_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
-                                                                     N.stream()), "ucod_vit_forward_train_lora_mlp")
+            lead, tabs, keep = self._pass_args(t, gh, gw, i)
+            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(*lead, *tabs[2:]))
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_train_lora_out_ex(*lead, *tabs, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_forward_train_lora_out_ex")
             if self.resid16:
                 self._guard.arm(torch.cuda.current_stream(self.device))
 
@@ -1317,29 +1307,11 @@ class ViTLoRAEngine(ViTEngine):
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             t.vit.resid16 = int(bool(resid16))
-            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
-            TO = self._out_table(self._tside_grad[i])
-            if TO is not None and self._out_flags:
-                fl = self._out_flags
-                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out_ex(C.byref(t), self.mlp, fl, TM, TO))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_out_ex(C.byref(t), self.mlp, fl, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws),
-                                                                             ws.numel(), N.stream()), "ucod_vit_forward_lora_infer_lora_out_ex")
-            elif TO is not None:
-                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out(C.byref(t), self.mlp, TM, TO))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
-                                                                          N.stream()), "ucod_vit_forward_lora_infer_lora_out")
-            elif TM is None:
-                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_mlp(C.byref(t), self.mlp))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_lora_infer_mlp(C.byref(t), self.mlp, T, TT, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                            "ucod_vit_forward_lora_infer")
-            else:
-                ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_mlp(C.byref(t), self.mlp, TM))
-                with self._guard.bind():
-                    N.check(self.lib.ucod_vit_forward_lora_infer_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(),
-                                                                          N.stream()), "ucod_vit_forward_lora_infer_lora_mlp")
+            lead, tabs, keep = self._pass_args(t, gh, gw, i)
+            ws = self._iside_ws[i] = self._workspace(self._iside_ws[i], self.lib.ucod_vit_lora_infer_workspace_bytes_lora_out_ex(*lead, *tabs[2:]))
+            with self._guard.bind():
+                N.check(self.lib.ucod_vit_forward_lora_infer_lora_out_ex(*lead, *tabs, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_forward_lora_infer_lora_out_ex")
             # this engine's own stream type may be f32 (its backward reads it), but THIS pass may run the fp16 one: its saturation counter is
             # fetched behind every chunk and polled by the next call / check_overflow(wait=True) at the loop's boundaries
             if resid16:
@@ -1361,20 +1333,9 @@ class ViTLoRAEngine(ViTEngine):
 
         def run(i, b0, b1):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
-            T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
-            TO = self._out_table(self._tside_grad[i])
+            lead, tabs, keep = self._pass_args(t, gh, gw, i)
             ws = self._tside_ws[i]
-            if TO is not None and self._out_flags:
-                N.check(self.lib.ucod_vit_backward_lora_out_ex(C.byref(t), self.mlp, self._out_flags, T, TT, TM, TO, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(),
-                                                               N.stream()), "ucod_vit_backward_lora_out_ex")
-            elif TO is not None:
-                N.check(self.lib.ucod_vit_backward_lora_out(C.byref(t), self.mlp, T, TT, TM, TO, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                        "ucod_vit_backward_lora_out")
-            elif TM is None:
-                N.check(self.lib.ucod_vit_backward_mlp(C.byref(t), self.mlp, T, TT, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward")
-            else:
-                N.check(self.lib.ucod_vit_backward_lora_mlp(C.byref(t), self.mlp, T, TT, TM, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
-                        "ucod_vit_backward_lora_mlp")
+            N.check(self.lib.ucod_vit_backward_lora_out_ex(*lead, *tabs, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward_lora_out_ex")
 
         self._fan_out(self._tside, self._bounds, run, (dkey,))
         if len(self._bounds) > 1:
