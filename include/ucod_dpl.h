@@ -62,6 +62,9 @@ extern "C" {
  * of the five training-pass entry points (one word of flags: UCOD_LORA_OUT_SWIGLU) were added; the _lora_out forms delegate to them with flags 0. */
 /* (still 5) The MLP hidden in MFMA-fragment order ("BLK16" below): epilogues 23 / 24, ucod_gemm_bf16_blk16a, ucod_gemm_blk16_pair_ok and
  * ucod_vit_forward_blk16 were added; the hidden's workspace slot is sized for 16 ceil(M / 16) rows; nothing existing changed. */
+/* (still 5) The deterministic training step ("Deterministic forms" below): the _det forms of ucod_dba_wgrad, ucod_conv_wgrad_f32, ucod_dba_heads_fwd, ucod_dba_bwd,
+ * ucod_apm_bce, ucod_disc_fwd and ucod_disc_bwd and their *_det_workspace_bytes helpers were added; additions only, the existing entry points are launch for launch
+ * and bit for bit what they were. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -930,6 +933,57 @@ int ucod_conv_wgrad_f32(const float* gd, const float* cols, float* gW, int B, in
 int ucod_linear_sigmoid_bwd(const float* x, const float* w, const float* prob, const float* gprob, float* gx, float* gw, float* gb, int B, int K,
                             int accumulate, void* stream);
 int ucod_disc_bce(const float* probs_student, const float* probs_pseudo, float* g_student, float* g_pseudo, float* loss, int B, float inv, void* stream);
+
+/* ------------------------------------------------------------------ Deterministic forms of the training step
+ *
+ * The entry points above sum across workgroups with floating-point atomics in seven places (the two weight-gradient kernels, sdiag of the heads kernel, the three
+ * small gradients of ucod_dba_bwd, the loss cells of ucod_apm_bce, the BatchNorm sums of ucod_disc_fwd, the Linear gradients of ucod_disc_bwd): their results
+ * depend on the order in which workgroups retire and differ from run to run in the last bits.  A `_det` form executes NO floating-point atomic: every workgroup
+ * stores its partial to a cell of its own in a caller-provided workspace, and a following launch adds the cells in an order that is a pure function of the
+ * problem shape -- never of a device query, an environment variable or ucod_accumulators_prezeroed.  Two calls on equal inputs give equal bits.
+ *
+ * Common rules: `ws` is `*_det_workspace_bytes(...)` bytes (0 = the shape is invalid), 4-byte aligned (8 for ucod_disc_fwd_det); nothing is allocated inside; a NULL
+ * pointer, an invalid shape or a workspace that is too small returns UCOD_EINVAL before anything is launched or written.  Outputs are WRITTEN: what they held
+ * before (NaN included) does not matter, and ucod_accumulators_prezeroed is not consulted.  Every output the default form computes without an atomic (fg, bg, gd, w,
+ * merged, gfg, gbg, the pre-BN activations ...) is bit-identical to the default form's: same kernel body, same arithmetic.
+ *
+ * ucod_dba_wgrad_det: gW [128,C] = sum_{b,p} gd[b][n][p] x[b][c][p].  exact = 0: the three-term bf16 kernel of ucod_dba_wgrad_split; exact != 0: the f32-MFMA kernel of
+ *   ucod_dba_wgrad.  SUMMATION ORDER (part of the contract): the pixel axis is cut into nchunk chunks; workgroup (image b, chunk) stores its f32 accumulator tile
+ *   with plain vector stores to plane q = b * nchunk + chunk of ws, laid out ws[q][n][c] (n = weight-gradient row, c = feature channel; Q = B * nchunk planes,
+ *   Q = workspace_bytes / (4 * 128 * C)); a second launch then writes, one thread per element,
+ *       gW[n][c] = (accumulate ? gW[n][c] : 0) + ws[0][n][c] + ws[1][n][c] + ... + ws[Q-1][n][c]
+ *   sequentially in ascending q, in f32 (ucod_dba_wgrad_det never accumulates).  nchunk depends on (B, C, HW) -- and Nout -- only; it may differ from the atomic form's.
+ * ucod_conv_wgrad_f32_det: the same for gW [Nout,C] with any Nout (ws[q][n][c], n < Nout) and the `accumulate` of ucod_conv_wgrad_f32.
+ * ucod_dba_heads_fwd_det: sdiag[b] = ws[b][0] + ws[b][1] + ... ascending, ws[b][j] = the share of the j-th 256-pixel workgroup (ws [B][ceil(HW/256)] f32).
+ *   ws may be NULL when sdiag is.
+ * ucod_dba_bwd_det: ws = the default form's workspace, then the per-image sums part[b][258] = (g_dec_bias terms [128] | g_head_w terms [128] | g_head_b terms [2]);
+ *   each gradient is the sum over b ascending.
+ * ucod_apm_bce_det: ws[b][3] = image b's terms of losses[0..2]; losses[k] = the sum over b ascending; losses[3] = 0.
+ * ucod_disc_fwd_det: the BatchNorm (sum, sum of squares) of each convolution become per-workgroup f64 partials in ws, summed in ascending workgroup order in f64.  The
+ *   running statistics and `nbt` behave as in ucod_disc_fwd.  The f64 sums at the end of `saved` are neither read nor written, so a caller may alternate the two forms
+ *   on one zero-initialised `saved` buffer.
+ * ucod_disc_bwd_det: ws = the default form's workspace, then per-image partials of g.lin_w and g.lin_b, added in ascending b (with the `accumulate` of ucod_disc_bwd). */
+size_t ucod_dba_wgrad_det_workspace_bytes(int B, int C, int HW, int exact);
+int ucod_dba_wgrad_det(const float* gd, const float* x, float* gW, int B, int C, int HW, int exact, void* ws, size_t ws_bytes, void* stream);
+size_t ucod_conv_wgrad_f32_det_workspace_bytes(int B, int C, int HW, int Nout);
+int ucod_conv_wgrad_f32_det(const float* gd, const float* cols, float* gW, int B, int C, int HW, int Nout, int accumulate, void* ws, size_t ws_bytes,
+                            void* stream);
+size_t ucod_dba_heads_fwd_det_workspace_bytes(int B, int HW);
+int ucod_dba_heads_fwd_det(const float* d, int ld_c, int c0, const float* emb, const float* norm, const float* head_w, const float* head_b, float* fg,
+                           float* bg, float* sdiag, void* ws, size_t ws_bytes, int B, int HW, void* stream);
+size_t ucod_dba_bwd_det_workspace_bytes(int B, int HW);
+int ucod_dba_bwd_det(const float* d, int ld_c, int c0, const float* emb, const float* norm, const float* head_w, const float* gram, const float* gfg,
+                     const float* gbg, float gextra, float* gd, float* g_head_w, float* g_head_b, float* g_dec_bias, void* ws, size_t ws_bytes, int B,
+                     int HW, void* stream);
+size_t ucod_apm_bce_det_workspace_bytes(int B);
+int ucod_apm_bce_det(const float* pl, const float* teacher, const float* fg, const float* bg, const float* p_s, const float* p_p, float epoch_frac,
+                     float gscale, float* w, float* merged, float* gfg, float* gbg, float* losses, void* ws, size_t ws_bytes, int B, int HW, void* stream);
+size_t ucod_disc_fwd_det_workspace_bytes(int B, int fs);
+int ucod_disc_fwd_det(const float* mask, const ucod_disc_params* p_host, float* prob, void* saved, int B, int fs, int update_running, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t ucod_disc_bwd_det_workspace_bytes(int B, int fs);
+int ucod_disc_bwd_det(const float* mask, const ucod_disc_params* p_host, const void* saved, const float* gprob, const ucod_disc_grads* g_host,
+                      int accumulate, void* ws, size_t ws_bytes, int B, int fs, void* stream);
 
 /* ------------------------------------------------------------------ Look-Twice (rows L1-L3) */
 

@@ -187,6 +187,22 @@ int gemm_split16_act(int epilogue, const void* A, const void* B, void* out, int 
 // ucod_accumulators_prezeroed (elementwise.hip): the caller has zeroed the accumulating outputs of the calls it issues next from this host thread
 // (one ucod_zero_segments launch per step instead of a memset in front of every producer)
 bool accumulators_prezeroed();
+// the deterministic forms (include/ucod_dpl.h, "deterministic training step"): the split-K partials of the three-term bf16 weight-gradient kernel
+// (gemm_split.hip) for ucod_dba_wgrad_det (gemm_f32.hip); nchunk = wgrad_split_chunks(B, C, HW), a function of the shape alone
+int wgrad_split_chunks(int B, int C, int HW, int* chunk);
+void wgrad_split_partials(const float* gd, const float* x, float* ws, int B, int C, int HW, hipStream_t s);
+
+// out[i] = (keep ? out[i] : 0) + in[i] + in[i + stride] + ... + in[i + (count - 1) stride], left to right in T: the ordered sum over per-workgroup
+// partials that stands where the default forms have a floating-point atomic.  One thread per element, loads coalesced over i.
+template <typename T>
+__global__ __launch_bounds__(256) void ordered_sum_kernel(const T* __restrict__ in, T* __restrict__ out, long n, long stride, int count, int keep) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  T s = keep ? out[i] : (T)0;
+#pragma unroll 8
+  for (int q = 0; q < count; ++q) s += in[(size_t)q * stride + i];
+  out[i] = s;
+}
 
 // op classes for the optional event profiler (prof.hip); the first six follow the UCOD_EPI_* numbering
 enum ProfClass {

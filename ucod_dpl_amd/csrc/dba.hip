@@ -13,6 +13,7 @@ namespace ucod {
 
 constexpr int E = 64;
 constexpr float NORM_EPS = 1e-12f;
+constexpr int DBA_BWD_PART = 258;   // per-image partials of the deterministic backward: sgd[128] | sga[128] | sg_up[2]
 
 // ---------------------------------------------------------------------------------- column norms
 __global__ __launch_bounds__(256) void colnorm_kernel(const float* __restrict__ d, int ld_c, int c0, const float* __restrict__ emb,
@@ -32,6 +33,8 @@ __global__ __launch_bounds__(256) void colnorm_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------- gate + heads (+ sdiag)
+// DET (ucod_dba_heads_fwd_det): sdiag is the workspace [B][gridDim.x]; the workgroup's share goes to its own cell, an ordered sum follows.
+template <bool DET>
 __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict__ d, int ld_c, int c0, const float* __restrict__ emb,
                                                         const float* __restrict__ norm, const float* __restrict__ head_w,
                                                         const float* __restrict__ head_b, float* __restrict__ fg,
@@ -73,8 +76,22 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
   }
   if (sdiag) {  // uniform branch
     s2 = block_sum(s2, red);
-    if (tid == 0) atomicAdd(&sdiag[b], s2);
+    if constexpr (DET) {
+      if (tid == 0) sdiag[(long)b * gridDim.x + blockIdx.x] = s2;
+    } else {
+      if (tid == 0) atomicAdd(&sdiag[b], s2);
+    }
   }
+}
+
+// out[r] = in[r][0] + in[r][1] + ... + in[r][n - 1], left to right (the ordered sum of the deterministic heads kernel's per-workgroup shares)
+__global__ __launch_bounds__(64) void ordered_sum_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int rows, int n) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= rows) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int j = 0; j < n; ++j) s += in[(long)r * n + j];
+  out[r] = s;
 }
 
 // ---------------------------------------------------------------------------------- Gram matrices (f32 MFMA)
@@ -274,6 +291,8 @@ __global__ __launch_bounds__(256, 2) void dba_bwd_a_kernel(const float* __restri
 // ---------------------------------------------------------------------------------- backward, pass B
 // workgroup = one (image, channel) row: projection backward of f = u/max(||u||,eps) over the pixel axis,
 // then gd; plus the per-channel parameter-gradient reductions (atomics into `small`).
+// DET (ucod_dba_bwd_det): g_dec_bias is the workspace [B][258] = (sgd[128] | sga[128] | sg_up[2]) of image b; dba_bwd_small_reduce_kernel sums over b.
+template <bool DET>
 __global__ __launch_bounds__(256) void dba_bwd_b_kernel(const float* __restrict__ d, int ld_c, int c0, const float* __restrict__ emb,
                                                         const float* __restrict__ norm, const float* __restrict__ head_w,
                                                         const float* __restrict__ gfg, const float* __restrict__ gbg,
@@ -318,14 +337,39 @@ __global__ __launch_bounds__(256) void dba_bwd_b_kernel(const float* __restrict_
   }
   sgd = block_sum(sgd, red);
   sga = block_sum(sga, red);
-  if (tid == 0) {
-    atomicAdd(&g_dec_bias[c], sgd);
-    atomicAdd(&g_head_w[c], sga);
+  if constexpr (DET) {
+    float* part = g_dec_bias + (long)b * DBA_BWD_PART;
+    if (tid == 0) {
+      part[c] = sgd;
+      part[128 + c] = sga;
+    }
+    if (c == 0 || c == E) {           // uniform per block
+      sg_up = block_sum(sg_up, red);
+      if (tid == 0) part[256 + (c == E ? 1 : 0)] = sg_up;
+    }
+  } else {
+    if (tid == 0) {
+      atomicAdd(&g_dec_bias[c], sgd);
+      atomicAdd(&g_head_w[c], sga);
+    }
+    if (c == 0 || c == E) {             // uniform per block
+      sg_up = block_sum(sg_up, red);
+      if (tid == 0) atomicAdd(&g_head_b[c == E ? 1 : 0], sg_up);
+    }
   }
-  if (c == 0 || c == E) {             // uniform per block
-    sg_up = block_sum(sg_up, red);
-    if (tid == 0) atomicAdd(&g_head_b[c == E ? 1 : 0], sg_up);
-  }
+}
+
+// thread i < 258: the ascending sum over images of part[b][i] -> g_dec_bias[i] | g_head_w[i - 128] | g_head_b[i - 256] (written, not accumulated)
+__global__ __launch_bounds__(320) void dba_bwd_small_reduce_kernel(const float* __restrict__ part, float* __restrict__ g_dec_bias,
+                                                                   float* __restrict__ g_head_w, float* __restrict__ g_head_b, int B) {
+  const int i = threadIdx.x;
+  if (i >= DBA_BWD_PART) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) s += part[(long)b * DBA_BWD_PART + i];
+  if (i < 128) g_dec_bias[i] = s;
+  else if (i < 256) g_head_w[i - 128] = s;
+  else g_head_b[i - 256] = s;
 }
 
 }  // namespace ucod
@@ -349,7 +393,25 @@ extern "C" int ucod_dba_heads_fwd(const float* d, int ld_c, int c0, const float*
     hipError_t e = hipMemsetAsync(sdiag, 0, sizeof(float) * B, s);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(heads_fwd_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, head_b, fg, bg, sdiag, HW);
+  hipLaunchKernelGGL(heads_fwd_kernel<false>, dim3(cdiv(HW, 256), B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, head_b, fg, bg, sdiag, HW);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" size_t ucod_dba_heads_fwd_det_workspace_bytes(int B, int HW) {
+  if (B <= 0 || HW <= 0) return 0;
+  return (size_t)B * cdiv(HW, 256) * sizeof(float);
+}
+
+extern "C" int ucod_dba_heads_fwd_det(const float* d, int ld_c, int c0, const float* emb, const float* norm, const float* head_w, const float* head_b,
+                                      float* fg, float* bg, float* sdiag, void* ws, size_t ws_bytes, int B, int HW, void* stream) {
+  if (!d || !emb || !norm || !head_w || !head_b || !fg || B <= 0 || HW <= 0 || c0 < 0 || c0 + 128 > ld_c) return UCOD_EINVAL;
+  if (sdiag && (!ws || ws_bytes < ucod_dba_heads_fwd_det_workspace_bytes(B, HW) || (((uintptr_t)ws) % 4) != 0)) return UCOD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  UCOD_PROF(PROF_DBA_HEADS, s);
+  const int nblk = cdiv(HW, 256);
+  hipLaunchKernelGGL(heads_fwd_kernel<true>, dim3(nblk, B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, head_b, fg, bg, sdiag ? (float*)ws : nullptr, HW);
+  if (sdiag) hipLaunchKernelGGL(ordered_sum_rows_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, (const float*)ws, sdiag, B, nblk);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
@@ -398,7 +460,31 @@ extern "C" int ucod_dba_bwd(const float* d, int ld_c, int c0, const float* emb, 
   if (e != hipSuccess) return (int)e;
   const float coef = (float)(2.0 * (double)gextra / ((double)B * (double)HW * (double)HW));
   hipLaunchKernelGGL(dba_bwd_a_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, gram, gfg, gbg, coef, gfeat, HW);
-  hipLaunchKernelGGL(dba_bwd_b_kernel, dim3(128, B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, gfg, gbg, gfeat, gd, g_head_w, g_head_b, g_dec_bias, HW);
+  hipLaunchKernelGGL(dba_bwd_b_kernel<false>, dim3(128, B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, gfg, gbg, gfeat, gd, g_head_w, g_head_b, g_dec_bias, HW);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+// workspace of the deterministic backward: the default form's (gfeat), then the per-image partials [B][258]
+extern "C" size_t ucod_dba_bwd_det_workspace_bytes(int B, int HW) {
+  if (B <= 0 || HW <= 0) return 0;
+  return ucod_dba_bwd_workspace_bytes(B, HW) + (size_t)B * DBA_BWD_PART * sizeof(float);
+}
+
+extern "C" int ucod_dba_bwd_det(const float* d, int ld_c, int c0, const float* emb, const float* norm, const float* head_w, const float* gram,
+                                const float* gfg, const float* gbg, float gextra, float* gd, float* g_head_w, float* g_head_b, float* g_dec_bias,
+                                void* ws, size_t ws_bytes, int B, int HW, void* stream) {
+  if (!d || !emb || !norm || !head_w || !gram || !gfg || !gbg || !gd || !g_head_w || !g_head_b || !g_dec_bias || !ws || B <= 0 || HW <= 0 ||
+      c0 < 0 || c0 + 128 > ld_c || ws_bytes < ucod_dba_bwd_det_workspace_bytes(B, HW) || (((uintptr_t)ws) % 4) != 0)
+    return UCOD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* gfeat = (float*)ws;
+  float* part = gfeat + (size_t)B * 128 * HW;
+  UCOD_PROF(PROF_DBA_BWD, s);
+  const float coef = (float)(2.0 * (double)gextra / ((double)B * (double)HW * (double)HW));
+  hipLaunchKernelGGL(dba_bwd_a_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, gram, gfg, gbg, coef, gfeat, HW);
+  hipLaunchKernelGGL(dba_bwd_b_kernel<true>, dim3(128, B), dim3(256), 0, s, d, ld_c, c0, emb, norm, head_w, gfg, gbg, gfeat, gd, nullptr, nullptr, part, HW);
+  hipLaunchKernelGGL(dba_bwd_small_reduce_kernel, dim3(1), dim3(320), 0, s, part, g_dec_bias, g_head_w, g_head_b, B);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -39,7 +39,9 @@ __device__ __forceinline__ float bn_lrelu(float y, float mean, float rstd, float
 }
 
 // in: [B,CIN,IH,IW] (pre-BN output of the previous block, or the raw mask when !BN_IN); out: [B,COUT,OH,OW] pre-BN
-template <int CIN, int COUT, int STRIDE, bool BN_IN, int CPT = COUT>
+// DET (ucod_disc_fwd_det): gacc is the workspace [gridDim.x][2*COUT]; the workgroup's (sum, sum of squares) go to its own row as plain f64 stores and
+// bn_finalize_det_kernel sums the rows in ascending order.
+template <int CIN, int COUT, int STRIDE, bool BN_IN, int CPT = COUT, bool DET = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                       const float* __restrict__ in_stats, const float* __restrict__ in_g,
                                                       const float* __restrict__ in_b, float* __restrict__ out,
@@ -149,22 +151,24 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const float* __restrict__ 
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int q = 0; q < PARTS; ++q) { s1 += psum[q][tid]; s2 += psq[q][tid]; }
-    atomicAdd(&gacc[c0 + tid], (double)s1);
-    atomicAdd(&gacc[COUT + c0 + tid], (double)s2);
+    if constexpr (DET) {
+      double* row = gacc + (size_t)blockIdx.x * 2 * COUT;
+      row[c0 + tid] = (double)s1;
+      row[COUT + c0 + tid] = (double)s2;
+    } else {
+      atomicAdd(&gacc[c0 + tid], (double)s1);
+      atomicAdd(&gacc[COUT + c0 + tid], (double)s2);
+    }
   }
 }
 
 // mean / biased variance from the f64 sums the conv kernel accumulated; writes (mean, rstd), updates the running buffers
 // (the sums are consumed here and nowhere else: they are left ZERO for the next call, so that a caller that keeps its `saved` buffer -- allocated
 // zeroed -- under ucod_accumulators_prezeroed never needs a memset in front of ucod_disc_fwd)
-__global__ void bn_finalize_kernel(double* __restrict__ gacc, int C, double n, float* __restrict__ stats,
-                                   float* __restrict__ rmean, float* __restrict__ rvar, int update) {
-  const int c = threadIdx.x;
-  if (c >= C) return;
-  const double mean = gacc[c] / n;
-  double var = gacc[C + c] / n - mean * mean;
-  gacc[c] = 0.0;
-  gacc[C + c] = 0.0;
+__device__ __forceinline__ void bn_finalize_channel(int c, int C, double s1, double s2, double n, float* __restrict__ stats,
+                                                    float* __restrict__ rmean, float* __restrict__ rvar, int update) {
+  const double mean = s1 / n;
+  double var = s2 / n - mean * mean;
   var = var > 0.0 ? var : 0.0;
   stats[c] = (float)mean;
   stats[C + c] = (float)(1.0 / sqrt(var + (double)BN_EPS));
@@ -173,6 +177,38 @@ __global__ void bn_finalize_kernel(double* __restrict__ gacc, int C, double n, f
     rmean[c] = (1.f - BN_MOM) * rmean[c] + BN_MOM * (float)mean;
     rvar[c] = (1.f - BN_MOM) * rvar[c] + BN_MOM * (float)unb;
   }
+}
+__global__ void bn_finalize_kernel(double* __restrict__ gacc, int C, double n, float* __restrict__ stats,
+                                   float* __restrict__ rmean, float* __restrict__ rvar, int update) {
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  const double s1 = gacc[c], s2 = gacc[C + c];
+  gacc[c] = 0.0;
+  gacc[C + c] = 0.0;
+  bn_finalize_channel(c, C, s1, s2, n, stats, rmean, rvar, update);
+}
+// the deterministic form: one workgroup (one wave) per channel sums the nblk per-workgroup partials part[q][2*C] in ascending q, in f64: the lanes fetch 64
+// partials at a time into LDS, lane 0 adds them left to right
+__global__ __launch_bounds__(64) void bn_finalize_det_kernel(const double* __restrict__ part, int nblk, int C, double n, float* __restrict__ stats,
+                                                             float* __restrict__ rmean, float* __restrict__ rvar, int update) {
+  __shared__ double t1[64], t2[64];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  double s1 = 0.0, s2 = 0.0;
+  for (int q0 = 0; q0 < nblk; q0 += 64) {
+    const int q = q0 + lane < nblk ? q0 + lane : nblk - 1;
+    t1[lane] = part[(size_t)q * 2 * C + c];
+    t2[lane] = part[(size_t)q * 2 * C + C + c];
+    __syncthreads();
+    if (lane == 0) {
+      const int m = nblk - q0 < 64 ? nblk - q0 : 64;
+      for (int j = 0; j < m; ++j) {
+        s1 += t1[j];
+        s2 += t2[j];
+      }
+    }
+    __syncthreads();
+  }
+  if (lane == 0) bn_finalize_channel(c, C, s1, s2, n, stats, rmean, rvar, update);
 }
 
 // one workgroup per image: BN3 + LeakyReLU, flatten (c, y, x), Linear, sigmoid
@@ -203,9 +239,16 @@ extern "C" size_t ucod_disc_saved_bytes(int B, int fs) {
   return acc_off_bytes(d) + 112 * sizeof(double);
 }
 
-extern "C" int ucod_disc_fwd(const float* mask, const ucod_disc_params* p, float* prob, void* saved, int B, int fs,
-                             int update_running, void* stream) {
-  if (!mask || !p || !prob || !saved || B <= 0 || fs < 4) return UCOD_EINVAL;
+// per-workgroup BatchNorm partials of the deterministic forward: [nb1][64] | [nb2][32] | [nb3][16] doubles (nb = workgroups along x of each convolution)
+extern "C" size_t ucod_disc_fwd_det_workspace_bytes(int B, int fs) {
+  if (B <= 0 || fs < 4) return 0;
+  const DiscDims d = disc_dims(B, fs);
+  return ((size_t)cdiv((long)B * d.s1 * d.s1, 256) * 64 + (size_t)cdiv((long)B * d.s2 * d.s2, 256) * 32 + (size_t)cdiv((long)B * d.s3 * d.s3, 256) * 16) *
+         sizeof(double);
+}
+
+static int disc_fwd_impl(const float* mask, const ucod_disc_params* p, float* prob, void* saved, int B, int fs, int update_running, double* det_ws,
+                         void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const DiscDims d = disc_dims(B, fs);
   float* y1 = (float*)saved;
@@ -218,6 +261,21 @@ extern "C" int ucod_disc_fwd(const float* mask, const ucod_disc_params* p, float
   double* ac1 = (double*)((char*)saved + acc_off_bytes(d));
   double* ac2 = ac1 + 64;
   double* ac3 = ac2 + 32;
+  if (det_ws) {            // (the sums in `saved` are neither read nor written: whatever the default form left there -- zero -- stays)
+    const int nb1 = cdiv((long)B * d.s1 * d.s1, 256), nb2 = cdiv((long)B * d.s2 * d.s2, 256), nb3 = cdiv((long)B * d.s3 * d.s3, 256);
+    double* pt1 = det_ws;
+    double* pt2 = pt1 + (size_t)nb1 * 64;
+    double* pt3 = pt2 + (size_t)nb2 * 32;
+    hipLaunchKernelGGL((conv3x3_kernel<1, 32, 1, false, 8, true>), dim3(nb1, 4), dim3(256), 0, s, mask, p->w1, nullptr, nullptr, nullptr, y1, pt1, B, fs, d.s1);
+    hipLaunchKernelGGL(bn_finalize_det_kernel, dim3(32), dim3(64), 0, s, pt1, nb1, 32, (double)B * d.s1 * d.s1, st1, p->rm1, p->rv1, update_running);
+    hipLaunchKernelGGL((conv3x3_kernel<32, 16, 2, true, 4, true>), dim3(nb2, 4), dim3(256), 0, s, y1, p->w2, st1, p->g1, p->b1, y2, pt2, B, d.s1, d.s2);
+    hipLaunchKernelGGL(bn_finalize_det_kernel, dim3(16), dim3(64), 0, s, pt2, nb2, 16, (double)B * d.s2 * d.s2, st2, p->rm2, p->rv2, update_running);
+    hipLaunchKernelGGL((conv3x3_kernel<16, 8, 2, true, 2, true>), dim3(nb3, 4), dim3(256), 0, s, y2, p->w3, st2, p->g2, p->b2, y3, pt3, B, d.s2, d.s3);
+    hipLaunchKernelGGL(bn_finalize_det_kernel, dim3(8), dim3(64), 0, s, pt3, nb3, 8, (double)B * d.s3 * d.s3, st3, p->rm3, p->rv3, update_running);
+    hipLaunchKernelGGL(disc_head_kernel, dim3(B), dim3(256), 0, s, y3, st3, p->g3, p->b3, p->lin_w, p->lin_b, prob, d.s3 * d.s3, update_running ? p->nbt : nullptr);
+    UCOD_CHECK_LAUNCH();
+    return UCOD_OK;
+  }
   if (!accumulators_prezeroed()) {
     hipError_t e = hipMemsetAsync(ac1, 0, 112 * sizeof(double), s);
     if (e != hipSuccess) return (int)e;
@@ -233,6 +291,19 @@ extern "C" int ucod_disc_fwd(const float* mask, const ucod_disc_params* p, float
   return UCOD_OK;
 }
 
+extern "C" int ucod_disc_fwd(const float* mask, const ucod_disc_params* p, float* prob, void* saved, int B, int fs,
+                             int update_running, void* stream) {
+  if (!mask || !p || !prob || !saved || B <= 0 || fs < 4) return UCOD_EINVAL;
+  return disc_fwd_impl(mask, p, prob, saved, B, fs, update_running, nullptr, stream);
+}
+
+extern "C" int ucod_disc_fwd_det(const float* mask, const ucod_disc_params* p, float* prob, void* saved, int B, int fs, int update_running, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (!mask || !p || !prob || !saved || !ws || B <= 0 || fs < 4 || ws_bytes < ucod_disc_fwd_det_workspace_bytes(B, fs) || (((uintptr_t)ws) % 8) != 0)
+    return UCOD_EINVAL;
+  return disc_fwd_impl(mask, p, prob, saved, B, fs, update_running, (double*)ws, stream);
+}
+
 // =====================================================================================================
 // Backward (discriminator phase, engine/runner/loop_UCOD_DPL.py:230-255): gradient of sum_b gprob[b]*prob[b]
 // w.r.t. every parameter.  Per block, from the top:  head -> [BN+LeakyReLU backward: per-channel sums of gh and
@@ -242,6 +313,9 @@ extern "C" int ucod_disc_fwd(const float* mask, const ucod_disc_params* p, float
 namespace ucod {
 
 // head: gz = gprob*p*(1-p); g_lin_w += gz*a3; g_lin_b += gz; gh3 = gz*lin_w*lrelu'(h3)
+// DET (ucod_disc_bwd_det): g_lw is the workspace [B][8*HW3] and g_lb the workspace [B]; image b's terms go to its own row, and
+// conv3x3_wgrad_reduce_kernel adds the rows in ascending b into the gradients.
+template <bool DET>
 __global__ __launch_bounds__(256) void disc_head_bwd_kernel(const float* __restrict__ y3, const float* __restrict__ stats,
                                                             const float* __restrict__ g, const float* __restrict__ bta,
                                                             const float* __restrict__ lw, const float* __restrict__ lb,
@@ -261,10 +335,15 @@ __global__ __launch_bounds__(256) void disc_head_bwd_kernel(const float* __restr
     const int c = i / HW3;
     const float h = (y3[(long)b * n + i] - stats[c]) * stats[8 + c] * g[c] + bta[c];
     const float a = h >= 0.f ? h : h * LRELU;
-    atomicAdd(&g_lw[i], gz * a);
+    if constexpr (DET) g_lw[(long)b * n + i] = gz * a;
+    else atomicAdd(&g_lw[i], gz * a);
     gh3[(long)b * n + i] = gz * lw[i] * (h >= 0.f ? 1.f : LRELU);
   }
-  if (tid == 0) atomicAdd(g_lb, gz);
+  if constexpr (DET) {
+    if (tid == 0) g_lb[b] = gz;
+  } else {
+    if (tid == 0) atomicAdd(g_lb, gz);
+  }
 }
 
 // one workgroup per channel: S1 = sum gh, S2 = sum gh*xhat (f64) -> g_beta, g_gamma (accumulated) and sums[c], sums[C+c]
@@ -439,9 +518,15 @@ extern "C" size_t ucod_disc_bwd_workspace_bytes(int B, int fs) {
   return (d.n1 + d.n2 + d.n3 + 2 * (32 + 16 + 8) + (size_t)WGRAD_MAX_PARTIAL) * sizeof(float);
 }
 
-extern "C" int ucod_disc_bwd(const float* mask, const ucod_disc_params* p, const void* saved, const float* gprob,
-                             const ucod_disc_grads* g, int accumulate, void* ws, int B, int fs, void* stream) {
-  if (!mask || !p || !saved || !gprob || !g || !ws || B <= 0 || fs < 4) return UCOD_EINVAL;
+// the default form's workspace, then the per-image partials of the Linear layer's gradients: g_lw [B][8*s3*s3] | g_lb [B]
+extern "C" size_t ucod_disc_bwd_det_workspace_bytes(int B, int fs) {
+  if (B <= 0 || fs < 4) return 0;
+  const DiscDims d = disc_dims(B, fs);
+  return ucod_disc_bwd_workspace_bytes(B, fs) + (d.n3 + (size_t)B) * sizeof(float);
+}
+
+static int disc_bwd_impl(const float* mask, const ucod_disc_params* p, const void* saved, const float* gprob, const ucod_disc_grads* g, int accumulate,
+                         void* ws, int B, int fs, bool det, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const DiscDims d = disc_dims(B, fs);
   const float* y1 = (const float*)saved;
@@ -468,7 +553,15 @@ extern "C" int ucod_disc_bwd(const float* mask, const ucod_disc_params* p, const
     if (e != hipSuccess) return (int)e;
   }
   auto blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)); };
-  hipLaunchKernelGGL(disc_head_bwd_kernel, dim3(B), dim3(256), 0, s, y3, st3, p->g3, p->b3, p->lin_w, p->lin_b, gprob, gh3, g->lin_w, g->lin_b, hw3);
+  if (det) {
+    float* lw_part = wpart + WGRAD_MAX_PARTIAL;
+    float* lb_part = lw_part + d.n3;
+    hipLaunchKernelGGL(disc_head_bwd_kernel<true>, dim3(B), dim3(256), 0, s, y3, st3, p->g3, p->b3, p->lin_w, p->lin_b, gprob, gh3, lw_part, lb_part, hw3);
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(cdiv(8 * hw3, 256)), dim3(256), 0, s, lw_part, g->lin_w, 8 * hw3, B);
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(1), dim3(256), 0, s, lb_part, g->lin_b, 1, B);
+  } else {
+    hipLaunchKernelGGL(disc_head_bwd_kernel<false>, dim3(B), dim3(256), 0, s, y3, st3, p->g3, p->b3, p->lin_w, p->lin_b, gprob, gh3, g->lin_w, g->lin_b, hw3);
+  }
   // block 3
   hipLaunchKernelGGL(bn_bwd_stats_kernel, dim3(8), dim3(1024), 0, s, y3, gh3, 8, B, hw3, st3, su3, g->g3, g->b3);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, blocks(d.n3), dim3(256), 0, s, y3, gh3, 8, hw3, (long)d.n3, st3, p->g3, su3);
@@ -497,4 +590,17 @@ extern "C" int ucod_disc_bwd(const float* mask, const ucod_disc_params* p, const
   }
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+
+extern "C" int ucod_disc_bwd(const float* mask, const ucod_disc_params* p, const void* saved, const float* gprob,
+                             const ucod_disc_grads* g, int accumulate, void* ws, int B, int fs, void* stream) {
+  if (!mask || !p || !saved || !gprob || !g || !ws || B <= 0 || fs < 4) return UCOD_EINVAL;
+  return disc_bwd_impl(mask, p, saved, gprob, g, accumulate, ws, B, fs, false, stream);
+}
+
+extern "C" int ucod_disc_bwd_det(const float* mask, const ucod_disc_params* p, const void* saved, const float* gprob, const ucod_disc_grads* g,
+                                 int accumulate, void* ws, size_t ws_bytes, int B, int fs, void* stream) {
+  if (!mask || !p || !saved || !gprob || !g || !ws || B <= 0 || fs < 4 || ws_bytes < ucod_disc_bwd_det_workspace_bytes(B, fs) || (((uintptr_t)ws) % 4) != 0)
+    return UCOD_EINVAL;
+  return disc_bwd_impl(mask, p, saved, gprob, g, accumulate, ws, B, fs, true, stream);
 }

@@ -250,7 +250,9 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
 // grid (B): one workgroup per image, whose two BCE sums reach `losses` as ONE f32 atomic each.  (One workgroup per 256 pixels added
 // B * HW / 256 = 608 atomics into each loss at the step's size: their order-dependent rounding reached 1.2e-6 of the loss over 300 launches,
 // past the 8-ulp bound of tests/test_gpu_train_kernels.py::test_apm_bce_at_the_headline_size; profiles/r08_apm_bce_loss_spread_ab.jsonl.)
+// DET (ucod_apm_bce_det): losses is the workspace [B][3]; image b's three terms go to its own row and apm_losses_reduce_kernel sums over b.
 constexpr int APM_THREADS = 1024;
+template <bool DET>
 __global__ __launch_bounds__(APM_THREADS) void apm_bce_kernel(const float* __restrict__ pl, const float* __restrict__ teacher,
                                                               const float* __restrict__ fg, const float* __restrict__ bg,
                                                               const float* __restrict__ p_s, const float* __restrict__ p_p, float epoch_frac,
@@ -278,12 +280,33 @@ __global__ __launch_bounds__(APM_THREADS) void apm_bce_kernel(const float* __res
   }
   l1 = block_sum(l1, red);
   l2 = block_sum(l2, red);
-  if (tid == 0) {
-    atomicAdd(&losses[0], l1 / n);
-    atomicAdd(&losses[1], l2 / n);
-    wout[b] = w;
-    atomicAdd(&losses[2], -fmaxf(logf(1.f - ps), -100.f) / (float)B);  // BCELoss(p_s, 0), torch clamps log at -100
+  if constexpr (DET) {
+    if (tid == 0) {
+      losses[3 * b + 0] = l1 / n;
+      losses[3 * b + 1] = l2 / n;
+      wout[b] = w;
+      losses[3 * b + 2] = -fmaxf(logf(1.f - ps), -100.f) / (float)B;
+    }
+  } else {
+    if (tid == 0) {
+      atomicAdd(&losses[0], l1 / n);
+      atomicAdd(&losses[1], l2 / n);
+      wout[b] = w;
+      atomicAdd(&losses[2], -fmaxf(logf(1.f - ps), -100.f) / (float)B);  // BCELoss(p_s, 0), torch clamps log at -100
+    }
   }
+}
+
+// losses[k] = part[0][k] + part[1][k] + ... + part[B - 1][k] for k < 3, left to right; losses[3] (unused) = 0
+__global__ void apm_losses_reduce_kernel(const float* __restrict__ part, float* __restrict__ losses, int B) {
+  const int k = threadIdx.x;
+  if (k >= 4) return;
+  float s = 0.f;
+  if (k < 3) {
+#pragma unroll 8
+    for (int b = 0; b < B; ++b) s += part[3 * b + k];
+  }
+  losses[k] = s;
 }
 
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -376,7 +399,23 @@ extern "C" int ucod_apm_bce(const float* pl, const float* teacher, const float* 
     hipError_t e = hipMemsetAsync(losses, 0, 4 * sizeof(float), s);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(apm_bce_kernel, dim3(B), dim3(APM_THREADS), 0, s, pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale, w, merged, gfg, gbg, losses, B, HW);
+  hipLaunchKernelGGL(apm_bce_kernel<false>, dim3(B), dim3(APM_THREADS), 0, s, pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale, w, merged, gfg, gbg, losses, B, HW);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" size_t ucod_apm_bce_det_workspace_bytes(int B) { return B > 0 ? (size_t)B * 3 * sizeof(float) : 0; }
+
+extern "C" int ucod_apm_bce_det(const float* pl, const float* teacher, const float* fg, const float* bg, const float* p_s, const float* p_p,
+                                float epoch_frac, float gscale, float* w, float* merged, float* gfg, float* gbg, float* losses, void* ws,
+                                size_t ws_bytes, int B, int HW, void* stream) {
+  if (!pl || !teacher || !fg || !bg || !p_s || !p_p || !w || !merged || !gfg || !gbg || !losses || !ws || B <= 0 || HW <= 0 ||
+      ws_bytes < ucod_apm_bce_det_workspace_bytes(B) || (((uintptr_t)ws) % 4) != 0)
+    return UCOD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  UCOD_PROF(PROF_APM, s);
+  hipLaunchKernelGGL(apm_bce_kernel<true>, dim3(B), dim3(APM_THREADS), 0, s, pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale, w, merged, gfg, gbg, (float*)ws, B, HW);
+  hipLaunchKernelGGL(apm_losses_reduce_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, losses, B);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -151,7 +151,9 @@ __global__ __launch_bounds__(256, 2) void dba_project_kernel(const float* __rest
 
 // ------------------------------------------------------------------------------------------- wgrad
 // block: 128 (n) x 128 (c) output tile, reduction over one pixel chunk of one image; waves 2x2, 64x64 each
-template <bool VEC>
+// DET (ucod_dba_wgrad_det / ucod_conv_wgrad_f32_det): gW is the workspace [B * nchunk][Nout][C]; the workgroup stores its tile to plane
+// q = b * nchunk + chunk (plain stores, lanes along c) and an ordered sum over q follows as a launch of its own.
+template <bool VEC, bool DET = false>
 __global__ __launch_bounds__(256, 2) void dba_wgrad_kernel(const float* __restrict__ gd, const float* __restrict__ x,
                                                         float* __restrict__ gW, int C, int HW, int WG_CHUNK, int Nout) {
   // Nout rows of gd per image (128 for the decoupling conv; any count for ucod_conv_wgrad_f32: blockIdx.x also walks 128-row blocks of gd)
@@ -201,6 +203,7 @@ __global__ __launch_bounds__(256, 2) void dba_wgrad_kernel(const float* __restri
       store_kcontig<LDP>(Bs[(t + 1) & 1], tid, rb);
     }
   }
+  if constexpr (DET) gW += ((size_t)b * gridDim.y + blockIdx.y) * (size_t)Nout * C;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -210,7 +213,11 @@ __global__ __launch_bounds__(256, 2) void dba_wgrad_kernel(const float* __restri
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int n = n0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (n < Nout) atomicAdd(&gW[(long)n * C + c], acc[i][j][r]);
+        if constexpr (DET) {
+          if (n < Nout) gW[(long)n * C + c] = acc[i][j][r];
+        } else {
+          if (n < Nout) atomicAdd(&gW[(long)n * C + c], acc[i][j][r]);
+        }
       }
     }
 }
@@ -271,4 +278,61 @@ extern "C" int ucod_conv_wgrad_f32(const float* gd, const float* cols, float* gW
     hipLaunchKernelGGL((dba_wgrad_kernel<false>), grid, block, 0, (hipStream_t)stream, gd, cols, gW, C, HW, WG_CHUNK, Nout);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
+}
+
+// ------------------------------------------------------------------------------------------- deterministic forms
+// Pixel chunk of the exact-f32 kernel in its DET form: coarser than the atomic form's (one wave of workgroups, not four: every chunk is a plane of the
+// workspace to write and read back).  A function of (B, C, HW, Nout) alone.
+static int wgrad_f32_det_chunk(int B, int C, int HW, int Nout) {
+  int chunk = 1024;
+  const long tiles = (long)ucod::cdiv(C, 128) * ucod::cdiv(Nout, 128);
+  while (chunk > 128 && tiles * ucod::cdiv(HW, chunk) * B < 256) chunk >>= 1;
+  return chunk;
+}
+
+extern "C" size_t ucod_conv_wgrad_f32_det_workspace_bytes(int B, int C, int HW, int Nout) {
+  if (B <= 0 || C <= 0 || HW <= 0 || Nout <= 0 || (long)ucod::cdiv(C, 128) * ucod::cdiv(Nout, 128) > 65535) return 0;
+  return (size_t)B * ucod::cdiv(HW, wgrad_f32_det_chunk(B, C, HW, Nout)) * Nout * C * sizeof(float);
+}
+
+extern "C" size_t ucod_dba_wgrad_det_workspace_bytes(int B, int C, int HW, int exact) {
+  if (B <= 0 || C <= 0 || HW <= 0) return 0;
+  if (exact) return ucod_conv_wgrad_f32_det_workspace_bytes(B, C, HW, 128);
+  int chunk;
+  return (size_t)B * ucod::wgrad_split_chunks(B, C, HW, &chunk) * 128 * C * sizeof(float);
+}
+
+// partials of the exact-f32 kernel into ws, then (both forms) the ordered sum over the planes into gW
+static int wgrad_det_run(const float* gd, const float* x, float* gW, int B, int C, int HW, int Nout, int exact, int accumulate, float* ws, size_t need,
+                         hipStream_t s) {
+  using namespace ucod;
+  if (exact) {
+    const int chunk = wgrad_f32_det_chunk(B, C, HW, Nout);
+    dim3 grid((unsigned)(cdiv(C, 128) * cdiv(Nout, 128)), cdiv(HW, chunk), B), block(256);
+    if ((HW % 4) == 0 && (((uintptr_t)x) % 16) == 0 && (((uintptr_t)gd) % 16) == 0)
+      hipLaunchKernelGGL((dba_wgrad_kernel<true, true>), grid, block, 0, s, gd, x, ws, C, HW, chunk, Nout);
+    else
+      hipLaunchKernelGGL((dba_wgrad_kernel<false, true>), grid, block, 0, s, gd, x, ws, C, HW, chunk, Nout);
+  } else {
+    wgrad_split_partials(gd, x, ws, B, C, HW, s);
+  }
+  const long n = (long)Nout * C;
+  const int planes = (int)(need / ((size_t)n * sizeof(float)));
+  hipLaunchKernelGGL(ordered_sum_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, gW, n, n, planes, accumulate);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" int ucod_dba_wgrad_det(const float* gd, const float* x, float* gW, int B, int C, int HW, int exact, void* ws, size_t ws_bytes, void* stream) {
+  const size_t need = ucod_dba_wgrad_det_workspace_bytes(B, C, HW, exact);
+  if (!gd || !x || !gW || !ws || need == 0 || ws_bytes < need || (((uintptr_t)ws) % 4) != 0) return UCOD_EINVAL;
+  UCOD_PROF(ucod::PROF_DBA_WGRAD, stream);
+  return wgrad_det_run(gd, x, gW, B, C, HW, 128, exact != 0, 0, (float*)ws, need, (hipStream_t)stream);
+}
+
+extern "C" int ucod_conv_wgrad_f32_det(const float* gd, const float* cols, float* gW, int B, int C, int HW, int Nout, int accumulate, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  const size_t need = ucod_conv_wgrad_f32_det_workspace_bytes(B, C, HW, Nout);
+  if (!gd || !cols || !gW || !ws || need == 0 || ws_bytes < need || (((uintptr_t)ws) % 4) != 0) return UCOD_EINVAL;
+  return wgrad_det_run(gd, cols, gW, B, C, HW, Nout, 1, accumulate != 0, (float*)ws, need, (hipStream_t)stream);
 }

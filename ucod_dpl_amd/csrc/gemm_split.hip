@@ -287,7 +287,10 @@ __global__ __launch_bounds__(512, 2) void dba_project_b3_kernel(const float* __r
 // halves swapped on odd 8-row groups).  block: 8 waves = all 128 n x CT = 384 channels (C = 768: two channel tiles, x is read exactly
 // once); wave (wr, wc): n 64 wr .., channels 96 wc ..; K-tile 16 pixels; ring of three stages, loads two K-tiles ahead in registers.
 // Split-K over (image, pixel chunk) with f32 atomics into gW, as the f32 kernel.
+// DET (ucod_dba_wgrad_det): gW is the workspace [B * nchunk][128][C]; the workgroup stores its tile to plane q = b * nchunk + chunk instead (plain
+// stores, lanes along c), and an ordered sum over q follows as a launch of its own.
 constexpr int WCT = 384;
+template <bool DET>
 __global__ __launch_bounds__(512, 2) void dba_wgrad_b3_kernel(const float* __restrict__ gd, const float* __restrict__ x, float* __restrict__ gW,
                                                               int C, int HW, int chunk) {
   constexpr int ROWS = 128 + WCT;          // gd rows 0..127 | x rows 128..
@@ -414,6 +417,7 @@ __global__ __launch_bounds__(512, 2) void dba_wgrad_b3_kernel(const float* __res
     if (t + 2 < nt) tile(t + 2, I2{});
   }
   // C/D map: col = lane&31 (channel), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (n)
+  if constexpr (DET) gW += ((size_t)b * gridDim.y + blockIdx.y) * 128 * (size_t)C;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -423,9 +427,24 @@ __global__ __launch_bounds__(512, 2) void dba_wgrad_b3_kernel(const float* __res
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int n = 64 * wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h5;
-        atomicAdd(&gW[(long)n * C + c], acc[i][j][r]);
+        if constexpr (DET) gW[(long)n * C + c] = acc[i][j][r];
+        else atomicAdd(&gW[(long)n * C + c], acc[i][j][r]);
       }
     }
+}
+
+// split-K granularity: about one workgroup per CU (chunk a multiple of the 16-pixel K-tile); a function of (B, C, HW) alone
+int wgrad_split_chunks(int B, int C, int HW, int* chunk) {
+  const int ctiles = cdiv(C, WCT);
+  const int nchunk = max(1, 256 / (ctiles * B));
+  *chunk = cdiv(cdiv(HW, nchunk), 16) * 16;
+  return cdiv(HW, *chunk);
+}
+
+void wgrad_split_partials(const float* gd, const float* x, float* ws, int B, int C, int HW, hipStream_t s) {
+  int chunk;
+  const int nchunk = wgrad_split_chunks(B, C, HW, &chunk);
+  hipLaunchKernelGGL(dba_wgrad_b3_kernel<true>, dim3(cdiv(C, WCT), nchunk, B), dim3(512), 0, s, gd, x, ws, C, HW, chunk);
 }
 
 }  // namespace ucod
@@ -453,16 +472,14 @@ extern "C" int ucod_dba_wgrad_split(const float* gd, const float* x, float* gW, 
   if (!gd || !x || !gW || B <= 0 || C <= 0 || HW <= 0) return UCOD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int ctiles = cdiv(C, WCT);
-  // split-K granularity: about one workgroup per CU (chunk a multiple of the 16-pixel K-tile)
-  int nchunk = max(1, 256 / (ctiles * B));
-  int chunk = cdiv(cdiv(HW, nchunk), 16) * 16;
-  nchunk = cdiv(HW, chunk);
+  int chunk;
+  const int nchunk = wgrad_split_chunks(B, C, HW, &chunk);
   UCOD_PROF(PROF_DBA_WGRAD, s);
   if (!ucod::accumulators_prezeroed()) {
     hipError_t e = hipMemsetAsync(gW, 0, sizeof(float) * 128 * (size_t)C, s);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(dba_wgrad_b3_kernel, dim3(ctiles, nchunk, B), dim3(512), 0, s, gd, x, gW, C, HW, chunk);
+  hipLaunchKernelGGL(dba_wgrad_b3_kernel<false>, dim3(ctiles, nchunk, B), dim3(512), 0, s, gd, x, gW, C, HW, chunk);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -22,6 +22,7 @@ import torch
 
 from ... import ops, parallel
 from ...models.modules.DBA import EMB
+from ..utils import seed as _seed
 
 
 # ------------------------------------------------------------------------------------------------ arenas
@@ -164,6 +165,9 @@ class TrainLoop(BaseLoop):
         self.save_interval = sc.save_interval
         self.log_interval = self.cfg.log_cfg.log_interval
         self.log_scalars = bool(self.cfg.log_cfg.get("log_scalars", False))   # build-only key: per-step .item() logging
+        # build-only key: the step's reductions as fixed-order sums of per-workgroup partials instead of floating-point atomics (the _det entry points of
+        # include/ucod_dpl.h) -- two runs from one seed are bit-identical.  Without the key: what set_random_seed(seed, deterministic=...) left (False).
+        self.deterministic = bool(getattr(self.cfg.train_cfg, "deterministic", _seed.deterministic_default()))
         self.best_mae = 1000.0
         self.best_result = None
         self.last = {}
@@ -187,6 +191,8 @@ class TrainLoop(BaseLoop):
         # gradient arena behind the embedding slot: weight gradient | bias | head_w | head_b); the discriminator's BatchNorm sums live in its saved
         # buffer and are left zero by every forward call.  Round 4: seven rocclr fills per step.
         scratch = self._step_scratch(B, dev)
+        if self.deterministic:                                # the deterministic forms write their outputs: nothing to zero
+            return self._process_batch_zeroed(pseudo_labels, features, pl, scratch)
         ops.zero_segments([scratch, A.g[A.o_W:]])
         with ops.prezeroed():
             return self._process_batch_zeroed(pseudo_labels, features, pl, scratch)
@@ -209,6 +215,7 @@ class TrainLoop(BaseLoop):
         dev = A.device
         fs = self.cfg.model_cfg.feature_size
         B = features.shape[0]
+        det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}
 
         # teacher (no grad) and student share one projection (:156-158).  The reference resizes the 768-channel features to
         # fs x fs first (:153) and then applies the 1x1 conv; both are linear and act on different axes, so they commute:
@@ -224,21 +231,21 @@ class TrainLoop(BaseLoop):
             d = ops.bilinear_resize(d.view(B, 256, fh, fw), fs, fs).view(B, 256, fs * fs)
         norm_s = ops.dba_colnorm(d, 0, emb_s)
         norm_t = ops.dba_colnorm(d, 128, emb_t)
-        fg, bg, sdiag = ops.dba_heads(d, 0, emb_s, norm_s, hw_s, hb_s, want_bg=True, want_sdiag=True, sdiag=scratch[:B])
+        fg, bg, sdiag = ops.dba_heads(d, 0, emb_s, norm_s, hw_s, hb_s, want_bg=True, want_sdiag=True, sdiag=scratch[:B], **det)
         teacher, _, _ = ops.dba_heads(d, 128, emb_t, norm_t, hw_t, hb_t, want_bg=False)
         extra, gram = ops.orth_gram(d, 0, emb_s, norm_s, sdiag)
 
         # APM (:257-272) + both BCE losses and their gradients (:161-173)
         p_s, p_p = self._disc_probs(ops.binarize(fg, logits=True).view(B, 1, fs, fs), ops.binarize(pl, logits=False), features, fs)
         epoch_frac = self._cur_epoch / (self._max_epoch + self._start_finetune)
-        w, merged, gfg, gbg, losses = ops.apm_bce(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world, losses=scratch[B:B + 4])
+        w, merged, gfg, gbg, losses = ops.apm_bce(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world, losses=scratch[B:B + 4], **det)
 
         # backward through heads / gate / normalisation / orthogonality loss, then the 1x1 conv weight gradient
         g_emb, g_W, g_b, g_hw, g_hb = A.slices(A.g)
-        gd, _, _, _ = ops.dba_bwd(d, 0, emb_s, norm_s, hw_s, gram, gfg, gbg, 1.0 / world, g_head_w=g_hw, g_head_b=g_hb, g_dec_bias=g_b)
+        gd, _, _, _ = ops.dba_bwd(d, 0, emb_s, norm_s, hw_s, gram, gfg, gbg, 1.0 / world, g_head_w=g_hw, g_head_b=g_hb, g_dec_bias=g_b, **det)
         if native_grid:                                       # pull the gradient back through the resize (its transpose)
             gd = ops.bilinear_resize_adjoint(gd.view(B, 128, fs, fs), fh, fw).view(B, 128, fh * fw)
-        ops.dba_wgrad(gd, features, gW=g_W)
+        ops.dba_wgrad(gd, features, gW=g_W, **det)
         # RCCL: one flat 128C+386-float buffer, pre-scaled by 1/world, issued asynchronously on the process group's stream; the
         # loss scalars below are assembled meanwhile and the optimiser launch is the first consumer.
         reduced = parallel.allreduce_prescaled_async(A.g)
@@ -327,6 +334,7 @@ class TrainLoop(BaseLoop):
         images = images.to(dev, torch.float32)
         pseudo_labels = pseudo_labels.to(dev, torch.float32)
         B = images.shape[0]
+        det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}   # (the LoRA backbone passes are fixed-order already)
         # the teacher's pass has no consumer until the decoder step: run it on a side stream, concurrently with the student's
         if getattr(self, "_teacher_stream", None) is None:
             self._teacher_stream = torch.cuda.Stream(device=dev)
@@ -355,17 +363,17 @@ class TrainLoop(BaseLoop):
             d_t = ops.bilinear_resize(d_t.view(B, 128, fh, fw), fs, fs).view(B, 128, fs * fs)
         norm_s = ops.dba_colnorm(d_s, 0, emb_s)
         norm_t = ops.dba_colnorm(d_t, 0, emb_t)
-        fg, bg, sdiag = ops.dba_heads(d_s, 0, emb_s, norm_s, hw_s, hb_s, want_bg=True, want_sdiag=True)
+        fg, bg, sdiag = ops.dba_heads(d_s, 0, emb_s, norm_s, hw_s, hb_s, want_bg=True, want_sdiag=True, **det)
         teacher, _, _ = ops.dba_heads(d_t, 0, emb_t, norm_t, hw_t, hb_t, want_bg=False)
         extra, gram = ops.orth_gram(d_s, 0, emb_s, norm_s, sdiag)
         p_s, p_p = self._disc_probs(ops.binarize(fg, logits=True).view(B, 1, fs, fs), ops.binarize(pl, logits=False), feat_s.detach(), fs)
         epoch_frac = self._cur_epoch / (self._max_epoch + self._start_finetune)
-        w, merged, gfg, gbg, losses = ops.apm_bce(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world)
+        w, merged, gfg, gbg, losses = ops.apm_bce(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world, **det)
         g_emb, g_W, g_b, g_hw, g_hb = A.slices(A.g)
-        gd, _, _, _ = ops.dba_bwd(d_s, 0, emb_s, norm_s, hw_s, gram, gfg, gbg, 1.0 / world, g_head_w=g_hw, g_head_b=g_hb, g_dec_bias=g_b)
+        gd, _, _, _ = ops.dba_bwd(d_s, 0, emb_s, norm_s, hw_s, gram, gfg, gbg, 1.0 / world, g_head_w=g_hw, g_head_b=g_hb, g_dec_bias=g_b, **det)
         if native_grid:
             gd = ops.bilinear_resize_adjoint(gd.view(B, 128, fs, fs), fh, fw).view(B, 128, fh * fw)
-        ops.dba_wgrad(gd, feat_s, gW=g_W)
+        ops.dba_wgrad(gd, feat_s, gW=g_W, **det)
         # cotangent of the key hook: the 1x1 conv transposed (same exact-f32 MFMA kernel), then the backbone backward
         if getattr(self, "_zero_c", None) is None or self._zero_c.numel() != A.C:
             self._zero_c = torch.zeros(A.C, device=dev)
@@ -405,9 +413,10 @@ class TrainLoop(BaseLoop):
             p_p, _ = disc.forward_features(pseudo_mask, feats)
             return p_s, p_p
         disc_t = disc.tensor_table()
-        p_s, _ = ops.disc_fwd(student_mask, disc_t, update_running=True, saved=r.disc_saved(B, fs))
+        det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}
+        p_s, _ = ops.disc_fwd(student_mask, disc_t, update_running=True, saved=r.disc_saved(B, fs), **det)
         disc._bump_num_batches(disc_t)                        # (a no-op: the kernel call bumps the counters the table carries)
-        p_p, _ = ops.disc_fwd(pseudo_mask, disc_t, update_running=True, saved=r.disc_saved(B, fs))
+        p_p, _ = ops.disc_fwd(pseudo_mask, disc_t, update_running=True, saved=r.disc_saved(B, fs), **det)
         disc._bump_num_batches(disc_t)
         return p_s, p_p
 
@@ -418,7 +427,8 @@ class TrainLoop(BaseLoop):
         p_s, p_p = self._disc_probs(ops.binarize(p_students.contiguous(), logits=True), ops.binarize(pseudo_labels.contiguous(), logits=False), features, H)
         frac = self._cur_epoch / (self._max_epoch + self._start_finetune)
         zeros = torch.zeros(B, H * W, device=pseudo_labels.device)
-        _, merged, _, _, losses = ops.apm_bce(pseudo_labels.reshape(B, -1).contiguous(), p_teachers.reshape(B, -1).contiguous(), zeros, zeros, p_s, p_p, frac)
+        det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}
+        _, merged, _, _, losses = ops.apm_bce(pseudo_labels.reshape(B, -1).contiguous(), p_teachers.reshape(B, -1).contiguous(), zeros, zeros, p_s, p_p, frac, **det)
         return merged.view(B, 1, H, W), losses[2]
 
     def update_ema_decoder(self):
@@ -466,25 +476,26 @@ class TrainLoop(BaseLoop):
         pl = ops.binarize(ops.bilinear_resize(pseudo_labels.to(dev, torch.float32), fs, fs), logits=False)           # :241
         disc = r.discriminator
         world = r.world_size
+        det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}
         if disc.use_features:
             feats = features if tuple(features.shape[-2:]) == (fs, fs) else ops.bilinear_resize(features, fs, fs)           # :236
             probs_pseudo, saved_p = disc.forward_features(pl, feats, save=True)                                       # :244
             probs_student, saved_s = disc.forward_features(preds, feats, save=True)                                   # :245
         else:
             t = disc.tensor_table()
-            probs_pseudo, saved_p = ops.disc_fwd(pl, t, update_running=True)                                          # :244
+            probs_pseudo, saved_p = ops.disc_fwd(pl, t, update_running=True, **det)                                   # :244
             disc._bump_num_batches(t)
-            probs_student, saved_s = ops.disc_fwd(preds, t, update_running=True)                                      # :245
+            probs_student, saved_s = ops.disc_fwd(preds, t, update_running=True, **det)                               # :245
             disc._bump_num_batches(t)
         # BCELoss(cat(student, pseudo), [0..0, 1..1]) mean over 2B (:246-247) and its gradient, one launch (ucod_disc_bce: torch's clamp of the
         # logarithms at -100 and its max(p (1 - p), 1e-12) denominator); the gradient carries 1 / (2 B world) for the pre-scaled all-reduce
         g_student, g_pseudo, loss = ops.disc_bce(probs_student, probs_pseudo, 1.0 / (2 * B * world))
         if disc.use_features:
-            disc.backward_features(saved_p, g_pseudo, DA.grad_views, accumulate=False)
-            disc.backward_features(saved_s, g_student, DA.grad_views, accumulate=True)
+            disc.backward_features(saved_p, g_pseudo, DA.grad_views, accumulate=False, deterministic=self.deterministic)
+            disc.backward_features(saved_s, g_student, DA.grad_views, accumulate=True, deterministic=self.deterministic)
         else:
-            ops.disc_bwd(pl, t, saved_p, g_pseudo, grads=DA.grad_views, accumulate=False)
-            ops.disc_bwd(preds, t, saved_s, g_student, grads=DA.grad_views, accumulate=True)
+            ops.disc_bwd(pl, t, saved_p, g_pseudo, grads=DA.grad_views, accumulate=False, **det)
+            ops.disc_bwd(preds, t, saved_s, g_student, grads=DA.grad_views, accumulate=True, **det)
         parallel.allreduce_prescaled_(DA.g)
         r.dis_optimizer.step()
         r.dis_lr_scheduler.step()

@@ -54,6 +54,7 @@ class StandardRunner:
         self.train_dataloader = train_dataloader if train_dataloader is not None else []
         self.val_dataloader = val_dataloader if val_dataloader is not None else []
         self._saved = {}
+        self.det_ws = ops.DetWorkspaces()                      # workspaces of the deterministic step (TrainLoop.deterministic), one per entry point and shape
         self.lora_engine = self.lora_engine_ema = self._val_backbone = None      # backbone-backward mode (TrainLoop.attach_lora_backbone sets the engines)
         self._build_model()
         self._build_optimizer()

@@ -9,9 +9,20 @@ import numpy
 import torch
 
 _SEEDERS = (random.seed, numpy.random.seed, torch.manual_seed)
+# what a TrainLoop built after this call takes for ``deterministic`` when its config has no ``train_cfg.deterministic`` key (the counterpart of the reference's
+# ``cudnn.deterministic = True`` beside its seeds, engine/utils/misc.py:60): the fixed-order forms of the training step's reductions
+_DETERMINISTIC_DEFAULT = False
 
 
-def set_random_seed(seed: int = 42) -> int:
+def deterministic_default() -> bool:
+    return _DETERMINISTIC_DEFAULT
+
+
+def set_random_seed(seed: int = 42, deterministic=None) -> int:
+    """``deterministic``: True / False sets the default of ``TrainLoop.deterministic``; None (``set_random_seed(42)``) leaves it as it is."""
+    global _DETERMINISTIC_DEFAULT
+    if deterministic is not None:
+        _DETERMINISTIC_DEFAULT = bool(deterministic)
     seed = int(seed)
     for seeder in _SEEDERS:
         seeder(seed)

@@ -160,8 +160,9 @@ class Discriminator(nn.Module):
         recs.update(x=x, prob=out, lw=lw) if save else None
         return out, (recs if save else None)
 
-    def _conv_block_bwd(self, rec, gout, g_w, g_gamma, g_beta, accumulate, need_input_grad):
-        """gout [B,Cout,Ho*Wo] = dL/d(block output) -> gradients of the conv weight / BN affine (written or accumulated) and, when asked, dL/d(input)"""
+    def _conv_block_bwd(self, rec, gout, g_w, g_gamma, g_beta, accumulate, need_input_grad, deterministic=False):
+        """gout [B,Cout,Ho*Wo] = dL/d(block output) -> gradients of the conv weight / BN affine (written or accumulated) and, when asked, dL/d(input).
+        ``deterministic``: the weight gradient through ucod_conv_wgrad_f32_det (ordered sum of per-workgroup partials; workspace cached per shape on the module)."""
         lib = N.load()
         B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad = rec["geom"]
         gy = torch.empty_like(rec["y_pre"])
@@ -169,7 +170,15 @@ class Discriminator(nn.Module):
         N.check(lib.ucod_bn_lrelu_bwd(N.ptr(rec["y_pre"]), N.ptr(gout), N.ptr(gy), N.ptr(rec["stats"]), N.ptr(rec["g"]), N.ptr(rec["b"]), N.ptr(g_gamma),
                                       N.ptr(g_beta), B, Cout, Ho * Wo, BN_EPS, LRELU, int(accumulate), N.ptr(ws), ws.numel(), N.stream()), "ucod_bn_lrelu_bwd")
         gwm = torch.empty(Cout, Kpad, dtype=torch.float32, device=gy.device)
-        N.check(lib.ucod_conv_wgrad_f32(N.ptr(gy), N.ptr(rec["cols"]), N.ptr(gwm), B, Kpad, Ho * Wo, Cout, 0, N.stream()), "ucod_conv_wgrad_f32")
+        if deterministic:
+            if getattr(self, "_det_ws", None) is None:
+                self._det_ws = ops.DetWorkspaces()
+            nb = lib.ucod_conv_wgrad_f32_det_workspace_bytes(B, Kpad, Ho * Wo, Cout)
+            wws = self._det_ws.get("ucod_conv_wgrad_f32_det", nb, gy.device)
+            N.check(lib.ucod_conv_wgrad_f32_det(N.ptr(gy), N.ptr(rec["cols"]), N.ptr(gwm), B, Kpad, Ho * Wo, Cout, 0, N.ptr(wws), wws.numel(), N.stream()),
+                    "ucod_conv_wgrad_f32_det")
+        else:
+            N.check(lib.ucod_conv_wgrad_f32(N.ptr(gy), N.ptr(rec["cols"]), N.ptr(gwm), B, Kpad, Ho * Wo, Cout, 0, N.stream()), "ucod_conv_wgrad_f32")
         gw_new = gwm[:, :K].reshape(g_w.shape)
         if accumulate:
             g_w.add_(gw_new)                                      # (two discriminator calls per step: the second adds)
@@ -193,7 +202,7 @@ class Discriminator(nn.Module):
         N.check(lib.ucod_fold3x3(N.ptr(gcols), N.ptr(gx), B, Cin, H, W, stride, Kpad, N.stream()), "ucod_fold3x3")
         return gx
 
-    def backward_features(self, saved, gprob, grads, accumulate=False):
+    def backward_features(self, saved, gprob, grads, accumulate=False, deterministic=False):
         """gradient of sum_b gprob[b] * prob[b] with respect to the 14 parameter tensors, into ``grads`` (tensors shaped like ``_param_list()``,
         written, or added to when ``accumulate``) -- loop_UCOD_DPL.py:248 ``accelerator.backward(loss)`` for this module"""
         lib = N.load()
@@ -207,12 +216,12 @@ class Discriminator(nn.Module):
                                             N.ptr(glw), N.ptr(g_lb), B, K, int(accumulate), N.stream()), "ucod_linear_sigmoid_bwd")
         c1, c0 = saved["c1"], saved["c0"]
         g = gx.view(B, c1["geom"][4], -1)
-        g = self._conv_block_bwd(c1, g.contiguous(), *gm["c1"], accumulate, True)
-        g = self._conv_block_bwd(c0, g.reshape(B, c0["geom"][4], -1).contiguous(), *gm["c0"], accumulate, True)
+        g = self._conv_block_bwd(c1, g.contiguous(), *gm["c1"], accumulate, True, deterministic)
+        g = self._conv_block_bwd(c0, g.reshape(B, c0["geom"][4], -1).contiguous(), *gm["c0"], accumulate, True, deterministic)
         nm = saved["mask"]["geom"][4]                                  # channels of the mask branch in the concatenation
         hw = g.shape[2] * g.shape[3]
-        self._conv_block_bwd(saved["mask"], g[:, :nm].reshape(B, nm, hw).contiguous(), *gm["mask"], accumulate, False)
-        self._conv_block_bwd(saved["feat"], g[:, nm:].reshape(B, g.shape[1] - nm, hw).contiguous(), *gm["feat"], accumulate, False)
+        self._conv_block_bwd(saved["mask"], g[:, :nm].reshape(B, nm, hw).contiguous(), *gm["mask"], accumulate, False, deterministic)
+        self._conv_block_bwd(saved["feat"], g[:, nm:].reshape(B, g.shape[1] - nm, hw).contiguous(), *gm["feat"], accumulate, False, deterministic)
 
     def _forward_with_features(self, mask, feature):
         params = self._param_list()

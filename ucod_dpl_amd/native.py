@@ -259,6 +259,21 @@ SIGNATURES = {
     "ucod_linear_sigmoid_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_disc_bce": (ci, [vp, vp, vp, vp, vp, ci, cf, vp]),
     "ucod_apm_bce": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, ci, ci, vp]),
+    # the deterministic forms of the training step's reductions (no floating-point atomics; explicit workspace behind the default form's arguments)
+    "ucod_dba_wgrad_det_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "ucod_dba_wgrad_det": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "ucod_conv_wgrad_f32_det_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "ucod_conv_wgrad_f32_det": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
+    "ucod_dba_heads_fwd_det_workspace_bytes": (sz, [ci, ci]),
+    "ucod_dba_heads_fwd_det": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, vp]),
+    "ucod_dba_bwd_det_workspace_bytes": (sz, [ci, ci]),
+    "ucod_dba_bwd_det": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, sz, ci, ci, vp]),
+    "ucod_apm_bce_det_workspace_bytes": (sz, [ci]),
+    "ucod_apm_bce_det": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, sz, ci, ci, vp]),
+    "ucod_disc_fwd_det_workspace_bytes": (sz, [ci, ci]),
+    "ucod_disc_fwd_det": (ci, [vp, C.POINTER(DiscParams), vp, vp, ci, ci, ci, vp, sz, vp]),
+    "ucod_disc_bwd_det_workspace_bytes": (sz, [ci, ci]),
+    "ucod_disc_bwd_det": (ci, [vp, C.POINTER(DiscParams), vp, vp, C.POINTER(DiscGrads), ci, vp, sz, ci, ci, vp]),
     "ucod_binarize": (ci, [vp, vp, sz, ci, vp]),
     "ucod_ccl8_host": (ci, [vp, ci, ci, vp]),
     "ucod_pil_resize_u8_host": (ci, [vp, ci, ci, vp, ci, ci, ci]),

@@ -404,12 +404,51 @@ def dba_colnorm(d, c0, emb):
     return norm
 
 
-def dba_heads(d, c0, emb, norm, head_w, head_b, want_bg=True, want_sdiag=False, sdiag=None):
+class DetWorkspaces:
+    """Per-(entry point, size, device) cache of the workspaces of the deterministic forms (``deterministic=True`` below): a caller that runs the step
+    again and again owns one (StandardRunner.det_ws, as it owns disc_saved) instead of a fresh ``torch.empty`` per call.  A workspace is consumed inside the
+    call that fills it (stream order), so calls on one stream may share it."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, name, nbytes, device):
+        key = (name, int(nbytes), str(device))
+        if key not in self._bufs:
+            self._bufs[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        return self._bufs[key]
+
+    def nbytes(self):
+        return sum(t.numel() for t in self._bufs.values())
+
+
+def _det_ws(ws, name, nbytes, device):
+    """``ws`` of a deterministic call: None (a fresh buffer), a uint8 tensor of at least ``nbytes`` (the caller reads the partials back), or a DetWorkspaces."""
+    if nbytes == 0:
+        raise ValueError(f"{name}: unsupported shape")
+    if ws is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if isinstance(ws, DetWorkspaces):
+        return ws.get(name, nbytes, device)
+    if ws.dtype != torch.uint8:
+        raise TypeError(f"{name}: the workspace is a uint8 tensor, got {ws.dtype}")
+    return ws                                               # (its size is checked by the entry point)
+
+
+def dba_heads(d, c0, emb, norm, head_w, head_b, want_bg=True, want_sdiag=False, sdiag=None, deterministic=False, ws=None):
+    """``deterministic``: ucod_dba_heads_fwd_det (sdiag as an ordered sum of per-workgroup shares; fg / bg are the same bits either way)."""
     B, ld_c, HW = d.shape
     fg = torch.empty(B, HW, dtype=torch.float32, device=d.device)
     bg = torch.empty(B, HW, dtype=torch.float32, device=d.device) if want_bg else None
     if sdiag is None:
         sdiag = torch.empty(B, dtype=torch.float32, device=d.device) if want_sdiag else None
+    if deterministic:
+        lib = N.load()
+        nb = lib.ucod_dba_heads_fwd_det_workspace_bytes(B, HW)
+        ws = _det_ws(ws, "ucod_dba_heads_fwd_det", nb, d.device) if sdiag is not None else None
+        check(lib.ucod_dba_heads_fwd_det(ptr(d), ld_c, c0, ptr(emb), ptr(norm), ptr(_f32(head_w)), ptr(_f32(head_b)), ptr(fg), ptr(bg), ptr(sdiag),
+                                         ptr(ws), 0 if ws is None else ws.numel(), B, HW, stream()), "ucod_dba_heads_fwd_det")
+        return fg, bg, sdiag
     check(N.load().ucod_dba_heads_fwd(ptr(d), ld_c, c0, ptr(emb), ptr(norm), ptr(_f32(head_w)), ptr(_f32(head_b)), ptr(fg), ptr(bg),
                                       ptr(sdiag), B, HW, stream()), "ucod_dba_heads_fwd")
     return fg, bg, sdiag
@@ -426,29 +465,42 @@ def orth_gram(d, c0, emb, norm, sdiag):
     return loss, gram
 
 
-def dba_bwd(d, c0, emb, norm, head_w, gram, gfg, gbg, gextra, g_head_w=None, g_head_b=None, g_dec_bias=None):
+def dba_bwd(d, c0, emb, norm, head_w, gram, gfg, gbg, gextra, g_head_w=None, g_head_b=None, g_dec_bias=None, deterministic=False, ws=None):
+    """``deterministic``: ucod_dba_bwd_det (the three small gradients as ordered sums over the images; gd is the same bits either way)."""
     B, ld_c, HW = d.shape
     lib = N.load()
     dev = d.device
-    ws = torch.empty(lib.ucod_dba_bwd_workspace_bytes(B, HW), dtype=torch.uint8, device=dev)
     gd = torch.empty(B, 128, HW, dtype=torch.float32, device=dev)
     g_head_w = torch.empty(2, 64, dtype=torch.float32, device=dev) if g_head_w is None else g_head_w
     g_head_b = torch.empty(2, dtype=torch.float32, device=dev) if g_head_b is None else g_head_b
     g_dec_bias = torch.empty(128, dtype=torch.float32, device=dev) if g_dec_bias is None else g_dec_bias
+    if deterministic:
+        ws = _det_ws(ws, "ucod_dba_bwd_det", lib.ucod_dba_bwd_det_workspace_bytes(B, HW), dev)
+        check(lib.ucod_dba_bwd_det(ptr(d), ld_c, c0, ptr(emb), ptr(norm), ptr(head_w), ptr(gram), ptr(_f32(gfg)), ptr(_f32(gbg)), float(gextra),
+                                   ptr(gd), ptr(g_head_w), ptr(g_head_b), ptr(g_dec_bias), ptr(ws), ws.numel(), B, HW, stream()), "ucod_dba_bwd_det")
+        return gd, g_head_w, g_head_b, g_dec_bias
+    ws = torch.empty(lib.ucod_dba_bwd_workspace_bytes(B, HW), dtype=torch.uint8, device=dev)
     check(lib.ucod_dba_bwd(ptr(d), ld_c, c0, ptr(emb), ptr(norm), ptr(head_w), ptr(gram), ptr(_f32(gfg)), ptr(_f32(gbg)), float(gextra),
                            ptr(gd), ptr(g_head_w), ptr(g_head_b), ptr(g_dec_bias), ptr(ws), B, HW, stream()), "ucod_dba_bwd")
     return gd, g_head_w, g_head_b, g_dec_bias
 
 
-def dba_wgrad(gd, x, gW=None, exact=None):
+def dba_wgrad(gd, x, gW=None, exact=None, deterministic=False, ws=None):
     """gW [128,C] = sum_{b,p} gd[b,n,p] x[b,c,p].  Default on large batches: the three-way bf16 split on the bf16 matrix pipe
-    (csrc/gemm_split.hip, f32-equivalent); exact=True / UCOD_DBA_EXACT_F32=1 / small batches: the f32 MFMA kernel."""
+    (csrc/gemm_split.hip, f32-equivalent); exact=True / UCOD_DBA_EXACT_F32=1 / small batches: the f32 MFMA kernel.
+    ``deterministic``: ucod_dba_wgrad_det -- the same kernel choice, per-workgroup partials in ``ws`` and an ordered sum instead of f32 atomics."""
     B, Cc = x.shape[0], x.shape[1]
     HW = gd.shape[2]
     gW = torch.empty(128, Cc, dtype=torch.float32, device=x.device) if gW is None else gW
     if exact is None and _EXACT_F32:
         exact = True
-    if exact is False or (not exact and B * ((Cc + 383) // 384) >= 32):
+    split = exact is False or (not exact and B * ((Cc + 383) // 384) >= 32)
+    if deterministic:
+        lib = N.load()
+        ws = _det_ws(ws, "ucod_dba_wgrad_det", lib.ucod_dba_wgrad_det_workspace_bytes(B, Cc, HW, int(not split)), x.device)
+        check(lib.ucod_dba_wgrad_det(ptr(gd), ptr(_f32(x)), ptr(gW), B, Cc, HW, int(not split), ptr(ws), ws.numel(), stream()), "ucod_dba_wgrad_det")
+        return gW
+    if split:
         check(N.load().ucod_dba_wgrad_split(ptr(gd), ptr(_f32(x)), ptr(gW), B, Cc, HW, stream()), "ucod_dba_wgrad_split")
     else:
         check(N.load().ucod_dba_wgrad(ptr(gd), ptr(_f32(x)), ptr(gW), B, Cc, HW, stream()), "ucod_dba_wgrad")
@@ -474,13 +526,19 @@ def step_loss(losses, extra, finetune):
     return out[0]
 
 
-def disc_fwd(mask, tensors, update_running=True, saved=None):
+def disc_fwd(mask, tensors, update_running=True, saved=None, deterministic=False, ws=None):
+    """``deterministic``: ucod_disc_fwd_det (the BatchNorm sums as ordered f64 sums of per-workgroup partials)."""
     B, _, fs, _ = mask.shape
     lib = N.load()
     if saved is None:
         saved = torch.empty(lib.ucod_disc_saved_bytes(B, fs), dtype=torch.uint8, device=mask.device)
     prob = torch.empty(B, dtype=torch.float32, device=mask.device)
     ps = disc_params_struct(tensors)
+    if deterministic:
+        ws = _det_ws(ws, "ucod_disc_fwd_det", lib.ucod_disc_fwd_det_workspace_bytes(B, fs), mask.device)
+        check(lib.ucod_disc_fwd_det(ptr(_f32(mask)), C.byref(ps), ptr(prob), ptr(saved), B, fs, int(update_running), ptr(ws), ws.numel(), stream()),
+              "ucod_disc_fwd_det")
+        return prob, saved
     check(lib.ucod_disc_fwd(ptr(_f32(mask)), C.byref(ps), ptr(prob), ptr(saved), B, fs, int(update_running), stream()), "ucod_disc_fwd")
     return prob, saved
 
@@ -536,7 +594,8 @@ def binarize(x, logits):
     return out
 
 
-def apm_bce(pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0, losses=None):
+def apm_bce(pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0, losses=None, deterministic=False, ws=None):
+    """``deterministic``: ucod_apm_bce_det (the three loss cells as ordered sums over the images; w, merged, gfg, gbg are the same bits either way)."""
     B = pl.shape[0]
     HW = pl.numel() // B
     dev = pl.device
@@ -545,6 +604,12 @@ def apm_bce(pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0, losses=None):
     gfg = torch.empty(B, HW, dtype=torch.float32, device=dev)
     gbg = torch.empty(B, HW, dtype=torch.float32, device=dev)
     losses = torch.empty(4, dtype=torch.float32, device=dev) if losses is None else losses
+    if deterministic:
+        lib = N.load()
+        ws = _det_ws(ws, "ucod_apm_bce_det", lib.ucod_apm_bce_det_workspace_bytes(B), dev)
+        check(lib.ucod_apm_bce_det(ptr(pl), ptr(teacher), ptr(fg), ptr(bg), ptr(p_s), ptr(p_p), float(epoch_frac), float(gscale), ptr(w), ptr(merged),
+                                   ptr(gfg), ptr(gbg), ptr(losses), ptr(ws), ws.numel(), B, HW, stream()), "ucod_apm_bce_det")
+        return w, merged, gfg, gbg, losses
     check(N.load().ucod_apm_bce(ptr(pl), ptr(teacher), ptr(fg), ptr(bg), ptr(p_s), ptr(p_p), float(epoch_frac), float(gscale), ptr(w),
                                 ptr(merged), ptr(gfg), ptr(gbg), ptr(losses), B, HW, stream()), "ucod_apm_bce")
     return w, merged, gfg, gbg, losses
@@ -559,8 +624,9 @@ DISC_GRAD_SHAPES = (("w1", (32, 1, 3, 3)), ("g1", (32,)), ("b1", (32,)), ("w2", 
                     ("w3", (8, 16, 3, 3)), ("g3", (8,)), ("b3", (8,)), ("lin_w", None), ("lin_b", (1,)))
 
 
-def disc_bwd(mask, tensors, saved, gprob, grads=None, accumulate=False):
-    """Gradients of sum_b gprob[b]*prob[b] w.r.t. the 11 discriminator parameters (reference order)."""
+def disc_bwd(mask, tensors, saved, gprob, grads=None, accumulate=False, deterministic=False, ws=None):
+    """Gradients of sum_b gprob[b]*prob[b] w.r.t. the 11 discriminator parameters (reference order).
+    ``deterministic``: ucod_disc_bwd_det (the Linear layer's gradients as ordered sums over the images)."""
     B, _, fs, _ = mask.shape
     lib = N.load()
     dev = mask.device
@@ -570,8 +636,13 @@ def disc_bwd(mask, tensors, saved, gprob, grads=None, accumulate=False):
     gs = N.DiscGrads()
     for (name, _), t in zip(DISC_GRAD_SHAPES, grads):
         setattr(gs, name, ptr(_f32(t)))
-    ws = torch.empty(lib.ucod_disc_bwd_workspace_bytes(B, fs), dtype=torch.uint8, device=dev)
     ps = disc_params_struct(tensors)
+    if deterministic:
+        ws = _det_ws(ws, "ucod_disc_bwd_det", lib.ucod_disc_bwd_det_workspace_bytes(B, fs), dev)
+        check(lib.ucod_disc_bwd_det(ptr(_f32(mask)), C.byref(ps), ptr(saved), ptr(_f32(gprob)), C.byref(gs), int(accumulate), ptr(ws), ws.numel(), B, fs,
+                                    stream()), "ucod_disc_bwd_det")
+        return grads
+    ws = torch.empty(lib.ucod_disc_bwd_workspace_bytes(B, fs), dtype=torch.uint8, device=dev)
     check(lib.ucod_disc_bwd(ptr(_f32(mask)), C.byref(ps), ptr(saved), ptr(_f32(gprob)), C.byref(gs), int(accumulate), ptr(ws), B, fs,
                             stream()), "ucod_disc_bwd")
     return grads
