@@ -65,6 +65,8 @@ extern "C" {
 /* (still 5) The deterministic training step ("Deterministic forms" below): the _det forms of ucod_dba_wgrad, ucod_conv_wgrad_f32, ucod_dba_heads_fwd, ucod_dba_bwd,
  * ucod_apm_bce, ucod_disc_fwd and ucod_disc_bwd and their *_det_workspace_bytes helpers were added; additions only, the existing entry points are launch for launch
  * and bit for bit what they were. */
+/* (still 5) LoRA bias="lora_only": ucod_colsum_det (+ its size helper), ucod_vit_train_workspace_bytes_lora_bias and ucod_vit_backward_lora_bias (the _lora_out_ex
+ * forms plus a bias table) were added; additions only: every older backward / size entry point delegates with a NULL table and is launch for launch what it was. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -768,6 +770,47 @@ size_t ucod_vit_lora_infer_workspace_bytes_lora_out_ex(const ucod_vit_train_desc
 int ucod_vit_forward_lora_infer_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
                                             const void* const* mlp_table_host, const void* const* out_table_host, const float* img, float* key_out, void* workspace,
                                             size_t workspace_bytes, void* stream);
+
+/* LoRA bias="lora_only" (models/modules/full_model.py:53,66: `bias` of lora_cfg is handed to peft's LoraConfig; "lora_only" sets requires_grad on the bias of every
+ * module that carries an adapter and has a bias, and changes nothing else: forward = base(x) + scaling * B(A(drop(x))) with the base layer's own bias, which
+ * dropout does not touch).  For y = x W^T + b the bias gradient is the column sum over token rows of y's cotangent.
+ *
+ * ucod_colsum_det (full_model.py:53,66; csrc/colsum.hip): out[n] = col_scale[n] * sum_{m < M} x[m][n] for n < N, accumulated in f32; col_scale NULL = ones.  x is
+ * [M, ld] row-major, elem = UCOD_ROPE_ELEM_HALF (the library's 16-bit operand type) or UCOD_ROPE_ELEM_F32; ld >= N in elements and ld * sizeof(element) a multiple
+ * of 16 (the rule of ucod_rope_qk_ld); x 16-byte aligned; columns N .. ld - 1 are never read.  `out` [N] is overwritten.  Deterministic, no floating-point
+ * atomics: slabs = min(128, ceil(M / 64)) -- a function of M alone -- row slabs of ceil(M / slabs) rows; inside a slab a thread adds rows rt, rt + 16, ... of its
+ * 16-byte column vector in ascending order, the sixteen row threads of a column are added in ascending rt, the workgroup stores workspace[slab][n] (f32
+ * [slabs][N]), and a second launch adds the slabs in ascending order, multiplies by col_scale and stores.  Two runs are bit-identical.
+ * ucod_colsum_det_workspace_bytes (full_model.py:53,66): slabs * N * 4, or 0 for M < 1 or N % 8 != 0 (N < 8 included).
+ * UCOD_EINVAL before any launch, nothing written: a null x / out / workspace, an unknown elem, M < 1, N % 8 != 0, ld < N, a misaligned ld or x, a workspace that is
+ * too small.  Both builds. */
+size_t ucod_colsum_det_workspace_bytes(int M, int N);
+int ucod_colsum_det(const void* x, int elem, int M, int N, int ld, const float* col_scale, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The backward with trained biases (full_model.py:53,66): ucod_vit_backward_lora_out_ex plus TB = bias_table_host, HOST array of DEVICE pointers, layer l at
+ * UCOD_VIT_TRAIN_BIAS_STRIDE*l:
+ *     +0 gb_q f32 [D]   +1 gb_k [D]   +2 gb_v [D]   +3 gb_m [N1] (fc1 / weights_in; SwiGLU: the engine's padded, interleaved order)   +4 gb_o [D] (dense / o_proj)
+ *     +5 gb_2 [D] (fc2 / weights_out / down_proj);  NULL = that bias is not trained (a module without a bias in the checkpoint, or one that is not targeted)
+ * Every non-NULL slot is overwritten with one ucod_colsum_det per layer below the last:
+ *   gb_q / gb_k / gb_v  the thirds of dqkv_aug [M, 3D+64] (columns 0 / D / 2D, ld = 3D+64) behind ucod_attention_bwd and the DINOv3 un-rotation, in front of
+ *                       ucod_lora_grad: the cotangents of the projection outputs (the softmax pre-scale is applied behind the bias, and attention backward
+ *                       returns dq of the unscaled q); when all three slots are set and lie side by side (gb_k = gb_q + D, gb_v = gb_q + 2 D, as one arena row
+ *                       holds them) they are written by ONE call over the 3 D columns
+ *   gb_m                the completed dpre [M, N1], behind ucod_lora_out_grad_x_ex, in front of ucod_layernorm_lora_mlp / the fc1 dgrad
+ *   gb_o, gb_2          the residual GEMMs compute x += lambda * (acc + b), so db = lambda * sum_rows dx: the column sums of s = bf16(lambda * dx), the operand of
+ *                       the out-proj / fc2 dgrad GEMM, with no col_scale -- gb_2 at the top of the layer (before h2_aug reuses s's buffer), gb_o behind the
+ *                       LayerNorm-2 backward that writes s
+ * In the last layer only the key projection reaches the key map: gb_k there is the column sum of what ucod_key_grad_tokens_reg scattered (CLS and register rows
+ * are zeros), the other five slots are written as zeros.  The partials of ucod_colsum_det (sized for its widest calls, N = 3 D and N = N1) are one more entry at the end of the
+ * workspace, counted only with a non-NULL table: ucod_vit_train_workspace_bytes_lora_bias (full_model.py:53,66) with NULL returns the bytes of ucod_vit_train_workspace_bytes_lora_out_ex, and
+ * ucod_vit_backward_lora_bias with NULL enqueues its launches; every older backward / size entry point delegates here with NULL.  ucod_vit_forward_train_lora_out_ex
+ * must have been given a workspace of at least the _lora_bias size (it uses the leading bytes).  The forward passes need no new entry point: they read biases
+ * from table_host. */
+#define UCOD_VIT_TRAIN_BIAS_STRIDE 6
+size_t ucod_vit_train_workspace_bytes_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,
+                                                const void* const* out_table_host, const void* const* bias_table_host);
+int ucod_vit_backward_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
+                                const void* const* mlp_table_host, const void* const* out_table_host, const void* const* bias_table_host, const float* dkey,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* The way out of LoRA mode: merging the trained matrices into ordinary weights (csrc/lora_merge.hip), so that every frozen-backbone engine runs the adapted model.
  * peft's merge of a LoRA module (what merge_and_unload() does to each module models/modules/full_model.py:47-72 wraps):  W <- W + (lora_alpha / r) B A.

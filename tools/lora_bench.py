@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """Backbone-backward (LoRA) mode at the headline size: forward_train + backward of DINOv2 ViT-B/14 @518 (or, sixth argument dinov2_vitg14, of ViT-g/14 with its
 SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both passes, @512), per-class kernel times.
-    lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side]]]]]]]]
+    lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side] [bias]]]]]]]]
 ``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
-on ViT-g; naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16)."""
+on ViT-g; naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
+``bias``: a trailing none / lora_only (peft's LoraConfig.bias; with or without ``side`` in front of it): lora_only also trains the targeted modules' biases -- one
+deterministic column sum per bias and layer in the backward (tools/lora_bias_bench.py times the two modes against each other in one process)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ucod_dpl_amd import native as N
-from ucod_dpl_amd.vit_engine import ViTLoRAEngine
+from ucod_dpl_amd.vit_engine import LORA_BIAS_MODES, ViTLoRAEngine
 from ucod_dpl_amd.data.utils.feature_extractor import random_state_dict, ARCHS, DINOV3_ARCHS, SWIGLU_ARCHS
 
+bias = sys.argv.pop() if sys.argv[-1] in LORA_BIAS_MODES else "none"
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 streams = int(sys.argv[3]) if len(sys.argv) > 3 else 2
@@ -29,6 +32,7 @@ if side % patch:
     sys.exit(f"the image side must be a multiple of the patch size {patch}, got {side}")
 grid, n_lead = side // patch, 1 + (DINOV3_ARCHS[arch] if v3 else 4 if arch.endswith("_reg") else 0)
 kw = {} if targets is None else dict(target_modules=targets)
+kw.update(bias=bias)
 if v3:
     kw.update(allow_rope=True, eps=1e-5)
 leaves = [t.rsplit(".", 1)[-1] for t in targets or ()]
@@ -38,7 +42,7 @@ if "weights_out" in leaves or ("down_proj" in leaves and arch in SWIGLU_ARCHS):
     kw.update(allow_swiglu_out=True)                      # ... and the SwiGLU MLP's has an opt-in of its own (the hidden is recomputed in the backward)
 eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
-    print(f"targets {targets}: arena [{eng.L}, {eng.lora.shape[1]}]")
+    print(f"targets {targets}, bias {bias}: arena [{eng.L}, {eng.lora.shape[1]}]")
 eng.train_streams = streams
 x = torch.randn(B, 3, side, side, device="cuda")
 dkey = torch.randn(B, 64 * heads, grid, grid, device="cuda")

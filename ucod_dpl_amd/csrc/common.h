@@ -210,7 +210,7 @@ enum ProfClass {
   PROF_IM2COL, PROF_CLS, PROF_BILINEAR, PROF_DBA_PROJECT, PROF_DBA_COLNORM, PROF_DBA_HEADS, PROF_ORTH, PROF_DBA_BWD,
   PROF_DBA_WGRAD, PROF_DISC_FWD, PROF_DISC_BWD, PROF_APM, PROF_BINARIZE, PROF_ADAMW, PROF_CROP, PROF_CAST, PROF_LN_BWD, PROF_LORA,
   PROF_ATTN_BWD, PROF_GEMM_EPI6, PROF_GEMM_EPI7, PROF_ROW_STATS, PROF_SPLIT, PROF_LN_SPLIT, PROF_ATTN_SPLIT, PROF_GEMM_EPI21, PROF_GEMM_EPI22,
-  PROF_LN_LORA_MLP, PROF_LORA_MLP_GRAD, PROF_LN_BWD_LORA_MLP, PROF_LORA_OUT_FWD, PROF_LORA_OUT_GRAD_S, PROF_LORA_OUT_GRAD_X, PROF_LORA_OUT_GRAD_X_SWIGLU, PROF_NUM
+  PROF_LN_LORA_MLP, PROF_LORA_MLP_GRAD, PROF_LN_BWD_LORA_MLP, PROF_LORA_OUT_FWD, PROF_LORA_OUT_GRAD_S, PROF_LORA_OUT_GRAD_X, PROF_LORA_OUT_GRAD_X_SWIGLU, PROF_COLSUM, PROF_NUM
 };
 struct ProfScope {
   int idx;

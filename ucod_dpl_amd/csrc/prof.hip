@@ -14,7 +14,7 @@ static const char* kNames[PROF_NUM] = {
     "adamw_ema", "crop_resize_norm", "cast", "layernorm_bwd", "lora_rowwise", "attention_bwd", "gemm_bf16_gelu_bwd",
     "gemm_bf16_fc1_gelu_save", "row_stats", "split_operands", "layernorm_split", "attention_split_fwd", "gemm_bf16_fc1_swiglu_save",
     "gemm_bf16_swiglu_bwd", "layernorm_lora_mlp", "lora_mlp_grad", "layernorm_bwd_lora_mlp", "lora_out_fwd", "lora_out_grad_s", "lora_out_grad_x",
-    "lora_out_grad_x_swiglu"};
+    "lora_out_grad_x_swiglu", "colsum_det"};
 
 struct Rec { int cls; hipEvent_t a, b; };
 static std::mutex g_mu;

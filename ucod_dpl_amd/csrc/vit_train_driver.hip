@@ -16,10 +16,15 @@
 //           behind its residual GEMM (ucod_lora_out_fwd: x += lambda * scaling * (drop(x_in) A^T) B^T) and two in the backward (ucod_lora_out_grad_s on the dgrad GEMM's
 //           operand s, ucod_lora_out_grad_x_ex on x_in and its cotangent).  On the SwiGLU MLP the fc2 slots need UCOD_LORA_OUT_SWIGLU in the flags: the backward then
 //           recomputes the hidden from the saved interleaved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU on pre / dpre [M, 2F])
+// and, for the backward alone, a fifth --
+//   TB      bias="lora_only" (full_model.py:53,66): gradient destinations of the targeted modules' biases, six slots per layer (gb_q, gb_k, gb_v [D], gb_m [N1],
+//           gb_o, gb_2 [D]; NULL = not trained).  For y = x W^T + b the gradient is the column sum over token rows of y's cotangent, and every such cotangent is a
+//           live buffer here: the thirds of dqkv (behind the DINOv3 un-rotation), the completed dpre, and s = bf16(lambda * dx) of the two residual dgrads (the
+//           residual GEMMs compute x += lambda * (acc + b), so db = lambda * sum dx).  One ucod_colsum_det each; the forwards read biases from the plain rows.
 // The last layer runs LayerNorm 1 and the key projection only: the gradients of its MLP and output modules are written as zeros.
 // Dropout: every module has its own mask, keyed kind * L + l (`dropout_of`: q / k / v, the MLP input, dense, fc2 = kinds 0 .. 3).
-// Every exported symbol -- five functions in five suffix tiers, the older tiers being the _lora_out_ex forms with NULL tables / flags 0 -- fills in a Pass and calls one
-// of the five functions below.  No allocation, no sync.
+// Every exported symbol -- five functions in five suffix tiers, the older tiers being the _lora_out_ex forms with NULL tables / flags 0, and the _lora_bias tier of
+// the backward and its size function -- fills in a Pass and calls one of the five functions below.  No allocation, no sync.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
 
@@ -33,6 +38,7 @@ struct Pass {
   const void* const* TT;
   const void* const* TM;
   const void* const* TO;
+  const void* const* TB;                                   // backward only (every other pass leaves it NULL)
 };
 
 struct Plan {
@@ -44,6 +50,7 @@ struct Plan {
   size_t dx, dh, s, da, dqkv, delta, lgw;                  // backward scratch (dpre aliases g, s aliases h2)
   size_t tm, mgw, mgw_bytes;                               // MLP LoRA module: t scratch [M, 64], partials of ucod_lora_mlp_grad
   size_t u_o, u_2, s_u, t_out, ogw, ogw_bytes;             // output modules: saved u [M, 8] per layer (dense, fc2), t scratch [M, 8], partials of ucod_lora_out_grad_*
+  size_t bgw, bgw_bytes;                                   // bias gradients (TB): partials of ucod_colsum_det
   size_t total;
 };
 
@@ -135,6 +142,12 @@ Plan train_plan(const Pass& c) {
     p.t_out = take(M * UCOD_LORA_OUT_W * 4);
     p.ogw_bytes = out_gw_bytes(t, m);
     p.ogw = take(p.ogw_bytes);
+  }
+  p.bgw = p.bgw_bytes = 0;
+  if (c.TB) {                                                   // (behind everything else, like TO: without a table no offset and no byte differs)
+    const size_t a = ucod_colsum_det_workspace_bytes(p.M, 3 * d->D), b = ucod_colsum_det_workspace_bytes(p.M, (int)FP);   // (the widest calls: q | k | v at once, dpre)
+    p.bgw_bytes = a > b ? a : b;
+    p.bgw = take(p.bgw_bytes);
   }
   p.total = o;
   return p;
@@ -324,8 +337,33 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   auto ln_bwd_plain = [&](const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale) -> int {
     return ucod_layernorm_bwd_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s, M, D, d->eps, stream);
   };
+  // a bias gradient: the column sums of a 16-bit cotangent buffer (TB; `dst` NULL = that bias is not trained)
+  const void* const* TB = c.TB;
+  auto bias_grad = [&](const void* dst, const void* cot, int n, int ld) -> int {
+    if (!dst) return UCOD_OK;
+    return ucod_colsum_det(cot, UCOD_ROPE_ELEM_HALF, M, n, ld, nullptr, (float*)const_cast<void*>(dst), ws + p.bgw, p.bgw_bytes, stream);
+  };
+  auto bias_zero = [&](const void* dst, int n) -> int {
+    if (dst && hipMemsetAsync(const_cast<void*>(dst), 0, (size_t)n * sizeof(float), (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
+    return UCOD_OK;
+  };
   auto qkv_side = [&](int l) -> int {   // dqkv_aug (k/q/v thirds filled) -> LoRA grads of layer l, dh = d LN1 output
     const void* const* X = TT + UCOD_VIT_TRAIN_STRIDE * l;
+    if (TB) {   // q / k / v biases: the thirds of dqkv, cotangents of the projection outputs (the last layer: only the key third reaches the key map)
+      const void* const* G = TB + UCOD_VIT_TRAIN_BIAS_STRIDE * l;
+      const bool is_last = l == d->L - 1;
+      // (all three trained and side by side, as one arena row holds them: one pass over the 3 D columns instead of three over D)
+      const bool together = !is_last && G[0] && G[1] == (const float*)G[0] + D && G[2] == (const float*)G[0] + 2 * D;
+      if (together) {
+        RUN(bias_grad(G[0], dqkv, 3 * D, KQ));
+      } else {
+        if (is_last) RUN(bias_zero(G[0], D));
+        else RUN(bias_grad(G[0], dqkv, D, KQ));
+        RUN(bias_grad(G[1], (const char*)dqkv + (size_t)D * 2, D, KQ));
+        if (is_last) RUN(bias_zero(G[2], D));
+        else RUN(bias_grad(G[2], (const char*)dqkv + (size_t)2 * D * 2, D, KQ));
+      }
+    }
     RUN(ucod_lora_grad(dqkv, at.h_aug(l), (const float*)X[5], r, t->lora_scaling, (float*)X[6], 0, lgw, lgw_bytes, M, D, dropout_of(t, MOD_QKV, l).ptr(), stream));
     RUN(ucod_gemm_bf16(epi_dh, dqkv, X[1], dh, M, D, KQ, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     return UCOD_OK;
@@ -352,6 +390,12 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
     if (om.o && hipMemsetAsync(const_cast<void*>(Z[1]), 0, (size_t)r * (size_t)(D + D) * sizeof(float), (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
     if (om.f && hipMemsetAsync(const_cast<void*>(Z[3]), 0, (size_t)r * (size_t)(F + D) * sizeof(float), (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
   }
+  if (TB) {   // (nor do the biases of its MLP and output projections)
+    const void* const* G = TB + UCOD_VIT_TRAIN_BIAS_STRIDE * last;
+    RUN(bias_zero(G[3], N1));
+    RUN(bias_zero(G[4], D));
+    RUN(bias_zero(G[5], D));
+  }
   RUN(ucod_key_grad_tokens_reg(dkey, dqkv, d->B, tok, D, d->n_reg, stream));
   RUN(qkv_side(last));
   if (last == 0) return UCOD_OK;
@@ -368,6 +412,9 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
     const void* qkv = at.qkv(l);
     const void* att = at.att(l);
     const void* pre = at.pre(l);
+    const void* const* G = TB ? TB + UCOD_VIT_TRAIN_BIAS_STRIDE * l : nullptr;
+    // fc2 / weights_out bias: x_next = x_mid + ls2 * (g W2^T + b2), so db2 = ls2 * sum dx = the column sums of s = bf16(ls2 * dx), before anything reuses its buffer
+    if (G) RUN(bias_grad(G[5], s, D, D));
     // MLP branch: s = ls2 * dx  ->  fc2 dgrad (x gelu')  ->  fc1 dgrad  ->  LN2 backward + residual
     // (SwiGLU: the weights_out dgrad's drain writes the cotangent of the interleaved weights_in output, dpre [M, 2F]; X[3] = weights_in^T [D, 2F] in that column order)
     RUN(ucod_gemm_bf16_train(swiglu ? UCOD_EPI_SWIGLU_BWD_BF16 : UCOD_EPI_GELU_BWD_BF16, s, X[4], dpre, M, F, D, nullptr, pre, nullptr, gv, stream));
@@ -381,6 +428,8 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
       RUN(ucod_lora_out_grad_x_ex(pre, swiglu ? UCOD_LORA_OUT_ACT_SWIGLU : UCOD_LORA_OUT_ACT_GELU, swiglu ? UCOD_LORA_OUT_SWIGLU : 0, dpre,
                                   (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D, dropout_of(t, MOD_FC2, l).ptr(), stream));
     }
+    // fc1 / weights_in bias: the column sums of the completed dpre (SwiGLU: the engine's padded, interleaved column order; padded columns hold exact zeros)
+    if (G) RUN(bias_grad(G[3], dpre, N1, N1));
     const Dropout drop_m = dropout_of(t, MOD_MLP_IN, l);
     const void* const* Y = TM ? TM + UCOD_VIT_TRAIN_MLP_STRIDE * l : nullptr;
     if (TM) {
@@ -396,6 +445,8 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
                                             (const float*)Y[1], r, drop_m.ptr(), stream));
     else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
+    // (dense / o_proj bias: db_o = ls1 * sum dx = the column sums of s, which stays as it is until the LayerNorm-1 backward rewrites it)
+    if (G) RUN(bias_grad(G[4], s, D, D));
     RUN(ucod_gemm_bf16(UCOD_EPI_BIAS_BF16, s, X[2], da, M, D, D, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     if (om.o) {   // LoRA on the attention output projection: s = bf16(ls1 * dx); da += mask/(1-p) * (t A_o) before attention backward reads it
       float* gz = (float*)const_cast<void*>(Z[1]);
@@ -473,6 +524,16 @@ extern "C" int ucod_vit_backward_lora_out(const ucod_vit_train_desc* t, int mlp,
 extern "C" int ucod_vit_backward_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT, const void* const* TM,
                                              const void* const* TO, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
   return backward(Pass{t, mlp, out_flags, T, TT, TM, TO}, dkey, workspace, workspace_bytes, stream);
+}
+
+// bias="lora_only": the backward and its workspace with the bias table (NULL = the _lora_out_ex forms, which delegate with NULL)
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO,
+                                                           const void* const* TB) {
+  return train_bytes(Pass{t, mlp, out_flags, nullptr, nullptr, TM, TO, TB});
+}
+extern "C" int ucod_vit_backward_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT, const void* const* TM,
+                                           const void* const* TO, const void* const* TB, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
+  return backward(Pass{t, mlp, out_flags, T, TT, TM, TO, TB}, dkey, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return infer_bytes(Pass{t, UCOD_MLP_GELU, 0, nullptr, nullptr, nullptr, nullptr}); }

@@ -4,7 +4,7 @@ imported: it needs ``peft`` and a module, ``models/modules/ocm.py``, that is not
 Same names and call shapes: ``load_lora(cfg, model)``, ``get_full_model(cfg, checkpoint_path)``,
 ``full_model(config, backbone, decoder)(inputs, ema=False, get_hidden_feature=False)``, ``freeze_lora`` / ``active_lora``,
 ``load_state_dict`` (decoder only, :146-147).  What runs underneath is the HIP training engine (``ViTLoRAEngine``):
-LoRA r / lora_alpha / target modules as :47-72 (subsets of query, key, value, plus the MLP input projection; bias 'none'), the key hook of the last layer -> CLS
+LoRA r / lora_alpha / target modules as :47-72 (subsets of query, key, value, plus the MLP input projection; bias 'none' or 'lora_only'), the key hook of the last layer -> CLS
 dropped -> NCHW -> bilinear 68x68 (:95-106), student backbone differentiable w.r.t. its LoRA matrices, EMA backbone
 frozen.  ``enable_ocm`` is rejected: its module does not exist in the reference.  LoRA dropout (``lora_dropout``, 0.05 in the
 reference config) is applied in train mode with counter-based masks (it cannot reproduce torch's RNG stream).
@@ -19,13 +19,13 @@ import torch
 from torch import nn
 
 from ... import ops
-from ...vit_engine import ViTLoRAEngine, is_dinov3
+from ...vit_engine import ViTLoRAEngine, check_lora_bias, is_dinov3
 from ..uscod import baseline
 
 
 class LoRABackbone(nn.Module):
     """nn.Module face of a ViTLoRAEngine: ONE flat parameter ``lora`` [L, P] that aliases the engine's arena (P = 6*r*D; with the MLP input projection
-    targeted, r*(D + N1) more)."""
+    targeted, r*(D + N1) more; with bias="lora_only" the trained biases at the end of each row)."""
 
     def __init__(self, engine: ViTLoRAEngine):
         super().__init__()
@@ -76,29 +76,33 @@ def _adapter_targets(engine):
 def save_lora_adapter(engine, folder):
     """Write the LoRA matrices of ``engine`` as a peft adapter folder: ``adapter_model.safetensors`` with the keys
     ``base_model.model.ViT.encoder.layer.{i}.attention.attention.query.lora_A.weight`` ... (shapes: ``lora_state_dict()``'s; B of ``weights_in`` in HF row order,
-    unpadded) and ``adapter_config.json`` with r, lora_alpha, lora_dropout, bias "none" and target_modules (models/modules/full_model.py:47-72).
-    peft is not a dependency of this package: the layout is restated from peft's documented adapter format and has not been checked against the library."""
+    unpadded) and ``adapter_config.json`` with r, lora_alpha, lora_dropout, bias and target_modules (models/modules/full_model.py:47-72).  ``bias`` is the
+    engine's: "none", or "lora_only" -- then the trained biases are stored beside the matrices under the module's own key, ``...query.bias`` (what peft's
+    get_peft_model_state_dict derives from a ``lora_`` key: everything in front of ``lora_`` plus ``bias``).
+    peft is not a dependency of this package: the layout is restated from peft's documented adapter format and has not been checked against the library -- the
+    bias key in particular (recent peft versions hold the wrapped Linear as ``base_layer``, and which of the two names their loader expects is unverified)."""
     from safetensors.torch import save_file
     os.makedirs(folder, exist_ok=True)
     sd = engine.lora_state_dict(prefix=_adapter_prefix(engine))
     save_file({k: v.detach().cpu().contiguous() for k, v in sd.items()}, os.path.join(folder, ADAPTER_WEIGHTS))
     alpha = float(engine.scaling) * int(engine.r)
     cfg = {"peft_type": "LORA", "r": int(engine.r), "lora_alpha": int(alpha) if alpha == int(alpha) else alpha,
-           "lora_dropout": float(getattr(engine, "lora_dropout", 0.0)), "bias": "none", "target_modules": _adapter_targets(engine)}
+           "lora_dropout": float(getattr(engine, "lora_dropout", 0.0)), "bias": str(getattr(engine, "bias", "none")), "target_modules": _adapter_targets(engine)}
     with open(os.path.join(folder, ADAPTER_CONFIG), "w") as f:
         json.dump(cfg, f, indent=2, sort_keys=True)
     return folder
 
 
 def load_lora_adapter(engine, folder):
-    """The inverse of ``save_lora_adapter``: read the folder into ``engine``'s arena.  An adapter whose r, lora_alpha or target_modules differ from the engine's is
-    refused (both sides are named): its matrices would not fit, or would be applied with another scale."""
+    """The inverse of ``save_lora_adapter``: read the folder into ``engine``'s arena.  An adapter whose r, lora_alpha, target_modules or bias mode differ from the
+    engine's is refused (both sides are named): its matrices would not fit, or would be applied with another scale, or its trained biases would be dropped."""
     from safetensors.torch import load_file
     with open(os.path.join(folder, ADAPTER_CONFIG)) as f:
         cfg = json.load(f)
-    mine = {"r": int(engine.r), "lora_alpha": float(engine.scaling) * int(engine.r), "target_modules": sorted(_adapter_targets(engine))}
-    theirs = {"r": int(cfg["r"]), "lora_alpha": float(cfg["lora_alpha"]), "target_modules": sorted(cfg["target_modules"])}
-    for k in ("r", "target_modules", "lora_alpha"):
+    mine = {"r": int(engine.r), "lora_alpha": float(engine.scaling) * int(engine.r), "target_modules": sorted(_adapter_targets(engine)),
+            "bias": str(getattr(engine, "bias", "none"))}
+    theirs = {"r": int(cfg["r"]), "lora_alpha": float(cfg["lora_alpha"]), "target_modules": sorted(cfg["target_modules"]), "bias": str(cfg.get("bias", "none"))}
+    for k in ("r", "target_modules", "lora_alpha", "bias"):
         if mine[k] != theirs[k]:
             raise ValueError(f"LoRA adapter {folder}: {k} is {theirs[k]!r} in {ADAPTER_CONFIG}, {mine[k]!r} in the engine")
     engine.load_lora_state_dict(load_file(os.path.join(folder, ADAPTER_WEIGHTS)), prefix=_adapter_prefix(engine))
@@ -114,7 +118,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     only the SwiGLU MLP's output projection stays refused.  The build-only key ``allow_swiglu_out`` (default False; needs ``allow_out``, and ``allow_rope`` on a
     DINOv3 checkpoint) lifts that too: ``weights_out`` on DINOv2 ViT-g/14, ``down_proj`` on a gated DINOv3 checkpoint whose hidden width is at most 4096.
     A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
-    100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
+    100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
+    trained too: ``ViTLoRAEngine``); "all" is refused with its reason and any other value is a ValueError, both before any device work.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
     r = getattr(config, "r", 2)
     if r == 0:
@@ -123,15 +128,14 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     targets = getattr(config, "target_modules", None)                        # None: query / key / value, the reference's default
     if targets is not None and not isinstance(targets, str):
         targets = list(targets)
-    if getattr(config, "bias", "none") != "none":
-        raise NotImplementedError("LoRA bias modes other than 'none' are not built")
+    bias = check_lora_bias(getattr(config, "bias", "none"))                  # :53,66
     drop = float(getattr(config, "lora_dropout", 0.05))                      # :50
     if eps is None:
         eps = 1e-5 if is_dinov3(state_dict) else 1e-6
     return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, eps=eps, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
                                       rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False)),
-                                      allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False))))
+                                      allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False)), bias=bias))
 
 
 class full_model(nn.Module):

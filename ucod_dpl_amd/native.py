@@ -58,6 +58,9 @@ LORA_OUT_W = 8                                              # include/ucod_dpl.h
 LORA_OUT_ACT_IDENTITY, LORA_OUT_ACT_GELU = 0, 1
 LORA_OUT_ACT_SWIGLU = 2                                     # include/ucod_dpl.h: UCOD_LORA_OUT_ACT_SWIGLU (x_in / cot are the interleaved [rows, 2K] pre-activation / dpre)
 LORA_OUT_SWIGLU = 1                                         # include/ucod_dpl.h: UCOD_LORA_OUT_SWIGLU (out_flags of the _lora_out_ex entry points)
+# the per-layer table of the trained biases' gradient destinations (bias="lora_only": the _lora_bias entry points); NULL = that bias is not trained
+VIT_TRAIN_BIAS_STRIDE = 6
+VIT_TRAIN_BIAS_SLOTS = ("gb_q", "gb_k", "gb_v", "gb_m", "gb_o", "gb_2")
 
 vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -215,6 +218,12 @@ SIGNATURES = {
     "ucod_vit_backward_lora_out_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     "ucod_vit_lora_infer_workspace_bytes_lora_out_ex": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp)]),
     "ucod_vit_forward_lora_infer_lora_out_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
+    # LoRA bias="lora_only": deterministic column sums (elem = ROPE_ELEM_HALF / ROPE_ELEM_F32), and the backward / its size function with the bias table behind the
+    # output modules' one (NULL = the _lora_out_ex forms)
+    "ucod_colsum_det_workspace_bytes": (sz, [ci, ci]),
+    "ucod_colsum_det": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
+    "ucod_vit_train_workspace_bytes_lora_bias": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_backward_lora_bias": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
     # merging trained LoRA matrices into ordinary weights, and the device form of the LayerNorm fold (fp16-operand build) for the merged weight
     "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
     "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),

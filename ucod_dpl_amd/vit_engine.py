@@ -951,6 +951,23 @@ def _dinov3_paths(sd):
     return pref, ("model.layer." if any(k.startswith(pref + "model.layer.") for k in sd) else "layer.")
 
 
+LORA_BIAS_MODES = ("none", "lora_only", "all")               # peft's LoraConfig.bias (models/modules/full_model.py:53,66)
+# the six Linear modules of a layer whose bias "lora_only" can train, in arena / bias-table order (native.VIT_TRAIN_BIAS_SLOTS)
+_BIAS_Q, _BIAS_K, _BIAS_V, _BIAS_M, _BIAS_O, _BIAS_2 = range(N.VIT_TRAIN_BIAS_STRIDE)
+
+
+def check_lora_bias(bias):
+    """peft's ``LoraConfig.bias`` as this package builds it: "none" and "lora_only" pass; "all" is refused with its reason; anything else is a ValueError.  Host
+    only: ``load_lora`` and ``ViTLoRAEngine`` call it before any device work."""
+    if bias not in LORA_BIAS_MODES:
+        raise ValueError(f"LoRA bias must be one of {LORA_BIAS_MODES} (peft's LoraConfig.bias), got {bias!r}")
+    if bias == "all":
+        raise NotImplementedError("LoRA bias='all' is not built: it also trains the LayerNorm and patch-embedding biases, and the LayerNorm backward of the "
+                                  "backbone-backward passes produces no gradient of beta (it returns the input's cotangent only); bias='lora_only' -- the biases "
+                                  "of the modules that carry an adapter -- is built")
+    return bias
+
+
 class ViTLoRAEngine(ViTEngine):
 
     """Backbone-backward mode: the frozen ViT with peft-style LoRA on query / key / value of every
@@ -981,14 +998,27 @@ class ViTLoRAEngine(ViTEngine):
     checkpoint, ``down_proj`` of a gated DINOv3 one.  The backward recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation
     (UCOD_LORA_OUT_ACT_SWIGLU; the passes' flags carry UCOD_LORA_OUT_SWIGLU, set only when the module is targeted).  The arena row ends in
     [A_2 (r x F) | B_2 (D x r)] with F the padded hidden width; the state dicts and the adapter folder carry A_2 as HF has it, [r, F0]: the padded columns are
-    zeros in the arena and absent outside it.  A hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers."""
+    zeros in the arena and absent outside it.  A hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers.
+
+    ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66) also trains the bias of every targeted module that has one in the checkpoint (DINOv3
+    ``k_proj`` has none: no parameter).  Nothing else changes: forward = base(x) + scaling B(A(drop(x))) with the base layer's own bias, which dropout does not
+    touch.  The arena row then ends, behind everything above, in the trained biases in the order q, k, v, MLP input (N1 values in the engine's padded, interleaved
+    order; padding zero), attention output, MLP output; they start at the checkpoint's values.  The backward writes their gradients -- column sums of cotangents
+    it already holds (include/ucod_dpl.h: ucod_colsum_det, ucod_vit_backward_lora_bias) -- into the same slots of the gradient arena; ``repack`` copies the
+    arena's biases into the engine's own bias vectors, which (with ``clone_for_ema``'s) are private copies in that mode.  Every last-layer bias but the key's
+    cannot receive a gradient (only the key projection reaches the key map): its arena slot holds zeros, which the fused AdamW keeps at an exact zero, and the
+    state dicts, merges and the adapter take the checkpoint's value for it (``_bias_frozen``).  ``lora_state_dict`` / ``merged_state_dict`` / ``merge_into``
+    carry the biases as ``{layer path}{i}.{module}.bias`` in HF order.  "all" is refused (``check_lora_bias``); "none" is the engine as it always was."""
 
     # (defaults of an engine built without ``allow_out``: no output projection is targeted)
     allow_out, out_targets, out_off, _out_paths = False, (False, False), (None, None), ("attention.output.dense", "mlp.fc2")
     allow_swiglu_out, _out_flags = False, 0
+    # (defaults of an engine built without ``bias``: no bias is trained)
+    bias, bias_off, bias_numel, _bias_flat = "none", (None,) * N.VIT_TRAIN_BIAS_STRIDE, 0, None
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
-                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False):
+                 seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False,
+                 bias="none"):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
@@ -997,7 +1027,9 @@ class ViTLoRAEngine(ViTEngine):
         ucod_vit_train_desc.allow_rope).  Its modules are ``{model.,}layer.{i}.attention.{q,k,v}_proj`` (``lora_targets_dinov3``); a gated-MLP checkpoint
         (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``.
         ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``.
-        ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (class docstring).  Opt-in: ``lora_cfg.allow_swiglu_out``."""
+        ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (class docstring).  Opt-in: ``lora_cfg.allow_swiglu_out``.
+        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" (the engine as it is, bit for bit) or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``."""
+        check_lora_bias(bias)
         canon = normalize_state_dict(state_dict)
         if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
             raise ValueError("allow_swiglu_out=True needs allow_out=True and allow_swiglu=True" + (", and allow_rope=True on a DINOv3 checkpoint" if canon.get("rope") else ""))
@@ -1070,6 +1102,8 @@ class ViTLoRAEngine(ViTEngine):
             self.out_off[m], numel = numel, numel + r * (K + D)
         # (the flags word of the passes: set only with the SwiGLU MLP's output projection targeted)
         self._out_flags = N.LORA_OUT_SWIGLU if self.out_targets[1] and self.mlp == N.UCOD_MLP_SWIGLU else 0
+        if bias == "lora_only":                         # (behind everything else: an engine without trained biases keeps its row to the last element)
+            numel = self._setup_bias(state_dict, numel)
         self.lora = torch.zeros(L, numel, dtype=torch.float32, device=dev)
         bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
@@ -1084,6 +1118,7 @@ class ViTLoRAEngine(ViTEngine):
                 self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = torch.nn.functional.pad(a2, (0, K - self._F0)).reshape(L, r * K).to(dev)
             elif self.out_targets[m]:
                 self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = ((torch.rand(L, r * K, generator=generator) * 2 - 1) / math.sqrt(K)).to(dev)
+        self._bias_init_arena()
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
         self.train_layers = []                          # rows of the training table without its two LoRA slots (native.VIT_TRAIN_SLOTS)
@@ -1124,6 +1159,106 @@ class ViTLoRAEngine(ViTEngine):
         """Input width of output module ``m`` as the checkpoint has it: D, or the MLP's own hidden width F0 (SwiGLU: before padding; otherwise F0 = F)."""
         return (self.D, self._F0)[m]
 
+    # ---- trained biases (bias="lora_only") ----------------------------------------------------------------------------
+    def _bias_modules(self):
+        """The module path below ``{layer path}{i}.`` of each of the six bias slots (q, k, v, MLP input, attention output, MLP output), None where the module is
+        not targeted."""
+        mods = [f"{self._qkv_dir}{name}" if self.targets[p] else None for p, name in enumerate(self._qkv_names)]
+        mods.append(f"mlp.{self.mlp_target}" if self.mlp_target is not None else None)
+        return mods + [path if self.out_targets[m] else None for m, path in enumerate(self._out_paths)]
+
+    def _bias_layout(self, state_dict, numel):
+        """bias="lora_only" (host only): give every targeted module that has a bias in the checkpoint a slot behind the row's ``numel`` elements, in the order q, k, v,
+        MLP input, attention output, MLP output (``bias_off``; None = no parameter), and fix the columns of ``_bias_flat``.  Returns the new row length."""
+        D = self.D
+        try:
+            pref = self._hf_prefix(state_dict)
+        except NotImplementedError:                     # (a layout without HF module names: every Linear of it has a bias)
+            pref = None
+        self._bias_sizes = (D, D, D, self.N1, D, D)
+        self._bias_cols = (0, D, 2 * D, 3 * D, 3 * D + self.N1, 4 * D + self.N1)
+        off = []
+        for mod, n in zip(self._bias_modules(), self._bias_sizes):
+            has = mod is not None and (pref is None or f"{pref}0.{mod}.bias" in state_dict)     # (DINOv3 k_proj: key_bias = False, no parameter to train)
+            off.append(numel if has else None)
+            numel += n if has else 0
+        self.bias, self.bias_off = "lora_only", tuple(off)
+        self.bias_numel = sum(n for n, o in zip(self._bias_sizes, off) if o is not None)
+        return numel
+
+    def _setup_bias(self, state_dict, numel):
+        """``_bias_layout``, then this engine's bias vectors move into one private buffer ``_bias_flat`` [L, 3D + N1 + D + D] (q | k | v | m | o | 2) that the rows
+        of ``self.layers`` view -- so that ``repack`` is one strided copy per module and no tensor is shared with the checkpoint or a clone."""
+        numel = self._bias_layout(state_dict, numel)
+        if self.bias_numel:
+            flat = torch.empty(self.L, 5 * self.D + self.N1, dtype=torch.float32, device=self.device)
+            for i, row in enumerate(self.layers):
+                flat[i] = torch.cat((row[N.QKV_B], row[N.FC1_B], row[N.PROJ_B], row[N.FC2_B]))
+            self._bias_flat = flat
+            self._link_bias()
+        return numel
+
+    def _bias_init_arena(self):
+        """Trained biases start at the checkpoint's values; a slot that cannot receive a gradient (``_bias_frozen``) stays zero."""
+        for j, o in enumerate(self.bias_off):
+            if o is not None:
+                c, n, Lj = self._bias_cols[j], self._bias_sizes[j], (self.L if j == _BIAS_K else self.L - 1)
+                self.lora[:Lj, o:o + n] = self._bias_flat[:Lj, c:c + n]
+                self.lora[Lj:, o:o + n] = 0.0
+
+    def _repack_bias(self):
+        """arena -> the engine's own bias vectors, one strided copy per trained module (frozen slots keep the checkpoint's value: ``_bias_frozen``)"""
+        for j, o in enumerate(self.bias_off):
+            if o is not None:
+                c, n, Lj = self._bias_cols[j], self._bias_sizes[j], (self.L if j == _BIAS_K else self.L - 1)
+                self._bias_flat[:Lj, c:c + n].copy_(self.lora[:Lj, o:o + n])
+
+    def _link_bias(self):
+        """Point the bias slots of ``self.layers`` (a private list of rows) at ``_bias_flat``."""
+        D, c = self.D, self._bias_cols
+        rows = []
+        for i, row in enumerate(self.layers):
+            row, f = list(row), self._bias_flat[i]
+            row[N.QKV_B], row[N.FC1_B], row[N.PROJ_B], row[N.FC2_B] = f[:3 * D], f[c[_BIAS_M]:c[_BIAS_O]], f[c[_BIAS_O]:c[_BIAS_2]], f[c[_BIAS_2]:]
+            rows.append(row)
+        self.layers = rows
+
+    def _bias_frozen(self, i, j):
+        """True for a bias slot that cannot receive a gradient: every bias of the last layer but the key's (only the key projection reaches the key map).  torch's
+        AdamW skips such a parameter (its grad is None); the flat arena would decay it by lr * wd per step, so its arena slot holds zeros -- an exact zero stays at
+        zero -- and every reader takes the engine's own copy, which holds the checkpoint's value."""
+        return i == self.L - 1 and j != _BIAS_K
+
+    def _bias_value(self, i, j, src=None):
+        """The bias of slot ``j`` in layer ``i`` as the engine orders it: from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
+        c, n, o = self._bias_cols[j], self._bias_sizes[j], self.bias_off[j]
+        if self._bias_frozen(i, j):
+            return self._bias_flat[i, c:c + n]
+        return (self.lora if src is None else src)[i, o:o + n]
+
+    def _bias_to_hf(self, j, v):
+        """engine order -> the checkpoint's (SwiGLU weights_in: padded and interleaved -> HF rows, unpadded)"""
+        if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU:
+            return lora_b_from_engine(v.reshape(self.N1, 1), self._F0).reshape(-1)
+        return v.clone()
+
+    def _bias_from_hf(self, j, v, name):
+        n0 = 2 * self._F0 if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU else self._bias_sizes[j]
+        if tuple(v.shape) != (n0,):
+            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(n0,)}")
+        if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU:
+            return lora_b_to_engine(v.reshape(-1, 1)).reshape(-1)
+        return v
+
+    def _bias_table(self, grad):
+        """The bias table of the backward (native.VIT_TRAIN_BIAS_SLOTS: gradient destinations in ``grad`` [L, P]; NULL = not trained), or None without one."""
+        if not self.bias_numel:
+            return None
+        ptrs = []
+        for i in range(self.L):
+            ptrs += [None if o is None else grad[i, o:].data_ptr() for o in self.bias_off]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
     def lora_state_dict(self, grads=False, prefix=None):
         """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
         projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded.  A DINOv3
@@ -1150,6 +1285,10 @@ class ViTLoRAEngine(ViTEngine):
                     sa, sb = self._out_slices(m)
                     out[f"{prefix}{i}.{path}.lora_A.weight"] = src[i, sa].reshape(self.r, -1)[:, :self._out_width(m)].clone()      # (padded columns dropped)
                     out[f"{prefix}{i}.{path}.lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
+            for j, mod in enumerate(self._bias_modules()):          # bias="lora_only": the trained biases, HF order (a frozen slot: the checkpoint's value, gradient zero)
+                if self.bias_off[j] is not None:
+                    v = torch.zeros(self._bias_sizes[j], device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
+                    out[f"{prefix}{i}.{mod}.bias"] = self._bias_to_hf(j, v)
         return out
 
     def load_lora_state_dict(self, sd, prefix=None):
@@ -1188,6 +1327,10 @@ class ViTLoRAEngine(ViTEngine):
                         raise ValueError(f"{prefix}{i}.{path}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
                     a = torch.nn.functional.pad(a, (0, (self.D, self.F)[m] - a.shape[1]))      # (SwiGLU: the padded hidden units' columns load as zeros)
                     self.lora[i, sa], self.lora[i, sb] = a.reshape(-1), b.reshape(-1)
+            for j, mod in enumerate(self._bias_modules()):
+                if self.bias_off[j] is not None:
+                    name = f"{prefix}{i}.{mod}.bias"
+                    self._bias_value(i, j).copy_(self._bias_from_hf(j, take(name), name))       # (a frozen slot: into the engine's own copy; its arena slot stays zero)
         self.repack()
 
     def train(self, mode=True):
@@ -1210,6 +1353,7 @@ class ViTLoRAEngine(ViTEngine):
         for i, ml in enumerate(self.mlp_layers):               # the MLP module's B columns of fc1_w_aug (its A term is always added by the LayerNorm-2 backward)
             N.check(self.lib.ucod_lora_mlp_pack(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()),
                     "ucod_lora_mlp_pack")
+        self._repack_bias()
         self._packed_zero_a = zero_a
 
     # ---- passes -----------------------------------------------------------------------------------------------------
@@ -1250,6 +1394,13 @@ class ViTLoRAEngine(ViTEngine):
         T, TT, TM, keep = self._tables(gh, gw, self._tside_grad[i])
         return (C.byref(t), self.mlp, self._out_flags), (T, TT, TM, self._out_table(self._tside_grad[i])), keep
 
+    def _train_bytes(self, lead, tabs, i):
+        """Workspace of chunk ``i``'s training pass and backward: with trained biases the _lora_bias size (the column sums' partials behind everything else)."""
+        TB = self._bias_table(self._tside_grad[i])
+        if TB is None:
+            return self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(*lead, *tabs[2:])
+        return self.lib.ucod_vit_train_workspace_bytes_lora_bias(*lead, *tabs[2:], TB)
+
     def _chunks(self, B):
         """Image-parallel sub-batches (``self.train_streams``, default 2): as in ViTEngine.forward, every kernel of both passes is
         per image except the LoRA-gradient reduction over rows, which is done per chunk into its own buffer and summed at the end."""
@@ -1283,7 +1434,7 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._seed_of_chunk(i, b0))
             self._chunk_seed[i] = t.seed
             lead, tabs, keep = self._pass_args(t, gh, gw, i)
-            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(*lead, *tabs[2:]))
+            ws = self._tside_ws[i] = self._workspace(self._tside_ws[i], self._train_bytes(lead, tabs, i))
             with self._guard.bind():
                 N.check(self.lib.ucod_vit_forward_train_lora_out_ex(*lead, *tabs, N.ptr(img[b0:b1]), N.ptr(key[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
                         "ucod_vit_forward_train_lora_out_ex")
@@ -1335,6 +1486,10 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
             lead, tabs, keep = self._pass_args(t, gh, gw, i)
             ws = self._tside_ws[i]
+            TB = self._bias_table(self._tside_grad[i])
+            if TB is not None:                                     # trained biases: the same pass plus one column sum per bias, written into the chunk's arena copy
+                N.check(self.lib.ucod_vit_backward_lora_bias(*lead, *tabs, TB, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward_lora_bias")
+                return
             N.check(self.lib.ucod_vit_backward_lora_out_ex(*lead, *tabs, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward_lora_out_ex")
 
         self._fan_out(self._tside, self._bounds, run, (dkey,))
@@ -1415,6 +1570,10 @@ class ViTLoRAEngine(ViTEngine):
                 w0[:, :k].copy_(w.detach())
                 self._merge(self.lib, w0, self.lora[i, sa], B, merged)
                 out[key] = merged[:, :k].contiguous().to(w.device, copy=True)
+            for j, mod in enumerate(self._bias_modules()):          # bias="lora_only": merge_and_unload() leaves the trained bias in the base layer
+                if self.bias_off[j] is not None:
+                    key = f"{pref}{i}.{mod}.bias"
+                    out[key] = self._bias_to_hf(j, self._bias_value(i, j)).to(base[key].device, base[key].dtype)
         return out
 
     def _engine_row_source(self):
@@ -1452,8 +1611,18 @@ class ViTLoRAEngine(ViTEngine):
         pref = self._hf_prefix(base)
         swiglu = self.mlp == N.UCOD_MLP_SWIGLU
         st = N.stream
+        base_ptrs = {v.untyped_storage().data_ptr() for v in base.values() if torch.is_tensor(v) and v.is_cuda} if self.bias_numel else ()
         for i in range(self.L):
             row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
+            for j, o in enumerate(self.bias_off):                  # bias="lora_only": the trained biases into the live bias vectors first, so that the LayerNorm fold
+                if o is not None:                                  # below reads them (its folded bias is b' = q (W beta + b)); output projections have no fold
+                    slot, r0 = ((N.QKV_B, 0), (N.QKV_B, D), (N.QKV_B, 2 * D), (N.FC1_B, 0), (N.PROJ_B, 0), (N.FC2_B, 0))[j]
+                    if row[slot].untyped_storage().data_ptr() in base_ptrs:      # (an f32 state dict on the device: the engine's vector IS the checkpoint's -- the one
+                        own = row[slot].clone()                                  #  case in which a tensor of ``engine`` is replaced, once, so that the base stays the base)
+                        if fl is not None and fl[slot] is row[slot]:
+                            fl[slot] = own
+                        row[slot] = own
+                    row[slot][r0:r0 + self._bias_sizes[j]].copy_(self._bias_value(i, j))
             for name, p in self._targeted():
                 w = base[f"{pref}{i}.{name}.weight"]
                 if isinstance(p, tuple):                           # an output projection: merged, cast into the live tensor; no LayerNorm stands in front of it, so no fold
@@ -1512,6 +1681,9 @@ class ViTLoRAEngine(ViTEngine):
         other.lora_grad = torch.zeros_like(self.lora)
         other.train_layers = [[t.clone() if s in (N.T_QKV_W_AUG, N.T_QKV_WT_AUG) else t for s, t in enumerate(tl)] for tl in self.train_layers]
         other.mlp_layers = [[t.clone() for t in ml] for ml in self.mlp_layers]          # (the augmented fc1 weight carries the clone's own B_m)
+        if self._bias_flat is not None:                            # trained biases: the clone's bias vectors follow ITS arena (``repack``), so they are its own
+            other._bias_flat = self._bias_flat.clone()
+            other._link_bias()
         other._tside, other._saved_for = None, None
         other._merge_buf = None                                    # (its own staging buffer; the f32 base weights ``_base_sd`` are shared)
         other._guard = _SaturationGuard(self.lib, self.device)
