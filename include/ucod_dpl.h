@@ -326,7 +326,12 @@ typedef struct {
   int layer;
 } ucod_lora_dropout;
 
-/* y_aug bf16 [rows, D+64] = [ LayerNorm(x) | dropout_q(LN(x)) A_q^T, dropout_k(LN(x)) A_k^T, dropout_v(LN(x)) A_v^T (3r values) | 0 ] */
+/* y_aug bf16 [rows, D+64] = [ LayerNorm(x) | dropout_q(LN(x)) A_q^T, dropout_k(LN(x)) A_k^T, dropout_v(LN(x)) A_v^T (3r values) | 0 ]
+ * Limit on (D, r): the kernel keeps the layer's 3 r rows of A in one workgroup's LDS, 3 * r * D * 4 bytes, which must fit what the device gives one
+ * workgroup (queried once; 160 KiB on gfx950: r <= 17 at D = 768, r <= 13 at 1024, r <= 8 at 1536).  Past 64 KiB the launch asks for the larger
+ * allocation itself.  A (D, r) that does not fit returns UCOD_EINVAL before any launch; ucod_layernorm_lora_fits(D, r, 3) tells beforehand
+ * (modules = 3: q / k / v, 1: the MLP input projection; 1 = fits, 0 = refused or invalid), and the training passes refuse such a descriptor. */
+int ucod_layernorm_lora_fits(int D, int r, int modules);
 int ucod_layernorm_lora(const float* x, const float* gamma, const float* beta, const float* lora_layer, int r, void* y_aug_bf16,
                         int rows, int D, float eps, const ucod_lora_dropout* dropout, void* stream);
 /* the same from an IEEE fp16 residual stream (the no-grad LoRA pass with vit.resid16) */

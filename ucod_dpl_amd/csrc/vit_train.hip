@@ -637,11 +637,42 @@ constexpr int LORA_GRAD_BLOCKS = 512;                            // (1024 measur
 
 using namespace ucod;
 
+// LDS one workgroup may have on the current device, queried once (gfx950: 160 KiB, of which a launch gets more than 64 KiB only after asking for it with
+// hipFuncAttributeMaxDynamicSharedMemorySize); SIZE_MAX when no device answers, so that descriptor checks made without one refuse nothing on its account
+static size_t lds_per_block() {
+  static const size_t v = [] {
+    hipDeviceProp_t pr;
+    int dv = 0;
+    if (hipGetDevice(&dv) != hipSuccess || hipGetDeviceProperties(&pr, dv) != hipSuccess) {
+      (void)hipGetLastError();
+      return (size_t)SIZE_MAX;
+    }
+    size_t m = pr.sharedMemPerBlock;
+    if (pr.sharedMemPerBlockOptin > m) m = pr.sharedMemPerBlockOptin;
+    if (pr.maxSharedMemoryPerMultiProcessor > m) m = pr.maxSharedMemoryPerMultiProcessor;   // (a CU's whole LDS can go to one workgroup)
+    return m;
+  }();
+  return v;
+}
+static inline size_t ln_lora_lds_bytes(int D, int r, int np) { return (size_t)np * (size_t)r * (size_t)D * sizeof(float); }
+
+extern "C" int ucod_layernorm_lora_fits(int D, int r, int modules) {
+  if (D <= 0 || r < 1 || (modules != 1 && modules != 3) || modules * r > AUG) return 0;
+  return ln_lora_lds_bytes(D, r, modules) <= lds_per_block() ? 1 : 0;
+}
+
+// a staging buffer past 64 KiB has to be asked for (per device: at every such launch, as ucod_lora_grad does)
+template <typename K>
+static inline hipError_t ask_lds(K kern, size_t lds) {
+  return lds > 65536 ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+
 // np: 3 = the q / k / v modules of one layer (lora = the layer's arena row), 1 = the MLP input projection (lora = A_m)
 static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const float* beta, const float* lora, int r, void* y_aug, int rows, int D, float eps,
                           const ucod_lora_dropout* dropout, void* stream, int np = 3) {
   if (!x || !gamma || !beta || !lora || !y_aug || rows <= 0 || D <= 0 || (D % 128) != 0 || r < 1 || np * r > AUG) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+  if (ln_lora_lds_bytes(D, r, np) > lds_per_block()) return UCOD_EINVAL;      // the np r A rows do not fit one workgroup's LDS: refused before any launch
   UCOD_PROF(np == 1 ? PROF_LN_LORA_MLP : PROF_LN, stream);
   const Drop drop = make_drop(dropout);
   static const int lnl_env = [] { const char* e = ucod::lab_env("UCOD_LN_LORA_NBLK"); return e ? atoi(e) : 0; }();          // measurement knob
@@ -649,16 +680,22 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   const int nblk = cdiv(rows, 8) < lnl_max ? cdiv(rows, 8) : lnl_max;   // block-stride over rows: the A rows are staged once per block
   dim3 grid(nblk), block(256);
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = (size_t)np * r * D * sizeof(float);
+  const size_t lds = ln_lora_lds_bytes(D, r, np);
   static const bool narrow = ucod::lab_env("UCOD_LN_LORA_NARROW") != nullptr;     // measurement knob: the 8-byte / 4-byte form
+#define LNL(kern)                                                                                                       \
+  do {                                                                                                                  \
+    const hipError_t e = ask_lds(kern, lds);                                                                            \
+    if (e != hipSuccess) return (int)e;                                                                                 \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);       \
+  } while (0)
   if ((D % 256) == 0 && D <= 1536 && !narrow) {
     switch (D / 256) {
 #define C4(n)                                                                                                                                        \
   case n:                                                                                                                                            \
-    if (np == 1 && x_h16) hipLaunchKernelGGL((ln_lora4_kernel<n, true, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
-    else if (np == 1) hipLaunchKernelGGL((ln_lora4_kernel<n, false, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);    \
-    else if (x_h16) hipLaunchKernelGGL((ln_lora4_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
-    else hipLaunchKernelGGL((ln_lora4_kernel<n, false>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);          \
+    if (np == 1 && x_h16) LNL((ln_lora4_kernel<n, true, 1>)); \
+    else if (np == 1) LNL((ln_lora4_kernel<n, false, 1>));    \
+    else if (x_h16) LNL((ln_lora4_kernel<n, true>)); \
+    else LNL((ln_lora4_kernel<n, false>));          \
     break;
       C4(1) C4(2) C4(3) C4(4) C4(5) C4(6)
 #undef C4
@@ -669,15 +706,16 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   switch (D / 128) {
 #define C(n)                                                                                                                                         \
   case n:                                                                                                                                            \
-    if (np == 1 && x_h16) hipLaunchKernelGGL((ln_lora_kernel<n, true, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop); \
-    else if (np == 1) hipLaunchKernelGGL((ln_lora_kernel<n, false, 1>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);    \
-    else if (x_h16) hipLaunchKernelGGL((ln_lora_kernel<n, true>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);      \
-    else hipLaunchKernelGGL((ln_lora_kernel<n, false>), grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);           \
+    if (np == 1 && x_h16) LNL((ln_lora_kernel<n, true, 1>)); \
+    else if (np == 1) LNL((ln_lora_kernel<n, false, 1>));    \
+    else if (x_h16) LNL((ln_lora_kernel<n, true>));      \
+    else LNL((ln_lora_kernel<n, false>));           \
     break;
     C(1) C(2) C(3) C(4) C(5) C(6) C(8) C(10) C(12)
 #undef C
     default: return UCOD_EINVAL;
   }
+#undef LNL
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -84,7 +84,8 @@ bool valid(const Pass& c) {
   const ucod_vit_desc* d = &t->vit;
   return d->B > 0 && d->C > 0 && d->P > 0 && d->H > 0 && d->W > 0 && d->H % d->P == 0 && d->W % d->P == 0 && d->D > 0 && d->heads > 0 &&
          d->D == d->heads * 64 && d->D % 128 == 0 && d->F % 128 == 0 && d->L >= 1 && d->Kpad % 64 == 0 && d->Kpad >= d->C * d->P * d->P &&
-         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
+         t->lora_r >= 1 && 3 * t->lora_r <= UCOD_LORA_AUG && ucod_layernorm_lora_fits(d->D, t->lora_r, 3) == 1 &&   // (the 3 r A rows fit one workgroup's LDS)
+         t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
          (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
          d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
          known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr) && valid_out(t, c.mlp, c.TO, c.out_flags);

@@ -228,6 +228,7 @@ SIGNATURES = {
     "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
     "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     "ucod_gemm_bf16_train": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+    "ucod_layernorm_lora_fits": (ci, [ci, ci, ci]),
     "ucod_layernorm_lora": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_lora_h16": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_bwd_lora": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, vp, vp, ci, C.POINTER(LoraDropout), vp]),

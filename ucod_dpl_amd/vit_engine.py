@@ -1077,6 +1077,9 @@ class ViTLoRAEngine(ViTEngine):
         self._seed, self._step, self._step_seed = int(seed), 0, 0
         if r < 1 or 3 * r > N.LORA_AUG:
             raise ValueError(f"LoRA rank {r} unsupported (1 <= r <= {N.LORA_AUG // 3})")
+        if N.load().ucod_layernorm_lora_fits(self.D, int(r), 3) != 1:
+            raise ValueError(f"LoRA rank {r} at width {self.D}: the 3 r rows of A ({3 * int(r) * self.D * 4} bytes) do not fit one workgroup's LDS "
+                             f"(include/ucod_dpl.h, ucod_layernorm_lora)")
         self.r, self.scaling = int(r), float(lora_alpha) / float(r)
         D, L, dev = self.D, self.L, self.device
         self.N1 = (2 if self.mlp == N.UCOD_MLP_SWIGLU else 1) * self.F          # rows of fc1 / of the padded, interleaved weights_in
