@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from ucod_dpl_amd import native as N
-from ucod_dpl_amd.vit_engine import ViTLoRAEngine, lora_targets, lora_targets_dinov3
+from ucod_dpl_amd.vit_engine import ViTLoRAEngine, lora_modules, lora_targets, lora_targets_dinov3
 import dinov3_ref as R3
 import dinov3_lora_ref as RL
 
@@ -140,14 +140,12 @@ def test_target_names_of_a_dinov3_checkpoint():
     assert lora_targets(["key", "weights_in"], "swiglu", 1) == ((False, True, False), "weights_in")
 
 
-def host_engine(tag, layer_path, targets=(True, True, True), r=2):
+def host_engine(tag, layer_path, targets=(True, True, True), r=2, family="dinov3"):
     """A ViTLoRAEngine as its constructor leaves the host side for a DINOv3 checkpoint, with the arena on the CPU (no library call is made by what is tested)."""
     m = R3.G22[tag]
     eng = object.__new__(ViTLoRAEngine)
-    eng.L, eng.D, eng.r, eng.scaling = R3.G22_LAYERS, m["D"], r, 2.0
-    eng.targets, eng.mlp_target, eng.mlp = targets, None, N.UCOD_MLP_GELU
-    eng._layer_path, eng._qkv_names, eng._qkv_dir = layer_path, ("q_proj", "k_proj", "v_proj"), "attention."
-    eng.qkv_numel = 6 * r * m["D"]
+    eng.L, eng.D, eng.r, eng.scaling, eng.mlp = R3.G22_LAYERS, m["D"], r, 2.0, N.UCOD_MLP_GELU
+    eng._adopt(layer_path, lora_modules(family, "gelu", m["D"], m["F"], m["F"], r, targets + (False, False, False)))
     eng.lora = torch.arange(eng.L * eng.qkv_numel, dtype=torch.float32).reshape(eng.L, eng.qkv_numel)
     eng.lora_grad = -eng.lora
     eng.lora_dropout = 0.05
@@ -183,8 +181,7 @@ def test_lora_state_dict_uses_the_checkpoints_names(layer_path, tmp_path):
 
 
 def test_a_dinov2_engine_keeps_its_names():
-    eng = host_engine("g46", "encoder.layer.")
-    eng._qkv_names, eng._qkv_dir = ("query", "key", "value"), "attention.attention."
+    eng = host_engine("g46", "encoder.layer.", family="dinov2")
     assert sorted(eng.lora_state_dict())[0] == "encoder.layer.0.attention.attention.key.lora_A.weight"
     assert ViTLoRAEngine._hf_prefix({"dinov2.encoder.layer.0.attention.attention.query.weight": 0}) == "dinov2.encoder.layer."
     from ucod_dpl_amd.models.modules import full_model as M

@@ -12,8 +12,7 @@ import torch
 
 from conftest import ROOT, load_golden, sub
 from ucod_dpl_amd import native as N
-from ucod_dpl_amd.vit_engine import (ViTLoRAEngine, _prepare_mlp, check_lora_bias, lora_targets, lora_targets_dinov3, normalize_state_dict, _QKV, _QKV3, _OUT, _OUT3,
-                                     _dinov3_paths)
+from ucod_dpl_amd.vit_engine import ViTLoRAEngine, _prepare_mlp, check_lora_bias, lora_layout, normalize_state_dict
 import dinov3_ref as R3
 import lora_bias_ref as RB
 import lora_out_ref as RO
@@ -102,42 +101,18 @@ def test_size_helpers_and_host_side_refusals():
 
 # ------------------------------------------------------------------------------------------------ the arena
 def host_engine(sd, targets, bias="lora_only", seed=1, **allow):
-    """A ViTLoRAEngine with what the constructor derives on the host -- targets, names, the row layout through the constructor's own ``_bias_layout`` /
-    ``_bias_init_arena`` -- and its arena and bias vectors on the CPU: the constructor itself uploads the backbone to a GPU, which this machine may not have
-    (tests/test_gpu_lora_bias.py checks real engines against the same expectations)."""
-    canon = normalize_state_dict(sd)
-    mlp, c = _prepare_mlp(canon)
-    swiglu = mlp == N.UCOD_MLP_SWIGLU
+    """A ViTLoRAEngine with what the constructor derives on the host -- its own ``lora_layout`` / ``_adopt`` / ``_bias_init_arena`` -- and its arena and bias
+    vectors on the CPU: the constructor itself uploads the backbone to a GPU, which this machine may not have (tests/test_gpu_lora_bias.py checks real engines
+    against the same expectations)."""
     e = object.__new__(ViTLoRAEngine)
-    e.device, e.r, e.mlp, e.L = torch.device("cpu"), 2, mlp, len(c["layers"])
-    e.D, e.F = c["patch_w"].shape[0], c["layers"][0]["fc2_w"].shape[1]
-    e._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if swiglu else 1)
-    e.N1, e.qkv_numel = (2 if swiglu else 1) * e.F, 6 * e.r * e.D
-    so = {"allow_swiglu_out": True, "hidden": e._F0} if allow.get("allow_swiglu_out") and swiglu else {}
-    ao = {"allow_out": True} if allow.get("allow_out") else {}
-    if canon.get("rope"):
-        e._layer_path, e._qkv_names, e._qkv_dir = _dinov3_paths(sd)[1], _QKV3, "attention."
-        e._out_paths, leaves = ("attention.o_proj", "mlp.down_proj"), _OUT3
-        hit = lora_targets_dinov3(targets, swiglu, e.L, e._layer_path, **ao, **so)
-        (e.targets, out_hit), e.mlp_target = (hit if ao else (hit, ())), None
-    else:
-        e._layer_path, e._qkv_names, e._qkv_dir = "encoder.layer.", _QKV, "attention.attention."
-        e._out_paths, leaves = (("attention.output.dense", "mlp.weights_out"), ("dense", "weights_out")) if so else (("attention.output.dense", "mlp.fc2"), _OUT)
-        hit = lora_targets(targets, "swiglu" if swiglu else "gelu", e.L, **ao, **so)
-        e.targets, e.mlp_target, out_hit = hit if ao else hit + ((),)
-    e.out_targets = tuple(leaf in out_hit for leaf in leaves)
-    numel = e.qkv_numel + (e.r * (e.D + e.N1) if e.mlp_target is not None else 0)
-    e.out_off = [None, None]
-    for m, K in enumerate((e.D, e.F)):
-        if e.out_targets[m]:
-            e.out_off[m], numel = numel, numel + e.r * (K + e.D)
-    e.base_numel = numel
-    if bias == "lora_only":
-        numel = e._bias_layout(sd, numel)
-        e._bias_flat = torch.stack([torch.cat([l[k].float() for k in ("qkv_b", "fc1_b", "proj_b", "fc2_b")]) for l in c["layers"]]) if e.bias_numel else None
-    e.lora = torch.randn(e.L, numel, generator=torch.Generator().manual_seed(seed))       # (every element nonzero: a slot the constructor's code does not write shows)
-    if bias == "lora_only":
-        e._bias_init_arena()
+    e.mlp, c = _prepare_mlp(normalize_state_dict(sd))
+    e.device, e.r, e.L, e.D, e.F = torch.device("cpu"), 2, len(c["layers"]), c["patch_w"].shape[0], c["layers"][0]["fc2_w"].shape[1]
+    e._adopt(*lora_layout(sd, e.r, targets, bias, **allow), bias)
+    e.base_numel = e.numel - e.bias_numel
+    if e.bias_numel:
+        e._bias_flat = torch.stack([torch.cat([l[k].float() for k in ("qkv_b", "fc1_b", "proj_b", "fc2_b")]) for l in c["layers"]])
+    e.lora = torch.randn(e.L, e.numel, generator=torch.Generator().manual_seed(seed))     # (every element nonzero: a slot the constructor's code does not write shows)
+    e._bias_init_arena()
     e.lora_grad = torch.zeros_like(e.lora)
     e.lora_dropout, e.scaling = 0.05, 2.0
     e.repack = e._repack_bias                    # (the host half of repack(): arena -> bias vectors)

@@ -229,23 +229,13 @@ def test_mask_helper_draws_over_the_padded_width():
 def arena_only_engine(sd, targets, seed):
     """A ViTLoRAEngine with the arena and the names its state-dict methods use, and nothing else: the constructor uploads the backbone to a GPU, which this
     machine may not have.  Layout as the constructor lays it out (tests/test_gpu_lora_swiglu_out.py checks the real engine against the same dict)."""
-    from ucod_dpl_amd.vit_engine import ViTLoRAEngine
+    from ucod_dpl_amd.vit_engine import ViTLoRAEngine, lora_layout
     from ucod_dpl_amd.swiglu import padded_hidden
-    D, r, L = 128, 2, 3
-    F0 = sd["encoder.layer.0.mlp.weights_out.weight"].shape[1]
-    qkv, mlp_hit, out_hit = lora_targets(targets, "swiglu", L, hidden=F0, **ALL)
     e = object.__new__(ViTLoRAEngine)
-    e.device, e.D, e.L, e.r, e.F, e._F0, e.mlp = torch.device("cpu"), D, L, r, padded_hidden(F0), F0, N.UCOD_MLP_SWIGLU
-    e.N1, e.qkv_numel = 2 * e.F, 6 * r * D
-    e._layer_path, e._qkv_names, e._qkv_dir = "encoder.layer.", ("query", "key", "value"), "attention.attention."
-    e.targets, e.mlp_target = qkv, mlp_hit
-    e._out_paths, e.out_targets = ("attention.output.dense", "mlp.weights_out"), tuple(leaf in out_hit for leaf in ("dense", "weights_out"))
-    numel = e.qkv_numel + (r * (D + e.N1) if mlp_hit else 0)
-    e.out_off = [None, None]
-    for m, K in enumerate((D, e.F)):
-        if e.out_targets[m]:
-            e.out_off[m], numel = numel, numel + r * (K + D)
-    e.lora = torch.randn(L, numel, generator=torch.Generator().manual_seed(seed))      # (every element nonzero: a column the loader does not write shows)
+    e.device, e.D, e.L, e.r, e.mlp = torch.device("cpu"), 128, 3, 2, N.UCOD_MLP_SWIGLU
+    e.F = padded_hidden(sd["encoder.layer.0.mlp.weights_out.weight"].shape[1])
+    e._adopt(*lora_layout(sd, e.r, targets, **ALL))
+    e.lora = torch.randn(e.L, e.numel, generator=torch.Generator().manual_seed(seed))  # (every element nonzero: a column the loader does not write shows)
     e.lora_grad = torch.zeros_like(e.lora)
     e.repack = lambda: None
     return e

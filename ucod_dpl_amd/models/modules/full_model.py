@@ -68,9 +68,10 @@ def _adapter_prefix(engine):
 def _adapter_targets(engine):
     """target_modules of an engine as peft lists them: the leaf names (query / key / value; q_proj / k_proj / v_proj on a DINOv3 checkpoint; with the output
     projections targeted also dense / fc2 -- weights_out on a SwiGLU checkpoint --, or o_proj / down_proj)"""
-    names = [n for n, on in zip(getattr(engine, "_qkv_names", ("query", "key", "value")), engine.targets) if on]
-    names += [engine.mlp_target] if engine.mlp_target is not None else []
-    return names + [path.rsplit(".", 1)[-1] for path, on in zip(getattr(engine, "_out_paths", ()), getattr(engine, "out_targets", ())) if on]
+    if hasattr(engine, "modules"):
+        return [m.leaf for m in engine.modules if m.targeted]
+    # (anything with the engine's LoRA interface and DINOv2's names: ``targets`` and ``mlp_target`` alone)
+    return [n for n, on in zip(("query", "key", "value"), engine.targets) if on] + ([engine.mlp_target] if engine.mlp_target is not None else [])
 
 
 def save_lora_adapter(engine, folder):

@@ -18,6 +18,7 @@ import contextlib
 import ctypes as C
 import math
 import os
+import typing
 
 import torch
 import torch.nn.functional as F
@@ -793,25 +794,160 @@ class SplitViTEngine(_BackboneEngine):
     __call__ = forward
 
 
-_QKV = ("query", "key", "value")
 _MASK64 = 0xFFFFFFFFFFFFFFFF
-_MLP_IN = {"gelu": "fc1", "swiglu": "weights_in"}            # the MLP input projection by MLP kind (modeling_dinov2.py:281-297 / :300-315)
-# the Linear modules of one DINOv2 encoder layer (and the patch embedding's conv) by HF name: what peft's suffix match walks
-_LAYER_MODULES = ("attention.attention.query", "attention.attention.key", "attention.attention.value", "attention.output.dense", "mlp.{mlp_in}", "mlp.{mlp_out}")
-_REFUSED = {
+LORA_OUT_MAX_K = 4096                                        # include/ucod_dpl.h: the widest input the output projections' LoRA kernels take
+
+# ---- LoRA mode: the six Linear modules of a layer that can carry an adapter, in arena / bias-table order (native.VIT_TRAIN_BIAS_SLOTS) ------------------------
+_Q, _K, _V, _MLP_IN, _ATTN_OUT, _MLP_OUT = range(N.VIT_TRAIN_BIAS_STRIDE)
+# their leaf names.  DINOv2 (HF Dinov2Model / ViTModel): q / k / v, the MLP input by MLP kind (modeling_dinov2.py:281-297 / :300-315), the output projections
+# ``allow_out`` builds; DINOv3ViTModel's in the same order (its gated MLP keeps the plain one's names)
+_QKV, _MLP_IN_LEAF, _OUT = ("query", "key", "value"), {"gelu": "fc1", "swiglu": "weights_in"}, ("dense", "fc2")
+_QKV3, _OUT3 = ("q_proj", "k_proj", "v_proj"), ("o_proj", "down_proj")
+# where each of the six lives in a frozen engine's row: weight, bias and column-sum slot, the LayerNorm folded into it (gamma, beta; none in front of an output
+# projection)
+_ENGINE_SLOTS = (((N.QKV_W, N.QKV_B, N.QKV_COLSUM, (N.LN1_G, N.LN1_B)),) * 3
+                 + ((N.FC1_W, N.FC1_B, N.FC1_COLSUM, (N.LN2_G, N.LN2_B)), (N.PROJ_W, N.PROJ_B, None, None), (N.FC2_W, N.FC2_B, None, None)))
+
+
+def lora_module_paths(family, mlp="gelu"):
+    """The six modules' HF paths below ``{layer path}{i}.`` -- query, key, value, MLP input, attention output, MLP output -- of a checkpoint family ("dinov2": HF
+    Dinov2Model / ViTModel; "dinov3": DINOv3ViTModel, whose gated MLP keeps the plain one's names) and MLP kind ("gelu" | "swiglu")."""
+    if family == "dinov3":
+        return tuple("attention." + n for n in _QKV3) + ("mlp.up_proj", "attention." + _OUT3[0], "mlp." + _OUT3[1])
+    return (tuple("attention.attention." + n for n in _QKV)
+            + ("mlp." + _MLP_IN_LEAF[mlp], "attention.output." + _OUT[0], "mlp." + (_OUT[1] if mlp == "gelu" else "weights_out")))
+
+
+class LoRAModule(typing.NamedTuple):
+    """One of the six modules as a ``ViTLoRAEngine`` holds it (``lora_modules``).  A is [r, k], B is [n, r]; ``k`` / ``n`` are the input width and row count in the
+    engine, ``k_hf`` / ``n_hf`` in the checkpoint -- they differ only on the SwiGLU MLP, whose hidden width is padded to a multiple of 128 and whose ``weights_in``
+    rows are interleaved (swiglu.py)."""
+    path: str                  # below the layer path: "attention.attention.query", "attention.q_proj", "mlp.weights_in" ...
+    targeted: bool
+    k: int
+    n: int
+    k_hf: int
+    n_hf: int
+    a: slice                   # A and B in a layer's arena row; None for an untargeted module without a place in it (q / k / v always have theirs)
+    b: slice
+    bias_off: int              # the trained bias [n] in the arena row, or None (bias="none", not targeted, or no bias in the checkpoint)
+    bias_cols: slice           # its bias in ``_bias_flat``
+    w_slot: int                # the frozen engine's row: weight, bias, column sums (None: never folded), (gamma, beta) of the folded LayerNorm or None
+    b_slot: int
+    c_slot: int
+    ln: tuple
+    row0: int                  # its first row in that weight / bias (the fused QKV weight holds three modules)
+    interleaved: bool          # rows in the engine's padded, interleaved order (SwiGLU ``weights_in``): B and the bias go through swiglu.lora_b_{to,from}_engine
+
+    @property
+    def leaf(self):
+        return self.path.rsplit(".", 1)[-1]
+
+    def a_to_hf(self, a):
+        """A [r, k] as the checkpoint's names carry it, [r, k_hf]: the padded hidden units' columns (zeros) are dropped."""
+        return a[:, :self.k_hf]
+
+    def a_from_hf(self, a):
+        return a if self.k == self.k_hf else torch.nn.functional.pad(a, (0, self.k - self.k_hf))
+
+    def rows_to_hf(self, v):
+        """B [n, r] (or the bias as [n, 1]) in the checkpoint's row order, [n_hf, ...]; the tensor itself where the orders agree."""
+        return lora_b_from_engine(v, self.n_hf // 2) if self.interleaved else v
+
+    def rows_from_hf(self, v):
+        return lora_b_to_engine(v) if self.interleaved else v
+
+
+def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 6):
+    """The module table of a LoRA engine: six ``LoRAModule`` in the order query, key, value, MLP input, attention output, MLP output.  Host only.
+    ``family`` / ``mlp``: ``lora_module_paths``; ``D``: the width; ``F`` / ``F0``: the MLP's hidden width in the engine (SwiGLU: padded) and in the checkpoint;
+    ``r``: the rank; ``hit``: which of the six are targeted (``resolve_lora_targets``); ``bias``: peft's mode; ``has_bias``: which have a bias in the checkpoint.
+    A layer's arena row is  [A_q | B_q | A_k | B_k | A_v | B_v]  -- always, an untargeted one's at zero --, then [A | B] of the MLP input, the attention output and
+    the MLP output where targeted, then (bias="lora_only") the biases of the targeted modules that have one, in the same order (``lora_row_numel``)."""
+    swiglu = mlp == "swiglu"
+    N1, N0 = (2 if swiglu else 1) * F, (2 if swiglu else 1) * F0
+    shapes = ((D, D, D, D),) * 3 + ((D, N1, D, N0), (D, D, D, D), (F, D, F0, D))          # (k, n, k_hf, n_hf)
+    mods, at, col = [], 0, 0
+    for j, (path, (k, n, k_hf, n_hf)) in enumerate(zip(lora_module_paths(family, mlp), shapes)):
+        a = b = None
+        if j <= _V or hit[j]:
+            a, b = slice(at, at + r * k), slice(at + r * k, at + r * (k + n))
+            at = b.stop
+        mods.append(LoRAModule(path, bool(hit[j]), k, n, k_hf, n_hf, a, b, None, slice(col, col + n), *_ENGINE_SLOTS[j], j * D if j <= _V else 0,
+                               swiglu and j == _MLP_IN))
+        col += n
+    for j, m in enumerate(mods):
+        if bias == "lora_only" and m.targeted and has_bias[j]:
+            mods[j], at = m._replace(bias_off=at), at + m.n
+    return tuple(mods)
+
+
+def lora_row_numel(mods):
+    """Length of a layer's arena row."""
+    return max([m.b.stop for m in mods if m.b is not None] + [m.bias_off + m.n for m in mods if m.bias_off is not None])
+
+
+# ---- target_modules -> which of the six --------------------------------------------------------------------------------------------------------------------------
+_REFUSED = {                                                 # DINOv2 names: why a module of that leaf name is not built (``allow_out`` lifts dense / fc2)
     "dense": "its input is written by the attention kernel, which has no leading-dimension argument for the 64 LoRA columns",
     "fc2": "its input is written by the fc1 GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
     "weights_out": "its input is written by the weights_in GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
     "projection": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
 }
-_OUT = ("dense", "fc2")                                      # the output projections ``allow_out`` builds, by leaf name (attention.output.dense, mlp.fc2)
 _SWIGLU_OUT = ("its input, the SwiGLU hidden, is not a saved activation: it would have to be recomputed from the interleaved, padded [M, 2F] pre-activation, "
                "which is not built yet")
 # (what the refusal says once that recomputation exists: the message above stays, with the way in behind it)
 _SWIGLU_OUT_OPT_IN = _SWIGLU_OUT + ".  That recomputation runs only with the opt-in allow_swiglu_out=True (beside allow_out and allow_swiglu)"
+_REFUSED3 = {                                                # DINOv3 names (``allow_out`` lifts o_proj and the plain MLP's down_proj)
+    "o_proj": "its input is written by the attention kernel, which has no leading-dimension argument for the 64 LoRA columns",
+    "down_proj": "its input is written by the MLP input GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
+    "up_proj": "the MLP input projection of a DINOv3 checkpoint is not built yet (on the gated MLP it is one of two peft modules, with gate_proj, on the one fused "
+               "weights_in GEMM)",
+    "gate_proj": "the gated MLP's input is two peft modules (gate_proj, up_proj) on the one fused weights_in GEMM: a LoRA module on one of them alone is not built",
+    "patch_embeddings": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
+}
+_DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", "weights_out", "projection")
 
 
-LORA_OUT_MAX_K = 4096                                        # include/ucod_dpl.h: the widest input the output projections' LoRA kernels take
+class _Names(typing.NamedTuple):
+    """What target resolution knows of a checkpoint family: the data in which ``lora_targets`` and ``lora_targets_dinov3`` differ."""
+    layer_path: str            # in front of the layer number
+    paths: tuple               # the six modules below it (``lora_module_paths``)
+    more: tuple                # what else peft's suffix rule can name: further modules of a layer ...
+    patch: str                 # ... and the patch embedding
+    refused: dict              # leaf name -> why a module of that name is not built, under the opt-ins given
+    ask: str                   # what an empty list is told to choose from
+    foreign: typing.Callable   # (target, its last component) -> "that is the other family's name", or None
+    swiglu: bool
+
+
+def _dinov2_names(mlp, allow_out, allow_swiglu_out):
+    refused = dict({k: v for k, v in _REFUSED.items() if k not in _OUT}, weights_out=_SWIGLU_OUT_OPT_IN) if allow_out else _REFUSED
+    if allow_swiglu_out:
+        refused = {k: v for k, v in refused.items() if k != "weights_out"}
+    mlp_in, other = _MLP_IN_LEAF[mlp], _MLP_IN_LEAF["swiglu" if mlp == "gelu" else "gelu"]
+
+    def foreign(t, last):
+        if last == other:
+            return f"target module {t!r}: this checkpoint has the {mlp.upper() if mlp == 'gelu' else 'SwiGLU'} MLP, whose input projection is {mlp_in!r}, not {other!r}"
+
+    return _Names("encoder.layer.", lora_module_paths("dinov2", mlp), (), "embeddings.patch_embeddings.projection", refused, "query / key / value", foreign, mlp == "swiglu")
+
+
+def _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out):
+    refused = _REFUSED3
+    if allow_out:
+        refused = {k: v for k, v in _REFUSED3.items() if k not in _OUT3}
+        if gated and not allow_swiglu_out:
+            refused["down_proj"] = _SWIGLU_OUT_OPT_IN
+
+    def foreign(t, last):
+        if last in _DINOV2_LEAVES:
+            return (f"target module {t!r} is a DINOv2 name: a DINOv3 checkpoint's attention projections are q_proj / k_proj / v_proj "
+                    f"({layer_path}{{i}}.attention.{{q,k,v}}_proj)")
+
+    return _Names(layer_path, lora_module_paths("dinov3"), ("mlp.gate_proj",) if gated else (), "embeddings.patch_embeddings", refused, "q_proj / k_proj / v_proj",
+                  foreign, bool(gated))
 
 
 def _check_swiglu_out(allow_out, allow_swiglu_out):
@@ -826,123 +962,75 @@ def _check_swiglu_out_width(name, hidden):
                                   f"{hidden}, padded) is beyond the kernels' K <= {LORA_OUT_MAX_K} -- a thread keeps the A values of its hidden units in registers")
 
 
+def resolve_lora_targets(target_modules, names, n_layers, hidden=None):
+    """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> which of the six modules are targeted, as six
+    booleans in table order.  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``; the same modules must be hit in
+    every layer; a name that hits a module that is not built (``names.refused``), no module at all, or the other family's module is refused with the reason.
+    None = query / key / value, the reference's.  ``hidden``: the checkpoint's MLP hidden width, when known: a SwiGLU MLP output projection beyond the kernels'
+    width is refused here, before anything touches the device."""
+    if target_modules is None:
+        return (True, True, True, False, False, False)
+    if isinstance(target_modules, str):
+        raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
+    targets = list(target_modules)
+    if not targets:
+        raise ValueError(f"target_modules is empty: name at least one of {names.ask}")
+    lay = names.layer_path
+    modules = [f"{lay}{i}.{m}" for i in range(n_layers) for m in names.paths + names.more] + [names.patch]
+    hit = set()
+    for t in targets:
+        if not isinstance(t, str) or not t:
+            raise ValueError(f"target_modules entry {t!r} is not a module name")
+        found = [n for n in modules if n == t or n.endswith("." + t)]
+        last = t.rsplit(".", 1)[-1]
+        if not found:
+            if names.foreign(t, last):
+                raise ValueError(names.foreign(t, last))
+            raise NotImplementedError(f"LoRA target module {t!r} is not built: {names.refused.get(last, 'no Linear module of the backbone has that name')}")
+        for n in found:
+            leaf = n.rsplit(".", 1)[-1]
+            if leaf in names.refused:
+                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {names.refused[leaf]}")
+            hit.add(n)
+    per_layer = [{n[len(f"{lay}{i}."):] for n in hit if n.startswith(f"{lay}{i}.")} for i in range(n_layers)]
+    if any(pl != per_layer[0] for pl in per_layer):
+        raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
+    if names.swiglu and names.paths[_MLP_OUT] in per_layer[0]:
+        _check_swiglu_out_width(names.paths[_MLP_OUT].rsplit(".", 1)[-1], hidden)
+    return tuple(p in per_layer[0] for p in names.paths)
+
+
+def _out_leaves(names, hit):
+    """the leaf names of the output projections that are hit, as the two public functions return them"""
+    return tuple(names.paths[j].rsplit(".", 1)[-1] for j in (_ATTN_OUT, _MLP_OUT) if hit[j])
+
+
 def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False, allow_swiglu_out=False, hidden=None):
-    """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> ((query, key, value) as booleans, the MLP
-    input projection's name or None).  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``.  Built: any
-    subset of query / key / value and the MLP input projection (``fc1`` on a GELU checkpoint, ``weights_in`` on a SwiGLU one) -- the modules whose input
-    is a LayerNorm output, which the LayerNorm kernel can extend by the LoRA down-projection.  None = the reference's query / key / value.
+    """``resolve_lora_targets`` on DINOv2's names -> ((query, key, value) as booleans, the MLP input projection's name or None).  Built: any subset of query / key /
+    value and the MLP input projection (``fc1`` on a GELU checkpoint, ``weights_in`` on a SwiGLU one) -- the modules whose input is a LayerNorm output, which the
+    LayerNorm kernel can extend by the LoRA down-projection.
     ``allow_out=True`` also accepts the output projections ``dense`` (attention.output.dense) and, on a GELU checkpoint, ``fc2`` -- row kernels beside their GEMMs
     (include/ucod_dpl.h: ucod_lora_out_fwd) -- and returns a third element: the accepted ones of ("dense", "fc2"), in that order.  ``weights_out`` stays refused.
     ``allow_swiglu_out=True`` (needs ``allow_out``; ValueError without it) accepts ``weights_out`` on a SwiGLU checkpoint as well -- the hidden is recomputed from
-    the saved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU) -- and the third element is then drawn from ("dense", "weights_out").  ``hidden``: the checkpoint's MLP
-    hidden width, when known; with it a ``weights_out`` whose padded width is beyond the kernels' 4096 is refused here (NotImplementedError)."""
-    if mlp not in _MLP_IN:
+    the saved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU) -- and the third element is then drawn from ("dense", "weights_out")."""
+    if mlp not in _MLP_IN_LEAF:
         raise ValueError(f"mlp must be 'gelu' or 'swiglu', got {mlp!r}")
     _check_swiglu_out(allow_out, allow_swiglu_out)
-    if target_modules is None:
-        return ((True, True, True), None, ()) if allow_out else ((True, True, True), None)
-    refused = dict({k: v for k, v in _REFUSED.items() if k not in _OUT}, weights_out=_SWIGLU_OUT_OPT_IN) if allow_out else _REFUSED
-    if allow_swiglu_out:
-        refused = {k: v for k, v in refused.items() if k != "weights_out"}
-    if isinstance(target_modules, str):
-        raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
-    targets = list(target_modules)
-    if not targets:
-        raise ValueError("target_modules is empty: name at least one of query / key / value")
-    mlp_in, mlp_out = _MLP_IN[mlp], {"gelu": "fc2", "swiglu": "weights_out"}[mlp]
-    names = [f"encoder.layer.{i}." + m.format(mlp_in=mlp_in, mlp_out=mlp_out) for i in range(n_layers) for m in _LAYER_MODULES]
-    names.append("embeddings.patch_embeddings.projection")
-    hit = set()
-    for t in targets:
-        if not isinstance(t, str) or not t:
-            raise ValueError(f"target_modules entry {t!r} is not a module name")
-        found = [n for n in names if n == t or n.endswith("." + t)]
-        last = t.rsplit(".", 1)[-1]
-        if not found:
-            other = _MLP_IN["swiglu" if mlp == "gelu" else "gelu"]
-            if last == other:
-                raise ValueError(f"target module {t!r}: this checkpoint has the {mlp.upper() if mlp == 'gelu' else 'SwiGLU'} MLP, whose input projection is "
-                                 f"{mlp_in!r}, not {other!r}")
-            reason = refused.get(last, "no Linear module of the backbone has that name")
-            raise NotImplementedError(f"LoRA target module {t!r} is not built: {reason}")
-        for n in found:
-            leaf = n.rsplit(".", 1)[-1]
-            if leaf in refused:
-                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {refused[leaf]}")
-            hit.add(n)
-    per_layer = [{n.split(".", 3)[3] for n in hit if n.startswith(f"encoder.layer.{i}.")} for i in range(n_layers)]
-    if any(pl != per_layer[0] for pl in per_layer):
-        raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
-    qkv = tuple("attention.attention." + n in per_layer[0] for n in _QKV)
-    mlp_hit = mlp_in if "mlp." + mlp_in in per_layer[0] else None
-    if not allow_out:
-        return qkv, mlp_hit
-    if mlp == "swiglu" and "mlp.weights_out" in per_layer[0]:
-        _check_swiglu_out_width("weights_out", hidden)
-    return qkv, mlp_hit, tuple(leaf for leaf, path in zip(("dense", mlp_out), ("attention.output.dense", "mlp." + mlp_out)) if path in per_layer[0])
-
-
-_QKV3 = ("q_proj", "k_proj", "v_proj")                       # DINOv3ViTAttention's projections, in the order of _QKV
-_REFUSED3 = {
-    "o_proj": "its input is written by the attention kernel, which has no leading-dimension argument for the 64 LoRA columns",
-    "down_proj": "its input is written by the MLP input GEMM's drain, which has no leading-dimension argument for the 64 LoRA columns",
-    "up_proj": "the MLP input projection of a DINOv3 checkpoint is not built yet (on the gated MLP it is one of two peft modules, with gate_proj, on the one fused "
-               "weights_in GEMM)",
-    "gate_proj": "the gated MLP's input is two peft modules (gate_proj, up_proj) on the one fused weights_in GEMM: a LoRA module on one of them alone is not built",
-    "patch_embeddings": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
-}
-_DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", "weights_out", "projection")
-
-
-_OUT3 = ("o_proj", "down_proj")                             # DINOv3's names of the two output projections, in the order of _OUT
+    names = _dinov2_names(mlp, allow_out, allow_swiglu_out)
+    hit = resolve_lora_targets(target_modules, names, n_layers, hidden)
+    mlp_hit = _MLP_IN_LEAF[mlp] if hit[_MLP_IN] else None
+    return (hit[:3], mlp_hit, _out_leaves(names, hit)) if allow_out else (hit[:3], mlp_hit)
 
 
 def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False, allow_swiglu_out=False, hidden=None):
-    """``lora_targets`` for a DINOv3 checkpoint, whose modules are ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj``
-    too): any non-empty subset of q_proj / k_proj / v_proj by peft's suffix rule, None = all three.  Returns the (q, k, v) booleans; no MLP input module is built.
-    ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` (``lora_targets``) and returns ((q, k, v), the accepted ones of
-    ("o_proj", "down_proj")); the gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well; ``hidden``
-    as in ``lora_targets`` (dinov3_vith16plus, 5120, is refused)."""
+    """``resolve_lora_targets`` on a DINOv3 checkpoint's names, ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj`` too):
+    any non-empty subset of q_proj / k_proj / v_proj.  Returns the (q, k, v) booleans; no MLP input module is built.
+    ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` and returns ((q, k, v), the accepted ones of ("o_proj", "down_proj")); the
+    gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well (dinov3_vith16plus, hidden 5120, is refused)."""
     _check_swiglu_out(allow_out, allow_swiglu_out)
-    if target_modules is None:
-        return ((True, True, True), ()) if allow_out else (True, True, True)
-    refused = _REFUSED3
-    if allow_out:
-        refused = {k: v for k, v in _REFUSED3.items() if k not in _OUT3}
-        if gated and not allow_swiglu_out:
-            refused["down_proj"] = _SWIGLU_OUT_OPT_IN
-    if isinstance(target_modules, str):
-        raise NotImplementedError(f"target_modules {target_modules!r}: a string is a regular expression to peft; only a list of module names is built")
-    targets = list(target_modules)
-    if not targets:
-        raise ValueError("target_modules is empty: name at least one of q_proj / k_proj / v_proj")
-    mods = ["attention." + n for n in _QKV3 + ("o_proj",)] + ["mlp.up_proj", "mlp.down_proj"] + (["mlp.gate_proj"] if gated else [])
-    names = [f"{layer_path}{i}.{m}" for i in range(n_layers) for m in mods] + ["embeddings.patch_embeddings"]
-    hit = set()
-    for t in targets:
-        if not isinstance(t, str) or not t:
-            raise ValueError(f"target_modules entry {t!r} is not a module name")
-        found = [n for n in names if n == t or n.endswith("." + t)]
-        last = t.rsplit(".", 1)[-1]
-        if not found:
-            if last in _DINOV2_LEAVES:
-                raise ValueError(f"target module {t!r} is a DINOv2 name: a DINOv3 checkpoint's attention projections are q_proj / k_proj / v_proj "
-                                 f"({layer_path}{{i}}.attention.{{q,k,v}}_proj)")
-            raise NotImplementedError(f"LoRA target module {t!r} is not built: {refused.get(last, 'no Linear module of the backbone has that name')}")
-        for n in found:
-            leaf = n.rsplit(".", 1)[-1]
-            if leaf in refused:
-                raise NotImplementedError(f"LoRA target module {t!r} ({n}) is not built: {refused[leaf]}")
-            hit.add(n)
-    per_layer = [{n[len(f"{layer_path}{i}."):] for n in hit if n.startswith(f"{layer_path}{i}.")} for i in range(n_layers)]
-    if any(pl != per_layer[0] for pl in per_layer):
-        raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
-    qkv = tuple("attention." + n in per_layer[0] for n in _QKV3)
-    if not allow_out:
-        return qkv
-    if gated and "mlp.down_proj" in per_layer[0]:
-        _check_swiglu_out_width("down_proj", hidden)
-    return qkv, tuple(leaf for leaf, path in zip(_OUT3, ("attention.o_proj", "mlp.down_proj")) if path in per_layer[0])
+    names = _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out)
+    hit = resolve_lora_targets(target_modules, names, n_layers, hidden)
+    return (hit[:3], _out_leaves(names, hit)) if allow_out else hit[:3]
 
 
 def _dinov3_paths(sd):
@@ -951,9 +1039,40 @@ def _dinov3_paths(sd):
     return pref, ("model.layer." if any(k.startswith(pref + "model.layer.") for k in sd) else "layer.")
 
 
+def _hf_prefix(sd):
+    """What stands in front of the layer number in ``sd``'s names: ``encoder.layer.`` behind "", "dinov2." or "vit."; a DINOv3 state dict's own
+    ``{model.,}layer.`` behind its prefix."""
+    if is_dinov3(sd):
+        pref, lay = _dinov3_paths(sd)
+        return pref + lay
+    for pref in ("", "dinov2.", "vit."):
+        if pref + "encoder.layer.0.attention.attention.query.weight" in sd:
+            return pref + "encoder.layer."
+    raise NotImplementedError("merging takes a HuggingFace DINOv2 state dict (encoder.layer.{i}.attention.attention.{query,key,value}): the names "
+                              "target_modules are matched against")
+
+
+def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False, allow_swiglu_out=False, canon=None):
+    """Host only: (layer path, module table) of a ``ViTLoRAEngine`` over ``state_dict`` -- the family's names, ``resolve_lora_targets`` with all its refusals,
+    which modules have a bias in the checkpoint (DINOv3 ``k_proj`` has none), ``lora_modules``.  ``canon``: ``normalize_state_dict(state_dict)`` if at hand."""
+    c = normalize_state_dict(state_dict) if canon is None else canon
+    mlp = "swiglu" if c.get("mlp") == "swiglu" else "gelu"
+    F0 = c["layers"][0]["fc1_w"].shape[0] // (2 if mlp == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
+    sw_out = bool(allow_swiglu_out and mlp == "swiglu")           # (on a GELU checkpoint the opt-in changes nothing: weights_out keeps its refusal's text)
+    if c.get("rope"):
+        family, names = "dinov3", _dinov3_names(mlp == "swiglu", _dinov3_paths(state_dict)[1], allow_out, sw_out)
+    else:
+        family, names = "dinov2", _dinov2_names(mlp, allow_out, sw_out)
+    hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out else None)
+    try:
+        pref = _hf_prefix(state_dict)
+    except NotImplementedError:                     # (a layout without HF module names: every Linear of it has a bias)
+        pref = None
+    has_bias = tuple(pref is None or f"{pref}0.{p}.bias" in state_dict for p in names.paths)
+    return names.layer_path, lora_modules(family, mlp, c["patch_w"].shape[0], padded_hidden(F0) if mlp == "swiglu" else F0, F0, r, hit, bias, has_bias)
+
+
 LORA_BIAS_MODES = ("none", "lora_only", "all")               # peft's LoraConfig.bias (models/modules/full_model.py:53,66)
-# the six Linear modules of a layer whose bias "lora_only" can train, in arena / bias-table order (native.VIT_TRAIN_BIAS_SLOTS)
-_BIAS_Q, _BIAS_K, _BIAS_V, _BIAS_M, _BIAS_O, _BIAS_2 = range(N.VIT_TRAIN_BIAS_STRIDE)
 
 
 def check_lora_bias(bias):
@@ -969,52 +1088,47 @@ def check_lora_bias(bias):
 
 
 class ViTLoRAEngine(ViTEngine):
+    """Backbone-backward mode: the frozen ViT with peft-style LoRA on Linear modules of every encoder layer, as
+    models/modules/full_model.py:47-72 configures it (r=2, lora_alpha=4, bias='none', target query / key / value; lora_A kaiming_uniform(a=sqrt 5), lora_B zeros).
+    ``forward_train`` saves activations, ``backward`` turns the cotangent of the key map into LoRA gradients -- both entirely in the HIP library.  Every pass is ONE
+    call of a _lora_out_ex entry point (``ucod_vit_forward_train_lora_out_ex`` / ``ucod_vit_backward_lora_out_ex`` / ``ucod_vit_forward_lora_infer_lora_out_ex``,
+    include/ucod_dpl.h) with the MLP kind, ``_out_flags`` and the tables of the targeted modules; an untargeted module's table is NULL, and the pass then enqueues the
+    launches it would without it.  LoRA dropout (``lora_dropout``, 0.05 in the reference config) is a counter-based hash mask on the LoRA branch's input in
+    ``train()`` mode and off in ``eval()`` (include/ucod_dpl.h: ucod_lora_dropout).
 
-    """Backbone-backward mode: the frozen ViT with peft-style LoRA on query / key / value of every
-    encoder layer, as models/modules/full_model.py:47-72 configures it (r=2, lora_alpha=4, bias='none', target
-    query/key/value; lora_A kaiming_uniform(a=sqrt 5), lora_B zeros).  ``forward_train`` saves activations,
-    ``backward`` turns the cotangent of the key map into LoRA gradients -- both entirely in the HIP library.  Every pass is ONE call of a _lora_out_ex entry point
-    (``ucod_vit_forward_train_lora_out_ex`` / ``ucod_vit_backward_lora_out_ex`` / ``ucod_vit_forward_lora_infer_lora_out_ex``, include/ucod_dpl.h) with the MLP kind,
-    ``_out_flags`` and the tables of the targeted modules; an untargeted module's table is NULL, and the pass then enqueues the launches it would without it.  LoRA dropout (``lora_dropout``, 0.05 in the reference config) is a counter-based
-    hash mask on the LoRA branch's input in ``train()`` mode and off in ``eval()`` (include/ucod_dpl.h: ucod_lora_dropout).
+    What can carry an adapter is described ONCE, in ``self.modules``: six ``LoRAModule`` (``lora_modules``) in the fixed order query, key, value, MLP input,
+    attention output, MLP output.  Each states its HF path below the layer path, whether it is targeted, its shapes in the engine and in the checkpoint, its place in
+    the arena, its bias, its slots in a frozen engine's row and the conversions between HF's order and the engine's; the state dicts, the merges, the adapter folder
+    and the passes' tables all walk it.
 
-    Parameters live in ONE flat f32 arena ``self.lora`` [L, 6*r*D] (layer-major: A_q | B_q | A_k | B_k | A_v | B_v), gradients
-    in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel.
+        module             DINOv2 (``encoder.layer.{i}.``)            DINOv3 (``{model.,}layer.{i}.``)   input   needs
+        query, key, value  attention.attention.{query,key,value}      attention.{q,k,v}_proj             D       --
+        MLP input          mlp.fc1 | mlp.weights_in (SwiGLU)          (mlp.up_proj: not built)           D       r <= 8
+        attention output   attention.output.dense                     attention.o_proj                   D       allow_out, r <= 8
+        MLP output         mlp.fc2 | mlp.weights_out (SwiGLU)         mlp.down_proj                      F       allow_out (SwiGLU / gated: + allow_swiglu_out), r <= 8
 
-    ``target_modules`` (``lora_targets``): a subset of query / key / value keeps that block and holds the untargeted projections' A and B at zero -- their
-    gradients are then zero by structure (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero.  With the MLP
-    input projection (``fc1`` / ``weights_in``) the row grows to [6*r*D | A_m (r x D) | B_m (N1 x r)], N1 = F (GELU) or 2F in the engine's padded, interleaved row
-    order (SwiGLU), and the passes are given the module's table (``mlp_table_host``, include/ucod_dpl.h).  None = query / key / value: the engine as it always was.
+    ``target_modules`` (``resolve_lora_targets``, peft's suffix rule) picks among them; None = query / key / value.  Parameters live in ONE flat f32 arena
+    ``self.lora`` [L, P], gradients in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel.  A layer's row:
 
-    A DINOv3 checkpoint (``allow_rope=True``) has its own module names -- ``{model.,}layer.{i}.attention.{q,k,v}_proj`` -- which ``target_modules``, the state dicts,
-    the merges and the adapter folder use; the arena layout is the same (q | k | v).  No MLP input module is built for it yet.
+        [A_q | B_q | A_k | B_k | A_v | B_v]   always; an untargeted projection's A and B are held at zero -- their gradients are then zero by structure
+                                              (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero
+        [A_m (r x D) | B_m (N1 x r)]          if the MLP input is targeted; N1 = F (GELU) or 2F in the engine's padded, interleaved row order (SwiGLU)
+        [A_o (r x D) | B_o (D x r)]           if the attention output is targeted
+        [A_2 (r x F) | B_2 (D x r)]           if the MLP output is targeted; SwiGLU: F is the padded hidden width, the padded columns are zeros in the arena and
+                                              absent outside it (the state dicts and the adapter folder carry A_2 as HF has it, [r, F0])
+        [b_q | b_k | b_v | b_m | b_o | b_2]   bias="lora_only": the bias of every targeted module that has one in the checkpoint (DINOv3 ``k_proj`` has none)
 
-    ``allow_out=True`` also takes the output projections -- ``dense`` (attention.output.dense) and ``fc2`` on a DINOv2 GELU checkpoint, ``o_proj`` and ``down_proj``
-    on a non-gated DINOv3 one -- as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x; the passes are given ``out_table_host``).  The arena
-    row then ends in [A_o (r x D) | B_o (D x r)] and [A_2 (r x F) | B_2 (D x r)], for the targeted ones only; 1 <= r <= 8.  The SwiGLU MLP's output projection stays
-    refused.  With the flag off, or on with neither module named, every pass is launch for launch what it was.
+    The output projections run as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x); on the SwiGLU MLP the backward
+    recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU; ``_out_flags`` carries UCOD_LORA_OUT_SWIGLU only when the
+    module is targeted), and a hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers.
 
-    ``allow_swiglu_out=True`` (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``) lifts that refusal: ``weights_out`` of a DINOv2 SwiGLU
-    checkpoint, ``down_proj`` of a gated DINOv3 one.  The backward recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation
-    (UCOD_LORA_OUT_ACT_SWIGLU; the passes' flags carry UCOD_LORA_OUT_SWIGLU, set only when the module is targeted).  The arena row ends in
-    [A_2 (r x F) | B_2 (D x r)] with F the padded hidden width; the state dicts and the adapter folder carry A_2 as HF has it, [r, F0]: the padded columns are
-    zeros in the arena and absent outside it.  A hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers.
-
-    ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66) also trains the bias of every targeted module that has one in the checkpoint (DINOv3
-    ``k_proj`` has none: no parameter).  Nothing else changes: forward = base(x) + scaling B(A(drop(x))) with the base layer's own bias, which dropout does not
-    touch.  The arena row then ends, behind everything above, in the trained biases in the order q, k, v, MLP input (N1 values in the engine's padded, interleaved
-    order; padding zero), attention output, MLP output; they start at the checkpoint's values.  The backward writes their gradients -- column sums of cotangents
-    it already holds (include/ucod_dpl.h: ucod_colsum_det, ucod_vit_backward_lora_bias) -- into the same slots of the gradient arena; ``repack`` copies the
-    arena's biases into the engine's own bias vectors, which (with ``clone_for_ema``'s) are private copies in that mode.  Every last-layer bias but the key's
-    cannot receive a gradient (only the key projection reaches the key map): its arena slot holds zeros, which the fused AdamW keeps at an exact zero, and the
-    state dicts, merges and the adapter take the checkpoint's value for it (``_bias_frozen``).  ``lora_state_dict`` / ``merged_state_dict`` / ``merge_into``
-    carry the biases as ``{layer path}{i}.{module}.bias`` in HF order.  "all" is refused (``check_lora_bias``); "none" is the engine as it always was."""
-
-    # (defaults of an engine built without ``allow_out``: no output projection is targeted)
-    allow_out, out_targets, out_off, _out_paths = False, (False, False), (None, None), ("attention.output.dense", "mlp.fc2")
-    allow_swiglu_out, _out_flags = False, 0
-    # (defaults of an engine built without ``bias``: no bias is trained)
-    bias, bias_off, bias_numel, _bias_flat = "none", (None,) * N.VIT_TRAIN_BIAS_STRIDE, 0, None
+    ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66) changes nothing else: forward = base(x) + scaling B(A(drop(x))) with the base layer's own
+    bias, which dropout does not touch.  The trained biases start at the checkpoint's values (the MLP input's N1 values in the engine's order, padding zero).  The
+    backward writes their gradients -- column sums of cotangents it already holds (include/ucod_dpl.h: ucod_colsum_det, ucod_vit_backward_lora_bias) -- into the same
+    slots of the gradient arena; ``repack`` copies the arena's biases into the engine's own bias vectors, which (with ``clone_for_ema``'s) are private copies in that
+    mode.  Every last-layer bias but the key's cannot receive a gradient (only the key projection reaches the key map): its arena slot holds zeros, which the fused
+    AdamW keeps at an exact zero, and the state dicts, merges and the adapter take the checkpoint's value for it (``_bias_frozen``).  ``lora_state_dict`` /
+    ``merged_state_dict`` / ``merge_into`` carry the biases as ``{layer path}{i}.{module}.bias`` in HF order.  "all" is refused (``check_lora_bias``)."""
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False,
@@ -1024,41 +1138,22 @@ class ViTLoRAEngine(ViTEngine):
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
         ``allow_rope``: accept a DINOv3 checkpoint (rotary position embedding; ``rope_theta`` as ``ViTEngine``).  Its passes rotate q / k of the patch rows between
         the QKV GEMM and attention and apply the transposed rotation to dq / dk behind attention backward (include/ucod_dpl.h: ucod_rope_qk_ld,
-        ucod_vit_train_desc.allow_rope).  Its modules are ``{model.,}layer.{i}.attention.{q,k,v}_proj`` (``lora_targets_dinov3``); a gated-MLP checkpoint
-        (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_rope``.
+        ucod_vit_train_desc.allow_rope); a gated-MLP checkpoint (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``lora_cfg.allow_rope``.
         ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``.
-        ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (class docstring).  Opt-in: ``lora_cfg.allow_swiglu_out``.
-        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" (the engine as it is, bit for bit) or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``."""
+        ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``).
+        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``."""
         check_lora_bias(bias)
         canon = normalize_state_dict(state_dict)
         if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
             raise ValueError("allow_swiglu_out=True needs allow_out=True and allow_swiglu=True" + (", and allow_rope=True on a DINOv3 checkpoint" if canon.get("rope") else ""))
-        mlp_kind = "swiglu" if canon.get("mlp") == "swiglu" else "gelu"
-        so = {"allow_swiglu_out": True, "hidden": canon["layers"][0]["fc1_w"].shape[0] // 2} if allow_swiglu_out and mlp_kind == "swiglu" else {}
         if canon.get("rope") and not allow_rope:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a DINOv3 checkpoint (rotary position embedding, RoPE: the passes rotate q / k and "
                                       "rotate dq / dk back) only with allow_rope=True")
-        self.allow_rope = bool(allow_rope)
+        self.allow_rope, self.allow_out, self.allow_swiglu_out = bool(allow_rope), bool(allow_out), bool(allow_swiglu_out)
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
-        if canon.get("rope"):
-            # the checkpoint's own names: layer path, module path below it, leaf names (what lora_state_dict, the merges and the adapter folder use)
-            self._layer_path = _dinov3_paths(state_dict)[1]
-            self._qkv_names, self._qkv_dir = _QKV3, "attention."
-            self._out_paths, out_leaves = ("attention.o_proj", "mlp.down_proj"), _OUT3
-            hit = lora_targets_dinov3(target_modules, mlp_kind == "swiglu", len(canon["layers"]), self._layer_path, **({"allow_out": True} if allow_out else {}), **so)
-            (self.targets, out_hit), self.mlp_target = (hit if allow_out else (hit, ())), None
-        else:
-            self._layer_path, self._qkv_names, self._qkv_dir = "encoder.layer.", _QKV, "attention.attention."
-            self._out_paths, out_leaves = ("attention.output.dense", "mlp.fc2"), _OUT
-            if allow_swiglu_out and mlp_kind == "swiglu":          # (Dinov2SwiGLUFFN names its output projection weights_out)
-                self._out_paths, out_leaves = ("attention.output.dense", "mlp.weights_out"), ("dense", "weights_out")
-            hit = lora_targets(target_modules, mlp_kind, len(canon["layers"]), **({"allow_out": True} if allow_out else {}), **so)
-            self.targets, self.mlp_target, out_hit = hit if allow_out else hit + ((),)
-        self.allow_out, self.allow_swiglu_out = bool(allow_out), bool(allow_swiglu_out)
-        self.out_targets = tuple(leaf in out_hit for leaf in out_leaves)          # (attention output projection, MLP output projection)
-        self._F0 = canon["layers"][0]["fc1_w"].shape[0] // (2 if mlp_kind == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
-        if mlp_kind == "swiglu" and not allow_swiglu:
+        self._adopt(*lora_layout(state_dict, r, target_modules, bias, allow_out, allow_swiglu_out, canon=canon), bias)
+        if canon.get("mlp") == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
                                       "allow_swiglu=True (models/modules/full_model.py: load_lora passes it); the frozen-backbone engines (ViTEngine / "
                                       "SplitViTEngine) take it as it is")
@@ -1082,45 +1177,39 @@ class ViTLoRAEngine(ViTEngine):
                              f"(include/ucod_dpl.h, ucod_layernorm_lora)")
         self.r, self.scaling = int(r), float(lora_alpha) / float(r)
         D, L, dev = self.D, self.L, self.device
-        self.N1 = (2 if self.mlp == N.UCOD_MLP_SWIGLU else 1) * self.F          # rows of fc1 / of the padded, interleaved weights_in
-        if self.mlp_target is not None:
+        mlp_in, outs = self.modules[_MLP_IN], self.modules[_ATTN_OUT:]
+        if mlp_in.targeted:
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with the MLP input projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its gradient kernel keeps a "
                                  f"lane's B values and accumulators in registers)")
-            if self.lib.ucod_lora_mlp_grad_workspace_bytes(self.N1, D) == 0:
-                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= 8192 rows of {self.mlp_target}")
-        self.qkv_numel = 6 * r * D
-        numel = self.qkv_numel + (r * (D + self.N1) if self.mlp_target is not None else 0)
-        self.out_off = [None, None]                     # where [A | B] of each targeted output module starts in a layer's arena row
-        for m, K in enumerate((D, self.F)):
-            if not self.out_targets[m]:
+            if self.lib.ucod_lora_mlp_grad_workspace_bytes(mlp_in.n, D) == 0:
+                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {mlp_in.n} <= 8192 rows of {mlp_in.leaf}")
+        for m in outs:
+            if not m.targeted:
                 continue
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with an output projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its kernels keep u and t {N.LORA_OUT_W} wide)")
-            if self.lib.ucod_lora_out_grad_workspace_bytes(r, K, D) == 0:
-                if m == 1 and self.mlp == N.UCOD_MLP_SWIGLU:
-                    raise NotImplementedError(f"LoRA on the SwiGLU MLP's output projection is not built for this hidden width: K = {K} is beyond the kernels' "
+            if self.lib.ucod_lora_out_grad_workspace_bytes(r, m.k, D) == 0:
+                if m is outs[1] and self._out_flags:
+                    raise NotImplementedError(f"LoRA on the SwiGLU MLP's output projection is not built for this hidden width: K = {m.k} is beyond the kernels' "
                                               f"K <= 4096 (a thread keeps the A values of its hidden units in registers); D = {D} must be <= 1536")
-                raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {K}")
-            self.out_off[m], numel = numel, numel + r * (K + D)
-        # (the flags word of the passes: set only with the SwiGLU MLP's output projection targeted)
-        self._out_flags = N.LORA_OUT_SWIGLU if self.out_targets[1] and self.mlp == N.UCOD_MLP_SWIGLU else 0
-        if bias == "lora_only":                         # (behind everything else: an engine without trained biases keeps its row to the last element)
-            numel = self._setup_bias(state_dict, numel)
-        self.lora = torch.zeros(L, numel, dtype=torch.float32, device=dev)
-        bound = 1.0 / math.sqrt(D)                      # kaiming_uniform_(a=sqrt(5)) on [r, D]: U(-1/sqrt(fan_in), 1/sqrt(fan_in))
+                raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {m.k}")
+        if self.bias_numel:
+            self._setup_bias()
+        self.lora = torch.zeros(L, self.numel, dtype=torch.float32, device=dev)
+        # A: kaiming_uniform_(a=sqrt(5)) on [r, fan_in] = U(-1/sqrt(fan_in), 1/sqrt(fan_in)), B zeros.  q / k / v are drawn as one tensor whether targeted or not (an
+        # untargeted projection keeps A = B = 0), then the MLP input, then the output modules: an engine without the later ones keeps its stream.
+        bound = 1.0 / math.sqrt(D)
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
-        for p in range(3):
-            if self.targets[p]:                         # (an untargeted projection keeps A = B = 0; the draws are made all the same)
-                self.lora[:, p * 2 * r * D:p * 2 * r * D + r * D] = a[:, p].to(dev)
-        if self.mlp_target is not None:                 # drawn after q / k / v: the default engine's stream is untouched
-            self.lora[:, self.qkv_numel:self.qkv_numel + r * D] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
-        for m, K in enumerate((D, self.F)):             # drawn after everything else: every engine without them keeps its stream (A: U(+-1/sqrt(fan_in)), B zeros)
-            if self.out_targets[m] and m == 1 and self._F0 != K:  # (SwiGLU, padded: fan_in is the checkpoint's own width F0, the padded columns stay zero)
-                a2 = (torch.rand(L, r, self._F0, generator=generator) * 2 - 1) / math.sqrt(self._F0)
-                self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = torch.nn.functional.pad(a2, (0, K - self._F0)).reshape(L, r * K).to(dev)
-            elif self.out_targets[m]:
-                self.lora[:, self.out_off[m]:self.out_off[m] + r * K] = ((torch.rand(L, r * K, generator=generator) * 2 - 1) / math.sqrt(K)).to(dev)
+        for p, m in enumerate(self.modules[:_MLP_IN]):
+            if m.targeted:
+                self.lora[:, m.a] = a[:, p].to(dev)
+        if mlp_in.targeted:
+            self.lora[:, mlp_in.a] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
+        for m in outs:
+            if m.targeted:                              # (SwiGLU, padded: fan_in is the checkpoint's own width F0, the padded columns stay zero)
+                a = (torch.rand(L, r, m.k_hf, generator=generator) * 2 - 1) / math.sqrt(m.k_hf)
+                self.lora[:, m.a] = m.a_from_hf(a).reshape(L, r * m.k).to(dev)
         self._bias_init_arena()
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
@@ -1133,9 +1222,9 @@ class ViTLoRAEngine(ViTEngine):
             # (SwiGLU: fc1_w is the padded, interleaved weights_in [2F, D] -- its transpose's K order is the column order of the pre-activation's cotangent)
             self.train_layers.append([w_aug, wt_aug] + [l[w].t().contiguous() for w in (N.PROJ_W, N.FC1_W, N.FC2_W)])
         self.mlp_layers = []                            # native.VIT_TRAIN_MLP_SLOTS without the two LoRA slots: the augmented fc1 / weights_in weight
-        if self.mlp_target is not None:
+        if mlp_in.targeted:
             for l in self.layers:
-                w_aug = torch.zeros(self.N1, D + A, dtype=torch.bfloat16, device=dev)
+                w_aug = torch.zeros(mlp_in.n, D + A, dtype=torch.bfloat16, device=dev)
                 w_aug[:, :D] = l[N.FC1_W]
                 self.mlp_layers.append([w_aug])
         self.train_streams = 2                          # image-parallel sub-batches of the training passes (_chunks)
@@ -1143,86 +1232,55 @@ class ViTLoRAEngine(ViTEngine):
         self._saved_for = None
         self.repack()
 
-    # ---- parameters -------------------------------------------------------------------------------------------------
-    def _slices(self, p):
-        rD = self.r * self.D
-        return slice(p * 2 * rD, p * 2 * rD + rD), slice(p * 2 * rD + rD, (p + 1) * 2 * rD)
+    # ---- the module table and what is read from it -----------------------------------------------------------------------
+    def _adopt(self, layer_path, modules, bias="none"):
+        """Take a module table (``lora_layout``; host only).  Whatever the engine knows of its modules it reads from ``self.modules``; the attributes below are plain
+        values derived from it here, once, for the passes and for callers that read them."""
+        mods = self.modules = tuple(modules)
+        self._layer_path, self.bias, self._bias_flat = layer_path, bias, None
+        self.numel = lora_row_numel(mods)
+        self.targets = tuple(m.targeted for m in mods[:_MLP_IN])                 # (query, key, value)
+        self.mlp_target = mods[_MLP_IN].leaf if mods[_MLP_IN].targeted else None
+        self.out_targets = tuple(m.targeted for m in mods[_ATTN_OUT:])           # (attention output projection, MLP output projection)
+        self.qkv_numel = mods[_V].b.stop
+        self.out_off = [m.a.start if m.targeted else None for m in mods[_ATTN_OUT:]]
+        self.bias_off = tuple(m.bias_off for m in mods)
+        self.bias_numel = sum(m.n for m in mods if m.bias_off is not None)
+        self.N1, self._F0 = mods[_MLP_IN].n, mods[_MLP_OUT].k_hf                 # rows of the MLP input weight in the engine; the checkpoint's own hidden width
+        # (the flags word of the passes: set only with the SwiGLU MLP's output projection targeted)
+        self._out_flags = N.LORA_OUT_SWIGLU if mods[_MLP_OUT].targeted and mods[_MLP_IN].interleaved else 0
+
+    def _slices(self, j):
+        """(A, B) of module ``j`` in one layer's arena row."""
+        return self.modules[j].a, self.modules[j].b
 
     def _mlp_slices(self):
-        """(A_m, B_m) of one layer's arena row."""
-        rD = self.r * self.D
-        return slice(self.qkv_numel, self.qkv_numel + rD), slice(self.qkv_numel + rD, self.qkv_numel + rD + self.N1 * self.r)
+        return self._slices(_MLP_IN)
 
     def _out_slices(self, m):
-        """(A, B) of output module ``m`` (0 = attention output projection [r, D], 1 = MLP output projection [r, F]; B is [D, r]) in one layer's arena row."""
-        o, rK = self.out_off[m], self.r * (self.D, self.F)[m]
-        return slice(o, o + rK), slice(o + rK, o + rK + self.D * self.r)
+        """... of output module ``m`` (0 = attention output projection, 1 = MLP output projection)"""
+        return self._slices(_ATTN_OUT + m)
 
-    def _out_width(self, m):
-        """Input width of output module ``m`` as the checkpoint has it: D, or the MLP's own hidden width F0 (SwiGLU: before padding; otherwise F0 = F)."""
-        return (self.D, self._F0)[m]
+    def _targeted(self):
+        """(path below ``{layer path}{i}.``, table entry) of every targeted module"""
+        return [(m.path, m) for m in self.modules if m.targeted]
 
     # ---- trained biases (bias="lora_only") ----------------------------------------------------------------------------
-    def _bias_modules(self):
-        """The module path below ``{layer path}{i}.`` of each of the six bias slots (q, k, v, MLP input, attention output, MLP output), None where the module is
-        not targeted."""
-        mods = [f"{self._qkv_dir}{name}" if self.targets[p] else None for p, name in enumerate(self._qkv_names)]
-        mods.append(f"mlp.{self.mlp_target}" if self.mlp_target is not None else None)
-        return mods + [path if self.out_targets[m] else None for m, path in enumerate(self._out_paths)]
-
-    def _bias_layout(self, state_dict, numel):
-        """bias="lora_only" (host only): give every targeted module that has a bias in the checkpoint a slot behind the row's ``numel`` elements, in the order q, k, v,
-        MLP input, attention output, MLP output (``bias_off``; None = no parameter), and fix the columns of ``_bias_flat``.  Returns the new row length."""
-        D = self.D
-        try:
-            pref = self._hf_prefix(state_dict)
-        except NotImplementedError:                     # (a layout without HF module names: every Linear of it has a bias)
-            pref = None
-        self._bias_sizes = (D, D, D, self.N1, D, D)
-        self._bias_cols = (0, D, 2 * D, 3 * D, 3 * D + self.N1, 4 * D + self.N1)
-        off = []
-        for mod, n in zip(self._bias_modules(), self._bias_sizes):
-            has = mod is not None and (pref is None or f"{pref}0.{mod}.bias" in state_dict)     # (DINOv3 k_proj: key_bias = False, no parameter to train)
-            off.append(numel if has else None)
-            numel += n if has else 0
-        self.bias, self.bias_off = "lora_only", tuple(off)
-        self.bias_numel = sum(n for n, o in zip(self._bias_sizes, off) if o is not None)
-        return numel
-
-    def _setup_bias(self, state_dict, numel):
-        """``_bias_layout``, then this engine's bias vectors move into one private buffer ``_bias_flat`` [L, 3D + N1 + D + D] (q | k | v | m | o | 2) that the rows
+    def _setup_bias(self):
+        """This engine's bias vectors move into one private buffer ``_bias_flat`` [L, 3D + N1 + D + D] (q | k | v | m | o | 2: ``LoRAModule.bias_cols``) that the rows
         of ``self.layers`` view -- so that ``repack`` is one strided copy per module and no tensor is shared with the checkpoint or a clone."""
-        numel = self._bias_layout(state_dict, numel)
-        if self.bias_numel:
-            flat = torch.empty(self.L, 5 * self.D + self.N1, dtype=torch.float32, device=self.device)
-            for i, row in enumerate(self.layers):
-                flat[i] = torch.cat((row[N.QKV_B], row[N.FC1_B], row[N.PROJ_B], row[N.FC2_B]))
-            self._bias_flat = flat
-            self._link_bias()
-        return numel
-
-    def _bias_init_arena(self):
-        """Trained biases start at the checkpoint's values; a slot that cannot receive a gradient (``_bias_frozen``) stays zero."""
-        for j, o in enumerate(self.bias_off):
-            if o is not None:
-                c, n, Lj = self._bias_cols[j], self._bias_sizes[j], (self.L if j == _BIAS_K else self.L - 1)
-                self.lora[:Lj, o:o + n] = self._bias_flat[:Lj, c:c + n]
-                self.lora[Lj:, o:o + n] = 0.0
-
-    def _repack_bias(self):
-        """arena -> the engine's own bias vectors, one strided copy per trained module (frozen slots keep the checkpoint's value: ``_bias_frozen``)"""
-        for j, o in enumerate(self.bias_off):
-            if o is not None:
-                c, n, Lj = self._bias_cols[j], self._bias_sizes[j], (self.L if j == _BIAS_K else self.L - 1)
-                self._bias_flat[:Lj, c:c + n].copy_(self.lora[:Lj, o:o + n])
+        slots = dict.fromkeys(m.b_slot for m in self.modules)
+        self._bias_flat = torch.stack([torch.cat([row[s] for s in slots]) for row in self.layers])
+        self._link_bias()
 
     def _link_bias(self):
         """Point the bias slots of ``self.layers`` (a private list of rows) at ``_bias_flat``."""
-        D, c = self.D, self._bias_cols
         rows = []
-        for i, row in enumerate(self.layers):
-            row, f = list(row), self._bias_flat[i]
-            row[N.QKV_B], row[N.FC1_B], row[N.PROJ_B], row[N.FC2_B] = f[:3 * D], f[c[_BIAS_M]:c[_BIAS_O]], f[c[_BIAS_O]:c[_BIAS_2]], f[c[_BIAS_2]:]
+        for row, f in zip(self.layers, self._bias_flat):
+            row = list(row)
+            for s in dict.fromkeys(m.b_slot for m in self.modules):
+                cols = [m.bias_cols for m in self.modules if m.b_slot == s]
+                row[s] = f[cols[0].start:cols[-1].stop]
             rows.append(row)
         self.layers = rows
 
@@ -1230,28 +1288,29 @@ class ViTLoRAEngine(ViTEngine):
         """True for a bias slot that cannot receive a gradient: every bias of the last layer but the key's (only the key projection reaches the key map).  torch's
         AdamW skips such a parameter (its grad is None); the flat arena would decay it by lr * wd per step, so its arena slot holds zeros -- an exact zero stays at
         zero -- and every reader takes the engine's own copy, which holds the checkpoint's value."""
-        return i == self.L - 1 and j != _BIAS_K
+        return i == self.L - 1 and j != _K
+
+    def _bias_live(self):
+        """(module, its arena columns, the layers below the frozen ones) of every trained bias"""
+        return [(m, slice(m.bias_off, m.bias_off + m.n), self.L if j == _K else self.L - 1) for j, m in enumerate(self.modules) if m.bias_off is not None]
+
+    def _bias_init_arena(self):
+        """Trained biases start at the checkpoint's values; a slot that cannot receive a gradient (``_bias_frozen``) stays zero."""
+        for m, o, Lj in self._bias_live():
+            self.lora[:Lj, o] = self._bias_flat[:Lj, m.bias_cols]
+            self.lora[Lj:, o] = 0.0
+
+    def _repack_bias(self):
+        """arena -> the engine's own bias vectors, one strided copy per trained module (frozen slots keep the checkpoint's value: ``_bias_frozen``)"""
+        for m, o, Lj in self._bias_live():
+            self._bias_flat[:Lj, m.bias_cols].copy_(self.lora[:Lj, o])
 
     def _bias_value(self, i, j, src=None):
-        """The bias of slot ``j`` in layer ``i`` as the engine orders it: from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
-        c, n, o = self._bias_cols[j], self._bias_sizes[j], self.bias_off[j]
+        """The bias of module ``j`` in layer ``i`` as the engine orders it: from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
+        m = self.modules[j]
         if self._bias_frozen(i, j):
-            return self._bias_flat[i, c:c + n]
-        return (self.lora if src is None else src)[i, o:o + n]
-
-    def _bias_to_hf(self, j, v):
-        """engine order -> the checkpoint's (SwiGLU weights_in: padded and interleaved -> HF rows, unpadded)"""
-        if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU:
-            return lora_b_from_engine(v.reshape(self.N1, 1), self._F0).reshape(-1)
-        return v.clone()
-
-    def _bias_from_hf(self, j, v, name):
-        n0 = 2 * self._F0 if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU else self._bias_sizes[j]
-        if tuple(v.shape) != (n0,):
-            raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(n0,)}")
-        if j == _BIAS_M and self.mlp == N.UCOD_MLP_SWIGLU:
-            return lora_b_to_engine(v.reshape(-1, 1)).reshape(-1)
-        return v
+            return self._bias_flat[i, m.bias_cols]
+        return (self.lora if src is None else src)[i, m.bias_off:m.bias_off + m.n]
 
     def _bias_table(self, grad):
         """The bias table of the backward (native.VIT_TRAIN_BIAS_SLOTS: gradient destinations in ``grad`` [L, P]; NULL = not trained), or None without one."""
@@ -1262,78 +1321,52 @@ class ViTLoRAEngine(ViTEngine):
             ptrs += [None if o is None else grad[i, o:].data_ptr() for o in self.bias_off]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
+    # ---- state dicts ------------------------------------------------------------------------------------------------------
     def lora_state_dict(self, grads=False, prefix=None):
-        """peft-style names of the targeted modules: encoder.layer.{i}.attention.attention.{query,key,value}.lora_{A,B}.weight and, with the MLP input
-        projection targeted, encoder.layer.{i}.mlp.{fc1,weights_in}.lora_{A,B}.weight -- B of weights_in [2 hidden, r] in HF row order, unpadded.  A DINOv3
-        checkpoint: {model.,}layer.{i}.attention.{q,k,v}_proj.lora_{A,B}.weight, the checkpoint's own layer path.  ``prefix`` replaces the layer path."""
+        """peft-style names of the targeted modules, ``{layer path}{i}.{module path}.lora_{A,B}.weight`` in table order (class docstring), in HF's shapes: B of a SwiGLU
+        ``weights_in`` [2 hidden, r] in HF row order, unpadded; A of a SwiGLU ``weights_out`` [r, hidden] without the padded columns.  Behind a layer's matrices, the
+        trained biases (bias="lora_only") as ``{module path}.bias``: a frozen slot reads as the checkpoint's value, its gradient as zero.  ``prefix`` replaces the
+        layer path."""
         prefix = self._layer_path if prefix is None else prefix
         src = self.lora_grad if grads else self.lora
         out = {}
         for i in range(self.L):
-            for p, name in enumerate(self._qkv_names):
-                if not self.targets[p]:
-                    continue
-                sa, sb = self._slices(p)
-                base = f"{prefix}{i}.{self._qkv_dir}{name}."
-                out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
-                out[base + "lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
-            if self.mlp_target is not None:
-                sa, sb = self._mlp_slices()
-                base = f"{prefix}{i}.mlp.{self.mlp_target}."
-                b = src[i, sb].reshape(self.N1, self.r)
-                out[base + "lora_A.weight"] = src[i, sa].reshape(self.r, self.D).clone()
-                out[base + "lora_B.weight"] = lora_b_from_engine(b, self._F0) if self.mlp == N.UCOD_MLP_SWIGLU else b.clone()
-            for m, path in enumerate(self._out_paths):
-                if self.out_targets[m]:
-                    sa, sb = self._out_slices(m)
-                    out[f"{prefix}{i}.{path}.lora_A.weight"] = src[i, sa].reshape(self.r, -1)[:, :self._out_width(m)].clone()      # (padded columns dropped)
-                    out[f"{prefix}{i}.{path}.lora_B.weight"] = src[i, sb].reshape(self.D, self.r).clone()
-            for j, mod in enumerate(self._bias_modules()):          # bias="lora_only": the trained biases, HF order (a frozen slot: the checkpoint's value, gradient zero)
-                if self.bias_off[j] is not None:
-                    v = torch.zeros(self._bias_sizes[j], device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
-                    out[f"{prefix}{i}.{mod}.bias"] = self._bias_to_hf(j, v)
+            for path, m in self._targeted():
+                out[f"{prefix}{i}.{path}.lora_A.weight"] = m.a_to_hf(src[i, m.a].reshape(self.r, m.k)).clone()
+                out[f"{prefix}{i}.{path}.lora_B.weight"] = m.rows_to_hf(src[i, m.b].reshape(m.n, self.r)).clone()
+            for j, m in enumerate(self.modules):
+                if m.bias_off is not None:
+                    v = torch.zeros(m.n, device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
+                    out[f"{prefix}{i}.{m.path}.bias"] = m.rows_to_hf(v.reshape(-1, 1)).reshape(-1).clone()
         return out
 
     def load_lora_state_dict(self, sd, prefix=None):
-        """The inverse of ``lora_state_dict``.  A LoRA key of a module this engine does not target is refused (its matrices are held at zero)."""
+        """The inverse of ``lora_state_dict``.  A LoRA key of a module this engine does not target is refused (its matrices are held at zero), and so is a tensor
+        that does not have HF's shape (a padded or transposed one would load without a sound)."""
         prefix = self._layer_path if prefix is None else prefix
-        names = [f"{self._qkv_dir}{name}." for p, name in enumerate(self._qkv_names) if self.targets[p]]
-        names += [f"mlp.{self.mlp_target}."] if self.mlp_target is not None else []
-        names += [path + "." for m, path in enumerate(self._out_paths) if self.out_targets[m]]
-        want = {f"{prefix}{i}.{n}lora_{ab}.weight" for i in range(self.L) for n in names for ab in "AB"}
+        mods = self._targeted()
+        want = {f"{prefix}{i}.{path}.lora_{ab}.weight" for i in range(self.L) for path, _ in mods for ab in "AB"}
         extra = sorted(k for k in sd if ".lora_" in k and k.startswith(prefix) and k not in want)
         if extra:
-            raise KeyError(f"LoRA matrices of modules this engine does not target ({', '.join(n.rstrip('.').rsplit('.', 1)[-1] for n in names)} are): {extra[:4]}"
+            raise KeyError(f"LoRA matrices of modules this engine does not target ({', '.join(m.leaf for _, m in mods)} are): {extra[:4]}"
                            + (" ..." if len(extra) > 4 else ""))
         take = lambda k: sd[k].to(self.device, torch.float32)  # noqa: E731
         for i in range(self.L):
-            for p, name in enumerate(self._qkv_names):
-                if not self.targets[p]:
-                    continue
-                sa, sb = self._slices(p)
-                base = f"{prefix}{i}.{self._qkv_dir}{name}."
-                self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
-                self.lora[i, sb] = take(base + "lora_B.weight").reshape(-1)
-            if self.mlp_target is not None:
-                sa, sb = self._mlp_slices()
-                base = f"{prefix}{i}.mlp.{self.mlp_target}."
-                b = take(base + "lora_B.weight")
-                if tuple(b.shape) != ((2 if self.mlp == N.UCOD_MLP_SWIGLU else 1) * self._F0, self.r):
-                    raise ValueError(f"{base}lora_B.weight has shape {tuple(b.shape)}")
-                self.lora[i, sa] = take(base + "lora_A.weight").reshape(-1)
-                self.lora[i, sb] = (lora_b_to_engine(b) if self.mlp == N.UCOD_MLP_SWIGLU else b).reshape(-1)
-            for m, path in enumerate(self._out_paths):
-                if self.out_targets[m]:
-                    sa, sb = self._out_slices(m)
-                    a, b = take(f"{prefix}{i}.{path}.lora_A.weight"), take(f"{prefix}{i}.{path}.lora_B.weight")
-                    if tuple(a.shape) != (self.r, self._out_width(m)) or tuple(b.shape) != (self.D, self.r):
-                        raise ValueError(f"{prefix}{i}.{path}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
-                    a = torch.nn.functional.pad(a, (0, (self.D, self.F)[m] - a.shape[1]))      # (SwiGLU: the padded hidden units' columns load as zeros)
-                    self.lora[i, sa], self.lora[i, sb] = a.reshape(-1), b.reshape(-1)
-            for j, mod in enumerate(self._bias_modules()):
-                if self.bias_off[j] is not None:
-                    name = f"{prefix}{i}.{mod}.bias"
-                    self._bias_value(i, j).copy_(self._bias_from_hf(j, take(name), name))       # (a frozen slot: into the engine's own copy; its arena slot stays zero)
+            for path, m in mods:
+                base = f"{prefix}{i}.{path}"
+                a, b = take(base + ".lora_A.weight"), take(base + ".lora_B.weight")
+                if m is self.modules[_MLP_IN] and tuple(b.shape) != (m.n_hf, self.r):       # (the text this refusal has always had)
+                    raise ValueError(f"{base}.lora_B.weight has shape {tuple(b.shape)}")
+                if tuple(a.shape) != (self.r, m.k_hf) or tuple(b.shape) != (m.n_hf, self.r):
+                    raise ValueError(f"{base}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
+                self.lora[i, m.a], self.lora[i, m.b] = m.a_from_hf(a).reshape(-1), m.rows_from_hf(b).reshape(-1)      # (padded units load as zeros)
+            for j, m in enumerate(self.modules):
+                if m.bias_off is not None:
+                    name = f"{prefix}{i}.{m.path}.bias"
+                    v = take(name)
+                    if tuple(v.shape) != (m.n_hf,):
+                        raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(m.n_hf,)}")
+                    self._bias_value(i, j).copy_(m.rows_from_hf(v.reshape(-1, 1)).reshape(-1))       # (a frozen slot: into the engine's own copy; its arena slot stays zero)
         self.repack()
 
     def train(self, mode=True):
@@ -1504,24 +1537,7 @@ class ViTLoRAEngine(ViTEngine):
         return self.lora_grad
 
     # ---- merging: the way out of LoRA mode ---------------------------------------------------------------------------
-    def _targeted(self):
-        """(module name below the layer path ``encoder.layer.{i}.``, its index among query / key / value or None for the MLP input projection) of every targeted module"""
-        mods = [(f"{self._qkv_dir}{name}", p) for p, name in enumerate(self._qkv_names) if self.targets[p]]
-        mods += [(f"mlp.{self.mlp_target}", None)] if self.mlp_target is not None else []
-        return mods + [(path, ("out", m)) for m, path in enumerate(self._out_paths) if self.out_targets[m]]     # (an output projection: ("out", 0 or 1))
-
-    @staticmethod
-    def _hf_prefix(sd):
-        """What stands in front of the layer path in ``sd``'s names, with that path: ``encoder.layer.`` behind "", "dinov2." or "vit."; a DINOv3 state dict's
-        own ``{model.,}layer.``."""
-        if is_dinov3(sd):
-            pref, lay = _dinov3_paths(sd)
-            return pref + lay
-        for pref in ("", "dinov2.", "vit."):
-            if pref + "encoder.layer.0.attention.attention.query.weight" in sd:
-                return pref + "encoder.layer."
-        raise NotImplementedError("merging takes a HuggingFace DINOv2 state dict (encoder.layer.{i}.attention.attention.{query,key,value}): the names "
-                                  "target_modules are matched against")
+    _hf_prefix = staticmethod(_hf_prefix)
 
     def _stage(self, numel):
         """The reusable f32 staging buffer, at least ``numel`` elements."""
@@ -1529,54 +1545,51 @@ class ViTLoRAEngine(ViTEngine):
             self._merge_buf = torch.empty(numel, dtype=torch.float32, device=self.device)
         return self._merge_buf
 
+    def _stage_weight(self, key, w, m, engine_rows):
+        """Stage the f32 base weight ``w`` [n_hf, k_hf] of module ``m`` at the engine's width k (zero columns for the padded hidden units: the merge kernel wants
+        K % 64 == 0, A's padded columns are zeros, the first k_hf columns are the HF weight) and, with ``engine_rows``, in the engine's row order.  Returns
+        (the staged weight, the buffer of its shape that the merge writes)."""
+        if tuple(w.shape) != (m.n_hf, m.k_hf):
+            raise ValueError(f"{key} has shape {tuple(w.shape)}, expected {(m.n_hf, m.k_hf)}")
+        gather = engine_rows and m.interleaved                     # SwiGLU weights_in: HF rows (+ one zero row for the padding), gathered into the engine's order
+        n, k, lead = (m.n if engine_rows else m.n_hf), m.k, ((m.n_hf + 1) * m.k if gather else 0)
+        buf = self._stage(lead + 2 * n * k)
+        w0, merged = buf[lead:lead + n * k].view(n, k), buf[lead + n * k:lead + 2 * n * k].view(n, k)
+        if gather:
+            hf = buf[:lead].view(m.n_hf + 1, k)
+            hf[:m.n_hf].copy_(w.detach())
+            hf[m.n_hf].zero_()
+            torch.index_select(hf, 0, self._engine_row_source(), out=w0)
+        else:
+            if m.k_hf != k:
+                w0.zero_()
+            w0[:, :m.k_hf].copy_(w.detach())
+        return w0, merged
+
     def _merge(self, lib, w0, A, B, out):
         n, k = w0.shape
         N.check(lib.ucod_lora_merge_f32(N.ptr(w0), A.data_ptr(), N.ptr(B), self.r, self.scaling, N.ptr(out), n, k, N.stream()), "ucod_lora_merge_f32")
 
     def merged_state_dict(self, base_state_dict=None):
         """peft's ``merge_and_unload()`` as a state dict: a copy of the HF-named base state dict (default: the one this engine was built from) in which ``weight``
-        of every targeted module is the merged f32 matrix  W + (lora_alpha / r) B A  (ucod_lora_merge_f32: f64 arithmetic, one rounding to f32); every other entry
-        is the same tensor.  Any frozen-backbone engine built from it runs the adapted model.  Merging is the eval-mode function: dropout plays no part.  A SwiGLU
-        checkpoint's ``weights_in`` is merged in HF row order, unpadded.  One module at a time through a reusable device buffer: stage, merge, copy back."""
+        of every targeted module is the merged f32 matrix  W + (lora_alpha / r) B A  (ucod_lora_merge_f32: f64 arithmetic, one rounding to f32) and, with
+        bias="lora_only", ``bias`` the trained one; every other entry is the same tensor.  Any frozen-backbone engine built from it runs the adapted model.  Merging is
+        the eval-mode function: dropout plays no part.  Everything is in HF's shapes and row order.  One module at a time through a reusable device buffer: stage,
+        merge, copy back."""
         base = self._base_sd if base_state_dict is None else base_state_dict
         pref = self._hf_prefix(base)
         out = dict(base)
-        swiglu = self.mlp == N.UCOD_MLP_SWIGLU
         for i in range(self.L):
-            for name, p in self._targeted():
-                key = f"{pref}{i}.{name}.weight"
+            for path, m in self._targeted():
+                key = f"{pref}{i}.{path}.weight"
                 w = base[key]
-                n, k = w.shape
-                kp = k                                             # the width the merge runs at
-                if isinstance(p, tuple):                           # an output projection: W [D, K], A [r, K], B [D, r]; neither padded nor reordered
-                    if (n, k) != (self.D, self._out_width(p[1])):
-                        raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine expects {(self.D, self._out_width(p[1]))}")
-                    sa, sb = self._out_slices(p[1])
-                    B = self.lora[i, sb]
-                    kp = (self.D, self.F)[p[1]]                    # (SwiGLU weights_out [D, F0]: merged at the padded width -- the kernel wants K % 64 == 0 and A's
-                                                                   #  padded columns are zeros --, the first F0 columns are the HF weight: the same sum per element)
-                elif k != self.D:
-                    raise ValueError(f"{key} has shape {tuple(w.shape)}, this engine has D = {self.D}")
-                elif p is not None:
-                    sa, sb = self._slices(p)
-                    B = self.lora[i, sb]
-                else:
-                    sa, sb = self._mlp_slices()
-                    B = self.lora[i, sb].reshape(self.N1, self.r)
-                    B = lora_b_from_engine(B, self._F0) if swiglu else B
-                if B.numel() != n * self.r:
-                    raise ValueError(f"{key} has {n} rows, the LoRA B matrix of this engine {B.numel() // self.r}")
-                buf = self._stage(2 * n * kp)
-                w0, merged = buf[:n * kp].view(n, kp), buf[n * kp:2 * n * kp].view(n, kp)
-                if kp != k:
-                    w0.zero_()
-                w0[:, :k].copy_(w.detach())
-                self._merge(self.lib, w0, self.lora[i, sa], B, merged)
-                out[key] = merged[:, :k].contiguous().to(w.device, copy=True)
-            for j, mod in enumerate(self._bias_modules()):          # bias="lora_only": merge_and_unload() leaves the trained bias in the base layer
-                if self.bias_off[j] is not None:
-                    key = f"{pref}{i}.{mod}.bias"
-                    out[key] = self._bias_to_hf(j, self._bias_value(i, j)).to(base[key].device, base[key].dtype)
+                w0, merged = self._stage_weight(key, w, m, engine_rows=False)
+                self._merge(self.lib, w0, self.lora[i, m.a], m.rows_to_hf(self.lora[i, m.b].reshape(m.n, self.r)), merged)
+                out[key] = merged[:, :m.k_hf].contiguous().to(w.device, copy=True)
+            for j, m in enumerate(self.modules):
+                if m.bias_off is not None:
+                    key = f"{pref}{i}.{m.path}.bias"
+                    out[key] = m.rows_to_hf(self._bias_value(i, j).reshape(-1, 1)).reshape(-1).to(base[key].device, base[key].dtype, copy=True)
         return out
 
     def _engine_row_source(self):
@@ -1592,10 +1605,11 @@ class ViTLoRAEngine(ViTEngine):
 
     def merge_into(self, engine):
         """Refresh a live ``ViTEngine`` of the same checkpoint IN PLACE with this engine's current LoRA matrices: for every targeted module of every layer the merged
-        f32 weight (from the f32 base weights, never from ``engine``'s current ones: refreshing after every optimiser step cannot drift) goes to a staging buffer and is
-        cast into the existing 16-bit tensor of ``engine.layers``; with ``engine.ln_fold`` it is also folded (ucod_fold_ln_linear) into the existing tensors of
-        ``engine.fold_layers``, with the Q-row pre-scale the engine was built with (``engine.q_row_scale``).  No tensor of ``engine`` is reallocated, untargeted tensors
-        (and the rows of untargeted projections in the fused QKV weight) are not written.  Runs on the current stream, ordered with ``engine``'s passes there."""
+        f32 weight (from the f32 base weights, never from ``engine``'s current ones: refreshing after every optimiser step cannot drift) is staged in the engine's
+        shape, merged and cast into the existing 16-bit tensor of ``engine.layers``; where a LayerNorm stands in front of the module and ``engine.ln_fold`` is on, it
+        is also folded (ucod_fold_ln_linear) into the existing tensors of ``engine.fold_layers``, with the Q-row pre-scale the engine was built with
+        (``engine.q_row_scale``).  No tensor of ``engine`` is reallocated, untargeted tensors (and the rows of untargeted projections in the fused QKV weight) are
+        not written.  Runs on the current stream, ordered with ``engine``'s passes there."""
         if isinstance(engine, SplitViTEngine):
             raise NotImplementedError("merge_into refreshes the 16-bit ViTEngine only; build a SplitViTEngine from merged_state_dict() (its operands are split "
                                       "per tensor with their own scales)")
@@ -1610,68 +1624,35 @@ class ViTLoRAEngine(ViTEngine):
             raise ValueError(f"merge_into: this engine has {self.R} register tokens, the other {engine.R}: they were not built from the same checkpoint")
         if engine.patch_w.device != self.lora.device:
             raise ValueError(f"merge_into: this engine is on {self.lora.device}, the other on {engine.patch_w.device}")
-        base, lib, D, r = self._base_sd, engine.lib, self.D, self.r
+        base, lib, st = self._base_sd, engine.lib, N.stream
         pref = self._hf_prefix(base)
-        swiglu = self.mlp == N.UCOD_MLP_SWIGLU
-        st = N.stream
         base_ptrs = {v.untyped_storage().data_ptr() for v in base.values() if torch.is_tensor(v) and v.is_cuda} if self.bias_numel else ()
         for i in range(self.L):
             row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
-            for j, o in enumerate(self.bias_off):                  # bias="lora_only": the trained biases into the live bias vectors first, so that the LayerNorm fold
-                if o is not None:                                  # below reads them (its folded bias is b' = q (W beta + b)); output projections have no fold
-                    slot, r0 = ((N.QKV_B, 0), (N.QKV_B, D), (N.QKV_B, 2 * D), (N.FC1_B, 0), (N.PROJ_B, 0), (N.FC2_B, 0))[j]
+            for j, m in enumerate(self.modules):                   # bias="lora_only": the trained biases into the live bias vectors first, so that the LayerNorm fold
+                if m.bias_off is not None:                         # below reads them (its folded bias is b' = q (W beta + b))
+                    slot = m.b_slot
                     if row[slot].untyped_storage().data_ptr() in base_ptrs:      # (an f32 state dict on the device: the engine's vector IS the checkpoint's -- the one
                         own = row[slot].clone()                                  #  case in which a tensor of ``engine`` is replaced, once, so that the base stays the base)
                         if fl is not None and fl[slot] is row[slot]:
                             fl[slot] = own
                         row[slot] = own
-                    row[slot][r0:r0 + self._bias_sizes[j]].copy_(self._bias_value(i, j))
-            for name, p in self._targeted():
-                w = base[f"{pref}{i}.{name}.weight"]
-                if isinstance(p, tuple):                           # an output projection: merged, cast into the live tensor; no LayerNorm stands in front of it, so no fold
-                    K, K0 = (D, self.F)[p[1]], self._out_width(p[1])
-                    if tuple(w.shape) != (D, K0):
-                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(D, K0)}")
-                    sa, sb = self._out_slices(p[1])
-                    buf = self._stage(2 * D * K)
-                    w0, merged = buf[:D * K].view(D, K), buf[D * K:2 * D * K].view(D, K)
-                    if K0 != K:                                    # (SwiGLU weights_out: the engine's tensor is zero-padded to [D, F]; A's padded columns are zeros)
-                        w0.zero_()
-                    w0[:, :K0].copy_(w.detach())
-                    self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
-                    N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), row[(N.PROJ_W, N.FC2_W)[p[1]]].data_ptr(), D * K, st()), "ucod_cast_f32_bf16")
-                    if p[1] == 1:
-                        engine.refresh_fc2_perm(i)                 # (the BLK16 copy of fc2 follows the plain one)
-                    continue
-                if p is not None:
-                    n, r0, (sa, sb) = D, p * D, self._slices(p)
-                    slot_w, slot_b, slot_c, g, be = N.QKV_W, N.QKV_B, N.QKV_COLSUM, row[N.LN1_G], row[N.LN1_B]
-                else:
-                    n, r0, (sa, sb) = self.N1, 0, self._mlp_slices()
-                    slot_w, slot_b, slot_c, g, be = N.FC1_W, N.FC1_B, N.FC1_COLSUM, row[N.LN2_G], row[N.LN2_B]
-                if p is None and swiglu:                         # stage HF rows (+ one zero row), gather them into the engine's row order
-                    n_hf = 2 * self._F0
-                    buf = self._stage((n_hf + 1 + 2 * n) * D)
-                    hf, rest = buf[:(n_hf + 1) * D].view(n_hf + 1, D), buf[(n_hf + 1) * D:]
-                    hf[:n_hf].copy_(w.detach())
-                    hf[n_hf].zero_()
-                    w0, merged = rest[:n * D].view(n, D), rest[n * D:2 * n * D].view(n, D)
-                    torch.index_select(hf, 0, self._engine_row_source(), out=w0)
-                else:
-                    if tuple(w.shape) != (n, D):
-                        raise ValueError(f"{pref}{i}.{name}.weight has shape {tuple(w.shape)}, expected {(n, D)}")
-                    buf = self._stage(2 * n * D)
-                    w0, merged = buf[:n * D].view(n, D), buf[n * D:2 * n * D].view(n, D)
-                    w0.copy_(w.detach())
-                self._merge(lib, w0, self.lora[i, sa], self.lora[i, sb], merged)
-                plain = row[slot_w]
-                N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), plain.data_ptr() + r0 * D * plain.element_size(), n * D, st()), "ucod_cast_f32_bf16")
-                if fl is not None:
-                    wf, bf, cs = fl[slot_w], fl[slot_b], fl[slot_c]
-                    q = engine.q_row_scale.data_ptr() + r0 * 4 if p is not None else None
-                    N.check(lib.ucod_fold_ln_linear(N.ptr(merged), N.ptr(g), N.ptr(be), row[slot_b].data_ptr() + r0 * 4, q, wf.data_ptr() + r0 * D * wf.element_size(),
-                                                    bf.data_ptr() + r0 * 4, cs.data_ptr() + r0 * 4, n, D, st()), "ucod_fold_ln_linear")
+                    row[slot][m.row0:m.row0 + m.n].copy_(self._bias_value(i, j))
+            for path, m in self._targeted():
+                key = f"{pref}{i}.{path}.weight"
+                w0, merged = self._stage_weight(key, base[key], m, engine_rows=True)
+                self._merge(lib, w0, self.lora[i, m.a], self.lora[i, m.b], merged)
+                n, k, r0, plain = m.n, m.k, m.row0, row[m.w_slot]
+                N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), plain.data_ptr() + r0 * k * plain.element_size(), n * k, st()), "ucod_cast_f32_bf16")
+                if m.w_slot == N.FC2_W:
+                    engine.refresh_fc2_perm(i)                     # (the BLK16 copy of fc2 follows the plain one)
+                if fl is not None and m.ln is not None:            # (no LayerNorm stands in front of an output projection: no fold)
+                    wf, bf, cs = fl[m.w_slot], fl[m.b_slot], fl[m.c_slot]
+                    q = engine.q_row_scale.data_ptr() + r0 * 4 if m.w_slot == N.QKV_W else None
+                    N.check(lib.ucod_fold_ln_linear(N.ptr(merged), N.ptr(row[m.ln[0]]), N.ptr(row[m.ln[1]]), row[m.b_slot].data_ptr() + r0 * 4, q,
+                                                    wf.data_ptr() + r0 * k * wf.element_size(), bf.data_ptr() + r0 * 4, cs.data_ptr() + r0 * 4, n, k, st()), "ucod_fold_ln_linear")
         return engine
+
 
     # ---- torch.autograd / nn.Module integration ----------------------------------------------------------------------
     def clone_for_ema(self):
