@@ -15,6 +15,7 @@ Pinned by tests/golden/g16_cod_metrics.npz (the real class on 18 seeded cases; t
 import numpy as np
 
 EPS = np.spacing(1)
+NEAREST_BLOCK = 2 ** 24                                   # (pixel, candidate) pairs nearest_foreground holds at a time (int64: 128 MiB each)
 
 
 def prepare(pred, gt):
@@ -128,15 +129,25 @@ def f_measure(p, g, beta=0.3):
 
 def nearest_foreground(g):
     """(distance, row index, col index) of the nearest True pixel for every pixel; ties: smallest column, then smallest row
-    (the observed behaviour of scipy.ndimage.distance_transform_edt(~g, return_indices=True))."""
+    (the observed behaviour of scipy.ndimage.distance_transform_edt(~g, return_indices=True)).
+
+    Brute force over (pixel, candidate) pairs, NEAREST_BLOCK pairs at a time so that memory stays bounded whatever the mask: a
+    foreground pixel is its own nearest (distance 0, no tie possible), so only the background pixels are searched, in raster-order
+    blocks of NEAREST_BLOCK // n_fg pixels against all candidates."""
     h, w = g.shape
     fr, fc = np.nonzero(g)
     order = np.lexsort((fr, fc))                          # candidates sorted by (col, row): argmin returns the first minimum
     fr, fc = fr[order], fc[order]
     yy, xx = np.mgrid[0:h, 0:w]
-    d2 = (yy[..., None] - fr) ** 2 + (xx[..., None] - fc) ** 2
-    k = d2.argmin(axis=-1)
-    return np.sqrt(d2.min(axis=-1).astype(np.float64)), fr[k], fc[k]
+    dist, ir, ic = np.zeros((h, w), np.float64), yy.copy(), xx.copy()
+    by, bx = np.nonzero(~g)
+    step = max(1, NEAREST_BLOCK // max(fr.size, 1))
+    for s in range(0, by.size if fr.size else 0, step):
+        y, x = by[s:s + step], bx[s:s + step]
+        d2 = (y[:, None] - fr) ** 2 + (x[:, None] - fc) ** 2
+        k = d2.argmin(axis=-1)
+        dist[y, x], ir[y, x], ic[y, x] = np.sqrt(d2[np.arange(y.size), k].astype(np.float64)), fr[k], fc[k]
+    return dist, ir, ic
 
 
 def gauss7():

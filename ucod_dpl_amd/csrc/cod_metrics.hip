@@ -9,9 +9,13 @@
 //
 // Passes (1024-thread workgroups over up to 64 pixel chunks per image, chunk partials combined in chunk order):
 //   1  min / max of prediction and ground truth (the min-max normalisation of _prepare_data :125-133);
-//   2  sums over pixels of everything that needs only p and g: MAE, ACC, IoU, the object-similarity moments, the centroid, and the
-//      two 256-bin histograms of uint8(p * 255) inside / outside the ground truth (integer LDS atomics);
-//   3  (needs the mean of p and the centroid) adaptive-threshold counts and the raw moments of the four S-measure quadrants;
+//   2  sums over pixels of everything that needs only p and g: MAE, ACC, IoU, the object-similarity sums (p inside, 1 - p outside
+//      the ground truth), the centroid, and the two 256-bin histograms of uint8(p * 255) inside / outside the ground truth
+//      (integer LDS atomics);
+//   3  (needs the sums of pass 2) adaptive-threshold counts; the object-similarity squared deviations about the two means of pass 2
+//      (the two-pass sample variance of the reference's std(ddof=1): a sum of squares, never negative, 0 over a flat region); the
+//      moments of the four S-measure quadrants, taken about each quadrant's own first pixel (quad_shift) so that the one-pass
+//      variance cancels nothing over a flat quadrant and loses ~1e-16 absolute, not relative to the mean square, elsewhere;
 //   4a per row: nearest foreground column to the left / right of every pixel;  4b per pixel: exact Euclidean distance to the nearest
 //      foreground pixel by walking rows outward (ties: smallest column, then smallest row -- what
 //      scipy.ndimage.distance_transform_edt(return_indices=True) returns) and the error |p - g| at that pixel;
@@ -25,7 +29,7 @@ namespace ucod {
 namespace {
 
 constexpr double EPS = 2.220446049250313e-16;            // np.spacing(1)
-constexpr int NS2 = 12, NS3 = 18;                        // doubles reduced by pass 2 / pass 3
+constexpr int NS2 = 10, NS3 = 20;                        // doubles reduced by pass 2 / pass 3 (cod_combine_kernel: at most 32)
 
 struct Norm {                                            // _prepare_data: how to turn the raw inputs into p (float64) and g (bool)
   double pmin, pden;                                     // p = (v - pmin) / pden, a true division as in the reference (not a reciprocal multiply)
@@ -131,8 +135,8 @@ __global__ __launch_bounds__(1024) void cod_pass2_kernel(const float* __restrict
     s[3] += (p == gf) ? 1.0 : 0.0;
     s[4] += (p != 0.0 && g) ? 1.0 : 0.0;
     s[5] += (p != 0.0 || g) ? 1.0 : 0.0;
-    if (g) { s[6] += p; s[7] += p * p; s[10] += (double)(i / W); s[11] += (double)(i % W); }
-    else { const double q = 1.0 - p; s[8] += q; s[9] += q * q; }
+    if (g) { s[6] += p; s[8] += (double)(i / W); s[9] += (double)(i % W); }
+    else s[7] += 1.0 - p;
     atomicAdd(&h[(g ? 0 : 256) + (int)(unsigned char)(p * 255.0)], 1u);
   }
   block_reduce<NS2>(s, red, S2 + ((size_t)b * gridDim.x + blockIdx.x) * NS2);
@@ -143,7 +147,15 @@ __global__ __launch_bounds__(1024) void cod_pass2_kernel(const float* __restrict
 // centroid of the ground truth (:259-268): np.round is round-half-even; an empty mask takes the image centre
 __device__ __forceinline__ void centroid(const double* S2, int H, int W, int& cx, int& cy) {
   if (S2[0] == 0.0) { cx = (int)rint(W / 2.0) + 1; cy = (int)rint(H / 2.0) + 1; }
-  else { cy = (int)rint(S2[10] / S2[0]) + 1; cx = (int)rint(S2[11] / S2[0]) + 1; }
+  else { cy = (int)rint(S2[8] / S2[0]) + 1; cx = (int)rint(S2[9] / S2[0]) + 1; }
+}
+
+// The value the moments of S-measure quadrant q (LT, RT, LB, RB) are taken about: p at the quadrant's first pixel, 0 for an empty
+// quadrant (cx == W or cy == H).  Any value works in exact arithmetic; one from the quadrant itself makes every term of a flat
+// quadrant exactly 0, as the reference's two-pass moments are when its mean is exact (a blank quadrant of a saturated map).
+__device__ __forceinline__ double quad_shift(const Norm& nm, const float* __restrict__ pred, int H, int W, int cx, int cy, int q) {
+  const int y = (q & 2) ? cy : 0, x = (q & 1) ? cx : 0;
+  return (y >= 0 && y < H && x >= 0 && x < W) ? norm_p(nm, pred[(size_t)y * W + x]) : 0.0;
 }
 
 __global__ __launch_bounds__(1024) void cod_pass3_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int H, int W,
@@ -157,6 +169,10 @@ __global__ __launch_bounds__(1024) void cod_pass3_kernel(const float* __restrict
   const double thr = fmin(2.0 * (s2[1] / (double)n), 1.0);            // _get_adaptive_threshold (:135-136)
   int cx, cy;
   centroid(s2, H, W, cx, cy);
+  double shift[4];
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) shift[qq] = quad_shift(nm, pred + (size_t)b * n, H, W, cx, cy, qq);
+  const double mean_fg = s2[6] / s2[0], mean_bg = s2[7] / ((double)n - s2[0]);      // of p inside, of 1 - p outside (NaN when there is no such pixel: not used then)
   double s[NS3];
 #pragma unroll
   for (int k = 0; k < NS3; ++k) s[k] = 0.0;
@@ -169,7 +185,9 @@ __global__ __launch_bounds__(1024) void cod_pass3_kernel(const float* __restrict
     const double gf = g ? 1.0 : 0.0;
 #pragma unroll
     for (int qq = 0; qq < 4; ++qq)
-      if (q == qq) { s[2 + 4 * qq] += p; s[3 + 4 * qq] += p * p; s[4 + 4 * qq] += gf; s[5 + 4 * qq] += p * gf; }
+      if (q == qq) { const double a = p - shift[qq]; s[2 + 4 * qq] += a; s[3 + 4 * qq] += a * a; s[4 + 4 * qq] += gf; s[5 + 4 * qq] += a * gf; }
+    if (g) { const double d = p - mean_fg; s[18] += d * d; }
+    else { const double d = (1.0 - p) - mean_bg; s[19] += d * d; }
   }
   block_reduce<NS3>(s, red, S3 + ((size_t)b * gridDim.x + blockIdx.x) * NS3);
 }
@@ -277,16 +295,23 @@ __device__ __forceinline__ double enhanced_alignment(double fg_fg, double fg_bg,
   return total / (n - 1.0 + EPS);
 }
 
-__device__ __forceinline__ double ssim_q(double N, double sp, double spp, double sg, double spg) {
-  const double x = sp / N, y = sg / N;
-  const double vx = (spp - N * x * x) / (N - 1.0), vy = (sg - N * y * y) / (N - 1.0), cxy = (spg - N * x * y) / (N - 1.0);
+// a = p - shift (quad_shift): sa, saa, sag are the sums of a, a^2 and a g over the quadrant's N pixels, sg the sum of g.  N x' y' is
+// written sum * mean, so that a quadrant wholly inside or outside the ground truth (y = 1 or 0) has vy = cxy = 0 exactly, as in the
+// reference.  The variances are clamped at 0 (a NaN, from N <= 1, stays a NaN: the reference's is one too).
+__device__ __forceinline__ double ssim_q(double N, double shift, double sa, double saa, double sg, double sag) {
+  const double xa = sa / N, x = shift + xa, y = sg / N;
+  double vx = (saa - sa * xa) / (N - 1.0), vy = (sg - sg * y) / (N - 1.0);
+  const double cxy = (sag - sa * y) / (N - 1.0);
+  vx = vx < 0.0 ? 0.0 : vx;
+  vy = vy < 0.0 ? 0.0 : vy;
   const double alpha = 4.0 * x * y * cxy, beta = (x * x + y * y) * (vx + vy);
   if (alpha != 0.0) return alpha / (beta + EPS);
   return (beta == 0.0) ? 1.0 : 0.0;
 }
 
-__global__ __launch_bounds__(256) void cod_finalize_kernel(int H, int W, const double* __restrict__ S2, const double* __restrict__ S3, const unsigned* __restrict__ hist,
-                                                           const double* __restrict__ T, double* __restrict__ out) {
+__global__ __launch_bounds__(256) void cod_finalize_kernel(const float* __restrict__ pred, int H, int W, const float* __restrict__ mm, const double* __restrict__ S2,
+                                                           const double* __restrict__ S3, const unsigned* __restrict__ hist, const double* __restrict__ T,
+                                                           double* __restrict__ out) {
   __shared__ double cfg[256], cbg[256];
   const int b = blockIdx.x, t = threadIdx.x;
   const double n = (double)H * W;
@@ -323,20 +348,23 @@ __global__ __launch_bounds__(256) void cod_finalize_kernel(int H, int W, const d
   if (y == 0.0) sm = 1.0 - mean_p;
   else if (y == 1.0) sm = mean_p;
   else {
-    auto s_object = [](double cnt, double sum, double sumsq) {
+    auto s_object = [](double cnt, double sum, double dev2) {          // dev2: squared deviations about sum / cnt (pass 3)
       const double x = sum / cnt;
-      const double sd = sqrt((sumsq - cnt * x * x) / (cnt - 1.0));
-      return 2.0 * x / (x * x + 1.0 + sd + EPS);
+      double var = dev2 / (cnt - 1.0);                                 // one pixel: 0 / 0, the NaN of the reference's std(ddof=1)
+      var = var < 0.0 ? 0.0 : var;                                     // (a sum of squares is not negative; this keeps a NaN)
+      return 2.0 * x / (x * x + 1.0 + sqrt(var) + EPS);
     };
     const double n_bg = n - n_fg;
-    const double obj = y * s_object(n_fg, s2[6], s2[7]) + (1.0 - y) * s_object(n_bg, s2[8], s2[9]);
+    const double obj = y * s_object(n_fg, s2[6], s3[18]) + (1.0 - y) * s_object(n_bg, s2[7], s3[19]);
     int cx, cy;
     centroid(s2, H, W, cx, cy);
+    const Norm nm = load_norm(mm + b * 4);
     const double Nq[4] = {(double)cx * cy, (double)(W - cx) * cy, (double)cx * (H - cy), (double)(W - cx) * (H - cy)};
     const double w1 = (double)cx * cy / n, w2 = (double)cy * (W - cx) / n, w3 = (double)(H - cy) * cx / n, w4 = 1.0 - w1 - w2 - w3;
     const double wq[4] = {w1, w2, w3, w4};
     double reg = 0.0;
-    for (int q = 0; q < 4; ++q) reg += wq[q] * ssim_q(Nq[q], s3[2 + 4 * q], s3[3 + 4 * q], s3[4 + 4 * q], s3[5 + 4 * q]);
+    for (int q = 0; q < 4; ++q)
+      reg += wq[q] * ssim_q(Nq[q], quad_shift(nm, pred + (size_t)b * H * W, H, W, cx, cy, q), s3[2 + 4 * q], s3[3 + 4 * q], s3[4 + 4 * q], s3[5 + 4 * q]);
     sm = 0.5 * obj + 0.5 * reg;
     sm = sm > 0.0 ? sm : 0.0;                                          // max(0, sm); a NaN (degenerate quadrant) ends as 0, as in the reference
   }
@@ -442,7 +470,7 @@ extern "C" int ucod_cod_metrics(const float* pred, const float* gt, int B, int H
   hipLaunchKernelGGL(cod_edt_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, s, pred, gt, H, W, mm, Lc, Rc, dist, Et);
   hipLaunchKernelGGL(cod_wfm_kernel, dim3(ch, B), dim3(1024), 0, s, pred, gt, H, W, mm, dist, Et, gk, part);
   hipLaunchKernelGGL(cod_combine_kernel, dim3(B), dim3(32), 0, s, part, ch, 2, T);
-  hipLaunchKernelGGL(cod_finalize_kernel, dim3(B), dim3(256), 0, s, H, W, S2, S3, hist, T, out);
+  hipLaunchKernelGGL(cod_finalize_kernel, dim3(B), dim3(256), 0, s, pred, H, W, mm, S2, S3, hist, T, out);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
