@@ -1060,9 +1060,18 @@ int ucod_cls_qk(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv
 int ucod_cls_attention(const float* q_cls, const float* k_cls, const float* key_map, float* att, int B, int heads, int hw, float scale, void* stream);
 /* With register tokens (tok = 1 + n_reg + hw): ucod_cls_qk_reg also projects the keys of tokens 1 .. n_reg into k_lead f32 [B, 1 + n_reg, D] (row 0 = the CLS key);
  * ucod_cls_attention_reg = outputs.attentions[-1][:, :, 0, 1 + n_reg:] -- the softmax runs over all tok keys (the n_reg + 1 of k_lead in its maximum and
- * denominator, the patch keys from the key map), the patch columns are returned, so a row sums to less than 1 by the CLS and register weights. */
+ * denominator, the patch keys from the key map), the patch columns are returned, so a row sums to less than 1 by the CLS and register weights.
+ * ucod_cls_attention_rope: the same row of a DINOv3 model (rotary position embedding), where the last layer rotates the PATCH keys -- not the CLS query, not the
+ * CLS and register keys of k_lead -- before the product.  key_map stays the UNROTATED k_proj output (what the key hook hands out and ucod_bkg_seg reads);
+ * cos_sin is the f32 [hw, 64] table of ucod_vit_desc.rope (cos 32 | sin 32 per patch, 16-byte aligned), and patch j scores
+ * scale * sum_{i<32} c_j[i] (q[i] k_j[i] + q[i+32] k_j[i+32]) + s_j[i] (q[i+32] k_j[i] - q[i] k_j[i+32]) = scale * q . rotate(k_j): no rotated copy of the key
+ * map is formed (the kernel sums it key column by key column against the query turned back by the patch's angles: with zero angles the scores are
+ * ucod_cls_attention_reg's bit for bit).  Same grid, threads and LDS as ucod_cls_attention_reg (one kernel, two instantiations), everything f32; UCOD_EINVAL before any launch for a null
+ * pointer (cos_sin included), B / heads / hw <= 0, hw > 12000, n_reg < 0 or > 1023, a misaligned table. */
 int ucod_cls_qk_reg(const void* h_ln1_bf16, const void* qkv_w_bf16, const float* qkv_b, float* q_cls, float* k_lead, int B, int tok, int D, int n_reg, void* stream);
 int ucod_cls_attention_reg(const float* q_cls, const float* k_lead, const float* key_map, float* att, int B, int heads, int hw, int n_reg, float scale, void* stream);
+int ucod_cls_attention_rope(const float* q_cls, const float* k_lead, const float* key_map, const float* cos_sin, float* att, int B, int heads, int hw, int n_reg,
+                            float scale, void* stream);
 int ucod_bkg_seg(const float* att, const float* key_map, float th_bkg, float epsilon, int apply_weights, float* bkg_mask, float* sim_map,
                  float* cos_row, int* seed, float* beta, void* scratch4, int B, int heads, int hw, void* stream);
 

@@ -4,7 +4,8 @@
 //                       outputs.attentions[-1], found_bkg_mask.py:23) from that layer's LN1 output, which ucod_vit_forward leaves
 //                       in its workspace;
 //   ucod_cls_attention  softmax over ALL keys (CLS + patches) of that query per head, patch columns kept -- from the NCHW key map
-//                       the backbone pass already produced (one token-contiguous row per channel: coalesced);
+//                       the backbone pass already produced (one token-contiguous row per channel: coalesced); ucod_cls_attention_rope: the same row of a
+//                       DINOv3 model, the patch keys rotated by the rotary table as they are read (the key map stays the unrotated hook output);
 //   ucod_bkg_seg        CroW sparsity weights, seed = least-attended patch, cosine similarity of every patch's (weighted) key
 //                       descriptor to the seed's, background mask and similarity map.  Only the seed's row of the HW x HW
 //                       similarity matrix is formed (the reference builds all of it and reads one row).  One workgroup per image.
@@ -65,8 +66,19 @@ __global__ __launch_bounds__(256) void cls_qk_kernel(const bf16_raw* __restrict_
 
 // grid (B, heads); att[b][h][j] for patches j (the CLS column and the `lead - 1` register-token columns dropped after the softmax, whose maximum and
 // denominator include them: kc f32 [B, lead, D] holds their keys, CLS first)
+// ROPE (DINOv3): the patch keys -- and only they: not the query, not kc -- are rotated by the rows of tab f32 [hw, 64] (cos 32 | sin 32 of patch j), regrouped
+// so that no rotated key is formed: score_j = scale sum_{i<32} c_j[i] (q[i] k[i] + q[i+32] k[i+32]) + s_j[i] (q[i+32] k[i] - q[i] k[i+32]) = q . rotate(k_j).
+// The sum is taken key column by key column, d = 0 .. 63 as the plain kernel takes it, each column times the query turned BACK by the patch's angles
+// (k[i] (c q[i] + s q[i+32]) + k[i+32] (c q[i+32] - s q[i])): one product chain of the plain kernel's length and order, and where the angles are zero (cos 1,
+// sin 0: a 1 x 1 grid) the very scores, bit for bit.
+// Key-map reads stay coalesced along j (kb[d hw + j] and kb[(d + 32) hw + j]).  Table reads: STRAIGHT FROM L2, a lane walking its own 256-byte row in sixteen
+// 16-byte loads -- not staged through LDS.  Every block of the grid reads the same table (256 KB at hw = 1024, resident in L2 beside nothing else of size), a
+// lane uses each fetched line in full within one j, and a 256-row LDS tile at a padded pitch would take 65 KB where the kernel holds (hw + 8) floats today;
+// tools/cls_row_bench.py measures what the rotation costs (profiles/dinov3_cls_row_kernel.txt: 47 us against the plain kernel's 28 at B = 32, 12 heads,
+// hw = 1024; 106 VGPRs, no scratch).  The ROPE = false instantiation is the kernel as it was (tab is never read).
+template <bool ROPE>
 __global__ __launch_bounds__(256) void cls_attention_kernel(const float* __restrict__ q, const float* __restrict__ kc, const float* __restrict__ key,
-                                                            float* __restrict__ att, int heads, int hw, float scale, int lead) {
+                                                            float* __restrict__ att, int heads, int hw, float scale, int lead, const float* __restrict__ tab) {
   extern __shared__ float sc[];                              // hw scores, then 8 floats of reduction space
   float* red = sc + hw;
   const int b = blockIdx.x, hd = blockIdx.y, D = heads * 64;
@@ -75,8 +87,27 @@ __global__ __launch_bounds__(256) void cls_attention_kernel(const float* __restr
   float mx = -3.0e38f;
   for (int j = threadIdx.x; j < hw; j += 256) {
     float s = 0.f;
+    if constexpr (ROPE) {
+      const float4* row = reinterpret_cast<const float4*>(tab + (size_t)j * 64);     // cos: row[0 .. 7], sin: row[8 .. 15]
+      float qr[32];                                          // columns 32 .. 63 of the query turned back by patch j's angles, held for the second half
+#pragma unroll
+      for (int i = 0; i < 32; i += 4) {
+        const float4 c4 = row[i >> 2], s4 = row[8 + (i >> 2)];
+        const float c[4] = {c4.x, c4.y, c4.z, c4.w}, sn[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int d = i + e;
+          const float qa = qh[d], qp = qh[d + 32];
+          s = fmaf(c[e] * qa + sn[e] * qp, kb[(size_t)d * hw + j], s);
+          qr[d] = c[e] * qp - sn[e] * qa;
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < 32; ++d) s = fmaf(qr[d], kb[(size_t)(d + 32) * hw + j], s);
+    } else {
 #pragma unroll 8
-    for (int d = 0; d < 64; ++d) s += qh[d] * kb[(size_t)d * hw + j];
+      for (int d = 0; d < 64; ++d) s += qh[d] * kb[(size_t)d * hw + j];
+    }
     s *= scale;
     sc[j] = s;
     mx = fmaxf(mx, s);
@@ -206,8 +237,17 @@ extern "C" int ucod_cls_qk(const void* h_ln1_bf16, const void* qkv_w_bf16, const
 extern "C" int ucod_cls_attention_reg(const float* q_cls, const float* k_lead, const float* key_map, float* att, int B, int heads, int hw, int n_reg, float scale,
                                       void* stream) {
   if (!q_cls || !k_lead || !key_map || !att || B <= 0 || heads <= 0 || hw <= 0 || hw > 12000 || n_reg < 0 || n_reg > 1023) return UCOD_EINVAL;
-  hipLaunchKernelGGL(cls_attention_kernel, dim3(B, heads), dim3(256), (size_t)(hw + 8) * sizeof(float), (hipStream_t)stream, q_cls, k_lead, key_map, att,
-                     heads, hw, scale, 1 + n_reg);
+  hipLaunchKernelGGL(cls_attention_kernel<false>, dim3(B, heads), dim3(256), (size_t)(hw + 8) * sizeof(float), (hipStream_t)stream, q_cls, k_lead, key_map, att,
+                     heads, hw, scale, 1 + n_reg, (const float*)nullptr);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+extern "C" int ucod_cls_attention_rope(const float* q_cls, const float* k_lead, const float* key_map, const float* cos_sin, float* att, int B, int heads, int hw,
+                                       int n_reg, float scale, void* stream) {
+  if (!q_cls || !k_lead || !key_map || !cos_sin || !att || B <= 0 || heads <= 0 || hw <= 0 || hw > 12000 || n_reg < 0 || n_reg > 1023) return UCOD_EINVAL;
+  if ((uintptr_t)cos_sin & 15) return UCOD_EINVAL;           // (16-byte loads of the table's rows, as ucod_rope_qk)
+  hipLaunchKernelGGL(cls_attention_kernel<true>, dim3(B, heads), dim3(256), (size_t)(hw + 8) * sizeof(float), (hipStream_t)stream, q_cls, k_lead, key_map, att,
+                     heads, hw, scale, 1 + n_reg, cos_sin);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

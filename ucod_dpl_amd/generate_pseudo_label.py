@@ -34,19 +34,21 @@ def refine_post_process(mask, area_threshold=4):
 
 
 class PseudoLabelGenerator:
-    def __init__(self, feature_extractor, th_bkg=0.6, area_threshold=4, precision="f32eq"):
+    def __init__(self, feature_extractor, th_bkg=0.6, area_threshold=4, precision="f32eq", allow_rope=False):
         """``precision``: the reference's script runs the backbone in plain fp32 under ``torch.no_grad()`` (generate_pseudo_label.py:71-89: no autocast), and its
         output is a THRESHOLDED map -- so a ``backbone`` wrapper is asked for its f32-equivalent sibling by default (``with_precision("f32eq")``: the
-        split-operand engine); ``precision=None`` keeps the extractor as given (a bare engine is always used as it is)."""
+        split-operand engine); ``precision=None`` keeps the extractor as given (a bare engine is always used as it is).
+        ``allow_rope``: handed to ``forward_with_cls_attention``.  A DINOv3 backbone (rotary position embedding) is refused without it; with it the CLS row is
+        computed with the last layer's patch keys rotated, and the generator makes that backbone's own training targets.  No effect on any other backbone."""
         if precision is not None and hasattr(feature_extractor, "with_precision"):
             feature_extractor = feature_extractor.with_precision(precision)
         self.engine = getattr(feature_extractor, "engine", feature_extractor)
-        self.th_bkg, self.area_threshold = th_bkg, area_threshold
+        self.th_bkg, self.area_threshold, self.allow_rope = th_bkg, area_threshold, bool(allow_rope)
 
     @torch.no_grad()
     def raw_masks(self, images):
         """images [B,3,H,W] (already transformed, :116-120) -> 1 - bkg_mask, float [B,h,w] on the device."""
-        key, att = self.engine.forward_with_cls_attention(images.to(self.engine.device))
+        key, att = self.engine.forward_with_cls_attention(images.to(self.engine.device), allow_rope=self.allow_rope)
         return 1.0 - bkg_seg_from_key_map(att, key, self.th_bkg)["bkg_mask"]
 
     def generate_masks(self, images):

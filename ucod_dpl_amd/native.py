@@ -150,6 +150,8 @@ SIGNATURES = {
     "ucod_key_grad_tokens_reg": (ci, [vp, vp, ci, ci, ci, ci, vp]),
     "ucod_cls_qk_reg": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "ucod_cls_attention_reg": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    # DINOv3: the same row with the patch keys rotated on the fly by the [hw, 64] rotary table (4th argument)
+    "ucod_cls_attention_rope": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
     "ucod_gemm_lnfold": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, cf, vp, ci, vp]),
     "ucod_gemm_bf16_blk16a": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp]),
     "ucod_gemm_bf16_stats": (ci, [ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp]),

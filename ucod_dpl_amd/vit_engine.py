@@ -298,6 +298,8 @@ class _SaturationGuard:
 # (forward_with_cls_attention on DINOv3) why the CLS attention row is refused
 _CLS_ROW_ON_ROPE = ("the CLS query's softmax row needs the ROTATED patch keys of the last layer, and the key map -- the hook's output, taken before the rotation -- "
                     "does not hold them")
+# ... and the way in: ucod_cls_attention_rope rotates the patch keys as it reads them.  Opt-in, because the refusal above is pinned by tests
+_CLS_ROW_WAY_IN = "; pass allow_rope=True for the row computed with the patch keys rotated on the fly (ucod_cls_attention_rope)"
 
 
 def _chunk_bounds(B, ns):
@@ -375,9 +377,22 @@ class _BackboneEngine:
             self._rope_cache[key] = rope_table(gh, gw, self.rope_theta).to(self.device)
         return self._rope_cache[key]
 
-    def _refuse_rope(self, what, why):
+    def _refuse_rope(self, what, why, way_in=""):
         if self.rope:
-            raise NotImplementedError(f"{what} is not built for a DINOv3 checkpoint (rotary position embedding, RoPE): {why}")
+            raise NotImplementedError(f"{what} is not built for a DINOv3 checkpoint (rotary position embedding, RoPE): {why}{way_in}")
+
+    def _cls_row(self, q, k_lead, key, R):
+        """att f32 [B, heads, hw]: the CLS query's softmax row over the keys of ``k_lead`` [B, 1 + R, D] and the patch keys of the key map, patch columns kept.
+        One kernel on every checkpoint (ucod_cls_attention_rope / _reg are its two instantiations): with a rotary table it rotates the patch keys as it reads them."""
+        B, hw = key.shape[0], key.shape[-2] * key.shape[-1]
+        att = torch.empty(B, self.heads, hw, dtype=torch.float32, device=self.device)
+        if self.rope:
+            table = self._rope(key.shape[-2], key.shape[-1])
+            N.check(self.lib.ucod_cls_attention_rope(N.ptr(q), N.ptr(k_lead), N.ptr(key), N.ptr(table), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()),
+                    "ucod_cls_attention_rope")
+        else:
+            N.check(self.lib.ucod_cls_attention_reg(N.ptr(q), N.ptr(k_lead), N.ptr(key), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()), "ucod_cls_attention")
+        return att
 
     def _desc(self, B, H, W, L=None):
         d = N.VitDesc()
@@ -619,12 +634,15 @@ class ViTEngine(_BackboneEngine):
             self.check_overflow(wait=True)
         return key
 
-    def forward_with_cls_attention(self, img):
+    def forward_with_cls_attention(self, img, allow_rope=False):
         """(key [B,D,h,w], att [B,heads,h*w]): the key map plus ``outputs.attentions[-1][:, :, 0, 1:]`` of the HF model -- the CLS
         query's softmax row of the LAST layer, which is all the pseudo-label generator reads from the attentions
         (data/utils/found_bkg_mask.py:23; generate_pseudo_label.py:78-89).  Single-stream pass: the CLS projections are taken
-        from the LayerNorm-1 output the pass leaves in its workspace."""
-        self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE)
+        from the LayerNorm-1 output the pass leaves in its workspace.
+        ``allow_rope``: on a DINOv3 checkpoint the method refuses without it; with it the row is ``attentions[-1][:, :, 0, 1 + R:]`` of DINOv3ViTModel, the patch
+        keys rotated inside the row kernel (the key map returned stays the unrotated hook output).  On every other checkpoint it changes nothing."""
+        if self.rope and not allow_rope:
+            self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE, _CLS_ROW_WAY_IN)
         if self.full_last_layer:
             raise RuntimeError("forward_with_cls_attention needs the key-minimal pass (full_last_layer=False)")
         ns, self.streams = self.streams, 1
@@ -636,15 +654,13 @@ class ViTEngine(_BackboneEngine):
         lib = self.lib
         d = self._desc(B, H, W)
         off = lib.ucod_vit_last_ln1_offset_mlp(C.byref(d), self.mlp)
-        hw, R = key.shape[-2] * key.shape[-1], self.R
+        R = self.R
         tok = self.tokens(key.shape[-2], key.shape[-1])
         last = self.layers[-1]
         q = torch.empty(B, self.D, dtype=torch.float32, device=self.device)
         k = torch.empty(B, 1 + R, self.D, dtype=torch.float32, device=self.device)      # the keys of CLS and of the R register tokens (in the softmax, not in the row)
         N.check(lib.ucod_cls_qk_reg(self._ws.data_ptr() + off, N.ptr(last[N.QKV_W]), N.ptr(last[N.QKV_B]), N.ptr(q), N.ptr(k), B, tok, self.D, R, N.stream()), "ucod_cls_qk")
-        att = torch.empty(B, self.heads, hw, dtype=torch.float32, device=self.device)
-        N.check(lib.ucod_cls_attention_reg(N.ptr(q), N.ptr(k), N.ptr(key), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()), "ucod_cls_attention")
-        return key, att
+        return key, self._cls_row(q, k, key, R)
 
     __call__ = forward
 
@@ -761,16 +777,17 @@ class SplitViTEngine(_BackboneEngine):
 
         return key, self._fan_out(self._side, _chunk_bounds(img.shape[0], 1), run, (img, key), wait=False)
 
-    def forward_with_cls_attention(self, img):
-        """(key [B,D,h,w], att [B,heads,h*w]) like ``ViTEngine.forward_with_cls_attention``: the key map plus ``outputs.attentions[-1][:, :, 0, 1:]`` of the HF model
+    def forward_with_cls_attention(self, img, allow_rope=False):
+        """(key [B,D,h,w], att [B,heads,h*w]) like ``ViTEngine.forward_with_cls_attention`` (``allow_rope`` included): the key map plus ``outputs.attentions[-1][:, :, 0, 1:]`` of the HF model
         (data/utils/found_bkg_mask.py:23; generate_pseudo_label.py:78-89 -- a plain fp32 pass under torch.no_grad() in the reference, which is why the
         pseudo-label generator asks for this engine).  The CLS rows of the last layer's input are taken from the f32 residual stream the pass leaves in its
         workspace, normalised by the f32 LayerNorm kernel, projected to the CLS query / key on split operands, and fed to the f32 attention-row kernel."""
-        self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE)
+        if self.rope and not allow_rope:
+            self._refuse_rope("forward_with_cls_attention", _CLS_ROW_ON_ROPE, _CLS_ROW_WAY_IN)
         key = self.forward(img)
         B, _, H, W = img.shape
         off = self._stream_offset(self._desc(B, H, W))
-        hw, R = key.shape[-2] * key.shape[-1], self.R
+        R = self.R
         tok = self.tokens(key.shape[-2], key.shape[-1])
         x = self._ws[off:off + B * tok * self.D * 4].view(torch.float32).view(B, tok, self.D)
         L_ = self._last
@@ -787,9 +804,7 @@ class SplitViTEngine(_BackboneEngine):
         else:
             q = ops.linear_split(h_cls, L_["wq"], L_["bq"], self.terms)
             k = ops.linear_split(h_lead, L_["wk"], L_["bk"], self.terms)
-        att = torch.empty(B, self.heads, hw, dtype=torch.float32, device=self.device)
-        N.check(self.lib.ucod_cls_attention_reg(N.ptr(q), N.ptr(k.contiguous()), N.ptr(key), N.ptr(att), B, self.heads, hw, R, 0.125, N.stream()), "ucod_cls_attention")
-        return key, att
+        return key, self._cls_row(q, k.contiguous(), key, R)
 
     __call__ = forward
 
