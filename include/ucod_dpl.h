@@ -841,7 +841,8 @@ int ucod_fold_ln_linear(const float* w, const float* gamma, const float* beta, c
 int ucod_bilinear_resize(const float* in, float* out, int planes, int ih, int iw, int oh, int ow, void* stream);
 /* Transpose of the above: gin [planes,ih,iw] = U^T gout [planes,oh,ow] (same taps and weights as the forward).  The
  * training step runs the 1x1 decoupling conv and its weight gradient on the backbone's native 37x37 grid and moves
- * d / gd across the resize instead of the 768-channel features (conv and resize commute). */
+ * d / gd across the resize instead of the 768-channel features (conv and resize commute).  UCOD_EINVAL when a source index
+ * of either axis can be reached by more than 16 outputs: min(ceil(2 out / in) + 1, out) > 16, up-sampling beyond 7.5x. */
 int ucod_bilinear_resize_adjoint(const float* gout, float* gin, int planes, int ih, int iw, int oh, int ow, void* stream);
 
 /* 1x1 "decoupling" conv as an exact-f32 MFMA GEMM (models/modules/DBA.py:13,35):

@@ -361,7 +361,9 @@ extern "C" int ucod_bilinear_resize_adjoint(const float* gout, float* gin, int p
   const float sh = (float)ih / (float)oh, sw = (float)iw / (float)ow;
   UCOD_PROF(PROF_BILINEAR, stream);
   (void)total;
-  const float taps = ceilf(2.f / fminf(sh, sw)) + 1.f;
+  // outputs that reach one source index, per axis: at most ceil(2 / scale) + 1 -- and never more than the axis has (a 1-wide source under a 9-wide
+  // output has 9 taps, not the 19 of the estimate alone, which refused it; tests/test_resize_ref_host.py holds this against the taps src_index() produces)
+  const float taps = fmaxf(fminf(ceilf(2.f / sh) + 1.f, (float)oh), fminf(ceilf(2.f / sw) + 1.f, (float)ow));
   if (taps > 16.f) return UCOD_EINVAL;                                       // more than 16 taps per axis (up-sampling beyond 7.5x)
   const int MAXT = taps > 8.f ? 16 : 8;
   const size_t lds = ((((size_t)oh * ow + 3) & ~(size_t)3) + (size_t)oh * iw + (size_t)ih * (2 * MAXT + 1)) * sizeof(float);
