@@ -645,6 +645,32 @@ int ucod_lora_mlp_grad(const void* dpre_bf16, const void* h2_aug_bf16, const flo
 int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
                                 void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
                                 const ucod_lora_dropout* dropout, void* stream);
+/* The gated MLP's input (DINOv3 vits16plus: down_proj(silu(gate_proj(x)) * up_proj(x))) is TWO peft modules, gate_proj and up_proj, each with its own A, B and
+ * dropout mask, on the ONE fused, padded, 4-interleaved weights_in GEMM: engine row 8k+e is gate row 4k+e for e < 4, row 8k+4+e is up row 4k+e.  The pair is a
+ * rank-2r module whose B is block diagonal.  One layer's parameters / gradients (f32): [A_g (r x D) | A_u (r x D) | B_m (N1 x r)], N1 = 2F, B_m in the engine's row
+ * order (row n is gate's iff n % 8 < 4: byte for byte the single module's B_m), padded rows zero.  A module of the pair that is not targeted has A = 0 and its
+ * rows of B = 0; its gradients are then exact zeros (u = 0 gives dB = 0, t = 0 gives dA = 0).  Masks: gate_proj is projection 0, up_proj projection 1 of
+ * ucod_lora_dropout with layer = L + l.  1 <= r <= UCOD_LORA_MLP_MAX_R.
+ * ucod_layernorm_lora_mlp_pair (full_model.py:47-72): y_aug bf16 [rows, D+64] = [ LN(x) | drop_0(LN x) A_g^T (r) | drop_1(LN x) A_u^T (r) | 0 ], a_pair f32 [2r, D]. */
+int ucod_layernorm_lora_mlp_pair(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_pair, int r, void* y_aug_bf16, int rows, int D,
+                                 float eps, const ucod_lora_dropout* dropout, void* stream);
+/* aug columns of fc1_w_aug bf16 [N1, D+64] from one layer's [A_g | A_u | B_m] (full_model.py:47-72): row n gets alpha/r * B_m[n][j] at column D + mod(n) r + j
+ * (mod(n) = 0 for a gate row, 1 for an up row); every other aug column is zero.  N1 % 8 == 0, N1 <= 8192. */
+int ucod_lora_mlp_pair_pack(const float* lora_pair, int r, float scaling, void* fc1_w_aug_bf16, int N1, int D, void* stream);
+/* Both modules' gradients of one layer in ONE pass over dpre bf16 [rows, N1] and h2_aug bf16 [rows, D+64] per two ranks (full_model.py:47-72): of a thread's
+ * 16-byte dpre vector elements 0-3 are gate's and 4-7 up's;  t bf16 [rows, 64]: column p r + j = alpha/r * sum over module p's rows n of dpre[:, n] B_m[n][j], the
+ * rest zero;  dB_m[n] = alpha/r * dpre[:, n]^T u_mod(n);  dA_p = t_p^T drop_p(h2), from the bf16-rounded t.  grad_pair f32 [r (2D + N1)] is overwritten.
+ * Deterministic: per-block partials in `workspace`, summed in a fixed order by a reduce kernel; no float atomics.  N1 % 128 == 0, N1 <= 8192, D % 128 == 0,
+ * D <= 1536 (else the size is 0 and the call UCOD_EINVAL before any launch; a workspace that is too small: UCOD_ENOMEM).  Every instantiation runs both modules in
+ * one pass: none of them spills to scratch memory, so the launch function has no two-pass case. */
+size_t ucod_lora_mlp_pair_grad_workspace_bytes(int N1, int D);
+int ucod_lora_mlp_pair_grad(const void* dpre_bf16, const void* h2_aug_bf16, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
+                            void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream);
+/* ucod_layernorm_bwd_lora_mlp for the pair (full_model.py:47-72):  dy += mask_0/(1-p) * (t_g A_g) + mask_1/(1-p) * (t_u A_u), t_p at columns p r + j of the
+ * bf16 rows of length ldt >= 2r, a_pair f32 [2r, D]. */
+int ucod_layernorm_bwd_lora_mlp_pair(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                     void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_pair, int r,
+                                     const ucod_lora_dropout* dropout, void* stream);
 /* The _lora_out_ex forms with out_table_host = NULL, out_flags = 0 (TM, the MLP module's own per-layer table, is described there; layer l at UCOD_VIT_TRAIN_MLP_STRIDE*l). */
 #define UCOD_VIT_TRAIN_MLP_STRIDE 3
 size_t ucod_vit_train_workspace_bytes_lora_mlp(const ucod_vit_train_desc* t, int mlp, const void* const* mlp_table_host);
@@ -760,8 +786,13 @@ int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, 
  *                          3 L + l; the training pass saves u in the fc2 module's slots, so the workspace is the GELU formula with K = F); in the backward, behind
  *                          the UCOD_EPI_SWIGLU_BWD_BF16 GEMM, ucod_lora_out_grad_s on s and ucod_lora_out_grad_x_ex(pre, UCOD_LORA_OUT_ACT_SWIGLU, dpre) in front of
  *                          ucod_layernorm_lora_mlp / ucod_lora_mlp_grad and the weights_in dgrad.  The last layer's gradients are written as zeros.  With
- *                          UCOD_MLP_GELU the flag changes nothing. */
+ *                          UCOD_MLP_GELU the flag changes nothing.
+ *   UCOD_LORA_MLP_PAIR     (full_model.py:47-72) valid only with UCOD_MLP_SWIGLU and a non-NULL TM (else UCOD_EINVAL, sizes 0): TM describes the gated MLP's PAIR
+ *                          gate_proj / up_proj -- slots +1 / +2 are [A_g | A_u | B_m], r (2D + N1) floats, +0's aug columns maintained by ucod_lora_mlp_pair_pack --
+ *                          and all three passes run ucod_layernorm_lora_mlp_pair / ucod_lora_mlp_pair_grad / ucod_layernorm_bwd_lora_mlp_pair where they ran the
+ *                          single module's kernels (dropout key L + l, projections 0 and 1).  The last layer's r (2D + N1) gradients are written as zeros. */
 #define UCOD_LORA_OUT_SWIGLU 1
+#define UCOD_LORA_MLP_PAIR 4
 size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,
                                                   const void* const* out_table_host);
 int ucod_vit_forward_train_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,

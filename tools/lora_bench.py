@@ -3,7 +3,7 @@
 SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both passes, @512), per-class kernel times.
     lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side] [bias]]]]]]]]
 ``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
-on ViT-g; naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
+on ViT-g, or q_proj,k_proj,v_proj,gate_proj,up_proj on dinov3_vits16plus (a DINOv3 MLP input module switches ``allow_mlp_in`` on); naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
 ``bias``: a trailing none / lora_only (peft's LoraConfig.bias; with or without ``side`` in front of it): lora_only also trains the targeted modules' biases -- one
 deterministic column sum per bias and layer in the backward (tools/lora_bias_bench.py times the two modes against each other in one process)."""
 import ctypes as C, os, sys, time
@@ -40,6 +40,8 @@ if any(t in ("dense", "fc2", "o_proj", "down_proj", "weights_out") for t in leav
     kw.update(allow_out=True)                             # the output projections are opt-in (ViTLoRAEngine)
 if "weights_out" in leaves or ("down_proj" in leaves and arch in SWIGLU_ARCHS):
     kw.update(allow_swiglu_out=True)                      # ... and the SwiGLU MLP's has an opt-in of its own (the hidden is recomputed in the backward)
+if v3 and any(t in ("up_proj", "gate_proj") for t in leaves):
+    kw.update(allow_mlp_in=True)                          # DINOv3's MLP input modules are opt-in too (on the gated MLP: the gate_proj / up_proj pair kernels)
 eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
     print(f"targets {targets}, bias {bias}: arena [{eng.L}, {eng.lora.shape[1]}]")

@@ -65,18 +65,19 @@ static Drop make_drop(const ucod_lora_dropout* dd) {
 // LayerNorm forward + LoRA down-projection.  One wave per row, D = 128*NCH, row in registers (as layernorm_kernel).
 // ---------------------------------------------------------------------------------------------------------------------
 // XH16: the residual stream is IEEE fp16 (the no-grad pass of the EMA teacher, ucod_vit_forward_lora_infer with resid16) instead of f32
-// NP: modules sharing the row -- 3 (query, key, value: `lora` is the layer's [A_q | B_q | A_k | B_k | A_v | B_v]) or 1 (the MLP input projection: `lora` is A_m)
+// NP: modules sharing the row -- 3 (query, key, value: `lora` is the layer's [A_q | B_q | A_k | B_k | A_v | B_v]), 1 (the MLP input projection: `lora` is A_m) or
+// 2 (gate_proj and up_proj of the gated MLP: `lora` is [A_g | A_u]).  A_p sits at lora + p * astride: 2 r D between q / k / v, r D between the adjacent pair
 template <int NCH, bool XH16 = false, int NP = 3>
 __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x_, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, const float* __restrict__ lora,
-                                                      int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop) {
+                                                      int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop, int astride) {
   // the 3r LoRA A rows live in LDS for the whole block (they were re-read from L2 for every row: 92 us against 33 us for the plain
   // LayerNorm); each wave walks rows block-stride, two rows in flight (as layernorm_kernel)
   extern __shared__ float a_lds[];                               // [NP r][D]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < NP * r * D; i += 256) {
-    const int p = i / (r * D), rem = i - p * r * D;               // A_p at lora + p*2*r*D
-    a_lds[i] = lora[(size_t)p * 2 * r * D + rem];
+    const int p = i / (r * D), rem = i - p * r * D;               // A_p at lora + p*astride
+    a_lds[i] = lora[(size_t)p * astride + rem];
   }
   __syncthreads();
   constexpr int R = 2;
@@ -157,12 +158,12 @@ __global__ __launch_bounds__(256) void ln_lora_kernel(const void* __restrict__ x
 template <int NV, bool XH16, int NP = 3>
 __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ x_, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, const float* __restrict__ lora,
-                                                       int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop) {
+                                                       int r, bf16_raw* __restrict__ y, int rows, int D, float eps, Drop drop, int astride) {
   extern __shared__ float a_lds[];                               // [NP r][D]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < NP * r * D; i += 256) {
     const int p = i / (r * D), rem = i - p * r * D;
-    a_lds[i] = lora[(size_t)p * 2 * r * D + rem];
+    a_lds[i] = lora[(size_t)p * astride + rem];
   }
   __syncthreads();
   constexpr int R = 2;
@@ -264,13 +265,15 @@ __global__ __launch_bounds__(256) void ln_lora4_kernel(const void* __restrict__ 
 // that one latency covers all three streams (round 3: 103 -> see profiles/r03_ln_bwd.txt).
 // DYB: dy arrives as bf16 (the dgrad GEMMs of the backward driver write their output in the 16-bit type: half the bytes on both sides).
 // XH: x (the saved LayerNorm input = the residual stream) is IEEE fp16 (training pass with vit.resid16).
-// LORA: 0, or the number of modules whose branch is added -- 3 (q / k / v: t at tq[p r + j], A_p at lora + p 2 r D) or 1 (the MLP input projection: lora = A_m)
+// LORA: 0, or the number of modules whose branch is added -- 3 (q / k / v: t at tq[p r + j], A_p at lora + p astride, astride = 2 r D), 1 (the MLP input
+// projection: lora = A_m) or 2 (gate_proj / up_proj of the gated MLP: lora = [A_g | A_u], astride = r D; masks 0 and 1)
 template <int NCH, int VW, int LORA, bool DYB, bool XH>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy_, const void* __restrict__ x_,
                                                      const float* __restrict__ gamma, const float* __restrict__ dres,
                                                      const float* __restrict__ scale, float* __restrict__ dx,
                                                      bf16_raw* __restrict__ sout, int rows, int D, float eps,
-                                                     const bf16_raw* __restrict__ tq, int ldt, const float* __restrict__ lora, int r, Drop drop) {
+                                                     const bf16_raw* __restrict__ tq, int ldt, const float* __restrict__ lora, int r, Drop drop,
+                                                     int astride) {
   typedef float vecf __attribute__((ext_vector_type(VW)));
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -322,7 +325,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
 #pragma unroll
           for (int jr = 0; jr < R; ++jr) {
             t[p][jr] = bf16_to_f32(tq[(size_t)row * ldt + p * R + jr]);
-            av[p][jr] = reinterpret_cast<const vecf*>(lora + (size_t)p * 2 * R * D + (size_t)jr * D)[lane + 64 * i];
+            av[p][jr] = reinterpret_cast<const vecf*>(lora + (size_t)p * astride + (size_t)jr * D)[lane + 64 * i];
           }
 #pragma unroll
         for (int p = 0; p < LORA; ++p) {
@@ -341,7 +344,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
           vecf acc = (vecf)(0.f);
           for (int jr = 0; jr < r; ++jr) {
             const float t = bf16_to_f32(tq[(size_t)row * ldt + p * r + jr]);
-            const vecf av = reinterpret_cast<const vecf*>(lora + (size_t)p * 2 * r * D + (size_t)jr * D)[lane + 64 * i];
+            const vecf av = reinterpret_cast<const vecf*>(lora + (size_t)p * astride + (size_t)jr * D)[lane + 64 * i];
             acc += t * av;
           }
 #pragma unroll
@@ -667,13 +670,13 @@ static inline hipError_t ask_lds(K kern, size_t lds) {
   return lds > 65536 ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
 }
 
-// np: 3 = the q / k / v modules of one layer (lora = the layer's arena row), 1 = the MLP input projection (lora = A_m)
+// np: 3 = the q / k / v modules of one layer (lora = the layer's arena row), 1 = the MLP input projection (lora = A_m), 2 = the gated MLP's pair (lora = [A_g | A_u])
 static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const float* beta, const float* lora, int r, void* y_aug, int rows, int D, float eps,
                           const ucod_lora_dropout* dropout, void* stream, int np = 3) {
   if (!x || !gamma || !beta || !lora || !y_aug || rows <= 0 || D <= 0 || (D % 128) != 0 || r < 1 || np * r > AUG) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   if (ln_lora_lds_bytes(D, r, np) > lds_per_block()) return UCOD_EINVAL;      // the np r A rows do not fit one workgroup's LDS: refused before any launch
-  UCOD_PROF(np == 1 ? PROF_LN_LORA_MLP : PROF_LN, stream);
+  UCOD_PROF(np == 3 ? PROF_LN : PROF_LN_LORA_MLP, stream);
   const Drop drop = make_drop(dropout);
   static const int lnl_env = [] { const char* e = ucod::lab_env("UCOD_LN_LORA_NBLK"); return e ? atoi(e) : 0; }();          // measurement knob
   const int lnl_max = lnl_env > 0 ? lnl_env : 2048;
@@ -681,12 +684,13 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   dim3 grid(nblk), block(256);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = ln_lora_lds_bytes(D, r, np);
+  const int astride = (np == 3 ? 2 : 1) * r * D;                  // from A_p to A_{p+1}: B_p lies between q / k / v, the pair's two are adjacent
   static const bool narrow = ucod::lab_env("UCOD_LN_LORA_NARROW") != nullptr;     // measurement knob: the 8-byte / 4-byte form
 #define LNL(kern)                                                                                                       \
   do {                                                                                                                  \
     const hipError_t e = ask_lds(kern, lds);                                                                            \
     if (e != hipSuccess) return (int)e;                                                                                 \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop);       \
+    hipLaunchKernelGGL(kern, grid, block, lds, s, x, gamma, beta, lora, r, (bf16_raw*)y_aug, rows, D, eps, drop, astride); \
   } while (0)
   if ((D % 256) == 0 && D <= 1536 && !narrow) {
     switch (D / 256) {
@@ -694,6 +698,8 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   case n:                                                                                                                                            \
     if (np == 1 && x_h16) LNL((ln_lora4_kernel<n, true, 1>)); \
     else if (np == 1) LNL((ln_lora4_kernel<n, false, 1>));    \
+    else if (np == 2 && x_h16) LNL((ln_lora4_kernel<n, true, 2>)); \
+    else if (np == 2) LNL((ln_lora4_kernel<n, false, 2>));    \
     else if (x_h16) LNL((ln_lora4_kernel<n, true>)); \
     else LNL((ln_lora4_kernel<n, false>));          \
     break;
@@ -708,6 +714,8 @@ static int launch_ln_lora(const void* x, bool x_h16, const float* gamma, const f
   case n:                                                                                                                                            \
     if (np == 1 && x_h16) LNL((ln_lora_kernel<n, true, 1>)); \
     else if (np == 1) LNL((ln_lora_kernel<n, false, 1>));    \
+    else if (np == 2 && x_h16) LNL((ln_lora_kernel<n, true, 2>)); \
+    else if (np == 2) LNL((ln_lora_kernel<n, false, 2>));    \
     else if (x_h16) LNL((ln_lora_kernel<n, true>));      \
     else LNL((ln_lora_kernel<n, false>));           \
     break;
@@ -736,13 +744,17 @@ static int launch_ln_bwd(const void* dy, bool dy_bf16, const void* x, bool x_f16
                          int rows, int D, float eps, const bf16_raw* tq, int ldt, const float* lora, int r, const Drop& drop, hipStream_t s, int np = 3) {
   dim3 grid(cdiv(rows, 4)), block(256);
   const bool lo = tq != nullptr;
+  const int astride = (np == 3 ? 2 : 1) * r * D;             // from A_p to A_{p+1} (launch_ln_lora)
   if (x_f16 && !dy_bf16) return UCOD_EINVAL;                // (the fp16 stream comes with bf16 dgrad outputs: the driver's only use)
-#define L(n, vw, lora_, dyb_, xh_) hipLaunchKernelGGL((ln_bwd_kernel<n, vw, lora_, dyb_, xh_>), grid, block, 0, s, dy, x, gamma, dres, next_scale, dx, (bf16_raw*)s_bf16, rows, D, eps, tq, ldt, lora, r, drop)
+#define L(n, vw, lora_, dyb_, xh_) hipLaunchKernelGGL((ln_bwd_kernel<n, vw, lora_, dyb_, xh_>), grid, block, 0, s, dy, x, gamma, dres, next_scale, dx, (bf16_raw*)s_bf16, rows, D, eps, tq, ldt, lora, r, drop, astride)
 #define C(n, vw)                                                                                                                               \
   case n:                                                                                                                                      \
     if (lo && np == 1 && x_f16) L(n, vw, 1, true, true);                                                                                       \
     else if (lo && np == 1 && dy_bf16) L(n, vw, 1, true, false);                                                                               \
     else if (lo && np == 1) L(n, vw, 1, false, false);                                                                                         \
+    else if (lo && np == 2 && x_f16) L(n, vw, 2, true, true);                                                                                  \
+    else if (lo && np == 2 && dy_bf16) L(n, vw, 2, true, false);                                                                               \
+    else if (lo && np == 2) L(n, vw, 2, false, false);                                                                                         \
     else if (lo && x_f16) L(n, vw, 3, true, true);                                                                                             \
     else if (lo && dy_bf16) L(n, vw, 3, true, false);                                                                                          \
     else if (lo) L(n, vw, 3, false, false);                                                                                                    \
@@ -1151,6 +1163,274 @@ extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int fl
   UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
   return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
                        (const bf16_raw*)t_bf16, ldt, a_m, r, make_drop(dropout), (hipStream_t)stream, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LoRA on the gated MLP's input (DINOv3 vits16plus: down_proj(silu(gate_proj(x)) * up_proj(x)); full_model.py:47-72 hands target_modules to peft, to which
+// gate_proj and up_proj are TWO modules, each with its own A, B and dropout mask).  Both sit on the one fused, padded, 4-interleaved weights_in GEMM: engine row
+// 8k+e is gate row 4k+e for e < 4, row 8k+4+e is up row 4k+e.  Together they are a rank-2r module whose B is block diagonal:
+//   forward   h2_aug [M, D+64] = [ LN2(x) | drop_0(LN2 x) A_g^T (r) | drop_1(LN2 x) A_u^T (r) | 0 ]      (ucod_layernorm_lora_mlp_pair: ln_lora*_kernel with NP = 2)
+//             fc1_w_aug [N1, D+64]: row n carries alpha/r * B_m[n][:] at columns D + mod(n) r ..., mod(n) = (n % 8 >= 4); zeros elsewhere  (ucod_lora_mlp_pair_pack)
+//   backward  t_p = alpha/r * dpre[:, rows of p] B_p -> scratch [M, 64] at columns p r + j,  dB rows of p = alpha/r * dpre^T u_p,  dA_p = t_p^T drop_p(LN2 x)
+//             in ONE pass over dpre per two ranks (ucod_lora_mlp_pair_grad); d LN2 += sum_p mask_p/(1-p) (t_p A_p)  (ucod_layernorm_bwd_lora_mlp_pair: LORA = 2)
+// Parameter layout of one layer (f32): [A_g (r x D) | A_u (r x D) | B_m (N1 x r)], B_m in the engine's row order -- byte for byte the single module's B_m.
+// An untargeted module of the pair has A = 0 and its rows of B = 0; its gradients are then zero by structure (u = 0 gives dB = 0, t = 0 gives dA = 0), because no
+// sum here mixes the two modules' elements.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ucod {
+
+__global__ __launch_bounds__(256) void lora_mlp_pair_pack_kernel(const float* __restrict__ lora, int r, float scaling, bf16_raw* __restrict__ w_aug, int N1, int D) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;                // one thread per (row, aug column)
+  if (idx >= N1 * AUG) return;
+  const int n = idx / AUG, c = idx - n * AUG;
+  const int j = c - ((n & 4) ? r : 0);                           // rank within the row's own module (gate: n % 8 < 4)
+  const float v = (j >= 0 && j < r) ? scaling * lora[(size_t)2 * r * D + (size_t)n * r + j] : 0.f;
+  w_aug[(size_t)n * (D + AUG) + D + c] = f32_to_bf16(v);
+}
+
+// lora_mlp_grad_kernel for the pair.  A thread's 16-byte dpre vector holds four gate elements (0-3) and four up elements (4-7): bw / accB keep their shape, each
+// element taking u of its own module; the row sum s, the bf16-rounded t and accA carry a module index, dA of module p uses mask p.  t goes to columns p r + j of
+// the [M, 64] scratch.  Partials per block: [2][RW][D] | [N1][RW], summed in a fixed order by lora_mlp_pair_grad_reduce_kernel.
+template <int NVT, int NPT>
+__global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw* __restrict__ dpre, const bf16_raw* __restrict__ h, const float* __restrict__ lora,
+                                                                 int r, int j0, float scaling, float* __restrict__ partial, bf16_raw* __restrict__ tout, int rows,
+                                                                 int N1, int D, Drop drop) {
+  constexpr int RW = MLP_RW, RB = MLP_RB;
+  __shared__ float red[2][4][RB][2][RW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NV = N1 / 8, NP2 = D / 2, ldh = D + AUG;
+  const float* Bm = lora + (size_t)2 * r * D;
+  float bw[NVT][8][RW], accB[NVT][8][RW], accA[2][RW][NPT][2];
+#pragma unroll
+  for (int i = 0; i < NVT; ++i) {
+    const int v = tid + 256 * i;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int j = 0; j < RW; ++j) {
+        bw[i][e][j] = (v < NV && j0 + j < r) ? Bm[(size_t)(8 * v + e) * r + j0 + j] : 0.f;
+        accB[i][e][j] = 0.f;
+      }
+  }
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int j = 0; j < RW; ++j)
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) accA[m][j][i][0] = accA[m][j][i][1] = 0.f;
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  int buf = 0;
+  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB, buf ^= 1) {
+    u4 dw[RB][NVT];
+    unsigned hw_[RB][NPT];
+    float u[RB][2][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      const bool live = row0 + q < rows;
+      const int row = live ? row0 + q : rows - 1;
+      const u4* dr = reinterpret_cast<const u4*>(dpre + (size_t)row * N1);
+      const unsigned* hr = reinterpret_cast<const unsigned*>(h + (size_t)row * ldh);
+#pragma unroll
+      for (int i = 0; i < NVT; ++i) dw[q][i] = (live && tid + 256 * i < NV) ? dr[tid + 256 * i] : (u4)(0u);
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) hw_[q][i] = (live && tid + 256 * i < NP2) ? hr[tid + 256 * i] : 0u;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < RW; ++j)                                // (block-uniform address; j0 + j < r <= 8 keeps m r + j0 + j inside the 64 aug columns)
+          u[q][m][j] = (live && j0 + j < r) ? bf16_to_f32(h[(size_t)row * ldh + D + m * r + j0 + j]) : 0.f;
+    }
+    float t[RB][2][RW];
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      float s[2][RW];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < RW; ++j) s[m][j] = 0.f;
+#pragma unroll
+      for (int i = 0; i < NVT; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          constexpr int HALF = 2;                                  // words 0, 1 = elements 0-3 (gate), words 2, 3 = elements 4-7 (up)
+          const int m = w / HALF;
+          const float d0 = __uint_as_float(dw[q][i][w] << 16), d1 = __uint_as_float(dw[q][i][w] & 0xFFFF0000u);
+#pragma unroll
+          for (int j = 0; j < RW; ++j) {
+            s[m][j] += d0 * bw[i][2 * w][j] + d1 * bw[i][2 * w + 1][j];
+            accB[i][2 * w][j] += d0 * u[q][m][j];
+            accB[i][2 * w + 1][j] += d1 * u[q][m][j];
+          }
+        }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < RW; ++j) {
+          const float ws = wave_sum(s[m][j]);
+          if (lane == 0) red[buf][wave][q][m][j] = ws;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < RB; ++q)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int j = 0; j < RW; ++j)     // the LayerNorm-2 backward sees the bf16 value: use it for dA too
+          t[q][m][j] = bf16_to_f32(f32_to_bf16(scaling * ((red[buf][0][q][m][j] + red[buf][1][q][m][j]) + (red[buf][2][q][m][j] + red[buf][3][q][m][j]))));
+    // wave q writes the 64 t columns of row q: the first pass every column (zeros beyond 2 r), later passes their two per module.  Lane = m r + jj.
+#pragma unroll
+    for (int q = 0; q < RB; ++q) {
+      if (q != wave || row0 + q >= rows) continue;
+      const int m = lane >= r ? 1 : 0, c = lane - m * r - j0;      // c: this lane's rank within the pass
+      const bool mine = lane < 2 * r && c >= 0 && c < RW && j0 + c < r;
+      const float t0 = m ? t[q][1][0] : t[q][0][0], t1 = m ? t[q][1][1] : t[q][0][1];
+      const float val = mine ? (c == 0 ? t0 : t1) : 0.f;
+      if (j0 == 0 || mine) tout[(size_t)(row0 + q) * AUG + lane] = f32_to_bf16(val);
+    }
+#pragma unroll
+    for (int q = 0; q < RB; ++q)
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        const float h0 = __uint_as_float(hw_[q][i] << 16), h1 = __uint_as_float(hw_[q][i] & 0xFFFF0000u);
+        float k0[2] = {1.f, 1.f}, k1[2] = {1.f, 1.f};
+        if (drop.thresh) {                                       // dA_p sees the SAME dropped input the forward's lora_A of module p saw (one mix, two fields)
+          const unsigned idx = (unsigned)(row0 + q) * (unsigned)D + 2u * (unsigned)(tid + 256 * i);
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            k0[m] = drop_scale(drop, m, idx);
+            k1[m] = drop_scale(drop, m, idx + 1u);
+          }
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int j = 0; j < RW; ++j) {
+            accA[m][j][i][0] += t[q][m][j] * (h0 * k0[m]);
+            accA[m][j][i][1] += t[q][m][j] * (h1 * k1[m]);
+          }
+      }
+  }
+  float* out = partial + (size_t)blockIdx.x * (size_t)(2 * RW * D + N1 * RW);
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int j = 0; j < RW; ++j)
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        const int c = tid + 256 * i;
+        if (c < NP2) *reinterpret_cast<float2*>(out + (size_t)(m * RW + j) * D + 2 * c) = make_float2(accA[m][j][i][0], accA[m][j][i][1]);
+      }
+  out += 2 * RW * D;
+#pragma unroll
+  for (int i = 0; i < NVT; ++i) {
+    const int v = tid + 256 * i;
+    if (v >= NV) continue;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int e = 0; e < 8; e += 2)       // rows 8v+e, 8v+e+1 of [N1][2]: four consecutive floats
+      *reinterpret_cast<f4*>(out + (size_t)(8 * v + e) * RW) =
+          (f4){scaling * accB[i][e][0], scaling * accB[i][e][1], scaling * accB[i][e + 1][0], scaling * accB[i][e + 1][1]};
+  }
+}
+
+// partial [nblk][2 * 2 D + 2 N1] -> grad [A_g (r x D) | A_u (r x D) | B_m (N1 x r)], ranks [j0, j0 + 2): 32 elements x 8 slices of the block list per workgroup
+__global__ __launch_bounds__(256) void lora_mlp_pair_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int r, int j0, float* __restrict__ grad, int N1,
+                                                                        int D) {
+  constexpr int RW = MLP_RW;
+  __shared__ float red[8][33];
+  const int nA = 2 * RW * D, n = nA + N1 * RW;
+  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + e;
+  float s = 0.f;
+  if (i < n) {
+#pragma unroll 4
+    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
+  }
+  red[sl][e] = s;
+  __syncthreads();
+  if (sl != 0 || i >= n) return;
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += red[k][e];
+  if (i < nA) {
+    const int mj = i / D, d = i - mj * D, m = mj / RW, j = mj - m * RW;
+    if (j0 + j < r) grad[(size_t)m * r * D + (size_t)(j0 + j) * D + d] = s;
+  } else {
+    const int k = i - nA, row = k / RW, j = k - row * RW;
+    if (j0 + j < r) grad[(size_t)2 * r * D + (size_t)row * r + j0 + j] = s;
+  }
+}
+
+}  // namespace ucod
+
+extern "C" int ucod_layernorm_lora_mlp_pair(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_pair, int r, void* y_aug, int rows,
+                                            int D, float eps, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (r < 1 || r > UCOD_LORA_MLP_MAX_R) return UCOD_EINVAL;
+  return launch_ln_lora(x, x_f16 != 0, gamma, beta, a_pair, r, y_aug, rows, D, eps, dropout, stream, 2);
+}
+
+extern "C" int ucod_lora_mlp_pair_pack(const float* lora_pair, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!lora_pair || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || (N1 % 8) != 0 || D <= 0) return UCOD_EINVAL;
+  UCOD_PROF(PROF_LORA, stream);
+  hipLaunchKernelGGL(lora_mlp_pair_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora_pair, r, scaling, (bf16_raw*)fc1_w_aug, N1, D);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" size_t ucod_lora_mlp_pair_grad_workspace_bytes(int N1, int D) {
+  if (N1 <= 0 || N1 > 8192 || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
+  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (2 * D + N1)) * sizeof(float);
+}
+
+extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
+                                       void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!dpre || !h2_aug || !lora_pair || !grad_pair || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
+  const size_t need = ucod_lora_mlp_pair_grad_workspace_bytes(N1, D);
+  if (need == 0) return UCOD_EINVAL;
+  if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+  if (workspace_bytes < need) return UCOD_ENOMEM;
+  UCOD_PROF(PROF_LORA_MLP_GRAD, stream);
+  const Drop drop = make_drop(dropout);
+  hipStream_t s = (hipStream_t)stream;
+  const int cap = mlp_grad_max_blocks(N1);
+  const int nblk = cdiv(rows, MLP_RB) < cap ? cdiv(rows, MLP_RB) : cap;
+  const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors, 1..3 column pairs per thread
+  for (int j0 = 0; j0 < r; j0 += MLP_RW) {
+#define MG(v, p) hipLaunchKernelGGL((lora_mlp_pair_grad_kernel<v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora_pair, r, j0, \
+                                    scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
+#define MGP(v)                   \
+  do {                           \
+    if (npt == 1) MG(v, 1);      \
+    else if (npt == 2) MG(v, 2); \
+    else MG(v, 3);               \
+  } while (0)
+    if (nvt == 1) MGP(1);
+    else if (nvt == 2) MGP(2);
+    else MGP(4);                                                  // (3 vectors per thread run the 4-vector form: the fourth is never live)
+#undef MGP
+#undef MG
+    UCOD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lora_mlp_pair_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (2 * D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, r, j0, grad_pair,
+                       N1, D);
+    UCOD_CHECK_LAUNCH();
+  }
+  return UCOD_OK;
+}
+
+extern "C" int ucod_layernorm_bwd_lora_mlp_pair(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                                void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_pair, int r,
+                                                const ucod_lora_dropout* dropout, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!dy || !x || !gamma || (!dx && !s_bf16) || rows <= 0 || D <= 0 || (D % 128) != 0 || !t_bf16 || ldt < 2 * r || !a_pair || r < 1 || r > UCOD_LORA_MLP_MAX_R ||
+      (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) || (flags & ~3))
+    return UCOD_EINVAL;
+  UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
+  return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
+                       (const bf16_raw*)t_bf16, ldt, a_pair, r, make_drop(dropout), (hipStream_t)stream, 2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

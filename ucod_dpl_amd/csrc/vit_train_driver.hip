@@ -9,7 +9,8 @@
 // One body serves both forwards (`forward`; the four places where it asks `save` are all that differs), so they cannot drift apart: the same arithmetic, the same
 // dropout masks for the same seed.  A call is a Pass: the descriptor, the MLP kind, one word of flags and four tables, of which two are optional --
 //   T, TT   the plain rows and the training table: LoRA on q / k / v rides on the QKV GEMM as 64 extra K columns (operand formats of the "aug" columns: vit_train.hip)
-//   TM      LoRA on the MLP input projection (fc1 / weights_in): LayerNorm 2 writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against
+//   TM      LoRA on the MLP input projection (fc1 / weights_in; with UCOD_LORA_MLP_PAIR in the flags the gated MLP's two modules gate_proj / up_proj on the fused
+//           weights_in, the _pair forms of the three kernels below): LayerNorm 2 writes h2_aug [M, D+64] with the module's down-projection, fc1 runs with K = D+64 against
 //           fc1_w_aug; the backward recomputes h2_aug from the saved residual stream, takes the gradients from dpre (ucod_lora_mlp_grad) and adds t A_m in the
 //           LayerNorm-2 backward
 //   TO      LoRA on the output projections (attention.output.dense / mlp.fc2; o_proj / down_proj): their inputs have no aug columns, so each module is one row kernel
@@ -59,8 +60,14 @@ inline size_t up(size_t v) { return (v + 255) / 256 * 256; }
 inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_SWIGLU; }
 inline int fc1_width(const ucod_vit_desc* d, int mlp) { return mlp == UCOD_MLP_SWIGLU ? 2 * d->F : d->F; }
 // mlpl: the pass carries a LoRA module on the MLP input projection (its rank limit and the widths its gradient kernel covers)
-inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl) {
-  return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && ucod_lora_mlp_grad_workspace_bytes(fc1_width(&t->vit, mlp), t->vit.D) != 0);
+// pair (UCOD_LORA_MLP_PAIR): the table describes gate_proj / up_proj of the gated MLP -- only with UCOD_MLP_SWIGLU and a table
+inline size_t mlp_gw_bytes(const ucod_vit_train_desc* t, int mlp, bool pair) {
+  const int N1 = fc1_width(&t->vit, mlp);
+  return pair ? ucod_lora_mlp_pair_grad_workspace_bytes(N1, t->vit.D) : ucod_lora_mlp_grad_workspace_bytes(N1, t->vit.D);
+}
+inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl, bool pair) {
+  if (pair && !(mlpl && mlp == UCOD_MLP_SWIGLU)) return false;
+  return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && mlp_gw_bytes(t, mlp, pair) != 0);
 }
 // the output modules a table names (layer 0's parameter slots: the same modules in every layer), and whether the pass can carry them
 struct OutMods { bool o, f; };
@@ -71,7 +78,7 @@ inline size_t out_gw_bytes(const ucod_vit_train_desc* t, OutMods m) {
 }
 inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TO, int out_flags) {
   const OutMods m = out_mods(TO);
-  if (out_flags & ~UCOD_LORA_OUT_SWIGLU) return false;            // an unknown flag bit
+  if (out_flags & ~(UCOD_LORA_OUT_SWIGLU | UCOD_LORA_MLP_PAIR)) return false;   // an unknown flag bit
   if (!TO) return true;
   if (!m.o && !m.f) return false;                                 // a table that names no module
   // (SwiGLU: the hidden is recomputed from the interleaved, padded [M, 2F] pre-activation -- only with UCOD_LORA_OUT_SWIGLU)
@@ -88,7 +95,7 @@ bool valid(const Pass& c) {
          t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
          (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
          d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
-         known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr) && valid_out(t, c.mlp, c.TO, c.out_flags);
+         known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr, (c.out_flags & UCOD_LORA_MLP_PAIR) != 0) && valid_out(t, c.mlp, c.TO, c.out_flags);
 }
 
 Plan train_plan(const Pass& c) {
@@ -131,7 +138,7 @@ Plan train_plan(const Pass& c) {
   p.tm = p.mgw = p.mgw_bytes = 0;
   if (mlpl) {
     p.tm = take(M * UCOD_LORA_AUG * 2);
-    p.mgw_bytes = ucod_lora_mlp_grad_workspace_bytes((int)FP, d->D);
+    p.mgw_bytes = mlp_gw_bytes(t, c.mlp, (c.out_flags & UCOD_LORA_MLP_PAIR) != 0);
     p.mgw = take(p.mgw_bytes);
   }
   p.u_o = p.u_2 = p.s_u = p.t_out = p.ogw = p.ogw_bytes = 0;
@@ -233,7 +240,7 @@ int forward(const Pass& c, bool save, const float* img, float* key_out, void* wo
   if (!valid(c) || !c.T || !c.TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_train_desc* t = c.t;
   const ucod_vit_desc* d = &t->vit;
-  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU;
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = (c.out_flags & UCOD_LORA_MLP_PAIR) != 0;
   const Plan p = save ? train_plan(c) : infer_plan(c);
   const OutMods om = out_mods(c.TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
@@ -285,8 +292,9 @@ int forward(const Pass& c, bool save, const float* img, float* key_out, void* wo
     int fc1_k = D;
     if (c.TM) {   // LoRA on the MLP input projection: LayerNorm 2 + down-projection, fc1 over K = D+64 against fc1_w_aug
       const void* const* Y = c.TM + UCOD_VIT_TRAIN_MLP_STRIDE * l;
-      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D, d->eps,
-                                  dropout_of(t, MOD_MLP_IN, l).ptr(), stream));
+      // (UCOD_LORA_MLP_PAIR: the gated MLP's gate_proj / up_proj, two down-projections with masks 0 and 1 of the same key)
+      RUN((pair ? ucod_layernorm_lora_mlp_pair : ucod_layernorm_lora_mlp)(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], t->lora_r, h2, M, D,
+                                                                          d->eps, dropout_of(t, MOD_MLP_IN, l).ptr(), stream));
       fc1_w = Y[0];
       fc1_k = KA;
     } else {
@@ -311,7 +319,7 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   const void* const* TT = c.TT;
   const void* const* TM = c.TM;
   const void* const* TO = c.TO;
-  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU;
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = (c.out_flags & UCOD_LORA_MLP_PAIR) != 0;
   const Plan p = train_plan(c);
   const OutMods om = out_mods(TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
@@ -383,7 +391,7 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   // last layer: only the key projection reaches the loss (its MLP never runs: the module's gradients there are zeros, written as such)
   const int last = d->L - 1;
   if (TM) {
-    const size_t n_m = (size_t)r * (size_t)(D + N1) * sizeof(float);
+    const size_t n_m = (size_t)r * (size_t)((pair ? 2 : 1) * D + N1) * sizeof(float);
     if (hipMemsetAsync(const_cast<void*>((TM + UCOD_VIT_TRAIN_MLP_STRIDE * last)[2]), 0, n_m, (hipStream_t)stream) != hipSuccess) return UCOD_EINVAL;
   }
   if (TO) {   // (nor do its attention output and fc2: zeros, written as such)
@@ -437,12 +445,14 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
       // LoRA on the MLP input projection.  `s` (the fc2 dgrad's operand) has been consumed: its buffer takes h2_aug, recomputed from the saved residual
       // stream with the forward's launch (same mask), and is rewritten by the LayerNorm-2 backward below, after the gradient kernel has read it
       void* h2_aug = ws + p.h2;
-      RUN(ucod_layernorm_lora_mlp(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D, d->eps, drop_m.ptr(), stream));
-      RUN(ucod_lora_mlp_grad(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M, N1, D,
-                             drop_m.ptr(), stream));
+      // (UCOD_LORA_MLP_PAIR: the three calls take their _pair forms -- same arguments, [A_g | A_u | B_m] behind Y[1] / Y[2])
+      RUN((pair ? ucod_layernorm_lora_mlp_pair : ucod_layernorm_lora_mlp)(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D,
+                                                                          d->eps, drop_m.ptr(), stream));
+      RUN((pair ? ucod_lora_mlp_pair_grad : ucod_lora_mlp_grad)(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M, N1, D,
+                                                                drop_m.ptr(), stream));
     }
     RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, N1, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
-    if (TM) RUN(ucod_layernorm_bwd_lora_mlp(dh, x_mid, lnb_flags, (const float*)W[7], dx, (const float*)W[6], dx, s, M, D, d->eps, ws + p.tm, UCOD_LORA_AUG,
+    if (TM) RUN((pair ? ucod_layernorm_bwd_lora_mlp_pair : ucod_layernorm_bwd_lora_mlp)(dh, x_mid, lnb_flags, (const float*)W[7], dx, (const float*)W[6], dx, s, M, D, d->eps, ws + p.tm, UCOD_LORA_AUG,
                                             (const float*)Y[1], r, drop_m.ptr(), stream));
     else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward

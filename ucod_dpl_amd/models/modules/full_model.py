@@ -119,7 +119,9 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     only the SwiGLU MLP's output projection stays refused.  The build-only key ``allow_swiglu_out`` (default False; needs ``allow_out``, and ``allow_rope`` on a
     DINOv3 checkpoint) lifts that too: ``weights_out`` on DINOv2 ViT-g/14, ``down_proj`` on a gated DINOv3 checkpoint whose hidden width is at most 4096.
     A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
-    100, goes with it); its targets are subsets of q_proj / k_proj / v_proj.  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
+    100, goes with it); its targets are subsets of q_proj / k_proj / v_proj -- and, with the build-only key ``allow_mlp_in`` (default False), ``up_proj`` and the
+    gated MLP's ``gate_proj`` as well, so that with ``allow_out`` / ``allow_swiglu_out`` every Linear of a DINOv3 block is targetable (dinov3_vith16plus is refused
+    by name: its widths are beyond the kernels').  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
     trained too: ``ViTLoRAEngine``); "all" is refused with its reason and any other value is a ValueError, both before any device work.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
     r = getattr(config, "r", 2)
@@ -136,7 +138,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     return LoRABackbone(ViTLoRAEngine(state_dict, heads, r=r, lora_alpha=alpha, eps=eps, device=device, generator=generator, lora_dropout=drop, allow_swiglu=True,
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
                                       rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False)),
-                                      allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False)), bias=bias))
+                                      allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False)), bias=bias,
+                                      allow_mlp_in=bool(getattr(config, "allow_mlp_in", False))))
 
 
 class full_model(nn.Module):

@@ -58,6 +58,7 @@ LORA_OUT_W = 8                                              # include/ucod_dpl.h
 LORA_OUT_ACT_IDENTITY, LORA_OUT_ACT_GELU = 0, 1
 LORA_OUT_ACT_SWIGLU = 2                                     # include/ucod_dpl.h: UCOD_LORA_OUT_ACT_SWIGLU (x_in / cot are the interleaved [rows, 2K] pre-activation / dpre)
 LORA_OUT_SWIGLU = 1                                         # include/ucod_dpl.h: UCOD_LORA_OUT_SWIGLU (out_flags of the _lora_out_ex entry points)
+LORA_MLP_PAIR = 4                                           # include/ucod_dpl.h: UCOD_LORA_MLP_PAIR (the MLP table holds the gated MLP's gate_proj / up_proj pair)
 # the per-layer table of the trained biases' gradient destinations (bias="lora_only": the _lora_bias entry points); NULL = that bias is not trained
 VIT_TRAIN_BIAS_STRIDE = 6
 VIT_TRAIN_BIAS_SLOTS = ("gb_q", "gb_k", "gb_v", "gb_m", "gb_o", "gb_2")
@@ -198,6 +199,12 @@ SIGNATURES = {
     "ucod_lora_mlp_grad_workspace_bytes": (sz, [ci, ci]),
     "ucod_lora_mlp_grad": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
     "ucod_layernorm_bwd_lora_mlp": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, vp, ci, C.POINTER(LoraDropout), vp]),
+    # the gated MLP's pair gate_proj / up_proj on the fused weights_in: [A_g | A_u | B_m], two masks (LORA_MLP_PAIR selects them in the _lora_out_ex passes)
+    "ucod_layernorm_lora_mlp_pair": (ci, [vp, ci, vp, vp, vp, ci, vp, ci, ci, cf, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_mlp_pair_pack": (ci, [vp, ci, cf, vp, ci, ci, vp]),
+    "ucod_lora_mlp_pair_grad_workspace_bytes": (sz, [ci, ci]),
+    "ucod_lora_mlp_pair_grad": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_layernorm_bwd_lora_mlp_pair": (ci, [vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, cf, vp, ci, vp, ci, C.POINTER(LoraDropout), vp]),
     "ucod_vit_train_workspace_bytes_lora_mlp": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp)]),
     "ucod_vit_forward_train_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_vit_backward_lora_mlp": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),

@@ -824,9 +824,16 @@ _ENGINE_SLOTS = (((N.QKV_W, N.QKV_B, N.QKV_COLSUM, (N.LN1_G, N.LN1_B)),) * 3
                  + ((N.FC1_W, N.FC1_B, N.FC1_COLSUM, (N.LN2_G, N.LN2_B)), (N.PROJ_W, N.PROJ_B, None, None), (N.FC2_W, N.FC2_B, None, None)))
 
 
-def lora_module_paths(family, mlp="gelu"):
+_MLP_IN2 = _MLP_OUT + 1                                     # the gated DINOv3 MLP's second input module (``lora_module_paths`` with ``pair``), behind the six
+
+
+def lora_module_paths(family, mlp="gelu", pair=False):
     """The six modules' HF paths below ``{layer path}{i}.`` -- query, key, value, MLP input, attention output, MLP output -- of a checkpoint family ("dinov2": HF
-    Dinov2Model / ViTModel; "dinov3": DINOv3ViTModel, whose gated MLP keeps the plain one's names) and MLP kind ("gelu" | "swiglu")."""
+    Dinov2Model / ViTModel; "dinov3": DINOv3ViTModel, whose gated MLP keeps the plain one's names) and MLP kind ("gelu" | "swiglu").
+    ``pair`` (DINOv3's gated MLP, whose input is TWO peft modules on the one fused weights_in): seven paths -- ``mlp.gate_proj`` in the MLP input's place and
+    ``mlp.up_proj`` behind the six (``_MLP_IN2``), so that every index of the six keeps its meaning."""
+    if family == "dinov3" and pair:
+        return tuple("attention." + n for n in _QKV3) + ("mlp.gate_proj", "attention." + _OUT3[0], "mlp." + _OUT3[1], "mlp.up_proj")
     if family == "dinov3":
         return tuple("attention." + n for n in _QKV3) + ("mlp.up_proj", "attention." + _OUT3[0], "mlp." + _OUT3[1])
     return (tuple("attention.attention." + n for n in _QKV)
@@ -853,10 +860,33 @@ class LoRAModule(typing.NamedTuple):
     ln: tuple
     row0: int                  # its first row in that weight / bias (the fused QKV weight holds three modules)
     interleaved: bool          # rows in the engine's padded, interleaved order (SwiGLU ``weights_in``): B and the bias go through swiglu.lora_b_{to,from}_engine
+    part: int = None           # 0 / 1: gate_proj / up_proj of the gated DINOv3 MLP.  The two share ONE B block (``b``) and ONE bias of 2n rows in the fused weights_in's
+    #                            4-interleaved order -- row 8k + 4 part + e of the block is this module's row 4k + e (``n`` = the padded hidden width F, ``n_hf`` = F0)
 
     @property
     def leaf(self):
         return self.path.rsplit(".", 1)[-1]
+
+    @property
+    def nb(self):
+        """rows of the B block ``b`` and of the bias in the arena: ``n``, or 2n for a module that shares them with its partner (``part``)"""
+        return self.n if self.part is None else 2 * self.n
+
+    def get_rows(self, block):
+        """This module's rows of ``block`` [nb, c] (its B block, or its bias as [nb, 1], in the engine's order) as the checkpoint has them: [n_hf, c].  A copy where
+        the orders differ, the tensor itself where they agree."""
+        if self.part is None:
+            return self.rows_to_hf(block)
+        return block.reshape(self.n // 4, 2, 4, -1)[:, self.part].reshape(self.n, -1)[:self.n_hf]
+
+    def set_rows(self, block, v):
+        """The inverse: write ``v`` [n_hf, c] into this module's rows of ``block`` [nb, c] IN PLACE (padded rows: zeros; a partner's rows are not touched)."""
+        if self.part is None:
+            block.copy_(self.rows_from_hf(v))
+            return
+        rows = v.new_zeros(self.n, v.shape[1])
+        rows[:self.n_hf] = v
+        block.view(self.n // 4, 2, 4, -1)[:, self.part] = rows.view(self.n // 4, 4, -1)
 
     def a_to_hf(self, a):
         """A [r, k] as the checkpoint's names carry it, [r, k_hf]: the padded hidden units' columns (zeros) are dropped."""
@@ -873,33 +903,53 @@ class LoRAModule(typing.NamedTuple):
         return lora_b_to_engine(v) if self.interleaved else v
 
 
-def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 6):
+def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 7):
     """The module table of a LoRA engine: six ``LoRAModule`` in the order query, key, value, MLP input, attention output, MLP output.  Host only.
+    With SEVEN answers in ``hit`` (a gated DINOv3 checkpoint with one of gate_proj / up_proj targeted) the table has seven: ``mlp.gate_proj`` in the MLP input's
+    place, ``mlp.up_proj`` last; the two are peft modules of their own (own A, own rows of B, HF's names and shapes outside the arena) over one arena block
+    [A_g | A_u | B_m] where [A_m | B_m] would stand -- the layout of ucod_lora_mlp_pair_grad (include/ucod_dpl.h).
     ``family`` / ``mlp``: ``lora_module_paths``; ``D``: the width; ``F`` / ``F0``: the MLP's hidden width in the engine (SwiGLU: padded) and in the checkpoint;
     ``r``: the rank; ``hit``: which of the six are targeted (``resolve_lora_targets``); ``bias``: peft's mode; ``has_bias``: which have a bias in the checkpoint.
     A layer's arena row is  [A_q | B_q | A_k | B_k | A_v | B_v]  -- always, an untargeted one's at zero --, then [A | B] of the MLP input, the attention output and
     the MLP output where targeted, then (bias="lora_only") the biases of the targeted modules that have one, in the same order (``lora_row_numel``)."""
     swiglu = mlp == "swiglu"
     N1, N0 = (2 if swiglu else 1) * F, (2 if swiglu else 1) * F0
+    pair = len(hit) > _MLP_IN2                                   # seven answers: the gated DINOv3 MLP's gate_proj / up_proj (``lora_module_paths`` with ``pair``)
+    if pair and not (family == "dinov3" and swiglu):
+        raise ValueError("a seventh module exists on a DINOv3 checkpoint with the gated MLP only")
     shapes = ((D, D, D, D),) * 3 + ((D, N1, D, N0), (D, D, D, D), (F, D, F0, D))          # (k, n, k_hf, n_hf)
     mods, at, col = [], 0, 0
-    for j, (path, (k, n, k_hf, n_hf)) in enumerate(zip(lora_module_paths(family, mlp), shapes)):
+    for j, (path, (k, n, k_hf, n_hf)) in enumerate(zip(lora_module_paths(family, mlp, pair), shapes)):
         a = b = None
+        if pair and j == _MLP_IN:
+            # the pair's one arena block [A_g | A_u | B_m (N1 x r)], there whenever one of the two is targeted (the other's A and rows of B then stay zero); this
+            # entry is gate_proj, its partner (built below, behind the six) up_proj: each has its own A, both name the B block and the fused bias
+            a, a_up, b = slice(at, at + r * k), slice(at + r * k, at + 2 * r * k), slice(at + 2 * r * k, at + r * (2 * k + N1))
+            at = b.stop
+            mods.append(LoRAModule(path, bool(hit[j]), k, F, k_hf, F0, a, b, None, slice(col, col + N1), *_ENGINE_SLOTS[j], 0, False, 0))
+            col += N1
+            continue
         if j <= _V or hit[j]:
             a, b = slice(at, at + r * k), slice(at + r * k, at + r * (k + n))
             at = b.stop
         mods.append(LoRAModule(path, bool(hit[j]), k, n, k_hf, n_hf, a, b, None, slice(col, col + n), *_ENGINE_SLOTS[j], j * D if j <= _V else 0,
                                swiglu and j == _MLP_IN))
         col += n
+    if pair:
+        g = mods[_MLP_IN]
+        mods.append(g._replace(path=lora_module_paths(family, mlp, True)[_MLP_IN2], targeted=bool(hit[_MLP_IN2]), a=a_up, part=1))
     for j, m in enumerate(mods):
         if bias == "lora_only" and m.targeted and has_bias[j]:
-            mods[j], at = m._replace(bias_off=at), at + m.n
+            if m.part == 1 and mods[_MLP_IN].bias_off is not None:
+                mods[j] = m._replace(bias_off=mods[_MLP_IN].bias_off)        # (the fused bias: one slot for both)
+            else:
+                mods[j], at = m._replace(bias_off=at), at + m.nb
     return tuple(mods)
 
 
 def lora_row_numel(mods):
     """Length of a layer's arena row."""
-    return max([m.b.stop for m in mods if m.b is not None] + [m.bias_off + m.n for m in mods if m.bias_off is not None])
+    return max([m.b.stop for m in mods if m.b is not None] + [m.bias_off + m.nb for m in mods if m.bias_off is not None])
 
 
 # ---- target_modules -> which of the six --------------------------------------------------------------------------------------------------------------------------
@@ -921,6 +971,11 @@ _REFUSED3 = {                                                # DINOv3 names (``a
     "gate_proj": "the gated MLP's input is two peft modules (gate_proj, up_proj) on the one fused weights_in GEMM: a LoRA module on one of them alone is not built",
     "patch_embeddings": "the patch embedding is a convolution over im2col rows, not a LayerNorm output",
 }
+_MLP_IN3 = ("gate_proj", "up_proj")                          # DINOv3's MLP input modules: what ``allow_mlp_in`` lifts
+# (what their refusals say now that they are built: the messages above stay, with the way in behind them)
+_MLP_IN_OPT_IN = (".  It runs only with the opt-in allow_mlp_in=True: up_proj on the fc1 GEMM's 64 extra K columns, the gated MLP's gate_proj / up_proj as a pair "
+                  "of modules with a block-diagonal B (ucod_lora_mlp_pair_grad)")
+LORA_MLP_MAX_N1 = 8192                                       # include/ucod_dpl.h: the most rows of the MLP input weight its gradient kernels take
 _DINOV2_LEAVES = ("query", "key", "value", "dense", "fc1", "fc2", "weights_in", "weights_out", "projection")
 
 
@@ -949,18 +1004,24 @@ def _dinov2_names(mlp, allow_out, allow_swiglu_out):
     return _Names("encoder.layer.", lora_module_paths("dinov2", mlp), (), "embeddings.patch_embeddings.projection", refused, "query / key / value", foreign, mlp == "swiglu")
 
 
-def _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out):
+def _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out, allow_mlp_in=False):
     refused = _REFUSED3
     if allow_out:
         refused = {k: v for k, v in _REFUSED3.items() if k not in _OUT3}
         if gated and not allow_swiglu_out:
             refused["down_proj"] = _SWIGLU_OUT_OPT_IN
+    if allow_mlp_in:       # (on the plain MLP ``gate_proj`` names no module: its reason stays in the table for the "no such module" refusal)
+        refused = {k: v for k, v in refused.items() if k not in (_MLP_IN3 if gated else _MLP_IN3[1:])}
+    else:
+        refused = dict(refused, **{k: _REFUSED3[k] + _MLP_IN_OPT_IN for k in _MLP_IN3})
 
     def foreign(t, last):
         if last in _DINOV2_LEAVES:
             return (f"target module {t!r} is a DINOv2 name: a DINOv3 checkpoint's attention projections are q_proj / k_proj / v_proj "
                     f"({layer_path}{{i}}.attention.{{q,k,v}}_proj)")
 
+    if gated and allow_mlp_in:                                   # seven modules to choose from: gate_proj in the MLP input's place, up_proj behind the six
+        return _Names(layer_path, lora_module_paths("dinov3", "swiglu", True), (), "embeddings.patch_embeddings", refused, "q_proj / k_proj / v_proj", foreign, True)
     return _Names(layer_path, lora_module_paths("dinov3"), ("mlp.gate_proj",) if gated else (), "embeddings.patch_embeddings", refused, "q_proj / k_proj / v_proj",
                   foreign, bool(gated))
 
@@ -975,6 +1036,18 @@ def _check_swiglu_out_width(name, hidden):
     if hidden is not None and padded_hidden(hidden) > LORA_OUT_MAX_K:
         raise NotImplementedError(f"LoRA target module {name!r} is not built for this checkpoint: its input width K = {padded_hidden(hidden)} (the MLP's hidden width "
                                   f"{hidden}, padded) is beyond the kernels' K <= {LORA_OUT_MAX_K} -- a thread keeps the A values of its hidden units in registers")
+
+
+def _check_mlp_in_width(name, hidden, gated):
+    """A DINOv3 MLP input module is targeted: refuse, by name and before anything touches the device, a checkpoint whose MLP input weight has more rows than the
+    gradient kernels take (dinov3_vith16plus: hidden 5120, gated, N1 = 2 x 5120 = 10240)."""
+    if hidden is None:
+        return
+    n1 = 2 * padded_hidden(hidden) if gated else hidden
+    if n1 > LORA_MLP_MAX_N1:
+        raise NotImplementedError(f"LoRA target module {name!r} is not built for this checkpoint: its MLP input weight has N1 = {n1} rows (hidden width {hidden}"
+                                  f"{', gate and up fused' if gated else ''}), beyond the gradient kernels' N1 <= {LORA_MLP_MAX_N1} -- a thread keeps the B values of "
+                                  f"its rows in registers (dinov3_vith16plus is the one such checkpoint)")
 
 
 def resolve_lora_targets(target_modules, names, n_layers, hidden=None):
@@ -1012,6 +1085,9 @@ def resolve_lora_targets(target_modules, names, n_layers, hidden=None):
         raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
     if names.swiglu and names.paths[_MLP_OUT] in per_layer[0]:
         _check_swiglu_out_width(names.paths[_MLP_OUT].rsplit(".", 1)[-1], hidden)
+    for p in names.paths[_MLP_IN:_MLP_IN + 1] + names.paths[_MLP_IN2:]:
+        if p in per_layer[0] and p.rsplit(".", 1)[-1] in _MLP_IN3:
+            _check_mlp_in_width(p.rsplit(".", 1)[-1], hidden, names.swiglu)
     return tuple(p in per_layer[0] for p in names.paths)
 
 
@@ -1037,15 +1113,22 @@ def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False, a
     return (hit[:3], mlp_hit, _out_leaves(names, hit)) if allow_out else (hit[:3], mlp_hit)
 
 
-def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False, allow_swiglu_out=False, hidden=None):
+def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False, allow_swiglu_out=False, hidden=None,
+                        allow_mlp_in=False):
     """``resolve_lora_targets`` on a DINOv3 checkpoint's names, ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj`` too):
-    any non-empty subset of q_proj / k_proj / v_proj.  Returns the (q, k, v) booleans; no MLP input module is built.
+    any non-empty subset of q_proj / k_proj / v_proj.  Returns the (q, k, v) booleans; without ``allow_mlp_in`` no MLP input module is accepted.
     ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` and returns ((q, k, v), the accepted ones of ("o_proj", "down_proj")); the
-    gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well (dinov3_vith16plus, hidden 5120, is refused)."""
+    gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well (dinov3_vith16plus, hidden 5120, is refused).
+    ``allow_mlp_in=True`` also accepts ``up_proj`` and, on the gated MLP, ``gate_proj`` (``gate_proj`` on a plain MLP stays refused; with ``hidden`` given,
+    dinov3_vith16plus -- N1 = 10240 rows against the kernels' 8192 -- is refused by name) and returns one more element behind the others: the accepted ones of
+    ("gate_proj", "up_proj"), in that order."""
     _check_swiglu_out(allow_out, allow_swiglu_out)
-    names = _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out)
+    names = _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out, allow_mlp_in)
     hit = resolve_lora_targets(target_modules, names, n_layers, hidden)
-    return (hit[:3], _out_leaves(names, hit)) if allow_out else hit[:3]
+    if not allow_mlp_in:
+        return (hit[:3], _out_leaves(names, hit)) if allow_out else hit[:3]
+    mlp_in = tuple(names.paths[j].rsplit(".", 1)[-1] for j in (_MLP_IN, _MLP_IN2) if j < len(hit) and hit[j])
+    return (hit[:3], _out_leaves(names, hit), mlp_in) if allow_out else (hit[:3], mlp_in)
 
 
 def _dinov3_paths(sd):
@@ -1067,18 +1150,26 @@ def _hf_prefix(sd):
                               "target_modules are matched against")
 
 
-def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False, allow_swiglu_out=False, canon=None):
+def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False, allow_swiglu_out=False, canon=None, allow_mlp_in=False):
     """Host only: (layer path, module table) of a ``ViTLoRAEngine`` over ``state_dict`` -- the family's names, ``resolve_lora_targets`` with all its refusals,
-    which modules have a bias in the checkpoint (DINOv3 ``k_proj`` has none), ``lora_modules``.  ``canon``: ``normalize_state_dict(state_dict)`` if at hand."""
+    which modules have a bias in the checkpoint (DINOv3 ``k_proj`` has none), ``lora_modules``.  ``canon``: ``normalize_state_dict(state_dict)`` if at hand.
+    ``allow_mlp_in`` (DINOv3 only; a DINOv2 checkpoint's MLP input needs no opt-in): ``lora_targets_dinov3``."""
     c = normalize_state_dict(state_dict) if canon is None else canon
     mlp = "swiglu" if c.get("mlp") == "swiglu" else "gelu"
     F0 = c["layers"][0]["fc1_w"].shape[0] // (2 if mlp == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
     sw_out = bool(allow_swiglu_out and mlp == "swiglu")           # (on a GELU checkpoint the opt-in changes nothing: weights_out keeps its refusal's text)
+    mlp_in3 = bool(allow_mlp_in and c.get("rope"))
     if c.get("rope"):
-        family, names = "dinov3", _dinov3_names(mlp == "swiglu", _dinov3_paths(state_dict)[1], allow_out, sw_out)
+        family, names = "dinov3", _dinov3_names(mlp == "swiglu", _dinov3_paths(state_dict)[1], allow_out, sw_out, mlp_in3)
     else:
         family, names = "dinov2", _dinov2_names(mlp, allow_out, sw_out)
-    hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out else None)
+    hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out or mlp_in3 else None)
+    if len(hit) > _MLP_IN2 and not (hit[_MLP_IN] or hit[_MLP_IN2]):         # neither of the gated pair: the table of six, as without the opt-in
+        hit, names = hit[:_MLP_IN2], names._replace(paths=lora_module_paths(family))
+    if len(hit) > _MLP_IN2 and bias == "lora_only" and hit[_MLP_IN] != hit[_MLP_IN2]:
+        raise NotImplementedError("LoRA bias='lora_only' with exactly one of gate_proj / up_proj targeted is not built: the two share the ONE fused bias of the "
+                                  "engine's weights_in GEMM, and its gradient (the column sums of the pre-activation's cotangent) is computed over all of its 2F "
+                                  "columns; target both, or neither, or use bias='none'")
     try:
         pref = _hf_prefix(state_dict)
     except NotImplementedError:                     # (a layout without HF module names: every Linear of it has a bias)
@@ -1118,9 +1209,16 @@ class ViTLoRAEngine(ViTEngine):
 
         module             DINOv2 (``encoder.layer.{i}.``)            DINOv3 (``{model.,}layer.{i}.``)   input   needs
         query, key, value  attention.attention.{query,key,value}      attention.{q,k,v}_proj             D       --
-        MLP input          mlp.fc1 | mlp.weights_in (SwiGLU)          (mlp.up_proj: not built)           D       r <= 8
+        MLP input          mlp.fc1 | mlp.weights_in (SwiGLU)          mlp.up_proj; gated: mlp.gate_proj  D       r <= 8; DINOv3: allow_mlp_in
+                                                                      and mlp.up_proj, a seventh entry
         attention output   attention.output.dense                     attention.o_proj                   D       allow_out, r <= 8
         MLP output         mlp.fc2 | mlp.weights_out (SwiGLU)         mlp.down_proj                      F       allow_out (SwiGLU / gated: + allow_swiglu_out), r <= 8
+
+    DINOv3's gated MLP (vits16plus) has TWO input modules, ``mlp.gate_proj`` and ``mlp.up_proj``, on the engine's one fused, padded, 4-interleaved weights_in.  With
+    ``allow_mlp_in`` and one of them targeted the table has seven entries -- gate_proj in the MLP input's place, up_proj behind the six (``_MLP_IN2``) --: each is a
+    peft module of its own (own A, own rows of B, own dropout mask, HF's names and shapes outside the arena), both name ONE arena block and the one fused bias
+    (``LoRAModule.part`` / ``get_rows`` / ``set_rows``), and the passes run the pair kernels (include/ucod_dpl.h: ucod_lora_mlp_pair_grad, UCOD_LORA_MLP_PAIR).  A
+    hidden width whose fused weight has more than 8192 rows (dinov3_vith16plus: 2 x 5120) is refused by name.
 
     ``target_modules`` (``resolve_lora_targets``, peft's suffix rule) picks among them; None = query / key / value.  Parameters live in ONE flat f32 arena
     ``self.lora`` [L, P], gradients in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel.  A layer's row:
@@ -1128,6 +1226,8 @@ class ViTLoRAEngine(ViTEngine):
         [A_q | B_q | A_k | B_k | A_v | B_v]   always; an untargeted projection's A and B are held at zero -- their gradients are then zero by structure
                                               (t = s dqkv B = 0 gives dA = 0, u = 0 gives dB = 0) and the fused AdamW leaves an exact zero at zero
         [A_m (r x D) | B_m (N1 x r)]          if the MLP input is targeted; N1 = F (GELU) or 2F in the engine's padded, interleaved row order (SwiGLU)
+        [A_g | A_u (r x D each) | B_m]        instead, if gate_proj or up_proj of the gated DINOv3 MLP is: row n of B_m is gate_proj's iff n % 8 < 4; an untargeted
+                                              one of the two keeps A = 0 and its rows of B = 0 -- its gradients are zero by structure, as for q / k / v
         [A_o (r x D) | B_o (D x r)]           if the attention output is targeted
         [A_2 (r x F) | B_2 (D x r)]           if the MLP output is targeted; SwiGLU: F is the padded hidden width, the padded columns are zeros in the arena and
                                               absent outside it (the state dicts and the adapter folder carry A_2 as HF has it, [r, F0])
@@ -1137,7 +1237,8 @@ class ViTLoRAEngine(ViTEngine):
     recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU; ``_out_flags`` carries UCOD_LORA_OUT_SWIGLU only when the
     module is targeted), and a hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers.
 
-    ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66) changes nothing else: forward = base(x) + scaling B(A(drop(x))) with the base layer's own
+    ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66; with exactly one of gate_proj / up_proj targeted it is refused: the two share the fused
+    bias) changes nothing else: forward = base(x) + scaling B(A(drop(x))) with the base layer's own
     bias, which dropout does not touch.  The trained biases start at the checkpoint's values (the MLP input's N1 values in the engine's order, padding zero).  The
     backward writes their gradients -- column sums of cotangents it already holds (include/ucod_dpl.h: ucod_colsum_det, ucod_vit_backward_lora_bias) -- into the same
     slots of the gradient arena; ``repack`` copies the arena's biases into the engine's own bias vectors, which (with ``clone_for_ema``'s) are private copies in that
@@ -1147,7 +1248,7 @@ class ViTLoRAEngine(ViTEngine):
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False,
-                 bias="none"):
+                 bias="none", allow_mlp_in=False):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
@@ -1156,7 +1257,9 @@ class ViTLoRAEngine(ViTEngine):
         ucod_vit_train_desc.allow_rope); a gated-MLP checkpoint (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``lora_cfg.allow_rope``.
         ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``.
         ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``).
-        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``."""
+        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``.
+        ``allow_mlp_in``: on a DINOv3 checkpoint, let ``target_modules`` name the MLP input modules -- ``up_proj``, and ``gate_proj`` on the gated MLP (class
+        docstring).  On a DINOv2 checkpoint it changes nothing.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_mlp_in``."""
         check_lora_bias(bias)
         canon = normalize_state_dict(state_dict)
         if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
@@ -1164,10 +1267,10 @@ class ViTLoRAEngine(ViTEngine):
         if canon.get("rope") and not allow_rope:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a DINOv3 checkpoint (rotary position embedding, RoPE: the passes rotate q / k and "
                                       "rotate dq / dk back) only with allow_rope=True")
-        self.allow_rope, self.allow_out, self.allow_swiglu_out = bool(allow_rope), bool(allow_out), bool(allow_swiglu_out)
+        self.allow_rope, self.allow_out, self.allow_swiglu_out, self.allow_mlp_in = bool(allow_rope), bool(allow_out), bool(allow_swiglu_out), bool(allow_mlp_in)
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
-        self._adopt(*lora_layout(state_dict, r, target_modules, bias, allow_out, allow_swiglu_out, canon=canon), bias)
+        self._adopt(*lora_layout(state_dict, r, target_modules, bias, allow_out, allow_swiglu_out, canon=canon, allow_mlp_in=allow_mlp_in), bias)
         if canon.get("mlp") == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
                                       "allow_swiglu=True (models/modules/full_model.py: load_lora passes it); the frozen-backbone engines (ViTEngine / "
@@ -1192,13 +1295,13 @@ class ViTLoRAEngine(ViTEngine):
                              f"(include/ucod_dpl.h, ucod_layernorm_lora)")
         self.r, self.scaling = int(r), float(lora_alpha) / float(r)
         D, L, dev = self.D, self.L, self.device
-        mlp_in, outs = self.modules[_MLP_IN], self.modules[_ATTN_OUT:]
-        if mlp_in.targeted:
+        mlp_in, outs = self.modules[_MLP_IN], self.modules[_ATTN_OUT:_MLP_IN2]
+        if self.mlp_in_live:
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with the MLP input projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its gradient kernel keeps a "
                                  f"lane's B values and accumulators in registers)")
-            if self.lib.ucod_lora_mlp_grad_workspace_bytes(mlp_in.n, D) == 0:
-                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {mlp_in.n} <= 8192 rows of {mlp_in.leaf}")
+            if (self.lib.ucod_lora_mlp_pair_grad_workspace_bytes if self.mlp_pair else self.lib.ucod_lora_mlp_grad_workspace_bytes)(self.N1, D) == 0:
+                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= 8192 rows of {mlp_in.leaf}")
         for m in outs:
             if not m.targeted:
                 continue
@@ -1213,18 +1316,23 @@ class ViTLoRAEngine(ViTEngine):
             self._setup_bias()
         self.lora = torch.zeros(L, self.numel, dtype=torch.float32, device=dev)
         # A: kaiming_uniform_(a=sqrt(5)) on [r, fan_in] = U(-1/sqrt(fan_in), 1/sqrt(fan_in)), B zeros.  q / k / v are drawn as one tensor whether targeted or not (an
-        # untargeted projection keeps A = B = 0), then the MLP input, then the output modules: an engine without the later ones keeps its stream.
+        # untargeted projection keeps A = B = 0), then the MLP input, then the output modules, then the gated DINOv3 pair (gate_proj, up_proj; an untargeted one of
+        # the two keeps A = 0 and its rows of B = 0): an engine without the later ones keeps its stream.
         bound = 1.0 / math.sqrt(D)
         a = (torch.rand(L, 3, r * D, generator=generator) * 2 - 1) * bound
         for p, m in enumerate(self.modules[:_MLP_IN]):
             if m.targeted:
                 self.lora[:, m.a] = a[:, p].to(dev)
-        if mlp_in.targeted:
+        if mlp_in.targeted and not self.mlp_pair:
             self.lora[:, mlp_in.a] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
         for m in outs:
             if m.targeted:                              # (SwiGLU, padded: fan_in is the checkpoint's own width F0, the padded columns stay zero)
                 a = (torch.rand(L, r, m.k_hf, generator=generator) * 2 - 1) / math.sqrt(m.k_hf)
                 self.lora[:, m.a] = m.a_from_hf(a).reshape(L, r * m.k).to(dev)
+        if self.mlp_pair:
+            for m in (mlp_in, self.modules[_MLP_IN2]):
+                if m.targeted:
+                    self.lora[:, m.a] = ((torch.rand(L, r * D, generator=generator) * 2 - 1) * bound).to(dev)
         self._bias_init_arena()
         self.lora_grad = torch.zeros_like(self.lora)
         A = N.LORA_AUG
@@ -1237,9 +1345,9 @@ class ViTLoRAEngine(ViTEngine):
             # (SwiGLU: fc1_w is the padded, interleaved weights_in [2F, D] -- its transpose's K order is the column order of the pre-activation's cotangent)
             self.train_layers.append([w_aug, wt_aug] + [l[w].t().contiguous() for w in (N.PROJ_W, N.FC1_W, N.FC2_W)])
         self.mlp_layers = []                            # native.VIT_TRAIN_MLP_SLOTS without the two LoRA slots: the augmented fc1 / weights_in weight
-        if mlp_in.targeted:
+        if self.mlp_in_live:
             for l in self.layers:
-                w_aug = torch.zeros(mlp_in.n, D + A, dtype=torch.bfloat16, device=dev)
+                w_aug = torch.zeros(self.N1, D + A, dtype=torch.bfloat16, device=dev)
                 w_aug[:, :D] = l[N.FC1_W]
                 self.mlp_layers.append([w_aug])
         self.train_streams = 2                          # image-parallel sub-batches of the training passes (_chunks)
@@ -1255,15 +1363,21 @@ class ViTLoRAEngine(ViTEngine):
         self._layer_path, self.bias, self._bias_flat = layer_path, bias, None
         self.numel = lora_row_numel(mods)
         self.targets = tuple(m.targeted for m in mods[:_MLP_IN])                 # (query, key, value)
-        self.mlp_target = mods[_MLP_IN].leaf if mods[_MLP_IN].targeted else None
-        self.out_targets = tuple(m.targeted for m in mods[_ATTN_OUT:])           # (attention output projection, MLP output projection)
+        self.mlp_pair = len(mods) > _MLP_IN2                                     # the gated DINOv3 MLP's gate_proj / up_proj: one arena block, the _pair kernels
+        mlp_ins = [m for m in (mods[_MLP_IN],) + mods[_MLP_IN2:] if m.targeted]
+        self.mlp_in_live = bool(mlp_ins)                                         # the passes carry the MLP table
+        self.mlp_target = mlp_ins[0].leaf if mlp_ins else None                   # (the pair: the first targeted of gate_proj, up_proj; ``modules`` names both)
+        self.out_targets = tuple(m.targeted for m in mods[_ATTN_OUT:_MLP_IN2])   # (attention output projection, MLP output projection)
         self.qkv_numel = mods[_V].b.stop
-        self.out_off = [m.a.start if m.targeted else None for m in mods[_ATTN_OUT:]]
-        self.bias_off = tuple(m.bias_off for m in mods)
-        self.bias_numel = sum(m.n for m in mods if m.bias_off is not None)
-        self.N1, self._F0 = mods[_MLP_IN].n, mods[_MLP_OUT].k_hf                 # rows of the MLP input weight in the engine; the checkpoint's own hidden width
-        # (the flags word of the passes: set only with the SwiGLU MLP's output projection targeted)
-        self._out_flags = N.LORA_OUT_SWIGLU if mods[_MLP_OUT].targeted and mods[_MLP_IN].interleaved else 0
+        self.out_off = [m.a.start if m.targeted else None for m in mods[_ATTN_OUT:_MLP_IN2]]
+        self.bias_off = tuple(m.bias_off for m in mods[:_MLP_IN2])               # (the bias table's six slots; the pair's fused bias is the MLP input's)
+        self.bias_numel = sum(m.nb for m in mods if m.bias_off is not None and m.part != 1)
+        if self.mlp_pair and mods[_MLP_IN].bias_off != mods[_MLP_IN2].bias_off:
+            raise ValueError("the fused bias of gate_proj / up_proj is trained for both or for neither (lora_layout refuses the rest)")
+        self.N1, self._F0 = mods[_MLP_IN].nb, mods[_MLP_OUT].k_hf                 # rows of the MLP input weight in the engine; the checkpoint's own hidden width
+        # (the flags word of the passes: a bit for the SwiGLU MLP's output projection and one for the gated pair, each set only with its module targeted)
+        swiglu = mods[_MLP_IN].interleaved or self.mlp_pair                      # (the MLP input's rows are interleaved: whole, or as the pair's two halves)
+        self._out_flags = (N.LORA_OUT_SWIGLU if mods[_MLP_OUT].targeted and swiglu else 0) | (N.LORA_MLP_PAIR if self.mlp_pair else 0)
 
     def _slices(self, j):
         """(A, B) of module ``j`` in one layer's arena row."""
@@ -1307,7 +1421,8 @@ class ViTLoRAEngine(ViTEngine):
 
     def _bias_live(self):
         """(module, its arena columns, the layers below the frozen ones) of every trained bias"""
-        return [(m, slice(m.bias_off, m.bias_off + m.n), self.L if j == _K else self.L - 1) for j, m in enumerate(self.modules) if m.bias_off is not None]
+        return [(m, slice(m.bias_off, m.bias_off + m.nb), self.L if j == _K else self.L - 1) for j, m in enumerate(self.modules)
+                if m.bias_off is not None and m.part != 1]                # (the pair's fused bias once, at gate_proj's entry)
 
     def _bias_init_arena(self):
         """Trained biases start at the checkpoint's values; a slot that cannot receive a gradient (``_bias_frozen``) stays zero."""
@@ -1321,11 +1436,11 @@ class ViTLoRAEngine(ViTEngine):
             self._bias_flat[:Lj, m.bias_cols].copy_(self.lora[:Lj, o])
 
     def _bias_value(self, i, j, src=None):
-        """The bias of module ``j`` in layer ``i`` as the engine orders it: from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
+        """The bias of module ``j`` in layer ``i`` as the engine orders it (gate_proj / up_proj: the fused bias, ``LoRAModule.nb`` values): from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
         m = self.modules[j]
         if self._bias_frozen(i, j):
             return self._bias_flat[i, m.bias_cols]
-        return (self.lora if src is None else src)[i, m.bias_off:m.bias_off + m.n]
+        return (self.lora if src is None else src)[i, m.bias_off:m.bias_off + m.nb]
 
     def _bias_table(self, grad):
         """The bias table of the backward (native.VIT_TRAIN_BIAS_SLOTS: gradient destinations in ``grad`` [L, P]; NULL = not trained), or None without one."""
@@ -1348,11 +1463,11 @@ class ViTLoRAEngine(ViTEngine):
         for i in range(self.L):
             for path, m in self._targeted():
                 out[f"{prefix}{i}.{path}.lora_A.weight"] = m.a_to_hf(src[i, m.a].reshape(self.r, m.k)).clone()
-                out[f"{prefix}{i}.{path}.lora_B.weight"] = m.rows_to_hf(src[i, m.b].reshape(m.n, self.r)).clone()
+                out[f"{prefix}{i}.{path}.lora_B.weight"] = m.get_rows(src[i, m.b].reshape(m.nb, self.r)).clone()
             for j, m in enumerate(self.modules):
                 if m.bias_off is not None:
-                    v = torch.zeros(m.n, device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
-                    out[f"{prefix}{i}.{m.path}.bias"] = m.rows_to_hf(v.reshape(-1, 1)).reshape(-1).clone()
+                    v = torch.zeros(m.nb, device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
+                    out[f"{prefix}{i}.{m.path}.bias"] = m.get_rows(v.reshape(-1, 1)).reshape(-1).clone()
         return out
 
     def load_lora_state_dict(self, sd, prefix=None):
@@ -1374,14 +1489,15 @@ class ViTLoRAEngine(ViTEngine):
                     raise ValueError(f"{base}.lora_B.weight has shape {tuple(b.shape)}")
                 if tuple(a.shape) != (self.r, m.k_hf) or tuple(b.shape) != (m.n_hf, self.r):
                     raise ValueError(f"{base}: lora_A has shape {tuple(a.shape)}, lora_B {tuple(b.shape)}")
-                self.lora[i, m.a], self.lora[i, m.b] = m.a_from_hf(a).reshape(-1), m.rows_from_hf(b).reshape(-1)      # (padded units load as zeros)
+                self.lora[i, m.a] = m.a_from_hf(a).reshape(-1)
+                m.set_rows(self.lora[i, m.b].view(m.nb, self.r), b)              # (padded units load as zeros)
             for j, m in enumerate(self.modules):
                 if m.bias_off is not None:
                     name = f"{prefix}{i}.{m.path}.bias"
                     v = take(name)
                     if tuple(v.shape) != (m.n_hf,):
                         raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(m.n_hf,)}")
-                    self._bias_value(i, j).copy_(m.rows_from_hf(v.reshape(-1, 1)).reshape(-1))       # (a frozen slot: into the engine's own copy; its arena slot stays zero)
+                    m.set_rows(self._bias_value(i, j).view(-1, 1), v.reshape(-1, 1))                 # (a frozen slot: into the engine's own copy; its arena slot stays zero)
         self.repack()
 
     def train(self, mode=True):
@@ -1402,8 +1518,9 @@ class ViTLoRAEngine(ViTEngine):
             N.check(self.lib.ucod_lora_pack(N.ptr(self.lora[i]), self.r, self.scaling, N.ptr(tl[N.T_QKV_W_AUG]), N.ptr(tl[N.T_QKV_WT_AUG]), self.D, zero_a, N.stream()),
                     "ucod_lora_pack")
         for i, ml in enumerate(self.mlp_layers):               # the MLP module's B columns of fc1_w_aug (its A term is always added by the LayerNorm-2 backward)
-            N.check(self.lib.ucod_lora_mlp_pack(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()),
-                    "ucod_lora_mlp_pack")
+            pack = self.lib.ucod_lora_mlp_pair_pack if self.mlp_pair else self.lib.ucod_lora_mlp_pack     # (the pair: each row's B values in its own module's columns)
+            N.check(pack(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()),
+                    "ucod_lora_mlp_pair_pack" if self.mlp_pair else "ucod_lora_mlp_pack")
         self._repack_bias()
         self._packed_zero_a = zero_a
 
@@ -1581,9 +1698,30 @@ class ViTLoRAEngine(ViTEngine):
             w0[:, :m.k_hf].copy_(w.detach())
         return w0, merged
 
-    def _merge(self, lib, w0, A, B, out):
+    def _merge(self, lib, w0, A, B, out, r=None):
         n, k = w0.shape
-        N.check(lib.ucod_lora_merge_f32(N.ptr(w0), A.data_ptr(), N.ptr(B), self.r, self.scaling, N.ptr(out), n, k, N.stream()), "ucod_lora_merge_f32")
+        N.check(lib.ucod_lora_merge_f32(N.ptr(w0), A.data_ptr(), N.ptr(B), self.r if r is None else r, self.scaling, N.ptr(out), n, k, N.stream()),
+                "ucod_lora_merge_f32")
+
+    def _engine_units(self, i, base, pref):
+        """What ``merge_into`` merges in layer ``i``, one unit per weight block of the ENGINE: (key, base weight in HF's shape, the module that describes the block,
+        A [R, k], B [n, R] in the engine's row order, R).  A targeted module is a unit of its own -- but gate_proj / up_proj of the gated MLP are ONE: the fused
+        weights_in [2 F0, D] = cat(gate, up) with the rank-2r module  A = [A_g | A_u],  B = blockdiag(B_g, B_u) spread over the interleaved rows (an untargeted
+        one of the two contributes zeros), so that the cast and the LayerNorm fold run over the engine's contiguous rows as for DINOv2's weights_in."""
+        out, fused = [], None
+        for path, m in self._targeted():
+            if m.part is None:
+                key = f"{pref}{i}.{path}.weight"
+                out.append((key, base[key], m, self.lora[i, m.a], self.lora[i, m.b], self.r))
+            elif fused is None:
+                g, up = self.modules[_MLP_IN], self.modules[_MLP_IN2]
+                keys = [f"{pref}{i}.{x.path}.weight" for x in (g, up)]
+                fused = g._replace(path="mlp.gate_proj+up_proj", n=g.nb, n_hf=2 * g.n_hf, interleaved=True, part=None)
+                r, bm = self.r, self.lora[i, g.b].view(g.nb // 8, 2, 4, self.r)
+                B = torch.zeros(g.nb // 8, 2, 4, 2 * r, dtype=torch.float32, device=self.device)
+                B[:, 0, :, :r], B[:, 1, :, r:] = bm[:, 0], bm[:, 1]
+                out.append((" + ".join(keys), torch.cat([base[k].detach() for k in keys], 0), fused, self.lora[i, g.a.start:up.a.stop], B.view(g.nb, 2 * r), 2 * r))
+        return out
 
     def merged_state_dict(self, base_state_dict=None):
         """peft's ``merge_and_unload()`` as a state dict: a copy of the HF-named base state dict (default: the one this engine was built from) in which ``weight``
@@ -1599,12 +1737,12 @@ class ViTLoRAEngine(ViTEngine):
                 key = f"{pref}{i}.{path}.weight"
                 w = base[key]
                 w0, merged = self._stage_weight(key, w, m, engine_rows=False)
-                self._merge(self.lib, w0, self.lora[i, m.a], m.rows_to_hf(self.lora[i, m.b].reshape(m.n, self.r)), merged)
+                self._merge(self.lib, w0, self.lora[i, m.a], m.get_rows(self.lora[i, m.b].reshape(m.nb, self.r)).contiguous(), merged)
                 out[key] = merged[:, :m.k_hf].contiguous().to(w.device, copy=True)
             for j, m in enumerate(self.modules):
                 if m.bias_off is not None:
                     key = f"{pref}{i}.{m.path}.bias"
-                    out[key] = m.rows_to_hf(self._bias_value(i, j).reshape(-1, 1)).reshape(-1).to(base[key].device, base[key].dtype, copy=True)
+                    out[key] = m.get_rows(self._bias_value(i, j).reshape(-1, 1)).reshape(-1).to(base[key].device, base[key].dtype, copy=True)
         return out
 
     def _engine_row_source(self):
@@ -1652,11 +1790,10 @@ class ViTLoRAEngine(ViTEngine):
                         if fl is not None and fl[slot] is row[slot]:
                             fl[slot] = own
                         row[slot] = own
-                    row[slot][m.row0:m.row0 + m.n].copy_(self._bias_value(i, j))
-            for path, m in self._targeted():
-                key = f"{pref}{i}.{path}.weight"
-                w0, merged = self._stage_weight(key, base[key], m, engine_rows=True)
-                self._merge(lib, w0, self.lora[i, m.a], self.lora[i, m.b], merged)
+                    row[slot][m.row0:m.row0 + m.nb].copy_(self._bias_value(i, j))
+            for key, w, m, A, B, rank in self._engine_units(i, base, pref):
+                w0, merged = self._stage_weight(key, w, m, engine_rows=True)
+                self._merge(lib, w0, A, B, merged, rank)
                 n, k, r0, plain = m.n, m.k, m.row0, row[m.w_slot]
                 N.check(lib.ucod_cast_f32_bf16(N.ptr(merged), plain.data_ptr() + r0 * k * plain.element_size(), n * k, st()), "ucod_cast_f32_bf16")
                 if m.w_slot == N.FC2_W:
