@@ -67,6 +67,8 @@ extern "C" {
  * and bit for bit what they were. */
 /* (still 5) LoRA bias="lora_only": ucod_colsum_det (+ its size helper), ucod_vit_train_workspace_bytes_lora_bias and ucod_vit_backward_lora_bias (the _lora_out_ex
  * forms plus a bias table) were added; additions only: every older backward / size entry point delegates with a NULL table and is launch for launch what it was. */
+/* (still 5) LoRA bias="all": ucod_colsum_det_lora, ucod_colsum_det_tok (+ their size helpers), ucod_vit_train_workspace_bytes_lora_bias_ex and
+ * ucod_vit_backward_lora_bias_ex (the _lora_bias forms plus a norm table) were added; additions only: the _lora_bias forms delegate with a NULL table. */
 #define UCOD_ABI_VERSION 5
 int ucod_abi_version(void);
 /* 1 when a gfx950 device is visible to this process (hipGetDeviceProperties().gcnArchName) */
@@ -847,6 +849,49 @@ size_t ucod_vit_train_workspace_bytes_lora_bias(const ucod_vit_train_desc* t, in
 int ucod_vit_backward_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
                                 const void* const* mlp_table_host, const void* const* out_table_host, const void* const* bias_table_host, const float* dkey,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* LoRA bias="all" (models/modules/full_model.py:53,66: peft sets requires_grad on every parameter with "bias" in its name -- the LayerNorm betas, the patch
+ * embedding's bias and the bias of every Linear, targeted or not; nothing else changes).  Two more column sums and a further tier of the backward.
+ *
+ * ucod_colsum_det_lora (full_model.py:53,66; csrc/vit_train.hip, beside ln_bwd_kernel, on its Drop / drop_scale): the gradient of a LayerNorm's beta, where the
+ * LayerNorm backward adds the masked LoRA branch to dy in registers and the complete cotangent never reaches memory:
+ *   out[n] = sum_{m < M} ( dy[m][n] + sum_{p < np} drop_scale_p(m D + n) * sum_{j < r} t_p[m][j] * A_p[j][n] ),  n < D
+ * with the operands of ucod_layernorm_bwd_lora_ex / _lora_mlp / _lora_mlp_pair: dy [M, D] bf16 (flags & UCOD_LNB_DY_BF16) or f32 (UCOD_LNB_X_F16 is accepted and
+ * means nothing here), 16-byte aligned; t bf16 at t_bf16[m * ldt + p * r + j] (for q / k / v the caller passes dqkv_aug + 3 D with ldt = 3 D + 64); A_p at
+ * lora + p * astride, astride = 2 r D for np = 3 (one layer's [A_q | B_q | A_k | ...]) and r D for np = 1 / 2 (A_m; [A_g | A_u]), 8-byte aligned; mask p of the
+ * dropout descriptor (NULL or p = 0: scale 1).  np in {1, 2, 3}; np * r <= 64 for np = 3, r <= UCOD_LORA_MLP_MAX_R otherwise.  t_bf16 NULL: no branch (lora, np, r,
+ * ldt and dropout are not looked at) and the result is ucod_colsum_det's on the same dy, bit for bit.
+ * Deterministic by ucod_colsum_det's rule: slabs = min(128, ceil(M / 64)), a thread adds its rows in ascending order, the sixteen row threads in ascending order, a
+ * second launch the slabs in ascending order; no floating-point atomics; two runs are bit-identical.  r = 2 and r = 4 (and r = 8 with one or two modules) keep the thread's A vectors
+ * in registers across its rows and read t two values per load (t 4-byte aligned, ldt even); other ranks take a generic loop.  workspace: ucod_colsum_det_lora_workspace_bytes (full_model.py:53,66) = slabs * D * 4, or 0 for M < 1 or
+ * D % 128 != 0.  UCOD_EINVAL before any launch, nothing written: a null dy / out / workspace, unknown flag bits, M < 1, D % 128 != 0, a misaligned pointer, a
+ * workspace that is too small and, with t_bf16 set, a null lora, np or r out of range, ldt < np * r, p outside [0, 1).  bf16 library only.
+ *
+ * ucod_colsum_det_tok (full_model.py:53,66; csrc/colsum.hip): the patch embedding's bias gradient -- the column sums over the patch rows only (CLS and register
+ * rows are no conv outputs):  out[n] = col_scale[n] * sum_{b < B} sum_{first <= i < tok} x[b * tok + i][n].  Element types, pitch, alignment and refusals of
+ * ucod_colsum_det; additionally refuses first < 0 or first >= tok.  slabs = min(128, ceil(B (tok - first) / 64)) over the selected rows in ascending order; with
+ * first = 0 the bits of ucod_colsum_det at M = B tok.  ucod_colsum_det_tok_workspace_bytes (full_model.py:53,66): slabs * N * 4, or 0.  Both builds. */
+size_t ucod_colsum_det_lora_workspace_bytes(int M, int D);
+int ucod_colsum_det_lora(const void* dy, int flags, int M, int D, const void* t_bf16, int ldt, const float* lora, int np, int r, const ucod_lora_dropout* dropout,
+                         float* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t ucod_colsum_det_tok_workspace_bytes(int B, int tok, int first, int N);
+int ucod_colsum_det_tok(const void* x, int elem, int B, int tok, int first, int N, int ld, const float* col_scale, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* The backward with trained LayerNorm and patch-embedding biases (full_model.py:53,66): ucod_vit_backward_lora_bias plus TN = norm_table_host, HOST array of
+ * 1 + 2 L DEVICE pointers:  [0] gb_patch f32 [D]   [1 + 2 l] g_beta1 of layer l [D]   [2 + 2 l] g_beta2 of layer l [D];  NULL = not trained.
+ *   g_beta1[l]  every layer, behind the QKV dgrad that leaves dh: ucod_colsum_det of dh with dropout off (the branch rode on the GEMM), ucod_colsum_det_lora with
+ *               np = 3 over dh, the aug columns of dqkv_aug and the layer's arena row with dropout on -- the operands of the LayerNorm-1 backward
+ *   g_beta2[l]  l < L - 1, behind the fc1 dgrad: ucod_colsum_det_lora with np = 1 (2 with UCOD_LORA_MLP_PAIR) over dh, the t scratch and the module's A when the
+ *               pass has an MLP table, ucod_colsum_det otherwise; the last layer's is written as zeros (its MLP never runs)
+ *   gb_patch    with this slot set the LayerNorm-1 backward also runs at layer 0 (dres = dx, or NULL for L = 1; no column scale, no 16-bit copy), and
+ *               ucod_colsum_det_tok sums the first residual state's cotangent dx over the patch rows (first = 1 + n_reg)
+ * The six Linear slots of TB are filled as before.  The partials share TB's entry of the workspace, which is sized for the widest call of either table and counted
+ * only with a non-NULL table.  A NULL TN is ucod_vit_backward_lora_bias launch for launch and byte for byte; every older entry point delegates with NULL. */
+size_t ucod_vit_train_workspace_bytes_lora_bias_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,
+                                                   const void* const* out_table_host, const void* const* bias_table_host, const void* const* norm_table_host);
+int ucod_vit_backward_lora_bias_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* table_host, const void* const* train_table_host,
+                                   const void* const* mlp_table_host, const void* const* out_table_host, const void* const* bias_table_host,
+                                   const void* const* norm_table_host, const float* dkey, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The way out of LoRA mode: merging the trained matrices into ordinary weights (csrc/lora_merge.hip), so that every frozen-backbone engine runs the adapted model.
  * peft's merge of a LoRA module (what merge_and_unload() does to each module models/modules/full_model.py:47-72 wraps):  W <- W + (lora_alpha / r) B A.

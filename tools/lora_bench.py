@@ -4,8 +4,8 @@ SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both pas
     lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side] [bias]]]]]]]]
 ``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
 on ViT-g, or q_proj,k_proj,v_proj,gate_proj,up_proj on dinov3_vits16plus (a DINOv3 MLP input module switches ``allow_mlp_in`` on); naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
-``bias``: a trailing none / lora_only (peft's LoraConfig.bias; with or without ``side`` in front of it): lora_only also trains the targeted modules' biases -- one
-deterministic column sum per bias and layer in the backward (tools/lora_bias_bench.py times the two modes against each other in one process)."""
+``bias``: a trailing none / lora_only / all (peft's LoraConfig.bias; with or without ``side`` in front of it): lora_only also trains the targeted modules' biases -- one
+deterministic column sum per bias and layer in the backward (tools/lora_bias_bench.py times the three modes against each other in one process)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,7 +32,7 @@ if side % patch:
     sys.exit(f"the image side must be a multiple of the patch size {patch}, got {side}")
 grid, n_lead = side // patch, 1 + (DINOV3_ARCHS[arch] if v3 else 4 if arch.endswith("_reg") else 0)
 kw = {} if targets is None else dict(target_modules=targets)
-kw.update(bias=bias)
+kw.update(bias=bias, allow_bias_all=bias == "all")    # (a trailing all: every bias of the backbone -- sets the opt-in)
 if v3:
     kw.update(allow_rope=True, eps=1e-5)
 leaves = [t.rsplit(".", 1)[-1] for t in targets or ()]

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""What LoRA bias="lora_only" costs: (1) forward_train + backward of the LoRA engine with bias "none" and "lora_only", two engines in one process, timed in alternating
+"""What LoRA bias="lora_only" costs: (1) forward_train + backward of the LoRA engine with bias "none", "lora_only" and "all", three engines in one process, timed in alternating
 rounds with device events; (2) ucod_colsum_det alone at the buffer shapes of that backward, as bytes read over time against the HBM rate.
     lora_bias_bench.py [B [rounds [streams [dropout [arch [targets]]]]]]
-The two engines share their side streams (see below: a second pair of streams would not get hardware queues of its own).
+The engines share their side streams (see below: a second pair of streams would not get hardware queues of its own).
 Defaults: 32 images, 7 rounds of 3 steps, 2 streams, dropout 0.05, dinov2_vitb14 @518, query,key,value,fc1,dense,fc2."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,8 +23,9 @@ side = 518
 grid = side // patch
 sd = random_state_dict(arch, seed=0)
 engines = {}
-for bias in ("none", "lora_only"):
-    e = ViTLoRAEngine(sd, heads=heads, device="cuda", lora_dropout=drop, target_modules=targets, allow_out=True, allow_swiglu=arch.startswith("dinov2_vitg14"), bias=bias)
+for bias in ("none", "lora_only", "all"):
+    e = ViTLoRAEngine(sd, heads=heads, device="cuda", lora_dropout=drop, target_modules=targets, allow_out=True, allow_swiglu=arch.startswith("dinov2_vitg14"), bias=bias,
+                      allow_bias_all=True)
     e.train_streams = streams
     engines[bias] = e
 x = torch.randn(B, 3, side, side, device="cuda")
@@ -36,10 +37,10 @@ torch.cuda.synchronize()
 # Both engines on the SAME side streams.  HIP gives a process a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default): with two side streams per engine the engine
 # built second shares queues with the first one's, its two image-parallel chunks run one after the other, and it measures 5 ms per step slower whichever mode it
 # is -- the first form of this tool reported +6.6 ms for lora_only that way (profiles/lora_bias_bench.txt).  The rounds below are serial, so sharing is safe.
-engines["lora_only"]._tside = engines["none"]._tside
+engines["lora_only"]._tside = engines["all"]._tside = engines["none"]._tside
 times = {k: [] for k in engines}
 for r in range(rounds):
-    for k in (("none", "lora_only") if r % 2 == 0 else ("lora_only", "none")):      # alternate the order as well
+    for k in (("none", "lora_only", "all") if r % 2 == 0 else ("all", "lora_only", "none")):      # alternate the order as well
         e = engines[k]
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -53,6 +54,8 @@ print(f"{arch} B={B} streams={streams} dropout={drop} targets={targets}: arena r
 for k, v in times.items():
     print(f"  bias={k:9s} forward_train + backward, ms per step over {rounds} rounds of {STEPS}: median {med[k]:.2f}, min {min(v):.2f}, max {max(v):.2f}")
 print(f"  lora_only - none = {med['lora_only'] - med['none']:+.3f} ms ({(med['lora_only'] / med['none'] - 1) * 100:+.2f} %); spread of one mode {max(times['none']) - min(times['none']):.3f} ms")
+d_lo, d_all = med["lora_only"] - med["none"], med["all"] - med["none"]
+print(f"  all - none = {d_all:+.3f} ms ({(med['all'] / med['none'] - 1) * 100:+.2f} %) = {d_all / max(d_lo, 1e-9):.2f} x what lora_only adds; arena row of all {engines['all'].lora.shape[1]}")
 # the kernel alone at the backward's buffer shapes (one chunk of `streams`): a third of dqkv [M, 3D+64], dpre [M, N1], s [M, D], and all of dqkv in one call
 lib, D, N1 = N.load(), eng.D, eng.N1
 M = (B // streams) * (1 + grid * grid)

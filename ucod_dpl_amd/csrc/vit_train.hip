@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "common.h"
 #include "../../include/ucod_dpl.h"
+#include "colsum.h"               // the workgroup shape, slab rule and second launch of the deterministic column sums (ucod_colsum_det_lora)
 #include "gemm_bf16_epilogue.h"   // gelu_erf2 / gelu_grad2: the fc1 drains' fit, which ucod_lora_out_grad_x recomputes the hidden with
 
 namespace ucod {
@@ -1431,6 +1432,176 @@ extern "C" int ucod_layernorm_bwd_lora_mlp_pair(const void* dy, const void* x, i
   UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
   return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
                        (const bf16_raw*)t_bf16, ldt, a_pair, r, make_drop(dropout), (hipStream_t)stream, 2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LoRA bias="all" (full_model.py:53,66): the gradient of a LayerNorm's beta is the column sum of the COMPLETE cotangent of its output.  Where ln_bwd_kernel<.., LORA>
+// adds the masked branch sum_p mask_p/(1-p) (t_p A_p) to dy in registers (LayerNorm 1 with dropout on, LayerNorm 2 whenever the MLP input carries an adapter), that
+// cotangent never reaches memory, so the sum is taken here from the same operands and through the same Drop / drop_scale:
+//   out[n] = sum_m ( dy[m][n] + sum_p drop_scale_p(m D + n) * sum_j t_p[m][j] A_p[j][n] )
+// The structure and the order of every addition are those of colsum_partial_kernel / colsum_finish_kernel (csrc/colsum.hip): grid (column groups, slabs), 16 row
+// threads x 16 column vectors of 16 bytes, a thread adds rows rt, rt + 16, ... of its slab in ascending order, the row threads are added through LDS in ascending
+// rt, a second launch adds the slabs in ascending order (csrc/colsum.h: the constants, colsum_slabs and colsum_finish_kernel are that file's).  No float atomics;
+// without a branch the entry point calls ucod_colsum_det itself.
+// R > 0 (r = 2, 4; r = 8 with one or two modules): the rank is known at compile time, the NP * R vectors of A for the thread's columns stay in registers across its rows, and a module's R values
+// of t are read as R / 2 four-byte loads (the host sends a t that is not 4-byte aligned to the generic loop).  R = 0: the generic rank loop, A from L1 / L2 in
+// every row -- r = 8 with THREE modules would be 192 registers of A beside the row's own, so it stays here, with every other rank.  The 16 column threads of a row thread read the same
+// t addresses: broadcast loads.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace ucod {
+
+template <bool F32, int NP, int R>
+__global__ __launch_bounds__(CS_THREADS) void colsum_lora_partial_kernel(const void* __restrict__ dy, float* __restrict__ part, int M, int D, int rows_per_slab,
+                                                                          const bf16_raw* __restrict__ tq, int ldt, const float* __restrict__ lora, int r, int astride,
+                                                                          Drop drop) {
+  constexpr int VW = F32 ? 4 : 8;                                // columns per 16-byte vector of dy
+  constexpr int NA = (NP > 0 && R > 0) ? NP * R : 1;
+  __shared__ float sm[CS_RT][CS_CV * VW];
+  const int cv = threadIdx.x % CS_CV, rt = threadIdx.x / CS_CV;
+  const int col0 = (blockIdx.x * CS_CV + cv) * VW;
+  const long r0 = (long)blockIdx.y * rows_per_slab;
+  const long r1 = r0 + rows_per_slab < (long)M ? r0 + rows_per_slab : (long)M;
+  float acc[VW];
+#pragma unroll
+  for (int e = 0; e < VW; ++e) acc[e] = 0.f;
+  if (col0 < D) {                                                // (D % 128 == 0: a vector that starts below D ends below it)
+    auto a_row = [&](int p, int j, float* a) {                   // A_p[j][col0 .. col0 + VW): 8-byte loads (the arena's alignment, as ln_bwd_kernel with VW = 2)
+      const float2* src = reinterpret_cast<const float2*>(lora + (size_t)p * astride + (size_t)j * D + col0);
+#pragma unroll
+      for (int e = 0; e < VW / 2; ++e) {
+        const float2 v = src[e];
+        a[2 * e] = v.x;
+        a[2 * e + 1] = v.y;
+      }
+    };
+    float av[NA][VW];
+    if constexpr (NP > 0 && R > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < R; ++j) a_row(p, j, av[p * R + j]);
+    }
+#pragma unroll 4
+    for (long m = r0 + rt; m < r1; m += CS_RT) {
+      float d[VW];
+      if constexpr (F32) {
+        const f32x4 v = *(const f32x4*)((const float*)dy + (size_t)m * D + col0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = v[e];
+      } else {
+        const u32x4 v = *(const u32x4*)((const bf16_raw*)dy + (size_t)m * D + col0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) unpack_h2(v[e], d[2 * e], d[2 * e + 1]);
+      }
+      if constexpr (NP > 0) {
+        const unsigned idx = (unsigned)m * (unsigned)D + (unsigned)col0;   // the element index of ln_lora / ln_bwd: the forward's mask, element for element
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          float b[VW];
+#pragma unroll
+          for (int e = 0; e < VW; ++e) b[e] = 0.f;
+          if constexpr (R > 0) {
+            float t[R];
+            const unsigned* t2 = reinterpret_cast<const unsigned*>(tq + (size_t)m * ldt + p * R);      // (R even, tq 4-byte aligned, ldt even: the host's rule)
+#pragma unroll
+            for (int j = 0; j < R / 2; ++j) unpack_h2(t2[j], t[2 * j], t[2 * j + 1]);
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+#pragma unroll
+              for (int e = 0; e < VW; ++e) b[e] += t[j] * av[p * R + j][e];
+          } else {
+            for (int j = 0; j < r; ++j) {
+              const float t = bf16_to_f32(tq[(size_t)m * ldt + p * r + j]);
+              float a[VW];
+              a_row(p, j, a);
+#pragma unroll
+              for (int e = 0; e < VW; ++e) b[e] += t * a[e];
+            }
+          }
+          if (drop.thresh) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) d[e] += b[e] * drop_scale(drop, p, idx + (unsigned)e);
+          } else {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) d[e] += b[e];
+          }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < VW; ++e) acc[e] += d[e];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < VW; ++e) sm[rt][cv * VW + e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < CS_CV * VW) {
+    const int n = blockIdx.x * CS_CV * VW + threadIdx.x;
+    float s = sm[0][threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < CS_RT; ++q) s += sm[q][threadIdx.x];
+    if (n < D) part[(size_t)blockIdx.y * D + n] = s;
+  }
+}
+
+}  // namespace ucod
+
+extern "C" size_t ucod_colsum_det_lora_workspace_bytes(int M, int D) {
+  if (M < 1 || D < 128 || D % 128 != 0) return 0;
+  return (size_t)colsum_slabs(M) * (size_t)D * sizeof(float);
+}
+
+extern "C" int ucod_colsum_det_lora(const void* dy, int flags, int M, int D, const void* t_bf16, int ldt, const float* lora, int np, int r,
+                                    const ucod_lora_dropout* dropout, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  UCOD_BF16_ONLY();
+  if (!dy || !out || !workspace || (flags & ~3)) return UCOD_EINVAL;
+  const size_t need = ucod_colsum_det_lora_workspace_bytes(M, D);
+  if (need == 0 || workspace_bytes < need) return UCOD_EINVAL;
+  if ((((uintptr_t)dy) & 15) || ((((uintptr_t)out) | ((uintptr_t)workspace)) & 3)) return UCOD_EINVAL;
+  if (t_bf16) {
+    if (!lora || (np != 1 && np != 2 && np != 3) || r < 1 || np * r > AUG || (np != 3 && r > UCOD_LORA_MLP_MAX_R) || ldt < np * r) return UCOD_EINVAL;
+    if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
+    if ((((uintptr_t)lora) & 7) || (((uintptr_t)t_bf16) & 1)) return UCOD_EINVAL;
+  }
+  const bool f32 = !(flags & UCOD_LNB_DY_BF16);
+  // without a branch: ucod_colsum_det itself (D % 128 == 0 and the alignment checked above are within its rules)
+  if (!t_bf16) return ucod_colsum_det(dy, f32 ? UCOD_ROPE_ELEM_F32 : UCOD_ROPE_ELEM_HALF, M, D, D, nullptr, out, workspace, workspace_bytes, stream);
+  UCOD_PROF(PROF_COLSUM, stream);
+  const int slabs = colsum_slabs(M), rows_per_slab = (int)(((long)M + slabs - 1) / slabs);
+  const int astride = (np == 3 ? 2 : 1) * r * D;             // from A_p to A_{p+1} (launch_ln_bwd)
+  const Drop drop = make_drop(dropout);
+  const bool t4 = !(((uintptr_t)t_bf16) & 3) && !(ldt & 1);   // a module's t values can be read two at a time
+  const bf16_raw* tq = (const bf16_raw*)t_bf16;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  const dim3 grid(cdiv(D, CS_CV * (f32 ? 4 : 8)), slabs), block(CS_THREADS);
+#define L(f, np_, r_) hipLaunchKernelGGL((colsum_lora_partial_kernel<f, np_, r_>), grid, block, 0, s, dy, part, M, D, rows_per_slab, tq, ldt, lora, r, astride, drop)
+#define P(f, np_)                                 \
+  do {                                            \
+    if (r == 2 && t4) L(f, np_, 2);               \
+    else if (r == 4 && t4) L(f, np_, 4);          \
+    else L(f, np_, 0);                            \
+  } while (0)
+#define P8(f, np_)                                \
+  do {                                            \
+    if (r == 8 && t4) L(f, np_, 8);               \
+    else P(f, np_);                               \
+  } while (0)
+#define F(f)                                      \
+  do {                                            \
+    if (np == 1) P8(f, 1);                        \
+    else if (np == 2) P8(f, 2);                   \
+    else P(f, 3);                                 \
+  } while (0)
+  if (f32) F(true);
+  else F(false);
+#undef F
+#undef P8
+#undef P
+#undef L
+  UCOD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv(D, CS_THREADS)), dim3(CS_THREADS), 0, s, part, (const float*)nullptr, out, D, slabs);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

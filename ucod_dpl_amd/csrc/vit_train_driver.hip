@@ -22,10 +22,14 @@
 //           gb_o, gb_2 [D]; NULL = not trained).  For y = x W^T + b the gradient is the column sum over token rows of y's cotangent, and every such cotangent is a
 //           live buffer here: the thirds of dqkv (behind the DINOv3 un-rotation), the completed dpre, and s = bf16(lambda * dx) of the two residual dgrads (the
 //           residual GEMMs compute x += lambda * (acc + b), so db = lambda * sum dx).  One ucod_colsum_det each; the forwards read biases from the plain rows.
+// and a sixth, behind it --
+//   TN      bias="all" (full_model.py:53,66), behind TB: gradient destinations of the patch embedding's bias and of the two LayerNorm betas of every layer
+//           ([0] gb_patch, [1 + 2 l] g_beta1, [2 + 2 l] g_beta2; NULL = not trained): column sums of dh (ucod_colsum_det, or ucod_colsum_det_lora where the LayerNorm
+//           backward adds the masked LoRA branch in registers) and of the first residual state's cotangent over the patch rows (ucod_colsum_det_tok)
 // The last layer runs LayerNorm 1 and the key projection only: the gradients of its MLP and output modules are written as zeros.
 // Dropout: every module has its own mask, keyed kind * L + l (`dropout_of`: q / k / v, the MLP input, dense, fc2 = kinds 0 .. 3).
-// Every exported symbol -- five functions in five suffix tiers, the older tiers being the _lora_out_ex forms with NULL tables / flags 0, and the _lora_bias tier of
-// the backward and its size function -- fills in a Pass and calls one of the five functions below.  No allocation, no sync.
+// Every exported symbol -- five functions in five suffix tiers, the older tiers being the _lora_out_ex forms with NULL tables / flags 0, and the _lora_bias and
+// _lora_bias_ex tiers of the backward and its size function -- fills in a Pass and calls one of the five functions below.  No allocation, no sync.
 #include "common.h"
 #include "../../include/ucod_dpl.h"
 
@@ -40,6 +44,7 @@ struct Pass {
   const void* const* TM;
   const void* const* TO;
   const void* const* TB;                                   // backward only (every other pass leaves it NULL)
+  const void* const* TN;                                   // backward only: bias="all", behind TB
 };
 
 struct Plan {
@@ -51,7 +56,7 @@ struct Plan {
   size_t dx, dh, s, da, dqkv, delta, lgw;                  // backward scratch (dpre aliases g, s aliases h2)
   size_t tm, mgw, mgw_bytes;                               // MLP LoRA module: t scratch [M, 64], partials of ucod_lora_mlp_grad
   size_t u_o, u_2, s_u, t_out, ogw, ogw_bytes;             // output modules: saved u [M, 8] per layer (dense, fc2), t scratch [M, 8], partials of ucod_lora_out_grad_*
-  size_t bgw, bgw_bytes;                                   // bias gradients (TB): partials of ucod_colsum_det
+  size_t bgw, bgw_bytes;                                   // bias gradients (TB, TN): partials of ucod_colsum_det and its _lora / _tok forms
   size_t total;
 };
 
@@ -152,9 +157,16 @@ Plan train_plan(const Pass& c) {
     p.ogw = take(p.ogw_bytes);
   }
   p.bgw = p.bgw_bytes = 0;
-  if (c.TB) {                                                   // (behind everything else, like TO: without a table no offset and no byte differs)
-    const size_t a = ucod_colsum_det_workspace_bytes(p.M, 3 * d->D), b = ucod_colsum_det_workspace_bytes(p.M, (int)FP);   // (the widest calls: q | k | v at once, dpre)
-    p.bgw_bytes = a > b ? a : b;
+  if (c.TB || c.TN) {                                           // (behind everything else, like TO: without a table no offset and no byte differs)
+    if (c.TB) {
+      const size_t a = ucod_colsum_det_workspace_bytes(p.M, 3 * d->D), b = ucod_colsum_det_workspace_bytes(p.M, (int)FP);   // (the widest calls: q | k | v at once, dpre)
+      p.bgw_bytes = a > b ? a : b;
+    }
+    if (c.TN) {   // (TN's calls are all M or fewer rows by D columns: with TB they fit what it counted, and no byte is added)
+      const size_t a = ucod_colsum_det_lora_workspace_bytes(p.M, d->D), b = ucod_colsum_det_tok_workspace_bytes(d->B, p.tok, 1 + d->n_reg, d->D);
+      if (a > p.bgw_bytes) p.bgw_bytes = a;
+      if (b > p.bgw_bytes) p.bgw_bytes = b;
+    }
     p.bgw = take(p.bgw_bytes);
   }
   p.total = o;
@@ -343,8 +355,9 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   const bool dgrad16 = dgrad16_env || r16;
   const int epi_dh = dgrad16 ? UCOD_EPI_BIAS_BF16 : UCOD_EPI_BIAS_F32;
   const int lnb_flags = (dgrad16 ? UCOD_LNB_DY_BF16 : 0) | (r16 ? UCOD_LNB_X_F16 : 0);
-  auto ln_bwd_plain = [&](const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale) -> int {
-    return ucod_layernorm_bwd_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s, M, D, d->eps, stream);
+  // (s_out: the 16-bit operand of the next dgrad GEMM -- `s`, or NULL where nothing follows: layer 0 under bias="all")
+  auto ln_bwd_plain = [&](const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale, void* s_out) -> int {
+    return ucod_layernorm_bwd_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s_out, M, D, d->eps, stream);
   };
   // a bias gradient: the column sums of a 16-bit cotangent buffer (TB; `dst` NULL = that bias is not trained)
   const void* const* TB = c.TB;
@@ -379,13 +392,38 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   };
 
   // LayerNorm-1 backward of layer l: with dropout on, the masked LoRA branch t A is added here (it cannot ride on the dgrad GEMM)
-  auto ln1_bwd = [&](int l, const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale) -> int {
+  auto ln1_bwd = [&](int l, const void* dy, const void* x, const float* gam, const float* dres, const float* next_scale, void* s_out) -> int {
     const Dropout drop = dropout_of(t, MOD_QKV, l);
     if (drop.on) {
       const float* lora_l = (const float*)(TT + UCOD_VIT_TRAIN_STRIDE * l)[5];
-      return ucod_layernorm_bwd_lora_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s, M, D, d->eps, dqkv, lora_l, r, drop.ptr(), stream);
+      return ucod_layernorm_bwd_lora_ex(dy, x, lnb_flags, gam, dres, next_scale, dx, s_out, M, D, d->eps, dqkv, lora_l, r, drop.ptr(), stream);
     }
-    return ln_bwd_plain(dy, x, gam, dres, next_scale);
+    return ln_bwd_plain(dy, x, gam, dres, next_scale, s_out);
+  };
+
+  // bias="all" (TN): the LayerNorm betas and the patch embedding's bias.  d beta = the column sums of the LayerNorm output's COMPLETE cotangent: dh, plus the masked
+  // LoRA branch wherever the LayerNorm backward adds it in registers -- then from that kernel's own operands (ucod_colsum_det_lora)
+  const void* const* TN = c.TN;
+  const int dh_elem = dgrad16 ? UCOD_ROPE_ELEM_HALF : UCOD_ROPE_ELEM_F32;
+  auto beta1_grad = [&](int l) -> int {   // behind qkv_side(l), which leaves dh; in front of whatever next overwrites dh
+    float* dst = TN ? (float*)const_cast<void*>(TN[1 + 2 * l]) : nullptr;
+    if (!dst) return UCOD_OK;
+    const Dropout drop = dropout_of(t, MOD_QKV, l);
+    if (!drop.on) return ucod_colsum_det(dh, dh_elem, M, D, D, nullptr, dst, ws + p.bgw, p.bgw_bytes, stream);   // (the branch rode on the dgrad GEMM)
+    return ucod_colsum_det_lora(dh, lnb_flags, M, D, (const char*)dqkv + (size_t)3 * D * 2, KQ, (const float*)(TT + UCOD_VIT_TRAIN_STRIDE * l)[5], 3, r, drop.ptr(), dst,
+                                ws + p.bgw, p.bgw_bytes, stream);
+  };
+  auto beta2_grad = [&](int l, const void* const* Y, const Dropout& drop_m) -> int {   // behind the fc1 dgrad; dpre has no aug columns, so the branch is always added
+    float* dst = TN ? (float*)const_cast<void*>(TN[2 + 2 * l]) : nullptr;
+    if (!dst) return UCOD_OK;
+    if (!Y) return ucod_colsum_det(dh, dh_elem, M, D, D, nullptr, dst, ws + p.bgw, p.bgw_bytes, stream);
+    return ucod_colsum_det_lora(dh, lnb_flags, M, D, ws + p.tm, UCOD_LORA_AUG, (const float*)Y[1], pair ? 2 : 1, r, drop_m.ptr(), dst, ws + p.bgw, p.bgw_bytes, stream);
+  };
+  // the patch embedding's bias: the first residual state's cotangent, which the pass otherwise never forms (layer 0's LayerNorm-1 backward), over the patch rows
+  auto patch_grad = [&](const float* dres) -> int {
+    if (!TN || !TN[0]) return UCOD_OK;
+    RUN(ln1_bwd(0, dh, at.x_in(0), (const float*)(T + 4)[0], dres, nullptr, nullptr));
+    return ucod_colsum_det_tok(dx, UCOD_ROPE_ELEM_F32, d->B, tok, 1 + d->n_reg, D, D, nullptr, (float*)const_cast<void*>(TN[0]), ws + p.bgw, p.bgw_bytes, stream);
   };
 
   // last layer: only the key projection reaches the loss (its MLP never runs: the module's gradients there are zeros, written as such)
@@ -405,13 +443,15 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
     RUN(bias_zero(G[4], D));
     RUN(bias_zero(G[5], D));
   }
+  if (TN) RUN(bias_zero(TN[2 + 2 * last], D));   // (nor does its LayerNorm 2)
   RUN(ucod_key_grad_tokens_reg(dkey, dqkv, d->B, tok, D, d->n_reg, stream));
   RUN(qkv_side(last));
-  if (last == 0) return UCOD_OK;
+  RUN(beta1_grad(last));
+  if (last == 0) return patch_grad(nullptr);
   {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * last;
     const void* const* Wp = T + 4 + UCOD_VIT_LAYER_STRIDE * (last - 1);
-    RUN(ln1_bwd(last, dh, at.x_in(last), (const float*)W[0], nullptr, (const float*)Wp[13]));
+    RUN(ln1_bwd(last, dh, at.x_in(last), (const float*)W[0], nullptr, (const float*)Wp[13], s));
   }
   for (int l = last - 1; l >= 0; --l) {
     const void* const* W = T + 4 + UCOD_VIT_LAYER_STRIDE * l;
@@ -452,9 +492,10 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
                                                                 drop_m.ptr(), stream));
     }
     RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, N1, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
+    RUN(beta2_grad(l, Y, drop_m));
     if (TM) RUN((pair ? ucod_layernorm_bwd_lora_mlp_pair : ucod_layernorm_bwd_lora_mlp)(dh, x_mid, lnb_flags, (const float*)W[7], dx, (const float*)W[6], dx, s, M, D, d->eps, ws + p.tm, UCOD_LORA_AUG,
                                             (const float*)Y[1], r, drop_m.ptr(), stream));
-    else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6]));
+    else RUN(ln_bwd_plain(dh, x_mid, (const float*)W[7], dx, (const float*)W[6], s));
     // attention branch: s = ls1 * dx  ->  out-proj dgrad  ->  attention backward  ->  LoRA grads + qkv dgrad  ->  LN1 backward
     // (dense / o_proj bias: db_o = ls1 * sum dx = the column sums of s, which stays as it is until the LayerNorm-1 backward rewrites it)
     if (G) RUN(bias_grad(G[4], s, D, D));
@@ -470,12 +511,13 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
     // d(pre) = R^T d(post) -- the same table with the sine negated, on the q | k thirds of dqkv_aug (attention_bwd.hip stores dq at 0, dk at D, dv at 2 D)
     if (d->rope) RUN(ucod_rope_qk_ld(dqkv, UCOD_ROPE_ELEM_HALF, d->rope, d->B, tok, d->n_reg, d->heads, KQ, 1, stream));
     RUN(qkv_side(l));
+    RUN(beta1_grad(l));
     if (l > 0) {
       const void* const* Wp = T + 4 + UCOD_VIT_LAYER_STRIDE * (l - 1);
-      RUN(ln1_bwd(l, dh, x_in, (const float*)W[0], dx, (const float*)Wp[13]));
+      RUN(ln1_bwd(l, dh, x_in, (const float*)W[0], dx, (const float*)Wp[13], s));
     }
   }
-  return UCOD_OK;
+  return patch_grad(dx);
 }
 
 }  // namespace
@@ -545,6 +587,17 @@ extern "C" size_t ucod_vit_train_workspace_bytes_lora_bias(const ucod_vit_train_
 extern "C" int ucod_vit_backward_lora_bias(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT, const void* const* TM,
                                            const void* const* TO, const void* const* TB, const float* dkey, void* workspace, size_t workspace_bytes, void* stream) {
   return backward(Pass{t, mlp, out_flags, T, TT, TM, TO, TB}, dkey, workspace, workspace_bytes, stream);
+}
+
+// bias="all": the same two with the norm table (NULL = the _lora_bias forms, which delegate with NULL)
+extern "C" size_t ucod_vit_train_workspace_bytes_lora_bias_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* TM, const void* const* TO,
+                                                              const void* const* TB, const void* const* TN) {
+  return train_bytes(Pass{t, mlp, out_flags, nullptr, nullptr, TM, TO, TB, TN});
+}
+extern "C" int ucod_vit_backward_lora_bias_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* T, const void* const* TT, const void* const* TM,
+                                              const void* const* TO, const void* const* TB, const void* const* TN, const float* dkey, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  return backward(Pass{t, mlp, out_flags, T, TT, TM, TO, TB, TN}, dkey, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ucod_vit_lora_infer_workspace_bytes(const ucod_vit_train_desc* t) { return infer_bytes(Pass{t, UCOD_MLP_GELU, 0, nullptr, nullptr, nullptr, nullptr}); }

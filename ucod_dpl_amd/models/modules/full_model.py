@@ -78,13 +78,19 @@ def save_lora_adapter(engine, folder):
     """Write the LoRA matrices of ``engine`` as a peft adapter folder: ``adapter_model.safetensors`` with the keys
     ``base_model.model.ViT.encoder.layer.{i}.attention.attention.query.lora_A.weight`` ... (shapes: ``lora_state_dict()``'s; B of ``weights_in`` in HF row order,
     unpadded) and ``adapter_config.json`` with r, lora_alpha, lora_dropout, bias and target_modules (models/modules/full_model.py:47-72).  ``bias`` is the
-    engine's: "none", or "lora_only" -- then the trained biases are stored beside the matrices under the module's own key, ``...query.bias`` (what peft's
+    engine's: "none", "all" (every ``...bias`` tensor of the checkpoint is stored: peft's rule ``"lora_" in k or "bias" in k``), or "lora_only" -- then the trained biases are stored beside the matrices under the module's own key, ``...query.bias`` (what peft's
     get_peft_model_state_dict derives from a ``lora_`` key: everything in front of ``lora_`` plus ``bias``).
     peft is not a dependency of this package: the layout is restated from peft's documented adapter format and has not been checked against the library -- the
     bias key in particular (recent peft versions hold the wrapped Linear as ``base_layer``, and which of the two names their loader expects is unverified)."""
     from safetensors.torch import save_file
     os.makedirs(folder, exist_ok=True)
     sd = engine.lora_state_dict(prefix=_adapter_prefix(engine))
+    if getattr(engine, "bias", "none") == "all":
+        # peft's rule for bias="all" stores every tensor with "bias" in its name: the trained value where trained (``lora_state_dict``), the checkpoint's otherwise
+        # -- what is left is the final LayerNorm's bias, which the key hook never reaches
+        for k, v in engine._base_sd.items():
+            if "bias" in k and ADAPTER_ROOT + k not in sd:
+                sd[ADAPTER_ROOT + k] = v
     save_file({k: v.detach().cpu().contiguous() for k, v in sd.items()}, os.path.join(folder, ADAPTER_WEIGHTS))
     alpha = float(engine.scaling) * int(engine.r)
     cfg = {"peft_type": "LORA", "r": int(engine.r), "lora_alpha": int(alpha) if alpha == int(alpha) else alpha,
@@ -122,7 +128,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     100, goes with it); its targets are subsets of q_proj / k_proj / v_proj -- and, with the build-only key ``allow_mlp_in`` (default False), ``up_proj`` and the
     gated MLP's ``gate_proj`` as well, so that with ``allow_out`` / ``allow_swiglu_out`` every Linear of a DINOv3 block is targetable (dinov3_vith16plus is refused
     by name: its widths are beyond the kernels').  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
-    trained too: ``ViTLoRAEngine``); "all" is refused with its reason and any other value is a ValueError, both before any device work.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
+    trained too: ``ViTLoRAEngine``); "all" -- every bias of the backbone but the final LayerNorm's, which the key hook never reaches -- is built with the
+    build-only key ``allow_bias_all`` (default False) and refused with its reason without it; any other value is a ValueError, both before any device work.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
     r = getattr(config, "r", 2)
     if r == 0:
@@ -131,7 +138,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     targets = getattr(config, "target_modules", None)                        # None: query / key / value, the reference's default
     if targets is not None and not isinstance(targets, str):
         targets = list(targets)
-    bias = check_lora_bias(getattr(config, "bias", "none"))                  # :53,66
+    allow_bias_all = bool(getattr(config, "allow_bias_all", False))
+    bias = check_lora_bias(getattr(config, "bias", "none"), allow_bias_all)  # :53,66
     drop = float(getattr(config, "lora_dropout", 0.05))                      # :50
     if eps is None:
         eps = 1e-5 if is_dinov3(state_dict) else 1e-6
@@ -139,7 +147,7 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
                                       rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False)),
                                       allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False)), bias=bias,
-                                      allow_mlp_in=bool(getattr(config, "allow_mlp_in", False))))
+                                      allow_mlp_in=bool(getattr(config, "allow_mlp_in", False)), allow_bias_all=allow_bias_all))
 
 
 class full_model(nn.Module):

@@ -233,6 +233,15 @@ SIGNATURES = {
     "ucod_colsum_det": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
     "ucod_vit_train_workspace_bytes_lora_bias": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "ucod_vit_backward_lora_bias": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),
+    # LoRA bias="all": the column sum of a LayerNorm output's complete cotangent (dy + the masked LoRA branch; flags = LNB_DY_BF16 or 0), the column sum over the
+    # patch rows of every image, and the backward / its size function with the norm table behind the bias table (NULL = the _lora_bias forms)
+    "ucod_colsum_det_lora_workspace_bytes": (sz, [ci, ci]),
+    "ucod_colsum_det_lora": (ci, [vp, ci, ci, ci, vp, ci, vp, ci, ci, C.POINTER(LoraDropout), vp, vp, sz, vp]),
+    "ucod_colsum_det_tok_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "ucod_colsum_det_tok": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, sz, vp]),
+    "ucod_vit_train_workspace_bytes_lora_bias_ex": (sz, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "ucod_vit_backward_lora_bias_ex": (ci, [C.POINTER(VitTrainDesc), ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                            vp, vp, sz, vp]),
     # merging trained LoRA matrices into ordinary weights, and the device form of the LayerNorm fold (fp16-operand build) for the merged weight
     "ucod_lora_merge_f32": (ci, [vp, vp, vp, ci, cf, vp, ci, ci, vp]),
     "ucod_fold_ln_linear": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),

@@ -911,7 +911,8 @@ def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 
     ``family`` / ``mlp``: ``lora_module_paths``; ``D``: the width; ``F`` / ``F0``: the MLP's hidden width in the engine (SwiGLU: padded) and in the checkpoint;
     ``r``: the rank; ``hit``: which of the six are targeted (``resolve_lora_targets``); ``bias``: peft's mode; ``has_bias``: which have a bias in the checkpoint.
     A layer's arena row is  [A_q | B_q | A_k | B_k | A_v | B_v]  -- always, an untargeted one's at zero --, then [A | B] of the MLP input, the attention output and
-    the MLP output where targeted, then (bias="lora_only") the biases of the targeted modules that have one, in the same order (``lora_row_numel``)."""
+    the MLP output where targeted, then (bias="lora_only") the biases of the targeted modules that have one -- (bias="all") of every module that has one, targeted
+    or not -- in the same order (``lora_row_numel``); bias="all" puts [beta1 | beta2 | b_patch] behind them (``lora_norm_offsets``)."""
     swiglu = mlp == "swiglu"
     N1, N0 = (2 if swiglu else 1) * F, (2 if swiglu else 1) * F0
     pair = len(hit) > _MLP_IN2                                   # seven answers: the gated DINOv3 MLP's gate_proj / up_proj (``lora_module_paths`` with ``pair``)
@@ -939,7 +940,7 @@ def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 
         g = mods[_MLP_IN]
         mods.append(g._replace(path=lora_module_paths(family, mlp, True)[_MLP_IN2], targeted=bool(hit[_MLP_IN2]), a=a_up, part=1))
     for j, m in enumerate(mods):
-        if bias == "lora_only" and m.targeted and has_bias[j]:
+        if ((bias == "lora_only" and m.targeted) or bias == "all") and has_bias[j]:
             if m.part == 1 and mods[_MLP_IN].bias_off is not None:
                 mods[j] = m._replace(bias_off=mods[_MLP_IN].bias_off)        # (the fused bias: one slot for both)
             else:
@@ -947,9 +948,19 @@ def lora_modules(family, mlp, D, F, F0, r, hit, bias="none", has_bias=(True,) * 
     return tuple(mods)
 
 
-def lora_row_numel(mods):
-    """Length of a layer's arena row."""
-    return max([m.b.stop for m in mods if m.b is not None] + [m.bias_off + m.nb for m in mods if m.bias_off is not None])
+def lora_row_numel(mods, bias="none"):
+    """Length of a layer's arena row (bias="all": with the three vectors of ``lora_norm_offsets`` at its end)."""
+    n = max([m.b.stop for m in mods if m.b is not None] + [m.bias_off + m.nb for m in mods if m.bias_off is not None])
+    return n + (3 * mods[_Q].k if bias == "all" else 0)
+
+
+def lora_norm_offsets(mods, bias="none"):
+    """bias="all": where a layer's arena row holds (norm1.bias, norm2.bias, the patch embedding's bias), D values each, behind the Linear biases; None otherwise.
+    The patch bias is live in row 0 only: in every other row its block holds exact zeros and is never read."""
+    if bias != "all":
+        return None
+    at, D = lora_row_numel(mods), mods[_Q].k
+    return at, at + D, at + 2 * D
 
 
 # ---- target_modules -> which of the six --------------------------------------------------------------------------------------------------------------------------
@@ -1166,6 +1177,10 @@ def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False
     hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out or mlp_in3 else None)
     if len(hit) > _MLP_IN2 and not (hit[_MLP_IN] or hit[_MLP_IN2]):         # neither of the gated pair: the table of six, as without the opt-in
         hit, names = hit[:_MLP_IN2], names._replace(paths=lora_module_paths(family))
+    if bias == "all" and family == "dinov3" and mlp == "swiglu" and len(hit) <= _MLP_IN2:
+        # (the table of six describes the gated MLP's input as ONE module ``up_proj`` with the fused bias: gate_proj.bias would have no name in the state dicts)
+        raise NotImplementedError("LoRA bias='all' on a gated DINOv3 checkpoint is built with gate_proj or up_proj targeted (allow_mlp_in=True) only: their biases "
+                                  "share the engine's one fused weights_in bias, which the module table carries as the pair's")
     if len(hit) > _MLP_IN2 and bias == "lora_only" and hit[_MLP_IN] != hit[_MLP_IN2]:
         raise NotImplementedError("LoRA bias='lora_only' with exactly one of gate_proj / up_proj targeted is not built: the two share the ONE fused bias of the "
                                   "engine's weights_in GEMM, and its gradient (the column sums of the pre-activation's cotangent) is computed over all of its 2F "
@@ -1181,15 +1196,16 @@ def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False
 LORA_BIAS_MODES = ("none", "lora_only", "all")               # peft's LoraConfig.bias (models/modules/full_model.py:53,66)
 
 
-def check_lora_bias(bias):
-    """peft's ``LoraConfig.bias`` as this package builds it: "none" and "lora_only" pass; "all" is refused with its reason; anything else is a ValueError.  Host
-    only: ``load_lora`` and ``ViTLoRAEngine`` call it before any device work."""
+def check_lora_bias(bias, allow_bias_all=False):
+    """peft's ``LoraConfig.bias`` as this package builds it: "none" and "lora_only" pass; "all" passes with the opt-in ``allow_bias_all`` and is refused with its
+    reason without it; anything else is a ValueError.  Host only: ``load_lora`` and ``ViTLoRAEngine`` call it before any device work."""
     if bias not in LORA_BIAS_MODES:
         raise ValueError(f"LoRA bias must be one of {LORA_BIAS_MODES} (peft's LoraConfig.bias), got {bias!r}")
-    if bias == "all":
+    if bias == "all" and not allow_bias_all:
         raise NotImplementedError("LoRA bias='all' is not built: it also trains the LayerNorm and patch-embedding biases, and the LayerNorm backward of the "
                                   "backbone-backward passes produces no gradient of beta (it returns the input's cotangent only); bias='lora_only' -- the biases "
-                                  "of the modules that carry an adapter -- is built")
+                                  "of the modules that carry an adapter -- is built, and so is 'all' with the opt-in allow_bias_all=True (lora_cfg.allow_bias_all), "
+                                  "which takes those gradients from column sums beside the pass (ucod_vit_backward_lora_bias_ex)")
     return bias
 
 
@@ -1244,11 +1260,19 @@ class ViTLoRAEngine(ViTEngine):
     slots of the gradient arena; ``repack`` copies the arena's biases into the engine's own bias vectors, which (with ``clone_for_ema``'s) are private copies in that
     mode.  Every last-layer bias but the key's cannot receive a gradient (only the key projection reaches the key map): its arena slot holds zeros, which the fused
     AdamW keeps at an exact zero, and the state dicts, merges and the adapter take the checkpoint's value for it (``_bias_frozen``).  ``lora_state_dict`` /
-    ``merged_state_dict`` / ``merge_into`` carry the biases as ``{layer path}{i}.{module}.bias`` in HF order.  "all" is refused (``check_lora_bias``)."""
+    ``merged_state_dict`` / ``merge_into`` carry the biases as ``{layer path}{i}.{module}.bias`` in HF order.
+
+    ``bias="all"`` (with ``allow_bias_all=True``; refused without it, ``check_lora_bias``) is peft's rule "every parameter with bias in its name": every module with
+    a bias in the checkpoint has its arena slot, targeted or not, and the row ends in [beta1 | beta2 | b_patch] (``lora_norm_offsets``: norm1.bias, norm2.bias and
+    the patch embedding's bias, the last live in row 0 only).  The backward runs ucod_vit_backward_lora_bias_ex with the norm table (``_norm_table``); the private
+    bias buffer holds the three vectors too, and the patch bias and the LayerNorm beta slots of this engine's rows view it.  The last layer's beta2 is frozen like
+    its Linear biases; the final LayerNorm's bias is not in the arena.  The state dicts carry ``{layer path}{i}.norm{1,2}.bias`` and the patch bias under its HF key;
+    ``merge_into`` also re-folds every folded QKV / fc1, targeted or not (their folded bias depends on beta).  On a gated DINOv3 checkpoint it needs gate_proj or
+    up_proj targeted (``lora_layout``)."""
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False,
-                 bias="none", allow_mlp_in=False):
+                 bias="none", allow_mlp_in=False, allow_bias_all=False):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
@@ -1257,10 +1281,11 @@ class ViTLoRAEngine(ViTEngine):
         ucod_vit_train_desc.allow_rope); a gated-MLP checkpoint (vits16plus / vith16plus) also needs ``allow_swiglu``.  Opt-in: ``lora_cfg.allow_rope``.
         ``allow_out``: let ``target_modules`` name the output projections (class docstring).  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_out``.
         ``allow_swiglu_out``: let it name the SwiGLU MLP's output projection too (with ``allow_out`` and ``allow_swiglu``; on DINOv3 also ``allow_rope``).
-        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none" or "lora_only"; ``load_lora`` passes ``lora_cfg.bias``.
+        ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none", "lora_only" or, with ``allow_bias_all``, "all"; ``load_lora`` passes ``lora_cfg.bias``.
         ``allow_mlp_in``: on a DINOv3 checkpoint, let ``target_modules`` name the MLP input modules -- ``up_proj``, and ``gate_proj`` on the gated MLP (class
-        docstring).  On a DINOv2 checkpoint it changes nothing.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_mlp_in``."""
-        check_lora_bias(bias)
+        docstring).  On a DINOv2 checkpoint it changes nothing.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_mlp_in``.
+        ``allow_bias_all``: let ``bias`` be "all" (class docstring); with "none" / "lora_only" it changes nothing.  Opt-in: ``lora_cfg.allow_bias_all``."""
+        check_lora_bias(bias, allow_bias_all)
         canon = normalize_state_dict(state_dict)
         if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
             raise ValueError("allow_swiglu_out=True needs allow_out=True and allow_swiglu=True" + (", and allow_rope=True on a DINOv3 checkpoint" if canon.get("rope") else ""))
@@ -1361,7 +1386,7 @@ class ViTLoRAEngine(ViTEngine):
         values derived from it here, once, for the passes and for callers that read them."""
         mods = self.modules = tuple(modules)
         self._layer_path, self.bias, self._bias_flat = layer_path, bias, None
-        self.numel = lora_row_numel(mods)
+        self.numel, self.norm_off = lora_row_numel(mods, bias), lora_norm_offsets(mods, bias)
         self.targets = tuple(m.targeted for m in mods[:_MLP_IN])                 # (query, key, value)
         self.mlp_pair = len(mods) > _MLP_IN2                                     # the gated DINOv3 MLP's gate_proj / up_proj: one arena block, the _pair kernels
         mlp_ins = [m for m in (mods[_MLP_IN],) + mods[_MLP_IN2:] if m.targeted]
@@ -1371,7 +1396,7 @@ class ViTLoRAEngine(ViTEngine):
         self.qkv_numel = mods[_V].b.stop
         self.out_off = [m.a.start if m.targeted else None for m in mods[_ATTN_OUT:_MLP_IN2]]
         self.bias_off = tuple(m.bias_off for m in mods[:_MLP_IN2])               # (the bias table's six slots; the pair's fused bias is the MLP input's)
-        self.bias_numel = sum(m.nb for m in mods if m.bias_off is not None and m.part != 1)
+        self.bias_numel = sum(m.nb for m in mods if m.bias_off is not None and m.part != 1) + (3 * mods[_Q].k if self.norm_off else 0)
         if self.mlp_pair and mods[_MLP_IN].bias_off != mods[_MLP_IN2].bias_off:
             raise ValueError("the fused bias of gate_proj / up_proj is trained for both or for neither (lora_layout refuses the rest)")
         self.N1, self._F0 = mods[_MLP_IN].nb, mods[_MLP_OUT].k_hf                 # rows of the MLP input weight in the engine; the checkpoint's own hidden width
@@ -1399,7 +1424,14 @@ class ViTLoRAEngine(ViTEngine):
         """This engine's bias vectors move into one private buffer ``_bias_flat`` [L, 3D + N1 + D + D] (q | k | v | m | o | 2: ``LoRAModule.bias_cols``) that the rows
         of ``self.layers`` view -- so that ``repack`` is one strided copy per module and no tensor is shared with the checkpoint or a clone."""
         slots = dict.fromkeys(m.b_slot for m in self.modules)
-        self._bias_flat = torch.stack([torch.cat([row[s] for s in slots]) for row in self.layers])
+        # (bias="all": behind them beta1 | beta2 | the patch bias -- the same patch vector in every row; row 0's is the one the passes read)
+        norm = (lambda row: [row[N.LN1_B], row[N.LN2_B], self.patch_b]) if self.norm_off else (lambda row: [])
+        self._bias_flat = torch.stack([torch.cat([row[s] for s in slots] + norm(row)) for row in self.layers])
+        if self.norm_off:
+            base = self._base_sd
+            self._patch_key = next((k for k in ("embeddings.patch_embeddings.projection.bias", "embeddings.patch_embeddings.bias") if k in base), None)
+            if self._patch_key is None:
+                raise NotImplementedError("LoRA bias='all' needs HF's names (the patch embedding's bias is carried under its HF key)")
         self._link_bias()
 
     def _link_bias(self):
@@ -1410,8 +1442,40 @@ class ViTLoRAEngine(ViTEngine):
             for s in dict.fromkeys(m.b_slot for m in self.modules):
                 cols = [m.bias_cols for m in self.modules if m.b_slot == s]
                 row[s] = f[cols[0].start:cols[-1].stop]
+            if self.norm_off:
+                c0 = self._norm_cols()
+                row[N.LN1_B], row[N.LN2_B] = f[c0:c0 + self.D], f[c0 + self.D:c0 + 2 * self.D]
             rows.append(row)
         self.layers = rows
+        if self.norm_off:
+            c0 = self._norm_cols()
+            self.patch_b = self._bias_flat[0, c0 + 2 * self.D:c0 + 3 * self.D]
+
+    def _norm_cols(self):
+        """first column of [beta1 | beta2 | b_patch] in ``_bias_flat``: behind the Linear biases"""
+        return max(m.bias_cols.stop for m in self.modules)
+
+    def _norm_live(self):
+        """bias="all": (arena columns, ``_bias_flat`` columns, the rows that are live) of beta1 (every layer: the last one's reaches the key map through the key
+        projection), beta2 (below the last layer) and the patch bias (row 0)"""
+        if not self.norm_off:
+            return []
+        D, c0 = self.D, self._norm_cols()
+        return [(slice(o, o + D), slice(c0 + k * D, c0 + (k + 1) * D), Lj) for k, (o, Lj) in enumerate(zip(self.norm_off, (self.L, self.L - 1, 1)))]
+
+    def _norm_names(self, prefix=None):
+        """[(name, row, which of the three)]: ``{layer path}{i}.norm{1,2}.bias`` of every layer and the patch bias under its HF key (in front of it whatever
+        ``prefix`` has in front of the layer path)"""
+        if not self.norm_off:
+            return []
+        prefix = self._layer_path if prefix is None else prefix
+        root = prefix[:len(prefix) - len(self._layer_path)] if prefix.endswith(self._layer_path) else ""
+        return [(root + self._patch_key, 0, 2)] + [(f"{prefix}{i}.norm{k + 1}.bias", i, k) for i in range(self.L) for k in (0, 1)]
+
+    def _norm_value(self, i, k, src=None):
+        """beta1 / beta2 of layer ``i`` or the patch bias (``k`` = 0 / 1 / 2): from the arena (``src``), or the engine's own copy for a frozen slot"""
+        o, cols, Lj = self._norm_live()[k]
+        return self._bias_flat[i, cols] if i >= Lj else (self.lora if src is None else src)[i, o]
 
     def _bias_frozen(self, i, j):
         """True for a bias slot that cannot receive a gradient: every bias of the last layer but the key's (only the key projection reaches the key map).  torch's
@@ -1420,20 +1484,21 @@ class ViTLoRAEngine(ViTEngine):
         return i == self.L - 1 and j != _K
 
     def _bias_live(self):
-        """(module, its arena columns, the layers below the frozen ones) of every trained bias"""
-        return [(m, slice(m.bias_off, m.bias_off + m.nb), self.L if j == _K else self.L - 1) for j, m in enumerate(self.modules)
-                if m.bias_off is not None and m.part != 1]                # (the pair's fused bias once, at gate_proj's entry)
+        """(its columns in ``_bias_flat``, its arena columns, the layers below the frozen ones) of every trained bias (bias="all": and of the three norm vectors)"""
+        return [(m.bias_cols, slice(m.bias_off, m.bias_off + m.nb), self.L if j == _K else self.L - 1) for j, m in enumerate(self.modules)
+                if m.bias_off is not None and m.part != 1] \
+            + [(cols, o, Lj) for o, cols, Lj in self._norm_live()]        # (the pair's fused bias once, at gate_proj's entry)
 
     def _bias_init_arena(self):
         """Trained biases start at the checkpoint's values; a slot that cannot receive a gradient (``_bias_frozen``) stays zero."""
-        for m, o, Lj in self._bias_live():
-            self.lora[:Lj, o] = self._bias_flat[:Lj, m.bias_cols]
+        for cols, o, Lj in self._bias_live():
+            self.lora[:Lj, o] = self._bias_flat[:Lj, cols]
             self.lora[Lj:, o] = 0.0
 
     def _repack_bias(self):
         """arena -> the engine's own bias vectors, one strided copy per trained module (frozen slots keep the checkpoint's value: ``_bias_frozen``)"""
-        for m, o, Lj in self._bias_live():
-            self._bias_flat[:Lj, m.bias_cols].copy_(self.lora[:Lj, o])
+        for cols, o, Lj in self._bias_live():
+            self._bias_flat[:Lj, cols].copy_(self.lora[:Lj, o])
 
     def _bias_value(self, i, j, src=None):
         """The bias of module ``j`` in layer ``i`` as the engine orders it (gate_proj / up_proj: the fused bias, ``LoRAModule.nb`` values): from the arena (``src``, default ``self.lora``), or the checkpoint's for a frozen slot."""
@@ -1449,6 +1514,17 @@ class ViTLoRAEngine(ViTEngine):
         ptrs = []
         for i in range(self.L):
             ptrs += [None if o is None else grad[i, o:].data_ptr() for o in self.bias_off]
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def _norm_table(self, grad):
+        """The norm table of the backward (include/ucod_dpl.h: ucod_vit_backward_lora_bias_ex -- [0] the patch bias, [1 + 2 l] beta1, [2 + 2 l] beta2 of layer l:
+        gradient destinations in ``grad`` [L, P]), or None unless bias="all"."""
+        if not self.norm_off:
+            return None
+        b1, b2, bp = self.norm_off
+        ptrs = [grad[0, bp:].data_ptr()]
+        for i in range(self.L):
+            ptrs += [grad[i, b1:].data_ptr(), grad[i, b2:].data_ptr()]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
     # ---- state dicts ------------------------------------------------------------------------------------------------------
@@ -1468,6 +1544,9 @@ class ViTLoRAEngine(ViTEngine):
                 if m.bias_off is not None:
                     v = torch.zeros(m.nb, device=self.device) if grads and self._bias_frozen(i, j) else self._bias_value(i, j, src)
                     out[f"{prefix}{i}.{m.path}.bias"] = m.get_rows(v.reshape(-1, 1)).reshape(-1).clone()
+        for name, i, k in self._norm_names(prefix):               # bias="all": the LayerNorm betas and the patch bias (a frozen slot: the checkpoint's value, gradient zero)
+            frozen = i >= self._norm_live()[k][2]
+            out[name] = torch.zeros(self.D, device=self.device) if grads and frozen else self._norm_value(i, k, src).clone()
         return out
 
     def load_lora_state_dict(self, sd, prefix=None):
@@ -1498,6 +1577,11 @@ class ViTLoRAEngine(ViTEngine):
                     if tuple(v.shape) != (m.n_hf,):
                         raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(m.n_hf,)}")
                     m.set_rows(self._bias_value(i, j).view(-1, 1), v.reshape(-1, 1))                 # (a frozen slot: into the engine's own copy; its arena slot stays zero)
+        for name, i, k in self._norm_names(prefix):
+            v = take(name)
+            if tuple(v.shape) != (self.D,):
+                raise ValueError(f"{name} has shape {tuple(v.shape)}, expected {(self.D,)}")
+            self._norm_value(i, k).copy_(v)
         self.repack()
 
     def train(self, mode=True):
@@ -1564,7 +1648,9 @@ class ViTLoRAEngine(ViTEngine):
 
     def _train_bytes(self, lead, tabs, i):
         """Workspace of chunk ``i``'s training pass and backward: with trained biases the _lora_bias size (the column sums' partials behind everything else)."""
-        TB = self._bias_table(self._tside_grad[i])
+        TB, TN = self._bias_table(self._tside_grad[i]), self._norm_table(self._tside_grad[i])
+        if TN is not None:
+            return self.lib.ucod_vit_train_workspace_bytes_lora_bias_ex(*lead, *tabs[2:], TB, TN)
         if TB is None:
             return self.lib.ucod_vit_train_workspace_bytes_lora_out_ex(*lead, *tabs[2:])
         return self.lib.ucod_vit_train_workspace_bytes_lora_bias(*lead, *tabs[2:], TB)
@@ -1654,7 +1740,11 @@ class ViTLoRAEngine(ViTEngine):
             t = self._train_desc(b1 - b0, H, W, self._chunk_seed[i])
             lead, tabs, keep = self._pass_args(t, gh, gw, i)
             ws = self._tside_ws[i]
-            TB = self._bias_table(self._tside_grad[i])
+            TB, TN = self._bias_table(self._tside_grad[i]), self._norm_table(self._tside_grad[i])
+            if TN is not None:                                     # bias="all": the same pass plus the sums of the LayerNorm betas and of the patch bias
+                N.check(self.lib.ucod_vit_backward_lora_bias_ex(*lead, *tabs, TB, TN, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()),
+                        "ucod_vit_backward_lora_bias_ex")
+                return
             if TB is not None:                                     # trained biases: the same pass plus one column sum per bias, written into the chunk's arena copy
                 N.check(self.lib.ucod_vit_backward_lora_bias(*lead, *tabs, TB, N.ptr(dkey[b0:b1]), N.ptr(ws), ws.numel(), N.stream()), "ucod_vit_backward_lora_bias")
                 return
@@ -1709,10 +1799,16 @@ class ViTLoRAEngine(ViTEngine):
         weights_in [2 F0, D] = cat(gate, up) with the rank-2r module  A = [A_g | A_u],  B = blockdiag(B_g, B_u) spread over the interleaved rows (an untargeted
         one of the two contributes zeros), so that the cast and the LayerNorm fold run over the engine's contiguous rows as for DINOv2's weights_in."""
         out, fused = [], None
-        for path, m in self._targeted():
+        # (bias="all": an untargeted module behind a LayerNorm is a unit too, with A = B = 0 -- its folded bias q (W beta + b) depends on the trained beta)
+        units = [(m.path, m) for m in self.modules if m.targeted or (self.norm_off and m.ln is not None)]
+        for path, m in units:
             if m.part is None:
                 key = f"{pref}{i}.{path}.weight"
-                out.append((key, base[key], m, self.lora[i, m.a], self.lora[i, m.b], self.r))
+                if m.a is None:                                    # (an untargeted MLP input: no place in the arena)
+                    A, B = (torch.zeros(self.r * x, dtype=torch.float32, device=self.device) for x in (m.k, m.nb))
+                else:
+                    A, B = self.lora[i, m.a], self.lora[i, m.b]
+                out.append((key, base[key], m, A, B, self.r))
             elif fused is None:
                 g, up = self.modules[_MLP_IN], self.modules[_MLP_IN2]
                 keys = [f"{pref}{i}.{x.path}.weight" for x in (g, up)]
@@ -1743,6 +1839,8 @@ class ViTLoRAEngine(ViTEngine):
                 if m.bias_off is not None:
                     key = f"{pref}{i}.{m.path}.bias"
                     out[key] = m.get_rows(self._bias_value(i, j).reshape(-1, 1)).reshape(-1).to(base[key].device, base[key].dtype, copy=True)
+        for name, i, k in self._norm_names(pref):                  # bias="all": the LayerNorm betas and the patch bias
+            out[name] = self._norm_value(i, k).to(base[name].device, base[name].dtype, copy=True)
         return out
 
     def _engine_row_source(self):
@@ -1780,8 +1878,19 @@ class ViTLoRAEngine(ViTEngine):
         base, lib, st = self._base_sd, engine.lib, N.stream
         pref = self._hf_prefix(base)
         base_ptrs = {v.untyped_storage().data_ptr() for v in base.values() if torch.is_tensor(v) and v.is_cuda} if self.bias_numel else ()
+        if self.norm_off:                                          # bias="all": the patch bias, and below every layer's betas, before the folds read them
+            if engine.patch_b.untyped_storage().data_ptr() in base_ptrs:
+                engine.patch_b = engine.patch_b.clone()
+            engine.patch_b.copy_(self._norm_value(0, 2))
         for i in range(self.L):
             row, fl = engine.layers[i], (engine.fold_layers[i] if engine.ln_fold else None)
+            for k, slot in enumerate((N.LN1_B, N.LN2_B) if self.norm_off else ()):
+                if row[slot].untyped_storage().data_ptr() in base_ptrs:
+                    own = row[slot].clone()
+                    if fl is not None and fl[slot] is row[slot]:
+                        fl[slot] = own
+                    row[slot] = own
+                row[slot].copy_(self._norm_value(i, k))
             for j, m in enumerate(self.modules):                   # bias="lora_only": the trained biases into the live bias vectors first, so that the LayerNorm fold
                 if m.bias_off is not None:                         # below reads them (its folded bias is b' = q (W beta + b))
                     slot = m.b_slot
