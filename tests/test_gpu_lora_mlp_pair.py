@@ -6,7 +6,9 @@ Bars are the single module's (tests/test_gpu_lora_targets.py): t 1e-2, dA and dB
 LayerNorm output 2e-2, u 1e-2; LayerNorm backward 2e-5 (dx) and 1e-2 (s).  tests/test_dinov3_lora_mlp_in_host.py shows the distances a wrong block structure
 produces to be of order 1: here a gate element multiplied by an up row of B, a shared mask or a live cross block would miss the references by as much.
 
-The gradient kernel's cases reach every instantiation of its launch function: N1 = 1024 / 3072 / 6144 / 8192 are 1, 2, 3 (in the 4 form) and 4 vectors per thread,
+The gradient kernel is one template for the pair and for the single module (ucod_lora_mlp_grad: every fc1 / up_proj adapter): its cases run for both module counts,
+the single module on the same dpre, h2 and B_m with every row its own, against the same references and bars.
+The cases reach every instantiation of its launch function: N1 = 1024 / 3072 / 6144 / 8192 are 1, 2, 3 (in the 4 form) and 4 vectors per thread,
 D = 128 / 768 / 1536 are 1, 2, 3 column pairs per thread -- every pair of the two occurs; r = 1 (half a pass live), 2 (one pass), 3 (odd tail), 8 (four passes)
 each occur with every vector count; 37 rows end inside a 4-row group, 2053 (N1 <= 4096) / 1029 rows are one group above the block-stride cap.
 """
@@ -56,68 +58,79 @@ def test_the_cases_cover_every_dispatch_case():
 
 
 @functools.lru_cache(maxsize=4)
-def operands(M, N1, D, r, p_drop, live=(True, True)):
+def operands(M, N1, D, r, p_drop, live=(True, True), modules=2):
     """bf16-rounded operands of one case and the f64 references that do not depend on the kernel's output (computed once, never modified).  ``live``: which of
-    (gate_proj, up_proj) is targeted -- the other has A = 0 and its rows of B = 0."""
+    (gate_proj, up_proj) is targeted -- the other has A = 0 and its rows of B = 0.  ``modules`` = 1: the single module on the same dpre, h and B_m -- every row is
+    module 0's, A is the pair's A_g, the flat layout [A_m | B_m]."""
     g = torch.Generator().manual_seed(M + N1 + D + r)
-    A = torch.randn(2, r, D, generator=g) / math.sqrt(D)
+    A = torch.randn(2, r, D, generator=g)[:modules] / math.sqrt(D)
     Bm = torch.randn(N1, r, generator=g) * 0.05
     dpre = torch.randn(M, N1, generator=g).bfloat16()
     h = torch.randn(M, D, generator=g).bfloat16()
-    gate = gate_rows(N1)
-    for p, on in enumerate(live):
+    gate = gate_rows(N1) if modules == 2 else torch.ones(N1, dtype=torch.bool)
+    for p, on in enumerate(live[:modules]):
         if not on:
             A[p] = 0.0
             Bm[gate if p == 0 else ~gate] = 0.0
     hd, u = [], []
-    for p in range(2):
+    for p in range(modules):
         mask = OV.lora_dropout_mask(SEED, LAYER, p, M, D, p_drop).double() if p_drop > 0 else torch.ones(M, D, dtype=torch.float64)
         hd.append((h.double() * mask).to(DEV))
         u.append((hd[p] @ A[p].double().to(DEV).t()).bfloat16())
     h_aug = torch.zeros(M, D + AUG, dtype=torch.bfloat16, device=DEV)
-    h_aug[:, :D], h_aug[:, D:D + r], h_aug[:, D + r:D + 2 * r] = h.to(DEV), u[0], u[1]
+    h_aug[:, :D], h_aug[:, D:D + modules * r] = h.to(DEV), torch.cat(u, 1)
     d64, b64, gd = dpre.double().to(DEV), Bm.double().to(DEV), gate.to(DEV)
-    t_ref = torch.cat((SCALING * d64[:, gd] @ b64[gd], SCALING * d64[:, ~gd] @ b64[~gd]), 1)           # [M, 2r]: columns p r + j
-    dB_ref = SCALING * torch.where(gd[:, None], d64.t() @ u[0].double(), d64.t() @ u[1].double())        # each row against u of its own module
+    t_ref = torch.cat([SCALING * d64[:, rows] @ b64[rows] for rows in (gd, ~gd)[:modules]], 1)          # [M, modules r]: columns p r + j
+    dB_ref = SCALING * torch.where(gd[:, None], d64.t() @ u[0].double(), d64.t() @ u[-1].double())       # each row against u of its own module
     return dict(flat=torch.cat((A.reshape(-1), Bm.reshape(-1))).to(DEV), dpre=dpre.to(DEV), h_aug=h_aug, hd=hd, t_ref=t_ref.cpu(), dB_ref=dB_ref.cpu(), gate=gate)
 
 
-def run_grad(o, M, N1, D, r, p_drop):
+def run_grad(o, M, N1, D, r, p_drop, modules=2):
     lib = N.load()
-    wsb = lib.ucod_lora_mlp_pair_grad_workspace_bytes(N1, D)
-    assert wsb == (256 if N1 > 4096 else 512) * 2 * (2 * D + N1) * 4
+    wsf, fn = (lib.ucod_lora_mlp_pair_grad_workspace_bytes, lib.ucod_lora_mlp_pair_grad) if modules == 2 else (lib.ucod_lora_mlp_grad_workspace_bytes, lib.ucod_lora_mlp_grad)
+    wsb = wsf(N1, D)
+    assert wsb == (256 if N1 > 4096 else 512) * 2 * (modules * D + N1) * 4
     ws = FlatGuarded(wsb // 4)
-    t, grad = Guarded(M, AUG, torch.bfloat16), Guarded(1, r * (2 * D + N1), torch.float32)
-    rc = lib.ucod_lora_mlp_pair_grad(N.ptr(o["dpre"]), N.ptr(o["h_aug"]), N.ptr(o["flat"]), r, SCALING, grad.ptr(), t.ptr(), ws.ptr(), wsb, M, N1, D,
-                                     drop_arg(p_drop, SEED, LAYER), N.stream())
+    t, grad = Guarded(M, AUG, torch.bfloat16), Guarded(1, r * (modules * D + N1), torch.float32)
+    rc = fn(N.ptr(o["dpre"]), N.ptr(o["h_aug"]), N.ptr(o["flat"]), r, SCALING, grad.ptr(), t.ptr(), ws.ptr(), wsb, M, N1, D, drop_arg(p_drop, SEED, LAYER), N.stream())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert t.guards_intact() and grad.guards_intact() and ws.guards_intact(), "wrote outside its outputs"
     return t.payload.clone(), grad.payload.clone().reshape(-1)
 
 
-@pytest.mark.parametrize("N1,D,r,M,p_drop", GRAD_CASES)
-def test_lora_mlp_pair_grad(N1, D, r, M, p_drop):
-    o = operands(M, N1, D, r, p_drop)
-    runs = [run_grad(o, M, N1, D, r, p_drop) for _ in range(2)]
+def grad_params():
+    """every case for the pair (under the ids the cases have always had) and for the single module"""
+    for modules in (2, 1):
+        for case in GRAD_CASES:
+            name = "-".join(str(v) for v in case)
+            yield pytest.param(*case, modules, id=name if modules == 2 else name + "-single")
+
+
+@pytest.mark.parametrize("N1,D,r,M,p_drop,modules", grad_params())
+def test_lora_mlp_pair_grad(N1, D, r, M, p_drop, modules):
+    o = operands(M, N1, D, r, p_drop, modules=modules)
+    runs = [run_grad(o, M, N1, D, r, p_drop, modules) for _ in range(2)]
     assert torch.equal(runs[0][0].view(torch.int16), runs[1][0].view(torch.int16)) and torch.equal(runs[0][1], runs[1][1]), "two runs differ"
     t_out, grad = runs[0][0].float().cpu(), runs[0][1].cpu()
     assert bool(torch.isfinite(t_out).all()) and bool(torch.isfinite(grad).all()), "left elements unwritten"
-    assert float(t_out[:, 2 * r:].abs().max()) == 0.0           # the unused aug columns
-    e_t = maxdiff(t_out[:, :2 * r], o["t_ref"]) / max(1.0, o["t_ref"].abs().max().item())
-    gA, gB = grad[:2 * r * D].reshape(2, r, D), grad[2 * r * D:].reshape(N1, r)
+    assert float(t_out[:, modules * r:].abs().max()) == 0.0     # the unused aug columns
+    e_t = maxdiff(t_out[:, :modules * r], o["t_ref"]) / max(1.0, o["t_ref"].abs().max().item())
+    gA, gB = grad[:modules * r * D].reshape(modules, r, D), grad[modules * r * D:].reshape(N1, r)
     e_a = 0.0
-    for p in range(2):                                           # dA_p = t_p^T drop_p(h), from the bf16 t the kernel wrote, under mask p
+    for p in range(modules):                                     # dA_p = t_p^T drop_p(h), from the bf16 t the kernel wrote, under mask p
         dA_ref = (t_out[:, p * r:(p + 1) * r].double().to(DEV).t() @ o["hd"][p]).cpu()
         e_a = max(e_a, maxdiff(gA[p], dA_ref) / max(1.0, dA_ref.abs().max().item()))
         assert float(gA[p].abs().max()) > 0
-        if p_drop > 0:                                           # ... and not under the other module's mask
+        if p_drop > 0 and modules == 2:                          # ... and not under the other module's mask
             other = (t_out[:, p * r:(p + 1) * r].double().to(DEV).t() @ o["hd"][1 - p]).cpu()
             assert maxdiff(gA[p], other) > 100 * 2e-4 * max(1.0, dA_ref.abs().max().item())
     e_b = maxdiff(gB, o["dB_ref"]) / max(1.0, o["dB_ref"].abs().max().item())
-    print(f"lora_mlp_pair_grad {(M, N1, D, r)} p={p_drop}: t {e_t:.2e} dA {e_a:.2e} dB {e_b:.2e}")
+    print(f"lora_mlp_grad, {modules} module(s) {(M, N1, D, r)} p={p_drop}: t {e_t:.2e} dA {e_a:.2e} dB {e_b:.2e}")
     assert e_t < 1e-2 and e_a < 2e-4 and e_b < 2e-4, (e_t, e_a, e_b)
-    assert float(gB[o["gate"]].abs().max()) > 0 and float(gB[~o["gate"]].abs().max()) > 0
+    assert float(gB.abs().max()) > 0
+    if modules == 2:
+        assert float(gB[o["gate"]].abs().max()) > 0 and float(gB[~o["gate"]].abs().max()) > 0
 
 
 @pytest.mark.parametrize("N1,D,r,M,p_drop", [(3072, 768, 3, 37, 0.05), (8192, 128, 2, 41, 0.0)])

@@ -596,26 +596,35 @@ __global__ __launch_bounds__(192 * NS) void lora_grad_kernel(bf16_raw* __restric
   for (int i = threadIdx.x; i < nA + nB; i += 192 * NS) out[i] = lds[i];
 }
 
+// The front of every reduce kernel here, called by all 256 threads of the workgroup: partial [nblk][n] summed over the block list in a fixed order.  A workgroup
+// takes 32 elements x 8 slices of the block list (a single thread walking all 512 partials was latency-bound): slice sl adds blocks sl, sl + 8, ... in ascending
+// order, then the slices are added in ascending order through LDS.  True for the one thread that holds the total `s` of element `i` (slice 0, i < n).
+__device__ __forceinline__ bool sum_partials(const float* __restrict__ partial, int nblk, int n, int& i, float& s) {
+  __shared__ float red[8][33];
+  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  i = blockIdx.x * 32 + e;
+  s = 0.f;
+  if (i < n) {
+#pragma unroll 4
+    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
+  }
+  red[sl][e] = s;
+  __syncthreads();
+  if (sl != 0 || i >= n) return false;
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += red[k][e];
+  return true;
+}
+
 // grad layout = parameter layout of the layer: [A_q | B_q | A_k | B_k | A_v | B_v]; accumulate = add to existing content
 template <int RW>
 __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int r, int j0, float* __restrict__ grad,
                                                                int D, int accumulate) {
-  // 32 elements x 8 slices of the block list per workgroup (a single thread walking all 512 partials was latency-bound)
-  __shared__ float red[8][33];
   const int nA = 3 * RW * D, nB = 3 * D * RW;
-  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + e;
-  float s = 0.f;
-  if (i < nA + nB) {
-#pragma unroll 4
-    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * (nA + nB) + i];
-  }
-  red[sl][e] = s;
-  __syncthreads();
-  if (sl != 0 || i >= nA + nB) return;
-  s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s += red[k][e];
+  int i;
+  float s;
+  if (!sum_partials(partial, nblk, nA + nB, i, s)) return;
   int p, j, d;
   size_t dst;
   if (i < nA) {
@@ -919,45 +928,56 @@ extern "C" int ucod_lora_grad(void* dqkv_aug, const void* h_aug, const float* lo
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// LoRA on the MLP input projection (fc1; weights_in of the SwiGLU MLP): ONE module of width N1 whose input is LayerNorm 2's output.
-//   forward   h2_aug [M, D+64] = [ LN2(x) | u = drop(LN2(x)) A_m^T (r values) | 0 ]          (ucod_layernorm_lora_mlp: ln_lora*_kernel with NP = 1)
-//             fc1_w_aug [N1, D+64] = [ fc1_w | alpha/r * B_m | 0 ]                            (ucod_lora_mlp_pack)
+// LoRA on the MLP input projection (fc1; weights_in of the SwiGLU MLP; DINOv3's up_proj / gate_proj): NM modules on the one GEMM of width N1 whose input is
+// LayerNorm 2's output.  NM = 1 is the single module (the _lora_mlp entry points).  NM = 2 is the gated MLP's pair (the _lora_mlp_pair entry points; DINOv3
+// vits16plus: down_proj(silu(gate_proj(x)) * up_proj(x)); full_model.py:47-72 hands target_modules to peft, to which gate_proj and up_proj are TWO modules, each
+// with its own A, B and dropout mask): both sit on the fused, padded, 4-interleaved weights_in, engine row 8k+e is gate row 4k+e for e < 4, row 8k+4+e is up row
+// 4k+e, so together they are a rank-2r module whose B is block diagonal.  mod(n) is the module of row n: (n % 8 >= 4) at NM = 2, else 0.
+//   forward   h2_aug [M, D+64] = [ LN2(x) | u_0 = drop_0(LN2 x) A_0^T (r) | .. | u_{NM-1} (r) | 0 ]                         (ln_lora*_kernel with NP = NM)
+//             fc1_w_aug [N1, D+64]: row n carries alpha/r * B_m[n][:] at columns D + mod(n) r ..., zeros in every other aug column  (lora_mlp_pack_kernel)
 //   backward  dpre [M, N1] comes out of the fc2 dgrad's drain without aug columns, so
-//             t = alpha/r * dpre B_m -> scratch [M, 64],  dB_m = alpha/r * dpre^T u,  dA_m = t^T drop(LN2(x))     (ucod_lora_mlp_grad)
-//             and the t A_m term of d LN2 is added by the LayerNorm-2 backward             (ucod_layernorm_bwd_lora_mlp: ln_bwd_kernel with LORA = 1)
-// Parameter layout of one layer (f32): [A_m (r x D) | B_m (N1 x r)].
+//             t_p = alpha/r * dpre[:, rows of p] B_p -> scratch [M, 64] at columns p r + j,  dB rows of p = alpha/r * dpre^T u_p,  dA_p = t_p^T drop_p(LN2 x)
+//             in ONE pass over dpre per two ranks (lora_mlp_grad_kernel), and d LN2 += sum_p mask_p/(1-p) (t_p A_p) in the LayerNorm-2 backward
+//             (ln_bwd_kernel with LORA = NM)
+// Parameter layout of one layer (f32): [A_0 (r x D) | .. | A_{NM-1} (r x D) | B_m (N1 x r)], B_m in the engine's row order -- the pair's is byte for byte the
+// single module's.  An untargeted module of the pair has A = 0 and its rows of B = 0; its gradients are then zero by structure (u = 0 gives dB = 0, t = 0 gives
+// dA = 0), because no sum here mixes the two modules' elements.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace ucod {
 
-__global__ __launch_bounds__(256) void lora_mlp_pack_kernel(const float* __restrict__ lora, int r, float scaling, bf16_raw* __restrict__ w_aug, int N1, int D) {
+__global__ __launch_bounds__(256) void lora_mlp_pack_kernel(const float* __restrict__ lora, int nm, int r, float scaling, bf16_raw* __restrict__ w_aug, int N1,
+                                                            int D) {
   const int idx = blockIdx.x * 256 + threadIdx.x;                // one thread per (row, aug column)
   if (idx >= N1 * AUG) return;
-  const int n = idx / AUG, j = idx - n * AUG;
-  const float v = j < r ? scaling * lora[(size_t)r * D + (size_t)n * r + j] : 0.f;              // B_m[n][j]
-  w_aug[(size_t)n * (D + AUG) + D + j] = f32_to_bf16(v);
+  const int n = idx / AUG, c = idx - n * AUG;
+  const int j = c - ((nm == 2 && (n & 4)) ? r : 0);              // rank within the row's own module (the pair's gate: n % 8 < 4)
+  const float v = (j >= 0 && j < r) ? scaling * lora[(size_t)nm * r * D + (size_t)n * r + j] : 0.f;            // B_m[n][j]
+  w_aug[(size_t)n * (D + AUG) + D + c] = f32_to_bf16(v);
 }
 
 constexpr int MLP_RB = 4;                                        // rows per iteration = waves per block (wave q writes row q's t)
 constexpr int MLP_RW = 2;                                        // ranks per pass, as lora_grad_kernel (the reference's r = 2 is one pass; r = 8 reads dpre four times)
 static inline int mlp_grad_max_blocks(int N1) { return N1 > 4096 ? 256 : 512; }   // one block per CU at 4 vectors per thread (256 VGPRs + AGPRs: one wave per SIMD), else two
 
-// Ranks [j0, j0 + 2) of the module in one pass over dpre and h2_aug.  The block's 256 threads share a row: thread `tid` owns the 16-byte vectors tid + 256 i of
-// the dpre row (its B_m values and dB accumulators stay in registers for all the block's rows) and the column pairs tid + 256 i of h2 (dA accumulators).  MLP_RB
+// Ranks [j0, j0 + 2) of the NM modules in one pass over dpre and h2_aug.  The block's 256 threads share a row: thread `tid` owns the 16-byte vectors tid + 256 i
+// of the dpre row (its B_m values and dB accumulators stay in registers for all the block's rows) and the column pairs tid + 256 i of h2 (dA accumulators).  MLP_RB
 // rows are loaded together, their partial t summed over the block through LDS (one barrier per MLP_RB rows: two buffers in turn), rounded to bf16 as the
-// LayerNorm-2 backward will read it, and used for dA.  No element has two owners in a block, so the partials go straight to memory: [2][D] | [N1][2] per block,
-// summed in a fixed order by lora_mlp_grad_reduce_kernel.  Rows past the end load nothing and contribute zeros.
-// Measured: 2.0 TB/s at ViT-B and at ViT-g, where <4, *> takes 256 VGPRs + 125-145 AGPRs (one wave per SIMD) and nothing overlaps a group's loads.
-// h2 is the smaller operand (D+64 against N1 columns) and is read with 4-byte loads.
-template <int NVT, int NPT>
+// LayerNorm-2 backward will read it, and used for dA.  At NM = 2 a 16-byte dpre vector holds four gate elements (0-3) and four up elements (4-7): bw / accB keep
+// their shape, each element taking u of its own module; the row sum s, the bf16-rounded t and accA carry the module index, dA of module p uses mask p.  No element
+// has two owners in a block, so the partials go straight to memory: [NM][2][D] | [N1][2] per block, summed in a fixed order by lora_mlp_grad_reduce_kernel.  Rows
+// past the end load nothing and contribute zeros.
+// Measured: 2.0 TB/s at ViT-B and at ViT-g, where <1, 4, *> takes 256 VGPRs + 125-145 AGPRs (one wave per SIMD) and nothing overlaps a group's
+// loads.  h2 is the smaller operand (D+64 against N1 columns) and is read with 4-byte loads.
+template <int NM, int NVT, int NPT>
 __global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __restrict__ dpre, const bf16_raw* __restrict__ h, const float* __restrict__ lora,
                                                             int r, int j0, float scaling, float* __restrict__ partial, bf16_raw* __restrict__ tout, int rows,
                                                             int N1, int D, Drop drop) {
   constexpr int RW = MLP_RW, RB = MLP_RB;
-  __shared__ float red[2][4][RB][RW];
+  __shared__ float red[2][4][RB][NM][RW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int NV = N1 / 8, NP2 = D / 2, ldh = D + AUG;
-  const float* Bm = lora + (size_t)r * D;
-  float bw[NVT][8][RW], accB[NVT][8][RW], accA[RW][NPT][2];
+  const float* Bm = lora + (size_t)NM * r * D;
+  float bw[NVT][8][RW], accB[NVT][8][RW], accA[NM][RW][NPT][2];
 #pragma unroll
   for (int i = 0; i < NVT; ++i) {
     const int v = tid + 256 * i;
@@ -970,251 +990,7 @@ __global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __re
       }
   }
 #pragma unroll
-  for (int j = 0; j < RW; ++j)
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) accA[j][i][0] = accA[j][i][1] = 0.f;
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  int buf = 0;
-  for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB, buf ^= 1) {
-    u4 dw[RB][NVT];
-    unsigned hw_[RB][NPT];
-    float u[RB][RW];
-#pragma unroll
-    for (int q = 0; q < RB; ++q) {
-      const bool live = row0 + q < rows;
-      const int row = live ? row0 + q : rows - 1;
-      const u4* dr = reinterpret_cast<const u4*>(dpre + (size_t)row * N1);
-      const unsigned* hr = reinterpret_cast<const unsigned*>(h + (size_t)row * ldh);
-#pragma unroll
-      for (int i = 0; i < NVT; ++i) dw[q][i] = (live && tid + 256 * i < NV) ? dr[tid + 256 * i] : (u4)(0u);
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) hw_[q][i] = (live && tid + 256 * i < NP2) ? hr[tid + 256 * i] : 0u;
-#pragma unroll
-      for (int j = 0; j < RW; ++j) u[q][j] = (live && j0 + j < r) ? bf16_to_f32(h[(size_t)row * ldh + D + j0 + j]) : 0.f;   // (block-uniform address)
-    }
-    float t[RB][RW];
-#pragma unroll
-    for (int q = 0; q < RB; ++q) {
-      float s[RW];
-#pragma unroll
-      for (int j = 0; j < RW; ++j) s[j] = 0.f;
-#pragma unroll
-      for (int i = 0; i < NVT; ++i)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const float d0 = __uint_as_float(dw[q][i][w] << 16), d1 = __uint_as_float(dw[q][i][w] & 0xFFFF0000u);
-#pragma unroll
-          for (int j = 0; j < RW; ++j) {
-            s[j] += d0 * bw[i][2 * w][j] + d1 * bw[i][2 * w + 1][j];
-            accB[i][2 * w][j] += d0 * u[q][j];
-            accB[i][2 * w + 1][j] += d1 * u[q][j];
-          }
-        }
-#pragma unroll
-      for (int j = 0; j < RW; ++j) {
-        const float ws = wave_sum(s[j]);
-        if (lane == 0) red[buf][wave][q][j] = ws;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < RB; ++q)
-#pragma unroll
-      for (int j = 0; j < RW; ++j)     // the LayerNorm-2 backward sees the bf16 value: use it for dA too
-        t[q][j] = bf16_to_f32(f32_to_bf16(scaling * ((red[buf][0][q][j] + red[buf][1][q][j]) + (red[buf][2][q][j] + red[buf][3][q][j]))));
-    // wave q writes the 64 t columns of row q: the first pass every column (zeros beyond the rank), later passes their two
-#pragma unroll
-    for (int q = 0; q < RB; ++q) {
-      if (q != wave || row0 + q >= rows) continue;
-      const int c = lane - j0;
-      const float val = (c == 0 && j0 < r) ? t[q][0] : (c == 1 && j0 + 1 < r) ? t[q][1] : 0.f;
-      if (j0 == 0 || (c >= 0 && c < RW && lane < r)) tout[(size_t)(row0 + q) * AUG + lane] = f32_to_bf16(val);
-    }
-#pragma unroll
-    for (int q = 0; q < RB; ++q)
-#pragma unroll
-      for (int i = 0; i < NPT; ++i) {
-        float h0 = __uint_as_float(hw_[q][i] << 16), h1 = __uint_as_float(hw_[q][i] & 0xFFFF0000u);
-        if (drop.thresh) {                                       // dA sees the SAME dropped input the forward's lora_A saw
-          const unsigned idx = (unsigned)(row0 + q) * (unsigned)D + 2u * (unsigned)(tid + 256 * i);
-          h0 *= drop_scale(drop, 0, idx);
-          h1 *= drop_scale(drop, 0, idx + 1u);
-        }
-#pragma unroll
-        for (int j = 0; j < RW; ++j) {
-          accA[j][i][0] += t[q][j] * h0;
-          accA[j][i][1] += t[q][j] * h1;
-        }
-      }
-  }
-  float* out = partial + (size_t)blockIdx.x * (size_t)(RW * D + N1 * RW);
-#pragma unroll
-  for (int j = 0; j < RW; ++j)
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int c = tid + 256 * i;
-      if (c < NP2) *reinterpret_cast<float2*>(out + (size_t)j * D + 2 * c) = make_float2(accA[j][i][0], accA[j][i][1]);
-    }
-  out += RW * D;
-#pragma unroll
-  for (int i = 0; i < NVT; ++i) {
-    const int v = tid + 256 * i;
-    if (v >= NV) continue;
-    typedef float f4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int e = 0; e < 8; e += 2)       // rows 8v+e, 8v+e+1 of [N1][2]: four consecutive floats
-      *reinterpret_cast<f4*>(out + (size_t)(8 * v + e) * RW) =
-          (f4){scaling * accB[i][e][0], scaling * accB[i][e][1], scaling * accB[i][e + 1][0], scaling * accB[i][e + 1][1]};
-  }
-}
-
-// partial [nblk][2 D + 2 N1] -> grad [A_m (r x D) | B_m (N1 x r)], ranks [j0, j0 + 2): 32 elements x 8 slices of the block list per workgroup
-__global__ __launch_bounds__(256) void lora_mlp_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int r, int j0, float* __restrict__ grad, int N1,
-                                                                   int D) {
-  constexpr int RW = MLP_RW;
-  __shared__ float red[8][33];
-  const int nA = RW * D, n = nA + N1 * RW;
-  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + e;
-  float s = 0.f;
-  if (i < n) {
-#pragma unroll 4
-    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
-  }
-  red[sl][e] = s;
-  __syncthreads();
-  if (sl != 0 || i >= n) return;
-  s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s += red[k][e];
-  if (i < nA) {
-    const int j = i / D, d = i - j * D;
-    if (j0 + j < r) grad[(size_t)(j0 + j) * D + d] = s;
-  } else {
-    const int k = i - nA, row = k / RW, j = k - row * RW;
-    if (j0 + j < r) grad[(size_t)r * D + (size_t)row * r + j0 + j] = s;
-  }
-}
-
-}  // namespace ucod
-
-extern "C" int ucod_layernorm_lora_mlp(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_m, int r, void* y_aug, int rows, int D,
-                                       float eps, const ucod_lora_dropout* dropout, void* stream) {
-  UCOD_BF16_ONLY();
-  if (r < 1 || r > UCOD_LORA_MLP_MAX_R) return UCOD_EINVAL;
-  return launch_ln_lora(x, x_f16 != 0, gamma, beta, a_m, r, y_aug, rows, D, eps, dropout, stream, 1);
-}
-
-extern "C" int ucod_lora_mlp_pack(const float* lora_mlp, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
-  UCOD_BF16_ONLY();
-  if (!lora_mlp || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || D <= 0) return UCOD_EINVAL;
-  UCOD_PROF(PROF_LORA, stream);
-  hipLaunchKernelGGL(lora_mlp_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora_mlp, r, scaling, (bf16_raw*)fc1_w_aug, N1, D);
-  UCOD_CHECK_LAUNCH();
-  return UCOD_OK;
-}
-
-extern "C" size_t ucod_lora_mlp_grad_workspace_bytes(int N1, int D) {
-  if (N1 <= 0 || N1 > 8192 || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
-  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (D + N1)) * sizeof(float);
-}
-
-extern "C" int ucod_lora_mlp_grad(const void* dpre, const void* h2_aug, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
-                                  void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
-  UCOD_BF16_ONLY();
-  if (!dpre || !h2_aug || !lora_mlp || !grad_mlp || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
-  const size_t need = ucod_lora_mlp_grad_workspace_bytes(N1, D);
-  if (need == 0) return UCOD_EINVAL;
-  if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
-  if (workspace_bytes < need) return UCOD_ENOMEM;
-  UCOD_PROF(PROF_LORA_MLP_GRAD, stream);
-  const Drop drop = make_drop(dropout);
-  hipStream_t s = (hipStream_t)stream;
-  const int cap = mlp_grad_max_blocks(N1);
-  const int nblk = cdiv(rows, MLP_RB) < cap ? cdiv(rows, MLP_RB) : cap;
-  const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors, 1..3 column pairs per thread
-  for (int j0 = 0; j0 < r; j0 += MLP_RW) {
-#define MG(v, p) hipLaunchKernelGGL((lora_mlp_grad_kernel<v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora_mlp, r, j0, \
-                                    scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
-#define MGP(v)                   \
-  do {                           \
-    if (npt == 1) MG(v, 1);      \
-    else if (npt == 2) MG(v, 2); \
-    else MG(v, 3);               \
-  } while (0)
-    if (nvt == 1) MGP(1);
-    else if (nvt == 2) MGP(2);
-    else MGP(4);                                                  // (3 vectors per thread run the 4-vector form: the fourth is never live)
-#undef MGP
-#undef MG
-    UCOD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, r, j0, grad_mlp, N1, D);
-    UCOD_CHECK_LAUNCH();
-  }
-  return UCOD_OK;
-}
-
-extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
-                                           void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
-                                           const ucod_lora_dropout* dropout, void* stream) {
-  UCOD_BF16_ONLY();
-  if (!dy || !x || !gamma || (!dx && !s_bf16) || rows <= 0 || D <= 0 || (D % 128) != 0 || !t_bf16 || ldt < r || !a_m || r < 1 || r > UCOD_LORA_MLP_MAX_R ||
-      (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) || (flags & ~3))
-    return UCOD_EINVAL;
-  UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
-  return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
-                       (const bf16_raw*)t_bf16, ldt, a_m, r, make_drop(dropout), (hipStream_t)stream, 1);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// LoRA on the gated MLP's input (DINOv3 vits16plus: down_proj(silu(gate_proj(x)) * up_proj(x)); full_model.py:47-72 hands target_modules to peft, to which
-// gate_proj and up_proj are TWO modules, each with its own A, B and dropout mask).  Both sit on the one fused, padded, 4-interleaved weights_in GEMM: engine row
-// 8k+e is gate row 4k+e for e < 4, row 8k+4+e is up row 4k+e.  Together they are a rank-2r module whose B is block diagonal:
-//   forward   h2_aug [M, D+64] = [ LN2(x) | drop_0(LN2 x) A_g^T (r) | drop_1(LN2 x) A_u^T (r) | 0 ]      (ucod_layernorm_lora_mlp_pair: ln_lora*_kernel with NP = 2)
-//             fc1_w_aug [N1, D+64]: row n carries alpha/r * B_m[n][:] at columns D + mod(n) r ..., mod(n) = (n % 8 >= 4); zeros elsewhere  (ucod_lora_mlp_pair_pack)
-//   backward  t_p = alpha/r * dpre[:, rows of p] B_p -> scratch [M, 64] at columns p r + j,  dB rows of p = alpha/r * dpre^T u_p,  dA_p = t_p^T drop_p(LN2 x)
-//             in ONE pass over dpre per two ranks (ucod_lora_mlp_pair_grad); d LN2 += sum_p mask_p/(1-p) (t_p A_p)  (ucod_layernorm_bwd_lora_mlp_pair: LORA = 2)
-// Parameter layout of one layer (f32): [A_g (r x D) | A_u (r x D) | B_m (N1 x r)], B_m in the engine's row order -- byte for byte the single module's B_m.
-// An untargeted module of the pair has A = 0 and its rows of B = 0; its gradients are then zero by structure (u = 0 gives dB = 0, t = 0 gives dA = 0), because no
-// sum here mixes the two modules' elements.
-// ---------------------------------------------------------------------------------------------------------------------
-namespace ucod {
-
-__global__ __launch_bounds__(256) void lora_mlp_pair_pack_kernel(const float* __restrict__ lora, int r, float scaling, bf16_raw* __restrict__ w_aug, int N1, int D) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;                // one thread per (row, aug column)
-  if (idx >= N1 * AUG) return;
-  const int n = idx / AUG, c = idx - n * AUG;
-  const int j = c - ((n & 4) ? r : 0);                           // rank within the row's own module (gate: n % 8 < 4)
-  const float v = (j >= 0 && j < r) ? scaling * lora[(size_t)2 * r * D + (size_t)n * r + j] : 0.f;
-  w_aug[(size_t)n * (D + AUG) + D + c] = f32_to_bf16(v);
-}
-
-// lora_mlp_grad_kernel for the pair.  A thread's 16-byte dpre vector holds four gate elements (0-3) and four up elements (4-7): bw / accB keep their shape, each
-// element taking u of its own module; the row sum s, the bf16-rounded t and accA carry a module index, dA of module p uses mask p.  t goes to columns p r + j of
-// the [M, 64] scratch.  Partials per block: [2][RW][D] | [N1][RW], summed in a fixed order by lora_mlp_pair_grad_reduce_kernel.
-template <int NVT, int NPT>
-__global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw* __restrict__ dpre, const bf16_raw* __restrict__ h, const float* __restrict__ lora,
-                                                                 int r, int j0, float scaling, float* __restrict__ partial, bf16_raw* __restrict__ tout, int rows,
-                                                                 int N1, int D, Drop drop) {
-  constexpr int RW = MLP_RW, RB = MLP_RB;
-  __shared__ float red[2][4][RB][2][RW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int NV = N1 / 8, NP2 = D / 2, ldh = D + AUG;
-  const float* Bm = lora + (size_t)2 * r * D;
-  float bw[NVT][8][RW], accB[NVT][8][RW], accA[2][RW][NPT][2];
-#pragma unroll
-  for (int i = 0; i < NVT; ++i) {
-    const int v = tid + 256 * i;
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-#pragma unroll
-      for (int j = 0; j < RW; ++j) {
-        bw[i][e][j] = (v < NV && j0 + j < r) ? Bm[(size_t)(8 * v + e) * r + j0 + j] : 0.f;
-        accB[i][e][j] = 0.f;
-      }
-  }
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < NM; ++m)
 #pragma unroll
     for (int j = 0; j < RW; ++j)
 #pragma unroll
@@ -1224,7 +1000,7 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
   for (int row0 = blockIdx.x * RB; row0 < rows; row0 += gridDim.x * RB, buf ^= 1) {
     u4 dw[RB][NVT];
     unsigned hw_[RB][NPT];
-    float u[RB][2][RW];
+    float u[RB][NM][RW];
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
       const bool live = row0 + q < rows;
@@ -1236,25 +1012,24 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
 #pragma unroll
       for (int i = 0; i < NPT; ++i) hw_[q][i] = (live && tid + 256 * i < NP2) ? hr[tid + 256 * i] : 0u;
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int j = 0; j < RW; ++j)                                // (block-uniform address; j0 + j < r <= 8 keeps m r + j0 + j inside the 64 aug columns)
           u[q][m][j] = (live && j0 + j < r) ? bf16_to_f32(h[(size_t)row * ldh + D + m * r + j0 + j]) : 0.f;
     }
-    float t[RB][2][RW];
+    float t[RB][NM][RW];
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
-      float s[2][RW];
+      float s[NM][RW];
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int j = 0; j < RW; ++j) s[m][j] = 0.f;
 #pragma unroll
       for (int i = 0; i < NVT; ++i)
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-          constexpr int HALF = 2;                                  // words 0, 1 = elements 0-3 (gate), words 2, 3 = elements 4-7 (up)
-          const int m = w / HALF;
+          const int m = NM == 2 ? w / 2 : 0;                       // the pair: words 0, 1 = elements 0-3 (gate), words 2, 3 = elements 4-7 (up)
           const float d0 = __uint_as_float(dw[q][i][w] << 16), d1 = __uint_as_float(dw[q][i][w] & 0xFFFF0000u);
 #pragma unroll
           for (int j = 0; j < RW; ++j) {
@@ -1264,7 +1039,7 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
           }
         }
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int j = 0; j < RW; ++j) {
           const float ws = wave_sum(s[m][j]);
@@ -1275,17 +1050,17 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
 #pragma unroll
     for (int q = 0; q < RB; ++q)
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int j = 0; j < RW; ++j)     // the LayerNorm-2 backward sees the bf16 value: use it for dA too
           t[q][m][j] = bf16_to_f32(f32_to_bf16(scaling * ((red[buf][0][q][m][j] + red[buf][1][q][m][j]) + (red[buf][2][q][m][j] + red[buf][3][q][m][j]))));
-    // wave q writes the 64 t columns of row q: the first pass every column (zeros beyond 2 r), later passes their two per module.  Lane = m r + jj.
+    // wave q writes the 64 t columns of row q: the first pass every column (zeros beyond NM r), later passes their two per module.  Lane = m r + jj.
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
       if (q != wave || row0 + q >= rows) continue;
-      const int m = lane >= r ? 1 : 0, c = lane - m * r - j0;      // c: this lane's rank within the pass
-      const bool mine = lane < 2 * r && c >= 0 && c < RW && j0 + c < r;
-      const float t0 = m ? t[q][1][0] : t[q][0][0], t1 = m ? t[q][1][1] : t[q][0][1];
+      const int m = (NM == 2 && lane >= r) ? 1 : 0, c = lane - m * r - j0;      // c: this lane's rank within the pass
+      const bool mine = lane < NM * r && c >= 0 && c < RW && j0 + c < r;
+      const float t0 = m ? t[q][NM - 1][0] : t[q][0][0], t1 = m ? t[q][NM - 1][1] : t[q][0][1];
       const float val = mine ? (c == 0 ? t0 : t1) : 0.f;
       if (j0 == 0 || mine) tout[(size_t)(row0 + q) * AUG + lane] = f32_to_bf16(val);
     }
@@ -1293,18 +1068,27 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
     for (int q = 0; q < RB; ++q)
 #pragma unroll
       for (int i = 0; i < NPT; ++i) {
-        const float h0 = __uint_as_float(hw_[q][i] << 16), h1 = __uint_as_float(hw_[q][i] & 0xFFFF0000u);
-        float k0[2] = {1.f, 1.f}, k1[2] = {1.f, 1.f};
-        if (drop.thresh) {                                       // dA_p sees the SAME dropped input the forward's lora_A of module p saw (one mix, two fields)
-          const unsigned idx = (unsigned)(row0 + q) * (unsigned)D + 2u * (unsigned)(tid + 256 * i);
+        float h0 = __uint_as_float(hw_[q][i] << 16), h1 = __uint_as_float(hw_[q][i] & 0xFFFF0000u);
+        float k0[NM], k1[NM];
 #pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            k0[m] = drop_scale(drop, m, idx);
-            k1[m] = drop_scale(drop, m, idx + 1u);
+        for (int m = 0; m < NM; ++m) k0[m] = k1[m] = 1.f;
+        if (drop.thresh) {                                       // dA_p sees the SAME dropped input the forward's lora_A of module p saw (one mix, NM fields)
+          const unsigned idx = (unsigned)(row0 + q) * (unsigned)D + 2u * (unsigned)(tid + 256 * i);
+          // One module: its scale goes into h here and k stays 1.  (Measured with kernel-resource-usage: k kept past the branch costs five of the nine NM = 1
+          // forms 4-10 registers; h scaled per module in here costs <2, 1, 1> a wave per SIMD.  Both give the same bits: t * (h * scale).)
+          if constexpr (NM == 1) {
+            h0 *= drop_scale(drop, 0, idx);
+            h1 *= drop_scale(drop, 0, idx + 1u);
+          } else {
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+              k0[m] = drop_scale(drop, m, idx);
+              k1[m] = drop_scale(drop, m, idx + 1u);
+            }
           }
         }
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < NM; ++m)
 #pragma unroll
           for (int j = 0; j < RW; ++j) {
             accA[m][j][i][0] += t[q][m][j] * (h0 * k0[m]);
@@ -1312,9 +1096,9 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
           }
       }
   }
-  float* out = partial + (size_t)blockIdx.x * (size_t)(2 * RW * D + N1 * RW);
+  float* out = partial + (size_t)blockIdx.x * (size_t)(NM * RW * D + N1 * RW);
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < NM; ++m)
 #pragma unroll
     for (int j = 0; j < RW; ++j)
 #pragma unroll
@@ -1322,7 +1106,7 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
         const int c = tid + 256 * i;
         if (c < NP2) *reinterpret_cast<float2*>(out + (size_t)(m * RW + j) * D + 2 * c) = make_float2(accA[m][j][i][0], accA[m][j][i][1]);
       }
-  out += 2 * RW * D;
+  out += NM * RW * D;
 #pragma unroll
   for (int i = 0; i < NVT; ++i) {
     const int v = tid + 256 * i;
@@ -1335,62 +1119,53 @@ __global__ __launch_bounds__(256) void lora_mlp_pair_grad_kernel(const bf16_raw*
   }
 }
 
-// partial [nblk][2 * 2 D + 2 N1] -> grad [A_g (r x D) | A_u (r x D) | B_m (N1 x r)], ranks [j0, j0 + 2): 32 elements x 8 slices of the block list per workgroup
-__global__ __launch_bounds__(256) void lora_mlp_pair_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int r, int j0, float* __restrict__ grad, int N1,
-                                                                        int D) {
+// partial [nblk][nm * 2 D + 2 N1] -> grad [A (nm x r x D) | B_m (N1 x r)], ranks [j0, j0 + 2)
+__global__ __launch_bounds__(256) void lora_mlp_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int nm, int r, int j0, float* __restrict__ grad,
+                                                                   int N1, int D) {
   constexpr int RW = MLP_RW;
-  __shared__ float red[8][33];
-  const int nA = 2 * RW * D, n = nA + N1 * RW;
-  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + e;
-  float s = 0.f;
-  if (i < n) {
-#pragma unroll 4
-    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
-  }
-  red[sl][e] = s;
-  __syncthreads();
-  if (sl != 0 || i >= n) return;
-  s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s += red[k][e];
+  const int nA = nm * RW * D;
+  int i;
+  float s;
+  if (!sum_partials(partial, nblk, nA + N1 * RW, i, s)) return;
   if (i < nA) {
     const int mj = i / D, d = i - mj * D, m = mj / RW, j = mj - m * RW;
     if (j0 + j < r) grad[(size_t)m * r * D + (size_t)(j0 + j) * D + d] = s;
   } else {
     const int k = i - nA, row = k / RW, j = k - row * RW;
-    if (j0 + j < r) grad[(size_t)2 * r * D + (size_t)row * r + j0 + j] = s;
+    if (j0 + j < r) grad[(size_t)nm * r * D + (size_t)row * r + j0 + j] = s;
   }
 }
 
 }  // namespace ucod
 
-extern "C" int ucod_layernorm_lora_mlp_pair(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_pair, int r, void* y_aug, int rows,
-                                            int D, float eps, const ucod_lora_dropout* dropout, void* stream) {
+// The ten entry points below are these five with modules = 1 (_lora_mlp) or 2 (_lora_mlp_pair).
+static int mlp_ln_lora(const void* x, int x_f16, const float* gamma, const float* beta, const float* a, int r, void* y_aug, int rows, int D, float eps,
+                       const ucod_lora_dropout* dropout, void* stream, int modules) {
   UCOD_BF16_ONLY();
   if (r < 1 || r > UCOD_LORA_MLP_MAX_R) return UCOD_EINVAL;
-  return launch_ln_lora(x, x_f16 != 0, gamma, beta, a_pair, r, y_aug, rows, D, eps, dropout, stream, 2);
+  return launch_ln_lora(x, x_f16 != 0, gamma, beta, a, r, y_aug, rows, D, eps, dropout, stream, modules);
 }
 
-extern "C" int ucod_lora_mlp_pair_pack(const float* lora_pair, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+static int mlp_pack(const float* lora, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream, int modules) {
   UCOD_BF16_ONLY();
-  if (!lora_pair || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || (N1 % 8) != 0 || D <= 0) return UCOD_EINVAL;
+  if (!lora || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || (modules == 2 && (N1 % 8) != 0) || D <= 0) return UCOD_EINVAL;
   UCOD_PROF(PROF_LORA, stream);
-  hipLaunchKernelGGL(lora_mlp_pair_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora_pair, r, scaling, (bf16_raw*)fc1_w_aug, N1, D);
+  hipLaunchKernelGGL(lora_mlp_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora, modules, r, scaling, (bf16_raw*)fc1_w_aug, N1,
+                     D);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
 
-extern "C" size_t ucod_lora_mlp_pair_grad_workspace_bytes(int N1, int D) {
+static size_t mlp_grad_workspace_bytes(int N1, int D, int modules) {
   if (N1 <= 0 || N1 > 8192 || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
-  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (2 * D + N1)) * sizeof(float);
+  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (modules * D + N1)) * sizeof(float);
 }
 
-extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
-                                       void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+static int mlp_grad(const void* dpre, const void* h2_aug, const float* lora, int r, float scaling, float* grad, void* t_bf16, void* workspace, size_t workspace_bytes,
+                    int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream, int modules) {
   UCOD_BF16_ONLY();
-  if (!dpre || !h2_aug || !lora_pair || !grad_pair || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
-  const size_t need = ucod_lora_mlp_pair_grad_workspace_bytes(N1, D);
+  if (!dpre || !h2_aug || !lora || !grad || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
+  const size_t need = mlp_grad_workspace_bytes(N1, D, modules);
   if (need == 0) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   if (workspace_bytes < need) return UCOD_ENOMEM;
@@ -1401,8 +1176,13 @@ extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, con
   const int nblk = cdiv(rows, MLP_RB) < cap ? cdiv(rows, MLP_RB) : cap;
   const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors, 1..3 column pairs per thread
   for (int j0 = 0; j0 < r; j0 += MLP_RW) {
-#define MG(v, p) hipLaunchKernelGGL((lora_mlp_pair_grad_kernel<v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora_pair, r, j0, \
-                                    scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
+#define MGK(nm, v, p) hipLaunchKernelGGL((lora_mlp_grad_kernel<nm, v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora, r, j0, \
+                                         scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
+#define MG(v, p)                        \
+  do {                                  \
+    if (modules == 2) MGK(2, v, p);     \
+    else MGK(1, v, p);                  \
+  } while (0)
 #define MGP(v)                   \
   do {                           \
     if (npt == 1) MG(v, 1);      \
@@ -1414,24 +1194,59 @@ extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, con
     else MGP(4);                                                  // (3 vectors per thread run the 4-vector form: the fourth is never live)
 #undef MGP
 #undef MG
+#undef MGK
     UCOD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lora_mlp_pair_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (2 * D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, r, j0, grad_pair,
-                       N1, D);
+    hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (modules * D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, modules, r, j0,
+                       grad, N1, D);
     UCOD_CHECK_LAUNCH();
   }
   return UCOD_OK;
 }
 
-extern "C" int ucod_layernorm_bwd_lora_mlp_pair(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
-                                                void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_pair, int r,
-                                                const ucod_lora_dropout* dropout, void* stream) {
+static int mlp_ln_bwd(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx, void* s_bf16, int rows,
+                      int D, float eps, const void* t_bf16, int ldt, const float* a, int r, const ucod_lora_dropout* dropout, void* stream, int modules) {
   UCOD_BF16_ONLY();
-  if (!dy || !x || !gamma || (!dx && !s_bf16) || rows <= 0 || D <= 0 || (D % 128) != 0 || !t_bf16 || ldt < 2 * r || !a_pair || r < 1 || r > UCOD_LORA_MLP_MAX_R ||
+  if (!dy || !x || !gamma || (!dx && !s_bf16) || rows <= 0 || D <= 0 || (D % 128) != 0 || !t_bf16 || ldt < modules * r || !a || r < 1 || r > UCOD_LORA_MLP_MAX_R ||
       (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) || (flags & ~3))
     return UCOD_EINVAL;
   UCOD_PROF(PROF_LN_BWD_LORA_MLP, stream);
   return launch_ln_bwd(dy, (flags & UCOD_LNB_DY_BF16) != 0, x, (flags & UCOD_LNB_X_F16) != 0, gamma, dres, next_scale, dx, s_bf16, rows, D, eps,
-                       (const bf16_raw*)t_bf16, ldt, a_pair, r, make_drop(dropout), (hipStream_t)stream, 2);
+                       (const bf16_raw*)t_bf16, ldt, a, r, make_drop(dropout), (hipStream_t)stream, modules);
+}
+
+extern "C" int ucod_layernorm_lora_mlp(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_m, int r, void* y_aug, int rows, int D,
+                                       float eps, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_ln_lora(x, x_f16, gamma, beta, a_m, r, y_aug, rows, D, eps, dropout, stream, 1);
+}
+extern "C" int ucod_layernorm_lora_mlp_pair(const void* x, int x_f16, const float* gamma, const float* beta, const float* a_pair, int r, void* y_aug, int rows,
+                                            int D, float eps, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_ln_lora(x, x_f16, gamma, beta, a_pair, r, y_aug, rows, D, eps, dropout, stream, 2);
+}
+extern "C" int ucod_lora_mlp_pack(const float* lora_mlp, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  return mlp_pack(lora_mlp, r, scaling, fc1_w_aug, N1, D, stream, 1);
+}
+extern "C" int ucod_lora_mlp_pair_pack(const float* lora_pair, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  return mlp_pack(lora_pair, r, scaling, fc1_w_aug, N1, D, stream, 2);
+}
+extern "C" size_t ucod_lora_mlp_grad_workspace_bytes(int N1, int D) { return mlp_grad_workspace_bytes(N1, D, 1); }
+extern "C" size_t ucod_lora_mlp_pair_grad_workspace_bytes(int N1, int D) { return mlp_grad_workspace_bytes(N1, D, 2); }
+extern "C" int ucod_lora_mlp_grad(const void* dpre, const void* h2_aug, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
+                                  void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_grad(dpre, h2_aug, lora_mlp, r, scaling, grad_mlp, t_bf16, workspace, workspace_bytes, rows, N1, D, dropout, stream, 1);
+}
+extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
+                                       void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_grad(dpre, h2_aug, lora_pair, r, scaling, grad_pair, t_bf16, workspace, workspace_bytes, rows, N1, D, dropout, stream, 2);
+}
+extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                           void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
+                                           const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_ln_bwd(dy, x, flags, gamma, dres, next_scale, dx, s_bf16, rows, D, eps, t_bf16, ldt, a_m, r, dropout, stream, 1);
+}
+extern "C" int ucod_layernorm_bwd_lora_mlp_pair(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
+                                                void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_pair, int r,
+                                                const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_ln_bwd(dy, x, flags, gamma, dres, next_scale, dx, s_bf16, rows, D, eps, t_bf16, ldt, a_pair, r, dropout, stream, 2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1921,23 +1736,11 @@ __global__ __launch_bounds__(128) void lora_out_grad_x_swiglu_kernel(const bf16_
     if (j < r) *reinterpret_cast<f4*>(out + (size_t)j * K) = (f4){acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
 }
 
-// partial [nblk][n] -> out [n], blocks in ascending order inside each of 8 slices, then the slices: 32 elements x 8 slices of the block list per workgroup
+// partial [nblk][n] -> out [n] (sum_partials: blocks in ascending order inside each of 8 slices, then the slices)
 __global__ __launch_bounds__(256) void lora_out_reduce_kernel(const float* __restrict__ partial, int nblk, int n, float* __restrict__ out) {
-  __shared__ float red[8][33];
-  const int e = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + e;
-  float s = 0.f;
-  if (i < n) {
-#pragma unroll 4
-    for (int b = sl; b < nblk; b += 8) s += partial[(size_t)b * n + i];
-  }
-  red[sl][e] = s;
-  __syncthreads();
-  if (sl != 0 || i >= n) return;
-  s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s += red[k][e];
-  out[i] = s;
+  int i;
+  float s;
+  if (sum_partials(partial, nblk, n, i, s)) out[i] = s;
 }
 
 static inline bool lora_out_dims_ok(int r, int K, int D) {
