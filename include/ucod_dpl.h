@@ -726,6 +726,32 @@ int ucod_lora_out_grad_x(const void* x_in_bf16, int act, void* cot_bf16, const f
  * unknown bit is UCOD_EINVAL).  out_flags = 0 is ucod_lora_out_grad_x, which delegates here. */
 int ucod_lora_out_grad_x_ex(const void* x_in_bf16, int act, int out_flags, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out,
                             void* workspace, size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
+/* Hidden widths past the register-resident forms (full_model.py:47-72: peft takes any Linear; DINOv3 ViT-H+/16 has a gated MLP of hidden width 5120, so
+ * N1 = 10240 and K = 5120).  The _wide entry points below are supersets of their namesakes: at N1 <= 8192 / K <= 4096 they enqueue the same launches with the same
+ * workspace size and give the same bits; above, up to UCOD_LORA_WIDE_MAX_N1 / UCOD_LORA_WIDE_MAX_K (what the wide kernels hold with no scratch memory),
+ *   ucod_lora_mlp_grad_wide / _pair_grad_wide   run the gradient kernel with FIVE 16-byte dpre vectors per thread and ONE rank per pass (r passes over dpre; the
+ *                                               partials are [modules][D] | [N1] per block, so the workspace is half the narrow formula's at the same N1),
+ *   ucod_lora_out_fwd_wide                      runs blocks of 512 threads with two 16-byte vectors each (eight wave partials, summed as two groups of four),
+ *   the others                                  run their one kernel (one thread per element, or K spread over blockIdx.y) with the real width.
+ * Same formulas, rounding points, dropout keys and mask indices as the narrow forms; D % 128 == 0, D <= 1536, r <= UCOD_LORA_MLP_MAX_R, widths % 128 == 0 as there
+ * (else the size is 0 and the call UCOD_EINVAL before any launch).  UCOD_LORA_WIDE in the flags word of ucod_lora_out_grad_x_ex is that function's wide form; in
+ * out_flags of the pass entry points (below) it makes the pass call the wide forms. */
+#define UCOD_LORA_WIDE 16
+#define UCOD_LORA_WIDE_MAX_N1 10240
+#define UCOD_LORA_WIDE_MAX_K 8192
+int ucod_lora_mlp_pack_wide(const float* lora_mlp, int r, float scaling, void* fc1_w_aug_bf16, int N1, int D, void* stream);
+int ucod_lora_mlp_pair_pack_wide(const float* lora_pair, int r, float scaling, void* fc1_w_aug_bf16, int N1, int D, void* stream);
+size_t ucod_lora_mlp_grad_workspace_bytes_wide(int N1, int D);
+size_t ucod_lora_mlp_pair_grad_workspace_bytes_wide(int N1, int D);
+int ucod_lora_mlp_grad_wide(const void* dpre_bf16, const void* h2_aug_bf16, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
+                            void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream);
+int ucod_lora_mlp_pair_grad_wide(const void* dpre_bf16, const void* h2_aug_bf16, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
+                                 void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream);
+size_t ucod_lora_out_grad_workspace_bytes_wide(int r, int K, int D);
+int ucod_lora_out_fwd_wide(const void* x_in_bf16, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out,
+                           int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream);
+int ucod_lora_out_grad_s_wide(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
+                              size_t workspace_bytes, int rows, int K, int D, void* stream);
 /* The _lora_out_ex forms with out_flags = 0: they refuse the fc2 slots on the SwiGLU MLP (TO, the output modules' own per-layer table, is described there; layer l at
  * UCOD_VIT_TRAIN_OUT_STRIDE*l). */
 #define UCOD_VIT_TRAIN_OUT_STRIDE 4
@@ -784,7 +810,7 @@ int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, 
  * out_flags:
  *   UCOD_LORA_OUT_SWIGLU   with UCOD_MLP_SWIGLU, slot +2 may be non-NULL: the LoRA module of the SwiGLU MLP's output projection (weights_out; the gated DINOv3
  *                          down_proj), parameters f32 [r (F + D)] with F the padded hidden width (K = F <= 4096 as above: ViT-g and vits16plus; vith16plus's
- *                          F = 5120 is refused).  Per layer below the last: one ucod_lora_out_fwd on the hidden [M, F] behind the weights_out residual GEMM (key
+ *                          F = 5120 needs UCOD_LORA_WIDE).  Per layer below the last: one ucod_lora_out_fwd on the hidden [M, F] behind the weights_out residual GEMM (key
  *                          3 L + l; the training pass saves u in the fc2 module's slots, so the workspace is the GELU formula with K = F); in the backward, behind
  *                          the UCOD_EPI_SWIGLU_BWD_BF16 GEMM, ucod_lora_out_grad_s on s and ucod_lora_out_grad_x_ex(pre, UCOD_LORA_OUT_ACT_SWIGLU, dpre) in front of
  *                          ucod_layernorm_lora_mlp / ucod_lora_mlp_grad and the weights_in dgrad.  The last layer's gradients are written as zeros.  With
@@ -792,7 +818,10 @@ int ucod_vit_forward_lora_infer_lora_out(const ucod_vit_train_desc* t, int mlp, 
  *   UCOD_LORA_MLP_PAIR     (full_model.py:47-72) valid only with UCOD_MLP_SWIGLU and a non-NULL TM (else UCOD_EINVAL, sizes 0): TM describes the gated MLP's PAIR
  *                          gate_proj / up_proj -- slots +1 / +2 are [A_g | A_u | B_m], r (2D + N1) floats, +0's aug columns maintained by ucod_lora_mlp_pair_pack --
  *                          and all three passes run ucod_layernorm_lora_mlp_pair / ucod_lora_mlp_pair_grad / ucod_layernorm_bwd_lora_mlp_pair where they ran the
- *                          single module's kernels (dropout key L + l, projections 0 and 1).  The last layer's r (2D + N1) gradients are written as zeros. */
+ *                          single module's kernels (dropout key L + l, projections 0 and 1).  The last layer's r (2D + N1) gradients are written as zeros.
+ *   UCOD_LORA_WIDE         (defined above; full_model.py:47-72) the pass sizes and runs the MLP and fc2 modules through the _wide row entry points, so TM may have
+ *                          N1 up to UCOD_LORA_WIDE_MAX_N1 and TO's fc2 slots F up to UCOD_LORA_WIDE_MAX_K (vith16plus: 10240 and 5120).  Valid only where a table
+ *                          needs it -- TM with N1 > 8192, or fc2 slots with F > 4096 -- else UCOD_EINVAL, sizes 0: a pass the narrow forms cover has one spelling. */
 #define UCOD_LORA_OUT_SWIGLU 1
 #define UCOD_LORA_MLP_PAIR 4
 size_t ucod_vit_train_workspace_bytes_lora_out_ex(const ucod_vit_train_desc* t, int mlp, int out_flags, const void* const* mlp_table_host,

@@ -3,7 +3,7 @@
 SwiGLU MLP; or a DINOv3 name such as dinov3_vitb16, rotary embedding in both passes, @512), per-class kernel times.
     lora_bench.py [B [steps [streams [dropout [resid [arch [targets [side] [bias]]]]]]]]
 ``targets``: comma list of LoRA target modules (default: the engine's query,key,value / q_proj,k_proj,v_proj), e.g. query,key,value,fc1 or query,key,value,weights_in
-on ViT-g, or q_proj,k_proj,v_proj,gate_proj,up_proj on dinov3_vits16plus (a DINOv3 MLP input module switches ``allow_mlp_in`` on); naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
+on ViT-g, or q_proj,k_proj,v_proj,gate_proj,up_proj on dinov3_vits16plus (a DINOv3 MLP input module switches ``allow_mlp_in`` on, an MLP module of dinov3_vith16plus ``allow_wide_mlp``); naming an output projection (dense, fc2; o_proj, down_proj) switches the engine's ``allow_out`` on, e.g. query,key,value,dense,fc2.  ``side``: the image side in pixels, a multiple of the patch size (default 518; 512 on a DINOv3 arch, patch 16).
 ``bias``: a trailing none / lora_only / all (peft's LoraConfig.bias; with or without ``side`` in front of it): lora_only also trains the targeted modules' biases -- one
 deterministic column sum per bias and layer in the backward (tools/lora_bias_bench.py times the three modes against each other in one process)."""
 import ctypes as C, os, sys, time
@@ -42,6 +42,8 @@ if "weights_out" in leaves or ("down_proj" in leaves and arch in SWIGLU_ARCHS):
     kw.update(allow_swiglu_out=True)                      # ... and the SwiGLU MLP's has an opt-in of its own (the hidden is recomputed in the backward)
 if v3 and any(t in ("up_proj", "gate_proj") for t in leaves):
     kw.update(allow_mlp_in=True)                          # DINOv3's MLP input modules are opt-in too (on the gated MLP: the gate_proj / up_proj pair kernels)
+if arch == "dinov3_vith16plus" and any(t in ("up_proj", "gate_proj", "down_proj") for t in leaves):
+    kw.update(allow_wide_mlp=True)                        # hidden 5120: N1 = 10240 rows and K = 5120 columns are the wide row kernels' (UCOD_LORA_WIDE)
 eng = ViTLoRAEngine(random_state_dict(arch, seed=0), heads=heads, device="cuda", lora_dropout=drop, resid=resid, allow_swiglu=giant or arch in SWIGLU_ARCHS, **kw)
 if targets is not None:
     print(f"targets {targets}, bias {bias}: arena [{eng.L}, {eng.lora.shape[1]}]")

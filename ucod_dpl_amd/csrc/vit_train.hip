@@ -966,13 +966,15 @@ static inline int mlp_grad_max_blocks(int N1) { return N1 > 4096 ? 256 : 512; } 
 // their shape, each element taking u of its own module; the row sum s, the bf16-rounded t and accA carry the module index, dA of module p uses mask p.  No element
 // has two owners in a block, so the partials go straight to memory: [NM][2][D] | [N1][2] per block, summed in a fixed order by lora_mlp_grad_reduce_kernel.  Rows
 // past the end load nothing and contribute zeros.
+// RW = 1, NVT = 5 is the wide form (8192 < N1 <= UCOD_LORA_WIDE_MAX_N1): a fifth vector per thread fits the register file only with one rank per pass, so it
+// reads dpre r times; its partials are [NM][D] | [N1] per block.
 // Measured: 2.0 TB/s at ViT-B and at ViT-g, where <1, 4, *> takes 256 VGPRs + 125-145 AGPRs (one wave per SIMD) and nothing overlaps a group's
 // loads.  h2 is the smaller operand (D+64 against N1 columns) and is read with 4-byte loads.
-template <int NM, int NVT, int NPT>
+template <int NM, int NVT, int NPT, int RW = MLP_RW>
 __global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __restrict__ dpre, const bf16_raw* __restrict__ h, const float* __restrict__ lora,
                                                             int r, int j0, float scaling, float* __restrict__ partial, bf16_raw* __restrict__ tout, int rows,
                                                             int N1, int D, Drop drop) {
-  constexpr int RW = MLP_RW, RB = MLP_RB;
+  constexpr int RB = MLP_RB;
   __shared__ float red[2][4][RB][NM][RW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int NV = N1 / 8, NP2 = D / 2, ldh = D + AUG;
@@ -1060,7 +1062,7 @@ __global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __re
       if (q != wave || row0 + q >= rows) continue;
       const int m = (NM == 2 && lane >= r) ? 1 : 0, c = lane - m * r - j0;      // c: this lane's rank within the pass
       const bool mine = lane < NM * r && c >= 0 && c < RW && j0 + c < r;
-      const float t0 = m ? t[q][NM - 1][0] : t[q][0][0], t1 = m ? t[q][NM - 1][1] : t[q][0][1];
+      const float t0 = m ? t[q][NM - 1][0] : t[q][0][0], t1 = m ? t[q][NM - 1][RW - 1] : t[q][0][RW - 1];
       const float val = mine ? (c == 0 ? t0 : t1) : 0.f;
       if (j0 == 0 || mine) tout[(size_t)(row0 + q) * AUG + lane] = f32_to_bf16(val);
     }
@@ -1112,17 +1114,25 @@ __global__ __launch_bounds__(256) void lora_mlp_grad_kernel(const bf16_raw* __re
     const int v = tid + 256 * i;
     if (v >= NV) continue;
     typedef float f4 __attribute__((ext_vector_type(4)));
+    if constexpr (RW == 2) {
 #pragma unroll
-    for (int e = 0; e < 8; e += 2)       // rows 8v+e, 8v+e+1 of [N1][2]: four consecutive floats
-      *reinterpret_cast<f4*>(out + (size_t)(8 * v + e) * RW) =
-          (f4){scaling * accB[i][e][0], scaling * accB[i][e][1], scaling * accB[i][e + 1][0], scaling * accB[i][e + 1][1]};
+      for (int e = 0; e < 8; e += 2)     // rows 8v+e, 8v+e+1 of [N1][2]: four consecutive floats
+        *reinterpret_cast<f4*>(out + (size_t)(8 * v + e) * RW) =
+            (f4){scaling * accB[i][e][0], scaling * accB[i][e][1], scaling * accB[i][e + 1][0], scaling * accB[i][e + 1][1]};
+    } else {
+      static_assert(RW == 1 || RW == 2, "one or two ranks per pass");
+#pragma unroll
+      for (int e = 0; e < 8; e += 4)     // rows 8v+e .. 8v+e+3 of [N1][1]
+        *reinterpret_cast<f4*>(out + (size_t)(8 * v + e)) =
+            (f4){scaling * accB[i][e][0], scaling * accB[i][e + 1][0], scaling * accB[i][e + 2][0], scaling * accB[i][e + 3][0]};
+    }
   }
 }
 
-// partial [nblk][nm * 2 D + 2 N1] -> grad [A (nm x r x D) | B_m (N1 x r)], ranks [j0, j0 + 2)
+// partial [nblk][nm * RW D + RW N1] -> grad [A (nm x r x D) | B_m (N1 x r)], ranks [j0, j0 + RW)
+template <int RW>
 __global__ __launch_bounds__(256) void lora_mlp_grad_reduce_kernel(const float* __restrict__ partial, int nblk, int nm, int r, int j0, float* __restrict__ grad,
                                                                    int N1, int D) {
-  constexpr int RW = MLP_RW;
   const int nA = nm * RW * D;
   int i;
   float s;
@@ -1146,9 +1156,12 @@ static int mlp_ln_lora(const void* x, int x_f16, const float* gamma, const float
   return launch_ln_lora(x, x_f16 != 0, gamma, beta, a, r, y_aug, rows, D, eps, dropout, stream, modules);
 }
 
-static int mlp_pack(const float* lora, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream, int modules) {
+// wide: the _wide entry points, whose N1 may reach UCOD_LORA_WIDE_MAX_N1; up to 8192 they run what the narrow ones run
+static inline int mlp_max_n1(bool wide) { return wide ? UCOD_LORA_WIDE_MAX_N1 : 8192; }
+
+static int mlp_pack(const float* lora, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream, int modules, bool wide = false) {
   UCOD_BF16_ONLY();
-  if (!lora || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > 8192 || (modules == 2 && (N1 % 8) != 0) || D <= 0) return UCOD_EINVAL;
+  if (!lora || !fc1_w_aug || r < 1 || r > UCOD_LORA_MLP_MAX_R || N1 <= 0 || N1 > mlp_max_n1(wide) || (modules == 2 && (N1 % 8) != 0) || D <= 0) return UCOD_EINVAL;
   UCOD_PROF(PROF_LORA, stream);
   hipLaunchKernelGGL(lora_mlp_pack_kernel, dim3(cdiv((long)N1 * AUG, 256)), dim3(256), 0, (hipStream_t)stream, lora, modules, r, scaling, (bf16_raw*)fc1_w_aug, N1,
                      D);
@@ -1156,16 +1169,16 @@ static int mlp_pack(const float* lora, int r, float scaling, void* fc1_w_aug, in
   return UCOD_OK;
 }
 
-static size_t mlp_grad_workspace_bytes(int N1, int D, int modules) {
-  if (N1 <= 0 || N1 > 8192 || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
-  return (size_t)mlp_grad_max_blocks(N1) * (size_t)(MLP_RW * (modules * D + N1)) * sizeof(float);
+static size_t mlp_grad_workspace_bytes(int N1, int D, int modules, bool wide = false) {
+  if (N1 <= 0 || N1 > mlp_max_n1(wide) || (N1 % 128) != 0 || D <= 0 || D > 1536 || (D % 128) != 0) return 0;
+  return (size_t)mlp_grad_max_blocks(N1) * (size_t)((N1 > 8192 ? 1 : MLP_RW) * (modules * D + N1)) * sizeof(float);      // (the wide form: one rank per pass)
 }
 
 static int mlp_grad(const void* dpre, const void* h2_aug, const float* lora, int r, float scaling, float* grad, void* t_bf16, void* workspace, size_t workspace_bytes,
-                    int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream, int modules) {
+                    int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream, int modules, bool wide = false) {
   UCOD_BF16_ONLY();
   if (!dpre || !h2_aug || !lora || !grad || !t_bf16 || !workspace || r < 1 || r > UCOD_LORA_MLP_MAX_R || rows <= 0) return UCOD_EINVAL;
-  const size_t need = mlp_grad_workspace_bytes(N1, D, modules);
+  const size_t need = mlp_grad_workspace_bytes(N1, D, modules, wide);
   if (need == 0) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   if (workspace_bytes < need) return UCOD_ENOMEM;
@@ -1174,30 +1187,33 @@ static int mlp_grad(const void* dpre, const void* h2_aug, const float* lora, int
   hipStream_t s = (hipStream_t)stream;
   const int cap = mlp_grad_max_blocks(N1);
   const int nblk = cdiv(rows, MLP_RB) < cap ? cdiv(rows, MLP_RB) : cap;
-  const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors, 1..3 column pairs per thread
-  for (int j0 = 0; j0 < r; j0 += MLP_RW) {
-#define MGK(nm, v, p) hipLaunchKernelGGL((lora_mlp_grad_kernel<nm, v, p>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora, r, j0, \
-                                         scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
-#define MG(v, p)                        \
+  const int nvt = cdiv(N1 / 8, 256), npt = cdiv(D / 2, 256);       // 1..4 vectors (the wide form: 5), 1..3 column pairs per thread
+  const int rw = nvt > 4 ? 1 : MLP_RW;
+  for (int j0 = 0; j0 < r; j0 += rw) {
+#define MGK(nm, v, p, w) hipLaunchKernelGGL((lora_mlp_grad_kernel<nm, v, p, w>), dim3(nblk), dim3(256), 0, s, (const bf16_raw*)dpre, (const bf16_raw*)h2_aug, lora, r, \
+                                            j0, scaling, (float*)workspace, (bf16_raw*)t_bf16, rows, N1, D, drop)
+#define MG(v, p, w)                     \
   do {                                  \
-    if (modules == 2) MGK(2, v, p);     \
-    else MGK(1, v, p);                  \
+    if (modules == 2) MGK(2, v, p, w);  \
+    else MGK(1, v, p, w);               \
   } while (0)
-#define MGP(v)                   \
-  do {                           \
-    if (npt == 1) MG(v, 1);      \
-    else if (npt == 2) MG(v, 2); \
-    else MG(v, 3);               \
+#define MGP(v, w)                   \
+  do {                              \
+    if (npt == 1) MG(v, 1, w);      \
+    else if (npt == 2) MG(v, 2, w); \
+    else MG(v, 3, w);               \
   } while (0)
-    if (nvt == 1) MGP(1);
-    else if (nvt == 2) MGP(2);
-    else MGP(4);                                                  // (3 vectors per thread run the 4-vector form: the fourth is never live)
+    if (nvt == 1) MGP(1, MLP_RW);
+    else if (nvt == 2) MGP(2, MLP_RW);
+    else if (nvt <= 4) MGP(4, MLP_RW);                            // (3 vectors per thread run the 4-vector form: the fourth is never live)
+    else MGP(5, 1);                                               // (UCOD_LORA_WIDE_MAX_N1 / 8 / 256 = 5)
 #undef MGP
 #undef MG
 #undef MGK
     UCOD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel, dim3(cdiv((long)MLP_RW * (modules * D + N1), 32)), dim3(256), 0, s, (const float*)workspace, nblk, modules, r, j0,
-                       grad, N1, D);
+    const dim3 rgrid(cdiv((long)rw * (modules * D + N1), 32));
+    if (rw == 1) hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel<1>, rgrid, dim3(256), 0, s, (const float*)workspace, nblk, modules, r, j0, grad, N1, D);
+    else hipLaunchKernelGGL(lora_mlp_grad_reduce_kernel<MLP_RW>, rgrid, dim3(256), 0, s, (const float*)workspace, nblk, modules, r, j0, grad, N1, D);
     UCOD_CHECK_LAUNCH();
   }
   return UCOD_OK;
@@ -1237,6 +1253,24 @@ extern "C" int ucod_lora_mlp_grad(const void* dpre, const void* h2_aug, const fl
 extern "C" int ucod_lora_mlp_pair_grad(const void* dpre, const void* h2_aug, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
                                        void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
   return mlp_grad(dpre, h2_aug, lora_pair, r, scaling, grad_pair, t_bf16, workspace, workspace_bytes, rows, N1, D, dropout, stream, 2);
+}
+// The wide forms (include/ucod_dpl.h): N1 up to UCOD_LORA_WIDE_MAX_N1; up to 8192 the launches, the workspace and the bits of the forms above.
+static_assert(UCOD_LORA_WIDE_MAX_N1 == 5 * 256 * 8 && UCOD_LORA_WIDE_MAX_K == 2 * 512 * 8, "the wide kernels' vectors per thread");
+extern "C" int ucod_lora_mlp_pack_wide(const float* lora_mlp, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  return mlp_pack(lora_mlp, r, scaling, fc1_w_aug, N1, D, stream, 1, true);
+}
+extern "C" int ucod_lora_mlp_pair_pack_wide(const float* lora_pair, int r, float scaling, void* fc1_w_aug, int N1, int D, void* stream) {
+  return mlp_pack(lora_pair, r, scaling, fc1_w_aug, N1, D, stream, 2, true);
+}
+extern "C" size_t ucod_lora_mlp_grad_workspace_bytes_wide(int N1, int D) { return mlp_grad_workspace_bytes(N1, D, 1, true); }
+extern "C" size_t ucod_lora_mlp_pair_grad_workspace_bytes_wide(int N1, int D) { return mlp_grad_workspace_bytes(N1, D, 2, true); }
+extern "C" int ucod_lora_mlp_grad_wide(const void* dpre, const void* h2_aug, const float* lora_mlp, int r, float scaling, float* grad_mlp, void* t_bf16,
+                                       void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_grad(dpre, h2_aug, lora_mlp, r, scaling, grad_mlp, t_bf16, workspace, workspace_bytes, rows, N1, D, dropout, stream, 1, true);
+}
+extern "C" int ucod_lora_mlp_pair_grad_wide(const void* dpre, const void* h2_aug, const float* lora_pair, int r, float scaling, float* grad_pair, void* t_bf16,
+                                            void* workspace, size_t workspace_bytes, int rows, int N1, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return mlp_grad(dpre, h2_aug, lora_pair, r, scaling, grad_pair, t_bf16, workspace, workspace_bytes, rows, N1, D, dropout, stream, 2, true);
 }
 extern "C" int ucod_layernorm_bwd_lora_mlp(const void* dy, const void* x, int flags, const float* gamma, const float* dres, const float* next_scale, float* dx,
                                            void* s_bf16, int rows, int D, float eps, const void* t_bf16, int ldt, const float* a_m, int r,
@@ -1441,13 +1475,17 @@ static inline int out_grad_x_blocks(int rows) { return cdiv(rows, OUT_RB) < 256 
 // products are summed over the block through LDS (one barrier per row: two buffers in turn), thread j < 8 stores u[row][j], then the D-wide row of the stream is
 // updated with lambda * alpha/r * B from LDS ([RW][D]: consecutive threads read consecutive 16 bytes).  XH16: the stream is IEEE fp16 (clamped and counted like
 // every writer of that stream).  u_out NULL (the no-grad pass): nothing is saved.
-template <int NVT, int RW, bool XH16>
-__global__ __launch_bounds__(256) void lora_out_fwd_kernel(const bf16_raw* __restrict__ x_in, const float* __restrict__ lora, const float* __restrict__ lam, int r,
+// NT = 512 is the wide form (4096 < K <= UCOD_LORA_WIDE_MAX_K): two vectors per thread of a block twice as wide, two waves per SIMD at up to 256 registers, eight
+// wave partials summed as two groups of four.
+template <int NVT, int RW, bool XH16, int NT = 256>
+__global__ __launch_bounds__(NT) void lora_out_fwd_kernel(const bf16_raw* __restrict__ x_in, const float* __restrict__ lora, const float* __restrict__ lam, int r,
                                                            float scaling, void* __restrict__ xs, float* __restrict__ u_out, int rows, int K, int D, Drop drop,
                                                            unsigned* __restrict__ ovf) {
   extern __shared__ __attribute__((aligned(16))) float out_smem[];
   float* sB = out_smem;                                          // [RW][D]
-  float* red = out_smem + RW * D;                                // [2][4][RW]
+  constexpr int NW = NT / 64;
+  static_assert(NW == 4 || NW == 8, "four or eight waves");
+  float* red = out_smem + RW * D;                                // [2][NW][RW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int NV = K / 8;
   const float* Bo = lora + (size_t)r * K;
@@ -1457,8 +1495,8 @@ __global__ __launch_bounds__(256) void lora_out_fwd_kernel(const bf16_raw* __res
 #pragma unroll
     for (int e = 0; e < 8; ++e)
 #pragma unroll
-      for (int j = 0; j < RW; ++j) a[i][e][j] = (tid + 256 * i < NV && j < r) ? lora[(size_t)j * K + 8 * (tid + 256 * i) + e] : 0.f;
-  for (int idx = tid; idx < RW * D; idx += 256) {
+      for (int j = 0; j < RW; ++j) a[i][e][j] = (tid + NT * i < NV && j < r) ? lora[(size_t)j * K + 8 * (tid + NT * i) + e] : 0.f;
+  for (int idx = tid; idx < RW * D; idx += NT) {
     const int j = idx / D, d = idx - j * D;
     sB[idx] = j < r ? (lam ? lam[d] : 1.f) * scaling * Bo[(size_t)d * r + j] : 0.f;
   }
@@ -1473,7 +1511,7 @@ __global__ __launch_bounds__(256) void lora_out_fwd_kernel(const bf16_raw* __res
     for (int j = 0; j < RW; ++j) s[j] = 0.f;
 #pragma unroll
     for (int i = 0; i < NVT; ++i) {
-      const int v = tid + 256 * i;
+      const int v = tid + NT * i;
       const u32x4 w = v < NV ? xr[v] : (u32x4)(0u);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -1487,18 +1525,23 @@ __global__ __launch_bounds__(256) void lora_out_fwd_kernel(const bf16_raw* __res
         for (int j = 0; j < RW; ++j) s[j] += x0 * a[i][2 * q][j] + x1 * a[i][2 * q + 1][j];
       }
     }
-    float* rb = red + buf * 4 * RW;
+    float* rb = red + buf * NW * RW;
 #pragma unroll
     for (int j = 0; j < RW; ++j) {
       const float ws = wave_sum(s[j]);
       if (lane == 0) rb[wave * RW + j] = ws;
     }
     __syncthreads();
+    auto waves = [&](int j) {
+      const float lo = (rb[j] + rb[RW + j]) + (rb[2 * RW + j] + rb[3 * RW + j]);
+      if constexpr (NW == 8) return lo + ((rb[4 * RW + j] + rb[5 * RW + j]) + (rb[6 * RW + j] + rb[7 * RW + j]));
+      else return lo;
+    };
     float u[RW];
 #pragma unroll
-    for (int j = 0; j < RW; ++j) u[j] = (rb[j] + rb[RW + j]) + (rb[2 * RW + j] + rb[3 * RW + j]);
-    if (u_out && tid < OUT_W) u_out[(size_t)row * OUT_W + tid] = tid < RW ? (rb[tid] + rb[RW + tid]) + (rb[2 * RW + tid] + rb[3 * RW + tid]) : 0.f;
-    for (int c = tid; c < D / 4; c += 256) {
+    for (int j = 0; j < RW; ++j) u[j] = waves(j);
+    if (u_out && tid < OUT_W) u_out[(size_t)row * OUT_W + tid] = tid < RW ? waves(tid) : 0.f;
+    for (int c = tid; c < D / 4; c += NT) {
       f4 acc = (f4)(0.f);
 #pragma unroll
       for (int j = 0; j < RW; ++j) acc += u[j] * *reinterpret_cast<const f4*>(sB + j * D + 4 * c);
@@ -1743,51 +1786,65 @@ __global__ __launch_bounds__(256) void lora_out_reduce_kernel(const float* __res
   if (sum_partials(partial, nblk, n, i, s)) out[i] = s;
 }
 
-static inline bool lora_out_dims_ok(int r, int K, int D) {
-  return r >= 1 && r <= UCOD_LORA_MLP_MAX_R && K >= 128 && K <= 4096 && (K % 128) == 0 && D >= 128 && D <= 1536 && (D % 128) == 0;
+// wide: the _wide entry points and UCOD_LORA_WIDE, whose K may reach UCOD_LORA_WIDE_MAX_K; up to 4096 they run what the narrow ones run
+static inline bool lora_out_dims_ok(int r, int K, int D, bool wide = false) {
+  return r >= 1 && r <= UCOD_LORA_MLP_MAX_R && K >= 128 && K <= (wide ? UCOD_LORA_WIDE_MAX_K : 4096) && (K % 128) == 0 && D >= 128 && D <= 1536 && (D % 128) == 0;
 }
 
 }  // namespace ucod
 
-extern "C" size_t ucod_lora_out_grad_workspace_bytes(int r, int K, int D) {
-  if (!lora_out_dims_ok(r, K, D)) return 0;
+static size_t out_grad_workspace_bytes(int r, int K, int D, bool wide) {
+  if (!lora_out_dims_ok(r, K, D, wide)) return 0;
   const size_t bs = (size_t)512 * (size_t)D * r, bx = (size_t)256 * (size_t)r * K;      // the most blocks either gradient kernel runs
   return (bs > bx ? bs : bx) * sizeof(float);
 }
+extern "C" size_t ucod_lora_out_grad_workspace_bytes(int r, int K, int D) { return out_grad_workspace_bytes(r, K, D, false); }
+extern "C" size_t ucod_lora_out_grad_workspace_bytes_wide(int r, int K, int D) { return out_grad_workspace_bytes(r, K, D, true); }
 
-extern "C" int ucod_lora_out_fwd(const void* x_in, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out,
-                                 int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+static int out_fwd(const void* x_in, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out, int rows, int K,
+                   int D, const ucod_lora_dropout* dropout, void* stream, bool wide) {
   UCOD_BF16_ONLY();
-  if (!x_in || !lora_out || !x_stream || rows <= 0 || !lora_out_dims_ok(r, K, D) || (stream_f16 != 0 && stream_f16 != 1)) return UCOD_EINVAL;
+  if (!x_in || !lora_out || !x_stream || rows <= 0 || !lora_out_dims_ok(r, K, D, wide) || (stream_f16 != 0 && stream_f16 != 1)) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   UCOD_PROF(PROF_LORA_OUT_FWD, stream);
   const Drop drop = make_drop(dropout);
   const int rw = r <= 2 ? 2 : 8, nvt = K / 8 <= 256 ? 1 : 2;
+  const int nt = K > 4096 ? 512 : 256;                            // (the wide form: two vectors per thread of 512)
   const int nblk = rows < 2048 ? rows : 2048;
-  const size_t lds = (size_t)(rw * D + 2 * 4 * rw) * sizeof(float);
+  const size_t lds = (size_t)(rw * D + 2 * (nt / 64) * rw) * sizeof(float);
   unsigned* ovf = stream_f16 ? resid16_overflow_counter() : nullptr;
-#define OF(v, w, h) hipLaunchKernelGGL((lora_out_fwd_kernel<v, w, h>), dim3(nblk), dim3(256), lds, (hipStream_t)stream, (const bf16_raw*)x_in, lora_out, lambda, r, \
-                                       scaling, x_stream, u_out, rows, K, D, drop, ovf)
-#define OFH(v, w)                 \
-  do {                            \
-    if (stream_f16) OF(v, w, true); \
-    else OF(v, w, false);         \
+#define OF(v, w, h, n) hipLaunchKernelGGL((lora_out_fwd_kernel<v, w, h, n>), dim3(nblk), dim3(n), lds, (hipStream_t)stream, (const bf16_raw*)x_in, lora_out, lambda, r, \
+                                          scaling, x_stream, u_out, rows, K, D, drop, ovf)
+#define OFH(v, w, n)                   \
+  do {                                 \
+    if (stream_f16) OF(v, w, true, n); \
+    else OF(v, w, false, n);           \
   } while (0)
-  if (nvt == 1 && rw == 2) OFH(1, 2);
-  else if (nvt == 1) OFH(1, 8);
-  else if (rw == 2) OFH(2, 2);
-  else OFH(2, 8);
+  if (nt == 512 && rw == 2) OFH(2, 2, 512);
+  else if (nt == 512) OFH(2, 8, 512);
+  else if (nvt == 1 && rw == 2) OFH(1, 2, 256);
+  else if (nvt == 1) OFH(1, 8, 256);
+  else if (rw == 2) OFH(2, 2, 256);
+  else OFH(2, 8, 256);
 #undef OFH
 #undef OF
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
+extern "C" int ucod_lora_out_fwd(const void* x_in, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16, float* u_out,
+                                 int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return out_fwd(x_in, lora_out, r, scaling, lambda, x_stream, stream_f16, u_out, rows, K, D, dropout, stream, false);
+}
+extern "C" int ucod_lora_out_fwd_wide(const void* x_in, const float* lora_out, int r, float scaling, const float* lambda, void* x_stream, int stream_f16,
+                                      float* u_out, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
+  return out_fwd(x_in, lora_out, r, scaling, lambda, x_stream, stream_f16, u_out, rows, K, D, dropout, stream, true);
+}
 
-extern "C" int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
-                                    size_t workspace_bytes, int rows, int K, int D, void* stream) {
+static int out_grad_s(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
+                      size_t workspace_bytes, int rows, int K, int D, void* stream, bool wide) {
   UCOD_BF16_ONLY();
   if (!s_bf16 || !u || !lora_out || !grad_out || !t_out || !workspace || rows <= 0) return UCOD_EINVAL;
-  const size_t need = ucod_lora_out_grad_workspace_bytes(r, K, D);
+  const size_t need = out_grad_workspace_bytes(r, K, D, wide);
   if (need == 0) return UCOD_EINVAL;
   if (workspace_bytes < need) return UCOD_ENOMEM;
   UCOD_PROF(PROF_LORA_OUT_GRAD_S, stream);
@@ -1812,15 +1869,24 @@ extern "C" int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const fl
   return UCOD_OK;
 }
 
+extern "C" int ucod_lora_out_grad_s(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out, void* workspace,
+                                    size_t workspace_bytes, int rows, int K, int D, void* stream) {
+  return out_grad_s(s_bf16, u, lora_out, r, scaling, grad_out, t_out, workspace, workspace_bytes, rows, K, D, stream, false);
+}
+extern "C" int ucod_lora_out_grad_s_wide(const void* s_bf16, const float* u, const float* lora_out, int r, float scaling, float* grad_out, float* t_out,
+                                         void* workspace, size_t workspace_bytes, int rows, int K, int D, void* stream) {
+  return out_grad_s(s_bf16, u, lora_out, r, scaling, grad_out, t_out, workspace, workspace_bytes, rows, K, D, stream, true);
+}
+
 // (the SwiGLU form reads and writes rows of 2K values where the other forms have K: it is taken only with UCOD_LORA_OUT_SWIGLU in out_flags, so that a caller of
 //  ucod_lora_out_grad_x, whose buffers are [rows, K], can never reach it -- there act = 2 stays the invalid argument it was)
 extern "C" int ucod_lora_out_grad_x_ex(const void* x_in, int act, int out_flags, void* cot_bf16, const float* t, const float* lora_out, int r, float* grad_out,
                                        void* workspace, size_t workspace_bytes, int rows, int K, int D, const ucod_lora_dropout* dropout, void* stream) {
   UCOD_BF16_ONLY();
-  if (!x_in || !cot_bf16 || !t || !lora_out || !grad_out || !workspace || rows <= 0 || (out_flags & ~UCOD_LORA_OUT_SWIGLU) ||
+  if (!x_in || !cot_bf16 || !t || !lora_out || !grad_out || !workspace || rows <= 0 || (out_flags & ~(UCOD_LORA_OUT_SWIGLU | UCOD_LORA_WIDE)) ||
       (act != UCOD_LORA_OUT_ACT_IDENTITY && act != UCOD_LORA_OUT_ACT_GELU && !(act == UCOD_LORA_OUT_ACT_SWIGLU && (out_flags & UCOD_LORA_OUT_SWIGLU))))
     return UCOD_EINVAL;
-  const size_t need = ucod_lora_out_grad_workspace_bytes(r, K, D);
+  const size_t need = out_grad_workspace_bytes(r, K, D, (out_flags & UCOD_LORA_WIDE) != 0);
   if (need == 0) return UCOD_EINVAL;
   if (dropout && (dropout->p < 0.f || dropout->p >= 1.f)) return UCOD_EINVAL;
   if (workspace_bytes < need) return UCOD_ENOMEM;

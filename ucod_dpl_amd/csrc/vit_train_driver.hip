@@ -66,29 +66,39 @@ inline bool known_mlp(int mlp) { return mlp == UCOD_MLP_GELU || mlp == UCOD_MLP_
 inline int fc1_width(const ucod_vit_desc* d, int mlp) { return mlp == UCOD_MLP_SWIGLU ? 2 * d->F : d->F; }
 // mlpl: the pass carries a LoRA module on the MLP input projection (its rank limit and the widths its gradient kernel covers)
 // pair (UCOD_LORA_MLP_PAIR): the table describes gate_proj / up_proj of the gated MLP -- only with UCOD_MLP_SWIGLU and a table
-inline size_t mlp_gw_bytes(const ucod_vit_train_desc* t, int mlp, bool pair) {
+// wide (UCOD_LORA_WIDE): the pass sizes and runs the MLP and output modules through the _wide row entry points, supersets of the narrow ones
+inline bool is_pair(int out_flags) { return (out_flags & UCOD_LORA_MLP_PAIR) != 0; }
+inline bool is_wide(int out_flags) { return (out_flags & UCOD_LORA_WIDE) != 0; }
+inline size_t mlp_gw_bytes(const ucod_vit_train_desc* t, int mlp, int out_flags) {
   const int N1 = fc1_width(&t->vit, mlp);
-  return pair ? ucod_lora_mlp_pair_grad_workspace_bytes(N1, t->vit.D) : ucod_lora_mlp_grad_workspace_bytes(N1, t->vit.D);
+  if (is_wide(out_flags)) return is_pair(out_flags) ? ucod_lora_mlp_pair_grad_workspace_bytes_wide(N1, t->vit.D) : ucod_lora_mlp_grad_workspace_bytes_wide(N1, t->vit.D);
+  return is_pair(out_flags) ? ucod_lora_mlp_pair_grad_workspace_bytes(N1, t->vit.D) : ucod_lora_mlp_grad_workspace_bytes(N1, t->vit.D);
 }
-inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl, bool pair) {
-  if (pair && !(mlpl && mlp == UCOD_MLP_SWIGLU)) return false;
-  return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && mlp_gw_bytes(t, mlp, pair) != 0);
+inline bool valid_mlpl(const ucod_vit_train_desc* t, int mlp, bool mlpl, int out_flags) {
+  if (is_pair(out_flags) && !(mlpl && mlp == UCOD_MLP_SWIGLU)) return false;
+  return !mlpl || (t->lora_r <= UCOD_LORA_MLP_MAX_R && mlp_gw_bytes(t, mlp, out_flags) != 0);
 }
 // the output modules a table names (layer 0's parameter slots: the same modules in every layer), and whether the pass can carry them
 struct OutMods { bool o, f; };
 inline OutMods out_mods(const void* const* TO) { return OutMods{TO && TO[0] != nullptr, TO && TO[2] != nullptr}; }
-inline size_t out_gw_bytes(const ucod_vit_train_desc* t, OutMods m) {
-  const size_t a = m.o ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) : 0, b = m.f ? ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) : 0;
+inline size_t out_ws(const ucod_vit_train_desc* t, int K, bool wide) {
+  return wide ? ucod_lora_out_grad_workspace_bytes_wide(t->lora_r, K, t->vit.D) : ucod_lora_out_grad_workspace_bytes(t->lora_r, K, t->vit.D);
+}
+inline size_t out_gw_bytes(const ucod_vit_train_desc* t, OutMods m, bool wide) {
+  const size_t a = m.o ? out_ws(t, t->vit.D, wide) : 0, b = m.f ? out_ws(t, t->vit.F, wide) : 0;
   return a > b ? a : b;
 }
-inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TO, int out_flags) {
+inline bool valid_out(const ucod_vit_train_desc* t, int mlp, const void* const* TM, const void* const* TO, int out_flags) {
   const OutMods m = out_mods(TO);
-  if (out_flags & ~(UCOD_LORA_OUT_SWIGLU | UCOD_LORA_MLP_PAIR)) return false;   // an unknown flag bit
+  if (out_flags & ~(UCOD_LORA_OUT_SWIGLU | UCOD_LORA_MLP_PAIR | UCOD_LORA_WIDE)) return false;   // an unknown flag bit
+  const bool wide = is_wide(out_flags);
+  // (the wide bit only where a table needs it: a pass the narrow forms cover has one spelling)
+  if (wide && !(TM && fc1_width(&t->vit, mlp) > 8192) && !(m.f && t->vit.F > 4096)) return false;
   if (!TO) return true;
   if (!m.o && !m.f) return false;                                 // a table that names no module
   // (SwiGLU: the hidden is recomputed from the interleaved, padded [M, 2F] pre-activation -- only with UCOD_LORA_OUT_SWIGLU)
   if (m.f && mlp != UCOD_MLP_GELU && !(out_flags & UCOD_LORA_OUT_SWIGLU)) return false;
-  return (!m.o || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.D, t->vit.D) != 0) && (!m.f || ucod_lora_out_grad_workspace_bytes(t->lora_r, t->vit.F, t->vit.D) != 0);
+  return (!m.o || out_ws(t, t->vit.D, wide) != 0) && (!m.f || out_ws(t, t->vit.F, wide) != 0);
 }
 bool valid(const Pass& c) {
   const ucod_vit_train_desc* t = c.t;
@@ -100,7 +110,7 @@ bool valid(const Pass& c) {
          t->lora_dropout >= 0.f && t->lora_dropout < 1.f &&
          (d->rope == nullptr || t->allow_rope == 1) &&              // DINOv3: only a caller that names the rotary passes (allow_rope) gets them; a zero-filled field refuses a table
          d->n_reg >= 0 && d->n_reg <= 1023 && (d->resid16 == 0 || d->resid16 == 1) &&   // resid16: the saved residual stream is IEEE fp16 (round 4: LayerNorm backward reads it)
-         known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr, (c.out_flags & UCOD_LORA_MLP_PAIR) != 0) && valid_out(t, c.mlp, c.TO, c.out_flags);
+         known_mlp(c.mlp) && valid_mlpl(t, c.mlp, c.TM != nullptr, c.out_flags) && valid_out(t, c.mlp, c.TM, c.TO, c.out_flags);
 }
 
 Plan train_plan(const Pass& c) {
@@ -143,7 +153,7 @@ Plan train_plan(const Pass& c) {
   p.tm = p.mgw = p.mgw_bytes = 0;
   if (mlpl) {
     p.tm = take(M * UCOD_LORA_AUG * 2);
-    p.mgw_bytes = mlp_gw_bytes(t, c.mlp, (c.out_flags & UCOD_LORA_MLP_PAIR) != 0);
+    p.mgw_bytes = mlp_gw_bytes(t, c.mlp, c.out_flags);
     p.mgw = take(p.mgw_bytes);
   }
   p.u_o = p.u_2 = p.s_u = p.t_out = p.ogw = p.ogw_bytes = 0;
@@ -153,7 +163,7 @@ Plan train_plan(const Pass& c) {
     if (m.o) p.u_o = take(p.s_u * (L - 1));
     if (m.f) p.u_2 = take(p.s_u * (L - 1));
     p.t_out = take(M * UCOD_LORA_OUT_W * 4);
-    p.ogw_bytes = out_gw_bytes(t, m);
+    p.ogw_bytes = out_gw_bytes(t, m, is_wide(c.out_flags));
     p.ogw = take(p.ogw_bytes);
   }
   p.bgw = p.bgw_bytes = 0;
@@ -252,7 +262,7 @@ int forward(const Pass& c, bool save, const float* img, float* key_out, void* wo
   if (!valid(c) || !c.T || !c.TT || !img || !key_out || !workspace) return UCOD_EINVAL;
   const ucod_vit_train_desc* t = c.t;
   const ucod_vit_desc* d = &t->vit;
-  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = (c.out_flags & UCOD_LORA_MLP_PAIR) != 0;
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = is_pair(c.out_flags), wide = is_wide(c.out_flags);
   const Plan p = save ? train_plan(c) : infer_plan(c);
   const OutMods om = out_mods(c.TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
@@ -316,8 +326,7 @@ int forward(const Pass& c, bool save, const float* img, float* key_out, void* wo
     else RUN(ucod_gemm_bf16(epi_fc1, h2, fc1_w, g, M, fc1_width(d, c.mlp), fc1_k, (const float*)W[10], nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(ucod_gemm_bf16(epi_resid, g, W[11], x_next, M, D, F, (const float*)W[12], (const float*)W[13], x_mid, nullptr, tok, gv, stream));
     if (om.f)   // LoRA on the MLP output projection: x_next += ls2 * scaling * (drop(g) A_2^T) B_2^T, u saved or dropped
-      RUN(ucod_lora_out_fwd(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x_next, r16, at.u_2(l), M, F, D, dropout_of(t, MOD_FC2, l).ptr(),
-                            stream));
+      RUN((wide ? ucod_lora_out_fwd_wide : ucod_lora_out_fwd)(g, (const float*)Z[2], t->lora_r, t->lora_scaling, (const float*)W[13], x_next, r16, at.u_2(l), M, F, D, dropout_of(t, MOD_FC2, l).ptr(), stream));
   }
   return UCOD_OK;
 }
@@ -331,7 +340,7 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
   const void* const* TT = c.TT;
   const void* const* TM = c.TM;
   const void* const* TO = c.TO;
-  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = (c.out_flags & UCOD_LORA_MLP_PAIR) != 0;
+  const bool swiglu = c.mlp == UCOD_MLP_SWIGLU, pair = is_pair(c.out_flags), wide = is_wide(c.out_flags);
   const Plan p = train_plan(c);
   const OutMods om = out_mods(TO);
   if (workspace_bytes < p.total) return UCOD_ENOMEM;
@@ -473,8 +482,8 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
       // then dA_2 from t and the hidden recomputed as gelu(pre), and dpre += gelu'(pre) * mask/(1-p) * (t A_2) -- completed before anything below reads dpre
       // (SwiGLU, UCOD_LORA_OUT_SWIGLU: the hidden is silu(x1) * x2 of the interleaved pre [M, 2F], and dpre [M, 2F] takes the term through both derivative factors)
       float* gz = (float*)const_cast<void*>(Z[3]);
-      RUN(ucod_lora_out_grad_s(s, at.u_2(l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes, M, F, D, stream));
-      RUN(ucod_lora_out_grad_x_ex(pre, swiglu ? UCOD_LORA_OUT_ACT_SWIGLU : UCOD_LORA_OUT_ACT_GELU, swiglu ? UCOD_LORA_OUT_SWIGLU : 0, dpre,
+      RUN((wide ? ucod_lora_out_grad_s_wide : ucod_lora_out_grad_s)(s, at.u_2(l), (const float*)Z[2], r, t->lora_scaling, gz, (float*)(ws + p.t_out), ws + p.ogw, p.ogw_bytes, M, F, D, stream));
+      RUN(ucod_lora_out_grad_x_ex(pre, swiglu ? UCOD_LORA_OUT_ACT_SWIGLU : UCOD_LORA_OUT_ACT_GELU, (swiglu ? UCOD_LORA_OUT_SWIGLU : 0) | (wide ? UCOD_LORA_WIDE : 0), dpre,
                                   (const float*)(ws + p.t_out), (const float*)Z[2], r, gz, ws + p.ogw, p.ogw_bytes, M, F, D, dropout_of(t, MOD_FC2, l).ptr(), stream));
     }
     // fc1 / weights_in bias: the column sums of the completed dpre (SwiGLU: the engine's padded, interleaved column order; padded columns hold exact zeros)
@@ -488,8 +497,9 @@ int backward(const Pass& c, const float* dkey, void* workspace, size_t workspace
       // (UCOD_LORA_MLP_PAIR: the three calls take their _pair forms -- same arguments, [A_g | A_u | B_m] behind Y[1] / Y[2])
       RUN((pair ? ucod_layernorm_lora_mlp_pair : ucod_layernorm_lora_mlp)(x_mid, r16, (const float*)W[7], (const float*)W[8], (const float*)Y[1], r, h2_aug, M, D,
                                                                           d->eps, drop_m.ptr(), stream));
-      RUN((pair ? ucod_lora_mlp_pair_grad : ucod_lora_mlp_grad)(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M, N1, D,
-                                                                drop_m.ptr(), stream));
+      const auto mlp_grad = wide ? (pair ? ucod_lora_mlp_pair_grad_wide : ucod_lora_mlp_grad_wide) : (pair ? ucod_lora_mlp_pair_grad : ucod_lora_mlp_grad);
+      RUN(mlp_grad(dpre, h2_aug, (const float*)Y[1], r, t->lora_scaling, (float*)const_cast<void*>(Y[2]), ws + p.tm, ws + p.mgw, p.mgw_bytes, M, N1, D,
+                   drop_m.ptr(), stream));
     }
     RUN(ucod_gemm_bf16(epi_dh, dpre, X[3], dh, M, D, N1, nullptr, nullptr, nullptr, nullptr, tok, gv, stream));
     RUN(beta2_grad(l, Y, drop_m));

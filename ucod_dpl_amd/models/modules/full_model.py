@@ -126,8 +126,9 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
     DINOv3 checkpoint) lifts that too: ``weights_out`` on DINOv2 ViT-g/14, ``down_proj`` on a gated DINOv3 checkpoint whose hidden width is at most 4096.
     A DINOv3 checkpoint is taken with the build-only key ``allow_rope`` (default False: without it the engine refuses the rotary table; ``rope_theta``, default
     100, goes with it); its targets are subsets of q_proj / k_proj / v_proj -- and, with the build-only key ``allow_mlp_in`` (default False), ``up_proj`` and the
-    gated MLP's ``gate_proj`` as well, so that with ``allow_out`` / ``allow_swiglu_out`` every Linear of a DINOv3 block is targetable (dinov3_vith16plus is refused
-    by name: its widths are beyond the kernels').  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
+    gated MLP's ``gate_proj`` as well, so that with ``allow_out`` / ``allow_swiglu_out`` every Linear of a DINOv3 block is targetable (dinov3_vith16plus, whose
+    MLP is wider than the register-resident row kernels take, is refused by name unless the build-only key ``allow_wide_mlp``, default False, is set: its MLP modules
+    then run the wide row kernels, UCOD_LORA_WIDE).  ``bias`` (:53,66) is "none" or "lora_only" (the biases of the targeted modules are
     trained too: ``ViTLoRAEngine``); "all" -- every bias of the backbone but the final LayerNorm's, which the key hook never reaches -- is built with the
     build-only key ``allow_bias_all`` (default False) and refused with its reason without it; any other value is a ValueError, both before any device work.  ``eps=None``: 1e-5 for a DINOv3 state dict (DINOv3ViTConfig's default), 1e-6
     otherwise, as ``backbone.from_state_dict``."""
@@ -147,7 +148,8 @@ def load_lora(config, state_dict, heads, device="cuda", generator=None, eps=None
                                       target_modules=targets, allow_rope=bool(getattr(config, "allow_rope", False)),
                                       rope_theta=float(getattr(config, "rope_theta", 100.0)), allow_out=bool(getattr(config, "allow_out", False)),
                                       allow_swiglu_out=bool(getattr(config, "allow_swiglu_out", False)), bias=bias,
-                                      allow_mlp_in=bool(getattr(config, "allow_mlp_in", False)), allow_bias_all=allow_bias_all))
+                                      allow_mlp_in=bool(getattr(config, "allow_mlp_in", False)), allow_bias_all=allow_bias_all,
+                                      allow_wide_mlp=bool(getattr(config, "allow_wide_mlp", False))))
 
 
 class full_model(nn.Module):

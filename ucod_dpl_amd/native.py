@@ -59,6 +59,8 @@ LORA_OUT_ACT_IDENTITY, LORA_OUT_ACT_GELU = 0, 1
 LORA_OUT_ACT_SWIGLU = 2                                     # include/ucod_dpl.h: UCOD_LORA_OUT_ACT_SWIGLU (x_in / cot are the interleaved [rows, 2K] pre-activation / dpre)
 LORA_OUT_SWIGLU = 1                                         # include/ucod_dpl.h: UCOD_LORA_OUT_SWIGLU (out_flags of the _lora_out_ex entry points)
 LORA_MLP_PAIR = 4                                           # include/ucod_dpl.h: UCOD_LORA_MLP_PAIR (the MLP table holds the gated MLP's gate_proj / up_proj pair)
+LORA_WIDE = 16                                              # include/ucod_dpl.h: UCOD_LORA_WIDE (the passes size and run the MLP modules through the _wide row entry points)
+LORA_WIDE_MAX_N1, LORA_WIDE_MAX_K = 10240, 8192             # include/ucod_dpl.h: UCOD_LORA_WIDE_MAX_N1 / _MAX_K (what the wide kernels hold with no scratch memory)
 # the per-layer table of the trained biases' gradient destinations (bias="lora_only": the _lora_bias entry points); NULL = that bias is not trained
 VIT_TRAIN_BIAS_STRIDE = 6
 VIT_TRAIN_BIAS_SLOTS = ("gb_q", "gb_k", "gb_v", "gb_m", "gb_o", "gb_2")
@@ -216,6 +218,16 @@ SIGNATURES = {
     "ucod_lora_out_grad_s": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, vp]),
     "ucod_lora_out_grad_x": (ci, [vp, ci, vp, vp, vp, ci, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
     "ucod_lora_out_grad_x_ex": (ci, [vp, ci, ci, vp, vp, vp, ci, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),      # (+ out_flags behind act: LORA_OUT_SWIGLU for act 2)
+    # the _wide forms of the row entry points without a flags word: supersets, up to LORA_WIDE_MAX_N1 rows of the MLP input weight / LORA_WIDE_MAX_K input columns
+    "ucod_lora_mlp_pack_wide": (ci, [vp, ci, cf, vp, ci, ci, vp]),
+    "ucod_lora_mlp_pair_pack_wide": (ci, [vp, ci, cf, vp, ci, ci, vp]),
+    "ucod_lora_mlp_grad_workspace_bytes_wide": (sz, [ci, ci]),
+    "ucod_lora_mlp_pair_grad_workspace_bytes_wide": (sz, [ci, ci]),
+    "ucod_lora_mlp_grad_wide": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_mlp_pair_grad_wide": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_out_grad_workspace_bytes_wide": (sz, [ci, ci, ci]),
+    "ucod_lora_out_fwd_wide": (ci, [vp, vp, ci, cf, vp, vp, ci, vp, ci, ci, ci, C.POINTER(LoraDropout), vp]),
+    "ucod_lora_out_grad_s_wide": (ci, [vp, vp, vp, ci, cf, vp, vp, vp, sz, ci, ci, ci, vp]),
     "ucod_vit_train_workspace_bytes_lora_out": (sz, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp)]),
     "ucod_vit_forward_train_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, sz, vp]),
     "ucod_vit_backward_lora_out": (ci, [C.POINTER(VitTrainDesc), ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, sz, vp]),

@@ -1042,31 +1042,40 @@ def _check_swiglu_out(allow_out, allow_swiglu_out):
         raise ValueError("allow_swiglu_out=True needs allow_out=True: the SwiGLU MLP's output projection is one of the output projections")
 
 
-def _check_swiglu_out_width(name, hidden):
+# (what the two width refusals below say now that wider kernels exist: their messages stay, with the way in behind them where it leads anywhere)
+_WIDE_OPT_IN = (".  Wider kernels run only with the opt-in allow_wide_mlp=True: the MLP input's gradient kernel with five vectors per thread and one rank per pass "
+                f"(N1 <= {N.LORA_WIDE_MAX_N1}), the output projection's forward in blocks of 512 threads (K <= {N.LORA_WIDE_MAX_K})")
+
+
+def _check_swiglu_out_width(name, hidden, allow_wide_mlp=False):
     """The SwiGLU MLP's output projection is targeted: refuse a hidden width the kernels do not cover, here, before anything touches the device."""
-    if hidden is not None and padded_hidden(hidden) > LORA_OUT_MAX_K:
+    top = N.LORA_WIDE_MAX_K if allow_wide_mlp else LORA_OUT_MAX_K
+    if hidden is not None and padded_hidden(hidden) > top:
         raise NotImplementedError(f"LoRA target module {name!r} is not built for this checkpoint: its input width K = {padded_hidden(hidden)} (the MLP's hidden width "
-                                  f"{hidden}, padded) is beyond the kernels' K <= {LORA_OUT_MAX_K} -- a thread keeps the A values of its hidden units in registers")
+                                  f"{hidden}, padded) is beyond the kernels' K <= {top} -- a thread keeps the A values of its hidden units in registers"
+                                  + ("" if allow_wide_mlp or padded_hidden(hidden) > N.LORA_WIDE_MAX_K else _WIDE_OPT_IN))
 
 
-def _check_mlp_in_width(name, hidden, gated):
+def _check_mlp_in_width(name, hidden, gated, allow_wide_mlp=False):
     """A DINOv3 MLP input module is targeted: refuse, by name and before anything touches the device, a checkpoint whose MLP input weight has more rows than the
-    gradient kernels take (dinov3_vith16plus: hidden 5120, gated, N1 = 2 x 5120 = 10240)."""
+    gradient kernels take (dinov3_vith16plus: hidden 5120, gated, N1 = 2 x 5120 = 10240 -- which ``allow_wide_mlp`` covers)."""
     if hidden is None:
         return
     n1 = 2 * padded_hidden(hidden) if gated else hidden
-    if n1 > LORA_MLP_MAX_N1:
+    top = N.LORA_WIDE_MAX_N1 if allow_wide_mlp else LORA_MLP_MAX_N1
+    if n1 > top:
         raise NotImplementedError(f"LoRA target module {name!r} is not built for this checkpoint: its MLP input weight has N1 = {n1} rows (hidden width {hidden}"
-                                  f"{', gate and up fused' if gated else ''}), beyond the gradient kernels' N1 <= {LORA_MLP_MAX_N1} -- a thread keeps the B values of "
-                                  f"its rows in registers (dinov3_vith16plus is the one such checkpoint)")
+                                  f"{', gate and up fused' if gated else ''}), beyond the gradient kernels' N1 <= {top} -- a thread keeps the B values of "
+                                  f"its rows in registers (dinov3_vith16plus is the one such checkpoint)"
+                                  + ("" if allow_wide_mlp or n1 > N.LORA_WIDE_MAX_N1 else _WIDE_OPT_IN))
 
 
-def resolve_lora_targets(target_modules, names, n_layers, hidden=None):
+def resolve_lora_targets(target_modules, names, n_layers, hidden=None, allow_wide_mlp=False):
     """``target_modules`` of peft's LoraConfig (models/modules/full_model.py:54,67 hands it over unchanged) -> which of the six modules are targeted, as six
     booleans in table order.  Matching is peft's: a module is targeted when its name equals a target or ends in ``.<target>``; the same modules must be hit in
     every layer; a name that hits a module that is not built (``names.refused``), no module at all, or the other family's module is refused with the reason.
     None = query / key / value, the reference's.  ``hidden``: the checkpoint's MLP hidden width, when known: a SwiGLU MLP output projection beyond the kernels'
-    width is refused here, before anything touches the device."""
+    width is refused here, before anything touches the device; ``allow_wide_mlp`` moves those two widths to the wide kernels' (native.LORA_WIDE_MAX_*)."""
     if target_modules is None:
         return (True, True, True, False, False, False)
     if isinstance(target_modules, str):
@@ -1095,10 +1104,10 @@ def resolve_lora_targets(target_modules, names, n_layers, hidden=None):
     if any(pl != per_layer[0] for pl in per_layer):
         raise NotImplementedError(f"target_modules {targets}: the same modules must be targeted in every layer")
     if names.swiglu and names.paths[_MLP_OUT] in per_layer[0]:
-        _check_swiglu_out_width(names.paths[_MLP_OUT].rsplit(".", 1)[-1], hidden)
+        _check_swiglu_out_width(names.paths[_MLP_OUT].rsplit(".", 1)[-1], hidden, allow_wide_mlp)
     for p in names.paths[_MLP_IN:_MLP_IN + 1] + names.paths[_MLP_IN2:]:
         if p in per_layer[0] and p.rsplit(".", 1)[-1] in _MLP_IN3:
-            _check_mlp_in_width(p.rsplit(".", 1)[-1], hidden, names.swiglu)
+            _check_mlp_in_width(p.rsplit(".", 1)[-1], hidden, names.swiglu, allow_wide_mlp)
     return tuple(p in per_layer[0] for p in names.paths)
 
 
@@ -1125,17 +1134,19 @@ def lora_targets(target_modules=None, mlp="gelu", n_layers=1, allow_out=False, a
 
 
 def lora_targets_dinov3(target_modules=None, gated=False, n_layers=1, layer_path="model.layer.", allow_out=False, allow_swiglu_out=False, hidden=None,
-                        allow_mlp_in=False):
+                        allow_mlp_in=False, allow_wide_mlp=False):
     """``resolve_lora_targets`` on a DINOv3 checkpoint's names, ``{layer_path}{i}.attention.{q,k,v,o}_proj`` and ``mlp.{up,down}_proj`` (gated: ``gate_proj`` too):
     any non-empty subset of q_proj / k_proj / v_proj.  Returns the (q, k, v) booleans; without ``allow_mlp_in`` no MLP input module is accepted.
     ``allow_out=True`` also accepts ``o_proj`` and, on a non-gated MLP, ``down_proj`` and returns ((q, k, v), the accepted ones of ("o_proj", "down_proj")); the
     gated MLP's ``down_proj`` stays refused -- unless ``allow_swiglu_out=True`` (needs ``allow_out``) is given as well (dinov3_vith16plus, hidden 5120, is refused).
     ``allow_mlp_in=True`` also accepts ``up_proj`` and, on the gated MLP, ``gate_proj`` (``gate_proj`` on a plain MLP stays refused; with ``hidden`` given,
     dinov3_vith16plus -- N1 = 10240 rows against the kernels' 8192 -- is refused by name) and returns one more element behind the others: the accepted ones of
-    ("gate_proj", "up_proj"), in that order."""
+    ("gate_proj", "up_proj"), in that order.
+    ``allow_wide_mlp=True`` accepts no further name: it moves the two width refusals to the wide kernels' limits (native.LORA_WIDE_MAX_N1 / _MAX_K), so that
+    dinov3_vith16plus's gate_proj / up_proj / down_proj pass."""
     _check_swiglu_out(allow_out, allow_swiglu_out)
     names = _dinov3_names(gated, layer_path, allow_out, allow_swiglu_out, allow_mlp_in)
-    hit = resolve_lora_targets(target_modules, names, n_layers, hidden)
+    hit = resolve_lora_targets(target_modules, names, n_layers, hidden, allow_wide_mlp)
     if not allow_mlp_in:
         return (hit[:3], _out_leaves(names, hit)) if allow_out else hit[:3]
     mlp_in = tuple(names.paths[j].rsplit(".", 1)[-1] for j in (_MLP_IN, _MLP_IN2) if j < len(hit) and hit[j])
@@ -1161,10 +1172,10 @@ def _hf_prefix(sd):
                               "target_modules are matched against")
 
 
-def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False, allow_swiglu_out=False, canon=None, allow_mlp_in=False):
+def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False, allow_swiglu_out=False, canon=None, allow_mlp_in=False, allow_wide_mlp=False):
     """Host only: (layer path, module table) of a ``ViTLoRAEngine`` over ``state_dict`` -- the family's names, ``resolve_lora_targets`` with all its refusals,
     which modules have a bias in the checkpoint (DINOv3 ``k_proj`` has none), ``lora_modules``.  ``canon``: ``normalize_state_dict(state_dict)`` if at hand.
-    ``allow_mlp_in`` (DINOv3 only; a DINOv2 checkpoint's MLP input needs no opt-in): ``lora_targets_dinov3``."""
+    ``allow_mlp_in`` (DINOv3 only; a DINOv2 checkpoint's MLP input needs no opt-in) and ``allow_wide_mlp``: ``lora_targets_dinov3``."""
     c = normalize_state_dict(state_dict) if canon is None else canon
     mlp = "swiglu" if c.get("mlp") == "swiglu" else "gelu"
     F0 = c["layers"][0]["fc1_w"].shape[0] // (2 if mlp == "swiglu" else 1)      # the checkpoint's own hidden width (SwiGLU: before padding)
@@ -1174,7 +1185,7 @@ def lora_layout(state_dict, r, target_modules=None, bias="none", allow_out=False
         family, names = "dinov3", _dinov3_names(mlp == "swiglu", _dinov3_paths(state_dict)[1], allow_out, sw_out, mlp_in3)
     else:
         family, names = "dinov2", _dinov2_names(mlp, allow_out, sw_out)
-    hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out or mlp_in3 else None)
+    hit = resolve_lora_targets(target_modules, names, len(c["layers"]), F0 if sw_out or mlp_in3 else None, allow_wide_mlp)
     if len(hit) > _MLP_IN2 and not (hit[_MLP_IN] or hit[_MLP_IN2]):         # neither of the gated pair: the table of six, as without the opt-in
         hit, names = hit[:_MLP_IN2], names._replace(paths=lora_module_paths(family))
     if bias == "all" and family == "dinov3" and mlp == "swiglu" and len(hit) <= _MLP_IN2:
@@ -1234,7 +1245,8 @@ class ViTLoRAEngine(ViTEngine):
     ``allow_mlp_in`` and one of them targeted the table has seven entries -- gate_proj in the MLP input's place, up_proj behind the six (``_MLP_IN2``) --: each is a
     peft module of its own (own A, own rows of B, own dropout mask, HF's names and shapes outside the arena), both name ONE arena block and the one fused bias
     (``LoRAModule.part`` / ``get_rows`` / ``set_rows``), and the passes run the pair kernels (include/ucod_dpl.h: ucod_lora_mlp_pair_grad, UCOD_LORA_MLP_PAIR).  A
-    hidden width whose fused weight has more than 8192 rows (dinov3_vith16plus: 2 x 5120) is refused by name.
+    hidden width whose fused weight has more than 8192 rows (dinov3_vith16plus: 2 x 5120) is refused by name -- unless ``allow_wide_mlp`` is given: the passes then
+    carry UCOD_LORA_WIDE (only when a targeted module needs it) and size and run the MLP modules through the _wide row entry points, up to native.LORA_WIDE_MAX_N1 rows.
 
     ``target_modules`` (``resolve_lora_targets``, peft's suffix rule) picks among them; None = query / key / value.  Parameters live in ONE flat f32 arena
     ``self.lora`` [L, P], gradients in ``self.lora_grad`` with the same layout -- ready for a single flat all-reduce and the fused AdamW kernel.  A layer's row:
@@ -1251,7 +1263,8 @@ class ViTLoRAEngine(ViTEngine):
 
     The output projections run as row kernels beside their GEMMs (include/ucod_dpl.h: ucod_lora_out_fwd / _grad_s / _grad_x); on the SwiGLU MLP the backward
     recomputes the hidden silu(x1) * x2 from the saved interleaved pre-activation (UCOD_LORA_OUT_ACT_SWIGLU; ``_out_flags`` carries UCOD_LORA_OUT_SWIGLU only when the
-    module is targeted), and a hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers.
+    module is targeted), and a hidden width beyond 4096 (dinov3_vith16plus: 5120) is refused: the kernels keep a thread's A values in registers -- with
+    ``allow_wide_mlp`` the limit is native.LORA_WIDE_MAX_K (the forward runs in blocks of 512 threads).
 
     ``bias="lora_only"`` (peft's ``LoraConfig.bias``, full_model.py:53,66; with exactly one of gate_proj / up_proj targeted it is refused: the two share the fused
     bias) changes nothing else: forward = base(x) + scaling B(A(drop(x))) with the base layer's own
@@ -1272,7 +1285,7 @@ class ViTLoRAEngine(ViTEngine):
 
     def __init__(self, state_dict, heads, r=2, lora_alpha=4, eps=1e-6, device="cuda", gemm_variant=0, generator=None, lora_dropout=0.0,
                  seed=0, resid="auto", allow_swiglu=False, target_modules=None, allow_rope=False, rope_theta=100.0, allow_out=False, allow_swiglu_out=False,
-                 bias="none", allow_mlp_in=False, allow_bias_all=False):
+                 bias="none", allow_mlp_in=False, allow_bias_all=False, allow_wide_mlp=False):
         """``allow_swiglu``: accept a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315).  Its passes run with
         UCOD_MLP_SWIGLU: the training-mode weights_in saves the interleaved pre-activation [M, 2F] and the weights_out dgrad's drain produces its cotangent
         (include/ucod_dpl.h: UCOD_EPI_BIAS_SWIGLU_SAVE_BF16 / UCOD_EPI_SWIGLU_BWD_BF16).  Opt-in: ``load_lora`` (models/modules/full_model.py) switches it on.
@@ -1284,7 +1297,9 @@ class ViTLoRAEngine(ViTEngine):
         ``bias``: peft's ``LoraConfig.bias`` (class docstring): "none", "lora_only" or, with ``allow_bias_all``, "all"; ``load_lora`` passes ``lora_cfg.bias``.
         ``allow_mlp_in``: on a DINOv3 checkpoint, let ``target_modules`` name the MLP input modules -- ``up_proj``, and ``gate_proj`` on the gated MLP (class
         docstring).  On a DINOv2 checkpoint it changes nothing.  Opt-in: ``load_lora`` passes its ``lora_cfg.allow_mlp_in``.
-        ``allow_bias_all``: let ``bias`` be "all" (class docstring); with "none" / "lora_only" it changes nothing.  Opt-in: ``lora_cfg.allow_bias_all``."""
+        ``allow_bias_all``: let ``bias`` be "all" (class docstring); with "none" / "lora_only" it changes nothing.  Opt-in: ``lora_cfg.allow_bias_all``.
+        ``allow_wide_mlp``: let the MLP modules be as wide as the wide kernels take (class docstring: dinov3_vith16plus); where every targeted module fits the
+        narrow kernels it changes nothing.  Opt-in: ``lora_cfg.allow_wide_mlp``."""
         check_lora_bias(bias, allow_bias_all)
         canon = normalize_state_dict(state_dict)
         if allow_swiglu_out and not (allow_out and allow_swiglu and (allow_rope or not canon.get("rope"))):
@@ -1295,7 +1310,9 @@ class ViTLoRAEngine(ViTEngine):
         self.allow_rope, self.allow_out, self.allow_swiglu_out, self.allow_mlp_in = bool(allow_rope), bool(allow_out), bool(allow_swiglu_out), bool(allow_mlp_in)
         self._base_sd = state_dict                                 # (a reference, not a copy, like backbone._src) the f32 base weights every merge starts from
         self._merge_buf = self._mlp_src_rows = None
-        self._adopt(*lora_layout(state_dict, r, target_modules, bias, allow_out, allow_swiglu_out, canon=canon, allow_mlp_in=allow_mlp_in), bias)
+        self.allow_wide_mlp = bool(allow_wide_mlp)
+        self._adopt(*lora_layout(state_dict, r, target_modules, bias, allow_out, allow_swiglu_out, canon=canon, allow_mlp_in=allow_mlp_in,
+                                 allow_wide_mlp=allow_wide_mlp), bias)
         if canon.get("mlp") == "swiglu" and not allow_swiglu:
             raise NotImplementedError("backbone-backward (LoRA) mode takes a checkpoint with the SwiGLU MLP (DINOv2 ViT-g/14, modeling_dinov2.py:300-315) only with "
                                       "allow_swiglu=True (models/modules/full_model.py: load_lora passes it); the frozen-backbone engines (ViTEngine / "
@@ -1325,18 +1342,20 @@ class ViTLoRAEngine(ViTEngine):
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with the MLP input projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its gradient kernel keeps a "
                                  f"lane's B values and accumulators in registers)")
-            if (self.lib.ucod_lora_mlp_pair_grad_workspace_bytes if self.mlp_pair else self.lib.ucod_lora_mlp_grad_workspace_bytes)(self.N1, D) == 0:
-                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= 8192 rows of {mlp_in.leaf}")
+            if self._row_fn("ucod_lora_mlp_pair_grad_workspace_bytes" if self.mlp_pair else "ucod_lora_mlp_grad_workspace_bytes")(self.N1, D) == 0:
+                raise ValueError(f"the MLP input projection's LoRA kernels cover D <= 1536 and {self.N1} <= {N.LORA_WIDE_MAX_N1 if self._wide else 8192} rows of "
+                                 f"{mlp_in.leaf}")
         for m in outs:
             if not m.targeted:
                 continue
             if r > N.LORA_MLP_MAX_R:
                 raise ValueError(f"LoRA rank {r} unsupported with an output projection targeted (1 <= r <= {N.LORA_MLP_MAX_R}: its kernels keep u and t {N.LORA_OUT_W} wide)")
-            if self.lib.ucod_lora_out_grad_workspace_bytes(r, m.k, D) == 0:
+            if self._row_fn("ucod_lora_out_grad_workspace_bytes")(r, m.k, D) == 0:
+                top = N.LORA_WIDE_MAX_K if self._wide else 4096
                 if m is outs[1] and self._out_flags:
                     raise NotImplementedError(f"LoRA on the SwiGLU MLP's output projection is not built for this hidden width: K = {m.k} is beyond the kernels' "
-                                              f"K <= 4096 (a thread keeps the A values of its hidden units in registers); D = {D} must be <= 1536")
-                raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= 4096 (a multiple of 128), got D = {D}, width {m.k}")
+                                              f"K <= {top} (a thread keeps the A values of its hidden units in registers); D = {D} must be <= 1536")
+                raise ValueError(f"the output projections' LoRA kernels cover D <= 1536 and an input width <= {top} (a multiple of 128), got D = {D}, width {m.k}")
         if self.bias_numel:
             self._setup_bias()
         self.lora = torch.zeros(L, self.numel, dtype=torch.float32, device=dev)
@@ -1403,6 +1422,14 @@ class ViTLoRAEngine(ViTEngine):
         # (the flags word of the passes: a bit for the SwiGLU MLP's output projection and one for the gated pair, each set only with its module targeted)
         swiglu = mods[_MLP_IN].interleaved or self.mlp_pair                      # (the MLP input's rows are interleaved: whole, or as the pair's two halves)
         self._out_flags = (N.LORA_OUT_SWIGLU if mods[_MLP_OUT].targeted and swiglu else 0) | (N.LORA_MLP_PAIR if self.mlp_pair else 0)
+        # (... and one for the wide row kernels, set only when ``allow_wide_mlp`` is given AND a targeted MLP module is beyond the narrow ones)
+        self._wide = bool(getattr(self, "allow_wide_mlp", False) and ((self.mlp_in_live and self.N1 > LORA_MLP_MAX_N1)
+                                                                      or (mods[_MLP_OUT].targeted and mods[_MLP_OUT].k > LORA_OUT_MAX_K)))
+        self._out_flags |= N.LORA_WIDE if self._wide else 0
+
+    def _row_fn(self, name):
+        """A row entry point that has a _wide form: that form when the passes carry UCOD_LORA_WIDE, else the narrow one."""
+        return getattr(self.lib, name + "_wide" if self._wide else name)
 
     def _slices(self, j):
         """(A, B) of module ``j`` in one layer's arena row."""
@@ -1602,9 +1629,8 @@ class ViTLoRAEngine(ViTEngine):
             N.check(self.lib.ucod_lora_pack(N.ptr(self.lora[i]), self.r, self.scaling, N.ptr(tl[N.T_QKV_W_AUG]), N.ptr(tl[N.T_QKV_WT_AUG]), self.D, zero_a, N.stream()),
                     "ucod_lora_pack")
         for i, ml in enumerate(self.mlp_layers):               # the MLP module's B columns of fc1_w_aug (its A term is always added by the LayerNorm-2 backward)
-            pack = self.lib.ucod_lora_mlp_pair_pack if self.mlp_pair else self.lib.ucod_lora_mlp_pack     # (the pair: each row's B values in its own module's columns)
-            N.check(pack(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()),
-                    "ucod_lora_mlp_pair_pack" if self.mlp_pair else "ucod_lora_mlp_pack")
+            name = "ucod_lora_mlp_pair_pack" if self.mlp_pair else "ucod_lora_mlp_pack"      # (the pair: each row's B values in its own module's columns)
+            N.check(self._row_fn(name)(self.lora[i, self.qkv_numel:].data_ptr(), self.r, self.scaling, N.ptr(ml[N.M_FC1_W_AUG]), self.N1, self.D, N.stream()), name)
         self._repack_bias()
         self._packed_zero_a = zero_a
 
