@@ -1087,6 +1087,27 @@ int ucod_conv_wgrad_f32(const float* gd, const float* cols, float* gW, int B, in
 int ucod_linear_sigmoid_bwd(const float* x, const float* w, const float* prob, const float* gprob, float* gx, float* gw, float* gb, int B, int K,
                             int accumulate, void* stream);
 int ucod_disc_bce(const float* probs_student, const float* probs_pseudo, float* g_student, float* g_pseudo, float* loss, int B, float inv, void* stream);
+/* The gradient INTO the features (backbone-backward mode with dis_use_features=True: the student's features are trained, so the step's loss reaches them
+ * through the discriminator's featureConv as well).
+ * ucod_conv3x3_f32: a 3x3 / stride 1 / pad 1 convolution without the unfold buffer.  x f32 [B,C,H,W], Wmat f32 [Nout,Kpad] row-major with column
+ *   c*9 + ky*3 + kx (F.unfold order; Kpad % 16 == 0, Kpad >= 9C, 16-byte aligned) -> y f32 [B,Nout,H*W].  The tile, K order and K-tiling of ucod_dba_project
+ *   with the rows of every K-tile gathered straight from x (zero padding by select): the SAME MFMAs on the same values in the same order as ucod_unfold3x3
+ *   (stride 1) followed by ucod_dba_project with a zero bias, so y equals that route's bit for bit.  No atomics, no split-K: deterministic.  A NULL pointer,
+ *   a non-positive size, a bad Kpad or a misaligned Wmat returns UCOD_EINVAL before anything is launched.
+ * ucod_conv3x3_dgrad_weights: W f32 [Cout,Cin,3,3] -> Wd f32 [Cin,Kpad], Kpad = 16 * ceil(9 Cout / 16):  Wd[ci][co*9 + t] = W[co][ci][8 - t], columns
+ *   >= 9 Cout zero (a copy: exact).  The data gradient of the pad-1 convolution y = conv(x; W) is the pad-1 convolution of gy with both spatial axes of the
+ *   kernel flipped and the channel axes exchanged:  gx = ucod_conv3x3_f32(gy, Wd)  -- no [B, 9C, HW] buffer, no fold pass.
+ * ucod_apm_bce_gprob: the step loss's gradient with respect to the two discriminator probabilities (ucod_apm_bce holds them constant).  With D = p_s - p_p,
+ *   u = 0.5 (1 + cos(pi |D|)) + epoch_frac, tb = sigmoid(teacher) > 0.5 (binarised as in ucod_apm_bce):
+ *     gw[b]   = 1/(B HW) sum_p (bg - fg)[b,p] (tb - pl)[b,p]        (d/dt BCEWithLogits(x, t) = -x; the bg term's target is 1 - merged)
+ *     dw/dD   = -0.5 pi sin(pi |D|) sign(D) when 0 <= u <= 1, else 0 (inclusive, as torch's clamp backward; sign(0) = 0 as torch's abs)
+ *     gp_p[b] = -gscale gw[b] dw/dD
+ *     gp_s[b] = +gscale gw[b] dw/dD  [ - gscale (1/B) p_s / max(p_s (1 - p_s), 1e-12)  when finetune == 0: `loss -= dis_loss`, torch's BCELoss backward at target 0 ]
+ *   One workgroup per image, the HW sum in a fixed order: deterministic. */
+int ucod_conv3x3_f32(const float* x, const float* Wmat, float* y, int B, int C, int H, int W, int Nout, int Kpad, void* stream);
+int ucod_conv3x3_dgrad_weights(const float* W, float* Wd, int Cout, int Cin, int Kpad, void* stream);
+int ucod_apm_bce_gprob(const float* pl, const float* teacher, const float* fg, const float* bg, const float* p_s, const float* p_p, float epoch_frac,
+                       float gscale, int finetune, float* gp_s, float* gp_p, int B, int HW, void* stream);
 
 /* ------------------------------------------------------------------ Deterministic forms of the training step
  *

@@ -299,11 +299,6 @@ class TrainLoop(BaseLoop):
         AdamW (same hyper-parameters as the decoder's: the reference ships no loop for this mode) with the EMA update of
         the teacher's copy folded into the same launch."""
         r = self.runner
-        if getattr(r.discriminator, "use_features", False):
-            # In the reference `loss -= dis_loss` with dis_loss = BCE(D(mask, features), 0) (loop_UCOD_DPL.py:160-169, 257-272): with a TRAINED backbone that term
-            # has a gradient path into the features through featureConv, which this loop does not build (it hands the discriminator detached features).
-            raise NotImplementedError("backbone-backward mode with dis_use_features=True is not supported: d(dis_loss)/d(features) through the discriminator's "
-                                      "featureConv is not implemented (use dis_use_features=False, as every shipped config does)")
         self.lora_engine = engine
         self.lora_engine_ema = engine.clone_for_ema()
         r.lora_engine, r.lora_engine_ema = self.lora_engine, self.lora_engine_ema      # the runner checkpoints and validates them (save_checkpoint, launch_val_look_twice)
@@ -366,7 +361,10 @@ class TrainLoop(BaseLoop):
         fg, bg, sdiag = ops.dba_heads(d_s, 0, emb_s, norm_s, hw_s, hb_s, want_bg=True, want_sdiag=True, **det)
         teacher, _, _ = ops.dba_heads(d_t, 0, emb_t, norm_t, hw_t, hb_t, want_bg=False)
         extra, gram = ops.orth_gram(d_s, 0, emb_s, norm_s, sdiag)
-        p_s, p_p = self._disc_probs(ops.binarize(fg, logits=True).view(B, 1, fs, fs), ops.binarize(pl, logits=False), feat_s.detach(), fs)
+        # dis_use_features: the discriminator sees the TRAINED features, so both probabilities carry gradient into them (the records of the two calls feed
+        # Discriminator.input_grad_features below); without the feature branch they depend on binarised masks alone and nothing is kept
+        disc_recs = [] if r.discriminator.use_features else None
+        p_s, p_p = self._disc_probs(ops.binarize(fg, logits=True).view(B, 1, fs, fs), ops.binarize(pl, logits=False), feat_s.detach(), fs, records=disc_recs)
         epoch_frac = self._cur_epoch / (self._max_epoch + self._start_finetune)
         w, merged, gfg, gbg, losses = ops.apm_bce(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world, **det)
         g_emb, g_W, g_b, g_hw, g_hb = A.slices(A.g)
@@ -378,6 +376,17 @@ class TrainLoop(BaseLoop):
         if getattr(self, "_zero_c", None) is None or self._zero_c.numel() != A.C:
             self._zero_c = torch.zeros(A.C, device=dev)
         dfeat = ops.dba_project(gd.view(B, 128, fh, fw), W_s.t().contiguous(), self._zero_c).view(B, A.C, fh, fw)
+        dfeat_disc = None
+        if disc_recs is not None:
+            # the discriminator's share (loop_UCOD_DPL.py:160-171, 257-272 under autograd): `loss -= dis_loss` acts on p_s, and the targets of both BCEWithLogits
+            # terms depend on w(p_s, p_p) -- torch differentiates binary_cross_entropy_with_logits with respect to its target.  ucod_apm_bce_gprob gives
+            # d(loss)/d(p_s, p_p); the two calls share featureConv, whose backward runs once on the sum of their cotangents.
+            gp_s, gp_p = ops.apm_bce_gprob(pl.view(B, -1), teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0 / world, finetune=self.finetune)
+            dfeat_disc = r.discriminator.input_grad_features(disc_recs, [gp_s, gp_p])
+            del disc_recs
+            if native_grid:
+                dfeat_disc = ops.bilinear_resize_adjoint(dfeat_disc, fh, fw)
+            dfeat.add_(dfeat_disc)
         # The decoder's gradient arena is final here: its all-reduce (128C+386 floats) goes out on the RCCL stream now and
         # travels over xGMI UNDER the backbone backward; the LoRA arena (6*r*D*L floats) exists only after that backward.
         reduced_dec = parallel.allreduce_prescaled_async(A.g)
@@ -395,11 +404,14 @@ class TrainLoop(BaseLoop):
         self.global_step += 1
         loss = ops.step_loss(losses, extra, self.finetune)     # losses[0] + losses[1] + extra (- dis loss unless finetune), one launch
         self.last = dict(loss=loss, dis_loss=losses[2], extra=extra[0], w=w, merged=merged, fg=fg, bg=bg, teacher=teacher, p_s=p_s, p_p=p_p)
+        if dfeat_disc is not None:                            # dis_use_features: the student's key map and the discriminator's share of its cotangent (own grid)
+            self.last.update(feat_s=feat_s, dfeat_disc=dfeat_disc)
         return loss
 
-    def _disc_probs(self, student_mask, pseudo_mask, features, fs):
+    def _disc_probs(self, student_mask, pseudo_mask, features, fs, records=None):
         """the two discriminator calls of the APM merge (:259-262): the student's binarised prediction first, then the pseudo label (the order
-        fixes the BatchNorm running statistics).  dis_use_features: both see the features at fs x fs (the reference resizes them first, :153)."""
+        fixes the BatchNorm running statistics).  dis_use_features: both see the features at fs x fs (the reference resizes them first, :153);
+        ``records`` (a list): the two calls' input-gradient records are appended (same launches, same bits)."""
         r = self.runner
         disc = r.discriminator
         B = student_mask.shape[0]
@@ -409,8 +421,11 @@ class TrainLoop(BaseLoop):
             feats = features.to(student_mask.device, torch.float32).contiguous()
             if tuple(feats.shape[-2:]) != (fs, fs):
                 feats = ops.bilinear_resize(feats, fs, fs)
-            p_s, _ = disc.forward_features(student_mask, feats)
-            p_p, _ = disc.forward_features(pseudo_mask, feats)
+            save = "input" if records is not None else False
+            p_s, rec_s = disc.forward_features(student_mask, feats, save=save)
+            p_p, rec_p = disc.forward_features(pseudo_mask, feats, save=save)
+            if records is not None:
+                records += [rec_s, rec_p]
             return p_s, p_p
         disc_t = disc.tensor_table()
         det = dict(deterministic=True, ws=r.det_ws) if self.deterministic else {}

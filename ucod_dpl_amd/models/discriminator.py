@@ -9,7 +9,9 @@ module to eval (loop_UCOD_DPL.py:136).  The nn modules are parameter containers;
 behind the mask branch; no shipped config enables it, configs/uscod/UCOD-DPL_dinov2.py:33) runs through generic kernels: forward
 ``ucod_unfold3x3`` + the exact-f32 MFMA GEMM ``ucod_dba_project`` + ``ucod_bn_lrelu_train_save`` + ``ucod_linear_sigmoid``; backward (the
 discriminator phase) ``ucod_linear_sigmoid_bwd``, and per ConvBlock ``ucod_bn_lrelu_bwd`` + ``ucod_conv_wgrad_f32`` + (``ucod_dba_project`` with
-the transposed weight + ``ucod_fold3x3`` for the input gradient).  Pinned on the real module's step (tests/golden G6b).
+the transposed weight + ``ucod_fold3x3`` for the input gradient).  Pinned on the real module's step (tests/golden G6b).  The gradient with respect to the
+FEATURE map (backbone-backward mode; ``feature.requires_grad`` under autograd): ``forward_features(save="input")`` + ``input_grad_features`` -- the calls on one
+feature map share featureConv's backward, whose data gradient is ``ucod_conv3x3_f32`` on the flipped, channel-exchanged kernel (no unfold-sized buffer).
 """
 import torch
 from torch import nn
@@ -52,15 +54,21 @@ class _DiscFeatFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mask, feature, module, *params):
-        prob, saved = module.forward_features(mask, feature, save=True)
-        ctx.module, ctx.saved = module, saved
+        # parameters trained: everything the weight gradients need; only the feature map asks: the lighter record of ``input_grad_features``
+        save = True if any(ctx.needs_input_grad[3:]) else "input"
+        prob, saved = module.forward_features(mask, feature, save=save)
+        ctx.module, ctx.saved, ctx.param_grads = module, saved, save is True
         return prob.view(-1, 1)
 
     @staticmethod
     def backward(ctx, gprob):
+        gprob = gprob.reshape(-1).float().contiguous()
+        gfeat = ctx.module.input_grad_features([ctx.saved], [gprob]) if ctx.needs_input_grad[1] else None
+        if not ctx.param_grads:
+            return (None, gfeat, None) + (None,) * len(ctx.module._param_list())
         grads = [torch.empty_like(p) for p in ctx.module._param_list()]
-        ctx.module.backward_features(ctx.saved, gprob.reshape(-1), grads, accumulate=False)
-        return (None, None, None) + tuple(grads)
+        ctx.module.backward_features(ctx.saved, gprob, grads, accumulate=False)
+        return (None, gfeat, None) + tuple(grads)
 
 
 @MODULE_REGISTRY.register()
@@ -115,7 +123,8 @@ class Discriminator(nn.Module):
     # ---- dis_use_features=True: the generic kernels (csrc/disc_features.hip) -------------------------------------------------------------
     def _conv_block(self, x, block, stride, save):
         """ConvBlock.forward (:60-70) in training mode: conv3x3(pad 1, no bias) as unfold + exact-f32 GEMM, BatchNorm2d with batch statistics
-        (running buffers updated), LeakyReLU(0.1).  ``save``: keep what the backward needs (the unfold, the conv output, the statistics)."""
+        (running buffers updated), LeakyReLU(0.1).  ``save``: keep what the backward needs (the unfold, the conv output, the statistics); ``"input"``: what the
+        INPUT gradient needs only (no unfold: no weight gradient is formed).  The launches are the same in every mode."""
         lib = N.load()
         conv, bn = block.layers[0], block.layers[1]
         B, Cin, H, W = x.shape
@@ -135,18 +144,22 @@ class Discriminator(nn.Module):
         y = torch.empty_like(y_pre) if save else y_pre
         N.check(lib.ucod_bn_lrelu_train_save(N.ptr(y_pre), N.ptr(y), N.ptr(g), N.ptr(b), N.ptr(bn.running_mean), N.ptr(bn.running_var), B, Cout, Ho * Wo,
                                              BN_EPS, BN_MOMENTUM, LRELU, 1, N.ptr(stats), stats.numel(), N.stream()), "ucod_bn_lrelu_train_save")
-        rec = dict(cols=cols, y_pre=y_pre, stats=stats, wmat=wmat, g=g, b=b, geom=(B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad)) if save else None
+        rec = dict(y_pre=y_pre, stats=stats, wmat=wmat, g=g, b=b, geom=(B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad)) if save else None
+        if save is True:
+            rec["cols"] = cols
         return y.view(B, Cout, Ho, Wo), rec
 
     def forward_features(self, mask, feature, save=False):
-        """-> (prob [B], saved): the feature-branch forward on device tensors; ``saved`` feeds ``backward_features``"""
+        """-> (prob [B], saved): the feature-branch forward on device tensors; ``saved`` feeds ``backward_features`` (``save=True``) or
+        ``input_grad_features`` (``save="input"``: y_pre and the statistics of featureConv and the two stride-2 blocks, no unfold, nothing of maskConv -- the
+        binarised mask carries no gradient).  Probabilities, running buffers and counters are the same bits in every mode."""
         if feature is None:
             raise ValueError("Discriminator(dis_use_features=True).forward needs the feature map")
         if not mask.is_cuda:
             raise RuntimeError("Discriminator runs on the HIP path only: move the module and its inputs to 'cuda'")
         recs = {}
         with torch.no_grad():
-            h, recs["mask"] = self._conv_block(mask.float().contiguous(), self.maskConv, 1, save)
+            h, recs["mask"] = self._conv_block(mask.float().contiguous(), self.maskConv, 1, save is True)
             f, recs["feat"] = self._conv_block(feature.float().contiguous(), self.featureConv, 1, save)
             h = torch.cat((h, f), 1).contiguous()                     # (memory movement only)
             h, recs["c0"] = self._conv_block(h, self.convs[0], 2, save)
@@ -160,15 +173,42 @@ class Discriminator(nn.Module):
         recs.update(x=x, prob=out, lw=lw) if save else None
         return out, (recs if save else None)
 
-    def _conv_block_bwd(self, rec, gout, g_w, g_gamma, g_beta, accumulate, need_input_grad, deterministic=False):
-        """gout [B,Cout,Ho*Wo] = dL/d(block output) -> gradients of the conv weight / BN affine (written or accumulated) and, when asked, dL/d(input).
-        ``deterministic``: the weight gradient through ucod_conv_wgrad_f32_det (ordered sum of per-workgroup partials; workspace cached per shape on the module)."""
+    def _bn_bwd(self, rec, gout, g_gamma, g_beta, accumulate):
+        """gout [B,Cout,Ho*Wo] = dL/d(block output) -> dL/d(conv output); the BatchNorm affine's gradients written or accumulated"""
         lib = N.load()
         B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad = rec["geom"]
         gy = torch.empty_like(rec["y_pre"])
         ws = torch.empty(lib.ucod_bn_lrelu_workspace_bytes(Cout), dtype=torch.uint8, device=gy.device)
         N.check(lib.ucod_bn_lrelu_bwd(N.ptr(rec["y_pre"]), N.ptr(gout), N.ptr(gy), N.ptr(rec["stats"]), N.ptr(rec["g"]), N.ptr(rec["b"]), N.ptr(g_gamma),
                                       N.ptr(g_beta), B, Cout, Ho * Wo, BN_EPS, LRELU, int(accumulate), N.ptr(ws), ws.numel(), N.stream()), "ucod_bn_lrelu_bwd")
+        return gy
+
+    def _conv_dgrad_fold(self, rec, gy):
+        """dL/d(conv output) -> dL/d(input): dL/d(cols) = W^T gy (the same GEMM with the transposed weight; its K = Cout padded to the GEMM's 16), then the
+        unfold's adjoint"""
+        lib = N.load()
+        B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad = rec["geom"]
+        Cp = (Cout + 15) // 16 * 16
+        wt = torch.zeros(Kpad, Cp, dtype=torch.float32, device=gy.device)
+        wt[:, :Cout] = rec["wmat"].t()
+        if Cp != Cout:
+            gyp = torch.zeros(B, Cp, Ho * Wo, dtype=torch.float32, device=gy.device)
+            gyp[:, :Cout] = gy
+        else:
+            gyp = gy
+        gcols = torch.empty(B, Kpad, Ho * Wo, dtype=torch.float32, device=gy.device)
+        zero_b = torch.zeros(Kpad, dtype=torch.float32, device=gy.device)
+        N.check(lib.ucod_dba_project(N.ptr(gyp), N.ptr(wt), N.ptr(zero_b), N.ptr(gcols), B, Cp, Ho * Wo, Kpad, N.stream()), "ucod_dba_project")
+        gx = torch.empty(B, Cin, H, W, dtype=torch.float32, device=gy.device)
+        N.check(lib.ucod_fold3x3(N.ptr(gcols), N.ptr(gx), B, Cin, H, W, stride, Kpad, N.stream()), "ucod_fold3x3")
+        return gx
+
+    def _conv_block_bwd(self, rec, gout, g_w, g_gamma, g_beta, accumulate, need_input_grad, deterministic=False):
+        """gout [B,Cout,Ho*Wo] = dL/d(block output) -> gradients of the conv weight / BN affine (written or accumulated) and, when asked, dL/d(input).
+        ``deterministic``: the weight gradient through ucod_conv_wgrad_f32_det (ordered sum of per-workgroup partials; workspace cached per shape on the module)."""
+        lib = N.load()
+        B, Cin, H, W, Cout, Ho, Wo, stride, K, Kpad = rec["geom"]
+        gy = self._bn_bwd(rec, gout, g_gamma, g_beta, accumulate)
         gwm = torch.empty(Cout, Kpad, dtype=torch.float32, device=gy.device)
         if deterministic:
             if getattr(self, "_det_ws", None) is None:
@@ -184,23 +224,7 @@ class Discriminator(nn.Module):
             g_w.add_(gw_new)                                      # (two discriminator calls per step: the second adds)
         else:
             g_w.copy_(gw_new)
-        if not need_input_grad:
-            return None
-        # dL/d(cols) = W^T gy (the same GEMM with the transposed weight; its K = Cout padded to the GEMM's 16), then the unfold's adjoint
-        Cp = (Cout + 15) // 16 * 16
-        wt = torch.zeros(Kpad, Cp, dtype=torch.float32, device=gy.device)
-        wt[:, :Cout] = rec["wmat"].t()
-        if Cp != Cout:
-            gyp = torch.zeros(B, Cp, Ho * Wo, dtype=torch.float32, device=gy.device)
-            gyp[:, :Cout] = gy
-        else:
-            gyp = gy
-        gcols = torch.empty(B, Kpad, Ho * Wo, dtype=torch.float32, device=gy.device)
-        zero_b = torch.zeros(Kpad, dtype=torch.float32, device=gy.device)
-        N.check(lib.ucod_dba_project(N.ptr(gyp), N.ptr(wt), N.ptr(zero_b), N.ptr(gcols), B, Cp, Ho * Wo, Kpad, N.stream()), "ucod_dba_project")
-        gx = torch.empty(B, Cin, H, W, dtype=torch.float32, device=gy.device)
-        N.check(lib.ucod_fold3x3(N.ptr(gcols), N.ptr(gx), B, Cin, H, W, stride, Kpad, N.stream()), "ucod_fold3x3")
-        return gx
+        return self._conv_dgrad_fold(rec, gy) if need_input_grad else None
 
     def backward_features(self, saved, gprob, grads, accumulate=False, deterministic=False):
         """gradient of sum_b gprob[b] * prob[b] with respect to the 14 parameter tensors, into ``grads`` (tensors shaped like ``_param_list()``,
@@ -223,9 +247,52 @@ class Discriminator(nn.Module):
         self._conv_block_bwd(saved["mask"], g[:, :nm].reshape(B, nm, hw).contiguous(), *gm["mask"], accumulate, False, deterministic)
         self._conv_block_bwd(saved["feat"], g[:, nm:].reshape(B, g.shape[1] - nm, hw).contiguous(), *gm["feat"], accumulate, False, deterministic)
 
+    def _feature_cotangent(self, saved, gprob):
+        """one call's share of dL/d(featureConv's output) [B,dim,fs*fs] for L = sum_b gprob[b] * prob[b]: Linear and the two stride-2 blocks backwards (their
+        parameter gradients go to scratch), then the feature channels of the concatenation"""
+        lib = N.load()
+        x = saved["x"]
+        B, K = x.shape
+        gx = torch.empty_like(x)
+        glw, glb = torch.empty(K, dtype=torch.float32, device=x.device), torch.empty(1, dtype=torch.float32, device=x.device)
+        N.check(lib.ucod_linear_sigmoid_bwd(N.ptr(x), N.ptr(saved["lw"]), N.ptr(saved["prob"]), N.ptr(gprob.reshape(-1).float().contiguous()), N.ptr(gx),
+                                            N.ptr(glw), N.ptr(glb), B, K, 0, N.stream()), "ucod_linear_sigmoid_bwd")
+        g = gx
+        for rec in (saved["c1"], saved["c0"]):
+            Cout = rec["geom"][4]
+            scratch = torch.empty(2, Cout, dtype=torch.float32, device=x.device)
+            gy = self._bn_bwd(rec, g.reshape(B, Cout, -1).contiguous(), scratch[0], scratch[1], False)
+            g = self._conv_dgrad_fold(rec, gy)
+        nm = self.maskConv.layers[0].weight.shape[0]                   # channels of the mask branch in the concatenation
+        return g[:, nm:].reshape(B, g.shape[1] - nm, -1).contiguous()
+
+    def _feature_block_input_grad(self, rec, gout):
+        """dL/d(featureConv's output) -> dL/d(feature): BatchNorm + LeakyReLU backward, then the data gradient as the pad-1 convolution of the cotangent with
+        the flipped, channel-exchanged kernel (ucod_conv3x3_dgrad_weights + ucod_conv3x3_f32: no [B, 9 dim, fs^2] buffer, no fold pass)"""
+        B, Cin, H, W, Cout = rec["geom"][:5]
+        scratch = torch.empty(2, Cout, dtype=torch.float32, device=gout.device)
+        gy = self._bn_bwd(rec, gout, scratch[0], scratch[1], False)
+        wd = ops.conv3x3_dgrad_weights(self.featureConv.layers[0].weight.detach())
+        return ops.conv3x3(gy.view(B, Cout, H, W), wd)
+
+    def input_grad_features(self, saved_list, gprob_list):
+        """-> dfeat [B,dim,fs,fs]: the gradient of sum_calls sum_b gprob[b] * prob[b] with respect to the feature map that ALL the calls saw (records of
+        ``forward_features(..., save="input")`` or ``save=True``).  featureConv is the same function of the same input in every call, so the calls' cotangents
+        of its output are added and its backward runs once.  No parameter gradient is touched."""
+        if not self.use_features:
+            raise ValueError("input_grad_features: the module has no feature branch (dis_use_features=False)")
+        if len(saved_list) != len(gprob_list) or not saved_list:
+            raise ValueError("input_grad_features: one gprob vector per saved record")
+        total = None
+        for saved, gprob in zip(saved_list, gprob_list):
+            g = self._feature_cotangent(saved, gprob)
+            total = g if total is None else total.add_(g)
+        return self._feature_block_input_grad(saved_list[0]["feat"], total)
+
     def _forward_with_features(self, mask, feature):
         params = self._param_list()
-        if any(p.requires_grad for p in params) and torch.is_grad_enabled():
+        wants_grad = any(p.requires_grad for p in params) or (torch.is_tensor(feature) and feature.requires_grad)
+        if wants_grad and torch.is_grad_enabled():
             return _DiscFeatFunction.apply(mask, feature, self, *params)
         return self.forward_features(mask, feature, save=False)[0].view(-1, 1)
 

@@ -299,6 +299,10 @@ SIGNATURES = {
     "ucod_linear_sigmoid_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_disc_bce": (ci, [vp, vp, vp, vp, vp, ci, cf, vp]),
     "ucod_apm_bce": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, ci, ci, vp]),
+    # the gradient into the features of the discriminator's feature branch: implicit 3x3 convolution, its data-gradient weights, d(step loss)/d(p_s, p_p)
+    "ucod_conv3x3_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "ucod_conv3x3_dgrad_weights": (ci, [vp, vp, ci, ci, ci, vp]),
+    "ucod_apm_bce_gprob": (ci, [vp, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, ci, ci, vp]),
     # the deterministic forms of the training step's reductions (no floating-point atomics; explicit workspace behind the default form's arguments)
     "ucod_dba_wgrad_det_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "ucod_dba_wgrad_det": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]),

@@ -615,6 +615,37 @@ def apm_bce(pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0, losses=None, 
     return w, merged, gfg, gbg, losses
 
 
+def apm_bce_gprob(pl, teacher, fg, bg, p_s, p_p, epoch_frac, gscale=1.0, finetune=False):
+    """-> (gp_s [B], gp_p [B]): the step loss's gradient with respect to the two discriminator probabilities (the targets of both BCEWithLogits terms
+    depend on w(p_s, p_p); ``loss -= dis_loss`` on p_s unless ``finetune``) -- what ``apm_bce`` holds constant.  Deterministic."""
+    B = pl.shape[0]
+    HW = pl.numel() // B
+    gp_s = torch.empty(B, dtype=torch.float32, device=pl.device)
+    gp_p = torch.empty(B, dtype=torch.float32, device=pl.device)
+    check(N.load().ucod_apm_bce_gprob(ptr(pl), ptr(teacher), ptr(fg), ptr(bg), ptr(p_s), ptr(p_p), float(epoch_frac), float(gscale), int(bool(finetune)),
+                                      ptr(gp_s), ptr(gp_p), B, HW, stream()), "ucod_apm_bce_gprob")
+    return gp_s, gp_p
+
+
+def conv3x3(x, wmat, nout=None):
+    """3x3 / stride 1 / pad 1 convolution without the unfold buffer: x [B,C,H,W] f32, wmat [Nout,Kpad] (column c*9 + ky*3 + kx, Kpad % 16 == 0,
+    Kpad >= 9C) -> [B,Nout,H,W]; bit-identical to ucod_unfold3x3 + ucod_dba_project with a zero bias"""
+    B, Cin, H, W = x.shape
+    nout = wmat.shape[0] if nout is None else nout
+    y = torch.empty(B, nout, H, W, dtype=torch.float32, device=x.device)
+    check(N.load().ucod_conv3x3_f32(ptr(x), ptr(wmat), ptr(y), B, Cin, H, W, nout, wmat.shape[1], stream()), "ucod_conv3x3_f32")
+    return y
+
+
+def conv3x3_dgrad_weights(weight):
+    """conv weight [Cout,Cin,3,3] -> Wd [Cin, 16 * ceil(9 Cout / 16)] with conv3x3(gy, Wd) = the data gradient of the pad-1 convolution (exact copy)"""
+    Cout, Cin = weight.shape[:2]
+    kpad = (9 * Cout + 15) // 16 * 16
+    wd = torch.empty(Cin, kpad, dtype=torch.float32, device=weight.device)
+    check(N.load().ucod_conv3x3_dgrad_weights(ptr(_f32(weight).contiguous()), ptr(wd), Cout, Cin, kpad, stream()), "ucod_conv3x3_dgrad_weights")
+    return wd
+
+
 def adamw_ema(p, g, m, v, ema, lr, step, ema_alpha=0.0, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01):
     check(N.load().ucod_adamw_ema(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), float(lr), beta1, beta2, eps, weight_decay, int(step),
                                   float(ema_alpha), stream()), "ucod_adamw_ema")
