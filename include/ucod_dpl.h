@@ -1282,6 +1282,61 @@ size_t ucod_gated_ensemble_workspace_bytes(int B, int h, int w);
 int ucod_gated_ensemble(const float* l1_up, const float* l2, const float* fuser0_w, const float* fuser0_b, const float* fuser2_w,
                         float fuser2_b, float* out, float* weight_out, void* workspace, int B, int h, int w, void* stream);
 
+/* ------------------------------------------------------------------ CORAL SparseRefiner, training of the window branch (HRE.CSF)
+ * The backward of ex_loss (models/UDLR.py:52-75) through models/modules/CSF.py:38-43 and the CrossAttentionBlock of models/modules/mlp.py:134-148,
+ * with respect to the 18 HRE.CSF parameters.  The dgrad products are ucod_gemm_bf16_train, the bias gradients ucod_colsum_det, the input cotangent of
+ * norm_mlp ucod_layernorm_bwd_ex; a weight gradient dW [N,K] = dY^T X is ucod_gemm_bf16(UCOD_EPI_BIAS_F32, A = dY^T, B = X^T, K = Mp, bias NULL) on the
+ * two transposes ucod_transpose_pad_bf16 writes.  Every reduction below runs in a fixed order without floating-point atomics: two runs are bit-identical.
+ * The kernels work on bf16 in both builds.  ABI stays 5 (additions only). */
+
+/* ucod_cross_attention96_fwd (mlp.py:122,143) that also returns the base-2 log-sum-exp of the scaled scores, lse f32 [B, heads, Nq].  The same kernel
+ * with the pointer set: out is bit-identical to ucod_cross_attention96_fwd's.  UCOD_EINVAL: a null pointer, a non-positive size, ldq / ldkv not a multiple
+ * of 8, B or heads above 65535, B * heads * Nq >= 2^31. */
+int ucod_cross_attention96_fwd_lse(const void* q_bf16, int ldq, const void* k_bf16, const void* v_bf16, int ldkv, void* out_bf16, float* lse,
+                                   int B, int Nq, int Nk, int heads, void* stream);
+
+/* Its backward (mlp.py:122,143 differentiated: nn.MultiheadAttention's softmax(q k^T 96^-0.5) v per (window, head), dropout 0).  q, k, v, ldq, ldkv as in
+ * the forward (q PRE-SCALED by 96^-0.5 * log2(e)); out, dout bf16 [B*Nq, heads*96]; lse from ucod_cross_attention96_fwd_lse; delta f32 [B, heads, Nq] is
+ * scratch (rowsum(dout * out), written by the first kernel, read by the second).  dq bf16 rows of stride lddq, dk / dv bf16 rows of stride lddkv (they may
+ * point into one [dk | dv] buffer) = the gradients w.r.t. the UNSCALED projections, ucod_attention_bwd's convention: with P = 2^(q' k^T - lse),
+ * dP = dout v^T, dS = P * (dP - delta):  dq = 96^-0.5 dS k,  dk = ln(2) dS^T q',  dv = P^T dout  (P and dS enter their products rounded to bf16).
+ * Columns past heads*96 of a dq / dk / dv row are not written.  Two kernels (queries per wave; keys per wave).
+ * UCOD_EINVAL before any launch: a null pointer, a non-positive size, a leading dimension that is not a multiple of 8 or is below heads*96, a pointer
+ * that is not 16-byte aligned, B or heads above 65535, B * heads * Nq >= 2^31. */
+int ucod_cross_attention96_bwd(const void* q_bf16, int ldq, const void* k_bf16, const void* v_bf16, int ldkv, const void* out_bf16, const void* dout_bf16,
+                               const float* lse, float* delta, void* dq_bf16, int lddq, void* dk_bf16, void* dv_bf16, int lddkv, int B, int Nq, int Nk,
+                               int heads, void* stream);
+
+/* d ex_loss / d window_preds (models/UDLR.py:62-75 differentiated), arguments as ucod_window_loss: g f32 [n,1,H,W] =
+ * upstream[0] / (2 n H W) * (sigmoid(x) - (w t + (1 - w) l)),  w = clamp(1.5 iou[i], 0, 1) from the iou_out ucod_window_loss wrote, l = sigmoid(l_up) > 0.5,
+ * t = h_targets[win_flat[i]] as given (also when the targets are logits: cal_ex_loss hands them to the BCE unchanged).  w, l and t carry no gradient
+ * (binary_iou works on integers).  upstream: DEVICE scalar, the cotangent of the loss; NULL = 1.  UCOD_EINVAL: a null pointer other than upstream,
+ * a non-positive size, n > 65535, H * W >= 2^29. */
+int ucod_window_loss_grad(const float* window_preds, const float* h_targets, const int* win_flat, const float* l_up, const float* iou,
+                          const float* upstream, float* g, int n, int B, int H, int W, int ws, void* stream);
+
+/* Backward of ucod_dwconv7_maskdec (models/modules/CSF.py:13-25,41-42 differentiated) for the cotangent g f32 [n,1,H,W] of its output; x_tokens,
+ * dw_tapmajor, dw_bias, w1 as in the forward.  With S[tap,c] = sum_{i,p} g[i,p] x[i,p+tap,c] (zero padding) and G = sum g:
+ *   d_dw f32 [C,49] (depthwise_conv.weight's own layout) = w1[c] S[tap,c];  d_dw_bias [C] = w1[c] G;  d_w1 [C] = dw_bias[c] G + sum_tap dw[tap,c] S[tap,c];
+ *   d_b1 [1] = G;  dx_tokens f32 [n,H,W,C] = w1[c] sum_tap dw[tap,c] g[i,q-tap].
+ * workspace: slabs * 49 * C floats, slabs = min(n * H, 64); slab s holds the partial S of image rows [s * ceil(n H / slabs), ...), the slabs are added in
+ * ascending order.  UCOD_EINVAL: a null pointer, a non-positive size, n or H above 65535, n * H * W >= 2^29, a workspace that is too small. */
+int ucod_dwconv7_maskdec_bwd(const float* g, const float* x_tokens, const float* dw_tapmajor, const float* dw_bias, const float* w1, float* d_dw,
+                             float* d_dw_bias, float* d_w1, float* d_b1, float* dx_tokens, void* workspace, size_t workspace_bytes, int n, int H, int W,
+                             int C, void* stream);
+
+/* LayerNorm parameter gradients (nn.LayerNorm of mlp.py:136-138,146 differentiated: norm_q, norm_kv, norm_mlp): dgamma[c] = sum_r dy[r,c] xhat[r,c],
+ * dbeta[c] = sum_r dy[r,c], xhat = (x - mean) * rsqrt(var + eps) from row statistics recomputed here.  dy f32 [rows,D], or bf16 with
+ * flags = UCOD_LNB_DY_BF16; x f32 [rows,D].  workspace: slabs * 2 * D floats, slabs = min(128, ceil(rows / 64)); row slabs of ceil(rows / slabs) rows,
+ * added in ascending order.  UCOD_EINVAL: a null pointer, rows < 1, D not a multiple of 64 or above 1024, another flag, a workspace that is too small. */
+int ucod_layernorm_param_grad(const void* dy, int flags, const float* x, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                              int rows, int D, float eps, void* stream);
+
+/* Operand of a weight-gradient product (the nn.Linear layers of mlp.py:122,141-143 differentiated in their weights): src rows [M, ld] of f32
+ * (src_is_bf16 = 0) or bf16 (1), columns 0 .. cols-1 -> dst bf16 [cols, Mp] = src^T rounded to nearest even, Mp = max(128, 64 * ceil(M / 64)), exact
+ * zeros in columns M .. Mp-1.  UCOD_EINVAL: a null pointer, a non-positive size, ld < cols, another src_is_bf16. */
+int ucod_transpose_pad_bf16(const void* src, int src_is_bf16, int M, int cols, int ld, void* dst_bf16, void* stream);
+
 /* ------------------------------------------------------------------ COD measures (row N4: engine/utils/metrics/metric.py::statistics)
  * pred, gt f32 [B,H,W] (any range: the measures min-max normalise the prediction and threshold the normalised ground truth at 0.5,
  * _prepare_data :125-133).  out f64 [B][UCOD_COD_RECORD], per image:

@@ -631,7 +631,7 @@ constexpr int XTILE = KT * XROW;          // 16 KiB per K or V tile
 
 __global__ __launch_bounds__(256, 2) void attn_cross96_kernel(const bf16_raw* __restrict__ qp_, int ldq, const bf16_raw* __restrict__ kp_,
                                                                const bf16_raw* __restrict__ vp_, int ldkv, bf16_raw* __restrict__ out,
-                                                               int Nq, int Nk, int heads) {
+                                                               int Nq, int Nk, int heads, float* __restrict__ lse) {
   __shared__ __attribute__((aligned(16))) char smem[4 * XTILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h5 = lane >> 5, l31 = lane & 31;
@@ -778,6 +778,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross96_kernel(const bf16_raw* __
   }
   const float inv = 1.0f / osum[0];
   const int q = q0 + l31;
+  if (lse && h5 == 0 && q < Nq) lse[((size_t)b * heads + head) * Nq + q] = m_run + __builtin_amdgcn_logf(osum[0]);   // base 2 (training mode)
   if (q < Nq) {
     bf16_raw* op = out + ((size_t)b * Nq + q) * D + head * HDX + 4 * h5;
 #pragma unroll
@@ -826,7 +827,21 @@ extern "C" int ucod_cross_attention96_fwd(const void* q, int ldq, const void* k,
   UCOD_PROF(PROF_ATTN, stream);
   dim3 grid(cdiv(Nq, QT), heads, B), block(256);
   hipLaunchKernelGGL(attn_cross96_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_raw*)q, ldq, (const bf16_raw*)k, (const bf16_raw*)v,
-                     ldkv, (bf16_raw*)out, Nq, Nk, heads);
+                     ldkv, (bf16_raw*)out, Nq, Nk, heads, (float*)nullptr);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+// the same kernel with the statistics pointer set: `out` is what ucod_cross_attention96_fwd writes, bit for bit
+extern "C" int ucod_cross_attention96_fwd_lse(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, float* lse, int B, int Nq,
+                                              int Nk, int heads, void* stream) {
+  using namespace ucod;
+  if (!q || !k || !v || !out || !lse || B <= 0 || Nq <= 0 || Nk <= 0 || heads <= 0 || (ldq % 8) || (ldkv % 8)) return UCOD_EINVAL;
+  if (heads > 65535 || B > 65535 || (long)B * heads * Nq >= (1l << 31)) return UCOD_EINVAL;
+  UCOD_PROF(PROF_ATTN, stream);
+  dim3 grid(cdiv(Nq, QT), heads, B), block(256);
+  hipLaunchKernelGGL(attn_cross96_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_raw*)q, ldq, (const bf16_raw*)k, (const bf16_raw*)v,
+                     ldkv, (bf16_raw*)out, Nq, Nk, heads, lse);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -11,8 +11,14 @@ head_dim-96 cross-attention kernel, fused depthwise-7x7 + mask head, window scat
 ``ex_loss`` is 0 in eval mode exactly as ``cal_ex_loss`` returns (UDLR.py:52-55).  In training mode (``.train()``) the forward is the same
 arithmetic (every dropout of the module is 0, there is no BatchNorm) and ``cal_ex_loss`` adds the IoU-weighted window loss of
 UDLR.py:56-75 from ``h_targets`` (HIP: ``ucod_window_loss``), with ``opt['window_targets']`` as the reference sets it.  The loss VALUE is
-what the reference defines; it ships no second-stage training loop (``LocalRefineTrainLoop: pass``, engine/runner/loop_CORAL.py:38-39), so
-no backward of the refiner exists to mirror and the returned loss carries no autograd graph.
+what the reference defines; it ships no second-stage training loop (``LocalRefineTrainLoop: pass``, engine/runner/loop_CORAL.py:38-39).
+
+The window branch can be trained: in training mode with grad mode on, ``h_targets`` given, at least one window selected and at least one
+``HRE.CSF`` parameter requiring grad, ``ex_loss`` hangs on torch autograd through ``_WindowBranchFunction`` (the idiom of
+models/discriminator.py::_DiscFunction): its inputs are the 18 ``HRE.CSF`` parameters, its forward is the same arithmetic with the activations
+saved, its backward is HIP throughout -- ``ucod_window_loss_grad``, ``ucod_dwconv7_maskdec_bwd``, the dgrad / weight-gradient GEMMs,
+``ucod_layernorm_bwd_ex`` / ``ucod_layernorm_param_grad``, ``ucod_cross_attention96_bwd`` -- and returns d ex_loss / d parameter.  ``outputs``,
+``opt[...]`` and the GE parameters stay outside the graph (the gradient through the window scatter and the gated ensembler is not built).
 """
 import math
 
@@ -68,6 +74,27 @@ class EntropySelector(nn.Module):
         self.window_size = window_size
 
 
+class _WindowBranchFunction(torch.autograd.Function):
+    """ex_loss of the selected windows under torch autograd: tensor inputs = the HRE.CSF parameters, in ``named_parameters`` order.
+    forward: CSF on the windows with its activations saved, then the window loss; -> (ex_loss, window_preds, window_targets, window_ious), only
+    ex_loss differentiable.  backward: one gradient per parameter in its own shape and dtype, None where it does not require grad."""
+
+    @staticmethod
+    def forward(ctx, module, args, *params):
+        saved = {}
+        win = module._csf(*args["csf"], save=saved)
+        loss, sel, ious, aux = module._window_loss(win, *args["loss"])
+        ctx.module, ctx.saved, ctx.aux = module, saved, aux
+        ctx.mark_non_differentiable(win, sel, ious)
+        return loss, win, sel, ious
+
+    @staticmethod
+    def backward(ctx, gloss, *_unused):
+        grads = ctx.module._csf_backward(ctx.saved, ctx.aux, gloss)
+        params = [p for _, p in ctx.module.HRE.CSF.named_parameters()]
+        return (None, None) + tuple(g.view(p.shape).to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.needs_input_grad[2:]))
+
+
 @MODULE_REGISTRY.register()
 class SparseRefiner(nn.Module):
     def __init__(self, config, window_size: int, threshold: float, dim: int = 768):
@@ -86,7 +113,8 @@ class SparseRefiner(nn.Module):
 
     # ------------------------------------------------------------------ weight preparation (bf16 GEMM operands, tap-major dw)
     def _prepare(self, dev):
-        if self._prepared is not None and self._prepared["dev"] == dev:
+        key = (dev, tuple((p.data_ptr(), p._version) for p in self.parameters()))           # an optimizer step changes the weights: prepare again
+        if self._prepared is not None and self._prepared["key"] == key:
             return self._prepared
         blk = self.HRE.CSF.attn
         C = blk.norm_q.weight.shape[0]
@@ -94,7 +122,7 @@ class SparseRefiner(nn.Module):
         f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
         W, b = f32(blk.attn.in_proj_weight), f32(blk.attn.in_proj_bias)
         qscale = torch.full((C,), (hd ** -0.5) * math.log2(math.e), dtype=torch.float32, device=dev)
-        p = dict(dev=dev, C=C,
+        p = dict(dev=dev, key=key, C=C,
                  wq=ops.cast_bf16(W[:C].contiguous()), bq=b[:C].contiguous(), qscale=qscale,
                  wkv=ops.cast_bf16(W[C:].contiguous()), bkv=b[C:].contiguous(),
                  wo=ops.cast_bf16(f32(blk.attn.out_proj.weight)), bo=f32(blk.attn.out_proj.bias),
@@ -111,7 +139,9 @@ class SparseRefiner(nn.Module):
         return p
 
     # ------------------------------------------------------------------ CSF on the selected windows (CSF.py:38-43)
-    def _csf(self, P, l_feats, h_inputs, l_idx, h_idx, H, W):
+    def _csf(self, P, l_feats, h_inputs, l_idx, h_idx, H, W, save=None):
+        """``save`` (a dict): the training-mode pass -- the same kernels with the attention's base-2 log-sum-exp and the fc1 pre-activation written as well,
+        and every activation the backward reads kept in ``save``."""
         lib = N.load()
         dev, C = P["dev"], P["C"]
         Nw, HW = int(h_idx.numel()), H * W
@@ -128,16 +158,80 @@ class SparseRefiner(nn.Module):
         kv = torch.empty(M, 2 * C, dtype=torch.bfloat16, device=dev)
         ops.gemm_bf16(N.EPI_BIAS_BF16, cn, P["wkv"], kv, M, 2 * C, C, bias=P["bkv"])
         att = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
-        N.check(lib.ucod_cross_attention96_fwd(N.ptr(q), C, N.ptr(kv), kv.data_ptr() + C * 2, 2 * C, N.ptr(att), Nw, HW, HW, HEADS, st),
-                "ucod_cross_attention96_fwd")
+        lse = None
+        if save is None:
+            N.check(lib.ucod_cross_attention96_fwd(N.ptr(q), C, N.ptr(kv), kv.data_ptr() + C * 2, 2 * C, N.ptr(att), Nw, HW, HW, HEADS, st),
+                    "ucod_cross_attention96_fwd")
+        else:
+            lse = torch.empty(Nw, HEADS, HW, dtype=torch.float32, device=dev)
+            N.check(lib.ucod_cross_attention96_fwd_lse(N.ptr(q), C, N.ptr(kv), kv.data_ptr() + C * 2, 2 * C, N.ptr(att), N.ptr(lse), Nw, HW, HW, HEADS, st),
+                    "ucod_cross_attention96_fwd_lse")
         x = ops.linear_scale_resid(att, P["wo"], P["bo"], P["ones"], q_tok)        # query + out_proj(attn)
         hn = ops.layernorm(x, *P["nm"], LN_EPS)
-        g = ops.linear_bf16(hn, P["w1"], P["b1"], gelu=True)
-        x = ops.linear_scale_resid(g, P["w2"], P["b2"], P["ones"], x)              # x + mlp(norm_mlp(x)); stays token-major
+        pre = None
+        if save is None:
+            g = ops.linear_bf16(hn, P["w1"], P["b1"], gelu=True)
+        else:
+            g = torch.empty(M, P["w1"].shape[0], dtype=torch.bfloat16, device=dev)
+            pre = torch.empty_like(g)
+            N.check(lib.ucod_gemm_bf16_train(N.EPI_BIAS_GELU_SAVE_BF16, N.ptr(hn), N.ptr(P["w1"]), N.ptr(g), M, g.shape[1], C, N.ptr(P["b1"]), None, N.ptr(pre), 0,
+                                             st), "ucod_gemm_bf16_train")
+        x2 = ops.linear_scale_resid(g, P["w2"], P["b2"], P["ones"], x)             # x + mlp(norm_mlp(x)); stays token-major
         win = torch.empty(Nw, 1, H, W, dtype=torch.float32, device=dev)
-        N.check(lib.ucod_dwconv7_maskdec(N.ptr(x), N.ptr(P["dwT"]), N.ptr(P["dwb"]), N.ptr(P["mw"]), P["mb"], N.ptr(win), Nw, H, W, C, st),
+        N.check(lib.ucod_dwconv7_maskdec(N.ptr(x2), N.ptr(P["dwT"]), N.ptr(P["dwb"]), N.ptr(P["mw"]), P["mb"], N.ptr(win), Nw, H, W, C, st),
                 "ucod_dwconv7_maskdec")
+        if save is not None:
+            save.update(P=P, Nw=Nw, H=H, W=W, q_tok=q_tok, c_tok=c_tok, qn=qn, cn=cn, q=q, kv=kv, att=att, lse=lse, x=x, hn=hn, pre=pre, gact=g, x2=x2, win=win)
         return win
+
+    # ------------------------------------------------------------------ d ex_loss / d HRE.CSF parameters (UDLR.py:52-75 through CSF.py:38-43, mlp.py:134-148)
+    def _csf_backward(self, S, aux, gloss):
+        """The 18 gradients in ``HRE.CSF.named_parameters()`` order, f32, flat or in the GEMM's [N, K] shape.  ``gloss``: the cotangent of ex_loss."""
+        lib, st = N.load(), N.stream()
+        P, Nw, H, W = S["P"], S["Nw"], S["H"], S["W"]
+        dev, C = P["dev"], P["C"]
+        M = Nw * H * W
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        wt = ops.transpose_pad_bf16                                                 # W bf16 [N, K] -> W^T [K, N]: the B operand of a dgrad product
+        up = gloss.detach().to(dev, torch.float32).reshape(1).contiguous()
+        g = f32(Nw, 1, H, W)
+        N.check(lib.ucod_window_loss_grad(N.ptr(S["win"]), N.ptr(aux["h_targets"]), N.ptr(aux["win_flat"]), N.ptr(aux["l_up"]), N.ptr(aux["ious"]), N.ptr(up),
+                                          N.ptr(g), Nw, aux["B"], H, W, self.window_size, st), "ucod_window_loss_grad")
+        # depthwise conv + mask head
+        wsb = f32(min(Nw * H, 64) * 49 * C)
+        d_dw, d_dwb, d_mw, d_mb, dx2 = f32(C, 49), f32(C), f32(C), f32(1), f32(M, C)
+        N.check(lib.ucod_dwconv7_maskdec_bwd(N.ptr(g), N.ptr(S["x2"]), N.ptr(P["dwT"]), N.ptr(P["dwb"]), N.ptr(P["mw"]), N.ptr(d_dw), N.ptr(d_dwb), N.ptr(d_mw),
+                                             N.ptr(d_mb), N.ptr(dx2), N.ptr(wsb), wsb.numel() * 4, Nw, H, W, C, st), "ucod_dwconv7_maskdec_bwd")
+        # x2 = x + fc2(gelu(fc1(norm_mlp(x))))
+        d_b2 = ops.colsum_det(dx2)
+        d_w2 = ops.weight_grad(dx2, S["gact"])
+        dpre = ops.dgrad_bf16(ops.cast_bf16(dx2), wt(P["w2"]), gelu_pre=S["pre"])
+        d_b1 = ops.colsum_det(dpre)
+        d_w1 = ops.weight_grad(dpre, S["hn"])
+        dhn = ops.dgrad_bf16(dpre, wt(P["w1"]))
+        d_nm_g, d_nm_b = ops.layernorm_param_grad(dhn, S["x"], LN_EPS)
+        dx, dxs = f32(M, C), torch.empty(M, C, dtype=torch.bfloat16, device=dev)   # the residual cotangent in front of norm_mlp, and its bf16 GEMM operand
+        N.check(lib.ucod_layernorm_bwd_ex(N.ptr(dhn), N.ptr(S["x"]), N.LNB_DY_BF16, N.ptr(P["nm"][0]), N.ptr(dx2), None, N.ptr(dx), N.ptr(dxs), M, C, LN_EPS, st),
+                "ucod_layernorm_bwd_ex")
+        # x = query + out_proj(attention); the gathered query / context rows are frozen features: no cotangent for them
+        d_bo = ops.colsum_det(dx)
+        d_wo = ops.weight_grad(dx, S["att"])
+        datt = ops.dgrad_bf16(dxs, wt(P["wo"]))
+        HW = H * W
+        delta = f32(Nw, HEADS, HW)
+        dq = torch.empty(M, C, dtype=torch.bfloat16, device=dev)
+        dkv = torch.empty(M, 2 * C, dtype=torch.bfloat16, device=dev)
+        q, kv = S["q"], S["kv"]
+        N.check(lib.ucod_cross_attention96_bwd(N.ptr(q), C, N.ptr(kv), kv.data_ptr() + C * 2, 2 * C, N.ptr(S["att"]), N.ptr(datt), N.ptr(S["lse"]), N.ptr(delta),
+                                               N.ptr(dq), C, N.ptr(dkv), dkv.data_ptr() + C * 2, 2 * C, Nw, HW, HW, HEADS, st), "ucod_cross_attention96_bwd")
+        d_inw, d_inb = f32(3 * C, C), f32(3 * C)
+        ops.weight_grad(dq, S["qn"], out=d_inw[:C])
+        ops.weight_grad(dkv, S["cn"], out=d_inw[C:])
+        ops.colsum_det(dq, out=d_inb[:C])
+        ops.colsum_det(dkv, out=d_inb[C:])
+        d_nq_g, d_nq_b = ops.layernorm_param_grad(ops.dgrad_bf16(dq, wt(P["wq"])), S["q_tok"], LN_EPS)
+        d_nkv_g, d_nkv_b = ops.layernorm_param_grad(ops.dgrad_bf16(dkv, wt(P["wkv"])), S["c_tok"], LN_EPS)
+        return (d_nq_g, d_nq_b, d_nkv_g, d_nkv_b, d_inw, d_inb, d_wo, d_bo, d_w1, d_b1, d_w2, d_b2, d_nm_g, d_nm_b, d_dw, d_dwb, d_mw, d_mb)
 
     def cal_ex_loss(self, opt, win_flat=None):
         """UDLR.py:52-75.  Eval mode / no selected window: 0 (python int, as the reference returns).  Training mode: a 0-d f32 tensor."""
@@ -150,14 +244,21 @@ class SparseRefiner(nn.Module):
             return loss, opt
         if h_targets is None:
             raise ValueError("SparseRefiner in training mode needs h_targets [B*ws*ws, 1, h, w] (models/UDLR.py:62)")
+        loss, sel, ious, _ = self._window_loss(window_preds, preds, h_targets, win_flat)
+        opt["window_targets"] = sel                                        # UDLR.py:71
+        opt["window_ious"] = ious
+        return loss, opt
+
+    def _window_loss(self, window_preds, preds, h_targets, win_flat):
+        """UDLR.py:62-75 on n >= 1 selected windows -> (loss 0-d f32, window_targets, ious, what the loss gradient reads)."""
+        n = int(window_preds.shape[0])
         lib, dev, ws = N.load(), window_preds.device, self.window_size
         h, w = window_preds.shape[-2:]
         B = preds.shape[0]
-        h_targets = h_targets.to(dev, torch.float32).contiguous()
+        h_targets = h_targets.detach().to(dev, torch.float32).contiguous()
         if tuple(h_targets.shape) not in ((B * ws * ws, 1, h, w), (B * ws * ws, h, w)):
             raise ValueError(f"h_targets shape {tuple(h_targets.shape)} != {(B * ws * ws, 1, h, w)}")
         sel = h_targets.view(B * ws * ws, 1, h, w).index_select(0, win_flat.long())
-        opt["window_targets"] = sel                                        # UDLR.py:71
         logits = int(sel.max().item() > 1)                                  # binary_iou's "already a probability?" test (one host sync)
         l_up = ops.bilinear_resize(preds, h * ws, w * ws)
         part = torch.empty(n, dtype=torch.float32, device=dev)
@@ -165,8 +266,7 @@ class SparseRefiner(nn.Module):
         out = torch.empty(1, dtype=torch.float32, device=dev)
         N.check(lib.ucod_window_loss(N.ptr(window_preds), N.ptr(h_targets), N.ptr(win_flat), N.ptr(l_up), logits, N.ptr(part), N.ptr(ious), N.ptr(out),
                                      n, B, h, w, ws, N.stream()), "ucod_window_loss")
-        opt["window_ious"] = ious
-        return out[0], opt
+        return out[0], sel, ious, dict(h_targets=h_targets, win_flat=win_flat, l_up=l_up, ious=ious, B=B)
 
     def forward(self, input_features, h_inputs, preds, h_targets=None):
         if not input_features.is_cuda:
@@ -194,10 +294,19 @@ class SparseRefiner(nn.Module):
         coords_list = torch.from_numpy(coords_np).to(dev)
         Nw = len(sel)
         hH, hW = h_inputs.shape[-2:]
+        csf_params = [p for _, p in self.HRE.CSF.named_parameters()]
+        # the window branch under autograd: only where a loss exists and somebody asks for its gradient; everything else is the plain forward
+        graph = (self.training and torch.is_grad_enabled() and Nw > 0 and h_targets is not None and any(p.requires_grad for p in csf_params))
+        trained = None
         if Nw > 0:
             l_idx = torch.from_numpy(sel[:, 0].astype(np.int32)).to(dev)
             h_idx = torch.from_numpy((sel[:, 0] * ws * ws + sel[:, 1]).astype(np.int32)).to(dev)
-            window_preds = self._csf(P, input_features, h_inputs, l_idx, h_idx, hH, hW)
+            if graph:
+                trained = _WindowBranchFunction.apply(self, dict(csf=(P, input_features.detach(), h_inputs.detach(), l_idx, h_idx, hH, hW),
+                                                                 loss=(preds.detach(), h_targets, h_idx)), *csf_params)
+                window_preds = trained[1]
+            else:
+                window_preds = self._csf(P, input_features, h_inputs, l_idx, h_idx, hH, hW)
             cd = coords_list.to(torch.int32).contiguous()
         else:
             l_idx = torch.zeros(0, dtype=torch.int32, device=dev)
@@ -217,5 +326,8 @@ class SparseRefiner(nn.Module):
                                         N.ptr(ge_w), N.ptr(wsb), B, h2, w2, st), "ucod_gated_ensemble")
         opt = {"mask": mask, "entropy": entropy, "h_preds": h_preds, "window_preds": window_preds, "GE_w": ge_w, "preds": preds,
                "coords_list": coords_list, "h_targets": h_targets}
-        ex_loss, opt = self.cal_ex_loss(opt, h_idx)
+        if trained is not None:
+            ex_loss, opt["window_targets"], opt["window_ious"] = trained[0], trained[2], trained[3]
+        else:
+            ex_loss, opt = self.cal_ex_loss(opt, h_idx)
         return outputs, ex_loss, opt

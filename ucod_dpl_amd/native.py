@@ -93,6 +93,7 @@ class DiscGrads(C.Structure):
 
 
 ROPE_ELEM_HALF, ROPE_ELEM_F32 = 0, 1          # element type of ucod_rope_qk's buffer: the library's 16-bit operand type / f32
+LNB_DY_BF16 = 1                              # include/ucod_dpl.h: UCOD_LNB_DY_BF16 (flag of ucod_layernorm_bwd_ex / ucod_layernorm_param_grad: dy is bf16)
 UCOD_MLP_GELU, UCOD_MLP_SWIGLU = 0, 1        # MLP kind of the _mlp backbone entry points (include/ucod_dpl.h)
 # activation operand classes of the fp16-term split pass (ucod_split16_class_scale)
 SPLIT16_LN, SPLIT16_QKV, SPLIT16_PROB, SPLIT16_ATT, SPLIT16_HIDDEN, SPLIT16_PATCH = range(6)
@@ -339,6 +340,14 @@ SIGNATURES = {
     "ucod_dwconv7_maskdec": (ci, [vp, vp, vp, vp, cf, vp, ci, ci, ci, ci, vp]),
     "ucod_window_scatter": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     "ucod_window_loss": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    # training of the refiner's window branch (HRE.CSF): the forward with the base-2 log-sum-exp, the head_dim-96 attention backward, the loss gradient, the
+    # depthwise-conv + mask-head backward, LayerNorm parameter gradients (flags = LNB_DY_BF16 or 0), the transposed bf16 operand of a weight-gradient GEMM
+    "ucod_cross_attention96_fwd_lse": (ci, [vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp]),
+    "ucod_cross_attention96_bwd": (ci, [vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ucod_window_loss_grad": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "ucod_dwconv7_maskdec_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, vp]),
+    "ucod_layernorm_param_grad": (ci, [vp, ci, vp, vp, vp, vp, sz, ci, ci, cf, vp]),
+    "ucod_transpose_pad_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
     "ucod_gated_ensemble_workspace_bytes": (sz, [ci, ci, ci]),
     "ucod_gated_ensemble": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_step_loss": (ci, [vp, vp, ci, vp, vp]),

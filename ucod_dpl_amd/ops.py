@@ -692,3 +692,60 @@ def cod_metrics(pred, gt):
     out = torch.empty(B, N.COD_RECORD, dtype=torch.float64, device=pred.device)
     check(lib.ucod_cod_metrics(ptr(pred), ptr(gt), B, H, W, ptr(out), ptr(ws), nbytes, stream()), "ucod_cod_metrics")
     return out
+
+
+# ----------------------------------------------------------------------------- refiner training (the window branch of models/UDLR.py)
+def pad_rows64(M):
+    """Mp of ucod_transpose_pad_bf16: the K of a weight-gradient GEMM over M token rows."""
+    return max(128, 64 * ((M + 63) // 64))
+
+
+def transpose_pad_bf16(src, cols=None):
+    """src [M, ld] f32 or bf16 -> bf16 [cols, Mp] = src[:, :cols]^T (round to nearest even), zeros in the pad columns M .. Mp-1."""
+    M, ld = src.shape
+    cols = ld if cols is None else cols
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"expected float32 or bfloat16, got {src.dtype}")
+    out = torch.empty(cols, pad_rows64(M), dtype=torch.bfloat16, device=src.device)
+    check(N.load().ucod_transpose_pad_bf16(ptr(src), int(src.dtype == torch.bfloat16), M, cols, ld, ptr(out), stream()), "ucod_transpose_pad_bf16")
+    return out
+
+
+def weight_grad(dy, x, out=None):
+    """dW f32 [N, K] = dy^T x for dy [M, N], x [M, K] (f32 or bf16 rows; 16-bit operands, f32 accumulation): two transposes and the project's GEMM."""
+    a, b = transpose_pad_bf16(dy), transpose_pad_bf16(x)
+    out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=dy.device) if out is None else out
+    return gemm_bf16(N.EPI_BIAS_F32, a, b, out, a.shape[0], b.shape[0], a.shape[1])
+
+
+def dgrad_bf16(dy, wt, gelu_pre=None):
+    """dx bf16 [M, K] = dy [M, N] wt[K, N]^T (wt = the transposed weight), times gelu'(gelu_pre) when the saved fc1 pre-activation is given."""
+    M, Nn = dy.shape
+    out = torch.empty(M, wt.shape[0], dtype=torch.bfloat16, device=dy.device)
+    epi = N.EPI_BIAS_BF16 if gelu_pre is None else N.EPI_GELU_BWD_BF16
+    check(N.load().ucod_gemm_bf16_train(epi, ptr(_bf16(dy)), ptr(_bf16(wt)), ptr(out), M, wt.shape[0], Nn, None, ptr(gelu_pre), None, 0, stream()),
+          "ucod_gemm_bf16_train")
+    return out
+
+
+def colsum_det(x, out=None):
+    """out f32 [N] = column sums of x [M, N] (f32 or bf16), fixed summation order."""
+    lib = N.load()
+    M, Nn = x.shape
+    out = torch.empty(Nn, dtype=torch.float32, device=x.device) if out is None else out
+    nbytes = lib.ucod_colsum_det_workspace_bytes(M, Nn)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    elem = N.ROPE_ELEM_F32 if x.dtype == torch.float32 else N.ROPE_ELEM_HALF
+    check(lib.ucod_colsum_det(ptr(x), elem, M, Nn, Nn, None, ptr(out), ptr(ws), nbytes, stream()), "ucod_colsum_det")
+    return out
+
+
+def layernorm_param_grad(dy, x, eps):
+    """(dgamma, dbeta) f32 [D] of a LayerNorm over rows: dy [rows, D] f32 or bf16, x f32 [rows, D]."""
+    rows, D = x.shape
+    slabs = min(128, (rows + 63) // 64)
+    ws = torch.empty(slabs * 2 * D, dtype=torch.float32, device=x.device)
+    dg, db = torch.empty(D, dtype=torch.float32, device=x.device), torch.empty(D, dtype=torch.float32, device=x.device)
+    check(N.load().ucod_layernorm_param_grad(ptr(dy), N.LNB_DY_BF16 if dy.dtype == torch.bfloat16 else 0, ptr(_f32(x)), ptr(dg), ptr(db), ptr(ws),
+                                             ws.numel() * 4, rows, D, float(eps), stream()), "ucod_layernorm_param_grad")
+    return dg, db
