@@ -1337,6 +1337,29 @@ int ucod_layernorm_param_grad(const void* dy, int flags, const float* x, float* 
  * zeros in columns M .. Mp-1.  UCOD_EINVAL: a null pointer, a non-positive size, ld < cols, another src_is_bf16. */
 int ucod_transpose_pad_bf16(const void* src, int src_is_bf16, int M, int cols, int ld, void* dst_bf16, void* stream);
 
+/* ------------------------------------------------------------------ CORAL SparseRefiner, the gradient through `outputs` (SparseRefiner(train_outputs=True))
+ * Backward of ucod_gated_ensemble (models/modules/GE_pix_level.py:16-25 differentiated) in l2 and in the fuser's four parameters, for the cotangent g_out
+ * f32 [B,1,h,w] of `out`.  l1_up, l2 as in the forward; ge_w = the weight_out the forward wrote (a function of the first-stage logits alone: no gradient is
+ * formed for it or for l1_up).  Per pixel i, with w = ge_w[i], y = l1_up[i] w + l2[i] (1 - w) (recomputed), z_k = a_k y + c_k, m_k = [z_k > 0] (torch's
+ * ReLU subgradient: 0 at z_k == 0), a = fuser0_w, c = fuser0_b, d = fuser2_w, G = g_out[i]:
+ *   dl2 f32 [B,1,h,w]: dl2[i] = G (1 - w) sum_k d_k a_k m_k;   d_fuser2_b [1] = sum_i G;   d_fuser2_w [64]: sum_i G max(z_k, 0);
+ *   d_fuser0_w [64]: sum_i G d_k m_k y;   d_fuser0_b [64]: sum_i G d_k m_k.
+ * The 193 sums: one partial per workgroup (a tile of 256 pixels of one image, walked in pixel order) in `workspace`
+ * (ucod_gated_ensemble_bwd_workspace_bytes(B, h, w) = B * ceil(h w / 256) * 193 floats), then added in ascending order in f64: no floating-point atomics,
+ * two runs are bit-identical.  UCOD_EINVAL before any launch: a null pointer, a non-positive size, B > 65535, B * h * w >= 2^29, a workspace that is too
+ * small.  ABI stays 5 (additions only). */
+size_t ucod_gated_ensemble_bwd_workspace_bytes(int B, int h, int w);
+int ucod_gated_ensemble_bwd(const float* l1_up, const float* l2, const float* ge_w, const float* fuser0_w, const float* fuser0_b, const float* fuser2_w,
+                            const float* g_out, float* dl2, float* d_fuser0_w, float* d_fuser0_b, float* d_fuser2_w, float* d_fuser2_b, void* workspace,
+                            size_t workspace_bytes, int B, int h, int w, void* stream);
+
+/* The adjoint of ucod_window_scatter (models/modules/HRE.py:18-39 differentiated in the windows): a gather.  dl2 f32 [B,1,ws*H,ws*W]; coords, win_img, n,
+ * B, H, W, ws as in the forward;  g f32 [n,1,H,W]:  g[i,py,px] (+)= dl2[win_img[i], coords[i].y*H + py, coords[i].x*W + px] / (1 + 1e-6)  -- the selected
+ * windows are distinct cells, so the count the forward divides by is 1.  accumulate = 1 adds into the g ucod_window_loss_grad wrote (one g for one CSF
+ * backward), 0 writes g alone.  n == 0: nothing to do, UCOD_OK.  A window whose coords or image index lie outside [0, ws) / [0, B) is left untouched.
+ * UCOD_EINVAL: a null pointer with n > 0, a non-positive size, n < 0 or n > 65535, B * ws * H * ws * W >= 2^29, accumulate other than 0 / 1. */
+int ucod_window_gather(const float* dl2, const int* coords, const int* win_img, float* g, int accumulate, int n, int B, int H, int W, int ws, void* stream);
+
 /* ------------------------------------------------------------------ COD measures (row N4: engine/utils/metrics/metric.py::statistics)
  * pred, gt f32 [B,H,W] (any range: the measures min-max normalise the prediction and threshold the normalised ground truth at 0.5,
  * _prepare_data :125-133).  out f64 [B][UCOD_COD_RECORD], per image:

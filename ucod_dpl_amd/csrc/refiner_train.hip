@@ -196,6 +196,83 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const void* __restri
   }
 }
 
+// ------------------------------------------------------------------ gated ensembler, backward (GE_pix_level.py:16-25 differentiated in l2 and the fuser)
+// Per pixel: w = GE_w (the forward's saved weight, a function of preds alone), y = l1 w + l2 (1 - w), z_k = a_k y + c_k, m_k = [z_k > 0] (torch's ReLU
+// subgradient).  A workgroup owns a tile of 256 pixels: thread = pixel for dl2 and for staging (G, y) in LDS, then thread t < 192 owns the sum `t >> 6`
+// (0: d d_k, 1: d a_k, 2: d c_k -- wave-uniform) of channel k = t & 63 and walks the tile in pixel order with broadcast LDS reads; thread 192 sums G.
+// part[block][193] = [d d | d a | d c | d bias]: no cross-lane reduction, no atomics, one fixed order.
+constexpr int GEB_TILE = 256;
+constexpr int GEB_SUMS = 193;
+
+__global__ __launch_bounds__(256) void ge_bwd_partial_kernel(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ gew,
+                                                             const float* __restrict__ f0w, const float* __restrict__ f0b, const float* __restrict__ f2w,
+                                                             const float* __restrict__ G, float* __restrict__ dl2, float* __restrict__ part, int hw) {
+  __shared__ float a[64], c[64], d[64], sg[GEB_TILE], sy[GEB_TILE];
+  const int t = threadIdx.x;
+  if (t < 64) { a[t] = f0w[t]; c[t] = f0b[t]; d[t] = f2w[t]; }
+  __syncthreads();
+  const int b = blockIdx.y, p = blockIdx.x * GEB_TILE + t;
+  float gv = 0.f, y = 0.f;                                          // past the image: G = 0 adds exact zeros to every sum
+  if (p < hw) {
+    const size_t i = (size_t)b * hw + p;
+    const float wt = gew[i];
+    gv = G[i];
+    y = l1[i] * wt + l2[i] * (1.f - wt);
+    float s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < 64; ++k) s += fmaf(a[k], y, c[k]) > 0.f ? d[k] * a[k] : 0.f;
+    dl2[i] = gv * (1.f - wt) * s;
+  }
+  sg[t] = gv;
+  sy[t] = y;
+  __syncthreads();
+  if (t > 192) return;
+  const int k = t & 63, which = t >> 6;
+  const float ak = a[k], ck = c[k], dk = d[k];
+  float acc = 0.f;
+  if (which == 0) {
+    for (int j = 0; j < GEB_TILE; ++j) acc = fmaf(sg[j], fmaxf(fmaf(ak, sy[j], ck), 0.f), acc);
+  } else if (which == 1) {
+    for (int j = 0; j < GEB_TILE; ++j) acc += fmaf(ak, sy[j], ck) > 0.f ? sg[j] * dk * sy[j] : 0.f;
+  } else if (which == 2) {
+    for (int j = 0; j < GEB_TILE; ++j) acc += fmaf(ak, sy[j], ck) > 0.f ? sg[j] * dk : 0.f;
+  } else {
+    for (int j = 0; j < GEB_TILE; ++j) acc += sg[j];
+  }
+  part[((size_t)b * gridDim.x + blockIdx.x) * GEB_SUMS + t] = acc;
+}
+
+// the workgroups' partials in ascending order, in f64 (window_loss_finish_kernel's way): thread = one of the 193 sums
+__global__ __launch_bounds__(256) void ge_bwd_finish_kernel(const float* __restrict__ part, int blocks, float* __restrict__ d_f0w, float* __restrict__ d_f0b,
+                                                            float* __restrict__ d_f2w, float* __restrict__ d_f2b) {
+  const int t = threadIdx.x;
+  if (t >= GEB_SUMS) return;
+  double acc = 0.0;
+  for (int s = 0; s < blocks; ++s) acc += (double)part[(size_t)s * GEB_SUMS + t];
+  const float v = (float)acc;
+  if (t < 64) d_f2w[t] = v;
+  else if (t < 128) d_f0w[t - 64] = v;
+  else if (t < 192) d_f0b[t - 128] = v;
+  else d_f2b[0] = v;
+}
+
+// ------------------------------------------------------------------ adjoint of the window scatter-average (HRE.py:18-39): a gather
+// dwin[i,p] = dl2[win_img[i], cy H + py, cx W + px] / (1 + 1e-6) -- the windows are distinct cells, so the count the forward divides by is 1.
+// ACC: added to the g ucod_window_loss_grad wrote (one g for one CSF backward).  A window whose cell lies outside the image is left alone.
+template <bool ACC>
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ dl2, const int* __restrict__ coords, const int* __restrict__ win_img,
+                                                            float* __restrict__ g, int B, int H, int W, int ws) {
+  const int i = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= H * W) return;
+  const int cy = coords[2 * i], cx = coords[2 * i + 1], b = win_img[i];
+  if (cy < 0 || cy >= ws || cx < 0 || cx >= ws || b < 0 || b >= B) return;
+  const int y = p / W, x = p - y * W;
+  const float v = dl2[((size_t)b * ws * H + (size_t)cy * H + y) * (ws * W) + (size_t)cx * W + x] / (1.0f + 1e-6f);
+  const size_t o = (size_t)i * H * W + p;
+  g[o] = ACC ? g[o] + v : v;
+}
+
 }  // namespace
 }  // namespace ucod
 
@@ -256,6 +333,42 @@ extern "C" int ucod_transpose_pad_bf16(const void* src, int src_is_bf16, int M, 
     hipLaunchKernelGGL(transpose_pad_kernel<true>, dim3(Mp / 64, cdiv(cols, 64)), dim3(256), 0, s, src, (bf16_raw*)dst_bf16, M, cols, ld, Mp);
   else
     hipLaunchKernelGGL(transpose_pad_kernel<false>, dim3(Mp / 64, cdiv(cols, 64)), dim3(256), 0, s, src, (bf16_raw*)dst_bf16, M, cols, ld, Mp);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" size_t ucod_gated_ensemble_bwd_workspace_bytes(int B, int h, int w) {
+  if (B <= 0 || h <= 0 || w <= 0) return 0;
+  return (size_t)B * cdiv((long)h * w, GEB_TILE) * GEB_SUMS * sizeof(float);
+}
+
+extern "C" int ucod_gated_ensemble_bwd(const float* l1_up, const float* l2, const float* ge_w, const float* f0w, const float* f0b, const float* f2w,
+                                       const float* g_out, float* dl2, float* d_f0w, float* d_f0b, float* d_f2w, float* d_f2b, void* workspace,
+                                       size_t workspace_bytes, int B, int h, int w, void* stream) {
+  if (!l1_up || !l2 || !ge_w || !f0w || !f0b || !f2w || !g_out || !dl2 || !d_f0w || !d_f0b || !d_f2w || !d_f2b || !workspace) return UCOD_EINVAL;
+  if (B <= 0 || h <= 0 || w <= 0 || B > 65535) return UCOD_EINVAL;
+  if ((long)B * h * w >= (1l << 31) / 4) return UCOD_EINVAL;
+  if (workspace_bytes < ucod_gated_ensemble_bwd_workspace_bytes(B, h, w)) return UCOD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles = cdiv((long)h * w, GEB_TILE);
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL(ge_bwd_partial_kernel, dim3(tiles, B), dim3(256), 0, s, l1_up, l2, ge_w, f0w, f0b, f2w, g_out, dl2, part, h * w);
+  hipLaunchKernelGGL(ge_bwd_finish_kernel, dim3(1), dim3(256), 0, s, part, tiles * B, d_f0w, d_f0b, d_f2w, d_f2b);
+  UCOD_CHECK_LAUNCH();
+  return UCOD_OK;
+}
+
+extern "C" int ucod_window_gather(const float* dl2, const int* coords, const int* win_img, float* g, int accumulate, int n, int B, int H, int W, int ws,
+                                  void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || ws <= 0 || n < 0 || n > 65535 || (accumulate != 0 && accumulate != 1)) return UCOD_EINVAL;
+  if ((long)B * ws * H * ws * W >= (1l << 31) / 4) return UCOD_EINVAL;
+  if (n == 0) return UCOD_OK;
+  if (!dl2 || !coords || !win_img || !g) return UCOD_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (accumulate)
+    hipLaunchKernelGGL(window_gather_kernel<true>, dim3(cdiv((long)H * W, 256), n), dim3(256), 0, s, dl2, coords, win_img, g, B, H, W, ws);
+  else
+    hipLaunchKernelGGL(window_gather_kernel<false>, dim3(cdiv((long)H * W, 256), n), dim3(256), 0, s, dl2, coords, win_img, g, B, H, W, ws);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }

@@ -18,7 +18,16 @@ The window branch can be trained: in training mode with grad mode on, ``h_target
 models/discriminator.py::_DiscFunction): its inputs are the 18 ``HRE.CSF`` parameters, its forward is the same arithmetic with the activations
 saved, its backward is HIP throughout -- ``ucod_window_loss_grad``, ``ucod_dwconv7_maskdec_bwd``, the dgrad / weight-gradient GEMMs,
 ``ucod_layernorm_bwd_ex`` / ``ucod_layernorm_param_grad``, ``ucod_cross_attention96_bwd`` -- and returns d ex_loss / d parameter.  ``outputs``,
-``opt[...]`` and the GE parameters stay outside the graph (the gradient through the window scatter and the gated ensembler is not built).
+``opt[...]`` and the GE parameters stay outside the graph unless the module was built with ``train_outputs``.
+
+``train_outputs`` (build-only config key ``config.train_outputs``, default False; the idiom of the ``allow_*`` keys): with it on, in training mode with
+grad mode on and at least one of the 22 parameters (the 18 ``HRE.CSF`` ones, ``GE.fuser.{0,2}.{weight,bias}``) requiring grad, ``outputs`` -- and
+``ex_loss`` where it exists -- hang on autograd through ``_RefinerFunction``: the same forward arithmetic, bit for bit, and a backward that is HIP
+throughout: ``ucod_gated_ensemble_bwd`` (dl2 and the four fuser gradients from the saved ``GE_w``), ``ucod_window_gather`` (the scatter's adjoint, added
+into the ``g`` of ``ucod_window_loss_grad``) and ONE ``_csf_backward`` on the sum of the two window cotangents; none when no window is selected (then
+``h_preds == 0`` and ``outputs`` depends on the fuser alone).  ``preds``, ``input_features`` and ``h_inputs`` are detached: ``preds`` reaches ``outputs``
+through the entropy weight, the 19x19 average and the batch-wide max, and in the CORAL setting all three come from a frozen first stage.  ``GE.alpha``, which
+the forward never reads, gets no gradient, as in the reference.  With ``train_outputs`` off every path is what it was.
 """
 import math
 
@@ -95,9 +104,52 @@ class _WindowBranchFunction(torch.autograd.Function):
         return (None, None) + tuple(g.view(p.shape).to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.needs_input_grad[2:]))
 
 
+class _RefinerFunction(torch.autograd.Function):
+    """``outputs`` (and ``ex_loss`` where it exists) under torch autograd: tensor inputs = the 18 HRE.CSF parameters in ``named_parameters`` order, then
+    GE.fuser.0.weight, GE.fuser.0.bias, GE.fuser.2.weight, GE.fuser.2.bias.  forward -> (outputs, ex_loss or None, window_preds, h_preds, GE_w,
+    window_targets or None, window_ious or None); only outputs and ex_loss are differentiable.  backward: a missing cotangent is skipped, the CSF chain
+    runs at most once (on the sum of the two window cotangents) and not at all without a selected window."""
+
+    @staticmethod
+    def forward(ctx, module, args, *params):
+        P, Nw = args["P"], args["Nw"]
+        saved, aux, loss, sel, ious = None, None, None, None, None
+        if Nw > 0:
+            saved = {} if args["save"] else None
+            win = module._csf(*args["csf"], save=saved)
+            if args["loss"] is not None:
+                loss, sel, ious, aux = module._window_loss(win, *args["loss"])
+        else:
+            win = args["no_windows"]
+        outputs, h_preds, ge_w, l1 = module._ensemble(P, win, *args["ensemble"])
+        ctx.module, ctx.saved, ctx.aux, ctx.P, ctx.Nw = module, saved, aux, P, Nw
+        ctx.ge = (l1, h_preds, ge_w)
+        ctx.where = args["ensemble"][:2]                                     # (coords, image index) of the windows
+        ctx.set_materialize_grads(False)
+        # (without a saved CSF forward nothing can flow back from ex_loss: it leaves as a constant, as it does with train_outputs off)
+        ctx.mark_non_differentiable(*[t for t in (win, h_preds, ge_w, sel, ious, loss if saved is None else None) if t is not None])
+        return outputs, loss, win, h_preds, ge_w, sel, ious
+
+    @staticmethod
+    def backward(ctx, gout, gloss, *_unused):
+        m, P = ctx.module, ctx.P
+        need = ctx.needs_input_grad[2:]
+        csf_params = [p for _, p in m.HRE.CSF.named_parameters()]
+        fuser = [m.GE.fuser[0].weight, m.GE.fuser[0].bias, m.GE.fuser[2].weight, m.GE.fuser[2].bias]
+        g_csf, g_fuser, dl2 = [None] * 18, [None] * 4, None
+        if gout is not None:
+            l1, h_preds, ge_w = ctx.ge
+            dl2, d_a, d_c, d_d, d_b = ops.gated_ensemble_bwd(l1, h_preds, ge_w, P["f0w"], P["f0b"], P["f2w"], gout.detach().to(l1.device, torch.float32).contiguous())
+            g_fuser = [d_a, d_c, d_d, d_b]
+        if ctx.Nw > 0 and ctx.saved is not None and any(need[:18]) and (dl2 is not None or (gloss is not None and ctx.aux is not None)):
+            g_csf = m._csf_backward(ctx.saved, ctx.aux, gloss if ctx.aux is not None else None, dwin=None if dl2 is None else (dl2,) + tuple(ctx.where))
+        grads = [g.view(p.shape).to(p.dtype) if (g is not None and n) else None for g, p, n in zip(list(g_csf) + g_fuser, csf_params + fuser, need)]
+        return (None, None) + tuple(grads)
+
+
 @MODULE_REGISTRY.register()
 class SparseRefiner(nn.Module):
-    def __init__(self, config, window_size: int, threshold: float, dim: int = 768):
+    def __init__(self, config, window_size: int, threshold: float, dim: int = 768, train_outputs: bool = False):
         super().__init__()
         self.config = config
         self.selector = EntropySelector(threshold, window_size)
@@ -105,11 +157,13 @@ class SparseRefiner(nn.Module):
         self.GE = GatedEnsembler(1)
         self.window_size = window_size
         self.threshold = threshold
+        self.train_outputs = bool(train_outputs)     # opt-in: `outputs` under autograd (module docstring); off: every path as it was
+        self.csf_backward_calls = 0                  # how often _csf_backward ran on this instance (one per backward that reaches the CSF parameters)
         self._prepared = None
 
     @classmethod
     def from_config(cls, config):
-        return cls(config, config.window_size, config.threshold)
+        return cls(config, config.window_size, config.threshold, train_outputs=bool(getattr(config, "train_outputs", False)))
 
     # ------------------------------------------------------------------ weight preparation (bf16 GEMM operands, tap-major dw)
     def _prepare(self, dev):
@@ -185,18 +239,23 @@ class SparseRefiner(nn.Module):
         return win
 
     # ------------------------------------------------------------------ d ex_loss / d HRE.CSF parameters (UDLR.py:52-75 through CSF.py:38-43, mlp.py:134-148)
-    def _csf_backward(self, S, aux, gloss):
-        """The 18 gradients in ``HRE.CSF.named_parameters()`` order, f32, flat or in the GEMM's [N, K] shape.  ``gloss``: the cotangent of ex_loss."""
+    def _csf_backward(self, S, aux, gloss, dwin=None):
+        """The 18 gradients in ``HRE.CSF.named_parameters()`` order, f32, flat or in the GEMM's [N, K] shape.  ``gloss``: the cotangent of ex_loss, or None;
+        ``dwin``: None, or (dl2, coords, image index) -- the cotangent of h_preds, gathered into the same window cotangent ``g``."""
+        self.csf_backward_calls += 1
         lib, st = N.load(), N.stream()
         P, Nw, H, W = S["P"], S["Nw"], S["H"], S["W"]
         dev, C = P["dev"], P["C"]
         M = Nw * H * W
         f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         wt = ops.transpose_pad_bf16                                                 # W bf16 [N, K] -> W^T [K, N]: the B operand of a dgrad product
-        up = gloss.detach().to(dev, torch.float32).reshape(1).contiguous()
         g = f32(Nw, 1, H, W)
-        N.check(lib.ucod_window_loss_grad(N.ptr(S["win"]), N.ptr(aux["h_targets"]), N.ptr(aux["win_flat"]), N.ptr(aux["l_up"]), N.ptr(aux["ious"]), N.ptr(up),
-                                          N.ptr(g), Nw, aux["B"], H, W, self.window_size, st), "ucod_window_loss_grad")
+        if gloss is not None:
+            up = gloss.detach().to(dev, torch.float32).reshape(1).contiguous()
+            N.check(lib.ucod_window_loss_grad(N.ptr(S["win"]), N.ptr(aux["h_targets"]), N.ptr(aux["win_flat"]), N.ptr(aux["l_up"]), N.ptr(aux["ious"]), N.ptr(up),
+                                              N.ptr(g), Nw, aux["B"], H, W, self.window_size, st), "ucod_window_loss_grad")
+        if dwin is not None:
+            ops.window_gather(dwin[0], dwin[1], dwin[2], g, gloss is not None, H, W, self.window_size)
         # depthwise conv + mask head
         wsb = f32(min(Nw * H, 64) * 49 * C)
         d_dw, d_dwb, d_mw, d_mb, dx2 = f32(C, 49), f32(C), f32(C), f32(1), f32(M, C)
@@ -268,6 +327,22 @@ class SparseRefiner(nn.Module):
                                      n, B, h, w, ws, N.stream()), "ucod_window_loss")
         return out[0], sel, ious, dict(h_targets=h_targets, win_flat=win_flat, l_up=l_up, ious=ious, B=B)
 
+    def _ensemble(self, P, window_preds, cd, l_idx, preds, hH, hW):
+        """window scatter (HRE.py:18-39) + GatedEnsembler (GE_pix_level.py:16-25) -> (outputs, h_preds, GE_w, the resized first-stage logits)."""
+        lib, st, dev, ws = N.load(), N.stream(), preds.device, self.window_size
+        B, Nw = preds.shape[0], int(window_preds.shape[0])
+        h_preds = torch.empty(B, 1, ws * hH, ws * hW, dtype=torch.float32, device=dev)
+        N.check(lib.ucod_window_scatter(N.ptr(window_preds) if Nw else None, N.ptr(cd) if Nw else None, N.ptr(l_idx) if Nw else None,
+                                        N.ptr(h_preds), Nw, B, hH, hW, ws, st), "ucod_window_scatter")
+        h2, w2 = h_preds.shape[-2:]
+        l1 = ops.bilinear_resize(preds, h2, w2)
+        outputs = torch.empty_like(h_preds)
+        ge_w = torch.empty_like(h_preds)
+        wsb = torch.empty(lib.ucod_gated_ensemble_workspace_bytes(B, h2, w2), dtype=torch.uint8, device=dev)
+        N.check(lib.ucod_gated_ensemble(N.ptr(l1), N.ptr(h_preds), N.ptr(P["f0w"]), N.ptr(P["f0b"]), N.ptr(P["f2w"]), P["f2b"], N.ptr(outputs),
+                                        N.ptr(ge_w), N.ptr(wsb), B, h2, w2, st), "ucod_gated_ensemble")
+        return outputs, h_preds, ge_w, l1
+
     def forward(self, input_features, h_inputs, preds, h_targets=None):
         if not input_features.is_cuda:
             raise RuntimeError("SparseRefiner runs on the HIP path only: move the module and its inputs to 'cuda'")
@@ -297,33 +372,40 @@ class SparseRefiner(nn.Module):
         csf_params = [p for _, p in self.HRE.CSF.named_parameters()]
         # the window branch under autograd: only where a loss exists and somebody asks for its gradient; everything else is the plain forward
         graph = (self.training and torch.is_grad_enabled() and Nw > 0 and h_targets is not None and any(p.requires_grad for p in csf_params))
-        trained = None
+        fuser_params = [self.GE.fuser[0].weight, self.GE.fuser[0].bias, self.GE.fuser[2].weight, self.GE.fuser[2].bias]
+        # `outputs` under autograd as well: opt-in (train_outputs), and only where somebody asks for a gradient
+        graph_out = (self.train_outputs and self.training and torch.is_grad_enabled() and any(p.requires_grad for p in csf_params + fuser_params))
+        trained, whole = None, None
         if Nw > 0:
             l_idx = torch.from_numpy(sel[:, 0].astype(np.int32)).to(dev)
             h_idx = torch.from_numpy((sel[:, 0] * ws * ws + sel[:, 1]).astype(np.int32)).to(dev)
-            if graph:
+            cd = coords_list.to(torch.int32).contiguous()
+            if graph_out:
+                window_preds = None
+            elif graph:
                 trained = _WindowBranchFunction.apply(self, dict(csf=(P, input_features.detach(), h_inputs.detach(), l_idx, h_idx, hH, hW),
                                                                  loss=(preds.detach(), h_targets, h_idx)), *csf_params)
                 window_preds = trained[1]
             else:
                 window_preds = self._csf(P, input_features, h_inputs, l_idx, h_idx, hH, hW)
-            cd = coords_list.to(torch.int32).contiguous()
         else:
             l_idx = torch.zeros(0, dtype=torch.int32, device=dev)
             h_idx = torch.zeros(0, dtype=torch.int32, device=dev)
             window_preds = torch.zeros(0, 1, hH, hW, dtype=torch.float32, device=dev)
             cd = torch.zeros(0, 2, dtype=torch.int32, device=dev)
-        h_preds = torch.empty(B, 1, ws * hH, ws * hW, dtype=torch.float32, device=dev)
-        N.check(lib.ucod_window_scatter(N.ptr(window_preds) if Nw else None, N.ptr(cd) if Nw else None, N.ptr(l_idx) if Nw else None,
-                                        N.ptr(h_preds), Nw, B, hH, hW, ws, st), "ucod_window_scatter")
-        # GatedEnsembler (GE_pix_level.py:16-25)
-        h2, w2 = h_preds.shape[-2:]
-        l1 = ops.bilinear_resize(preds, h2, w2)
-        outputs = torch.empty_like(h_preds)
-        ge_w = torch.empty_like(h_preds)
-        wsb = torch.empty(lib.ucod_gated_ensemble_workspace_bytes(B, h2, w2), dtype=torch.uint8, device=dev)
-        N.check(lib.ucod_gated_ensemble(N.ptr(l1), N.ptr(h_preds), N.ptr(P["f0w"]), N.ptr(P["f0b"]), N.ptr(P["f2w"]), P["f2b"], N.ptr(outputs),
-                                        N.ptr(ge_w), N.ptr(wsb), B, h2, w2, st), "ucod_gated_ensemble")
+        if graph_out:
+            # the activations are saved exactly where the window branch alone would save them: the forward is bit for bit the one with train_outputs off
+            whole = _RefinerFunction.apply(self, dict(P=P, Nw=Nw, save=any(p.requires_grad for p in csf_params), no_windows=window_preds,
+                                                      csf=(P, input_features.detach(), h_inputs.detach(), l_idx, h_idx, hH, hW),
+                                                      loss=None if h_targets is None else (preds.detach(), h_targets, h_idx),
+                                                      ensemble=(cd, l_idx, preds.detach(), hH, hW)), *csf_params, *fuser_params)
+            window_preds = whole[2]
+            if whole[1] is not None:
+                trained = (whole[1], None, whole[5], whole[6])
+        if whole is not None:
+            outputs, h_preds, ge_w = whole[0], whole[3], whole[4]
+        else:
+            outputs, h_preds, ge_w, _ = self._ensemble(P, window_preds, cd, l_idx, preds, hH, hW)
         opt = {"mask": mask, "entropy": entropy, "h_preds": h_preds, "window_preds": window_preds, "GE_w": ge_w, "preds": preds,
                "coords_list": coords_list, "h_targets": h_targets}
         if trained is not None:

@@ -348,6 +348,10 @@ SIGNATURES = {
     "ucod_dwconv7_maskdec_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, ci, vp]),
     "ucod_layernorm_param_grad": (ci, [vp, ci, vp, vp, vp, vp, sz, ci, ci, cf, vp]),
     "ucod_transpose_pad_bf16": (ci, [vp, ci, ci, ci, ci, vp, vp]),
+    # the gradient through the refiner's `outputs` (train_outputs): backward of the gated ensembler in l2 and the fuser, and the window scatter's adjoint
+    "ucod_gated_ensemble_bwd_workspace_bytes": (sz, [ci, ci, ci]),
+    "ucod_gated_ensemble_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, vp]),
+    "ucod_window_gather": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "ucod_gated_ensemble_workspace_bytes": (sz, [ci, ci, ci]),
     "ucod_gated_ensemble": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_step_loss": (ci, [vp, vp, ci, vp, vp]),

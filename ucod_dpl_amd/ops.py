@@ -749,3 +749,27 @@ def layernorm_param_grad(dy, x, eps):
     check(N.load().ucod_layernorm_param_grad(ptr(dy), N.LNB_DY_BF16 if dy.dtype == torch.bfloat16 else 0, ptr(_f32(x)), ptr(dg), ptr(db), ptr(ws),
                                              ws.numel() * 4, rows, D, float(eps), stream()), "ucod_layernorm_param_grad")
     return dg, db
+
+
+def gated_ensemble_bwd(l1_up, l2, ge_w, f0w, f0b, f2w, g_out):
+    """Backward of ucod_gated_ensemble for the cotangent ``g_out`` of its output -> (dl2 [B,1,h,w], d fuser.0.weight [64], d fuser.0.bias [64],
+    d fuser.2.weight [64], d fuser.2.bias [1]), all f32; deterministic (per-workgroup partials, one ordered f64 sum)."""
+    lib = N.load()
+    B, _, h, w = l2.shape
+    dev = l2.device
+    dl2 = torch.empty_like(l2)
+    d_a, d_c, d_d = (torch.empty(64, dtype=torch.float32, device=dev) for _ in range(3))
+    d_b = torch.empty(1, dtype=torch.float32, device=dev)
+    nbytes = lib.ucod_gated_ensemble_bwd_workspace_bytes(B, h, w)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib.ucod_gated_ensemble_bwd(ptr(_f32(l1_up)), ptr(_f32(l2)), ptr(_f32(ge_w)), ptr(f0w), ptr(f0b), ptr(f2w), ptr(_f32(g_out)), ptr(dl2), ptr(d_a), ptr(d_c),
+                                      ptr(d_d), ptr(d_b), ptr(ws), nbytes, B, h, w, stream()), "ucod_gated_ensemble_bwd")
+    return dl2, d_a, d_c, d_d, d_b
+
+
+def window_gather(dl2, coords, win_img, g, accumulate, H, W, ws):
+    """g [n,1,H,W] (+)= the windows' cells of dl2 [B,1,ws*H,ws*W] / (1 + 1e-6): the adjoint of ucod_window_scatter."""
+    n, B = int(g.shape[0]), int(dl2.shape[0])
+    check(N.load().ucod_window_gather(ptr(dl2), ptr(coords) if n else None, ptr(win_img) if n else None, ptr(g) if n else None, int(bool(accumulate)), n, B, H, W,
+                                      ws, stream()), "ucod_window_gather")
+    return g
