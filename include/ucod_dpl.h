@@ -1360,6 +1360,25 @@ int ucod_gated_ensemble_bwd(const float* l1_up, const float* l2, const float* ge
  * UCOD_EINVAL: a null pointer with n > 0, a non-positive size, n < 0 or n > 65535, B * ws * H * ws * W >= 2^29, accumulate other than 0 / 1. */
 int ucod_window_gather(const float* dl2, const int* coords, const int* win_img, float* g, int accumulate, int n, int B, int H, int W, int ws, void* stream);
 
+/* ------------------------------------------------------------------ CORAL SparseRefiner, the optimizer step (SparseRefiner(direct_wgrad=True))
+ * Weight gradient of an nn.Linear (mlp.py:122,141-143 differentiated in the weights) from the TOKEN-major operands, with no transposed copy in global
+ * memory:  dW[n][k] (+)= sum_m dy[m][n] x[m][k];  dy bf16 [M, ld_dy], x bf16 [M, ld_x], dW f32 [N, ld_dw]; bf16 products accumulated in f32 on the MFMA.
+ * The token axis is split deterministically:
+ *   nsplit(M, N, K):  tiles = ceil(N / 128) * ceil(K / 128);  n = floor((256 + tiles / 2) / tiles) [integer tiles / 2] clamped to [1, ceil(M / 64)];
+ *                     chunk = 64 * ceil(ceil(M / n) / 64);  nsplit = ceil(M / chunk)      (a function of the three sizes only; chunk(nsplit) == chunk)
+ * chunk s owns rows [s chunk, min(M, (s + 1) chunk)); a workgroup owns one 128 x 128 tile of one chunk and walks it in 64-row slabs, one
+ * v_mfma_f32_32x32x16_bf16 per 16 rows; its f32 partial goes to workspace[s][N][K]; a second kernel adds the partials in ascending s in f32 and then
+ * writes the sum to dW, or (accumulate != 0) adds it to dW.  nsplit == 1: no workspace (it may be NULL), the tile is written or added to dW directly.
+ * No atomics: two runs are bit-identical.  7 chunks at 768 x 768 (252 workgroups), 4 at 1536 x 768, 2 at 3072 x 768 and 768 x 3072.
+ * ucod_wgrad_bf16_det_workspace_bytes = nsplit > 1 ? nsplit * N * K * 4 : 0; both helpers return 0 for sizes the entry point refuses.
+ * UCOD_EINVAL with nothing launched: a null pointer (workspace only where it is needed), M < 1, N or K not a positive multiple of 64, ld_dy < N, ld_x < K,
+ * ld_dw < K, ld_dy or ld_x not a multiple of 4 or dy / x not 8-byte aligned (row starts must be), dW or workspace not 4-byte aligned, a workspace that is
+ * too small.  bf16 in both libraries.  ABI stays 5 (additions only). */
+size_t ucod_wgrad_bf16_det_workspace_bytes(int M, int N, int K);
+int ucod_wgrad_bf16_det_nsplit(int M, int N, int K);
+int ucod_wgrad_bf16_det(const void* dy_bf16, int ld_dy, const void* x_bf16, int ld_x, float* dW, int ld_dw, int M, int N, int K, int accumulate, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ COD measures (row N4: engine/utils/metrics/metric.py::statistics)
  * pred, gt f32 [B,H,W] (any range: the measures min-max normalise the prediction and threshold the normalised ground truth at 0.5,
  * _prepare_data :125-133).  out f64 [B][UCOD_COD_RECORD], per image:

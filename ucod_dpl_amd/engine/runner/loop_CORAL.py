@@ -8,12 +8,15 @@ decoder, the refinement from the HIP refiner; predictions are not written to dis
 scope); the statistics are the nine COD measures of engine/utils/metrics/metric.py::statistics, computed on the device
 (``engine/utils/metrics``, csrc/cod_metrics.hip).  ``WindowFeatures`` is the data side (data/datasets/lr_dataset.py:82-166): the 3x3 window key
 features and the 2x2 overlapping crops of the 54x54 key map, with every backbone call of an image batched into one pass.
+
+Second-stage TRAINING: the reference's ``LocalRefineTrainLoop`` is ``pass`` (:38-39).  Here it is a loop (below): ``RefinerArena`` + two fused AdamW segments +
+StepLR around ``SparseRefiner.loss_and_grads``, opt-in through ``train_cfg.refiner_train_loop`` (``LocalRefineRunner.launch_train``).
 """
 import numpy as np
 import torch
 
 from ... import ops, parallel
-from .loop_UCOD_DPL import BaseLoop
+from .loop_UCOD_DPL import BaseLoop, FusedAdamW, StepLR
 from .loop_look_twice import MAEStatistics  # noqa: F401  (re-exported)
 from ..utils.metrics import statistics
 
@@ -98,12 +101,12 @@ class LocalRefineValidationLoop(BaseLoop):
     def _should_crop_center(self, preds):
         return bool((preds > 0).sum() / (preds.shape[2] * preds.shape[3]) < 0.001)
 
-    def _features_and_preds(self, l_in, m_in, h_in):
+    def _features_and_preds(self, l_in, m_in, h_in, require_m=None):
         wl = self.window_length
         b, c = l_in.shape[:2]
         l = ops.bilinear_resize(l_in.to(self.device, torch.float32), wl, wl)
         h = ops.bilinear_resize(h_in.to(self.device, torch.float32).flatten(0, 1), wl, wl).reshape(b, -1, c, wl, wl)
-        if self.cfg.dataset_cfg.valset_cfg.require_m_patches:
+        if self.cfg.dataset_cfg.valset_cfg.require_m_patches if require_m is None else require_m:
             m = ops.bilinear_resize(m_in.to(self.device, torch.float32).flatten(0, 1), 68, 68)
             preds = self.concate_preds(self.runner.model(m)[0].reshape(b, -1, 1, 68, 68))
         else:
@@ -152,3 +155,124 @@ class LocalRefineValidationLoop(BaseLoop):
         result = stats.get_result()
         self.runner.logger.log_table({k: [round(v, 4)] for k, v in result.items()})
         return result
+
+
+# ------------------------------------------------------------------------------------------------ second-stage training
+class RefinerArena:
+    """Flat f32 storage ``p, g, m, v`` (parameters, gradients, Adam moments) of a ``SparseRefiner``, in this order: the 18 ``HRE.CSF`` parameters in
+    ``named_parameters`` order (segment ``csf``), ``GE.fuser.{0.weight, 0.bias, 2.weight, 2.bias}`` (segment ``fuser``), ``GE.alpha`` (never stepped: the
+    forward does not read it).  The parameters are re-pointed at views of ``p``, the way ``DiscArena`` does it: ``state_dict`` names and shapes, the checkpoint
+    layout and ``load_state_dict`` keep working, the arena is the storage.  Move the module to its device BEFORE building the arena (``module.to`` would
+    detach the parameters from it again)."""
+
+    FUSER = ("GE.fuser.0.weight", "GE.fuser.0.bias", "GE.fuser.2.weight", "GE.fuser.2.bias")
+
+    def __init__(self, refiner, device=None):
+        params = dict(refiner.named_parameters())
+        self.names = ["HRE.CSF." + n for n, _ in refiner.HRE.CSF.named_parameters()] + list(self.FUSER) + ["GE.alpha"]
+        if sorted(self.names) != sorted(params):
+            raise ValueError("RefinerArena: the module's parameters are not the 18 HRE.CSF + 4 GE.fuser + GE.alpha of a SparseRefiner")
+        device = params[self.names[0]].device if device is None else torch.device(device)
+        self.device = device
+        self.sizes = [params[n].numel() for n in self.names]
+        self.offsets = [sum(self.sizes[:i]) for i in range(len(self.sizes))]
+        self.n = sum(self.sizes)
+        self.n_csf, self.n_fuser = sum(self.sizes[:18]), sum(self.sizes[18:22])
+        mk = lambda: torch.zeros(self.n, dtype=torch.float32, device=device)  # noqa: E731
+        self.p, self.g, self.m, self.v = mk(), mk(), mk(), mk()
+        self.grad_views = []
+        for name, off, n in zip(self.names, self.offsets, self.sizes):
+            prm = params[name]
+            view = self.p[off:off + n].view(prm.shape)
+            view.copy_(prm.data.to(device))
+            prm.data = view
+            self.grad_views.append(self.g[off:off + n].view(prm.shape))
+        refiner._prepared = None
+
+    def segment(self, flat, which):
+        """the ``csf`` or ``fuser`` slice of one of the four flat tensors"""
+        a, b = {"csf": (0, self.n_csf), "fuser": (self.n_csf, self.n_csf + self.n_fuser)}[which]
+        return flat[a:b]
+
+
+class LocalRefineTrainLoop(LocalRefineValidationLoop):
+    """The second-stage training loop the reference leaves empty (``LocalRefineTrainLoop: pass``, engine/runner/loop_CORAL.py:38-39), with the optimizer its runner
+    builds for it (engine/runner/runner.py:444-460: ``AdamW(refiner.parameters(), lr=lr0)`` with torch's defaults, ``StepLR(step_lr_size, step_lr_gamma)``) run as
+    fused HIP launches over a flat ``RefinerArena``, and the refiner block of models/modules/mlp.py differentiated by ``SparseRefiner.loss_and_grads`` -- no autograd
+    graph.
+
+    Two ``FusedAdamW`` instances (``ucod_adamw_ema`` with no EMA target), one per segment, each with its own step count: a segment is stepped only when it received
+    a gradient this step -- ``torch.optim.AdamW``'s rule for ``grad is None`` (no decay, no moment update, no count).  ``ex_loss`` alone reaches the ``HRE.CSF``
+    segment only; the ``GE.fuser`` segment moves when ``outputs_cotangent(outputs, opt) -> d loss / d outputs`` is set.  ``GE.alpha`` is never stepped.  Both
+    StepLR schedules are stepped once per epoch.
+
+    ``step(batch)``: ``preds`` from the frozen baseline as the validation loop obtains them (``_features_and_preds``; the m-patch route when
+    ``dataset_cfg.trainset_cfg.require_m_patches`` is set), ``h_targets`` from ``batch['h_targets']`` ([B*ws*ws, 1, wl, wl]; the reference's LR dataset does not
+    supply it, the caller's loader does), ``loss_and_grads`` into the arena's gradient views, the segment steps, and then ``refiner._prepared = None``: the module
+    keys its bf16 operands on ``(data_ptr, _version)``, which an in-place HIP update does not change.  A batch with no selected window and no cotangent takes no
+    step.  ``last``: ``ex_loss``, ``windows``, ``stepped``.  One GPU, one batch per step."""
+
+    def __init__(self, config, runner, arena=None, outputs_cotangent=None):
+        super().__init__(config, runner)
+        self._mode = "train"
+        tc = self.cfg.train_cfg
+        self.refiner = runner.refiner
+        self.arena = arena if arena is not None else RefinerArena(self.refiner, self.device)
+        self.refiner.direct_wgrad = bool(tc.get("refiner_direct_wgrad", True))
+        self.outputs_cotangent = outputs_cotangent
+        A = self.arena
+        self.optimizers = {k: FusedAdamW(*(A.segment(t, k) for t in (A.p, A.g, A.m, A.v)), tc.lr0) for k in ("csf", "fuser")}
+        self.lr_schedulers = {k: StepLR(o, tc.step_lr_size, tc.step_lr_gamma) for k, o in self.optimizers.items()}
+        ds = self.cfg.get("dataset_cfg", None)
+        self.require_m_patches = bool(ds.trainset_cfg.get("require_m_patches", False)) if ds is not None and "trainset_cfg" in ds else False
+        self._cur_epoch = tc.get("start_epoch", 0)
+        self._max_epoch = tc.max_epoch
+        sc = tc.save_cfg
+        self.save_start = (self._max_epoch + sc.start_save) if sc.start_save < 0 else sc.start_save
+        self.save_interval = sc.save_interval
+        self.global_step = 0
+        self.last = {}
+
+    def refine_step(self, l_features, h_features, preds, h_targets):
+        """loss_and_grads into the arena, the segment steps, the invalidation -> ``last``"""
+        A, r = self.arena, self.refiner
+        _, ex_loss, opt = r.loss_and_grads(l_features, h_features, preds, h_targets, A.grad_views[:22], outputs_cotangent=self.outputs_cotangent)
+        stepped = self.apply_updates(*opt["grads_written"])
+        self.last = dict(ex_loss=ex_loss, windows=int(opt["window_preds"].shape[0]), stepped=stepped)
+        return self.last
+
+    def apply_updates(self, csf, fuser):
+        """step the segments that received a gradient; the bf16 operands of the module are stale afterwards"""
+        stepped = False
+        for k, got in (("csf", csf), ("fuser", fuser)):
+            if got:
+                self.optimizers[k].step()
+                stepped = True
+        if stepped:
+            self.refiner._prepared = None
+        return stepped
+
+    def step(self, batch):
+        if "h_targets" not in batch or batch["h_targets"] is None:
+            raise KeyError("LocalRefineTrainLoop.step: the batch has no 'h_targets' ([B*ws*ws, 1, window_length, window_length]); the LR dataset of the reference does "
+                           "not supply the window targets, the caller's loader has to")
+        with torch.no_grad():
+            fd = self._features_and_preds(batch["features"], batch.get("m_inputs", None), batch["h_inputs"], require_m=self.require_m_patches)
+            out = self.refine_step(fd["l_features"], fd["h_features"], fd["preds"], batch["h_targets"].to(self.device, torch.float32))
+        self.global_step += 1
+        return out
+
+    def decide_to_save(self):
+        return self._cur_epoch >= self.save_start and self._cur_epoch % self.save_interval == 0
+
+    def run(self):
+        self.refiner.train()
+        while self._cur_epoch < self._max_epoch:
+            for batch in self.runner.train_dataloader:
+                self.step(batch)
+            for s in self.lr_schedulers.values():
+                s.step()
+            self._cur_epoch += 1
+            if self.decide_to_save():
+                self.runner.save_checkpoint(self._cur_epoch)
+        return self.last

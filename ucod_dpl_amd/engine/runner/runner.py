@@ -147,9 +147,10 @@ class LocalRefineRunner(StandardRunner):
     """CORAL second stage -- host-side mirror of engine/runner/runner.py::LocalRefineRunner (:400-590): the frozen first-stage
     ``baseline`` (checkpoint from ``train_cfg.checkpoint``), the ``SparseRefiner`` built by ``SparseRefiner.from_config(model_cfg)``
     (weights from ``train_cfg.refiner_path``), ``launch_val`` -> ``LocalRefineValidationLoop`` on the HIP decoder / refiner.
-    The reference's second-stage TRAINING loop is empty (``LocalRefineTrainLoop: pass``, loop_CORAL.py:38-39) and so is this one:
-    the AdamW/StepLR pair over the refiner's parameters is built with the reference's hyper-parameters for parity of the object,
-    ``launch_train`` raises.  No first-stage discriminator, arena or dataloader factory is needed here."""
+    The reference's second-stage TRAINING loop is empty (``LocalRefineTrainLoop: pass``, loop_CORAL.py:38-39): with the unmodified configs
+    the AdamW/StepLR pair over the refiner's parameters is built with the reference's hyper-parameters for parity of the object and
+    ``launch_train`` raises; with ``train_cfg.refiner_train_loop`` it runs this project's ``LocalRefineTrainLoop`` (loop_CORAL.py) over a
+    ``RefinerArena``.  No first-stage discriminator, decoder arena or dataloader factory is needed here."""
 
     def __init__(self, config, train_dataloader=None, val_dataloader=None, device=None, window_features=None):
         self.refiner = None
@@ -200,7 +201,17 @@ class LocalRefineRunner(StandardRunner):
         self.logger.info("Successfully loaded refiner weights")
 
     def launch_train(self):
-        raise NotImplementedError("the reference ships no second-stage training loop (LocalRefineTrainLoop: pass, loop_CORAL.py:38-39)")
+        """Opt-in (build-only key ``train_cfg.refiner_train_loop``; the shipped configs do not set it and keep raising): the refiner's parameters move into a
+        flat ``RefinerArena`` and ``LocalRefineTrainLoop`` runs -- fused AdamW segments with the hyper-parameters of runner.py:444-460 in place of ``self.optimizer``."""
+        if not bool(self.config.train_cfg.get("refiner_train_loop", False)):
+            raise NotImplementedError("the reference ships no second-stage training loop (LocalRefineTrainLoop: pass, loop_CORAL.py:38-39); "
+                                      "train_cfg.refiner_train_loop=True runs this project's")
+        from .loop_CORAL import LocalRefineTrainLoop, RefinerArena
+        if getattr(self, "refiner_arena", None) is None:
+            self.refiner_arena = RefinerArena(self.refiner, self.device)
+        self.trainloop = LocalRefineTrainLoop(self.config, self, arena=self.refiner_arena)
+        self.optimizer, self.lr_scheduler = self.trainloop.optimizers["csf"], self.trainloop.lr_schedulers["csf"]
+        return self.trainloop.run()
 
     def launch_val(self):                                      # :584-590
         from .loop_CORAL import LocalRefineValidationLoop

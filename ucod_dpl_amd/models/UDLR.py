@@ -28,6 +28,13 @@ into the ``g`` of ``ucod_window_loss_grad``) and ONE ``_csf_backward`` on the su
 ``h_preds == 0`` and ``outputs`` depends on the fuser alone).  ``preds``, ``input_features`` and ``h_inputs`` are detached: ``preds`` reaches ``outputs``
 through the entropy weight, the 19x19 average and the batch-wide max, and in the CORAL setting all three come from a frozen first stage.  ``GE.alpha``, which
 the forward never reads, gets no gradient, as in the reference.  With ``train_outputs`` off every path is what it was.
+
+``direct_wgrad`` (build-only config key ``config.direct_wgrad``, default False): the six weight gradients of ``_csf_backward`` -- the nn.Linear layers of
+models/modules/mlp.py:122,141-143 differentiated in their weights -- come from ``ucod_wgrad_bf16_det`` (csrc/wgrad.hip: the token-major bf16 operands read where
+they lie, the token axis split deterministically) instead of two transposes and the plain GEMM: the same operand values, another order of the f32 additions.
+``loss_and_grads`` is the training forward and the backward with no torch autograd, into caller-owned gradient buffers: what the second-stage training loop calls
+(engine/runner/loop_CORAL.py::LocalRefineTrainLoop; the reference's is ``pass``, engine/runner/loop_CORAL.py:38-39, under the optimizer of
+engine/runner/runner.py:444-460).  An in-place update of the weights that changes neither ``data_ptr`` nor ``_version`` has to set ``_prepared = None``.
 """
 import math
 
@@ -149,7 +156,7 @@ class _RefinerFunction(torch.autograd.Function):
 
 @MODULE_REGISTRY.register()
 class SparseRefiner(nn.Module):
-    def __init__(self, config, window_size: int, threshold: float, dim: int = 768, train_outputs: bool = False):
+    def __init__(self, config, window_size: int, threshold: float, dim: int = 768, train_outputs: bool = False, direct_wgrad: bool = False):
         super().__init__()
         self.config = config
         self.selector = EntropySelector(threshold, window_size)
@@ -158,12 +165,14 @@ class SparseRefiner(nn.Module):
         self.window_size = window_size
         self.threshold = threshold
         self.train_outputs = bool(train_outputs)     # opt-in: `outputs` under autograd (module docstring); off: every path as it was
+        self.direct_wgrad = bool(direct_wgrad)       # opt-in: the six weight gradients by ucod_wgrad_bf16_det (ops.weight_grad_direct); off: every path as it was
         self.csf_backward_calls = 0                  # how often _csf_backward ran on this instance (one per backward that reaches the CSF parameters)
         self._prepared = None
 
     @classmethod
     def from_config(cls, config):
-        return cls(config, config.window_size, config.threshold, train_outputs=bool(getattr(config, "train_outputs", False)))
+        return cls(config, config.window_size, config.threshold, train_outputs=bool(getattr(config, "train_outputs", False)),
+                   direct_wgrad=bool(getattr(config, "direct_wgrad", False)))
 
     # ------------------------------------------------------------------ weight preparation (bf16 GEMM operands, tap-major dw)
     def _prepare(self, dev):
@@ -239,15 +248,29 @@ class SparseRefiner(nn.Module):
         return win
 
     # ------------------------------------------------------------------ d ex_loss / d HRE.CSF parameters (UDLR.py:52-75 through CSF.py:38-43, mlp.py:134-148)
-    def _csf_backward(self, S, aux, gloss, dwin=None):
+    def _csf_backward(self, S, aux, gloss, dwin=None, out=None):
         """The 18 gradients in ``HRE.CSF.named_parameters()`` order, f32, flat or in the GEMM's [N, K] shape.  ``gloss``: the cotangent of ex_loss, or None;
-        ``dwin``: None, or (dl2, coords, image index) -- the cotangent of h_preds, gathered into the same window cotangent ``g``."""
+        ``dwin``: None, or (dl2, coords, image index) -- the cotangent of h_preds, gathered into the same window cotangent ``g``.  ``out``: None, or 18
+        contiguous f32 buffers of the parameters' sizes (any shape) that the kernels write instead of fresh tensors (the arena views of a training loop); the
+        values are the same bits.  With ``direct_wgrad`` the six weight gradients come from ``ops.weight_grad_direct`` on the bf16 operands the chain holds
+        anyway (the values ``ops.weight_grad`` rounds to; only the order of the f32 additions differs) and share one workspace."""
         self.csf_backward_calls += 1
         lib, st = N.load(), N.stream()
         P, Nw, H, W = S["P"], S["Nw"], S["H"], S["W"]
         dev, C = P["dev"], P["C"]
         M = Nw * H * W
-        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        if out is not None and (len(out) != 18 or any(o.dtype != torch.float32 or not o.is_contiguous() or not o.is_cuda for o in out)):
+            raise ValueError("_csf_backward: out must be 18 contiguous float32 device buffers")
+        f32 = new
+        buf = (lambda i, *shape: new(*shape)) if out is None else (lambda i, *shape: out[i].view(*shape))          # noqa: E731
+        if self.direct_wgrad:
+            F4 = P["w1"].shape[0]
+            wsb_w = torch.empty(max(16, max(lib.ucod_wgrad_bf16_det_workspace_bytes(M, n, k) for n, k in ((C, C), (2 * C, C), (F4, C), (C, F4)))),
+                                dtype=torch.uint8, device=dev)
+            wgrad = lambda dy16, dy, x, o: ops.weight_grad_direct(dy16, x, out=o, ws=wsb_w)                          # noqa: E731
+        else:
+            wgrad = lambda dy16, dy, x, o: ops.weight_grad(dy, x, out=o)                                              # noqa: E731
         wt = ops.transpose_pad_bf16                                                 # W bf16 [N, K] -> W^T [K, N]: the B operand of a dgrad product
         g = f32(Nw, 1, H, W)
         if gloss is not None:
@@ -258,23 +281,24 @@ class SparseRefiner(nn.Module):
             ops.window_gather(dwin[0], dwin[1], dwin[2], g, gloss is not None, H, W, self.window_size)
         # depthwise conv + mask head
         wsb = f32(min(Nw * H, 64) * 49 * C)
-        d_dw, d_dwb, d_mw, d_mb, dx2 = f32(C, 49), f32(C), f32(C), f32(1), f32(M, C)
+        d_dw, d_dwb, d_mw, d_mb, dx2 = buf(14, C, 49), buf(15, C), buf(16, C), buf(17, 1), f32(M, C)
         N.check(lib.ucod_dwconv7_maskdec_bwd(N.ptr(g), N.ptr(S["x2"]), N.ptr(P["dwT"]), N.ptr(P["dwb"]), N.ptr(P["mw"]), N.ptr(d_dw), N.ptr(d_dwb), N.ptr(d_mw),
                                              N.ptr(d_mb), N.ptr(dx2), N.ptr(wsb), wsb.numel() * 4, Nw, H, W, C, st), "ucod_dwconv7_maskdec_bwd")
         # x2 = x + fc2(gelu(fc1(norm_mlp(x))))
-        d_b2 = ops.colsum_det(dx2)
-        d_w2 = ops.weight_grad(dx2, S["gact"])
-        dpre = ops.dgrad_bf16(ops.cast_bf16(dx2), wt(P["w2"]), gelu_pre=S["pre"])
-        d_b1 = ops.colsum_det(dpre)
-        d_w1 = ops.weight_grad(dpre, S["hn"])
+        d_b2 = ops.colsum_det(dx2, out=buf(11, C))
+        dx2s = ops.cast_bf16(dx2)
+        d_w2 = wgrad(dx2s, dx2, S["gact"], buf(10, C, S["gact"].shape[1]))
+        dpre = ops.dgrad_bf16(dx2s, wt(P["w2"]), gelu_pre=S["pre"])
+        d_b1 = ops.colsum_det(dpre, out=buf(9, dpre.shape[1]))
+        d_w1 = wgrad(dpre, dpre, S["hn"], buf(8, dpre.shape[1], C))
         dhn = ops.dgrad_bf16(dpre, wt(P["w1"]))
-        d_nm_g, d_nm_b = ops.layernorm_param_grad(dhn, S["x"], LN_EPS)
+        d_nm_g, d_nm_b = ops.layernorm_param_grad(dhn, S["x"], LN_EPS, out=(buf(12, C), buf(13, C)))
         dx, dxs = f32(M, C), torch.empty(M, C, dtype=torch.bfloat16, device=dev)   # the residual cotangent in front of norm_mlp, and its bf16 GEMM operand
         N.check(lib.ucod_layernorm_bwd_ex(N.ptr(dhn), N.ptr(S["x"]), N.LNB_DY_BF16, N.ptr(P["nm"][0]), N.ptr(dx2), None, N.ptr(dx), N.ptr(dxs), M, C, LN_EPS, st),
                 "ucod_layernorm_bwd_ex")
         # x = query + out_proj(attention); the gathered query / context rows are frozen features: no cotangent for them
-        d_bo = ops.colsum_det(dx)
-        d_wo = ops.weight_grad(dx, S["att"])
+        d_bo = ops.colsum_det(dx, out=buf(7, C))
+        d_wo = wgrad(dxs, dx, S["att"], buf(6, C, C))
         datt = ops.dgrad_bf16(dxs, wt(P["wo"]))
         HW = H * W
         delta = f32(Nw, HEADS, HW)
@@ -283,13 +307,13 @@ class SparseRefiner(nn.Module):
         q, kv = S["q"], S["kv"]
         N.check(lib.ucod_cross_attention96_bwd(N.ptr(q), C, N.ptr(kv), kv.data_ptr() + C * 2, 2 * C, N.ptr(S["att"]), N.ptr(datt), N.ptr(S["lse"]), N.ptr(delta),
                                                N.ptr(dq), C, N.ptr(dkv), dkv.data_ptr() + C * 2, 2 * C, Nw, HW, HW, HEADS, st), "ucod_cross_attention96_bwd")
-        d_inw, d_inb = f32(3 * C, C), f32(3 * C)
-        ops.weight_grad(dq, S["qn"], out=d_inw[:C])
-        ops.weight_grad(dkv, S["cn"], out=d_inw[C:])
+        d_inw, d_inb = buf(4, 3 * C, C), buf(5, 3 * C)
+        wgrad(dq, dq, S["qn"], d_inw[:C])
+        wgrad(dkv, dkv, S["cn"], d_inw[C:])
         ops.colsum_det(dq, out=d_inb[:C])
         ops.colsum_det(dkv, out=d_inb[C:])
-        d_nq_g, d_nq_b = ops.layernorm_param_grad(ops.dgrad_bf16(dq, wt(P["wq"])), S["q_tok"], LN_EPS)
-        d_nkv_g, d_nkv_b = ops.layernorm_param_grad(ops.dgrad_bf16(dkv, wt(P["wkv"])), S["c_tok"], LN_EPS)
+        d_nq_g, d_nq_b = ops.layernorm_param_grad(ops.dgrad_bf16(dq, wt(P["wq"])), S["q_tok"], LN_EPS, out=(buf(0, C), buf(1, C)))
+        d_nkv_g, d_nkv_b = ops.layernorm_param_grad(ops.dgrad_bf16(dkv, wt(P["wkv"])), S["c_tok"], LN_EPS, out=(buf(2, C), buf(3, C)))
         return (d_nq_g, d_nq_b, d_nkv_g, d_nkv_b, d_inw, d_inb, d_wo, d_bo, d_w1, d_b1, d_w2, d_b2, d_nm_g, d_nm_b, d_dw, d_dwb, d_mw, d_mb)
 
     def cal_ex_loss(self, opt, win_flat=None):
@@ -343,12 +367,12 @@ class SparseRefiner(nn.Module):
                                         N.ptr(ge_w), N.ptr(wsb), B, h2, w2, st), "ucod_gated_ensemble")
         return outputs, h_preds, ge_w, l1
 
-    def forward(self, input_features, h_inputs, preds, h_targets=None):
+    def _select(self, input_features, h_inputs, preds):
+        """EntropySelector (ASR.py:41-51) on the first-stage logits -> (input_features, h_inputs, preds as contiguous f32, mask, entropy, sel, coords_list)."""
         if not input_features.is_cuda:
             raise RuntimeError("SparseRefiner runs on the HIP path only: move the module and its inputs to 'cuda'")
         lib = N.load()
         dev = input_features.device
-        P = self._prepare(dev)
         ws = self.window_size
         input_features = input_features.float().contiguous()
         h_inputs = h_inputs.float().contiguous()
@@ -356,7 +380,7 @@ class SparseRefiner(nn.Module):
         B, C, H, W = input_features.shape
         ph, pw = preds.shape[-2:]
         st = N.stream()
-        # EntropySelector (ASR.py:41-51); the "already a probability?" heuristic is a data-dependent branch -> one host sync
+        # the "already a probability?" heuristic is a data-dependent branch -> one host sync
         lo, hi = torch.aminmax(preds)
         use_sigmoid = 0 if (lo.item() >= 0 and hi.item() <= 1) else 1
         entropy = torch.empty_like(preds)
@@ -367,6 +391,67 @@ class SparseRefiner(nn.Module):
         sel = np.argwhere(mask_h)                                             # rows (b, j) in (b-major, raster) order
         coords_np = np.stack([sel[:, 1] // ws, sel[:, 1] % ws], 1).astype(np.int64) if len(sel) else np.zeros((0, 2), np.int64)
         coords_list = torch.from_numpy(coords_np).to(dev)
+        return input_features, h_inputs, preds, mask, entropy, sel, coords_list
+
+    def _window_indices(self, sel, coords_list, dev):
+        """(image index, flat window index, coords) of the selected windows as int32 device tensors"""
+        ws = self.window_size
+        if len(sel) == 0:
+            return (torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, 2, dtype=torch.int32, device=dev))
+        l_idx = torch.from_numpy(sel[:, 0].astype(np.int32)).to(dev)
+        h_idx = torch.from_numpy((sel[:, 0] * ws * ws + sel[:, 1]).astype(np.int32)).to(dev)
+        return l_idx, h_idx, coords_list.to(torch.int32).contiguous()
+
+    def loss_and_grads(self, input_features, h_inputs, preds, h_targets, grads, outputs_cotangent=None):
+        """The training forward and the backward with no torch autograd, into caller-owned gradient buffers -> (outputs, ex_loss, opt), as ``forward`` returns them.
+        ``grads``: 18 contiguous f32 device buffers of the ``HRE.CSF`` parameters' sizes in ``named_parameters`` order, or 22 with those of
+        ``GE.fuser.{0.weight, 0.bias, 2.weight, 2.bias}`` behind them -- the order of ``_RefinerFunction``'s inputs.  The gradient is that of ``ex_loss``; with
+        ``outputs_cotangent(outputs, opt) -> G`` (d loss / d ``outputs``, [B,1,h,w]) it is that of ex_loss + loss(outputs): the fuser gradients need the 22 buffers,
+        and the CSF chain runs ONCE on the sum of the two window cotangents, exactly as ``_RefinerFunction.backward`` does.  Nothing to differentiate -- no selected
+        window (or no ``h_targets``) and no ``outputs_cotangent`` -- : ex_loss is 0 and no buffer is touched.  ``opt['grads_written']`` = (CSF, fuser) says which
+        of the two groups of buffers this call wrote.  ``preds`` and the features carry no gradient (they come from a frozen first stage)."""
+        if len(grads) not in (18, 22):
+            raise ValueError(f"loss_and_grads: grads must have 18 or 22 entries, got {len(grads)}")
+        input_features, h_inputs, preds, mask, entropy, sel, coords_list = self._select(input_features, h_inputs, preds)
+        dev = input_features.device
+        P = self._prepare(dev)
+        Nw = len(sel)
+        hH, hW = h_inputs.shape[-2:]
+        l_idx, h_idx, cd = self._window_indices(sel, coords_list, dev)
+        saved, aux, loss, tsel, ious = None, None, None, None, None
+        if Nw > 0:
+            saved = {}
+            window_preds = self._csf(P, input_features, h_inputs, l_idx, h_idx, hH, hW, save=saved)
+            if h_targets is not None:
+                loss, tsel, ious, aux = self._window_loss(window_preds, preds, h_targets, h_idx)
+        else:
+            window_preds = torch.zeros(0, 1, hH, hW, dtype=torch.float32, device=dev)
+        outputs, h_preds, ge_w, l1 = self._ensemble(P, window_preds, cd, l_idx, preds, hH, hW)
+        opt = {"mask": mask, "entropy": entropy, "h_preds": h_preds, "window_preds": window_preds, "GE_w": ge_w, "preds": preds,
+               "coords_list": coords_list, "h_targets": h_targets, "grads_written": (False, False)}
+        if loss is not None:
+            opt["window_targets"], opt["window_ious"] = tsel, ious
+        G = None if outputs_cotangent is None else outputs_cotangent(outputs, opt)
+        dl2 = None
+        if G is not None:
+            if len(grads) != 22:
+                raise ValueError("loss_and_grads: an outputs_cotangent needs the 22 gradient buffers (the four GE.fuser ones behind the 18)")
+            dl2, d_a, d_c, d_d, d_b = ops.gated_ensemble_bwd(l1, h_preds, ge_w, P["f0w"], P["f0b"], P["f2w"], G.detach().to(dev, torch.float32).contiguous())
+            for dst, src in zip(grads[18:], (d_a, d_c, d_d, d_b)):
+                dst.view(-1).copy_(src.view(-1))
+        csf = Nw > 0 and (dl2 is not None or aux is not None)
+        if csf:
+            one = torch.ones(1, dtype=torch.float32, device=dev) if aux is not None else None
+            self._csf_backward(saved, aux, one, dwin=None if dl2 is None else (dl2, cd, l_idx), out=list(grads[:18]))
+        opt["grads_written"] = (csf, G is not None)
+        return outputs, (loss if loss is not None else 0), opt
+
+    def forward(self, input_features, h_inputs, preds, h_targets=None):
+        input_features, h_inputs, preds, mask, entropy, sel, coords_list = self._select(input_features, h_inputs, preds)
+        dev = input_features.device
+        P = self._prepare(dev)
+        ws = self.window_size
+        B = input_features.shape[0]
         Nw = len(sel)
         hH, hW = h_inputs.shape[-2:]
         csf_params = [p for _, p in self.HRE.CSF.named_parameters()]

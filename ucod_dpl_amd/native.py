@@ -352,6 +352,9 @@ SIGNATURES = {
     "ucod_gated_ensemble_bwd_workspace_bytes": (sz, [ci, ci, ci]),
     "ucod_gated_ensemble_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, ci, ci, vp]),
     "ucod_window_gather": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "ucod_wgrad_bf16_det_workspace_bytes": (sz, [ci, ci, ci]),
+    "ucod_wgrad_bf16_det_nsplit": (ci, [ci, ci, ci]),
+    "ucod_wgrad_bf16_det": (ci, [vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
     "ucod_gated_ensemble_workspace_bytes": (sz, [ci, ci, ci]),
     "ucod_gated_ensemble": (ci, [vp, vp, vp, vp, vp, cf, vp, vp, vp, ci, ci, ci, vp]),
     "ucod_step_loss": (ci, [vp, vp, ci, vp, vp]),

@@ -718,6 +718,42 @@ def weight_grad(dy, x, out=None):
     return gemm_bf16(N.EPI_BIAS_F32, a, b, out, a.shape[0], b.shape[0], a.shape[1])
 
 
+def _rows2d(t, what):
+    """(data pointer, row stride) of a 2-D device tensor whose rows are dense; a column slice of a wider buffer (``kv[:, C:]``) is taken where it lies."""
+    if not t.is_cuda:
+        raise RuntimeError("ucod_dpl_amd: tensor is not on a GPU; the HIP path has no CPU fallback")
+    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise RuntimeError(f"ucod_dpl_amd: {what} must be 2-D with dense rows, got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t.data_ptr(), int(t.stride(0))
+
+
+def weight_grad_direct(dy, x, out=None, accumulate=False, ws=None):
+    """dW f32 [N, K] (+)= dy^T x for bf16 dy [M, N], x [M, K] read token-major where they lie (row-strided views allowed; no transposed copy): ucod_wgrad_bf16_det,
+    the token axis split into ``ucod_wgrad_bf16_det_nsplit(M, N, K)`` chunks whose f32 partials are added in ascending order -- bit-identical from run to run.
+    ``out``: f32 [N, K] rows of any stride >= K (e.g. rows of the in_proj gradient); ``accumulate`` adds into it.  ``ws``: a uint8 workspace of at least
+    ``ucod_wgrad_bf16_det_workspace_bytes(M, N, K)`` bytes to reuse; allocated when None."""
+    lib = N.load()
+    _bf16(dy), _bf16(x)
+    (pdy, ld_dy), (px, ld_x) = _rows2d(dy, "dy"), _rows2d(x, "x")
+    M, Nn = dy.shape
+    K = x.shape[1]
+    if x.shape[0] != M:
+        raise ValueError(f"weight_grad_direct: dy has {M} rows, x has {x.shape[0]}")
+    if out is None:
+        if accumulate:
+            raise ValueError("weight_grad_direct: accumulate needs out")
+        out = torch.empty(Nn, K, dtype=torch.float32, device=dy.device)
+    if tuple(out.shape) != (Nn, K):
+        raise ValueError(f"weight_grad_direct: out shape {tuple(out.shape)} != {(Nn, K)}")
+    pout, ld_dw = _rows2d(_f32(out), "out")
+    nbytes = lib.ucod_wgrad_bf16_det_workspace_bytes(M, Nn, K)
+    if ws is None and nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    check(lib.ucod_wgrad_bf16_det(pdy, ld_dy, px, ld_x, pout, ld_dw, M, Nn, K, int(bool(accumulate)), ptr(ws) if nbytes else None,
+                                  ws.numel() * ws.element_size() if nbytes else 0, stream()), "ucod_wgrad_bf16_det")
+    return out
+
+
 def dgrad_bf16(dy, wt, gelu_pre=None):
     """dx bf16 [M, K] = dy [M, N] wt[K, N]^T (wt = the transposed weight), times gelu'(gelu_pre) when the saved fc1 pre-activation is given."""
     M, Nn = dy.shape
@@ -740,12 +776,12 @@ def colsum_det(x, out=None):
     return out
 
 
-def layernorm_param_grad(dy, x, eps):
-    """(dgamma, dbeta) f32 [D] of a LayerNorm over rows: dy [rows, D] f32 or bf16, x f32 [rows, D]."""
+def layernorm_param_grad(dy, x, eps, out=None):
+    """(dgamma, dbeta) f32 [D] of a LayerNorm over rows: dy [rows, D] f32 or bf16, x f32 [rows, D].  ``out``: the two f32 [D] destinations, or None."""
     rows, D = x.shape
     slabs = min(128, (rows + 63) // 64)
     ws = torch.empty(slabs * 2 * D, dtype=torch.float32, device=x.device)
-    dg, db = torch.empty(D, dtype=torch.float32, device=x.device), torch.empty(D, dtype=torch.float32, device=x.device)
+    dg, db = (torch.empty(D, dtype=torch.float32, device=x.device), torch.empty(D, dtype=torch.float32, device=x.device)) if out is None else (_f32(out[0]), _f32(out[1]))
     check(N.load().ucod_layernorm_param_grad(ptr(dy), N.LNB_DY_BF16 if dy.dtype == torch.bfloat16 else 0, ptr(_f32(x)), ptr(dg), ptr(db), ptr(ws),
                                              ws.numel() * 4, rows, D, float(eps), stream()), "ucod_layernorm_param_grad")
     return dg, db
