@@ -1277,7 +1277,10 @@ int ucod_window_loss(const float* window_preds, const float* h_targets, const in
 
 /* GatedEnsembler (models/modules/GE_pix_level.py:16-25) after the bilinear resize of l1: 19x19 zero-padded average of
  * sigmoid(l1), its entropy normalised by the maximum over the WHOLE batch, gate = ((1 - en/en_max) + mean sigmoid(l1))/2,
- * y = l1*gate + l2*(1-gate), out = fuser(y) (1x1 conv 1->64, ReLU, 1x1 conv 64->1).  All maps f32 [B,1,h,w]. */
+ * y = l1*gate + l2*(1-gate), out = fuser(y) (1x1 conv 1->64, ReLU, 1x1 conv 64->1).  All maps f32 [B,1,h,w].
+ * workspace: ucod_gated_ensemble_workspace_bytes(B, h, w) = 4 * (2 B h w + B ceil(h w / 256) + 1) bytes -- the entropy map, sigmoid(l1), one partial sum of
+ * sigmoid(l1) per 256-pixel workgroup and the batch maximum; it need not be initialised.  The mean of sigmoid(l1) is the sum of an image's partials in a
+ * fixed order and the maximum an integer atomicMax: the call executes no floating-point atomic and two runs are bit-identical at every size. */
 size_t ucod_gated_ensemble_workspace_bytes(int B, int h, int w);
 int ucod_gated_ensemble(const float* l1_up, const float* l2, const float* fuser0_w, const float* fuser0_b, const float* fuser2_w,
                         float fuser2_b, float* out, float* weight_out, void* workspace, int B, int h, int w, void* stream);

@@ -6,7 +6,9 @@ window, C = 768, B = 2, all 18 windows selected, random init), three steps inter
   (c) ucod_gated_ensemble_bwd + ucod_window_gather alone, on the step's own tensors.
 The condition: (b) <= 1.05 x (a), both measured in this run (a second CSF backward would show as roughly 2 x).  The spread between the rounds of (a) is
 printed beside it: above 5 % the windows are too short to carry the ratio -- raise REPS.
-    refiner_outputs_bench.py [rounds [reps]]     -> profiles/refiner_outputs_bench.txt (and stdout)"""
+    refiner_outputs_bench.py [rounds [reps]]     -> profiles/refiner_outputs_bench.txt (and stdout)
+    refiner_outputs_bench.py ge [rounds [reps]]  -> stdout: ucod_gated_ensemble (the forward) alone at B = 2, 168 x 168, the production map, of whichever
+                                                    library ucod_dpl_amd.native loads (profiles/gated_ensemble_fwd.txt keeps two such runs)"""
 import os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,8 +17,10 @@ from ucod_dpl_amd import ops
 from ucod_dpl_amd.engine.config import CfgNode
 from ucod_dpl_amd.models.UDLR import SparseRefiner
 
-ROUNDS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+GE_ONLY = len(sys.argv) > 1 and sys.argv[1] == "ge"
+ARGS = sys.argv[2:] if GE_ONLY else sys.argv[1:]
+ROUNDS = int(ARGS[0]) if len(ARGS) > 0 else 7
+REPS = int(ARGS[1]) if len(ARGS) > 1 else (200 if GE_ONLY else 10)
 B, WS, WL, C = 2, 3, 56, 768
 DEV = "cuda"
 lines = []
@@ -108,6 +112,33 @@ def main():
         sys.exit(f"(b) / (a) = {ratio:.4f} > 1.05")
 
 
+def ge_forward():
+    """ucod_gated_ensemble alone on the production map: random logits, the module's default fuser"""
+    from ucod_dpl_amd import native as N
+    lib, st = N.load(), N.stream()
+    torch.manual_seed(0)
+    m = SparseRefiner.from_config(CfgNode(dict(window_size=WS, threshold=0.0015))).to(DEV)
+    P = m._prepare(torch.device(DEV, torch.cuda.current_device()))
+    g = torch.Generator().manual_seed(1)
+    h = w = WS * WL
+    l1, l2 = ((torch.randn(B, 1, h, w, generator=g) * 2).to(DEV) for _ in range(2))
+    out, wgt = torch.empty_like(l1), torch.empty_like(l1)
+    nbytes = lib.ucod_gated_ensemble_workspace_bytes(B, h, w)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+
+    def call():
+        N.check(lib.ucod_gated_ensemble(N.ptr(l1), N.ptr(l2), N.ptr(P["f0w"]), N.ptr(P["f0b"]), N.ptr(P["f2w"]), P["f2b"], N.ptr(out), N.ptr(wgt), N.ptr(wsb),
+                                        B, h, w, st), "ucod_gated_ensemble")
+
+    med, rounds = interleaved({"ge": call})
+    first = wgt.clone()
+    call()
+    torch.cuda.synchronize()
+    say(f"# ucod_gated_ensemble at [{B},1,{h},{w}] ({-(-h * w // 256)} workgroups per image), workspace {nbytes} bytes, library {N.LIB_PATH}")
+    say(f"median of {ROUNDS} x {REPS}: {med['ge'] * 1e3:9.2f} us   (rounds {', '.join(f'{t * 1e3:.2f}' for t in rounds['ge'])})")
+    say(f"GE_w of two calls bit-identical: {bool(torch.equal(first.view(torch.int32), wgt.view(torch.int32)))}")
+
+
 def write():
     out = os.path.join(ROOT, "profiles", "refiner_outputs_bench.txt")
     with open(out, "w") as f:
@@ -119,4 +150,4 @@ if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("refiner_outputs_bench.py measures on the GPU: none found")
     say(f"refiner_outputs_bench.py {' '.join(sys.argv[1:])}  ({torch.cuda.get_device_name(0)})")
-    main()
+    ge_forward() if GE_ONLY else main()

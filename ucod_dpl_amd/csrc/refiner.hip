@@ -91,9 +91,11 @@ __global__ __launch_bounds__(256) void window_scatter_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ gated ensembling (GE_pix_level.py:16-25)
-// pass 0: p = sigmoid(l1) once per pixel (round 3: the entropy pass evaluated the sigmoid of all 361 neighbours of every pixel), psum[b] += p.
+// pass 0: p = sigmoid(l1) once per pixel (round 3: the entropy pass evaluated the sigmoid of all 361 neighbours of every pixel); each workgroup leaves the
+//         sum of its 256 p in ppart[b][workgroup].  No floating-point atomic: pass 2 adds an image's partials in a fixed order, so the mean of p, and with it
+//         the gate, `outputs` and every gradient behind them, does not depend on the order in which the workgroups retire.
 // pass 1: en = -m*log(max(m,1e-5)), m = 19x19 average of p (zero padded, /361), summed in the same (dy, dx) order as before; enmax = max en.
-__global__ __launch_bounds__(256) void ge_prob_kernel(const float* __restrict__ l1, float* __restrict__ pm, float* __restrict__ psum, int hw) {
+__global__ __launch_bounds__(256) void ge_prob_kernel(const float* __restrict__ l1, float* __restrict__ pm, float* __restrict__ ppart, int hw) {
   __shared__ float red[16];
   const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   float pv = 0.f;
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void ge_prob_kernel(const float* __restrict__ 
     pm[(size_t)b * hw + p] = pv;
   }
   const float bs = block_sum(pv, red);
-  if (threadIdx.x == 0) atomicAdd(&psum[b], bs);
+  if (threadIdx.x == 0) ppart[(size_t)b * gridDim.x + blockIdx.x] = bs;
 }
 
 __global__ __launch_bounds__(256) void ge_stats_kernel(const float* __restrict__ pm, float* __restrict__ en, unsigned* __restrict__ enmax_bits,
@@ -139,19 +141,23 @@ __global__ __launch_bounds__(256) void ge_stats_kernel(const float* __restrict__
   if ((threadIdx.x & 63) == 0) atomicMax(enmax_bits, __float_as_uint(fmaxf(mx, 0.f)));   // en >= 0: uint order == float order
 }
 
-// pass 2: weight = ((1 - en/enmax) + mean_p)/2; y = l1*w + l2*(1-w); out = fuser(y) (1 -> 64 ReLU -> 1, 1x1 convs)
+// pass 2: weight = ((1 - en/enmax) + mean_p)/2; y = l1*w + l2*(1-w); out = fuser(y) (1 -> 64 ReLU -> 1, 1x1 convs).  mean_p = (sum of the image's gridDim.x
+//         partials of pass 0) / hw: every workgroup adds them itself, thread t the partials t, t + 256, ... in ascending order and then block_sum's fixed
+//         tree, so all workgroups of an image hold the same bits (with <= 2 partials that is 0 + a + b, the value the former atomic sum gave).
 __global__ __launch_bounds__(256) void ge_fuse_kernel(const float* __restrict__ l1, const float* __restrict__ l2, const float* __restrict__ en,
-                                                      const float* __restrict__ psum, const unsigned* __restrict__ enmax_bits,
+                                                      const float* __restrict__ ppart, const unsigned* __restrict__ enmax_bits,
                                                       const float* __restrict__ f0w, const float* __restrict__ f0b, const float* __restrict__ f2w,
                                                       float f2b, float* __restrict__ out, float* __restrict__ wout, int h, int w) {
-  __shared__ float a[64], c[64], d[64];
+  __shared__ float a[64], c[64], d[64], red[16];
   if (threadIdx.x < 64) { a[threadIdx.x] = f0w[threadIdx.x]; c[threadIdx.x] = f0b[threadIdx.x]; d[threadIdx.x] = f2w[threadIdx.x]; }
-  __syncthreads();
   const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+  float ps = 0.f;
+  for (int k = threadIdx.x; k < (int)gridDim.x; k += 256) ps += ppart[(size_t)b * gridDim.x + k];
+  const float psum = block_sum(ps, red);                             // (its barriers also publish a, c, d)
   if (p >= h * w) return;
   const size_t i = (size_t)b * h * w + p;
   const float enmax = __uint_as_float(*enmax_bits);
-  const float wt = ((1.f - en[i] / enmax) + psum[b] / (float)(h * w)) * 0.5f;
+  const float wt = ((1.f - en[i] / enmax) + psum / (float)(h * w)) * 0.5f;
   const float y = l1[i] * wt + l2[i] * (1.f - wt);
   float o = f2b;
 #pragma unroll 8
@@ -245,11 +251,11 @@ extern "C" int ucod_dwconv7_maskdec(const float* x_tokens, const float* dw_tapma
 extern "C" int ucod_window_scatter(const float* windows, const int* coords, const int* win_img, float* out, int n, int B, int H, int W, int ws,
                                    void* stream) {
   if (!out || B <= 0 || H <= 0 || W <= 0 || ws <= 0 || n < 0) return UCOD_EINVAL;
+  if (n > 0 && (!windows || !coords || !win_img)) return UCOD_EINVAL;      // (in front of the memset: a refusal writes nothing)
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * ws * H * ws * W, s);
   if (e != hipSuccess) return (int)e;
   if (n == 0) return UCOD_OK;
-  if (!windows || !coords || !win_img) return UCOD_EINVAL;
   hipLaunchKernelGGL(window_scatter_kernel, dim3(cdiv(H * W, 256), n), dim3(256), 0, s, windows, coords, win_img, out, H, W, ws);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
@@ -259,20 +265,23 @@ extern "C" int ucod_gated_ensemble(const float* l1_up, const float* l2, const fl
                                    float* out, float* weight_out, void* ws, int B, int h, int w, void* stream) {
   if (!l1_up || !l2 || !f0w || !f0b || !f2w || !out || !weight_out || !ws || B <= 0 || h <= 0 || w <= 0) return UCOD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
+  const int nblk = cdiv(h * w, 256);
   float* en = (float*)ws;
-  float* psum = en + (size_t)B * h * w;
-  unsigned* enmax = (unsigned*)(psum + B);
-  float* pm = psum + B + 1;                                       // sigmoid(l1), B*h*w
-  hipError_t e = hipMemsetAsync(psum, 0, sizeof(float) * (B + 1), s);
+  float* ppart = en + (size_t)B * h * w;                          // [B][nblk]: every entry is written by pass 0
+  unsigned* enmax = (unsigned*)(ppart + (size_t)B * nblk);
+  float* pm = ppart + (size_t)B * nblk + 1;                       // sigmoid(l1), B*h*w
+  hipError_t e = hipMemsetAsync(enmax, 0, sizeof(unsigned), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(ge_prob_kernel, dim3(cdiv(h * w, 256), B), dim3(256), 0, s, l1_up, pm, psum, h * w);
-  hipLaunchKernelGGL(ge_stats_kernel, dim3(cdiv(h * w, 256), B), dim3(256), 0, s, pm, en, enmax, h, w);
-  hipLaunchKernelGGL(ge_fuse_kernel, dim3(cdiv(h * w, 256), B), dim3(256), 0, s, l1_up, l2, en, psum, enmax, f0w, f0b, f2w, f2b, out, weight_out, h, w);
+  hipLaunchKernelGGL(ge_prob_kernel, dim3(nblk, B), dim3(256), 0, s, l1_up, pm, ppart, h * w);
+  hipLaunchKernelGGL(ge_stats_kernel, dim3(nblk, B), dim3(256), 0, s, pm, en, enmax, h, w);
+  hipLaunchKernelGGL(ge_fuse_kernel, dim3(nblk, B), dim3(256), 0, s, l1_up, l2, en, ppart, enmax, f0w, f0b, f2w, f2b, out, weight_out, h, w);
   UCOD_CHECK_LAUNCH();
   return UCOD_OK;
 }
 
-extern "C" size_t ucod_gated_ensemble_workspace_bytes(int B, int h, int w) { return ((size_t)2 * B * h * w + B + 1) * sizeof(float); }
+extern "C" size_t ucod_gated_ensemble_workspace_bytes(int B, int h, int w) {
+  return ((size_t)2 * B * h * w + (size_t)B * cdiv((long)h * w, 256) + 1) * sizeof(float);
+}
 
 extern "C" int ucod_window_loss(const float* window_preds, const float* h_targets, const int* win_flat, const float* l_up, int targets_are_logits,
                                 float* part, float* iou_out, float* loss_out, int n, int B, int H, int W, int ws, void* stream) {
